@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """V-GAN training-step benchmark (BASELINE.json metric: train steps/sec, batch=1024, d=784).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One step = one VGAN_no_kl.fit step body (reference src/vgan.py:597-621) at the GLOBAL batch of
@@ -9,12 +9,17 @@ One step = one VGAN_no_kl.fit step body (reference src/vgan.py:597-621) at the G
 -> upper_softmax -> U*X -> 5-bandwidth RBF MMD^2 (+penalty) -> backward -> Adadelta.  N > 1 shards
 the batch rows across ranks (exact data parallel; strong scaling: total work fixed).
 
-Timing: W untimed warm-up steps, then `--repeats` blocks of EXACTLY K steps, each bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced by MAX over ranks; `value` is the MEDIAN block (every block's rate is kept
-in `repeat_steps_per_s`).  Every timed block starts at an epoch boundary and one untimed block of the same K steps runs
-first, so the blocks replay exactly the HIP graphs a fit replays (16 steps per graph launch + one graph for the remainder).
+Timing: the engine's first epoch (bandwidth calibration, graph captures), a clock ramp (`--prewarm-seconds` of steps on a
+throwaway engine of the same workload), W untimed warm-up steps, then ONE block of EXACTLY K steps bracketed by barrier +
+torch.cuda.synchronize() on both sides and reduced by MAX over ranks.  The block starts at an epoch boundary and replays
+exactly the HIP graphs a fit replays (16 steps per graph launch + one graph for the remainder), all captured before it.
+With --full the headline is the MEDIAN of `--repeats` (default 5) such blocks after one untimed block of the same K steps
+(every block's rate is kept in `repeat_steps_per_s`).  The step count before the timed block does not depend on the clock,
+so with the same arguments every run trains on the same inputs: --dump-outputs DIR writes what the last timed step left
+(the generator's parameters, that step's loss and the RBF bandwidth) as DIR/<name>.npy, float32, for output-to-output
+comparison of two builds.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract fields it carries
+Rank 0 prints ONE JSON line with the driver's contract fields.  With --full it also carries
   roofline      the LONGEST MMD kernel of the active precision mode against the MFMA peak of the instruction it issues
                 (durations measured here with HIP events); every other MMD kernel, both modes, under `also`
   fp32_mode     the same workload timed again with the fp32-MFMA kernels (the reference's own arithmetic is fp32)
@@ -62,7 +67,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rehearsal block and median of --repeats blocks, roofline, fp32 mode, the c4 / c5 / "
+                         "alternative-schedule legs, CPU baseline and parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (generator parameters, loss, bandwidth) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; the median block is reported (default 1; with --full 5)")
     ap.add_argument("--prewarm-seconds", type=float, default=0.5,
                     help="untimed steps run right after graph capture so that the GPU clock has ramped (DVFS) before the "
                          "W warm-up steps; a fit runs for minutes, so the ramped state is the representative one")
@@ -70,18 +81,23 @@ def parse():
     ap.add_argument("--path", choices=["nokl", "kl"], default="nokl",
                     help="nokl: the metric's VGAN_no_kl step (default); kl: VGAN.fit's step mix (SURVEY 8a10), an extra "
                          "informational line, one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c4 / c5 / alternative-schedule legs of the default run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and parity leg of a --full run")
+    ap.add_argument("--no-extra", action="store_true", help="skip the c4 / c5 / alternative-schedule legs of a --full run")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--precision", choices=["auto", "fp32", "bf16x3"], default=None,
                     help="MMD contraction mode (default: VGAN_MMD_PRECISION or the engine's 'auto' rule, bf16x3 at this size)")
     ap.add_argument("--front", choices=["auto", "replicated", "sharded"], default=None,
                     help="data-parallel front of the step (trainer.py; default: the engine's size rule)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the CPU baseline (--full)")
     ap.add_argument("--optional-seconds", type=float, default=600.0,
                     help="budget of everything behind the metric's own leg (fp32 mode, c4 / c5 legs, CPU baseline): past it the line "
                          "is printed as it stands and the process ends")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.path != "nokl":
+        ap.error("--dump-outputs writes the outputs of the VGAN_no_kl step (--path nokl)")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def build_engine(rank, world, use_graph, **engine_kw):
@@ -123,6 +139,27 @@ def run_steps(eng, count, start_step):
         t += k
         if not eng.epoch_staged and os.environ.get("VGAN_FEED_DIRECT") != "1":  # the next epoch's table, while the GPU works through these steps (NoKLStepEngine.stage_epoch_batches)
             eng.stage_epoch_batches(epoch_batches(eng.data.shape[0], N_BATCH))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir, rank):
+    """What the last step left for a caller of the step: the generator's parameters (named as in its state_dict), that step's
+    loss (summed over ranks) and the RBF bandwidth, as float32 `out_dir/<name>.npy`.  Every rank takes part (the loss is
+    all-reduced); rank 0 writes, the replicas being identical."""
+    arrays = {f"generator.main.{k // 2}.{'bias' if k % 2 else 'weight'}": eng.fp.view(eng.fp.flat, k) for k in range(len(eng.fp.shapes))}
+    arrays = {name: t.detach().cpu().numpy().astype(np.float32) for name, t in arrays.items()}
+    arrays["loss"] = np.array([eng.step_loss()], dtype=np.float32)
+    arrays["bandwidth"] = eng.bw.cpu().numpy().astype(np.float32)
+    if rank != 0:
+        return
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def time_kernel(fn, iters=30, repeats=5):
@@ -309,20 +346,21 @@ def bench_kl(args):
         res[name] = (time.perf_counter() - t0) / (epochs * nb)
     steps = epochs * nb
     mix = (res["detector_step_frozen_encoder"] + 5.0 * res["generator_phase_step"]) / 6.0
-    # the MMD of this path runs at p = L (exp-bound regime): algorithmic 8 n^2 L flop and 2 n^2 exps per step
-    n, p = N_BATCH, eng.pz
-    gram_ms = time_kernel(lambda: ops.mmd_gram(eng.encZ, eng.sq, n, p, eng.bw, eng.tiles0, False, None, 0, eng.partial))
-    flop = 4.0 * n * n * L
     out = {"metric": f"VGAN.fit steps/sec (batch={N_BATCH}, d={D_FEAT})", "value": 1.0 / mix, "unit": "steps/s", "n_gpus": 1,
            "steps": steps, "ms_per_step": 1e3 * mix, "higher_is_better": True, "dtype": "f32", "data": "synthetic",
            "config": {"workload": WORKLOAD + " [VGAN.fit: 1 detector epoch (encoder frozen) : 5 generator epochs, HIP-graph replay, device-resident feed]",
-                      "step_kinds_ms": {k: 1e3 * v for k, v in res.items()}},
-           "roofline": {"bound": "mfma", "kernel": "mmd_gram_kernel<4,false,1> at p = L", "achieved": flop / (gram_ms * 1e-3) / 1e12,
-                        "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": flop / (gram_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                        "traffic": None, "avg_launch_ms": gram_ms, "algorithmic_flop_per_launch": flop,
-                        "note": "at p = L = d/16 the MMD is bound by its 2 n^2 exponentials and the epilogue, not by the Gram; the "
-                                "step itself is launch-latency bound (see step_kinds_ms)"}}
-    if not args.no_cpu_baseline:
+                      "step_kinds_ms": {k: 1e3 * v for k, v in res.items()}}}
+    if args.full:
+        # the MMD of this path runs at p = L (exp-bound regime): algorithmic 8 n^2 L flop and 2 n^2 exps per step
+        n, p = N_BATCH, eng.pz
+        gram_ms = time_kernel(lambda: ops.mmd_gram(eng.encZ, eng.sq, n, p, eng.bw, eng.tiles0, False, None, 0, eng.partial))
+        flop = 4.0 * n * n * L
+        out["roofline"] = {"bound": "mfma", "kernel": "mmd_gram_kernel<4,false,1> at p = L", "achieved": flop / (gram_ms * 1e-3) / 1e12,
+                           "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": flop / (gram_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+                           "traffic": None, "avg_launch_ms": gram_ms, "algorithmic_flop_per_launch": flop,
+                           "note": "at p = L = d/16 the MMD is bound by its 2 n^2 exponentials and the epilogue, not by the Gram; the "
+                                   "step itself is launch-latency bound (see step_kinds_ms)"}
+    if args.full and not args.no_cpu_baseline:
         from oracle import torch_port as port
         cores = usable_cores()
         torch.set_num_threads(cores)
@@ -435,28 +473,38 @@ def main():
     torch.manual_seed(1234)
     graph_ok = [not args.no_graph and backend == "nccl"]
 
-    def prewarm(e):
-        # every rank must run the SAME number of steps (each one holds a collective and draws the shared shuffles): rank 0
+    def prewarm(**ekw):
+        # The clock ramp runs on a throwaway engine of the same workload: how many steps it takes follows the clock, so it must
+        # not advance the measured engine or the torch RNG that draws the measured engine's shuffles.
+        # Every rank must run the SAME number of steps (each one holds a collective and draws the shared shuffles): rank 0
         # times one epoch and broadcasts how many more to run
-        t0 = time.perf_counter()
-        run_steps(e, EPOCH_BATCHES, 0)
-        torch.cuda.synchronize()
-        more = torch.tensor([max(0, min(2000, int(args.prewarm_seconds / max(time.perf_counter() - t0, 1e-6))))], device="cuda")
-        if dist:
-            dist.broadcast(more, src=0)
-        for it in range(int(more.item())):
-            run_steps(e, EPOCH_BATCHES, (it + 1) * EPOCH_BATCHES)
-        torch.cuda.synchronize()
+        with torch.random.fork_rng(devices=[torch.cuda.current_device()]):
+            e, _, _ = build_engine(rank, world, graph_ok[0], **ekw)
+            t0 = time.perf_counter()
+            run_steps(e, EPOCH_BATCHES, 0)
+            torch.cuda.synchronize()
+            more = torch.tensor([max(0, min(2000, int(args.prewarm_seconds / max(time.perf_counter() - t0, 1e-6))))], device="cuda")
+            if dist:
+                dist.broadcast(more, src=0)
+            for it in range(int(more.item())):
+                run_steps(e, EPOCH_BATCHES, (it + 1) * EPOCH_BATCHES)
+            torch.cuda.synchronize()
 
     def timed_leg(steps, warmup, **ekw):
-        """Build an engine, pre-warm, W warm-up steps, one untimed block of K steps (captures every graph the block replays),
-        then `repeats` blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both sides, MAX over ranks.
+        """Build an engine, run its first epoch (bandwidth calibration, graph captures), ramp the clock (`prewarm`), W warm-up
+        steps, then replay once every graph the timed block replays -- with --full: one untimed block of K steps -- and time
+        `repeats` blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both sides, MAX over ranks.
         Returns (engine, data, params, per-block seconds, mean loss of the timed steps)."""
         def warm():
             e, data, params = build_engine(rank, world, graph_ok[0], **ekw)
-            prewarm(e)
+            run_steps(e, EPOCH_BATCHES, 0)
+            prewarm(**ekw)
             run_steps(e, warmup, 0)
-            run_steps(e, steps, 0)
+            if args.full:
+                run_steps(e, steps, 0)
+            else:  # a block from an epoch start replays graphs of min(K, epoch) steps and of the remainder K % epoch
+                for k in sorted({min(steps, EPOCH_BATCHES), steps % EPOCH_BATCHES} - {0}):
+                    run_steps(e, k, 0)
             torch.cuda.synchronize()
             return e, data, params
         try:
@@ -495,7 +543,7 @@ def main():
                 "repeat_steps_per_s": [steps / b for b in blocks], "min": steps / max(blocks), "max": steps / min(blocks)}
 
     steps, warmup = args.steps, args.warmup
-    if CONFIG in ("c4", "c5"):
+    if CONFIG in ("c4", "c5") and args.full:
         steps, warmup = min(steps, 200), min(warmup, 8)
         args.no_cpu_baseline = args.no_cpu_baseline or CONFIG == "c5"  # N = 16384: ~17 GB and ~15 s per CPU step
     ekw = {}
@@ -505,21 +553,18 @@ def main():
         ekw["front"] = args.front
     eng, data, params, blocks, mean_loss = timed_leg(steps, warmup, **ekw)
     main_rate = rates(blocks, steps)
-    kern = kernel_rooflines(eng)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank)
     main_cfg = {"workload": WORKLOAD, "global_batch": N_BATCH, "features": D_FEAT, "latent": eng.L,
                 "rows_per_gpu": eng.nl, "parallelism": f"dp{world} (row-sharded Gram, {'sharded' if eng.front_sharded else 'replicated'} front)",
                 "hip_graph": bool(graph_ok[0] and eng.use_graph), "mean_loss": mean_loss, "first_timed_step": eng.first_timed_step,
                 "prewarm_s": args.prewarm_seconds, "generator": eng.mode, "chain_association": "flops" if eng.chain_flops else "depth",
                 "mmd_precision": eng.precision, "gram_tile": eng.gram_tile, "timed_blocks": len(blocks)}
-    main_roof = roofline_of(eng, kern, main_rate["value"], world)
+    main_roof = roofline_of(eng, kernel_rooflines(eng), main_rate["value"], world) if args.full else None
     main_bf3, main_precision = eng.bf3, eng.precision
     del eng
     torch.cuda.empty_cache()
 
-    # The one line, as far as the metric's own leg goes.  Everything below is OPTIONAL evidence added to the same line: a leg that
-    # raises is recorded as {"error": ...}, and if the optional legs together overrun --optional-seconds (a collective that never
-    # returns on some rank, say) a watchdog prints the line as it stands and ends the process, so that the metric is never lost
-    # to its side measurements.
     out = {
         "metric": f"V-GAN train steps/sec (batch={N_BATCH}, d={D_FEAT})", "value": main_rate["value"], "unit": "steps/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": main_rate["ms_per_step"],
@@ -527,9 +572,22 @@ def main():
         "dtype": ("f32; MMD contractions of `value`: split-bf16 x3 on the bf16 MFMA with fp32 accumulation (centred operand); "
                   "the same step with the fp32 MFMA is timed in `fp32_mode`") if main_bf3 else "f32", "data": "synthetic",
         "config": main_cfg, "repeat_steps_per_s": main_rate["repeat_steps_per_s"],
-        "timing": f"median of {main_rate['repeats']} blocks of {steps} steps, each bracketed by barrier + synchronize, max over ranks",
-        "roofline": main_roof,
+        "timing": (f"median of {main_rate['repeats']} blocks of {steps} steps, each" if main_rate["repeats"] > 1 else
+                   f"one block of {steps} steps,") + " bracketed by barrier + synchronize, max over ranks",
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    out["roofline"] = main_roof
+
+    # --full: the one line, as far as the metric's own leg goes.  Everything below is OPTIONAL evidence added to the same line: a
+    # leg that raises is recorded as {"error": ...}, and if the optional legs together overrun --optional-seconds (a collective
+    # that never returns on some rank, say) a watchdog prints the line as it stands and ends the process, so that the metric is
+    # never lost to its side measurements.
     import threading
     lock, printed = threading.Lock(), [False]
 

@@ -13,11 +13,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 if [ "$PART" = a ]; then
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/${TAG}_pytest.log 2>&1; rc=$?; tail -3 $O/${TAG}_pytest.log; [ $rc -eq 0 ] || exit 1
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
 cut -c1-300 $O/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/${TAG}_prof $O/${TAG}_pmc_*
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -- python3 $R/bench.py --steps 1000 --warmup 100 --no-cpu-baseline --no-extra > $O/${TAG}_prof.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -- python3 $R/bench.py --full --steps 1000 --warmup 100 --no-cpu-baseline --no-extra > $O/${TAG}_prof.log 2>&1 || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
 rocprofv3 --pmc $c --output-format csv -d $O/${TAG}_pmc_$c -- python3 $R/tools/kbench.py > $O/${TAG}_pmc_$c.log 2>&1 || exit 1
 done
@@ -25,10 +25,10 @@ rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_LDS_BANK_CO
 cd $R
 python3 tools/pmc_traffic.py $O/${TAG}_pmc_FETCH_SIZE $O/${TAG}_pmc_WRITE_SIZE $O/${TAG}_pmc_SQ > /dev/null && cp profiles/traffic.json $O/${TAG}_traffic.json
 cp $(ls $O/${TAG}_prof/*/*kernel_stats.csv | head -1) $O/${TAG}_kernel_stats.csv
-for w in c1 c2 c4 c5; do python bench.py --workload $w > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err; cut -c1-160 $O/${TAG}_bench_$w.json; done
-python bench.py --workload c2 --precision bf16x3 > $O/${TAG}_bench_c2_bf16x3.json 2> $O/${TAG}_bench_c2_bf16x3.err; cut -c1-160 $O/${TAG}_bench_c2_bf16x3.json
-python bench.py --workload c5 --precision fp32 > $O/${TAG}_bench_c5_fp32.json 2> $O/${TAG}_bench_c5_fp32.err; cut -c1-160 $O/${TAG}_bench_c5_fp32.json
-python bench.py --path kl > $O/${TAG}_bench_kl.json 2> $O/${TAG}_bench_kl.err; cut -c1-160 $O/${TAG}_bench_kl.json
+for w in c1 c2 c4 c5; do python bench.py --full --workload $w > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err; cut -c1-160 $O/${TAG}_bench_$w.json; done
+python bench.py --full --workload c2 --precision bf16x3 > $O/${TAG}_bench_c2_bf16x3.json 2> $O/${TAG}_bench_c2_bf16x3.err; cut -c1-160 $O/${TAG}_bench_c2_bf16x3.json
+python bench.py --full --workload c5 --precision fp32 > $O/${TAG}_bench_c5_fp32.json 2> $O/${TAG}_bench_c5_fp32.err; cut -c1-160 $O/${TAG}_bench_c5_fp32.json
+python bench.py --full --path kl > $O/${TAG}_bench_kl.json 2> $O/${TAG}_bench_kl.err; cut -c1-160 $O/${TAG}_bench_kl.json
 else
 bash tools/pmc_c5.sh c5 | tail -1
 bash tools/pmc_c5.sh c4 | tail -1
