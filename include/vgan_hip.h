@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 6
+#define VGAN_ABI_VERSION 7
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -528,6 +528,59 @@ int vgan_rbf_multi_kernel_matrix(const float* Z, int ldz, int m, int p, const fl
                                  vgan_stream_t stream);
 int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out, int rows, int cols,
                   vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Outlier scoring over generated subspaces  (v-gan_amd/outlier.py: SubspaceEnsemble; the use the reference
+ * README gives the learnt subspaces, "ensembling in the Outlier Detection problem", with pyod's KNN / LOF
+ * as the base detectors).  A SUBSPACE TABLE is three device arrays over S subspaces:
+ *   feat      int32, the feature indices of every subspace, concatenated;
+ *   feat_off  int32 [S+1], subspace s holds feat[feat_off[s] .. feat_off[s+1]), d_s of them (d_s >= 1);
+ *   col_off   int64 [S+1], col_off[s] = sum_{t<s} w_t with w_t = round4(d_t): the packed column offsets.
+ * A call covers the subspaces [first, first + count) of the table (a chunk).  The PACKED block of a row set of
+ * n rows holds, for chunk subspace s, the rows [n, w_s] row-major at element n * (col_off[s] - col_off[first]).
+ * Neighbour order everywhere is the strict total order (distance, reference index).
+ * vgan_outlier_pack: the packed block of X [n, d] (ldx): X[i, feat] - center[feat] (center may be NULL: not centred), zero
+ *   padded to w_s; sq (may be NULL) [count, n] receives the squared row norms of the packed values.
+ * vgan_outlier_knn: for every chunk subspace and query row q < nq, the k reference rows nearest in the packed blocks Pq / Pr,
+ *   nbr [count, nq, k] int32 in (engine distance, index) order.  engine VGAN_OUTLIER_ENGINE_EXACT sums (q_f - r_f)^2 on the
+ *   vector ALU (sq_q / sq_r unused); VGAN_OUTLIER_ENGINE_GRAM forms |q|^2 + |r|^2 - 2 q.r with the fp32 MFMA (needs sq_q /
+ *   sq_r; give it centred blocks).  exclude_self != 0: the query set IS the reference set (nq == nr) and row q never lists
+ *   itself (exact duplicates of it stay).  splits J > 1 cuts the reference rows into J slices; slice lists go to the
+ *   workspaces part_d / part_i [count, J, nq, k] and a second launch merges them.  The result is the same for every J.
+ *   1 <= k <= VGAN_OUTLIER_MAX_K, nr >= k (+1 when self is excluded).
+ * vgan_outlier_refine: the k neighbours of nbr re-measured in float64 from the raw rows Xq [nq, d] / Xr [nr, d] over each
+ *   subspace's features, re-sorted by (float32 distance, index): out_idx / out_dist [count, nq, k]; kdist (may be NULL)
+ *   [count, nq] receives the k-th distance.
+ * vgan_outlier_score: from sorted lists (idx, dist) [count, nq, k]:
+ *   VGAN_OUTLIER_KNN_LARGEST / _MEAN / _MEDIAN  score[row, q] = k-th / mean / median distance;
+ *   VGAN_OUTLIER_LRD   lrd_out [count, nq] (float64) = 1 / (mean_o max(kdist_ref[o], dist(q, o)) + 1e-10);
+ *   VGAN_OUTLIER_LOF   score[row, q] = mean_o lrd_ref[o] / lrd(q)  (sklearn's LocalOutlierFactor, positive: larger is
+ *                      more outlying; kdist_ref [count, nr] float32, lrd_ref [count, nr] float64 of the reference rows).
+ *   row = score_row[z] for chunk subspace z (score_row: device int32 [count], may be NULL: row = z); ld_score >= nq.
+ * vgan_outlier_combine: out[i] = sum_s weights[s] * score[s, i] for s = 0 .. S-1 in that order, float64.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_OUTLIER_MAX_K 32
+#define VGAN_OUTLIER_ENGINE_EXACT 0
+#define VGAN_OUTLIER_ENGINE_GRAM 1
+#define VGAN_OUTLIER_KNN_LARGEST 0
+#define VGAN_OUTLIER_KNN_MEAN 1
+#define VGAN_OUTLIER_KNN_MEDIAN 2
+#define VGAN_OUTLIER_LRD 3
+#define VGAN_OUTLIER_LOF 4
+int vgan_outlier_pack(const float* X, int ldx, int n, int d, const float* center, const int32_t* feat,
+                      const int32_t* feat_off, const int64_t* col_off, int first, int count, float* packed, float* sq,
+                      vgan_stream_t stream);
+int vgan_outlier_knn(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
+                     const int32_t* feat_off, const int64_t* col_off, int first, int count, int k, int exclude_self,
+                     int engine, int splits, float* part_d, int32_t* part_i, int32_t* nbr, vgan_stream_t stream);
+int vgan_outlier_refine(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
+                        const int32_t* feat_off, int first, int count, const int32_t* nbr, int k, int32_t* out_idx,
+                        float* out_dist, float* kdist, vgan_stream_t stream);
+int vgan_outlier_score(const int32_t* idx, const float* dist, int nq, int k, int count, int method, const float* kdist_ref,
+                       const double* lrd_ref, int nr, float* score, const int32_t* score_row, int ld_score, double* lrd_out,
+                       vgan_stream_t stream);
+int vgan_outlier_combine(const float* score, int ld, int S, int n, const double* weights, double* out,
+                         vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

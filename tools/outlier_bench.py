@@ -1,0 +1,123 @@
+"""Subspace outlier scoring on one GPU: the fused HIP path (vgan_amd.SubspaceEnsemble, kNN "largest", fit = self-excluded
+scoring of the training set) against a plain-torch GPU baseline (per subspace: torch.cdist + topk over query-row blocks).
+Subspaces come from approx_subspace_dist of a briefly trained VGAN_no_kl, so their sizes are the ones a user gets.
+Prints one JSON line: per configuration the median time of both paths over warm repetitions, the fused path's rate
+against the fp32 peak (2 n^2 sum d_s flops), and whether both paths chose the same k-th distances.
+--sweep adds the engine crossover: exact vs Gram engine on subspaces of a fixed size."""
+import argparse
+import gc
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vgan_amd  # noqa: E402
+
+FP32_PEAK = 157.3e12  # MI355X fp32 vector / MFMA dense peak (MI355X_MICROARCH)
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), [round(t, 5) for t in ts]
+
+
+def baseline(X, subspaces, proba, k, block=4096):
+    n = X.shape[0]
+    out = torch.zeros(n, dtype=torch.float64, device=X.device)
+    for s in range(len(subspaces)):
+        Xs = X[:, torch.as_tensor(np.flatnonzero(subspaces[s]), device=X.device)].contiguous()
+        kth = torch.empty(n, dtype=torch.float32, device=X.device)
+        for q0 in range(0, n, block):
+            D = torch.cdist(Xs[q0:q0 + block], Xs)
+            D[torch.arange(D.shape[0], device=X.device), torch.arange(q0, q0 + D.shape[0], device=X.device)] = float("inf")
+            kth[q0:q0 + block] = torch.topk(D, k, dim=1, largest=False).values[:, k - 1]
+        out += float(proba[s]) * kth.double()
+    return out
+
+
+def subspaces_for(d, n, count, seed):
+    rng = np.random.default_rng(seed)
+    X = rng.normal(size=(n, d)).astype(np.float32)
+    X[:, 1] = X[:, 0] + 0.1 * X[:, 1]
+    model = vgan_amd.VGAN_no_kl(epochs=2, batch_size=min(500, n))
+    model.fit(X[:min(n, 5000)])
+    model.approx_subspace_dist(count)
+    m, p = model.subspaces, model.proba
+    # the model's training engine holds a captured HIP graph: release it here, not at a garbage collection that may fall
+    # inside the next model's capture (destroying a graph is not permitted while a stream captures)
+    del model
+    gc.collect()
+    torch.cuda.synchronize()
+    return X, m, p
+
+
+def run_config(d, n, count, k, reps, with_baseline):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    ens = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=k)
+    t_fused, ts = timed(lambda: ens.fit(Xd), reps)
+    dims = m.sum(axis=1)
+    flops = 2.0 * n * n * float(dims.sum())
+    row = {"d": d, "n": n, "S_sampled": count, "S_distinct": int(len(m)), "k": k,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "gram_subspaces": int(ens.plan.gram.sum()), "fused_s": round(t_fused, 5), "fused_reps_s": ts,
+           "fused_tflops": round(flops / t_fused / 1e12, 2), "fused_frac_fp32_peak": round(flops / t_fused / FP32_PEAK, 4)}
+    if with_baseline:
+        t_base, tb = timed(lambda: baseline(Xd, m, p, k), reps)
+        want = baseline(Xd, m, p, k).cpu().numpy()
+        row.update({"torch_s": round(t_base, 5), "torch_reps_s": tb, "speedup": round(t_base / t_fused, 2),
+                    "max_rel_diff_vs_torch": float(np.max(np.abs(ens.decision_scores_ - want) / np.maximum(np.abs(want), 1e-12)))})
+    return row
+
+
+def sweep(n, reps):
+    rng = np.random.default_rng(0)
+    rows = []
+    for ds in [4, 8, 16, 24, 32, 48, 64, 128]:
+        d = max(ds, 128)
+        X = torch.as_tensor(rng.normal(size=(n, d)).astype(np.float32), device="cuda")
+        m = np.zeros((16, d), bool)
+        for s in range(16):
+            m[s, rng.choice(d, ds, replace=False)] = True
+        row = {"d_s": ds, "n": n, "S": 16, "k": 5}
+        for engine in ["exact", "gram"]:
+            ens = vgan_amd.SubspaceEnsemble(m, np.full(16, 1 / 16), n_neighbors=5, engine=engine)
+            t, _ = timed(lambda: ens.fit(X), reps)
+            row[f"{engine}_s"] = round(t, 5)
+        rows.append(row)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "outlier_bench needs an MI355X"
+    configs = [(10, 10_000, 50, 5, True), (10, 10_000, 50, 20, True), (10, 50_000, 500, 5, True), (10, 50_000, 500, 20, False),
+               (784, 10_000, 50, 5, True), (784, 10_000, 50, 20, False), (784, 50_000, 50, 5, False)]
+    if args.quick:
+        configs = [(10, 2000, 20, 5, True), (784, 2000, 10, 5, True)]
+    out = {"tool": "outlier_bench", "device": torch.cuda.get_device_name(0), "configs": []}
+    for d, n, count, k, with_base in configs:
+        out["configs"].append(run_config(d, n, count, k, args.reps, with_base))
+        print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+    if args.sweep:
+        out["engine_sweep"] = sweep(2000 if args.quick else 10_000, args.reps)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

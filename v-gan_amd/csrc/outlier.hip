@@ -1,0 +1,421 @@
+// Outlier scoring over generated subspaces: kNN distance / LOF per subspace, combined with the subspace probabilities
+// (the use the reference README names for the learnt subspaces: "ensembling in the Outlier Detection problem").
+//
+// Per subspace s (feature list F_s, d_s = |F_s|, w_s = round4(d_s)):
+//   1. pack     gather F_s of every row into a row-major block [n, w_s] (zero pad), optionally centred, with row norms
+//   2. knn      distance + top-k, fused: a workgroup owns 64 query rows and walks the reference rows 64 at a time; the
+//               n_q x n_r distance matrix never exists.  Two distance engines share one selection epilogue:
+//                 exact  sum_f (q_f - r_f)^2 on the VALU (small d_s: no cancellation, duplicates give exactly 0)
+//                 gram   |q|^2 + |r|^2 - 2 q.r with the fp32 MFMA tile of gemm_core.hpp (large d_s, centred operands)
+//               optional split of the reference rows over J workgroups + a merge launch; every comparison is on the
+//               strict total order (d2, index), so the k-list is the same for every J and every chunking.
+//   3. refine   recompute the k selected distances in float64 from the raw rows, re-sort by (distance, index)
+//   4. score    kNN (largest / mean / median of the k distances) or LOF (k_distance, lrd, mean lrd ratio)
+//   5. combine  out[i] = sum_s p_s score_s[i] in float64, subspaces in order
+#include <float.h>
+#include <limits.h>
+
+#include "gemm_core.hpp"
+
+namespace vgan {
+
+constexpr int kOTile = 64;  // query rows per workgroup = reference rows per tile
+constexpr int kOFB = 32;    // features per LDS block of the exact engine
+constexpr int kOLd = kOFB + 4;  // LDS row stride of those blocks (36 / 4 = 9 odd: conflict-free 16-byte reads)
+
+__device__ __forceinline__ bool cand_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
+
+// k best (d2, index) pairs of one thread, ascending; unused slots hold (+inf, INT_MAX)
+template <int K>
+struct TopK {
+    float d[K];
+    int i[K];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int t = 0; t < K; ++t) {
+            d[t] = INFINITY;
+            i[t] = INT_MAX;
+        }
+    }
+    __device__ __forceinline__ void push(float nd, int ni) {
+        if (!cand_less(nd, ni, d[K - 1], i[K - 1])) return;  // prune against the current K-th
+#pragma unroll
+        for (int t = K - 1; t > 0; --t) {
+            const bool up = cand_less(nd, ni, d[t - 1], i[t - 1]);
+            const bool here = cand_less(nd, ni, d[t], i[t]);
+            d[t] = up ? d[t - 1] : (here ? nd : d[t]);
+            i[t] = up ? i[t - 1] : (here ? ni : i[t]);
+        }
+        if (cand_less(nd, ni, d[0], i[0])) {
+            d[0] = nd;
+            i[0] = ni;
+        }
+    }
+};
+
+// LDS of the knn kernel: the engine's images, reused by the final merge of the four waves' lists
+template <int K, bool GRAM>
+struct KnnLds {
+    using G = GemmTile<64, 64, 32, KC, KC, 4>;
+    static constexpr int kEngine = GRAM ? G::kLdsFloats + kOTile * (kOTile + 1) : 2 * kOTile * kOLd;
+    static constexpr int kMerge = 2 * 2 * K * kOTile;  // (d, i) of two waves
+    static constexpr int kFloats = kEngine > kMerge ? kEngine : kMerge;
+};
+
+// Grid (query blocks, J, subspaces).  Lane l of every wave owns query row q0 + l; wave w selects among columns
+// [16w, 16w + 16) of each 64-row reference tile, then the four lists of a row are merged.
+template <int K, bool GRAM>
+__global__ __launch_bounds__(kBlock, 2) void outlier_knn_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
+                                                                const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
+                                                                const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
+                                                                int first, int k, int exclude_self, int splits,
+                                                                float* __restrict__ part_d, int32_t* __restrict__ part_i,
+                                                                int32_t* __restrict__ nbr) {
+    using G = typename KnnLds<K, GRAM>::G;
+    __shared__ __attribute__((aligned(16))) float lds[KnnLds<K, GRAM>::kFloats];
+    const int z = blockIdx.z, s = first + z, slice = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q0 = blockIdx.x * kOTile, q = q0 + lane;
+    const int ds = feat_off[s + 1] - feat_off[s];
+    const int w = (ds + 3) & ~3;
+    const long base = col_off[s] - col_off[first];
+    const float* Q = Pq + base * nq;
+    const float* R = Pr + base * nr;
+    if constexpr (GRAM) {  // norms of chunk subspace z: [count, n]
+        sqq += (long)z * nq;
+        sqr += (long)z * nr;
+    }
+    const int ntiles = (nr + kOTile - 1) / kOTile, per = (ntiles + splits - 1) / splits;
+    const int t_begin = slice * per, t_end = min(ntiles, t_begin + per);
+
+    TopK<K> top;
+    top.init();
+    auto select = [&](const float (&d2)[16], int c0) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = c0 + j;
+            if (c < nr && !(exclude_self && c == q)) top.push(d2[j], c);
+        }
+    };
+
+    if constexpr (GRAM) {
+        float* dist = lds + G::kLdsFloats;  // [64][65]
+        for (int t = t_begin; t < t_end; ++t) {
+            const int r0 = t * kOTile;
+            f32x16 acc[1][1];
+            zero_acc(acc);
+            G::template run<false>(Q, w, R, w, q0, r0, nq, nr, w, lds, nullptr, acc);
+            const int col = G::sub_col(0);
+            const float sc = r0 + col < nr ? sqr[r0 + col] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = G::sub_row(0, r);
+                const float sr = q0 + row < nq ? sqq[q0 + row] : 0.f;
+                dist[row * (kOTile + 1) + col] = fmaxf(sr + sc - 2.f * acc[0][0][r], 0.f);
+            }
+            __syncthreads();
+            float d2[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) d2[j] = dist[lane * (kOTile + 1) + 16 * wave + j];
+            select(d2, r0 + 16 * wave);
+            __syncthreads();
+        }
+    } else {
+        float* sQ = lds;  // [64][kOLd]
+        float* sR = lds + kOTile * kOLd;
+        // 64 rows x 32 features = 512 float4 per operand block: two per thread, zero outside [rows) x [w)
+        auto stage = [&](float* dst, const float* src, int n, int row0, int f0) {
+#pragma unroll
+            for (int v = 0; v < 2; ++v) {
+                const int e = tid + kBlock * v, row = e >> 3, c = f0 + 4 * (e & 7);
+                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row0 + row < n && c < w) x = *reinterpret_cast<const float4*>(src + (long)(row0 + row) * w + c);
+                *reinterpret_cast<float4*>(dst + row * kOLd + 4 * (e & 7)) = x;
+            }
+        };
+        const bool q_resident = w <= kOFB;
+        if (q_resident) stage(sQ, Q, nq, q0, 0);
+        for (int t = t_begin; t < t_end; ++t) {
+            const int r0 = t * kOTile;
+            float d2[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) d2[j] = 0.f;
+            for (int f0 = 0; f0 < w; f0 += kOFB) {
+                __syncthreads();
+                if (!q_resident) stage(sQ, Q, nq, q0, f0);
+                stage(sR, R, nr, r0, f0);
+                __syncthreads();
+                const int nc = min(kOFB, w - f0) >> 2;
+                for (int c = 0; c < nc; ++c) {
+                    const float4 a = *reinterpret_cast<const float4*>(sQ + lane * kOLd + 4 * c);
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const float4 b = *reinterpret_cast<const float4*>(sR + (16 * wave + j) * kOLd + 4 * c);
+                        const float x = a.x - b.x, y = a.y - b.y, u = a.z - b.z, v = a.w - b.w;
+                        d2[j] = fmaf(x, x, fmaf(y, y, fmaf(u, u, fmaf(v, v, d2[j]))));
+                    }
+                }
+            }
+            select(d2, r0 + 16 * wave);
+        }
+    }
+
+    // merge the four waves' lists of each row: waves 2, 3 hand theirs to waves 0, 1, then wave 1 to wave 0
+    __syncthreads();
+    float* md = lds;
+    int* mi = reinterpret_cast<int*>(lds + 2 * K * kOTile);
+    for (int round = 0; round < 2; ++round) {
+        const int hi = round == 0 ? 2 : 1;  // waves [hi, 2 hi) give, waves [0, hi) take
+        if (wave >= hi && wave < 2 * hi) {
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+                md[((wave - hi) * K + t) * kOTile + lane] = top.d[t];
+                mi[((wave - hi) * K + t) * kOTile + lane] = top.i[t];
+            }
+        }
+        __syncthreads();
+        if (wave < hi) {
+#pragma unroll
+            for (int t = 0; t < K; ++t) top.push(md[(wave * K + t) * kOTile + lane], mi[(wave * K + t) * kOTile + lane]);
+        }
+        __syncthreads();
+    }
+    if (wave == 0 && q < nq) {
+        if (splits == 1) {
+            int32_t* o = nbr + ((long)z * nq + q) * k;
+#pragma unroll
+            for (int t = 0; t < K; ++t)
+                if (t < k) o[t] = top.i[t];
+        } else {
+            const long off = (((long)z * splits + slice) * nq + q) * k;
+#pragma unroll
+            for (int t = 0; t < K; ++t)
+                if (t < k) {
+                    part_d[off + t] = top.d[t];
+                    part_i[off + t] = top.i[t];
+                }
+        }
+    }
+}
+
+// the J partial lists of a (subspace, query row) -> its k-list; one thread per row
+template <int K>
+__global__ void outlier_knn_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int nq, int count,
+                                         int k, int splits, int32_t* __restrict__ nbr) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= (long)count * nq) return;
+    const long z = row / nq, q = row % nq;
+    TopK<K> top;
+    top.init();
+    for (int j = 0; j < splits; ++j) {
+        const long off = ((z * splits + j) * nq + q) * k;
+        for (int t = 0; t < k; ++t) top.push(part_d[off + t], part_i[off + t]);
+    }
+    int32_t* o = nbr + row * k;
+#pragma unroll
+    for (int t = 0; t < K; ++t)
+        if (t < k) o[t] = top.i[t];
+}
+
+// packed[n * (col_off[s] - col_off[first]) + i * w_s + c] = X[i, feat[feat_off[s] + c]] - center[...] (0 for c >= d_s);
+// sq[(s - first) * n + i] = its squared norm.  Grid (row blocks of 64, subspaces); one wave per row, lanes over features.
+__global__ void outlier_pack_kernel(const float* __restrict__ X, int ldx, int n, const float* __restrict__ center,
+                                    const int32_t* __restrict__ feat, const int32_t* __restrict__ feat_off,
+                                    const int64_t* __restrict__ col_off, int first, float* __restrict__ packed, float* __restrict__ sq) {
+    const int z = blockIdx.y, s = first + z;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f0 = feat_off[s], ds = feat_off[s + 1] - f0, w = (ds + 3) & ~3;
+    float* P = packed + (col_off[s] - col_off[first]) * n;
+    for (int i = blockIdx.x * kOTile + wave; i < min(n, (blockIdx.x + 1) * kOTile); i += kBlock / kWave) {
+        float acc = 0.f;
+        for (int c = lane; c < w; c += kWave) {
+            float v = 0.f;
+            if (c < ds) {
+                const int f = feat[f0 + c];
+                v = X[(long)i * ldx + f];
+                if (center != nullptr) v -= center[f];
+            }
+            P[(long)i * w + c] = v;
+            acc = fmaf(v, v, acc);
+        }
+        acc = wave_sum(acc);
+        if (sq != nullptr && lane == 0) sq[(long)z * n + i] = acc;
+    }
+}
+
+// One wave per (subspace, query row): lane t < k recomputes |x_q - x_{nbr_t}| over F_s in float64 from the raw rows, then the
+// k values are ranked by (distance as float32, index) and written in that order.  kdist (may be NULL) gets the k-th.
+__global__ void outlier_refine_kernel(const float* __restrict__ Xq, int ldq, int nq, const float* __restrict__ Xr, int ldr, int nr,
+                                      const int32_t* __restrict__ feat, const int32_t* __restrict__ feat_off, int first, int count,
+                                      const int32_t* __restrict__ nbr, int k, int32_t* __restrict__ out_idx,
+                                      float* __restrict__ out_dist, float* __restrict__ kdist) {
+    const long row = (long)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (row >= (long)count * nq) return;
+    const int lane = threadIdx.x & 63;
+    const int z = (int)(row / nq), q = (int)(row % nq), s = first + z;
+    const int f0 = feat_off[s], ds = feat_off[s + 1] - f0;
+    int idx = INT_MAX;
+    float dist = INFINITY;
+    if (lane < k) idx = nbr[row * k + lane];
+    if (idx >= 0 && idx < nr) {
+        const float* xq = Xq + (long)q * ldq;
+        const float* xr = Xr + (long)idx * ldr;
+        double acc = 0.0;
+        for (int c = 0; c < ds; ++c) {
+            const int f = feat[f0 + c];
+            const double e = (double)xq[f] - (double)xr[f];
+            acc = fma(e, e, acc);
+        }
+        dist = (float)sqrt(acc);
+    }
+    int rank = 0;
+    for (int u = 0; u < k; ++u) {
+        const float du = __shfl(dist, u, 64);
+        const int iu = __shfl(idx, u, 64);
+        rank += cand_less(du, iu, dist, idx) ? 1 : 0;
+    }
+    if (lane < k) {
+        out_idx[row * k + rank] = idx;
+        out_dist[row * k + rank] = dist;
+        if (kdist != nullptr && rank == k - 1) kdist[row] = dist;
+    }
+}
+
+// One thread per (subspace, query row) over its sorted list (dist, idx).
+//   method 0/1/2: kNN largest / mean / median -> score
+//   method 3:     lrd(p) = 1 / (mean_o max(kdist_ref(o), d(p, o)) + 1e-10) -> lrd_out
+//   method 4:     LOF(p) = mean_o lrd_ref(o) / lrd(p)                          -> score
+// score row of subspace z: score_row[z] (score_row may be NULL: row z), leading dimension ld_score.
+__global__ void outlier_score_kernel(const int32_t* __restrict__ idx, const float* __restrict__ dist, int nq, int k, int count,
+                                     int method, const float* __restrict__ kdist_ref, const double* __restrict__ lrd_ref, int nr,
+                                     float* __restrict__ score, const int32_t* __restrict__ score_row, int ld_score,
+                                     double* __restrict__ lrd_out) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= (long)count * nq) return;
+    const int z = (int)(row / nq), q = (int)(row % nq);
+    const float* d = dist + row * k;
+    const int32_t* o = idx + row * k;
+    double v;
+    if (method == VGAN_OUTLIER_KNN_LARGEST) {
+        v = d[k - 1];
+    } else if (method == VGAN_OUTLIER_KNN_MEAN) {
+        double a = 0.0;
+        for (int t = 0; t < k; ++t) a += d[t];
+        v = a / k;
+    } else if (method == VGAN_OUTLIER_KNN_MEDIAN) {
+        v = (k & 1) ? (double)d[k / 2] : 0.5 * ((double)d[k / 2 - 1] + (double)d[k / 2]);
+    } else {
+        for (int t = 0; t < k; ++t)
+            if ((unsigned)o[t] >= (unsigned)nr) return;  // not a list of refine: nothing to read
+        const float* kd = kdist_ref + (long)z * nr;
+        double a = 0.0;
+        for (int t = 0; t < k; ++t) a += fmax((double)kd[o[t]], (double)d[t]);
+        const double lrd = 1.0 / (a / k + 1e-10);
+        if (method == VGAN_OUTLIER_LRD) {
+            lrd_out[row] = lrd;
+            return;
+        }
+        const double* lr = lrd_ref + (long)z * nr;
+        double b = 0.0;
+        for (int t = 0; t < k; ++t) b += lr[o[t]] / lrd;
+        v = b / k;
+    }
+    score[(long)(score_row ? score_row[z] : z) * ld_score + q] = (float)v;
+}
+
+// out[i] = sum_s p[s] * score[s, i], float64, s ascending
+__global__ void outlier_combine_kernel(const float* __restrict__ score, int ld, int S, int n, const double* __restrict__ p,
+                                       double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a = 0.0;
+    for (int s = 0; s < S; ++s) a += p[s] * (double)score[(long)s * ld + i];
+    out[i] = a;
+}
+
+template <int K>
+static int launch_knn(const float* Pq, const float* sqq, int nq, const float* Pr, const float* sqr, int nr, const int32_t* feat_off,
+                      const int64_t* col_off, int first, int count, int k, int exclude_self, int engine, int splits, float* part_d,
+                      int32_t* part_i, int32_t* nbr, hipStream_t st) {
+    dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
+    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
+        hipLaunchKernelGGL((outlier_knn_kernel<K, true>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off,
+                           first, k, exclude_self, splits, part_d, part_i, nbr);
+    else
+        hipLaunchKernelGGL((outlier_knn_kernel<K, false>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off,
+                           first, k, exclude_self, splits, part_d, part_i, nbr);
+    VGAN_CHECK_LAUNCH();
+    if (splits > 1) {
+        const long rows = (long)count * nq;
+        hipLaunchKernelGGL(outlier_knn_merge_kernel<K>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, part_d, part_i, nq,
+                           count, k, splits, nbr);
+        VGAN_CHECK_LAUNCH();
+    }
+    return VGAN_OK;
+}
+
+}  // namespace vgan
+
+using namespace vgan;
+
+extern "C" int vgan_outlier_pack(const float* X, int ldx, int n, int d, const float* center, const int32_t* feat,
+                                 const int32_t* feat_off, const int64_t* col_off, int first, int count, float* packed, float* sq,
+                                 vgan_stream_t stream) {
+    VGAN_CHECK_ARG(X && feat && feat_off && col_off && packed && n > 0 && d > 0 && ldx >= d && first >= 0 && count > 0);
+    VGAN_CHECK_ARG(count <= 65535 && aligned16(packed));
+    hipLaunchKernelGGL(outlier_pack_kernel, dim3((n + kOTile - 1) / kOTile, count), dim3(kBlock), 0, (hipStream_t)stream, X, ldx, n,
+                       center, feat, feat_off, col_off, first, packed, sq);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_outlier_knn(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
+                                const int32_t* feat_off, const int64_t* col_off, int first, int count, int k, int exclude_self,
+                                int engine, int splits, float* part_d, int32_t* part_i, int32_t* nbr, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && nbr && nq > 0 && nr > 0 && first >= 0 && count > 0 && count <= 65535);
+    VGAN_CHECK_ARG(k >= 1 && k <= VGAN_OUTLIER_MAX_K);
+    VGAN_CHECK_ARG(nr >= k + (exclude_self ? 1 : 0) && (!exclude_self || nq == nr));
+    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
+    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
+    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && (splits == 1 || (part_d && part_i)));
+    VGAN_CHECK_ARG(aligned16(Pq) && aligned16(Pr));
+    const hipStream_t st = (hipStream_t)stream;
+    if (k <= 8) return launch_knn<8>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
+    if (k <= 16) return launch_knn<16>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
+    return launch_knn<32>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
+}
+
+extern "C" int vgan_outlier_refine(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
+                                   const int32_t* feat_off, int first, int count, const int32_t* nbr, int k, int32_t* out_idx,
+                                   float* out_dist, float* kdist, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Xq && Xr && feat && feat_off && nbr && out_idx && out_dist && nq > 0 && nr > 0 && d > 0);
+    VGAN_CHECK_ARG(ldq >= d && ldr >= d && first >= 0 && count > 0 && k >= 1 && k <= VGAN_OUTLIER_MAX_K && nr >= k);
+    const long rows = (long)count * nq;
+    hipLaunchKernelGGL(outlier_refine_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(kBlock), 0, (hipStream_t)stream, Xq, ldq, nq, Xr, ldr,
+                       nr, feat, feat_off, first, count, nbr, k, out_idx, out_dist, kdist);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_outlier_score(const int32_t* idx, const float* dist, int nq, int k, int count, int method, const float* kdist_ref,
+                                  const double* lrd_ref, int nr, float* score, const int32_t* score_row, int ld_score, double* lrd_out,
+                                  vgan_stream_t stream) {
+    VGAN_CHECK_ARG(idx && dist && nq > 0 && count > 0 && k >= 1 && k <= VGAN_OUTLIER_MAX_K);
+    VGAN_CHECK_ARG(method >= VGAN_OUTLIER_KNN_LARGEST && method <= VGAN_OUTLIER_LOF);
+    VGAN_CHECK_ARG(method < VGAN_OUTLIER_LRD || (kdist_ref && nr >= k));
+    VGAN_CHECK_ARG(method == VGAN_OUTLIER_LRD ? lrd_out != nullptr : (score != nullptr && ld_score >= nq));
+    VGAN_CHECK_ARG(method != VGAN_OUTLIER_LOF || lrd_ref);
+    const long rows = (long)count * nq;
+    hipLaunchKernelGGL(outlier_score_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, dist, nq, k,
+                       count, method, kdist_ref, lrd_ref, nr, score, score_row, ld_score, lrd_out);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_outlier_combine(const float* score, int ld, int S, int n, const double* weights, double* out,
+                                    vgan_stream_t stream) {
+    VGAN_CHECK_ARG(score && weights && out && S > 0 && n > 0 && ld >= n);
+    hipLaunchKernelGGL(outlier_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, score, ld, S, n, weights, out);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}

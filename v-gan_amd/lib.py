@@ -114,9 +114,14 @@ SIGNATURES = {
     "vgan_dp_allgather": (_i, [_p, _p, _i64, _p]),
     "vgan_dp_comm_destroy": (_i, [_p]),
     "vgan_mse": (_i, [_p, _i, _p, _i, _i, _i, _f, _p, _i, _p]),
+    "vgan_outlier_pack": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "vgan_outlier_knn": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "vgan_outlier_refine": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "vgan_outlier_score": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p]),
+    "vgan_outlier_combine": (_i, [_p, _i, _i, _i, _p, _p, _p]),
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 _lib = None
 
 

@@ -594,6 +594,44 @@ class HipOps:
         _lib.check(self.lib.vgan_mse(_ptr(a), a.stride(0), _ptr(b), b.stride(0), n, d, float(scale), _ptr(out),
                                      int(bool(accumulate)), self._stream()), "vgan_mse")
 
+    # ---- outlier scoring over subspaces (vgan_amd.outlier) -------------------------------------------
+    # A subspace table is (feat int32, feat_off int32 [S+1], col_off int64 [S+1]) on the device; calls cover [first, first + count).
+    def outlier_pack(self, X, center, table, first, count, packed, sq=None):
+        _mat(X, "X"), _vec(packed, "packed")
+        feat, feat_off, col_off = table
+        n, d = X.shape
+        _lib.check(self.lib.vgan_outlier_pack(_ptr(X), X.stride(0), n, d, _ptr(center), _ptr(feat), _ptr(feat_off), _ptr(col_off),
+                                              int(first), int(count), _ptr(packed), _ptr(sq), self._stream()), "vgan_outlier_pack")
+
+    def outlier_knn(self, Pq, sq_q, nq, Pr, sq_r, nr, table, first, count, k, exclude_self, engine, splits, nbr,
+                    part_d=None, part_i=None):
+        _vec(nbr, "nbr", torch.int32)
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_outlier_knn(_ptr(Pq), _ptr(sq_q), int(nq), _ptr(Pr), _ptr(sq_r), int(nr), _ptr(feat_off), _ptr(col_off),
+                                             int(first), int(count), int(k), int(bool(exclude_self)), int(engine), int(splits),
+                                             _ptr(part_d), _ptr(part_i), _ptr(nbr), self._stream()), "vgan_outlier_knn")
+
+    def outlier_refine(self, Xq, Xr, table, first, count, nbr, k, out_idx, out_dist, kdist=None):
+        _mat(Xq, "Xq"), _mat(Xr, "Xr"), _vec(out_idx, "out_idx", torch.int32), _vec(out_dist, "out_dist")
+        feat, feat_off, _ = table
+        assert Xq.shape[1] == Xr.shape[1]
+        _lib.check(self.lib.vgan_outlier_refine(_ptr(Xq), Xq.stride(0), Xq.shape[0], _ptr(Xr), Xr.stride(0), Xr.shape[0], Xq.shape[1],
+                                                _ptr(feat), _ptr(feat_off), int(first), int(count), _ptr(nbr), int(k), _ptr(out_idx),
+                                                _ptr(out_dist), _ptr(kdist), self._stream()), "vgan_outlier_refine")
+
+    def outlier_score(self, idx, dist, nq, k, count, method, score=None, score_row=None, kdist_ref=None, lrd_ref=None, nr=0,
+                      lrd_out=None):
+        ld = score.stride(0) if score is not None else nq
+        _lib.check(self.lib.vgan_outlier_score(_ptr(idx), _ptr(dist), int(nq), int(k), int(count), int(method), _ptr(kdist_ref),
+                                               _ptr(lrd_ref), int(nr), _ptr(score), _ptr(score_row), int(ld), _ptr(lrd_out),
+                                               self._stream()), "vgan_outlier_score")
+
+    def outlier_combine(self, score, weights, out):
+        _mat(score, "score"), _vec(weights, "weights", torch.float64), _vec(out, "out", torch.float64)
+        S, n = score.shape
+        _lib.check(self.lib.vgan_outlier_combine(_ptr(score), score.stride(0), S, n, _ptr(weights), _ptr(out), self._stream()),
+                   "vgan_outlier_combine")
+
 
 _default = None
 

@@ -1,0 +1,241 @@
+"""Outlier scoring over generated subspaces: a pyod-style ensemble of kNN / LOF detectors, one per subspace of a model,
+combined with the subspace probabilities (``model.subspaces`` / ``model.proba``).
+
+For subspace s with feature set F_s and weight p_s, dist_s(x, y) = sqrt(sum_{f in F_s} (x_f - y_f)^2) on the raw features.
+Neighbour lists hold the k reference rows nearest in that distance, ordered by (distance, reference index).  ``fit``
+scores the reference set with each row's own index excluded (sklearn's ``kneighbors(X=None)``); ``decision_function``
+excludes nothing.  kNN scores are the k-th ("largest"), mean or median distance; LOF is sklearn's LocalOutlierFactor
+(positive, larger is more outlying).  The ensemble score is sum_s p_s score_s in float64, subspaces in order.
+
+All distance, selection and scoring work runs in libvgan_hip.so (csrc/outlier.hip); this module plans the work on the
+host (feature lists, chunks of subspaces under a workspace limit) and owns the device buffers.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .ops import default_ops
+
+MAX_NEIGHBORS = 32  # VGAN_OUTLIER_MAX_K
+# Subspaces with at least this many features go through the fp32 MFMA Gram engine, smaller ones through the exact
+# difference engine (the two meet at 32 on the MI355X).
+GRAM_MIN_DIMS = 32
+ENGINE_ENV = "VGAN_OUTLIER_ENGINE"  # "exact" / "gram" forces one engine for every subspace
+ENGINES = {"exact": 0, "gram": 1}
+KNN_METHODS = {"largest": 0, "mean": 1, "median": 2}
+_LRD, _LOF = 3, 4
+DEFAULT_WORKSPACE_BYTES = 1 << 30
+_TARGET_BLOCKS = 512  # two workgroups per CU of the 256 on an MI355X
+
+
+def check_neighbors(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_NEIGHBORS:
+        raise ValueError(f"n_neighbors must be an integer between 1 and {MAX_NEIGHBORS}, got {k!r}")
+    return int(k)
+
+
+def check_reference_rows(n_ref, k, exclude_self):
+    need = k + 1 if exclude_self else k
+    if n_ref < need:
+        what = "fit needs at least n_neighbors + 1" if exclude_self else "scoring needs at least n_neighbors"
+        raise ValueError(f"{what} reference rows ({need}), got {n_ref}")
+
+
+def _round4(v):
+    return (np.asarray(v, dtype=np.int64) + 3) // 4 * 4
+
+
+class SubspacePlan:
+    """Host plan of a subspace set: the subspaces in processing order (exact-engine ones first, each group in the given
+    order), their concatenated feature lists, feature offsets and packed column offsets, and chunking."""
+
+    def __init__(self, subspaces, engine="auto", gram_min_dims=GRAM_MIN_DIMS):
+        m = np.asarray(subspaces)
+        if m.ndim == 1:
+            m = m[None, :]
+        if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+            raise ValueError(f"subspaces must be a non-empty [S, d] boolean matrix, got shape {m.shape}")
+        m = m.astype(bool)
+        dims = m.sum(axis=1)
+        if (dims == 0).any():
+            raise ValueError(f"subspace {int(np.flatnonzero(dims == 0)[0])} selects no feature")
+        if engine not in ("auto", "exact", "gram"):
+            raise ValueError(f"engine must be 'auto', 'exact' or 'gram', got {engine!r}")
+        gram = dims >= gram_min_dims if engine == "auto" else np.full(len(dims), engine == "gram")
+        self.order = np.argsort(gram, kind="stable").astype(np.int32)  # processing position -> subspace index
+        self.gram = gram[self.order]
+        self.dims = dims[self.order].astype(np.int64)
+        self.d = m.shape[1]
+        self.feat = np.concatenate([np.flatnonzero(m[s]) for s in self.order]).astype(np.int32)
+        self.feat_off = np.concatenate([[0], np.cumsum(self.dims)]).astype(np.int32)
+        self.col_off = np.concatenate([[0], np.cumsum(_round4(self.dims))]).astype(np.int64)
+
+    @property
+    def count(self):
+        return len(self.order)
+
+    def chunks(self, rows, limit_bytes):
+        """[(first, count, gram)]: consecutive runs of the processing order, one engine each, whose packed blocks of `rows`
+        rows (values and norms, float32) fit in limit_bytes; a subspace that alone exceeds it forms a chunk of its own."""
+        out, first = [], 0
+        widths = _round4(self.dims)
+        while first < self.count:
+            end, used = first, 0
+            while end < self.count and self.gram[end] == self.gram[first]:
+                need = int(rows) * (int(widths[end]) + 1) * 4
+                if end > first and used + need > limit_bytes:
+                    break
+                used += need
+                end += 1
+            out.append((first, end - first, bool(self.gram[first])))
+            first = end
+        return out
+
+
+def _device_matrix(X, d=None):
+    X = torch.as_tensor(np.asarray(X) if not isinstance(X, torch.Tensor) else X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be a 2-d matrix, got shape {tuple(X.shape)}")
+    if d is not None and X.shape[1] != d:
+        raise ValueError(f"X has {X.shape[1]} features, the subspaces {d}")
+    return X.to(device="cuda", dtype=torch.float32).contiguous()
+
+
+class SubspaceEnsemble:
+    """kNN / LOF detector per subspace, probability-weighted mean of the scores (pyod-style: ``fit`` sets
+    ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying).
+
+    engine: "auto" (by subspace size, GRAM_MIN_DIMS), "exact" or "gram"; the environment variable VGAN_OUTLIER_ENGINE
+    overrides "auto".  splits: reference-row split J of the neighbour search (None: chosen to fill the chip).
+    workspace_bytes: limit on the packed subspace blocks of one chunk."""
+
+    def __init__(self, subspaces, proba, method="knn", n_neighbors=5, knn_method="largest", engine="auto", splits=None,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+        if method not in ("knn", "lof"):
+            raise ValueError(f"method must be 'knn' or 'lof', got {method!r}")
+        if knn_method not in KNN_METHODS:
+            raise ValueError(f"knn_method must be one of {sorted(KNN_METHODS)}, got {knn_method!r}")
+        self.n_neighbors = check_neighbors(n_neighbors)
+        if engine == "auto":
+            engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
+        self.plan = SubspacePlan(subspaces, engine=engine)
+        p = np.asarray(proba, dtype=np.float64).reshape(-1)
+        if p.shape[0] != self.plan.count:
+            raise ValueError(f"proba has {p.shape[0]} entries for {self.plan.count} subspaces")
+        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
+            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
+        self.method, self.knn_method, self.engine, self.splits = method, knn_method, engine, splits
+        self.workspace_bytes = int(workspace_bytes)
+        self.proba = p
+        self.ops = default_ops()
+        dev = "cuda"
+        self._table = (torch.as_tensor(self.plan.feat, device=dev), torch.as_tensor(self.plan.feat_off, device=dev),
+                       torch.as_tensor(self.plan.col_off, device=dev))
+        self._rows = torch.as_tensor(self.plan.order, device=dev)
+        self._proba = torch.as_tensor(p, device=dev)
+        self._X = None
+
+    # ---- pipeline --------------------------------------------------------------------------------
+    def _pack(self, X, first, count, gram):
+        n = X.shape[0]
+        cols = int(self.plan.col_off[first + count] - self.plan.col_off[first])
+        packed = torch.empty(n * cols, dtype=torch.float32, device=X.device)
+        sq = torch.empty(count, n, dtype=torch.float32, device=X.device) if gram else None
+        self.ops.outlier_pack(X, self._center if gram else None, self._table, first, count, packed, sq)
+        return packed, sq
+
+    def _splits(self, nq, nr, count):
+        if self.splits is not None:
+            return int(self.splits)
+        blocks = -(-nq // 64) * count
+        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
+
+    def _neighbors(self, Xq, kdist=None):
+        """Yields (first, count, idx, dist) per chunk: the sorted refined lists [count, nq, k] of Xq (None: the reference
+        set, self excluded).  kdist (fit only): [S, n] receives the k-th distances in processing order."""
+        k, Xr = self.n_neighbors, self._X
+        nr = Xr.shape[0]
+        nq = nr if Xq is None else Xq.shape[0]
+        rows = nr if Xq is None else nr + nq
+        for first, count, gram in self.plan.chunks(rows, self.workspace_bytes):
+            Pr, sqr = self._pack(Xr, first, count, gram)
+            Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
+            J = self._splits(nq, nr, count)
+            nbr = torch.empty(count, nq, k, dtype=torch.int32, device=Xr.device)
+            part_d = part_i = None
+            if J > 1:
+                part_d = torch.empty(count * J * nq * k, dtype=torch.float32, device=Xr.device)
+                part_i = torch.empty(count * J * nq * k, dtype=torch.int32, device=Xr.device)
+            self.ops.outlier_knn(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, k, Xq is None, ENGINES["gram" if gram else "exact"],
+                                 J, nbr, part_d, part_i)
+            del Pq, Pr, sqq, sqr, part_d, part_i
+            idx = torch.empty_like(nbr)
+            dist = torch.empty(count, nq, k, dtype=torch.float32, device=Xr.device)
+            self.ops.outlier_refine(Xr if Xq is None else Xq, Xr, self._table, first, count, nbr, k, idx, dist,
+                                    None if kdist is None else kdist[first:first + count])
+            yield first, count, idx, dist
+
+    def _score(self, Xq, fitting):
+        k = self.n_neighbors
+        nq = self._X.shape[0] if Xq is None else Xq.shape[0]
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=self._X.device)
+        for first, count, idx, dist in self._neighbors(Xq, self._kdist if (fitting and self.method == "lof") else None):
+            rows = self._rows[first:first + count]
+            if self.method == "knn":
+                self.ops.outlier_score(idx, dist, nq, k, count, KNN_METHODS[self.knn_method], score=per, score_row=rows)
+                continue
+            kd, lrd = self._kdist[first:first + count], self._lrd[first:first + count]
+            if fitting:
+                self.ops.outlier_score(idx, dist, nq, k, count, _LRD, kdist_ref=kd, nr=nq, lrd_out=lrd)
+            self.ops.outlier_score(idx, dist, nq, k, count, _LOF, score=per, score_row=rows, kdist_ref=kd, lrd_ref=lrd,
+                                   nr=self._X.shape[0])
+        out = torch.empty(nq, dtype=torch.float64, device=self._X.device)
+        self.ops.outlier_combine(per, self._proba, out)
+        return out, per
+
+    # ---- public surface --------------------------------------------------------------------------
+    def fit(self, X, y=None):
+        """Keeps X resident as the reference set and scores it (self excluded): decision_scores_, float64 [n]."""
+        X = _device_matrix(X, self.plan.d)
+        check_reference_rows(X.shape[0], self.n_neighbors, exclude_self=True)
+        self._X = X
+        self._center = torch.empty(X.shape[1], dtype=torch.float32, device=X.device)
+        self.ops.col_mean(X, self._center)
+        n = X.shape[0]
+        if self.method == "lof":
+            self._kdist = torch.empty(self.plan.count, n, dtype=torch.float32, device=X.device)
+            self._lrd = torch.empty(self.plan.count, n, dtype=torch.float64, device=X.device)
+        scores, per = self._score(None, fitting=True)
+        self.decision_scores_ = scores.cpu().numpy()
+        self.per_subspace_scores_ = per.cpu().numpy()
+        return self
+
+    def _require_fit(self):
+        if self._X is None:
+            raise RuntimeError("SubspaceEnsemble is not fitted: call fit(X_train) first")
+
+    def decision_function(self, X, return_per_subspace=False):
+        """Ensemble scores of X against the fitted reference set (nothing excluded), float64 [n]; with
+        return_per_subspace=True also the float32 [S, n] per-subspace scores (subspaces in the given order)."""
+        self._require_fit()
+        X = _device_matrix(X, self.plan.d)
+        check_reference_rows(self._X.shape[0], self.n_neighbors, exclude_self=False)
+        scores, per = self._score(X, fitting=False)
+        if return_per_subspace:
+            return scores.cpu().numpy(), per.cpu().numpy()
+        return scores.cpu().numpy()
+
+    def kneighbors(self, X=None):
+        """(dist float32 [S, n, k], idx int32 [S, n, k]) per subspace: the sorted neighbour lists of X, or of the reference
+        set itself with self excluded (X=None)."""
+        self._require_fit()
+        Xq = None if X is None else _device_matrix(X, self.plan.d)
+        nq = self._X.shape[0] if Xq is None else Xq.shape[0]
+        k = self.n_neighbors
+        D = torch.empty(self.plan.count, nq, k, dtype=torch.float32, device=self._X.device)
+        I = torch.empty(self.plan.count, nq, k, dtype=torch.int32, device=self._X.device)
+        for first, count, idx, dist in self._neighbors(Xq):
+            rows = self._rows[first:first + count].long()
+            D[rows], I[rows] = dist, idx
+        return D.cpu().numpy(), I.cpu().numpy()

@@ -14,6 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
+from .outlier import SubspaceEnsemble
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -168,6 +169,14 @@ class _RunFolder:
             weights = np.append(weights / weights.sum(), 1.0)
         self.subspaces = distinct
         self.proba = weights / weights.sum()
+
+    def outlier_ensemble(self, method="knn", n_neighbors=5, subspace_count=500, X=None, **kw):
+        """A SubspaceEnsemble (vgan_amd.outlier) over this model's subspaces and probabilities: self.subspaces / self.proba
+        if they are set, otherwise approx_subspace_dist(subspace_count) first.  Fitted on X when X is given."""
+        if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
+            self.approx_subspace_dist(subspace_count)
+        ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
+        return ens if X is None else ens.fit(X)
 
     def check_if_myopic(self, x_data, bandwidth=0.01, count=500, n_permutations=1000):
         """src/vgan.py:384-431: two-sample (MMD, permutation) test of P(x) against P(u * x + mean(x) * ~u), once per given
