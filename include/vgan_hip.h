@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 7
+#define VGAN_ABI_VERSION 8
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -531,8 +531,8 @@ int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out,
 
 /* ---------------------------------------------------------------------------------------------
  * Outlier scoring over generated subspaces  (v-gan_amd/outlier.py: SubspaceEnsemble; the use the reference
- * README gives the learnt subspaces, "ensembling in the Outlier Detection problem", with pyod's KNN / LOF
- * as the base detectors).  A SUBSPACE TABLE is three device arrays over S subspaces:
+ * README gives the learnt subspaces, "ensembling in the Outlier Detection problem", with pyod's KNN / LOF /
+ * KDE as the base detectors).  A SUBSPACE TABLE is three device arrays over S subspaces:
  *   feat      int32, the feature indices of every subspace, concatenated;
  *   feat_off  int32 [S+1], subspace s holds feat[feat_off[s] .. feat_off[s+1]), d_s of them (d_s >= 1);
  *   col_off   int64 [S+1], col_off[s] = sum_{t<s} w_t with w_t = round4(d_t): the packed column offsets.
@@ -557,6 +557,16 @@ int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out,
  *   VGAN_OUTLIER_LOF   score[row, q] = mean_o lrd_ref[o] / lrd(q)  (sklearn's LocalOutlierFactor, positive: larger is
  *                      more outlying; kdist_ref [count, nr] float32, lrd_ref [count, nr] float64 of the reference rows).
  *   row = score_row[z] for chunk subspace z (score_row: device int32 [count], may be NULL: row = z); ld_score >= nq.
+ * vgan_outlier_kde: Gaussian kernel density of every query row q < nq among the reference rows in each chunk subspace,
+ *   score[row, q] = -log p_s(q) (float32; row and ld_score as for vgan_outlier_score), with p_s from the packed blocks
+ *   Pq / Pr and the engines of vgan_outlier_knn (same sq_q / sq_r rules):
+ *     log p_s(q) = logsumexp_r(-d2(q, r) / (2 h_s^2)) - log N - d_s log h_s - d_s / 2 log(2 pi).
+ *   bandwidth: device float64 [S], h_s by table position (processing order), finite and > 0.  exclude_self != 0: the
+ *   query set IS the reference set (nq == nr >= 2), row q's own index is left out and N = nr - 1 (exact duplicates of it
+ *   stay); otherwise N = nr.  Workspaces pivot uint32 [count, nq] and acc uint64 [count, nq] are initialised by the call.
+ *   Three sweeps: the per-row minimum d2 (pivot), sum_r exp2(c_s (pivot - d2)) in uint64 fixed point at 2^-40 (every term
+ *   <= 1, so nothing underflows to -inf; integer atomics, so the result is the same for every J), the float64 score.
+ *   nr <= VGAN_OUTLIER_KDE_MAX_ROWS keeps the fixed-point sum below 2^63.
  * vgan_outlier_combine: out[i] = sum_s weights[s] * score[s, i] for s = 0 .. S-1 in that order, float64.
  * ------------------------------------------------------------------------------------------- */
 #define VGAN_OUTLIER_MAX_K 32
@@ -567,6 +577,7 @@ int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out,
 #define VGAN_OUTLIER_KNN_MEDIAN 2
 #define VGAN_OUTLIER_LRD 3
 #define VGAN_OUTLIER_LOF 4
+#define VGAN_OUTLIER_KDE_MAX_ROWS 8388607 /* 2^23 - 1 */
 int vgan_outlier_pack(const float* X, int ldx, int n, int d, const float* center, const int32_t* feat,
                       const int32_t* feat_off, const int64_t* col_off, int first, int count, float* packed, float* sq,
                       vgan_stream_t stream);
@@ -579,6 +590,10 @@ int vgan_outlier_refine(const float* Xq, int ldq, int nq, const float* Xr, int l
 int vgan_outlier_score(const int32_t* idx, const float* dist, int nq, int k, int count, int method, const float* kdist_ref,
                        const double* lrd_ref, int nr, float* score, const int32_t* score_row, int ld_score, double* lrd_out,
                        vgan_stream_t stream);
+int vgan_outlier_kde(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
+                     const int32_t* feat_off, const int64_t* col_off, int first, int count, const double* bandwidth,
+                     int exclude_self, int engine, int splits, uint32_t* pivot, uint64_t* acc, float* score,
+                     const int32_t* score_row, int ld_score, vgan_stream_t stream);
 int vgan_outlier_combine(const float* score, int ld, int S, int n, const double* weights, double* out,
                          vgan_stream_t stream);
 

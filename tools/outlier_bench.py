@@ -1,9 +1,12 @@
-"""Subspace outlier scoring on one GPU: the fused HIP path (vgan_amd.SubspaceEnsemble, kNN "largest", fit = self-excluded
-scoring of the training set) against a plain-torch GPU baseline (per subspace: torch.cdist + topk over query-row blocks).
+"""Subspace outlier scoring on one GPU: the fused HIP path (vgan_amd.SubspaceEnsemble, fit = self-excluded scoring of the
+training set) against a plain-torch GPU baseline over 4096-row query blocks, per subspace:
+  --method knn (default): kNN "largest"; baseline torch.cdist + topk.
+  --method kde: Gaussian KDE (--bandwidth, default 1.0); baseline torch.cdist + torch.logsumexp.
 Subspaces come from approx_subspace_dist of a briefly trained VGAN_no_kl, so their sizes are the ones a user gets.
 Prints one JSON line: per configuration the median time of both paths over warm repetitions, the fused path's rate
-against the fp32 peak (2 n^2 sum d_s flops), and whether both paths chose the same k-th distances.
---sweep adds the engine crossover: exact vs Gram engine on subspaces of a fixed size."""
+against the fp32 peak (2 n^2 sum d_s flops per distance sweep: one for kNN, two for KDE), and the largest relative
+difference of the two paths' ensemble scores.
+--sweep adds the engine crossover: exact vs Gram engine on subspaces of a fixed size (kNN)."""
 import argparse
 import gc
 import json
@@ -46,6 +49,22 @@ def baseline(X, subspaces, proba, k, block=4096):
     return out
 
 
+def baseline_kde(X, subspaces, proba, bandwidths, block=4096):
+    n = X.shape[0]
+    out = torch.zeros(n, dtype=torch.float64, device=X.device)
+    for s in range(len(subspaces)):
+        Xs = X[:, torch.as_tensor(np.flatnonzero(subspaces[s]), device=X.device)].contiguous()
+        ds, h = Xs.shape[1], float(bandwidths[s])
+        score = torch.empty(n, dtype=torch.float32, device=X.device)
+        for q0 in range(0, n, block):
+            D = torch.cdist(Xs[q0:q0 + block], Xs)
+            L = D * D * (-0.5 / (h * h))
+            L[torch.arange(L.shape[0], device=X.device), torch.arange(q0, q0 + L.shape[0], device=X.device)] = float("-inf")
+            score[q0:q0 + block] = -(torch.logsumexp(L, dim=1) - np.log(n - 1) - ds * np.log(h) - 0.5 * ds * np.log(2 * np.pi))
+        out += float(proba[s]) * score.double()
+    return out
+
+
 def subspaces_for(d, n, count, seed):
     rng = np.random.default_rng(seed)
     X = rng.normal(size=(n, d)).astype(np.float32)
@@ -62,20 +81,28 @@ def subspaces_for(d, n, count, seed):
     return X, m, p
 
 
-def run_config(d, n, count, k, reps, with_baseline):
+def run_config(d, n, count, k, reps, with_baseline, method="knn", bandwidth=1.0):
     X, m, p = subspaces_for(d, n, count, seed=d + n + count)
     Xd = torch.as_tensor(X, device="cuda")
-    ens = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=k)
+    if method == "kde":
+        ens = vgan_amd.SubspaceEnsemble(m, p, method="kde", bandwidth=bandwidth)
+    else:
+        ens = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=k)
     t_fused, ts = timed(lambda: ens.fit(Xd), reps)
     dims = m.sum(axis=1)
-    flops = 2.0 * n * n * float(dims.sum())
-    row = {"d": d, "n": n, "S_sampled": count, "S_distinct": int(len(m)), "k": k,
+    flops = (2 if method == "kde" else 1) * 2.0 * n * n * float(dims.sum())
+    row = {"method": method, "d": d, "n": n, "S_sampled": count, "S_distinct": int(len(m)),
+           **({"bandwidth": bandwidth} if method == "kde" else {"k": k}),
            "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
            "gram_subspaces": int(ens.plan.gram.sum()), "fused_s": round(t_fused, 5), "fused_reps_s": ts,
            "fused_tflops": round(flops / t_fused / 1e12, 2), "fused_frac_fp32_peak": round(flops / t_fused / FP32_PEAK, 4)}
     if with_baseline:
-        t_base, tb = timed(lambda: baseline(Xd, m, p, k), reps)
-        want = baseline(Xd, m, p, k).cpu().numpy()
+        if method == "kde":
+            base = lambda: baseline_kde(Xd, m, p, ens.bandwidth_)  # noqa: E731
+        else:
+            base = lambda: baseline(Xd, m, p, k)  # noqa: E731
+        t_base, tb = timed(base, reps)
+        want = base().cpu().numpy()
         row.update({"torch_s": round(t_base, 5), "torch_reps_s": tb, "speedup": round(t_base / t_fused, 2),
                     "max_rel_diff_vs_torch": float(np.max(np.abs(ens.decision_scores_ - want) / np.maximum(np.abs(want), 1e-12)))})
     return row
@@ -104,15 +131,20 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
+    ap.add_argument("--method", choices=["knn", "kde"], default="knn")
+    ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     args = ap.parse_args()
+    bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
     assert torch.cuda.is_available(), "outlier_bench needs an MI355X"
     configs = [(10, 10_000, 50, 5, True), (10, 10_000, 50, 20, True), (10, 50_000, 500, 5, True), (10, 50_000, 500, 20, False),
                (784, 10_000, 50, 5, True), (784, 10_000, 50, 20, False), (784, 50_000, 50, 5, False)]
+    if args.method == "kde":
+        configs = [(10, 10_000, 50, 0, True), (10, 50_000, 500, 0, True), (784, 10_000, 50, 0, True)]
     if args.quick:
         configs = [(10, 2000, 20, 5, True), (784, 2000, 10, 5, True)]
     out = {"tool": "outlier_bench", "device": torch.cuda.get_device_name(0), "configs": []}
     for d, n, count, k, with_base in configs:
-        out["configs"].append(run_config(d, n, count, k, args.reps, with_base))
+        out["configs"].append(run_config(d, n, count, k, args.reps, with_base, args.method, bandwidth))
         print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
     if args.sweep:
         out["engine_sweep"] = sweep(2000 if args.quick else 10_000, args.reps)

@@ -1,17 +1,20 @@
-// Outlier scoring over generated subspaces: kNN distance / LOF per subspace, combined with the subspace probabilities
-// (the use the reference README names for the learnt subspaces: "ensembling in the Outlier Detection problem").
+// Outlier scoring over generated subspaces: kNN distance / LOF / Gaussian KDE per subspace, combined with the subspace
+// probabilities (the use the reference README names for the learnt subspaces: "ensembling in the Outlier Detection problem").
 //
 // Per subspace s (feature list F_s, d_s = |F_s|, w_s = round4(d_s)):
 //   1. pack     gather F_s of every row into a row-major block [n, w_s] (zero pad), optionally centred, with row norms
-//   2. knn      distance + top-k, fused: a workgroup owns 64 query rows and walks the reference rows 64 at a time; the
-//               n_q x n_r distance matrix never exists.  Two distance engines share one selection epilogue:
+//   2. distance a workgroup owns 64 query rows and walks the reference rows 64 at a time (outlier_distances); the
+//               n_q x n_r distance matrix never exists.  Two distance engines feed every consumer:
 //                 exact  sum_f (q_f - r_f)^2 on the VALU (small d_s: no cancellation, duplicates give exactly 0)
 //                 gram   |q|^2 + |r|^2 - 2 q.r with the fp32 MFMA tile of gemm_core.hpp (large d_s, centred operands)
-//               optional split of the reference rows over J workgroups + a merge launch; every comparison is on the
-//               strict total order (d2, index), so the k-list is the same for every J and every chunking.
-//   3. refine   recompute the k selected distances in float64 from the raw rows, re-sort by (distance, index)
-//   4. score    kNN (largest / mean / median of the k distances) or LOF (k_distance, lrd, mean lrd ratio)
-//   5. combine  out[i] = sum_s p_s score_s[i] in float64, subspaces in order
+//               optional split of the reference rows over J workgroups.  Consumers:
+//                 knn    top-k on the strict total order (d2, index) + a merge launch: the same k-list for every J and
+//                        every chunking; then
+//                        refine  recompute the k selected distances in float64 from the raw rows, re-sort by (distance, index)
+//                        score   kNN (largest / mean / median of the k distances) or LOF (k_distance, lrd, mean lrd ratio)
+//                 kde    pivot sweep (min d2), sum sweep (exp2 terms against the pivot, uint64 fixed point: the same sum
+//                        for every J), score (Gaussian -log density in float64)
+//   3. combine  out[i] = sum_s p_s score_s[i] in float64, subspaces in order
 #include <float.h>
 #include <limits.h>
 
@@ -53,29 +56,36 @@ struct TopK {
     }
 };
 
+// LDS of the distance producer's engine: the Gram tile's operand images and a 64 x 65 d2 tile, or the exact engine's
+// two 64-row x 32-feature operand blocks
+template <bool GRAM>
+struct DistLds {
+    using G = GemmTile<64, 64, 32, KC, KC, 4>;
+    static constexpr int kFloats = GRAM ? G::kLdsFloats + kOTile * (kOTile + 1) : 2 * kOTile * kOLd;
+};
+
 // LDS of the knn kernel: the engine's images, reused by the final merge of the four waves' lists
 template <int K, bool GRAM>
 struct KnnLds {
-    using G = GemmTile<64, 64, 32, KC, KC, 4>;
-    static constexpr int kEngine = GRAM ? G::kLdsFloats + kOTile * (kOTile + 1) : 2 * kOTile * kOLd;
+    static constexpr int kEngine = DistLds<GRAM>::kFloats;
     static constexpr int kMerge = 2 * 2 * K * kOTile;  // (d, i) of two waves
     static constexpr int kFloats = kEngine > kMerge ? kEngine : kMerge;
 };
 
-// Grid (query blocks, J, subspaces).  Lane l of every wave owns query row q0 + l; wave w selects among columns
-// [16w, 16w + 16) of each 64-row reference tile, then the four lists of a row are merged.
-template <int K, bool GRAM>
-__global__ __launch_bounds__(kBlock, 2) void outlier_knn_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
-                                                                const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
-                                                                const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
-                                                                int first, int k, int exclude_self, int splits,
-                                                                float* __restrict__ part_d, int32_t* __restrict__ part_i,
-                                                                int32_t* __restrict__ nbr) {
-    using G = typename KnnLds<K, GRAM>::G;
-    __shared__ __attribute__((aligned(16))) float lds[KnnLds<K, GRAM>::kFloats];
+// The distance producer shared by the knn and kde kernels.  Grid (query blocks, J, chunk subspaces): the workgroup owns
+// query rows [q0, q0 + 64) of chunk subspace blockIdx.z and slice blockIdx.y of its 64-row reference tiles.  For every
+// tile at r0, lane l of wave w calls consume(d2, c0) with c0 = r0 + 16 w and d2[j] = d^2(q0 + l, c0 + j), j < 16; columns
+// c0 + j >= nr (and rows q0 + l >= nq) hold values the consumer must skip.  A pair's d2 does not depend on the tile,
+// slice or chunk that computes it.  lds: DistLds<GRAM>::kFloats floats, free again after the call.
+template <bool GRAM, class Consume>
+__device__ __forceinline__ void outlier_distances(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
+                                                  const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
+                                                  const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
+                                                  int first, int splits, float* lds, Consume&& consume) {
+    using G = typename DistLds<GRAM>::G;
     const int z = blockIdx.z, s = first + z, slice = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q0 = blockIdx.x * kOTile, q = q0 + lane;
+    const int q0 = blockIdx.x * kOTile;
     const int ds = feat_off[s + 1] - feat_off[s];
     const int w = (ds + 3) & ~3;
     const long base = col_off[s] - col_off[first];
@@ -87,16 +97,6 @@ __global__ __launch_bounds__(kBlock, 2) void outlier_knn_kernel(const float* __r
     }
     const int ntiles = (nr + kOTile - 1) / kOTile, per = (ntiles + splits - 1) / splits;
     const int t_begin = slice * per, t_end = min(ntiles, t_begin + per);
-
-    TopK<K> top;
-    top.init();
-    auto select = [&](const float (&d2)[16], int c0) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = c0 + j;
-            if (c < nr && !(exclude_self && c == q)) top.push(d2[j], c);
-        }
-    };
 
     if constexpr (GRAM) {
         float* dist = lds + G::kLdsFloats;  // [64][65]
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kBlock, 2) void outlier_knn_kernel(const float* __r
             float d2[16];
 #pragma unroll
             for (int j = 0; j < 16; ++j) d2[j] = dist[lane * (kOTile + 1) + 16 * wave + j];
-            select(d2, r0 + 16 * wave);
+            consume(d2, r0 + 16 * wave);
             __syncthreads();
         }
     } else {
@@ -156,9 +156,34 @@ __global__ __launch_bounds__(kBlock, 2) void outlier_knn_kernel(const float* __r
                     }
                 }
             }
-            select(d2, r0 + 16 * wave);
+            consume(d2, r0 + 16 * wave);
         }
     }
+}
+
+// kNN selection over the distance producer.  Lane l of every wave owns query row q0 + l; wave w selects among columns
+// [16w, 16w + 16) of each 64-row reference tile, then the four lists of a row are merged.
+template <int K, bool GRAM>
+__global__ __launch_bounds__(kBlock, 2) void outlier_knn_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
+                                                                const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
+                                                                const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
+                                                                int first, int k, int exclude_self, int splits,
+                                                                float* __restrict__ part_d, int32_t* __restrict__ part_i,
+                                                                int32_t* __restrict__ nbr) {
+    __shared__ __attribute__((aligned(16))) float lds[KnnLds<K, GRAM>::kFloats];
+    const int z = blockIdx.z, slice = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x * kOTile + lane;
+
+    TopK<K> top;
+    top.init();
+    outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = c0 + j;
+            if (c < nr && !(exclude_self && c == q)) top.push(d2[j], c);
+        }
+    });
 
     // merge the four waves' lists of each row: waves 2, 3 hand theirs to waves 0, 1, then wave 1 to wave 0
     __syncthreads();
@@ -215,6 +240,90 @@ __global__ void outlier_knn_merge_kernel(const float* __restrict__ part_d, const
 #pragma unroll
     for (int t = 0; t < K; ++t)
         if (t < k) o[t] = top.i[t];
+}
+
+// c_s = log2(e) / (2 h^2) in float32, finite (a kernel term is exp2f(c_s (m_q - d2)) = exp(-(d2 - m_q) / (2 h^2)));
+// the sum sweep and the score take the same value, so the score is exact for the bandwidth c_s stands for
+__device__ __forceinline__ float kde_coef(double h) { return fminf((float)(1.4426950408889634 / (2.0 * h * h)), FLT_MAX); }
+
+// pivot[row] = +inf bits, acc[row] = 0 for the count * nq rows of a kde call
+__global__ void outlier_kde_init_kernel(unsigned* __restrict__ pivot, unsigned long long* __restrict__ acc, long rows) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    pivot[row] = 0x7f800000u;
+    acc[row] = 0ull;
+}
+
+// The two Gaussian-KDE sweeps over the distance producer; a row is (chunk subspace z, query q), at z * nq + q.
+//   PIVOT  m_q = min of d2 over the summed reference rows -> atomicMin into pivot (float bits as unsigned: d2 >= 0, so
+//          the bit order is the value order; -0 is mapped to +0).  Min is exact: the same m_q for every J.
+//   !PIVOT sum_r exp2f(c_s (m_q - d2)): every term <= 1 and the nearest row gives exactly 1.  A lane sums its 16 columns of
+//          a tile in float32 in fixed order and adds the partial, rounded at 2^-40, to a uint64 fixed-point accumulator;
+//          the waves merge exactly through LDS and atomicAdd into acc.  Integer sums are associative: the same acc for
+//          every J.  Terms <= 1 and nr < 2^23 keep acc below 2^63.
+// One atomic per (slice, row), from wave 0, whose 64 lanes hold 64 consecutive rows.
+template <bool GRAM, bool PIVOT>
+__global__ __launch_bounds__(kBlock, 2) void outlier_kde_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
+                                                                const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
+                                                                const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
+                                                                int first, int exclude_self, int splits, const double* __restrict__ bandwidth,
+                                                                unsigned* __restrict__ pivot, unsigned long long* __restrict__ acc) {
+    static_assert(DistLds<GRAM>::kFloats >= 2 * kBlock, "merge scratch");
+    __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
+    const int z = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x * kOTile + lane;
+    const long row = (long)z * nq + q;
+    if constexpr (PIVOT) {
+        float m = INFINITY;
+        outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int c = c0 + j;
+                if (c < nr && !(exclude_self && c == q)) m = fminf(m, d2[j]);
+            }
+        });
+        __syncthreads();
+        lds[tid] = m;
+        __syncthreads();
+        if (wave == 0 && q < nq) {
+            m = fminf(fminf(lds[lane], lds[kWave + lane]), fminf(lds[2 * kWave + lane], lds[3 * kWave + lane]));
+            atomicMin(pivot + row, __float_as_uint(m) & 0x7fffffffu);
+        }
+    } else {
+        const float c_s = kde_coef(bandwidth[first + z]);
+        const float m = q < nq ? __uint_as_float(pivot[row]) : 0.f;
+        unsigned long long a = 0;
+        outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
+            float t = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int c = c0 + j;
+                if (c < nr && !(exclude_self && c == q)) t += exp2f(c_s * (m - d2[j]));
+            }
+            a += (unsigned long long)rintf(t * 0x1p40f);
+        });
+        __syncthreads();
+        unsigned long long* la = reinterpret_cast<unsigned long long*>(lds);
+        la[tid] = a;
+        __syncthreads();
+        if (wave == 0 && q < nq) atomicAdd(acc + row, la[lane] + la[kWave + lane] + la[2 * kWave + lane] + la[3 * kWave + lane]);
+    }
+}
+
+// score[score_row[z], q] = -log p_s(q) = -(ln(acc 2^-40) - c_s m_q ln 2 - ln n_sum - d_s ln h - d_s / 2 ln 2 pi), float64;
+// one thread per row
+__global__ void outlier_kde_score_kernel(const unsigned* __restrict__ pivot, const unsigned long long* __restrict__ acc, int nq,
+                                         int count, const int32_t* __restrict__ feat_off, int first, const double* __restrict__ bandwidth,
+                                         int n_sum, float* __restrict__ score, const int32_t* __restrict__ score_row, int ld_score) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= (long)count * nq) return;
+    const int z = (int)(row / nq), q = (int)(row % nq), s = first + z;
+    const int ds = feat_off[s + 1] - feat_off[s];
+    const double h = bandwidth[s];
+    const double m = __uint_as_float(pivot[row]);
+    const double lp = log((double)acc[row] * 0x1p-40) - (double)kde_coef(h) * m * 0.6931471805599453 - log((double)n_sum) -
+                      ds * log(h) - 0.5 * ds * 1.8378770664093453;  // ln(2 pi)
+    score[(long)(score_row ? score_row[z] : z) * ld_score + q] = (float)(-lp);
 }
 
 // packed[n * (col_off[s] - col_off[first]) + i * w_s + c] = X[i, feat[feat_off[s] + c]] - center[...] (0 for c >= d_s);
@@ -354,6 +463,18 @@ static int launch_knn(const float* Pq, const float* sqq, int nq, const float* Pr
     return VGAN_OK;
 }
 
+// the pivot and sum sweeps of a kde call
+template <bool GRAM>
+static void launch_kde(const float* Pq, const float* sqq, int nq, const float* Pr, const float* sqr, int nr, const int32_t* feat_off,
+                       const int64_t* col_off, int first, int count, int exclude_self, int splits, const double* bandwidth,
+                       unsigned* pivot, unsigned long long* acc, hipStream_t st) {
+    const dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
+    hipLaunchKernelGGL((outlier_kde_kernel<GRAM, true>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first,
+                       exclude_self, splits, bandwidth, pivot, acc);
+    hipLaunchKernelGGL((outlier_kde_kernel<GRAM, false>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first,
+                       exclude_self, splits, bandwidth, pivot, acc);
+}
+
 }  // namespace vgan
 
 using namespace vgan;
@@ -383,6 +504,33 @@ extern "C" int vgan_outlier_knn(const float* Pq, const float* sq_q, int nq, cons
     if (k <= 8) return launch_knn<8>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
     if (k <= 16) return launch_knn<16>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
     return launch_knn<32>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
+}
+
+extern "C" int vgan_outlier_kde(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
+                                const int32_t* feat_off, const int64_t* col_off, int first, int count, const double* bandwidth,
+                                int exclude_self, int engine, int splits, uint32_t* pivot, uint64_t* acc, float* score,
+                                const int32_t* score_row, int ld_score, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && bandwidth && pivot && acc && score && nq > 0 && nr > 0 && first >= 0);
+    VGAN_CHECK_ARG(count > 0 && count <= 65535 && ld_score >= nq && nr <= VGAN_OUTLIER_KDE_MAX_ROWS);
+    VGAN_CHECK_ARG(!exclude_self || (nq == nr && nr >= 2));
+    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
+    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
+    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(Pq) && aligned16(Pr));
+    const hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)count * nq;
+    unsigned* piv = reinterpret_cast<unsigned*>(pivot);
+    unsigned long long* sum = reinterpret_cast<unsigned long long*>(acc);
+    hipLaunchKernelGGL(outlier_kde_init_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, piv, sum, rows);
+    VGAN_CHECK_LAUNCH();
+    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
+        launch_kde<true>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, exclude_self, splits, bandwidth, piv, sum, st);
+    else
+        launch_kde<false>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, exclude_self, splits, bandwidth, piv, sum, st);
+    VGAN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(outlier_kde_score_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, piv, sum, nq, count, feat_off,
+                       first, bandwidth, exclude_self ? nr - 1 : nr, score, score_row, ld_score);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
 }
 
 extern "C" int vgan_outlier_refine(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,

@@ -118,10 +118,11 @@ SIGNATURES = {
     "vgan_outlier_knn": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "vgan_outlier_refine": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
     "vgan_outlier_score": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p]),
+    "vgan_outlier_kde": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "vgan_outlier_combine": (_i, [_p, _i, _i, _i, _p, _p, _p]),
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _lib = None
 
 

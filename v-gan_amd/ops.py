@@ -626,6 +626,17 @@ class HipOps:
                                                _ptr(lrd_ref), int(nr), _ptr(score), _ptr(score_row), int(ld), _ptr(lrd_out),
                                                self._stream()), "vgan_outlier_score")
 
+    def outlier_kde(self, Pq, sq_q, nq, Pr, sq_r, nr, table, first, count, bandwidth, exclude_self, engine, splits, pivot, acc,
+                    score, score_row=None):
+        _vec(bandwidth, "bandwidth", torch.float64), _vec(pivot, "pivot", torch.int32), _vec(acc, "acc", torch.int64)
+        _mat(score, "score")
+        assert pivot.numel() >= count * nq and acc.numel() >= count * nq
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_outlier_kde(_ptr(Pq), _ptr(sq_q), int(nq), _ptr(Pr), _ptr(sq_r), int(nr), _ptr(feat_off), _ptr(col_off),
+                                             int(first), int(count), _ptr(bandwidth), int(bool(exclude_self)), int(engine), int(splits),
+                                             _ptr(pivot), _ptr(acc), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
+                   "vgan_outlier_kde")
+
     def outlier_combine(self, score, weights, out):
         _mat(score, "score"), _vec(weights, "weights", torch.float64), _vec(out, "out", torch.float64)
         S, n = score.shape

@@ -1,11 +1,17 @@
-"""Outlier scoring over generated subspaces: a pyod-style ensemble of kNN / LOF detectors, one per subspace of a model,
-combined with the subspace probabilities (``model.subspaces`` / ``model.proba``).
+"""Outlier scoring over generated subspaces: a pyod-style ensemble of kNN / LOF / KDE detectors, one per subspace of a
+model, combined with the subspace probabilities (``model.subspaces`` / ``model.proba``).
 
 For subspace s with feature set F_s and weight p_s, dist_s(x, y) = sqrt(sum_{f in F_s} (x_f - y_f)^2) on the raw features.
 Neighbour lists hold the k reference rows nearest in that distance, ordered by (distance, reference index).  ``fit``
 scores the reference set with each row's own index excluded (sklearn's ``kneighbors(X=None)``); ``decision_function``
 excludes nothing.  kNN scores are the k-th ("largest"), mean or median distance; LOF is sklearn's LocalOutlierFactor
-(positive, larger is more outlying).  The ensemble score is sum_s p_s score_s in float64, subspaces in order.
+(positive, larger is more outlying).  KDE is the Gaussian kernel density with bandwidth h_s (d_s = |F_s|):
+
+    log p_s(q) = logsumexp_r(-dist_s(q, r)^2 / (2 h_s^2)) - log N - d_s log h_s - (d_s / 2) log(2 pi),  score_s = -log p_s
+
+over the N reference rows r, which is sklearn's ``KernelDensity(bandwidth=h_s).score_samples`` negated (pyod's KDE);
+``fit`` leaves row q's own index out (N = n - 1), ``decision_function`` nothing (N = n).  The ensemble score is
+sum_s p_s score_s in float64, subspaces in order.
 
 All distance, selection and scoring work runs in libvgan_hip.so (csrc/outlier.hip); this module plans the work on the
 host (feature lists, chunks of subspaces under a workspace limit) and owns the device buffers.
@@ -25,6 +31,8 @@ ENGINE_ENV = "VGAN_OUTLIER_ENGINE"  # "exact" / "gram" forces one engine for eve
 ENGINES = {"exact": 0, "gram": 1}
 KNN_METHODS = {"largest": 0, "mean": 1, "median": 2}
 _LRD, _LOF = 3, 4
+KDE_MAX_ROWS = (1 << 23) - 1  # VGAN_OUTLIER_KDE_MAX_ROWS: the fixed-point density sum stays below 2^63
+BANDWIDTH_RULES = ("scott", "silverman")
 DEFAULT_WORKSPACE_BYTES = 1 << 30
 _TARGET_BLOCKS = 512  # two workgroups per CU of the 256 on an MI355X
 
@@ -40,6 +48,41 @@ def check_reference_rows(n_ref, k, exclude_self):
     if n_ref < need:
         what = "fit needs at least n_neighbors + 1" if exclude_self else "scoring needs at least n_neighbors"
         raise ValueError(f"{what} reference rows ({need}), got {n_ref}")
+
+
+def check_bandwidth(bandwidth):
+    """A positive finite float, or the name of one of sklearn's rules ("scott", "silverman")."""
+    if isinstance(bandwidth, str):
+        if bandwidth not in BANDWIDTH_RULES:
+            raise ValueError(f"bandwidth must be a positive float, 'scott' or 'silverman', got {bandwidth!r}")
+        return bandwidth
+    if isinstance(bandwidth, bool) or not isinstance(bandwidth, (int, float, np.integer, np.floating)):
+        raise ValueError(f"bandwidth must be a positive float, 'scott' or 'silverman', got {bandwidth!r}")
+    if not (np.isfinite(bandwidth) and bandwidth > 0):
+        raise ValueError(f"bandwidth must be positive and finite, got {bandwidth!r}")
+    return float(bandwidth)
+
+
+def resolve_bandwidth(bandwidth, n, dims):
+    """float64 [S]: h_s per subspace of dims (sizes d_s) for a reference set of n rows; sklearn's KernelDensity rules
+    scott n^(-1 / (d_s + 4)) and silverman (n (d_s + 2) / 4)^(-1 / (d_s + 4))."""
+    bandwidth = check_bandwidth(bandwidth)
+    d = np.asarray(dims, dtype=np.float64)
+    if bandwidth == "scott":
+        return float(n) ** (-1.0 / (d + 4))
+    if bandwidth == "silverman":
+        return (float(n) * (d + 2) / 4.0) ** (-1.0 / (d + 4))
+    return np.full(d.shape, bandwidth, dtype=np.float64)
+
+
+def check_kde_rows(n_ref, exclude_self):
+    """fit (self excluded) needs 2 reference rows, decision_function 1; the fixed-point sum caps them at KDE_MAX_ROWS."""
+    need = 2 if exclude_self else 1
+    if n_ref < need:
+        what = "fit needs at least 2" if exclude_self else "scoring needs at least 1"
+        raise ValueError(f"KDE {what} reference rows, got {n_ref}")
+    if n_ref > KDE_MAX_ROWS:
+        raise ValueError(f"KDE takes at most {KDE_MAX_ROWS} reference rows, got {n_ref}")
 
 
 def _round4(v):
@@ -103,19 +146,25 @@ def _device_matrix(X, d=None):
 
 
 class SubspaceEnsemble:
-    """kNN / LOF detector per subspace, probability-weighted mean of the scores (pyod-style: ``fit`` sets
+    """kNN / LOF / KDE detector per subspace, probability-weighted sum of the scores (pyod-style: ``fit`` sets
     ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying).
 
+    method "kde": Gaussian kernel density; bandwidth is a positive float for every subspace (default 1.0, as in pyod and
+    sklearn) or "scott" / "silverman", sklearn's rules per subspace from the n rows given to ``fit`` and d_s; ``fit`` sets
+    ``bandwidth_``, float64 [S] in the given subspace order.  ``fit`` scores the training set leave-one-out; pyod's
+    in-sample ``decision_scores_`` (self included) are ``decision_function(X_train)``.  n_neighbors and knn_method only
+    serve kNN / LOF (and ``kneighbors``); kNN / LOF ignore bandwidth.
     engine: "auto" (by subspace size, GRAM_MIN_DIMS), "exact" or "gram"; the environment variable VGAN_OUTLIER_ENGINE
-    overrides "auto".  splits: reference-row split J of the neighbour search (None: chosen to fill the chip).
-    workspace_bytes: limit on the packed subspace blocks of one chunk."""
+    overrides "auto".  splits: reference-row split J of the neighbour search / density sum (None: chosen to fill the
+    chip).  workspace_bytes: limit on the packed subspace blocks of one chunk."""
 
-    def __init__(self, subspaces, proba, method="knn", n_neighbors=5, knn_method="largest", engine="auto", splits=None,
-                 workspace_bytes=DEFAULT_WORKSPACE_BYTES):
-        if method not in ("knn", "lof"):
-            raise ValueError(f"method must be 'knn' or 'lof', got {method!r}")
+    def __init__(self, subspaces, proba, method="knn", n_neighbors=5, knn_method="largest", bandwidth=1.0, engine="auto",
+                 splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+        if method not in ("knn", "lof", "kde"):
+            raise ValueError(f"method must be 'knn', 'lof' or 'kde', got {method!r}")
         if knn_method not in KNN_METHODS:
             raise ValueError(f"knn_method must be one of {sorted(KNN_METHODS)}, got {knn_method!r}")
+        self.bandwidth = check_bandwidth(bandwidth) if method == "kde" else bandwidth
         self.n_neighbors = check_neighbors(n_neighbors)
         if engine == "auto":
             engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
@@ -176,7 +225,30 @@ class SubspaceEnsemble:
                                     None if kdist is None else kdist[first:first + count])
             yield first, count, idx, dist
 
+    def _density(self, Xq):
+        """float32 [S, nq]: -log p_s of Xq (None: the reference set, leave-one-out), rows in the given subspace order."""
+        Xr = self._X
+        nr = Xr.shape[0]
+        nq = nr if Xq is None else Xq.shape[0]
+        rows = nr if Xq is None else nr + nq
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xr.device)
+        for first, count, gram in self.plan.chunks(rows, self.workspace_bytes):
+            Pr, sqr = self._pack(Xr, first, count, gram)
+            Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
+            pivot = torch.empty(count * nq, dtype=torch.int32, device=Xr.device)
+            acc = torch.empty(count * nq, dtype=torch.int64, device=Xr.device)
+            self.ops.outlier_kde(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, self._bw, Xq is None,
+                                 ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count), pivot, acc, per,
+                                 self._rows[first:first + count])
+            del Pq, Pr, sqq, sqr
+        return per
+
     def _score(self, Xq, fitting):
+        if self.method == "kde":
+            per = self._density(Xq)
+            out = torch.empty(per.shape[1], dtype=torch.float64, device=per.device)
+            self.ops.outlier_combine(per, self._proba, out)
+            return out, per
         k = self.n_neighbors
         nq = self._X.shape[0] if Xq is None else Xq.shape[0]
         per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=self._X.device)
@@ -198,7 +270,12 @@ class SubspaceEnsemble:
     def fit(self, X, y=None):
         """Keeps X resident as the reference set and scores it (self excluded): decision_scores_, float64 [n]."""
         X = _device_matrix(X, self.plan.d)
-        check_reference_rows(X.shape[0], self.n_neighbors, exclude_self=True)
+        if self.method == "kde":
+            check_kde_rows(X.shape[0], exclude_self=True)
+            self.bandwidth_ = resolve_bandwidth(self.bandwidth, X.shape[0], self.plan.dims[np.argsort(self.plan.order)])
+            self._bw = torch.as_tensor(self.bandwidth_[self.plan.order], device=X.device)
+        else:
+            check_reference_rows(X.shape[0], self.n_neighbors, exclude_self=True)
         self._X = X
         self._center = torch.empty(X.shape[1], dtype=torch.float32, device=X.device)
         self.ops.col_mean(X, self._center)
@@ -220,7 +297,10 @@ class SubspaceEnsemble:
         return_per_subspace=True also the float32 [S, n] per-subspace scores (subspaces in the given order)."""
         self._require_fit()
         X = _device_matrix(X, self.plan.d)
-        check_reference_rows(self._X.shape[0], self.n_neighbors, exclude_self=False)
+        if self.method == "kde":
+            check_kde_rows(self._X.shape[0], exclude_self=False)
+        else:
+            check_reference_rows(self._X.shape[0], self.n_neighbors, exclude_self=False)
         scores, per = self._score(X, fitting=False)
         if return_per_subspace:
             return scores.cpu().numpy(), per.cpu().numpy()
