@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 8
+#define VGAN_ABI_VERSION 9
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -568,6 +568,21 @@ int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out,
  *   <= 1, so nothing underflows to -inf; integer atomics, so the result is the same for every J), the float64 score.
  *   nr <= VGAN_OUTLIER_KDE_MAX_ROWS keeps the fixed-point sum below 2^63.
  * vgan_outlier_combine: out[i] = sum_s weights[s] * score[s, i] for s = 0 .. S-1 in that order, float64.
+ * vgan_outlier_score_stats: a centre and a scale (float64 [S]) per row of the finished score matrix [S, ld] (n scores a
+ *   row, float32, taken as float64).  Row s is whatever the caller stored there: the call knows no subspace table, and
+ *   center[s] / scale[s] belong to row s (SubspaceEnsemble keeps the matrix in the given subspace order).
+ *     VGAN_OUTLIER_NORM_ZSCORE  mean; population standard deviation sqrt(mean((x - center)^2)), two passes
+ *     VGAN_OUTLIER_NORM_ROBUST  median (even n: half the sum of the two middle order statistics);
+ *                               median(fabs(x - center)) / 0.6744897501960817, fabs(x - center) formed in float64
+ *     VGAN_OUTLIER_NORM_MINMAX  minimum; maximum - minimum
+ *   A scale that would be 0 is 1.  The order statistics are exact (a segmented radix select on integer counts), the
+ *   moments fixed-shape float64 reductions without float atomics: every output is bit-identical from run to run.
+ *   Non-finite scores leave the statistics unspecified (no fault).  workspace: device memory, 16-byte aligned, of at
+ *   least vgan_outlier_score_stats_ws_bytes(S, n, mode) bytes (-1 for bad arguments), initialised by the call.
+ *   1 <= S <= 65535, 1 <= n <= ld.
+ * vgan_outlier_combine_normalized: with t_s(x) = (double(x) - center[s]) / scale[s] (center and scale both NULL: t_s(x) =
+ *   double(x)), out[i] = sum_s weights[s] * t_s(score[s, i]) (VGAN_OUTLIER_COMBINE_SUM, s = 0 .. S-1 in that order) or
+ *   max_s t_s(score[s, i]) (VGAN_OUTLIER_COMBINE_MAX; weights unused, may be NULL), float64.
  * ------------------------------------------------------------------------------------------- */
 #define VGAN_OUTLIER_MAX_K 32
 #define VGAN_OUTLIER_ENGINE_EXACT 0
@@ -596,6 +611,16 @@ int vgan_outlier_kde(const float* Pq, const float* sq_q, int nq, const float* Pr
                      const int32_t* score_row, int ld_score, vgan_stream_t stream);
 int vgan_outlier_combine(const float* score, int ld, int S, int n, const double* weights, double* out,
                          vgan_stream_t stream);
+#define VGAN_OUTLIER_NORM_ZSCORE 1
+#define VGAN_OUTLIER_NORM_ROBUST 2
+#define VGAN_OUTLIER_NORM_MINMAX 3
+#define VGAN_OUTLIER_COMBINE_SUM 0
+#define VGAN_OUTLIER_COMBINE_MAX 1
+int64_t vgan_outlier_score_stats_ws_bytes(int S, int n, int mode);
+int vgan_outlier_score_stats(const float* score, int ld, int S, int n, int mode, double* center, double* scale,
+                             void* workspace, int64_t workspace_bytes, vgan_stream_t stream);
+int vgan_outlier_combine_normalized(const float* score, int ld, int S, int n, const double* center, const double* scale,
+                                    const double* weights, int combination, double* out, vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

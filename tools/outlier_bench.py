@@ -6,7 +6,11 @@ Subspaces come from approx_subspace_dist of a briefly trained VGAN_no_kl, so the
 Prints one JSON line: per configuration the median time of both paths over warm repetitions, the fused path's rate
 against the fp32 peak (2 n^2 sum d_s flops per distance sweep: one for kNN, two for KDE), and the largest relative
 difference of the two paths' ensemble scores.
---sweep adds the engine crossover: exact vs Gram engine on subspaces of a fixed size (kNN)."""
+--sweep adds the engine crossover: exact vs Gram engine on subspaces of a fixed size (kNN).
+--normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
+table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
+the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
+launches on their own.  --out also writes the JSON to a file."""
 import argparse
 import gc
 import json
@@ -108,6 +112,80 @@ def run_config(d, n, count, k, reps, with_baseline, method="knn", bandwidth=1.0)
     return row
 
 
+def host_normalized(per, proba, mode):
+    """The numpy alternative to csrc/outlier_norm.hip: float64 statistics per row of per [S, n], transform, weighted sum."""
+    x = per.astype(np.float64)
+    if mode == "zscore":
+        c, w = x.mean(axis=1), x.std(axis=1)
+    elif mode == "robust":
+        c = np.median(x, axis=1)
+        w = np.median(np.abs(x - c[:, None]), axis=1) / 0.6744897501960817
+    else:
+        c = x.min(axis=1)
+        w = x.max(axis=1) - c
+    w[w == 0.0] = 1.0
+    x -= c[:, None]
+    x /= w[:, None]
+    return np.asarray(proba) @ x
+
+
+def run_normalize(d, n, count, mode, reps):
+    from vgan_amd.outlier import COMBINATIONS, NORMALIZATIONS
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    raw = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=5)
+    ens = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=5, normalize=mode)
+    # the three paths differ by tens of microseconds at the small shapes: warm all of them, then time them in turn
+    paths = [lambda: raw.fit(Xd), lambda: ens.fit(Xd), lambda: host_normalized(raw.fit(Xd).per_subspace_scores_, p, mode)]
+    for fn in paths * 3:
+        fn()
+    torch.cuda.synchronize()
+    times = [[], [], []]
+    for _ in range(reps):
+        for ts, fn in zip(times, paths):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+    (t_raw, t_dev, t_host), (r_raw, r_dev, r_host) = [float(np.median(ts)) for ts in times], [[round(t, 6) for t in ts] for ts in times]
+    want = host_normalized(raw.per_subspace_scores_, p, mode)
+    per = torch.as_tensor(raw.per_subspace_scores_, device="cuda")
+    c, w = (torch.empty(len(m), dtype=torch.float64, device="cuda") for _ in range(2))
+    out = torch.empty(n, dtype=torch.float64, device="cuda")
+    t_stats, _ = timed(lambda: ens.ops.outlier_score_stats(per, NORMALIZATIONS[mode], c, w), reps)
+    t_comb, _ = timed(lambda: ens.ops.outlier_combine_normalized(per, c, w, ens._proba, COMBINATIONS["sum"], out), reps)
+    return {"normalize": mode, "d": d, "n": n, "S_sampled": count, "S_distinct": int(len(m)), "k": 5,
+            "fit_raw_s": round(t_raw, 6), "fit_raw_reps_s": r_raw, "fit_normalized_s": round(t_dev, 6), "fit_normalized_reps_s": r_dev,
+            "fit_raw_plus_host_s": round(t_host, 6), "fit_raw_plus_host_reps_s": r_host,
+            "device_added_s": round(t_dev - t_raw, 6), "host_added_s": round(t_host - t_raw, 6),
+            "device_adds_less_than_host": bool(t_dev - t_raw < t_host - t_raw),
+            "stats_launches_s": round(t_stats, 6), "combine_launch_s": round(t_comb, 6),
+            "max_abs_diff_vs_host": float(np.max(np.abs(ens.decision_scores_ - want)))}
+
+
+def normalize_launches(mode, reps, S=500, n=50_000):
+    """The statistics and combine launches alone on a full [S, n] score matrix (approx_subspace_dist returns few distinct
+    subspaces at d = 10, so the fit rows above see a small matrix), against numpy on the same matrix on the host."""
+    from vgan_amd.outlier import COMBINATIONS, NORMALIZATIONS
+    ops = vgan_amd.ops.default_ops()
+    rng = np.random.default_rng(S + n)
+    per_host = (rng.gamma(4.0, size=(S, n)) * rng.uniform(0.5, 20.0, size=(S, 1))).astype(np.float32)
+    p = np.full(S, 1.0 / S)
+    per, pd = torch.as_tensor(per_host, device="cuda"), torch.as_tensor(p, device="cuda")
+    stats = torch.empty(2, S, dtype=torch.float64, device="cuda")
+    out = torch.empty(n, dtype=torch.float64, device="cuda")
+    t_stats, _ = timed(lambda: ops.outlier_score_stats(per, NORMALIZATIONS[mode], stats[0], stats[1]), max(reps, 5))
+    t_comb, _ = timed(lambda: ops.outlier_combine_normalized(per, stats[0], stats[1], pd, COMBINATIONS["sum"], out), max(reps, 5))
+    t0 = time.perf_counter()
+    want = host_normalized(per_host, p, mode)
+    t_host = time.perf_counter() - t0
+    passes = {"zscore": 2, "robust": 12, "minmax": 1}[mode]
+    return {"normalize": mode, "S": S, "n": n, "matrix_bytes": 4 * S * n, "stats_launches_s": round(t_stats, 6),
+            "stats_passes": passes, "stats_read_GBps": round(passes * 4.0 * S * n / t_stats / 1e9, 1),
+            "combine_launch_s": round(t_comb, 6), "combine_read_GBps": round(4.0 * S * n / t_comb / 1e9, 1),
+            "host_numpy_s": round(t_host, 4), "max_abs_diff_vs_host": float(np.max(np.abs(out.cpu().numpy() - want)))}
+
+
 def sweep(n, reps):
     rng = np.random.default_rng(0)
     rows = []
@@ -133,6 +211,9 @@ def main():
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
     ap.add_argument("--method", choices=["knn", "kde"], default="knn")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
+    ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
+                    help="measure score normalisation (repeat for several modes)")
+    ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
     assert torch.cuda.is_available(), "outlier_bench needs an MI355X"
@@ -143,12 +224,25 @@ def main():
     if args.quick:
         configs = [(10, 2000, 20, 5, True), (784, 2000, 10, 5, True)]
     out = {"tool": "outlier_bench", "device": torch.cuda.get_device_name(0), "configs": []}
+    if args.normalize:
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50)]
+        for mode in args.normalize:
+            for d, n, count in shapes:
+                out["configs"].append(run_normalize(d, n, count, mode, args.reps))
+                print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        if not args.quick:
+            out["launches_on_a_full_matrix"] = [normalize_launches(mode, args.reps) for mode in args.normalize]
+        configs = []
     for d, n, count, k, with_base in configs:
         out["configs"].append(run_config(d, n, count, k, args.reps, with_base, args.method, bandwidth))
         print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
     if args.sweep:
         out["engine_sweep"] = sweep(2000 if args.quick else 10_000, args.reps)
     print(json.dumps(out))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":

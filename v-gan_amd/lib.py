@@ -120,9 +120,12 @@ SIGNATURES = {
     "vgan_outlier_score": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p]),
     "vgan_outlier_kde": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "vgan_outlier_combine": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "vgan_outlier_score_stats_ws_bytes": (_i64, [_i, _i, _i]),
+    "vgan_outlier_score_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
+    "vgan_outlier_combine_normalized": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 

@@ -643,6 +643,30 @@ class HipOps:
         _lib.check(self.lib.vgan_outlier_combine(_ptr(score), score.stride(0), S, n, _ptr(weights), _ptr(out), self._stream()),
                    "vgan_outlier_combine")
 
+    def outlier_score_stats(self, score, mode, center, scale):
+        """center / scale (float64 [S]) of the rows of score [S, n]; mode is a VGAN_OUTLIER_NORM_* value."""
+        _mat(score, "score"), _vec(center, "center", torch.float64), _vec(scale, "scale", torch.float64)
+        S, n = score.shape
+        assert center.numel() >= S and scale.numel() >= S
+        need = self.lib.vgan_outlier_score_stats_ws_bytes(S, n, int(mode))
+        if need < 0:
+            _lib.check(1, "vgan_outlier_score_stats_ws_bytes")
+        ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=score.device)
+        _lib.check(self.lib.vgan_outlier_score_stats(_ptr(score), score.stride(0), S, n, int(mode), _ptr(center), _ptr(scale),
+                                                     _ptr(ws), ws.numel() * 8, self._stream()), "vgan_outlier_score_stats")
+
+    def outlier_combine_normalized(self, score, center, scale, weights, combination, out):
+        """out[i] = sum_s weights[s] t_s or max_s t_s with t_s = (score[s, i] - center[s]) / scale[s] (center / scale None:
+        the raw scores); combination is a VGAN_OUTLIER_COMBINE_* value."""
+        _mat(score, "score"), _vec(out, "out", torch.float64)
+        for name, v in (("center", center), ("scale", scale), ("weights", weights)):
+            if v is not None:
+                _vec(v, name, torch.float64)
+        S, n = score.shape
+        _lib.check(self.lib.vgan_outlier_combine_normalized(_ptr(score), score.stride(0), S, n, _ptr(center), _ptr(scale),
+                                                            _ptr(weights), int(combination), _ptr(out), self._stream()),
+                   "vgan_outlier_combine_normalized")
+
 
 _default = None
 

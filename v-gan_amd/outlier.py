@@ -13,9 +13,28 @@ over the N reference rows r, which is sklearn's ``KernelDensity(bandwidth=h_s).s
 ``fit`` leaves row q's own index out (N = n - 1), ``decision_function`` nothing (N = n).  The ensemble score is
 sum_s p_s score_s in float64, subspaces in order.
 
+Normalisation and combination (opt-in; the defaults keep the raw weighted sum).  Only LOF is scale free: a kNN distance
+grows like sqrt(d_s) and a KDE -log p linearly with d_s, so raw scores let the widest subspaces decide.  With
+``normalize`` set, ``fit`` takes from the n fit-time scores x of every subspace (float32, as float64) a centre c_s and a
+scale w_s, both float64 (``score_center_`` / ``score_scale_``, [S] in the given subspace order):
+
+    "zscore"  mean; population standard deviation sqrt(mean((x - c_s)^2))                  (sklearn's StandardScaler)
+    "robust"  numpy.median(x); median(abs(x - c_s)) / 0.6744897501960817   (scipy's median_abs_deviation, scale="normal")
+    "minmax"  minimum; maximum - minimum                                                     (sklearn's MinMaxScaler)
+
+A scale that would be 0 (constant scores) is 1.  t_s(x) = (float64(x) - c_s) / w_s, or float64(x) without ``normalize``;
+``combination`` "sum" gives sum_s p_s t_s(score_s), subspaces in order, "max" gives max_s t_s(score_s) (pyod's
+maximization; proba is not used).  ``decision_function`` applies the statistics stored by ``fit`` to the scores of the new
+rows (pyod's standardizer(train, test)) and computes none of its own; the per-subspace scores handed out stay the raw
+detector scores.  Non-finite scores (NaN input) leave the statistics unspecified; they neither fault nor hang.
+``contamination`` sets ``threshold_`` = numpy.percentile(decision_scores_, 100 (1 - contamination)), ``labels_`` =
+(decision_scores_ > threshold_), and serves ``predict`` / ``predict_proba`` (pyod's rules, host code on the [n] vector).
+
 All distance, selection and scoring work runs in libvgan_hip.so (csrc/outlier.hip); this module plans the work on the
-host (feature lists, chunks of subspaces under a workspace limit) and owns the device buffers.
+host (feature lists, chunks of subspaces under a workspace limit) and owns the device buffers.  The statistics, the
+transform and the combination run there too (csrc/outlier_norm.hip), on the score matrix the detectors left on the device.
 """
+import math
 import os
 
 import numpy as np
@@ -35,6 +54,9 @@ KDE_MAX_ROWS = (1 << 23) - 1  # VGAN_OUTLIER_KDE_MAX_ROWS: the fixed-point densi
 BANDWIDTH_RULES = ("scott", "silverman")
 DEFAULT_WORKSPACE_BYTES = 1 << 30
 _TARGET_BLOCKS = 512  # two workgroups per CU of the 256 on an MI355X
+NORMALIZATIONS = {"zscore": 1, "robust": 2, "minmax": 3}  # VGAN_OUTLIER_NORM_*
+COMBINATIONS = {"sum": 0, "max": 1}  # VGAN_OUTLIER_COMBINE_*
+PROBA_METHODS = ("linear", "unify")
 
 
 def check_neighbors(k):
@@ -83,6 +105,52 @@ def check_kde_rows(n_ref, exclude_self):
         raise ValueError(f"KDE {what} reference rows, got {n_ref}")
     if n_ref > KDE_MAX_ROWS:
         raise ValueError(f"KDE takes at most {KDE_MAX_ROWS} reference rows, got {n_ref}")
+
+
+def check_normalize(normalize):
+    if normalize is not None and not (isinstance(normalize, str) and normalize in NORMALIZATIONS):
+        raise ValueError(f"normalize must be None, 'zscore', 'robust' or 'minmax', got {normalize!r}")
+    return normalize
+
+
+def check_combination(combination):
+    if not (isinstance(combination, str) and combination in COMBINATIONS):
+        raise ValueError(f"combination must be 'sum' or 'max', got {combination!r}")
+    return combination
+
+
+def check_contamination(contamination):
+    """A float in (0, 0.5] (pyod's range)."""
+    if isinstance(contamination, bool) or not isinstance(contamination, (int, float, np.integer, np.floating)):
+        raise ValueError(f"contamination must be a float in (0, 0.5], got {contamination!r}")
+    if not 0.0 < float(contamination) <= 0.5:  # False for nan
+        raise ValueError(f"contamination must be in (0, 0.5], got {contamination!r}")
+    return float(contamination)
+
+
+def decision_threshold(scores, contamination):
+    """pyod's threshold_: numpy.percentile(scores, 100 (1 - contamination)); labels are scores > threshold."""
+    contamination = check_contamination(contamination)
+    return float(np.percentile(np.asarray(scores, dtype=np.float64), 100.0 * (1.0 - contamination)))
+
+
+def outlier_probability(train_scores, scores, method="linear"):
+    """float64 [n, 2]: column 1 the outlier probability of scores, column 0 its complement (pyod's predict_proba).
+    "linear": (s - min) / (max - min) over train_scores; "unify": erf((s - mean) / (std sqrt(2))), population std; both
+    clipped to [0, 1].  A zero range or std (constant train_scores) counts as 1, the scalers' rule for a constant column."""
+    if method not in PROBA_METHODS:
+        raise ValueError(f"method must be 'linear' or 'unify', got {method!r}")
+    train = np.asarray(train_scores, dtype=np.float64).reshape(-1)
+    s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    if method == "linear":
+        lo, width = train.min(), train.max() - train.min()
+        p = (s - lo) / (width if width != 0.0 else 1.0)
+    else:
+        sigma = train.std()
+        z = (s - train.mean()) / ((sigma if sigma != 0.0 else 1.0) * math.sqrt(2.0))
+        p = torch.erf(torch.as_tensor(z, dtype=torch.float64)).numpy()
+    p = np.clip(p, 0.0, 1.0)
+    return np.stack([1.0 - p, p], axis=1)
 
 
 def _round4(v):
@@ -156,14 +224,25 @@ class SubspaceEnsemble:
     serve kNN / LOF (and ``kneighbors``); kNN / LOF ignore bandwidth.
     engine: "auto" (by subspace size, GRAM_MIN_DIMS), "exact" or "gram"; the environment variable VGAN_OUTLIER_ENGINE
     overrides "auto".  splits: reference-row split J of the neighbour search / density sum (None: chosen to fill the
-    chip).  workspace_bytes: limit on the packed subspace blocks of one chunk."""
+    chip).  workspace_bytes: limit on the packed subspace blocks of one chunk.
+
+    normalize: None (raw scores), "zscore", "robust" (median / MAD) or "minmax": per-subspace statistics of the fit-time
+    scores, published as ``score_center_`` / ``score_scale_`` (float64 [S], given order; None without normalize) and
+    applied by ``fit`` and ``decision_function`` alike.  combination: "sum" (probability-weighted) or "max" (pyod's
+    maximization; proba is not used).  contamination in (0, 0.5]: after ``fit``, ``threshold_`` is that upper percentile
+    of ``decision_scores_`` and ``labels_`` marks the rows above it (both taken on first use); ``predict`` /
+    ``predict_proba`` follow pyod.  ``per_subspace_scores_`` and
+    ``return_per_subspace`` stay the raw detector scores.  Non-finite scores leave the statistics unspecified."""
 
     def __init__(self, subspaces, proba, method="knn", n_neighbors=5, knn_method="largest", bandwidth=1.0, engine="auto",
-                 splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+                 splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
         if method not in ("knn", "lof", "kde"):
             raise ValueError(f"method must be 'knn', 'lof' or 'kde', got {method!r}")
         if knn_method not in KNN_METHODS:
             raise ValueError(f"knn_method must be one of {sorted(KNN_METHODS)}, got {knn_method!r}")
+        self.normalize = check_normalize(normalize)
+        self.combination = check_combination(combination)
+        self.contamination = check_contamination(contamination)
         self.bandwidth = check_bandwidth(bandwidth) if method == "kde" else bandwidth
         self.n_neighbors = check_neighbors(n_neighbors)
         if engine == "auto":
@@ -184,6 +263,9 @@ class SubspaceEnsemble:
         self._rows = torch.as_tensor(self.plan.order, device=dev)
         self._proba = torch.as_tensor(p, device=dev)
         self._X = None
+        self._stats = None  # float64 [2, S] on the device (centres, scales), set by fit when normalize is given
+        self._decisions = None  # (threshold_, labels_), taken from decision_scores_ on first use
+        self.score_center_ = self.score_scale_ = None
 
     # ---- pipeline --------------------------------------------------------------------------------
     def _pack(self, X, first, count, gram):
@@ -243,12 +325,24 @@ class SubspaceEnsemble:
             del Pq, Pr, sqq, sqr
         return per
 
+    def _combine(self, per, fitting):
+        """float64 [n]: the ensemble score of the raw per-subspace scores per [S, n]; fit takes the statistics first."""
+        S, n = per.shape
+        if fitting and self.normalize is not None:
+            self._stats = torch.empty(2, S, dtype=torch.float64, device=per.device)
+            self.ops.outlier_score_stats(per, NORMALIZATIONS[self.normalize], self._stats[0], self._stats[1])
+        out = torch.empty(n, dtype=torch.float64, device=per.device)
+        if self.normalize is None and self.combination == "sum":
+            self.ops.outlier_combine(per, self._proba, out)
+        else:
+            center, scale = (None, None) if self.normalize is None else self._stats
+            self.ops.outlier_combine_normalized(per, center, scale, self._proba, COMBINATIONS[self.combination], out)
+        return out
+
     def _score(self, Xq, fitting):
         if self.method == "kde":
             per = self._density(Xq)
-            out = torch.empty(per.shape[1], dtype=torch.float64, device=per.device)
-            self.ops.outlier_combine(per, self._proba, out)
-            return out, per
+            return self._combine(per, fitting), per
         k = self.n_neighbors
         nq = self._X.shape[0] if Xq is None else Xq.shape[0]
         per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=self._X.device)
@@ -262,13 +356,12 @@ class SubspaceEnsemble:
                 self.ops.outlier_score(idx, dist, nq, k, count, _LRD, kdist_ref=kd, nr=nq, lrd_out=lrd)
             self.ops.outlier_score(idx, dist, nq, k, count, _LOF, score=per, score_row=rows, kdist_ref=kd, lrd_ref=lrd,
                                    nr=self._X.shape[0])
-        out = torch.empty(nq, dtype=torch.float64, device=self._X.device)
-        self.ops.outlier_combine(per, self._proba, out)
-        return out, per
+        return self._combine(per, fitting), per
 
     # ---- public surface --------------------------------------------------------------------------
     def fit(self, X, y=None):
-        """Keeps X resident as the reference set and scores it (self excluded): decision_scores_, float64 [n]."""
+        """Keeps X resident as the reference set and scores it (self excluded): decision_scores_, float64 [n]; with
+        normalize also score_center_ / score_scale_; threshold_ and labels_ from contamination."""
         X = _device_matrix(X, self.plan.d)
         if self.method == "kde":
             check_kde_rows(X.shape[0], exclude_self=True)
@@ -286,7 +379,27 @@ class SubspaceEnsemble:
         scores, per = self._score(None, fitting=True)
         self.decision_scores_ = scores.cpu().numpy()
         self.per_subspace_scores_ = per.cpu().numpy()
+        if self.normalize is not None:
+            self.score_center_, self.score_scale_ = self._stats.cpu().numpy()
+        self._decisions = None
         return self
+
+    def _decide(self):
+        if self._decisions is None:
+            threshold = decision_threshold(self.decision_scores_, self.contamination)
+            self._decisions = (threshold, (self.decision_scores_ > threshold).astype(int))
+        return self._decisions
+
+    @property
+    def threshold_(self):
+        """numpy.percentile(decision_scores_, 100 (1 - contamination)); taken on first use, so that a fit that never asks
+        for a decision does not pay for the percentile on the host."""
+        return self._decide()[0]
+
+    @property
+    def labels_(self):
+        """int [n]: 1 where decision_scores_ exceeds threshold_."""
+        return self._decide()[1]
 
     def _require_fit(self):
         if self._X is None:
@@ -305,6 +418,17 @@ class SubspaceEnsemble:
         if return_per_subspace:
             return scores.cpu().numpy(), per.cpu().numpy()
         return scores.cpu().numpy()
+
+    def predict(self, X):
+        """int [n]: 1 where decision_function(X) exceeds threshold_ (pyod's predict)."""
+        return (self.decision_function(X) > self.threshold_).astype(int)
+
+    def predict_proba(self, X, method="linear"):
+        """float64 [n, 2], column 1 the outlier probability: outlier_probability(decision_scores_, decision_function(X))."""
+        if method not in PROBA_METHODS:
+            raise ValueError(f"method must be 'linear' or 'unify', got {method!r}")
+        self._require_fit()
+        return outlier_probability(self.decision_scores_, self.decision_function(X), method)
 
     def kneighbors(self, X=None):
         """(dist float32 [S, n, k], idx int32 [S, n, k]) per subspace: the sorted neighbour lists of X, or of the reference

@@ -173,8 +173,9 @@ class _RunFolder:
     def outlier_ensemble(self, method="knn", n_neighbors=5, subspace_count=500, X=None, **kw):
         """A SubspaceEnsemble (vgan_amd.outlier) over this model's subspaces and probabilities: self.subspaces / self.proba
         if they are set, otherwise approx_subspace_dist(subspace_count) first.  Fitted on X when X is given.  method is
-        "knn", "lof" or "kde"; further keywords (knn_method, bandwidth, engine, splits, workspace_bytes) go to
-        SubspaceEnsemble, e.g. outlier_ensemble(method="kde", bandwidth="scott", X=X)."""
+        "knn", "lof" or "kde"; further keywords (knn_method, bandwidth, engine, splits, workspace_bytes, normalize,
+        combination, contamination) go to SubspaceEnsemble, e.g. outlier_ensemble(method="kde", bandwidth="scott", X=X) or
+        outlier_ensemble(method="knn", normalize="robust", combination="max", contamination=0.05, X=X)."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
