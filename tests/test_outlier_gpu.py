@@ -3,6 +3,7 @@ restatement in test_outlier_cpu.py."""
 import numpy as np
 import pytest
 
+from outlier_checks import check_neighbor_lists
 from test_outlier_cpu import restate_ensemble, restate_neighbors
 
 pytestmark = pytest.mark.gpu
@@ -59,6 +60,7 @@ def test_neighbor_lists_match_the_restatement(data, engine, ds):
             assert (np.diff(D[0], axis=1) >= 0).all()
             if excl:
                 assert not (I[0] == np.arange(777)[:, None]).any()
+            check_neighbor_lists(D[0], I[0], Xr if Q is None else Q, Xr, feats, k, excl, engine)  # every row, no filter
 
 
 @pytest.mark.parametrize("engine", ["exact", "gram"])

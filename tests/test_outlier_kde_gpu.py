@@ -3,6 +3,7 @@ float64 restatement in test_outlier_kde_cpu.py."""
 import numpy as np
 import pytest
 
+from outlier_checks import kde_tolerance as _tolerance
 from test_outlier_cpu import restate_neighbors
 from test_outlier_gpu import _planted
 from test_outlier_kde_cpu import (restate_bandwidth, restate_kde, restate_kde_ensemble, restate_kde_from_sq_dists,
@@ -17,26 +18,6 @@ def _single(d, feats):
     m = np.zeros((1, d), bool)
     m[0, feats] = True
     return m
-
-
-def _tolerance(D2, want, ds, h, exclude_self, engine, d2_abs=None):
-    """Per-row bound on |score - restatement|: 1e-5 relative, 1e-6 absolute for the float32 sums of the exp2 terms and
-    the float32 output, plus the float32 error of the engine's d2 carried through the logsumexp.  A d2 error of at most
-    e_r moves -log p by at most max_r e_r / (2 h^2) over the rows that carry weight; the exact engine's sum of w_s
-    non-negative squares is within (w_s + 2) eps32 relative, so there the move is at most (w_s + 2) eps32 times the
-    softmax-weighted mean of d2 / (2 h^2).  The Gram engine's error is absolute, d2_abs per row (the cancellation bound
-    of test_outlier_gpu.py)."""
-    L = -D2 / (2.0 * h * h)
-    if exclude_self:
-        L = L.copy()
-        np.fill_diagonal(L, -np.inf)
-    w = np.exp(L - L.max(axis=1, keepdims=True))
-    w /= w.sum(axis=1, keepdims=True)
-    energy = np.nansum(w * np.where(np.isfinite(L), -L, 0.0), axis=1)
-    tol = 1e-5 * np.abs(want) + 1e-6 + (ds + 6) * EPS32 * energy
-    if engine == "gram":
-        tol += d2_abs / (2.0 * h * h)
-    return tol
 
 
 _D2 = {}
