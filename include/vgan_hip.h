@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 9
+#define VGAN_ABI_VERSION 10
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -621,6 +621,54 @@ int vgan_outlier_score_stats(const float* score, int ld, int S, int n, int mode,
                              void* workspace, int64_t workspace_bytes, vgan_stream_t stream);
 int vgan_outlier_combine_normalized(const float* score, int ld, int S, int n, const double* center, const double* scale,
                                     const double* weights, int combination, double* out, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched k-means over the subspaces of a SUBSPACE TABLE and the cluster-based local outlier factor (CBLOF; He, Xu,
+ * Deng 2003; pyod's CBLOF) on top of it  (v-gan_amd/outlier.py: SubspaceCBLOF).  C = n_clusters, 2 <= C <=
+ * VGAN_CLUSTER_MAX_CLUSTERS, squared Euclidean distance over the raw features of each subspace.  Per-subspace state
+ * lives in device arrays indexed by table position s:
+ *   centers   float64, the [C, d_s] centres of subspace s at element C * feat_off[s]: the master copy;
+ *   changed   int32 [S], labels changed by the last E step (cleared by the M step); done int32 [S], 0 running,
+ *             1 an E step changed no label (strict convergence), 2 the tolerance rule; n_iter int32 [S], M steps done;
+ *   tol_var   float64 [S]: an M step whose summed squared centre shift is <= tol_var[s] ends the subspace; 0 disables.
+ * and per chunk: img float32, the centres as the distance engines read them (chunk subspace s: [C, w_s] at element
+ * C * (col_off[s] - col_off[first]), minus col_center[feat] when col_center is given, zero padded), img_sq [count, C]
+ * its squared row norms (Gram engine), label int32 [count, n] (the caller fills it with -1 before the first iteration).
+ * vgan_cluster_image: img / img_sq (may be NULL) from centers, for the chunk.
+ * vgan_cluster_lloyd: enqueues `iterations` Lloyd iterations for the chunk; nothing is read back.  One iteration:
+ *   E  every row of the packed block Pq (sq_q: its norms, Gram engine; as for vgan_outlier_knn) takes the centre with the
+ *      smallest (engine d2, centre index); changed[s] counts the labels that differ from the previous ones;
+ *   M  changed[s] == 0: done[s] = 1 and no M step.  Otherwise every centre becomes the float64 mean of its raw rows
+ *      X [n, d] (ldx), summed over a fixed partition of the rows (slices of VGAN_CLUSTER_SLICE_ROWS rows by
+ *      n, inside a slice row groups by C and d_s, then the slices in order; never by the chunk): no float atomics, the
+ *      same bits for every chunking.  A
+ *      cluster without rows keeps its centre.  img / img_sq are rewritten, n_iter[s] += 1, the tolerance rule is applied.
+ *   A subspace with done[s] != 0 is skipped by every kernel.  total_dims = sum of d_s over the chunk, max_dims = the
+ *   largest d_s; workspace: 16-byte aligned, vgan_cluster_lloyd_ws_bytes(n, C, count, total_dims) bytes (-1 for bad
+ *   arguments).  n >= C.
+ * vgan_cluster_final: float64 from the raw rows Xq [nq, d] (ldq) and centers, all S subspaces of the table.
+ *   large == NULL  label [S, nq] = the nearest centre by (d2, index); sizes int64 [S, C] += the label counts (zeroed by
+ *                  the caller); inertia [S] = sum of the d2 to the own centre (inertia_part: float64 workspace
+ *                  [S, ceil(nq / 64)]; fixed order).
+ *   large != NULL  (int32 [S, C], non-zero: a large cluster) score[row, q] = the distance to the own centre if it is
+ *                  large, otherwise to the nearest large centre, times sizes[s, label] if use_weights (float32; row =
+ *                  score_row[s], or s when score_row is NULL; ld_score >= nq); label may be NULL.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_CLUSTER_MAX_CLUSTERS 64
+#define VGAN_CLUSTER_SLICE_ROWS 1024
+int64_t vgan_cluster_lloyd_ws_bytes(int n, int n_clusters, int count, int total_dims);
+int vgan_cluster_image(const double* centers, int n_clusters, const int32_t* feat, const int32_t* feat_off,
+                       const int64_t* col_off, int first, int count, const float* col_center, float* img, float* img_sq,
+                       vgan_stream_t stream);
+int vgan_cluster_lloyd(const float* Pq, const float* sq_q, const float* X, int ldx, int n, int d, const int32_t* feat,
+                       const int32_t* feat_off, const int64_t* col_off, int first, int count, int total_dims, int max_dims,
+                       int n_clusters, int engine, const float* col_center, const double* tol_var, double* centers,
+                       float* img, float* img_sq, int32_t* label, int32_t* changed, int32_t* done, int32_t* n_iter,
+                       void* workspace, int64_t workspace_bytes, int iterations, vgan_stream_t stream);
+int vgan_cluster_final(const float* Xq, int ldq, int nq, int d, const int32_t* feat, const int32_t* feat_off, int S,
+                       int n_clusters, const double* centers, const int32_t* large, int64_t* sizes, int use_weights,
+                       int32_t* label, double* inertia_part, double* inertia, float* score, const int32_t* score_row,
+                       int ld_score, vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

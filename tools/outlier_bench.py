@@ -7,6 +7,11 @@ Prints one JSON line: per configuration the median time of both paths over warm 
 against the fp32 peak (2 n^2 sum d_s flops per distance sweep: one for kNN, two for KDE), and the largest relative
 difference of the two paths' ensemble scores.
 --sweep adds the engine crossover: exact vs Gram engine on subspaces of a fixed size (kNN).
+  --method cblof: k-means + CBLOF (vgan_amd.SubspaceCBLOF) at C = 8 and C = 64 from the same random rows, tol = 0 and a
+    fixed max_iter (--iters): fit time, time per Lloyd iteration, fit time per polling stride; baseline (a) per subspace
+    torch.cdist + argmin + index_add_ on the GPU with the float64 score tail in torch, (b) sklearn's KMeans (lloyd, same
+    init and iteration count) on the CPUs for a sample of the subspaces, scaled to all of them; and the E step composed
+    from vgan_outlier_knn with k = 1 over the centres against one whole iteration (assign + update) on the same operands.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -112,6 +117,122 @@ def run_config(d, n, count, k, reps, with_baseline, method="knn", bandwidth=1.0)
     return row
 
 
+def baseline_cblof(X, subspaces, proba, rows, C, iters, alpha=0.9, beta=5.0):
+    """Per subspace on the GPU: iters Lloyd iterations (float32 cdist + argmin, float64 index_add_ means, an empty cluster
+    keeps its centre), then the float64 assignment and CBLOF scores; the boundary on the host as in the product."""
+    from vgan_amd.outlier import large_cluster_boundary
+    n = X.shape[0]
+    out = torch.zeros(n, dtype=torch.float64, device=X.device)
+    rows = torch.as_tensor(rows, device=X.device)
+    for s in range(len(subspaces)):
+        Xs = X[:, torch.as_tensor(np.flatnonzero(subspaces[s]), device=X.device)].contiguous()
+        X64 = Xs.double()
+        cen = X64[rows].clone()
+        ones = torch.ones(n, dtype=torch.float64, device=X.device)
+        for _ in range(iters):
+            lab = torch.cdist(Xs, cen.float()).argmin(dim=1)
+            sums = torch.zeros_like(cen).index_add_(0, lab, X64)
+            cnt = torch.zeros(C, dtype=torch.float64, device=X.device).index_add_(0, lab, ones)
+            cen = torch.where(cnt[:, None] > 0, sums / cnt.clamp(min=1.0)[:, None], cen)
+        D = torch.cdist(X64, cen)
+        lab = D.argmin(dim=1)
+        sizes = torch.bincount(lab, minlength=C).cpu().numpy()
+        large = torch.as_tensor(large_cluster_boundary(sizes, alpha, beta)[1], device=X.device)
+        own = D.gather(1, lab[:, None])[:, 0]
+        score = torch.where(large[lab], own, D[:, large].min(dim=1).values).float()
+        out += float(proba[s]) * score.double()
+    return out
+
+
+def cblof_baselines(row, ens, X, Xd, m, p, rows, C, iters, reps, t_fit, sklearn_sample):
+    S = len(m)
+    # (a) torch on the same GPU
+    t_base, tb = timed(lambda: baseline_cblof(Xd, m, p, rows, C, iters), reps)
+    want = baseline_cblof(Xd, m, p, rows, C, iters).cpu().numpy()
+    rel = np.abs(ens.decision_scores_ - want) / np.maximum(np.abs(want), 1e-12)
+    row.update({"torch_s": round(t_base, 5), "torch_reps_s": tb, "speedup_vs_torch": round(t_base / t_fit, 2),
+                "max_rel_diff_vs_torch": float(rel.max()), "median_rel_diff_vs_torch": float(np.median(rel)),
+                "rows_beyond_1e-5_vs_torch": int((rel > 1e-5).sum())})
+    # (b) sklearn on the CPUs, a sample of the subspaces scaled to all of them
+    try:
+        from sklearn.cluster import KMeans
+        import warnings
+        pick = np.unique(np.linspace(0, S - 1, min(S, sklearn_sample)).astype(int))
+        X64 = X.astype(np.float64)
+        t0 = time.perf_counter()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            for s in pick:
+                f = np.flatnonzero(m[s])
+                KMeans(n_clusters=C, init=X64[rows][:, f], n_init=1, algorithm="lloyd", max_iter=iters, tol=0.0).fit(X64[:, f])
+        t_sk = (time.perf_counter() - t0) * S / len(pick)
+        row.update({"sklearn_s": round(t_sk, 4), "sklearn_subspaces_timed": int(len(pick)), "speedup_vs_sklearn": round(t_sk / t_fit, 1)})
+    except ImportError:
+        row["sklearn_s"] = None
+
+
+def run_cblof(d, n, count, C, reps, iters, baselines=True, sklearn_sample=20):
+    from vgan_amd.outlier import ENGINES
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    rows = np.random.default_rng(0).choice(n, C, replace=False)
+
+    def make(max_iter, stride=None):
+        ens = vgan_amd.SubspaceCBLOF(m, p, n_clusters=C, init=rows, tol=0.0, max_iter=max_iter)
+        if stride is not None:
+            ens.poll_stride = stride
+        return ens
+
+    ens = make(iters)
+    t_fit, ts = timed(lambda: ens.fit(Xd), reps)
+    one = make(1)
+    t_one, _ = timed(lambda: one.fit(Xd), reps)
+    row = {"method": "cblof", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_clusters": C, "max_iter": iters,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "gram_subspaces": int(ens.plan.gram.sum()), "n_iter_min": int(ens.n_iter_.min()), "n_iter_max": int(ens.n_iter_.max()),
+           "fit_s": round(t_fit, 5), "fit_reps_s": ts, "fit_max_iter_1_s": round(t_one, 5),
+           "per_iteration_s": round((t_fit - t_one) / max(iters - 1, 1), 6), "poll_stride_default": ens.poll_stride}
+    dflt = vgan_amd.SubspaceCBLOF(m, p, n_clusters=C, init=rows, max_iter=iters)  # tol = 1e-4: the variances are taken too
+    row["fit_default_tol_s"] = round(timed(lambda: dflt.fit(Xd), reps)[0], 5)
+    row["n_iter_default_tol_min_max"] = [int(dflt.n_iter_.min()), int(dflt.n_iter_.max())]
+    for stride in (1, 2, 4, 8, 16):
+        e = make(iters, stride)
+        row[f"fit_stride_{stride}_s"] = round(timed(lambda: e.fit(Xd), reps)[0], 5)
+    if baselines:
+        cblof_baselines(row, ens, X, Xd, m, p, rows, C, iters, reps, t_fit, sklearn_sample)
+    # the E step composed from vgan_outlier_knn (k = 1, the centres as reference rows) against one whole iteration
+    ops, dev = ens.ops, Xd.device
+    jobs = []
+    for first, cnt, gram in ens.plan.chunks(n, ens.workspace_bytes):
+        cols = int(ens.plan.col_off[first + cnt] - ens.plan.col_off[first])
+        Pq, sqq = ens._pack(Xd, first, cnt, gram, centred=True)
+        img = torch.empty(C * cols, dtype=torch.float32, device=dev)
+        img_sq = torch.empty(cnt, C, dtype=torch.float32, device=dev) if gram else None
+        ops.cluster_image(ens._centers, C, ens._table, first, cnt, ens._center, img, img_sq)
+        dd = ens.plan.dims[first:first + cnt]
+        ws = torch.empty(ops.cluster_lloyd_ws_bytes(n, C, cnt, int(dd.sum())) // 8, dtype=torch.float64, device=dev)
+        jobs.append((first, cnt, ENGINES["gram" if gram else "exact"], Pq, sqq, img, img_sq, int(dd.sum()), int(dd.max()), ws,
+                     torch.empty(cnt, n, 1, dtype=torch.int32, device=dev), torch.empty(cnt, n, dtype=torch.int32, device=dev)))
+    centers = ens._centers.clone()
+    state = torch.zeros(3, S, dtype=torch.int32, device=dev)
+
+    def knn_sweep():
+        for first, cnt, eng, Pq, sqq, img, img_sq, _, _, _, nbr, _ in jobs:
+            ops.outlier_knn(Pq, sqq, n, img, img_sq, C, ens._table, first, cnt, 1, False, eng, 1, nbr)
+
+    def iteration():
+        state.zero_()
+        for first, cnt, eng, Pq, sqq, img, img_sq, tot, mx, ws, _, label in jobs:
+            label.fill_(-1)
+            ops.cluster_lloyd(Pq, sqq, Xd, ens._table, first, cnt, tot, mx, C, eng, ens._center, ens._tol_var, centers, img, img_sq,
+                              label, state[0], state[1], state[2], ws, 1)
+
+    row["knn_k1_sweep_s"] = round(timed(knn_sweep, max(reps, 5))[0], 6)
+    row["one_iteration_s"] = round(timed(iteration, max(reps, 5))[0], 6)
+    return row
+
+
 def host_normalized(per, proba, mode):
     """The numpy alternative to csrc/outlier_norm.hip: float64 statistics per row of per [S, n], transform, weighted sum."""
     x = per.astype(np.float64)
@@ -209,7 +330,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof"], default="knn")
+    ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
@@ -232,6 +355,13 @@ def main():
                 print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         if not args.quick:
             out["launches_on_a_full_matrix"] = [normalize_launches(mode, args.reps) for mode in args.normalize]
+        configs = []
+    if args.method == "cblof":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50)]
+        for d, n, count in shapes:
+            for C in (8, 64):
+                out["configs"].append(run_cblof(d, n, count, C, args.reps, args.iters, baselines=not args.no_baselines))
+                print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     for d, n, count, k, with_base in configs:
         out["configs"].append(run_config(d, n, count, k, args.reps, with_base, args.method, bandwidth))

@@ -42,13 +42,6 @@ __device__ __forceinline__ float f32_from_key(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {  // fixed order; result valid in thread 0
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // A thread's kNPer elements of a slice, all loads issued before the first use: indices past the end are clamped to the
 // last element (an unconditional load; the callers mask those values or, for min / max, do not mind the repeat).
 __device__ __forceinline__ void load_slice(const float* __restrict__ row, long base, int n, float (&x)[kNPer]) {

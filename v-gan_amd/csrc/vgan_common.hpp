@@ -61,6 +61,15 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
     return v;
 }
 
+// float64 sum over a kBlock-thread workgroup in a fixed order (wave butterfly, then the four waves in order); red: 4 doubles
+// of LDS; the result is valid in thread 0
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // Column-max key: U > 0 always, so its IEEE bits order like the value; ties go to the LOWEST row.
 __device__ __forceinline__ unsigned long long colkey_pack(float u, unsigned row) {
     return ((unsigned long long)__float_as_uint(u) << 32) | (unsigned long long)(0xFFFFFFFFu - row);

@@ -123,9 +123,14 @@ SIGNATURES = {
     "vgan_outlier_score_stats_ws_bytes": (_i64, [_i, _i, _i]),
     "vgan_outlier_score_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
     "vgan_outlier_combine_normalized": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
+    "vgan_cluster_lloyd_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "vgan_cluster_image": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "vgan_cluster_lloyd": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                _p, _i64, _i, _p]),
+    "vgan_cluster_final": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 _lib = None
 
 

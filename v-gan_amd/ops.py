@@ -667,6 +667,56 @@ class HipOps:
                                                             _ptr(weights), int(combination), _ptr(out), self._stream()),
                    "vgan_outlier_combine_normalized")
 
+    # ---- k-means / CBLOF over subspaces (vgan_amd.outlier.SubspaceCBLOF) ------------------------------
+    def cluster_lloyd_ws_bytes(self, n, n_clusters, count, total_dims):
+        need = self.lib.vgan_cluster_lloyd_ws_bytes(int(n), int(n_clusters), int(count), int(total_dims))
+        if need < 0:
+            _lib.check(1, "vgan_cluster_lloyd_ws_bytes")
+        return need
+
+    def cluster_image(self, centers, n_clusters, table, first, count, col_center, img, img_sq=None):
+        _vec(centers, "centers", torch.float64), _vec(img, "img")
+        feat, feat_off, col_off = table
+        _lib.check(self.lib.vgan_cluster_image(_ptr(centers), int(n_clusters), _ptr(feat), _ptr(feat_off), _ptr(col_off), int(first),
+                                               int(count), _ptr(col_center), _ptr(img), _ptr(img_sq), self._stream()),
+                   "vgan_cluster_image")
+
+    def cluster_lloyd(self, Pq, sq_q, X, table, first, count, total_dims, max_dims, n_clusters, engine, col_center, tol_var, centers,
+                      img, img_sq, label, changed, done, n_iter, workspace, iterations):
+        """Enqueues `iterations` Lloyd iterations for the chunk [first, first + count); reads nothing back."""
+        _mat(X, "X"), _vec(Pq, "Pq"), _vec(img, "img"), _vec(centers, "centers", torch.float64), _vec(tol_var, "tol_var", torch.float64)
+        _vec(workspace, "workspace", torch.float64), _vec(label, "label", torch.int32)
+        for name, v in (("changed", changed), ("done", done), ("n_iter", n_iter)):
+            _vec(v, name, torch.int32)
+        assert label.numel() >= count * X.shape[0]
+        feat, feat_off, col_off = table
+        n, d = X.shape
+        _lib.check(self.lib.vgan_cluster_lloyd(_ptr(Pq), _ptr(sq_q), _ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(col_off),
+                                               int(first), int(count), int(total_dims), int(max_dims), int(n_clusters), int(engine),
+                                               _ptr(col_center), _ptr(tol_var), _ptr(centers), _ptr(img), _ptr(img_sq), _ptr(label),
+                                               _ptr(changed), _ptr(done), _ptr(n_iter), _ptr(workspace), workspace.numel() * 8,
+                                               int(iterations), self._stream()), "vgan_cluster_lloyd")
+
+    def cluster_final(self, Xq, table, S, n_clusters, centers, sizes, large=None, use_weights=False, label=None, inertia=None,
+                      score=None, score_row=None):
+        """large None: label [S, nq], sizes [S, C] (+=) and inertia [S]; otherwise the CBLOF scores (and label if given)."""
+        _mat(Xq, "Xq"), _vec(centers, "centers", torch.float64), _vec(sizes, "sizes", torch.int64)
+        feat, feat_off, _ = table
+        nq, d = Xq.shape
+        part = None
+        if large is None:
+            _vec(label, "label", torch.int32), _vec(inertia, "inertia", torch.float64)
+            assert label.numel() >= S * nq and inertia.numel() >= S
+            part = torch.empty(S * ((nq + 63) // 64), dtype=torch.float64, device=Xq.device)
+        else:
+            _vec(large, "large", torch.int32), _mat(score, "score")
+            assert large.numel() >= S * n_clusters and score.shape[0] >= S
+        assert sizes.numel() >= S * n_clusters
+        _lib.check(self.lib.vgan_cluster_final(_ptr(Xq), Xq.stride(0), nq, d, _ptr(feat), _ptr(feat_off), int(S), int(n_clusters),
+                                               _ptr(centers), _ptr(large), _ptr(sizes), int(bool(use_weights)), _ptr(label), _ptr(part),
+                                               _ptr(inertia), _ptr(score), _ptr(score_row), score.stride(0) if score is not None else 0,
+                                               self._stream()), "vgan_cluster_final")
+
 
 _default = None
 

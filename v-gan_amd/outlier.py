@@ -33,6 +33,11 @@ detector scores.  Non-finite scores (NaN input) leave the statistics unspecified
 All distance, selection and scoring work runs in libvgan_hip.so (csrc/outlier.hip); this module plans the work on the
 host (feature lists, chunks of subspaces under a workspace limit) and owns the device buffers.  The statistics, the
 transform and the combination run there too (csrc/outlier_norm.hip), on the score matrix the detectors left on the device.
+
+``SubspaceCBLOF`` is the cluster-based detector: k-means over all subspaces at once and the cluster-based local outlier
+factor on its clusters (csrc/cluster.hip); its contract (initial centres, the E and M steps and their precision, the stop
+rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.  It
+shares the tail above (normalize, combination, contamination, predict) with ``SubspaceEnsemble`` through one base class.
 """
 import math
 import os
@@ -213,7 +218,84 @@ def _device_matrix(X, d=None):
     return X.to(device="cuda", dtype=torch.float32).contiguous()
 
 
-class SubspaceEnsemble:
+class _SubspaceScorer:
+    """What every per-subspace detector of this module shares: the device copy of the subspace table, the packed blocks,
+    and the tail after the [S, n] score matrix (statistics, transform, combination, threshold, predict).  A subclass
+    sets plan, proba, normalize, combination and contamination, calls _attach() once the device may be touched, keeps
+    the reference rows in _X and publishes decision_scores_."""
+
+    _X = None
+    _stats = None  # float64 [2, S] on the device (centres, scales), set by fit when normalize is given
+    _decisions = None  # (threshold_, labels_), taken from decision_scores_ on first use
+    score_center_ = score_scale_ = None
+
+    def _attach(self):
+        self.ops = default_ops()
+        dev = "cuda"
+        self._table = (torch.as_tensor(self.plan.feat, device=dev), torch.as_tensor(self.plan.feat_off, device=dev),
+                       torch.as_tensor(self.plan.col_off, device=dev))
+        self._rows = torch.as_tensor(self.plan.order, device=dev)
+        self._proba = torch.as_tensor(self.proba, device=dev)
+
+    def _pack(self, X, first, count, gram, centred=None):
+        """(packed block, squared row norms or None) of the chunk; centred on the column mean for the Gram engine, and for
+        the exact engine too when centred is True (default: Gram only)."""
+        n = X.shape[0]
+        cols = int(self.plan.col_off[first + count] - self.plan.col_off[first])
+        packed = torch.empty(n * cols, dtype=torch.float32, device=X.device)
+        sq = torch.empty(count, n, dtype=torch.float32, device=X.device) if gram else None
+        centred = gram if centred is None else centred
+        self.ops.outlier_pack(X, self._center if centred else None, self._table, first, count, packed, sq)
+        return packed, sq
+
+    def _combine(self, per, fitting):
+        """float64 [n]: the ensemble score of the raw per-subspace scores per [S, n]; fit takes the statistics first."""
+        S, n = per.shape
+        if fitting and self.normalize is not None:
+            self._stats = torch.empty(2, S, dtype=torch.float64, device=per.device)
+            self.ops.outlier_score_stats(per, NORMALIZATIONS[self.normalize], self._stats[0], self._stats[1])
+        out = torch.empty(n, dtype=torch.float64, device=per.device)
+        if self.normalize is None and self.combination == "sum":
+            self.ops.outlier_combine(per, self._proba, out)
+        else:
+            center, scale = (None, None) if self.normalize is None else self._stats
+            self.ops.outlier_combine_normalized(per, center, scale, self._proba, COMBINATIONS[self.combination], out)
+        return out
+
+    def _decide(self):
+        if self._decisions is None:
+            threshold = decision_threshold(self.decision_scores_, self.contamination)
+            self._decisions = (threshold, (self.decision_scores_ > threshold).astype(int))
+        return self._decisions
+
+    @property
+    def threshold_(self):
+        """numpy.percentile(decision_scores_, 100 (1 - contamination)); taken on first use, so that a fit that never asks
+        for a decision does not pay for the percentile on the host."""
+        return self._decide()[0]
+
+    @property
+    def labels_(self):
+        """int [n]: 1 where decision_scores_ exceeds threshold_."""
+        return self._decide()[1]
+
+    def _require_fit(self):
+        if self._X is None:
+            raise RuntimeError(f"{type(self).__name__} is not fitted: call fit(X_train) first")
+
+    def predict(self, X):
+        """int [n]: 1 where decision_function(X) exceeds threshold_ (pyod's predict)."""
+        return (self.decision_function(X) > self.threshold_).astype(int)
+
+    def predict_proba(self, X, method="linear"):
+        """float64 [n, 2], column 1 the outlier probability: outlier_probability(decision_scores_, decision_function(X))."""
+        if method not in PROBA_METHODS:
+            raise ValueError(f"method must be 'linear' or 'unify', got {method!r}")
+        self._require_fit()
+        return outlier_probability(self.decision_scores_, self.decision_function(X), method)
+
+
+class SubspaceEnsemble(_SubspaceScorer):
     """kNN / LOF / KDE detector per subspace, probability-weighted sum of the scores (pyod-style: ``fit`` sets
     ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying).
 
@@ -256,26 +338,9 @@ class SubspaceEnsemble:
         self.method, self.knn_method, self.engine, self.splits = method, knn_method, engine, splits
         self.workspace_bytes = int(workspace_bytes)
         self.proba = p
-        self.ops = default_ops()
-        dev = "cuda"
-        self._table = (torch.as_tensor(self.plan.feat, device=dev), torch.as_tensor(self.plan.feat_off, device=dev),
-                       torch.as_tensor(self.plan.col_off, device=dev))
-        self._rows = torch.as_tensor(self.plan.order, device=dev)
-        self._proba = torch.as_tensor(p, device=dev)
-        self._X = None
-        self._stats = None  # float64 [2, S] on the device (centres, scales), set by fit when normalize is given
-        self._decisions = None  # (threshold_, labels_), taken from decision_scores_ on first use
-        self.score_center_ = self.score_scale_ = None
+        self._attach()
 
     # ---- pipeline --------------------------------------------------------------------------------
-    def _pack(self, X, first, count, gram):
-        n = X.shape[0]
-        cols = int(self.plan.col_off[first + count] - self.plan.col_off[first])
-        packed = torch.empty(n * cols, dtype=torch.float32, device=X.device)
-        sq = torch.empty(count, n, dtype=torch.float32, device=X.device) if gram else None
-        self.ops.outlier_pack(X, self._center if gram else None, self._table, first, count, packed, sq)
-        return packed, sq
-
     def _splits(self, nq, nr, count):
         if self.splits is not None:
             return int(self.splits)
@@ -325,20 +390,6 @@ class SubspaceEnsemble:
             del Pq, Pr, sqq, sqr
         return per
 
-    def _combine(self, per, fitting):
-        """float64 [n]: the ensemble score of the raw per-subspace scores per [S, n]; fit takes the statistics first."""
-        S, n = per.shape
-        if fitting and self.normalize is not None:
-            self._stats = torch.empty(2, S, dtype=torch.float64, device=per.device)
-            self.ops.outlier_score_stats(per, NORMALIZATIONS[self.normalize], self._stats[0], self._stats[1])
-        out = torch.empty(n, dtype=torch.float64, device=per.device)
-        if self.normalize is None and self.combination == "sum":
-            self.ops.outlier_combine(per, self._proba, out)
-        else:
-            center, scale = (None, None) if self.normalize is None else self._stats
-            self.ops.outlier_combine_normalized(per, center, scale, self._proba, COMBINATIONS[self.combination], out)
-        return out
-
     def _score(self, Xq, fitting):
         if self.method == "kde":
             per = self._density(Xq)
@@ -384,27 +435,6 @@ class SubspaceEnsemble:
         self._decisions = None
         return self
 
-    def _decide(self):
-        if self._decisions is None:
-            threshold = decision_threshold(self.decision_scores_, self.contamination)
-            self._decisions = (threshold, (self.decision_scores_ > threshold).astype(int))
-        return self._decisions
-
-    @property
-    def threshold_(self):
-        """numpy.percentile(decision_scores_, 100 (1 - contamination)); taken on first use, so that a fit that never asks
-        for a decision does not pay for the percentile on the host."""
-        return self._decide()[0]
-
-    @property
-    def labels_(self):
-        """int [n]: 1 where decision_scores_ exceeds threshold_."""
-        return self._decide()[1]
-
-    def _require_fit(self):
-        if self._X is None:
-            raise RuntimeError("SubspaceEnsemble is not fitted: call fit(X_train) first")
-
     def decision_function(self, X, return_per_subspace=False):
         """Ensemble scores of X against the fitted reference set (nothing excluded), float64 [n]; with
         return_per_subspace=True also the float32 [S, n] per-subspace scores (subspaces in the given order)."""
@@ -419,17 +449,6 @@ class SubspaceEnsemble:
             return scores.cpu().numpy(), per.cpu().numpy()
         return scores.cpu().numpy()
 
-    def predict(self, X):
-        """int [n]: 1 where decision_function(X) exceeds threshold_ (pyod's predict)."""
-        return (self.decision_function(X) > self.threshold_).astype(int)
-
-    def predict_proba(self, X, method="linear"):
-        """float64 [n, 2], column 1 the outlier probability: outlier_probability(decision_scores_, decision_function(X))."""
-        if method not in PROBA_METHODS:
-            raise ValueError(f"method must be 'linear' or 'unify', got {method!r}")
-        self._require_fit()
-        return outlier_probability(self.decision_scores_, self.decision_function(X), method)
-
     def kneighbors(self, X=None):
         """(dist float32 [S, n, k], idx int32 [S, n, k]) per subspace: the sorted neighbour lists of X, or of the reference
         set itself with self excluded (X=None)."""
@@ -443,3 +462,328 @@ class SubspaceEnsemble:
             rows = self._rows[first:first + count].long()
             D[rows], I[rows] = dist, idx
         return D.cpu().numpy(), I.cpu().numpy()
+
+
+# ---- k-means + CBLOF over the subspaces ----------------------------------------------------------------------------------
+MAX_CLUSTERS = 64  # VGAN_CLUSTER_MAX_CLUSTERS: the centres of a subspace are one reference tile of the distance engines
+# Lloyd iterations enqueued between two looks at the done flags.  An iteration after a subspace has finished costs its
+# launches an early return, a look costs a blocking copy: DESIGN.md section 9 has the measurement behind the value.
+POLL_STRIDE = 4
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _is_real(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def check_cblof_params(n_clusters, alpha, beta, max_iter, tol):
+    if not (_is_int(n_clusters) and 2 <= int(n_clusters) <= MAX_CLUSTERS):
+        raise ValueError(f"n_clusters must be an integer between 2 and {MAX_CLUSTERS}, got {n_clusters!r}")
+    if not (_is_real(alpha) and 0.5 < float(alpha) < 1.0):
+        raise ValueError(f"alpha must be a float in (0.5, 1), got {alpha!r}")
+    if not (_is_real(beta) and np.isfinite(beta) and float(beta) > 1.0):
+        raise ValueError(f"beta must be a finite float above 1, got {beta!r}")
+    if not (_is_int(max_iter) and int(max_iter) >= 1):
+        raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
+    if not (_is_real(tol) and np.isfinite(tol) and float(tol) >= 0.0):
+        raise ValueError(f"tol must be a finite float >= 0, got {tol!r}")
+    return int(n_clusters), float(alpha), float(beta), int(max_iter), float(tol)
+
+
+def _index_array(init):
+    """init as an integer array if it is one (an ndarray or nested lists of integers), else None."""
+    if isinstance(init, np.ndarray):
+        return init if init.dtype.kind in "iu" else None
+    if isinstance(init, (list, tuple)) and len(init) > 0:
+        try:
+            a = np.asarray(init)
+        except ValueError:  # ragged: a list of centre arrays of different widths
+            return None
+        return a if a.dtype.kind in "iu" else None
+    return None
+
+
+def check_kmeans_init(init, n_clusters, dims):
+    """init as the constructor can judge it, without the data: "random", an integer array of row indices [C] or [S, C]
+    (distinct within a subspace), or S float arrays [C, d_s] (dims: the d_s in the given subspace order).  Returns
+    "random", ("rows", int64 [S, C]) or ("centers", [float64 [C, d_s]])."""
+    S, C = len(dims), n_clusters
+    if isinstance(init, str):
+        if init != "random":
+            raise ValueError(f"init must be 'random', row indices or a list of centre arrays, got {init!r}")
+        return "random"
+    if _index_array(init) is not None:
+        idx = np.asarray(init, dtype=np.int64)
+        if idx.ndim == 1:
+            idx = np.broadcast_to(idx, (S, idx.shape[0]))
+        if idx.ndim != 2 or idx.shape != (S, C):
+            raise ValueError(f"init row indices must have shape ({C},) or ({S}, {C}), got {np.asarray(init).shape}")
+        if (idx < 0).any():
+            raise ValueError("init row indices must be >= 0")
+        if (np.diff(np.sort(idx, axis=1), axis=1) == 0).any():
+            raise ValueError("init row indices must be distinct within a subspace")
+        return "rows", np.ascontiguousarray(idx)
+    if isinstance(init, (list, tuple)) or (isinstance(init, np.ndarray) and init.dtype.kind == "f"):
+        arrays = [init] if isinstance(init, np.ndarray) and init.ndim == 2 else list(init)
+        if len(arrays) != S:
+            raise ValueError(f"init holds {len(arrays)} centre arrays for {S} subspaces")
+        out = []
+        for s, (a, ds) in enumerate(zip(arrays, dims)):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (C, int(ds)):
+                raise ValueError(f"init centres of subspace {s} must have shape ({C}, {int(ds)}), got {a.shape}")
+            if not np.isfinite(a).all():
+                raise ValueError(f"init centres of subspace {s} are not finite")
+            out.append(np.ascontiguousarray(a))
+        return "centers", out
+    raise ValueError(f"init must be 'random', row indices or a list of centre arrays, got {type(init).__name__}")
+
+
+def resolve_kmeans_rows(init, n, n_clusters, n_subspaces, seed):
+    """int64 [S, C]: the initial rows for n data rows; "random" draws C distinct rows once with
+    numpy.random.default_rng(seed) and uses them for every subspace."""
+    if n < n_clusters:
+        raise ValueError(f"fit needs at least n_clusters rows ({n_clusters}), got {n}")
+    if isinstance(init, str):
+        idx = np.random.default_rng(seed).choice(n, size=n_clusters, replace=False).astype(np.int64)
+        return np.broadcast_to(idx, (n_subspaces, n_clusters)).copy()
+    idx = init[1]
+    if (idx >= n).any():
+        raise ValueError(f"init row index {int(idx.max())} is out of range for {n} rows")
+    return idx
+
+
+def large_cluster_boundary(sizes, alpha, beta):
+    """pyod's _set_small_large_clusters on one size table [C]: (t, large bool [C]).  The clusters are ordered by (size
+    descending, index ascending); for i = 1 .. C-1, A_i: the first i sizes sum to >= alpha n; B_i: size_(i-1) / size_(i)
+    >= beta (a zero denominator counts as holding).  t is the first i with A_i and B_i, failing that the first with A_i,
+    failing that the first with B_i; the first t clusters are large.  Where pyod raises (no i at all) t = C: every
+    cluster is large."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    C = sizes.shape[0]
+    order = np.lexsort((np.arange(C), -sizes))
+    sz = sizes[order]
+    n = int(sz.sum())
+    i = np.arange(1, C)
+    A = np.cumsum(sz)[:-1] >= alpha * n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        B = np.where(sz[1:] == 0, True, sz[:-1] / np.where(sz[1:] == 0, 1, sz[1:]) >= beta)
+    t = C
+    for cond in (A & B, A, B):
+        if cond.any():
+            t = int(i[np.argmax(cond)])
+            break
+    large = np.zeros(C, dtype=bool)
+    large[order[:t]] = True
+    return t, large
+
+
+class SubspaceCBLOF(_SubspaceScorer):
+    """Cluster-based local outlier factor per subspace (He, Xu, Deng 2003; pyod's CBLOF over k-means), combined like the
+    detectors of SubspaceEnsemble: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows.
+
+    Per subspace s (features F_s, raw values, squared Euclidean distance), C = n_clusters (2 .. 64):
+
+    k-means (Lloyd).  init "random": C distinct rows drawn once with numpy.random.default_rng(seed), the same rows for
+    every subspace; or row indices [C] / [S, C]; or S float arrays [C, d_s] (given subspace order).  No k-means++, no
+    restarts.  E step: every row takes the centre with the smallest (d2, centre index), d2 from the subspace's float32
+    distance engine (exact below GRAM_MIN_DIMS, Gram above, as for kNN; here the operands of both engines are centred on
+    the column mean, so that rounding a centre to float32 costs no more than rounding a data row).  M step:
+    every centre becomes the mean of its rows, accumulated in float64 from the float32 data; the float64 centre is the
+    master copy and the engines' float32 image is derived from it after every update.  A cluster that received no row
+    keeps its centre (sklearn relocates it to a far row instead; the two differ whenever a cluster empties).  A
+    subspace stops when an E step changes no label (``converged_[s]`` True; no M step follows), or when the summed
+    squared centre shift of an M step is <= tol x the mean population variance of its features (sklearn's rule; tol=0
+    disables it; ``converged_[s]`` stays False), or after max_iter M steps.  ``n_iter_[s]`` counts the M steps.  After
+    the loop one assignment in float64 from the raw rows and the float64 centres gives ``cluster_labels_`` (the exactly
+    nearest centre of ``cluster_centers_`` by (d2, index)), ``inertia_`` (the float64 sum of those d2) and
+    ``cluster_sizes_``; the float32 engines serve only the iterations.
+
+    Large and small clusters: large_cluster_boundary (pyod's rule, alpha in (0.5, 1), beta > 1) on every subspace's size
+    table -> ``large_cluster_mask_``.  Where pyod raises "could not form valid cluster separation" every cluster of that
+    subspace counts as large: one odd subspace out of hundreds does not fail the ensemble.
+
+    Score: the float64 distance of a row to its nearest centre if that cluster is large, otherwise to the nearest large
+    centre; times the size of the row's cluster with use_weights.  The score matrix is float32 [S, n], and normalize /
+    combination / contamination / ``threshold_`` / ``labels_`` (outlier labels, pyod's meaning) / ``predict`` /
+    ``predict_proba`` / return_per_subspace are those of SubspaceEnsemble.  ``fit`` scores the training rows with nothing
+    excluded: ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.
+
+    No float atomics: the centre sums run over a fixed partition of the rows (slices by n; inside a slice, row groups
+    by n_clusters and d_s), never by the chunk, so labels, centres, ``n_iter_`` and scores are bit-identical from run to
+    run and for every workspace_bytes; they may differ between the two engines.  All of it runs in libvgan_hip.so
+    (csrc/cluster.hip).  workspace_bytes limits the packed blocks of a chunk as in SubspaceEnsemble; the chunk's
+    iteration labels (int32 [count, n]) and the slice partials of the centre sums (float64, ceil(n / 1024) x n_clusters
+    x (sum of d_s + count)) come on top of it.
+
+    Two attributes, set after construction, serve tests and measurements and change no result: ``poll_stride`` (Lloyd
+    iterations enqueued between two looks at the done flags, default POLL_STRIDE) and ``keep_iteration_labels`` (True:
+    ``fit`` also publishes ``last_iteration_labels_``, int32 [S, n], the labels of the last E step, which the float32
+    engines took, as opposed to the float64 ``cluster_labels_``)."""
+
+    def __init__(self, subspaces, proba, n_clusters=8, alpha=0.9, beta=5.0, use_weights=False, init="random", max_iter=300,
+                 tol=1e-4, seed=0, engine="auto", workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum",
+                 contamination=0.1):
+        self.n_clusters, self.alpha, self.beta, self.max_iter, self.tol = check_cblof_params(n_clusters, alpha, beta, max_iter, tol)
+        self.normalize = check_normalize(normalize)
+        self.combination = check_combination(combination)
+        self.contamination = check_contamination(contamination)
+        if engine == "auto":
+            engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
+        self.plan = SubspacePlan(subspaces, engine=engine)
+        p = np.asarray(proba, dtype=np.float64).reshape(-1)
+        if p.shape[0] != self.plan.count:
+            raise ValueError(f"proba has {p.shape[0]} entries for {self.plan.count} subspaces")
+        self._given = np.argsort(self.plan.order)  # given subspace index -> processing position
+        self.init = check_kmeans_init(init, self.n_clusters, self.plan.dims[self._given])
+        self.use_weights, self.seed, self.engine = bool(use_weights), seed, engine
+        self.workspace_bytes = int(workspace_bytes)
+        self.poll_stride = POLL_STRIDE
+        self.keep_iteration_labels = False
+        self.proba = p
+        self._attached = False
+
+    # ---- pipeline --------------------------------------------------------------------------------
+    def _initial_centers(self, X, n):
+        """float64 centres of every subspace in processing order, concatenated ([C, d_s] blocks)."""
+        feats = [self.plan.feat[self.plan.feat_off[z]:self.plan.feat_off[z + 1]] for z in range(self.plan.count)]
+        if isinstance(self.init, tuple) and self.init[0] == "centers":
+            return np.concatenate([self.init[1][s].reshape(-1) for s in self.plan.order])
+        idx = resolve_kmeans_rows(self.init, n, self.n_clusters, self.plan.count, self.seed)
+        uniq, inv = np.unique(idx, return_inverse=True)
+        rows = X[torch.as_tensor(uniq, device=X.device)].cpu().numpy().astype(np.float64)
+        inv = inv.reshape(idx.shape)
+        return np.concatenate([rows[inv[s]][:, feats[z]].reshape(-1) for z, s in enumerate(self.plan.order)])
+
+    def _tolerance(self, X):
+        """float64 [S], processing order: tol x the mean over F_s of the population variance of the feature (float64 numpy
+        on a host copy of X, once per fit; tol = 0 skips it)."""
+        S = self.plan.count
+        if self.tol == 0.0:
+            return np.zeros(S)
+        host = X.cpu().numpy()
+        var = np.concatenate([host[:, c:c + 64].astype(np.float64).var(axis=0) for c in range(0, host.shape[1], 64)])
+        return np.array([self.tol * var[self.plan.feat[self.plan.feat_off[z]:self.plan.feat_off[z + 1]]].mean() for z in range(S)])
+
+    def _lloyd(self, X):
+        """Chunks outermost, iterations inside: a chunk is packed once.  The host enqueues poll_stride iterations at a
+        time and then reads the chunk's done flags through one pinned buffer."""
+        n, S, C, dev = X.shape[0], self.plan.count, self.n_clusters, X.device
+        self._changed = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._done = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._iters = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._iteration_labels = torch.empty(S, n, dtype=torch.int32, device=dev) if self.keep_iteration_labels else None
+        flags = torch.empty(S, dtype=torch.int32).pin_memory()
+        stream = torch.cuda.current_stream()
+        for first, count, gram in self.plan.chunks(n, self.workspace_bytes):
+            # both engines get operands centred on the column mean here: a centre is a float64 mean, and rounding it to
+            # float32 about the mean instead of about 0 keeps that rounding small on data with a large offset
+            cols = int(self.plan.col_off[first + count] - self.plan.col_off[first])
+            dims = self.plan.dims[first:first + count]
+            Pq, sqq = self._pack(X, first, count, gram, centred=True)
+            img = torch.empty(C * cols, dtype=torch.float32, device=dev)
+            img_sq = torch.empty(count, C, dtype=torch.float32, device=dev) if gram else None
+            center = self._center
+            self.ops.cluster_image(self._centers, C, self._table, first, count, center, img, img_sq)
+            label = torch.full((count, n), -1, dtype=torch.int32, device=dev)
+            ws = torch.empty(self.ops.cluster_lloyd_ws_bytes(n, C, count, int(dims.sum())) // 8, dtype=torch.float64, device=dev)
+            launched = 0
+            while launched < self.max_iter:
+                it = min(max(1, int(self.poll_stride)), self.max_iter - launched)
+                self.ops.cluster_lloyd(Pq, sqq, X, self._table, first, count, int(dims.sum()), int(dims.max()), C,
+                                       ENGINES["gram" if gram else "exact"], center, self._tol_var, self._centers, img, img_sq,
+                                       label, self._changed, self._done, self._iters, ws, it)
+                launched += it
+                flags[:count].copy_(self._done[first:first + count], non_blocking=True)
+                stream.synchronize()
+                if bool((flags[:count] != 0).all()):
+                    break
+            if self.keep_iteration_labels:
+                self._iteration_labels[first:first + count] = label
+            del Pq, sqq, img, img_sq, label, ws
+
+    def _final(self, X, want_labels=False):
+        """(per float32 [S, n] in the given order, labels int32 [S, n] in processing order or None) of X against the fitted
+        centres, float64."""
+        S, C, nq = self.plan.count, self.n_clusters, X.shape[0]
+        label = torch.empty(S, nq, dtype=torch.int32, device=X.device) if want_labels else None
+        per = torch.empty(S, nq, dtype=torch.float32, device=X.device)
+        self.ops.cluster_final(X, self._table, S, C, self._centers, self._sizes, large=self._large, use_weights=self.use_weights,
+                               label=label, score=per, score_row=self._rows)
+        return per, label
+
+    def _require_fit(self):  # the centres, sizes and the large-cluster mask are the fitted state: X itself is not kept
+        if getattr(self, "_large", None) is None:
+            raise RuntimeError(f"{type(self).__name__} is not fitted: call fit(X_train) first")
+
+    # ---- public surface --------------------------------------------------------------------------
+    def fit(self, X, y=None):
+        """k-means per subspace on X, then the CBLOF scores of X itself: decision_scores_ (float64 [n]),
+        per_subspace_scores_, cluster_centers_, cluster_labels_, cluster_sizes_, large_cluster_mask_, n_iter_,
+        converged_, inertia_, all in the given subspace order."""
+        shape = tuple(X.shape) if hasattr(X, "shape") else np.asarray(X).shape
+        if len(shape) != 2:
+            raise ValueError(f"X must be a 2-d matrix, got shape {shape}")
+        if shape[1] != self.plan.d:
+            raise ValueError(f"X has {shape[1]} features, the subspaces {self.plan.d}")
+        if not isinstance(self.init, tuple) or self.init[0] == "rows":
+            resolve_kmeans_rows(self.init, shape[0], self.n_clusters, self.plan.count, self.seed)  # the checks, before the device
+        elif shape[0] < self.n_clusters:
+            raise ValueError(f"fit needs at least n_clusters rows ({self.n_clusters}), got {shape[0]}")
+        if not self._attached:
+            self._attach()
+            self._attached = True
+        X = _device_matrix(X, self.plan.d)
+        n, S, C, dev = X.shape[0], self.plan.count, self.n_clusters, X.device
+        self._center = torch.empty(X.shape[1], dtype=torch.float32, device=dev)
+        self.ops.col_mean(X, self._center)
+        self._centers = torch.as_tensor(self._initial_centers(X, n), device=dev)
+        self._tol_var = torch.as_tensor(self._tolerance(X), device=dev)
+        self._lloyd(X)
+        # final float64 assignment, the host boundary step, the scores
+        self._sizes = torch.zeros(S, C, dtype=torch.int64, device=dev)
+        labels = torch.empty(S, n, dtype=torch.int32, device=dev)
+        inertia = torch.empty(S, dtype=torch.float64, device=dev)
+        self.ops.cluster_final(X, self._table, S, C, self._centers, self._sizes, label=labels, inertia=inertia)
+        sizes = self._sizes.cpu().numpy()
+        large = np.stack([large_cluster_boundary(sizes[z], self.alpha, self.beta)[1] for z in range(S)])
+        self._large = torch.as_tensor(large.astype(np.int32), device=dev)
+        per, _ = self._final(X)
+        scores = self._combine(per, fitting=True)
+        g = self._given
+        flat, off = self._centers.cpu().numpy(), C * self.plan.feat_off.astype(np.int64)
+        self.cluster_centers_ = [flat[off[z]:off[z + 1]].reshape(C, -1).copy() for z in g]
+        self.cluster_labels_ = labels.cpu().numpy()[g]
+        self.cluster_sizes_ = sizes[g]
+        self.large_cluster_mask_ = large[g]
+        self.n_iter_ = self._iters.cpu().numpy()[g].astype(np.int64)
+        self.converged_ = self._done.cpu().numpy()[g] == 1
+        self.inertia_ = inertia.cpu().numpy()[g]
+        if self.keep_iteration_labels:
+            self.last_iteration_labels_ = self._iteration_labels.cpu().numpy()[g]
+            self._iteration_labels = None
+        self.decision_scores_ = scores.cpu().numpy()
+        self.per_subspace_scores_ = per.cpu().numpy()
+        if self.normalize is not None:
+            self.score_center_, self.score_scale_ = self._stats.cpu().numpy()
+        self._decisions = None
+        return self
+
+    def decision_function(self, X, return_per_subspace=False):
+        """Ensemble scores of X against the fitted clusters, float64 [n]; with return_per_subspace=True also the float32
+        [S, n] per-subspace CBLOF scores (subspaces in the given order)."""
+        self._require_fit()
+        per, _ = self._final(_device_matrix(X, self.plan.d))
+        scores = self._combine(per, fitting=False)
+        if return_per_subspace:
+            return scores.cpu().numpy(), per.cpu().numpy()
+        return scores.cpu().numpy()
+
+    def predict_clusters(self, X):
+        """int32 [S, n]: the nearest fitted centre of every row of X in every subspace (float64, (d2, index) order)."""
+        self._require_fit()
+        _, label = self._final(_device_matrix(X, self.plan.d), want_labels=True)
+        return label.cpu().numpy()[self._given]

@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import SubspaceEnsemble
+from .outlier import SubspaceCBLOF, SubspaceEnsemble
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -175,10 +175,17 @@ class _RunFolder:
         if they are set, otherwise approx_subspace_dist(subspace_count) first.  Fitted on X when X is given.  method is
         "knn", "lof" or "kde"; further keywords (knn_method, bandwidth, engine, splits, workspace_bytes, normalize,
         combination, contamination) go to SubspaceEnsemble, e.g. outlier_ensemble(method="kde", bandwidth="scott", X=X) or
-        outlier_ensemble(method="knn", normalize="robust", combination="max", contamination=0.05, X=X)."""
+        outlier_ensemble(method="knn", normalize="robust", combination="max", contamination=0.05, X=X).
+        method "cblof" builds a SubspaceCBLOF instead (k-means per subspace and the cluster-based local outlier factor):
+        its keywords are n_clusters, alpha, beta, use_weights, init, max_iter, tol, seed, engine, workspace_bytes and the
+        same normalize / combination / contamination, e.g. outlier_ensemble(method="cblof", n_clusters=8, X=X);
+        n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
-        ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
+        if method == "cblof":
+            ens = SubspaceCBLOF(self.subspaces, self.proba, **kw)
+        else:
+            ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
 
     def check_if_myopic(self, x_data, bandwidth=0.01, count=500, n_permutations=1000):
