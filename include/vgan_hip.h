@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 10
+#define VGAN_ABI_VERSION 11
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -583,6 +583,19 @@ int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out,
  * vgan_outlier_combine_normalized: with t_s(x) = (double(x) - center[s]) / scale[s] (center and scale both NULL: t_s(x) =
  *   double(x)), out[i] = sum_s weights[s] * t_s(score[s, i]) (VGAN_OUTLIER_COMBINE_SUM, s = 0 .. S-1 in that order) or
  *   max_s t_s(score[s, i]) (VGAN_OUTLIER_COMBINE_MAX; weights unused, may be NULL), float64.
+ * vgan_outlier_abod: angle-based outlier scores (FastABOD: Kriegel, Schubert, Zimek 2008; pyod's ABOD, method="fast") from
+ *   the refined lists idx [count, nq, k] of vgan_outlier_refine and the raw rows Xq [nq, d] (ldq) / Xr [nr, d] (ldr).  For
+ *   chunk subspace s, query row q and each listed reference row a: v_a = Xr[a, F_s] - Xq[q, F_s] in float64 (exact), n_a =
+ *   |v_a|^2; a is usable if n_a > 0 (an entry outside [0, nr) is not).  Over the unordered pairs of usable neighbours,
+ *   w_ab = <v_a, v_b> / (n_a n_b), and score[row, q] = -var(w): the population variance, two passes (mean, then mean
+ *   squared deviation) in float64 in a fixed order, stored as float32 (row and ld_score as for vgan_outlier_score); a
+ *   result below the float32 range is stored as -FLT_MAX.  One pair gives 0.  A row with fewer than two usable
+ *   neighbours is DEGENERATE and its score is stored as NaN, for vgan_outlier_abod_floor.  The lists decide the bits:
+ *   the same lists give the same scores in every run and for every chunking.  2 <= k <= VGAN_OUTLIER_MAX_K, nr >= k.
+ * vgan_outlier_abod_floor: on the finished score matrix [S, ld] (n scores a row), row by row.  fit != 0: score_floor[s]
+ *   (float64 [S]) = the smallest score of row s that is not NaN, 0 if every score is NaN; n_degenerate[s] (int32 [S]) =
+ *   the number of NaN scores.  fit == 0: score_floor is read, n_degenerate is not touched (may be NULL).  Then every NaN
+ *   of row s becomes (float)score_floor[s].  The call knows no subspace table: row s is whatever the caller stored there.
  * ------------------------------------------------------------------------------------------- */
 #define VGAN_OUTLIER_MAX_K 32
 #define VGAN_OUTLIER_ENGINE_EXACT 0
@@ -611,6 +624,11 @@ int vgan_outlier_kde(const float* Pq, const float* sq_q, int nq, const float* Pr
                      const int32_t* score_row, int ld_score, vgan_stream_t stream);
 int vgan_outlier_combine(const float* score, int ld, int S, int n, const double* weights, double* out,
                          vgan_stream_t stream);
+int vgan_outlier_abod(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
+                      const int32_t* feat_off, int first, int count, const int32_t* idx, int k, float* score,
+                      const int32_t* score_row, int ld_score, vgan_stream_t stream);
+int vgan_outlier_abod_floor(float* score, int ld, int S, int n, int fit, double* score_floor, int32_t* n_degenerate,
+                            vgan_stream_t stream);
 #define VGAN_OUTLIER_NORM_ZSCORE 1
 #define VGAN_OUTLIER_NORM_ROBUST 2
 #define VGAN_OUTLIER_NORM_MINMAX 3

@@ -12,6 +12,13 @@ difference of the two paths' ensemble scores.
     torch.cdist + argmin + index_add_ on the GPU with the float64 score tail in torch, (b) sklearn's KMeans (lloyd, same
     init and iteration count) on the CPUs for a sample of the subspaces, scaled to all of them; and the E step composed
     from vgan_outlier_knn with k = 1 over the centres against one whole iteration (assign + update) on the same operands.
+  --method abod: angle-based scores (vgan_amd.SubspaceABOD) at k = 10 and 32: (a) its fit against the kNN fit with the same
+    k on the same subspaces (the difference is what ABOD adds to the neighbour search); (b) the ABOD launches alone on
+    the resident neighbour lists against a torch baseline handed the same lists (gather, float64 bmm, masked two-pass
+    variance), with the largest relative score difference of the two; (c) the gather bandwidth and the float64
+    multiply-add rate of (b) from n sum_s k d_s 4 B and n sum_s k^2 d_s multiply-adds (the kernel pads k to 8, 16 or 32
+    and forms the whole k x k matrix: the executed count is given as well).  --no-baselines leaves the torch path out
+    (for a run under a profiler), --shape d,n,S picks one shape.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -233,6 +240,75 @@ def run_cblof(d, n, count, C, reps, iters, baselines=True, sklearn_sample=20):
     return row
 
 
+def baseline_abod(X, feats, idx, block=8192):
+    """torch on the same GPU from the same neighbour lists idx [n, k] of one subspace: float64 [n], NaN without a pair."""
+    n, k = idx.shape
+    Xs = X[:, feats].double()
+    out = torch.empty(n, dtype=torch.float64, device=X.device)
+    upper = torch.triu(torch.ones(k, k, dtype=torch.bool, device=X.device), diagonal=1)
+    for q0 in range(0, n, block):
+        V = Xs[idx[q0:q0 + block].long()] - Xs[q0:q0 + block, None, :]
+        G = torch.bmm(V, V.transpose(1, 2))
+        n2 = torch.diagonal(G, dim1=1, dim2=2)
+        use = (n2 > 0)[:, :, None] & (n2 > 0)[:, None, :] & upper
+        W = torch.where(use, G / (n2[:, :, None] * n2[:, None, :]), torch.zeros_like(G))
+        cnt = use.sum(dim=(1, 2)).double()
+        mean = W.sum(dim=(1, 2)) / cnt
+        dev = torch.where(use, (W - mean[:, None, None]) ** 2, torch.zeros_like(G))
+        out[q0:q0 + block] = -(dev.sum(dim=(1, 2)) / cnt)
+    return out
+
+
+def run_abod(d, n, count, k, reps, baselines=True):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    abod = vgan_amd.SubspaceABOD(m, p, n_neighbors=k)
+    knn = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=k)
+    t_abod, ta = timed(lambda: abod.fit(Xd), reps)
+    t_knn, tk = timed(lambda: knn.fit(Xd), reps)
+    # the launches alone, on the resident lists of the fit
+    lists = [(first, cnt, idx) for first, cnt, idx, _ in abod._neighbors(None)]
+    per = torch.empty(S, n, dtype=torch.float32, device="cuda")
+
+    def launches():
+        for first, cnt, idx in lists:
+            abod.ops.outlier_abod(Xd, Xd, abod._table, first, cnt, idx, k, per, abod._rows[first:first + cnt])
+
+    t_launch, tl = timed(launches, max(reps, 5))
+    kp = 8 if k <= 8 else 16 if k <= 16 else 32
+    gather_bytes = 4.0 * n * k * float(dims.sum())
+    row = {"method": "abod", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "k": k,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "abod_fit_s": round(t_abod, 5), "abod_fit_reps_s": ta, "knn_fit_s": round(t_knn, 5), "knn_fit_reps_s": tk,
+           "abod_added_s": round(t_abod - t_knn, 5), "abod_over_knn": round(t_abod / t_knn, 3),
+           "abod_launch_s": round(t_launch, 6), "abod_launch_reps_s": tl, "n_degenerate": int(abod.n_degenerate_.sum()),
+           "gather_bytes": gather_bytes, "gather_GBps": round(gather_bytes / t_launch / 1e9, 1),
+           "fp64_fma_nominal": float(n) * k * k * float(dims.sum()),
+           "fp64_fma_nominal_per_s": round(float(n) * k * k * float(dims.sum()) / t_launch / 1e12, 3),
+           "fp64_fma_executed_per_s": round(float(n) * kp * kp * float(dims.sum()) / t_launch / 1e12, 3)}
+    if baselines:
+        order = abod.plan.order
+        feats = [torch.as_tensor(np.flatnonzero(m[s]), device="cuda") for s in range(S)]
+        want = torch.empty(S, n, dtype=torch.float64, device="cuda")
+
+        def torch_path():
+            for first, cnt, idx in lists:
+                for z in range(cnt):
+                    s = int(order[first + z])
+                    want[s] = baseline_abod(Xd, feats[s], idx[z])
+
+        t_base, tb = timed(torch_path, reps)
+        launches()
+        got, ref = per.double(), want
+        ok = ~torch.isnan(ref)
+        rel = (got[ok] - ref[ok]).abs() / ref[ok].abs().clamp(min=1e-300)
+        row.update({"torch_s": round(t_base, 5), "torch_reps_s": tb, "launch_speedup_vs_torch": round(t_base / t_launch, 2),
+                    "max_rel_diff_vs_torch": float(rel.max()) if rel.numel() else 0.0,
+                    "nan_rows_agree": bool((torch.isnan(per) == torch.isnan(ref)).all())})
+    return row
+
+
 def host_normalized(per, proba, mode):
     """The numpy alternative to csrc/outlier_norm.hip: float64 statistics per row of per [S, n], transform, weighted sum."""
     x = per.astype(np.float64)
@@ -330,12 +406,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
+    ap.add_argument("--shape", help="abod: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -361,6 +438,16 @@ def main():
         for d, n, count in shapes:
             for C in (8, 64):
                 out["configs"].append(run_cblof(d, n, count, C, args.reps, args.iters, baselines=not args.no_baselines))
+                print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "abod":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            for k in (10, 32):
+                out["configs"].append(run_abod(d, n, count, k, args.reps, baselines=not args.no_baselines))
                 print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     for d, n, count, k, with_base in configs:

@@ -120,6 +120,8 @@ SIGNATURES = {
     "vgan_outlier_score": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p]),
     "vgan_outlier_kde": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "vgan_outlier_combine": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "vgan_outlier_abod": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _i, _p]),
+    "vgan_outlier_abod_floor": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "vgan_outlier_score_stats_ws_bytes": (_i64, [_i, _i, _i]),
     "vgan_outlier_score_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
     "vgan_outlier_combine_normalized": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
@@ -130,7 +132,7 @@ SIGNATURES = {
     "vgan_cluster_final": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
 }
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 _lib = None
 
 

@@ -643,6 +643,27 @@ class HipOps:
         _lib.check(self.lib.vgan_outlier_combine(_ptr(score), score.stride(0), S, n, _ptr(weights), _ptr(out), self._stream()),
                    "vgan_outlier_combine")
 
+    def outlier_abod(self, Xq, Xr, table, first, count, idx, k, score, score_row=None):
+        """FastABOD scores of the refined lists idx [count, nq, k] into rows score_row of score; NaN marks a degenerate row."""
+        _mat(Xq, "Xq"), _mat(Xr, "Xr"), _vec(idx, "idx", torch.int32), _mat(score, "score")
+        feat, feat_off, _ = table
+        assert Xq.shape[1] == Xr.shape[1] and idx.numel() >= count * Xq.shape[0] * k
+        _lib.check(self.lib.vgan_outlier_abod(_ptr(Xq), Xq.stride(0), Xq.shape[0], _ptr(Xr), Xr.stride(0), Xr.shape[0], Xq.shape[1],
+                                              _ptr(feat), _ptr(feat_off), int(first), int(count), _ptr(idx), int(k), _ptr(score),
+                                              _ptr(score_row), score.stride(0), self._stream()), "vgan_outlier_abod")
+
+    def outlier_abod_floor(self, score, score_floor, n_degenerate=None):
+        """n_degenerate given (fit): score_floor [S] and n_degenerate [S] are taken from score [S, n]; otherwise score_floor
+        is applied as stored.  Either way the NaN scores of row s become score_floor[s]."""
+        _mat(score, "score"), _vec(score_floor, "score_floor", torch.float64)
+        S, n = score.shape
+        assert score_floor.numel() >= S
+        if n_degenerate is not None:
+            _vec(n_degenerate, "n_degenerate", torch.int32)
+            assert n_degenerate.numel() >= S
+        _lib.check(self.lib.vgan_outlier_abod_floor(_ptr(score), score.stride(0), S, n, int(n_degenerate is not None),
+                                                    _ptr(score_floor), _ptr(n_degenerate), self._stream()), "vgan_outlier_abod_floor")
+
     def outlier_score_stats(self, score, mode, center, scale):
         """center / scale (float64 [S]) of the rows of score [S, n]; mode is a VGAN_OUTLIER_NORM_* value."""
         _mat(score, "score"), _vec(center, "center", torch.float64), _vec(scale, "scale", torch.float64)

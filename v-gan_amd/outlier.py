@@ -34,10 +34,14 @@ All distance, selection and scoring work runs in libvgan_hip.so (csrc/outlier.hi
 host (feature lists, chunks of subspaces under a workspace limit) and owns the device buffers.  The statistics, the
 transform and the combination run there too (csrc/outlier_norm.hip), on the score matrix the detectors left on the device.
 
+``SubspaceABOD`` is the angle-based detector (FastABOD): it takes the neighbour lists above and scores a row by the variance
+of the distance-weighted angles under which it sees pairs of its neighbours (csrc/outlier_abod.hip); its contract (usable
+neighbours, the two-pass variance, the floor that degenerate rows take) is that class's docstring.
+
 ``SubspaceCBLOF`` is the cluster-based detector: k-means over all subspaces at once and the cluster-based local outlier
 factor on its clusters (csrc/cluster.hip); its contract (initial centres, the E and M steps and their precision, the stop
-rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.  It
-shares the tail above (normalize, combination, contamination, predict) with ``SubspaceEnsemble`` through one base class.
+rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.  Both
+share the tail above (normalize, combination, contamination, predict) with ``SubspaceEnsemble`` through one base class.
 """
 import math
 import os
@@ -295,7 +299,58 @@ class _SubspaceScorer:
         return outlier_probability(self.decision_scores_, self.decision_function(X), method)
 
 
-class SubspaceEnsemble(_SubspaceScorer):
+class _NeighborScorer(_SubspaceScorer):
+    """The neighbour pipeline (pack -> knn -> refine) of the detectors that score a row from its k nearest reference rows:
+    a subclass sets n_neighbors, splits and workspace_bytes, and keeps the reference rows in _X and their column mean in
+    _center."""
+
+    def _splits(self, nq, nr, count):
+        if self.splits is not None:
+            return int(self.splits)
+        blocks = -(-nq // 64) * count
+        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
+
+    def _neighbors(self, Xq, kdist=None):
+        """Yields (first, count, idx, dist) per chunk: the sorted refined lists [count, nq, k] of Xq (None: the reference
+        set, self excluded).  kdist (fit only): [S, n] receives the k-th distances in processing order."""
+        k, Xr = self.n_neighbors, self._X
+        nr = Xr.shape[0]
+        nq = nr if Xq is None else Xq.shape[0]
+        rows = nr if Xq is None else nr + nq
+        for first, count, gram in self.plan.chunks(rows, self.workspace_bytes):
+            Pr, sqr = self._pack(Xr, first, count, gram)
+            Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
+            J = self._splits(nq, nr, count)
+            nbr = torch.empty(count, nq, k, dtype=torch.int32, device=Xr.device)
+            part_d = part_i = None
+            if J > 1:
+                part_d = torch.empty(count * J * nq * k, dtype=torch.float32, device=Xr.device)
+                part_i = torch.empty(count * J * nq * k, dtype=torch.int32, device=Xr.device)
+            self.ops.outlier_knn(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, k, Xq is None, ENGINES["gram" if gram else "exact"],
+                                 J, nbr, part_d, part_i)
+            del Pq, Pr, sqq, sqr, part_d, part_i
+            idx = torch.empty_like(nbr)
+            dist = torch.empty(count, nq, k, dtype=torch.float32, device=Xr.device)
+            self.ops.outlier_refine(Xr if Xq is None else Xq, Xr, self._table, first, count, nbr, k, idx, dist,
+                                    None if kdist is None else kdist[first:first + count])
+            yield first, count, idx, dist
+
+    def kneighbors(self, X=None):
+        """(dist float32 [S, n, k], idx int32 [S, n, k]) per subspace: the sorted neighbour lists of X, or of the reference
+        set itself with self excluded (X=None)."""
+        self._require_fit()
+        Xq = None if X is None else _device_matrix(X, self.plan.d)
+        nq = self._X.shape[0] if Xq is None else Xq.shape[0]
+        k = self.n_neighbors
+        D = torch.empty(self.plan.count, nq, k, dtype=torch.float32, device=self._X.device)
+        I = torch.empty(self.plan.count, nq, k, dtype=torch.int32, device=self._X.device)
+        for first, count, idx, dist in self._neighbors(Xq):
+            rows = self._rows[first:first + count].long()
+            D[rows], I[rows] = dist, idx
+        return D.cpu().numpy(), I.cpu().numpy()
+
+
+class SubspaceEnsemble(_NeighborScorer):
     """kNN / LOF / KDE detector per subspace, probability-weighted sum of the scores (pyod-style: ``fit`` sets
     ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying).
 
@@ -341,37 +396,6 @@ class SubspaceEnsemble(_SubspaceScorer):
         self._attach()
 
     # ---- pipeline --------------------------------------------------------------------------------
-    def _splits(self, nq, nr, count):
-        if self.splits is not None:
-            return int(self.splits)
-        blocks = -(-nq // 64) * count
-        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
-
-    def _neighbors(self, Xq, kdist=None):
-        """Yields (first, count, idx, dist) per chunk: the sorted refined lists [count, nq, k] of Xq (None: the reference
-        set, self excluded).  kdist (fit only): [S, n] receives the k-th distances in processing order."""
-        k, Xr = self.n_neighbors, self._X
-        nr = Xr.shape[0]
-        nq = nr if Xq is None else Xq.shape[0]
-        rows = nr if Xq is None else nr + nq
-        for first, count, gram in self.plan.chunks(rows, self.workspace_bytes):
-            Pr, sqr = self._pack(Xr, first, count, gram)
-            Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
-            J = self._splits(nq, nr, count)
-            nbr = torch.empty(count, nq, k, dtype=torch.int32, device=Xr.device)
-            part_d = part_i = None
-            if J > 1:
-                part_d = torch.empty(count * J * nq * k, dtype=torch.float32, device=Xr.device)
-                part_i = torch.empty(count * J * nq * k, dtype=torch.int32, device=Xr.device)
-            self.ops.outlier_knn(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, k, Xq is None, ENGINES["gram" if gram else "exact"],
-                                 J, nbr, part_d, part_i)
-            del Pq, Pr, sqq, sqr, part_d, part_i
-            idx = torch.empty_like(nbr)
-            dist = torch.empty(count, nq, k, dtype=torch.float32, device=Xr.device)
-            self.ops.outlier_refine(Xr if Xq is None else Xq, Xr, self._table, first, count, nbr, k, idx, dist,
-                                    None if kdist is None else kdist[first:first + count])
-            yield first, count, idx, dist
-
     def _density(self, Xq):
         """float32 [S, nq]: -log p_s of Xq (None: the reference set, leave-one-out), rows in the given subspace order."""
         Xr = self._X
@@ -449,19 +473,128 @@ class SubspaceEnsemble(_SubspaceScorer):
             return scores.cpu().numpy(), per.cpu().numpy()
         return scores.cpu().numpy()
 
-    def kneighbors(self, X=None):
-        """(dist float32 [S, n, k], idx int32 [S, n, k]) per subspace: the sorted neighbour lists of X, or of the reference
-        set itself with self excluded (X=None)."""
-        self._require_fit()
-        Xq = None if X is None else _device_matrix(X, self.plan.d)
+
+# ---- angle-based scores (FastABOD) over the subspaces ----------------------------------------------------------------------
+ABOD_MIN_NEIGHBORS = 2  # one pair
+
+
+def check_abod_neighbors(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not ABOD_MIN_NEIGHBORS <= int(k) <= MAX_NEIGHBORS:
+        raise ValueError(f"n_neighbors must be an integer between {ABOD_MIN_NEIGHBORS} and {MAX_NEIGHBORS}, got {k!r}")
+    return int(k)
+
+
+class SubspaceABOD(_NeighborScorer):
+    """Angle-based outlier detector per subspace (Kriegel, Schubert, Zimek 2008), in its fast form over the k nearest
+    neighbours (FastABOD; pyod's ``ABOD`` with its default ``method="fast"``), combined like the detectors of
+    SubspaceEnsemble: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying.
+
+    Per subspace s (features F_s), query row q and its neighbour list N(q): the k reference rows nearest in dist_s, the
+    very lists SubspaceEnsemble builds (``fit`` excludes q's own index, ``decision_function`` nothing; ties by (distance,
+    index); ``kneighbors`` hands them out).  For a neighbour a, v_a = r_a[F_s] - q[F_s] in float64 from the raw float32
+    values (exact) and |v_a|^2 its float64 squared norm; a is usable if |v_a|^2 > 0, and m is the number of usable
+    neighbours.  Over the m (m - 1) / 2 unordered pairs of usable neighbours
+
+        w_ab = <v_a, v_b> / (|v_a|^2 |v_b|^2),      score_s(q) = -var(w)
+
+    with var the population variance (numpy.var), two passes (the mean, then the mean squared deviation) in float64 in a
+    fixed order, stored as float32 in the [S, n] score matrix; a result below the float32 range is stored as the most
+    negative finite float32, never -inf.  Scores are <= 0 and the closer to 0 the more outlying; inside one subspace they
+    span many orders of magnitude, so ``normalize="robust"`` or ``"minmax"`` and ``combination="max"`` are what to
+    reach for when subspaces are mixed, not a logarithm (-log var is +inf at one pair).
+
+    This is pyod's FastABOD as its source is remembered here (``_calculate_wocs`` skips a pair when one of its points equals
+    the query; ``decision_scores_`` is the negated variance); pyod was not at hand to pin it, so the definition above
+    and its numpy restatement in tests/test_outlier_abod_cpu.py are what binds, not pyod.
+
+    Degenerate rows.  m < 2 leaves no pair (a row whose neighbours all coincide with it in F_s: common in narrow
+    subspaces of discrete features).  pyod returns NaN there, which would poison every sum, percentile and statistic
+    downstream.  Such a row sits on a point mass and is as inlying as a row can be, so it takes the floor of its
+    subspace: ``score_floor_[s]``, the smallest float32 score among the non-degenerate rows of the subspace at ``fit`` (0
+    if there is none).  ``fit`` publishes ``score_floor_`` (float64 [S]) and ``n_degenerate_`` (int [S]) in the given
+    subspace order; ``decision_function`` applies the stored floor to its degenerate rows and computes none of its own.
+    m = 2 is not degenerate: one pair, variance 0, score 0, as in pyod.
+
+    ``decision_function(X_train)`` is not ``decision_scores_``: there every row is its own nearest neighbour, which is
+    unusable, and the other k - 1 form the pairs (the KDE remark of SubspaceEnsemble, for the same reason).
+
+    n_neighbors: 2 .. 32 (default 10, pyod's).  engine, splits, workspace_bytes: as for SubspaceEnsemble.  normalize,
+    combination, contamination, ``threshold_``, ``labels_``, ``predict``, ``predict_proba``, return_per_subspace: the
+    shared tail; ``per_subspace_scores_`` are the raw scores with the floor applied.  Given the same neighbour lists the
+    scores are bit-identical from run to run, and the lists do not depend on splits or workspace_bytes.  The scores run
+    in libvgan_hip.so (csrc/outlier_abod.hip)."""
+
+    def __init__(self, subspaces, proba, n_neighbors=10, engine="auto", splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
+                 normalize=None, combination="sum", contamination=0.1):
+        self.normalize = check_normalize(normalize)
+        self.combination = check_combination(combination)
+        self.contamination = check_contamination(contamination)
+        self.n_neighbors = check_abod_neighbors(n_neighbors)
+        if engine == "auto":
+            engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
+        self.plan = SubspacePlan(subspaces, engine=engine)
+        p = np.asarray(proba, dtype=np.float64).reshape(-1)
+        if p.shape[0] != self.plan.count:
+            raise ValueError(f"proba has {p.shape[0]} entries for {self.plan.count} subspaces")
+        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
+            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
+        self.engine, self.splits = engine, splits
+        self.workspace_bytes = int(workspace_bytes)
+        self.proba = p
+        self._attached = False
+
+    def _score(self, Xq, fitting):
+        """(ensemble scores float64 [n], per float32 [S, n] with the floor applied), both on the device."""
+        k, dev = self.n_neighbors, self._X.device
         nq = self._X.shape[0] if Xq is None else Xq.shape[0]
-        k = self.n_neighbors
-        D = torch.empty(self.plan.count, nq, k, dtype=torch.float32, device=self._X.device)
-        I = torch.empty(self.plan.count, nq, k, dtype=torch.int32, device=self._X.device)
-        for first, count, idx, dist in self._neighbors(Xq):
-            rows = self._rows[first:first + count].long()
-            D[rows], I[rows] = dist, idx
-        return D.cpu().numpy(), I.cpu().numpy()
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=dev)
+        for first, count, idx, _ in self._neighbors(Xq):
+            self.ops.outlier_abod(self._X if Xq is None else Xq, self._X, self._table, first, count, idx, k, per,
+                                  self._rows[first:first + count])
+        if fitting:
+            self._floor = torch.empty(self.plan.count, dtype=torch.float64, device=dev)
+            self._n_degenerate = torch.empty(self.plan.count, dtype=torch.int32, device=dev)
+            self.ops.outlier_abod_floor(per, self._floor, self._n_degenerate)
+        else:
+            self.ops.outlier_abod_floor(per, self._floor)
+        return self._combine(per, fitting), per
+
+    def fit(self, X, y=None):
+        """Keeps X resident as the reference set and scores it (self excluded): decision_scores_ (float64 [n]),
+        per_subspace_scores_, score_floor_, n_degenerate_; with normalize also score_center_ / score_scale_."""
+        shape = tuple(X.shape) if hasattr(X, "shape") else np.asarray(X).shape
+        if len(shape) != 2:
+            raise ValueError(f"X must be a 2-d matrix, got shape {shape}")
+        if shape[1] != self.plan.d:
+            raise ValueError(f"X has {shape[1]} features, the subspaces {self.plan.d}")
+        check_reference_rows(shape[0], self.n_neighbors, exclude_self=True)
+        if not self._attached:
+            self._attach()
+            self._attached = True
+        X = _device_matrix(X, self.plan.d)
+        self._X = X
+        self._center = torch.empty(X.shape[1], dtype=torch.float32, device=X.device)
+        self.ops.col_mean(X, self._center)
+        scores, per = self._score(None, fitting=True)
+        self.decision_scores_ = scores.cpu().numpy()
+        self.per_subspace_scores_ = per.cpu().numpy()
+        self.score_floor_ = self._floor.cpu().numpy()
+        self.n_degenerate_ = self._n_degenerate.cpu().numpy().astype(np.int64)
+        if self.normalize is not None:
+            self.score_center_, self.score_scale_ = self._stats.cpu().numpy()
+        self._decisions = None
+        return self
+
+    def decision_function(self, X, return_per_subspace=False):
+        """Ensemble scores of X against the fitted reference set (nothing excluded), float64 [n]; with
+        return_per_subspace=True also the float32 [S, n] per-subspace scores (subspaces in the given order)."""
+        self._require_fit()
+        X = _device_matrix(X, self.plan.d)
+        check_reference_rows(self._X.shape[0], self.n_neighbors, exclude_self=False)
+        scores, per = self._score(X, fitting=False)
+        if return_per_subspace:
+            return scores.cpu().numpy(), per.cpu().numpy()
+        return scores.cpu().numpy()
 
 
 # ---- k-means + CBLOF over the subspaces ----------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import SubspaceCBLOF, SubspaceEnsemble
+from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceEnsemble
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -179,11 +179,16 @@ class _RunFolder:
         method "cblof" builds a SubspaceCBLOF instead (k-means per subspace and the cluster-based local outlier factor):
         its keywords are n_clusters, alpha, beta, use_weights, init, max_iter, tol, seed, engine, workspace_bytes and the
         same normalize / combination / contamination, e.g. outlier_ensemble(method="cblof", n_clusters=8, X=X);
-        n_neighbors is not used there."""
+        n_neighbors is not used there.
+        method "abod" builds a SubspaceABOD (angle-based scores over the n_neighbors nearest neighbours, FastABOD; pyod's
+        default there is 10): its keywords are engine, splits, workspace_bytes and the same normalize / combination /
+        contamination, e.g. outlier_ensemble(method="abod", n_neighbors=10, X=X)."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
             ens = SubspaceCBLOF(self.subspaces, self.proba, **kw)
+        elif method == "abod":
+            ens = SubspaceABOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
