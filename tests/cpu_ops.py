@@ -474,12 +474,13 @@ class CpuOps:
 
     def mse_grad(self, target, pred, gscale, part, g):
         n, d = pred.shape
-        df = _np(pred)[:, :d].astype(np.float64) - _np(target)[:, :d].astype(np.float64)
+        df32 = _np(pred)[:, :d] - _np(target)[:, :d]  # the float32 difference: squared and summed in float64, scaled in float32
+        df = df32.astype(np.float64)
         rows = (df * df).sum(1)
         pad = np.zeros((n + 3) // 4 * 4)
         pad[:n] = rows
         part[:(n + 3) // 4].copy_(torch.as_tensor(pad.reshape(-1, 4).sum(1)))
-        g[:, :d].copy_(torch.as_tensor(float(gscale) * df))
+        g[:, :d].copy_(torch.as_tensor(np.float32(gscale) * df32))
 
     def sum_f64(self, src, count, scale, out, accumulate=False):
         v = float(_np(src)[:count].sum() * scale)
@@ -526,10 +527,10 @@ class CpuOps:
             self.noise_normal(next_noise, seed, step_counter, 0, cols=noise_cols, ones_col=noise_ones_col)
         m = pmap.long()
         live = m >= 0
-        g = torch.zeros_like(p)
-        g[live] = g_packed[m[live]]
-        self.adadelta_step(p, g, sq, acc, lr, rho, eps, weight_decay, grad_scale)
-        w_packed[m[live]] = p[live]
+        pl, sl, al = p[live], sq[live], acc[live]  # pmap[i] < 0 is layout padding: the kernel skips it, state included
+        self.adadelta_step(pl, g_packed[m[live]], sl, al, lr, rho, eps, weight_decay, grad_scale)
+        p[live], sq[live], acc[live] = pl, sl, al
+        w_packed[m[live]] = pl
 
     def noise_normal(self, z, seed, step_counter, stream_id=0, cols=None, ones_col=-1):
         g = torch.Generator()
