@@ -79,7 +79,7 @@ int vgan_reduce_slabs(const float* src, int64_t slab_stride, int nslabs, float* 
  *   whole epoch's table of shuffled indices and t = *row_cursor is the device-side step counter
  *   (row_cursor == NULL: t = 0;  rows == NULL: X_batch row i = data[row_offset + i]).  U may be NULL.
  *   center (may be NULL): a per-feature constant c[d] subtracted from EVERY row of Z, i.e. Zx[i] = X[i] - c and
- *   Zy[i] = fl(U[i] * X[i]) - c.  cdist(Z,Z)**2 (Mmd_loss_constrained.py:25) is translation invariant, so the loss and
+ *   Zy[i] = fma(U[i], X[i], -c) (one rounding: the library is built with -ffp-contract=fast).  cdist(Z,Z)**2 (Mmd_loss_constrained.py:25) is translation invariant, so the loss and
  *   its gradient are unchanged in exact arithmetic, while a common offset of a feature no longer eats the mantissa of
  *   the fp32 (and above all the split-bf16) operands; the step engine passes the data-set mean (vgan_col_mean).
  *   norm_split != 0: sqx/sqy are the norms of the split values hi + lo that vgan_mmd_bf3_prepare will produce from
@@ -313,6 +313,26 @@ int vgan_mmd_backward_bf3_rm_xx(const uint16_t* Wh, const uint16_t* Wl, int ldw,
                                 int p, const float* mul, int ldmul, const float* mul_shift, float* out, int ldo,
                                 int splits, int64_t slab_stride, const vgan_finalize_job* finalize,
                                 const struct vgan_xx_job* xx, vgan_stream_t stream);
+/* The training step's form of that launch without an fp32 copy of Z: gU = 2 (rowsum(W) y - W . Z) * x for the nr batch rows,
+ * where the epilogue forms its two operands itself instead of loading them from Z and `mul`:
+ *     x = data[xrow[i], j],  c = center[j],  u = S[i, j] < 1/p ? S[i, j] : 1,
+ *     y = fma(u, x, -c)  (the Y row vgan_mask_project_forward_bf3 writes),  multiplier = fl(fl(x - c) + c)  (mul + mul_shift).
+ * Bit for bit the result of vgan_mmd_backward_bf3_rm_xx called with the Z that vgan_mask_project_forward_bf3 wrote from the same
+ * data rows, S and centre, mul = its X half and mul_shift = center -- so the mask / projection launch need not write Z at all
+ * (vgan_mask_project_forward_bf3_ex, write_z = 0: 6.4 of its 22.8 MB per step at n = 1024, d = 784).  64-wide tiles;
+ * xrow: int32 [nr] as that launch leaves it; S: [nr, lds] with p columns; xx and finalize may be NULL. */
+typedef struct vgan_bwd_rebuild {
+    const float* data;   /* the data set [rows, ldd] */
+    const int32_t* xrow; /* [nr] data-set row of each batch row */
+    const float* S;      /* [nr, lds] softmax rows */
+    const float* center; /* [p] */
+    int32_t ldd, lds;
+} vgan_bwd_rebuild;
+int vgan_mmd_backward_bf3_rm_rebuild(const uint16_t* Wh, const uint16_t* Wl, int ldw, int kn, const uint16_t* Zh,
+                                     const uint16_t* Zl, int kp, int zrows, int nr, int p,
+                                     const vgan_bwd_rebuild* rebuild, float* out, int ldo, int splits,
+                                     int64_t slab_stride, const vgan_finalize_job* finalize,
+                                     const struct vgan_xx_job* xx, vgan_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * Grouped small products: up to VGAN_GEMM_MAX_GROUP independent row-major GEMMs in one launch.
  * Generator_big (src/models/Generator.py:61-66) has no activation between its Linear layers, so its
@@ -393,7 +413,10 @@ int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count, const vga
  * (vgan_gather_rows_split over the whole data set with norm_split = 1).  tiles / ntiles: the X-X part of the tile table
  * (vgan_mmd_build_tiles, flags slot 0); partial: where their sums go (4 floats per tile, the layout vgan_mmd_finalize folds);
  * bw: the frozen bandwidth.  The Gram launch then covers the XY and YY tiles only.
- * chain (may be NULL; needs ZTh == NULL): as in vgan_mask_project_forward. */
+ * chain (may be NULL; needs ZTh == NULL): as in vgan_mask_project_forward.
+ * vgan_mask_project_forward_bf3_ex: the same launch with two more arguments.  write_z == 0: the fp32 operand Z is not written
+ * (Z may be NULL; S, sq and the split images are written as always) -- for steps whose backward is
+ * vgan_mmd_backward_bf3_rm_rebuild.  xrow (may be NULL): int32 [n], receives the data-set row of every batch row. */
 typedef struct vgan_xx_job {
     const uint16_t* Dh;
     const uint16_t* Dl;
@@ -408,6 +431,12 @@ int vgan_mask_project_forward_bf3(const float* logits, int ldl, const float* dat
                                   int ldz, float* sq, uint16_t* Zh, uint16_t* Zl, int kp, uint16_t* ZTh,
                                   uint16_t* ZTl, int kn, int n, int d, const float* center, int write_x,
                                   const vgan_xx_job* xx, const vgan_logits_chain* chain, vgan_stream_t stream);
+int vgan_mask_project_forward_bf3_ex(const float* logits, int ldl, const float* data, int ldd, const int32_t* rows,
+                                     const uint64_t* row_cursor, int row_batches, int row_stride, float* S, float* Z,
+                                     int ldz, float* sq, uint16_t* Zh, uint16_t* Zl, int kp, uint16_t* ZTh,
+                                     uint16_t* ZTl, int kn, int n, int d, const float* center, int write_x,
+                                     const vgan_xx_job* xx, const vgan_logits_chain* chain, int write_z, int32_t* xrow,
+                                     vgan_stream_t stream);
 /* squared row norms sq[r] = |Z_r|^2 (for callers that assemble Z themselves) */
 int vgan_row_sqnorm(const float* Z, int ldz, float* sq, int rows, int p, vgan_stream_t stream);
 

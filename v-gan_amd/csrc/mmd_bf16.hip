@@ -518,7 +518,19 @@ __global__ __launch_bounds__(768, 3) void mmd_gram_bf3_wide_kernel(const unsigne
 // ---- backward: out = 2 (rowsum(W) z - W . Z) * mul, W = Wh + Wl [nr, kn], Z^T = ZTh + ZTl [kp, kn] -------------
 // RM: the B operand is Z's ROW-MAJOR split images (Zh, Zl [zrows, kp], what the Gram reads) instead of the transposed copies
 // (ZTh, ZTl [kp, kn]); `kn` is then the padded contraction length (columns of W) and `brows` the rows of Zh that exist.
-template <int BK, bool RM>
+// REBUILD: Z, mul and mul_shift are not read.  The two epilogue operands of an element -- z, the Y row, and the multiplier, the X
+// row plus the centre -- are formed from the data row xrow[i], the softmax S and the centre (vgan_common.hpp: the functions the
+// mask / projection launch wrote Z with, so the numbers are the same bits).  The loads of x and s stand where those of z and
+// the multiplier stood: before the K loop, clamped, unconditional -- the same 32 registers held across it.
+struct BwdRebuild {
+    const float* data;
+    const int* xrow;
+    const float* S;
+    const float* center;
+    int ldd, lds;
+};
+
+template <int BK, bool RM, bool REBUILD>
 __global__ __launch_bounds__(kBlock, BK == 64 ? 2 : 3) void mmd_backward_bf3_kernel(const unsigned short* __restrict__ Wh, const unsigned short* __restrict__ Wl,
                                                                     int ldw, const unsigned short* __restrict__ ZTh,
                                                                     const unsigned short* __restrict__ ZTl, int kn, int ldb, int brows,
@@ -526,7 +538,7 @@ __global__ __launch_bounds__(kBlock, BK == 64 ? 2 : 3) void mmd_backward_bf3_ker
                                                                     int ptiles, const float* __restrict__ mul, int ldmul,
                                                                     const float* __restrict__ mul_shift, float* __restrict__ out, int ldo,
                                                                     int kchunk, long slab_stride, vgan_finalize_job job, int nfin,
-                                                                    XXJob xx) {
+                                                                    XXJob xx, BwdRebuild rb) {
     using G = GemmBF3<BK>;
     constexpr int kBytes = (RM ? G::kLdsBytesT : G::kLdsBytes) > G::kLdsBytes ? (RM ? G::kLdsBytesT : G::kLdsBytes) : G::kLdsBytes;
     __shared__ __attribute__((aligned(16))) char lds[kBytes];
@@ -557,13 +569,24 @@ __global__ __launch_bounds__(kBlock, BK == 64 ? 2 : 3) void mmd_backward_bf3_ker
     // the epilogue's operands (z and the multiplier, clamped addresses) are requested BEFORE the main loop: issued after it
     // they would add one full memory latency to every tile
     const int col = n0 + G::sub_col(), colc = min(col, p - 1);
-    float z_pre[16], m_pre[16];
-    const float mshift = mul_shift != nullptr ? mul_shift[colc] : 0.f;  // mul is stored centred (see vgan_mmd_backward)
+    float z_pre[16], m_pre[16];  // REBUILD: s and x
+    float mshift;                // REBUILD: the centre
+    if constexpr (REBUILD) {
+        mshift = rb.center[colc];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int rowc = min(m0 + G::sub_row(r), nr - 1);
-        z_pre[r] = Z[(long)(wrow0 + rowc) * ldz + colc];
-        m_pre[r] = mul != nullptr ? mul[(long)rowc * ldmul + colc] + mshift : 1.f;
+        for (int r = 0; r < 16; ++r) {
+            const int rowc = min(m0 + G::sub_row(r), nr - 1);
+            z_pre[r] = rb.S[(long)rowc * rb.lds + colc];
+            m_pre[r] = rb.data[(long)rb.xrow[rowc] * rb.ldd + colc];
+        }
+    } else {
+        mshift = mul_shift != nullptr ? mul_shift[colc] : 0.f;  // mul is stored centred (see vgan_mmd_backward)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rowc = min(m0 + G::sub_row(r), nr - 1);
+            z_pre[r] = Z[(long)(wrow0 + rowc) * ldz + colc];
+            m_pre[r] = mul != nullptr ? mul[(long)rowc * ldmul + colc] + mshift : 1.f;
+        }
     }
     if (klen > 0) {
         if constexpr (RM)
@@ -573,6 +596,15 @@ __global__ __launch_bounds__(kBlock, BK == 64 ? 2 : 3) void mmd_backward_bf3_ker
             G::template run<true>(Wh + k0, Wl + k0, ldw, ZTh + k0, ZTl + k0, ldb, m0, n0, nr, gx * 64, klen, lds, rs, acc);
     }
     if (col >= p) return;
+    if constexpr (REBUILD) {
+        const float tau = 1.0f / (float)p;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float x = m_pre[r];
+            z_pre[r] = project_centred(upper_mask(z_pre[r], tau), x, mshift);
+            m_pre[r] = uncentred_x(centred_x(x, mshift), mshift);
+        }
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int lrow = G::sub_row(r), row = m0 + lrow;
@@ -816,9 +848,16 @@ static int launch_backward_bf3(int rm, const uint16_t* Wh, const uint16_t* Wl, i
                                int zrows, const float* Z, int ldz, int wrow0, int nr, int p, const float* mul, int ldmul,
                                const float* mul_shift, float* out, int ldo, int splits, int64_t slab_stride, int tile,
                                const vgan_finalize_job* finalize, vgan_stream_t stream, const vgan_xx_job* xxjob = nullptr,
-                               const float* rs_part = nullptr, int ldrs = 0) {
-    VGAN_CHECK_ARG(Wh && Wl && Bh && Bl && Z && out && nr > 0 && p > 0 && kn > 0 && kn % 64 == 0 && kp >= p && kp % 64 == 0);
-    VGAN_CHECK_ARG(ldw >= kn && ldz >= p && ldo >= p && (mul == nullptr || ldmul >= p) && wrow0 >= 0);
+                               const float* rs_part = nullptr, int ldrs = 0, const vgan_bwd_rebuild* rebuild = nullptr) {
+    VGAN_CHECK_ARG(Wh && Wl && Bh && Bl && (Z || rebuild) && out && nr > 0 && p > 0 && kn > 0 && kn % 64 == 0 && kp >= p && kp % 64 == 0);
+    VGAN_CHECK_ARG(ldw >= kn && (rebuild || ldz >= p) && ldo >= p && (mul == nullptr || ldmul >= p) && wrow0 >= 0);
+    BwdRebuild rb{};
+    if (rebuild != nullptr) {  // 64-wide tiles on the row-major operand only; S and the data rows have p columns
+        const vgan_bwd_rebuild& q = *rebuild;
+        VGAN_CHECK_ARG(rm && tile == 64 && q.data && q.xrow && q.S && q.center && q.ldd >= p && q.lds >= p && Z == nullptr && mul == nullptr &&
+                       mul_shift == nullptr);
+        rb = BwdRebuild{q.data, q.xrow, q.S, q.center, q.ldd, q.lds};
+    }
     VGAN_CHECK_ARG(aligned16(Wh) && aligned16(Wl) && aligned16(Bh) && aligned16(Bl) && ldw % 8 == 0);
     VGAN_CHECK_ARG(splits >= 1 && splits <= 64 && (splits == 1 || slab_stride >= (int64_t)nr * ldo));
     VGAN_CHECK_ARG((tile == 0 || tile == 64 || tile == 128 || tile == 256) && (mul_shift == nullptr || mul != nullptr) && (!rm || zrows > 0));
@@ -867,12 +906,15 @@ static int launch_backward_bf3(int rm, const uint16_t* Wh, const uint16_t* Wl, i
     }
     const int ptiles = (p + 63) / 64;
     dim3 grid(ptiles * ((nr + 63) / 64) + nfin + xx.ntiles, splits);
-    if (rm)
-        hipLaunchKernelGGL((mmd_backward_bf3_kernel<64, true>), grid, dim3(kBlock), 0, st, Wh, Wl, ldw, Bh, Bl, kn, ldb, zrows, Z, ldz, wrow0, nr,
-                           p, ptiles, mul, ldmul, mul_shift, out, ldo, kchunk, (long)slab_stride, job, nfin, xx);
+    if (rebuild != nullptr)
+        hipLaunchKernelGGL((mmd_backward_bf3_kernel<64, true, true>), grid, dim3(kBlock), 0, st, Wh, Wl, ldw, Bh, Bl, kn, ldb, zrows, Z, ldz, wrow0,
+                           nr, p, ptiles, mul, ldmul, mul_shift, out, ldo, kchunk, (long)slab_stride, job, nfin, xx, rb);
+    else if (rm)
+        hipLaunchKernelGGL((mmd_backward_bf3_kernel<64, true, false>), grid, dim3(kBlock), 0, st, Wh, Wl, ldw, Bh, Bl, kn, ldb, zrows, Z, ldz, wrow0,
+                           nr, p, ptiles, mul, ldmul, mul_shift, out, ldo, kchunk, (long)slab_stride, job, nfin, xx, rb);
     else
-        hipLaunchKernelGGL((mmd_backward_bf3_kernel<64, false>), grid, dim3(kBlock), 0, st, Wh, Wl, ldw, Bh, Bl, kn, ldb, 0, Z, ldz, wrow0, nr, p,
-                           ptiles, mul, ldmul, mul_shift, out, ldo, kchunk, (long)slab_stride, job, nfin, xx);
+        hipLaunchKernelGGL((mmd_backward_bf3_kernel<64, false, false>), grid, dim3(kBlock), 0, st, Wh, Wl, ldw, Bh, Bl, kn, ldb, 0, Z, ldz, wrow0, nr,
+                           p, ptiles, mul, ldmul, mul_shift, out, ldo, kchunk, (long)slab_stride, job, nfin, xx, rb);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }
@@ -900,4 +942,13 @@ extern "C" int vgan_mmd_backward_bf3_rm(const uint16_t* Wh, const uint16_t* Wl, 
                                         const vgan_finalize_job* finalize, const float* rs_part, int ldrs, vgan_stream_t stream) {
     return launch_backward_bf3(1, Wh, Wl, ldw, Zh, Zl, kn, kp, zrows, Z, ldz, wrow0, nr, p, mul, ldmul, mul_shift, out, ldo, splits,
                                slab_stride, tile, finalize, stream, nullptr, rs_part, ldrs);
+}
+
+extern "C" int vgan_mmd_backward_bf3_rm_rebuild(const uint16_t* Wh, const uint16_t* Wl, int ldw, int kn, const uint16_t* Zh, const uint16_t* Zl,
+                                                int kp, int zrows, int nr, int p, const vgan_bwd_rebuild* rebuild, float* out, int ldo,
+                                                int splits, int64_t slab_stride, const vgan_finalize_job* finalize, const vgan_xx_job* xx,
+                                                vgan_stream_t stream) {
+    VGAN_CHECK_ARG(rebuild != nullptr);
+    return launch_backward_bf3(1, Wh, Wl, ldw, Zh, Zl, kn, kp, zrows, nullptr, 0, 0, nr, p, nullptr, 0, nullptr, out, ldo, splits, slab_stride, 64,
+                               finalize, stream, xx, nullptr, 0, rebuild);
 }

@@ -27,13 +27,7 @@ struct RowSel {
     }
 };
 
-// y = fl(u * x) - c with the product ROUNDED first, as the reference forms `U * batch` (src/vgan.py:616) before any distance
-// is taken (the file is compiled with -ffp-contract=fast, which would otherwise fuse the two into one fma)
-__device__ __forceinline__ float project_centred(float u, float x, float c) {
-#pragma clang fp contract(off)
-    const float y = u * x;
-    return y - c;
-}
+// (project_centred, centred_x: vgan_common.hpp -- shared with the MMD backward that rebuilds these values)
 
 template <bool PROJECT>
 __global__ __launch_bounds__(kBlock) void mask_forward_kernel(const float* __restrict__ logits, int ldl, const float* __restrict__ data,
@@ -218,6 +212,10 @@ __global__ __launch_bounds__(kBlock) void mask_forward_vec_kernel(const float* _
 // (ZTh, ZTl: [feature][row]) through an LDS tile, so that 8 rows leave as one 16-byte store per feature and image.  This
 // removes the separate preparation launch (~6 us of a ~120 us step at d = 784) and its 13 MB re-read of Z.
 // XX: workgroups past the row groups run the X-X tiles of this step's Gram (mmd_xx.hpp), one tile each.
+// write_z == 0: the fp32 operand Z is not written (6.4 of the launch's 22.8 MB at n = 1024, d = 784) -- the Gram reads the
+// split images, and the 64-wide backward rebuilds the two numbers it took from Z (vgan_mmd_backward_bf3_rm_rebuild) from the
+// data row, S and the centre.  xrow (may be NULL): xrow[i] = the data-set row of batch row i, for that backward: the step tail
+// that rides in ITS launch advances the batch cursor, so the index is fixed here.
 template <int NT, bool XX, bool CHAIN>
 __global__ __launch_bounds__(512) void mask_forward_bf3_kernel(const float* __restrict__ logits, int ldl, const float* __restrict__ data,
                                                                  int ldd, RowSel rows, float* __restrict__ S, float* __restrict__ Z,
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(512) void mask_forward_bf3_kernel(const float* __re
                                                                  unsigned short* __restrict__ Zl, int kp, unsigned short* __restrict__ ZTh,
                                                                  unsigned short* __restrict__ ZTl, int kn, int n, int d,
                                                                  const float* __restrict__ center, int write_x, int mask_blocks,
-                                                                 XXJob xx, LogitsChain ch) {
+                                                                 XXJob xx, LogitsChain ch, int write_z, int* __restrict__ xrow) {
     constexpr int R = 8;  // rows per workgroup = waves per workgroup (512 threads; 4 rows in 256 threads measured the same: 11.7 us)
     if constexpr (XX) {
         __shared__ __attribute__((aligned(16))) char xx_lds[GemmBF3<64>::kLdsBytes];
@@ -254,7 +252,9 @@ __global__ __launch_bounds__(512) void mask_forward_bf3_kernel(const float* __re
         if constexpr (CHAIN) chain_logits<NT>(ch, reinterpret_cast<float*>(tile), d, i, i < n, v);
         if (i < n) {
             const float4* x4 = reinterpret_cast<const float4*>(logits + (long)i * ldl);
-            const float4* xr4 = reinterpret_cast<const float4*>(data + rows(i) * ldd);
+            const long src = rows(i);
+            const float4* xr4 = reinterpret_cast<const float4*>(data + src * ldd);
+            if (xrow != nullptr && lane == 0) xrow[i] = (int)src;
             float4 xv[NT], cv[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -281,15 +281,18 @@ __global__ __launch_bounds__(512) void mask_forward_bf3_kernel(const float* __re
                 const int q = lane + 64 * t;
                 if (q < nq) {
                     const float4 s4 = make_float4(v[t].x / sum, v[t].y / sum, v[t].z / sum, v[t].w / sum);
-                    const float4 u4 = make_float4(s4.x < tau ? s4.x : 1.f, s4.y < tau ? s4.y : 1.f, s4.z < tau ? s4.z : 1.f, s4.w < tau ? s4.w : 1.f);
+                    const float4 u4 = make_float4(upper_mask(s4.x, tau), upper_mask(s4.y, tau), upper_mask(s4.z, tau), upper_mask(s4.w, tau));
                     // centred operand (see mask_forward_vec_kernel); the row norms are those of the SPLIT values hi + lo, the
                     // numbers the Gram kernel actually multiplies, so that L = s_i + s_j - 2 g is |zhat_i - zhat_j|^2 exactly
-                    const float4 x4c = make_float4(xv[t].x - cv[t].x, xv[t].y - cv[t].y, xv[t].z - cv[t].z, xv[t].w - cv[t].w);
+                    const float4 x4c = make_float4(centred_x(xv[t].x, cv[t].x), centred_x(xv[t].y, cv[t].y), centred_x(xv[t].z, cv[t].z),
+                                                   centred_x(xv[t].w, cv[t].w));
                     const float4 y4 = make_float4(project_centred(u4.x, xv[t].x, cv[t].x), project_centred(u4.y, xv[t].y, cv[t].y), project_centred(u4.z, xv[t].z, cv[t].z),
                                               project_centred(u4.w, xv[t].w, cv[t].w));
                     reinterpret_cast<float4*>(S + (long)i * d)[q] = s4;
-                    if (write_x) reinterpret_cast<float4*>(Z + (long)i * ldz)[q] = x4c;
-                    reinterpret_cast<float4*>(Z + (long)(n + i) * ldz)[q] = y4;
+                    if (write_z) {  // (uniform)
+                        if (write_x) reinterpret_cast<float4*>(Z + (long)i * ldz)[q] = x4c;
+                        reinterpret_cast<float4*>(Z + (long)(n + i) * ldz)[q] = y4;
+                    }
                     const float xs[4] = {x4c.x, x4c.y, x4c.z, x4c.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w};
                     unsigned short h[2][4], l[2][4];
                     float xn[4], yn[4];
@@ -598,8 +601,18 @@ extern "C" int vgan_mask_project_forward_bf3(const float* logits, int ldl, const
                                              float* sq, uint16_t* Zh, uint16_t* Zl, int kp, uint16_t* ZTh, uint16_t* ZTl, int kn,
                                              int n, int d, const float* center, int write_x, const vgan_xx_job* xxjob,
                                              const vgan_logits_chain* chain, vgan_stream_t stream) {
-    VGAN_CHECK_ARG((logits || chain) && data && S && Z && sq && Zh && Zl && n > 0 && d > 0 && (logits == nullptr || ldl >= d) && ldd >= d &&
-                   ldz >= d);
+    VGAN_CHECK_ARG(Z != nullptr);
+    return vgan_mask_project_forward_bf3_ex(logits, ldl, data, ldd, rows, row_cursor, row_batches, row_stride, S, Z, ldz, sq, Zh, Zl, kp, ZTh,
+                                            ZTl, kn, n, d, center, write_x, xxjob, chain, 1, nullptr, stream);
+}
+
+extern "C" int vgan_mask_project_forward_bf3_ex(const float* logits, int ldl, const float* data, int ldd, const int32_t* rows,
+                                                const uint64_t* row_cursor, int row_batches, int row_stride, float* S, float* Z, int ldz,
+                                                float* sq, uint16_t* Zh, uint16_t* Zl, int kp, uint16_t* ZTh, uint16_t* ZTl, int kn,
+                                                int n, int d, const float* center, int write_x, const vgan_xx_job* xxjob,
+                                                const vgan_logits_chain* chain, int write_z, int32_t* xrow, vgan_stream_t stream) {
+    VGAN_CHECK_ARG((logits || chain) && data && S && (Z || !write_z) && sq && Zh && Zl && n > 0 && d > 0 && (logits == nullptr || ldl >= d) &&
+                   ldd >= d && (!write_z || ldz >= d));
     LogitsChain ch{};
     if (chain != nullptr) {
         VGAN_CHECK_ARG(ZTh == nullptr && chain->za && chain->At4 && chain->e0 > 0 && chain->e0 % 4 == 0 && chain->ldza >= chain->e0 &&
@@ -611,8 +624,8 @@ extern "C" int vgan_mask_project_forward_bf3(const float* logits, int ldl, const
     VGAN_CHECK_ARG(row_batches >= 1 && row_stride >= 0 && kp >= d && kp % 64 == 0 && (ZTh == nullptr || (kn >= 2 * n && kn % 64 == 0)));
     VGAN_CHECK_ARG(write_x || ZTh == nullptr);  // the transposed images are always written whole
     // shape contract of the fused path (callers fall back to vgan_mask_project_forward + vgan_mmd_bf3_prepare otherwise)
-    VGAN_CHECK_ARG(d % 4 == 0 && d <= 1024 && n % 8 == 0 && ldl % 4 == 0 && ldd % 4 == 0 && ldz % 4 == 0);
-    VGAN_CHECK_ARG(aligned16(logits) && aligned16(data) && aligned16(S) && aligned16(Z) && aligned16(Zh) && aligned16(Zl) &&
+    VGAN_CHECK_ARG(d % 4 == 0 && d <= 1024 && n % 8 == 0 && ldl % 4 == 0 && ldd % 4 == 0 && (!write_z || ldz % 4 == 0));
+    VGAN_CHECK_ARG(aligned16(logits) && aligned16(data) && aligned16(S) && (!write_z || aligned16(Z)) && aligned16(Zh) && aligned16(Zl) &&
                    (ZTh == nullptr || (aligned16(ZTh) && aligned16(ZTl))) && (center == nullptr || aligned16(center)));
     const RowSel sel{rows, reinterpret_cast<const unsigned long long*>(row_cursor), row_batches, row_stride, 0};
     const int mask_blocks = 8 * ((n / 8 + 7) / 8);
@@ -638,7 +651,7 @@ extern "C" int vgan_mask_project_forward_bf3(const float* logits, int ldl, const
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mask_forward_bf3_kernel<NT, XXF, CHF>),                          \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                                      \
         hipLaunchKernelGGL((mask_forward_bf3_kernel<NT, XXF, CHF>), grid, block, shmem, st, logits, ldl, data, ldd, sel, S, Z, ldz, sq, \
-                           Zh, Zl, kp, ZTh, ZTl, kn, n, d, center, write_x, mask_blocks, xx, ch);                                    \
+                           Zh, Zl, kp, ZTh, ZTl, kn, n, d, center, write_x, mask_blocks, xx, ch, write_z, xrow);                     \
     } while (0)
 #define VGAN_LAUNCH_FWD3(NT)                                                                                                        \
     do {                                                                                                                            \

@@ -130,6 +130,24 @@ __device__ __forceinline__ float split_value(float v) {
     return bf16_val(hi) + bf16_val(lo);
 }
 
+// ---- one element of the centred MMD operand Z = [X - c ; U * X - c] and of the multiplier X, from x, u and the centre c ------
+// Two launches form these numbers independently -- the mask / projection launch that writes the operand, and the 64-wide
+// split-bf16 MMD backward when it rebuilds its epilogue operands instead of reading an fp32 copy of Z -- and they must agree
+// bit for bit, so every operation is spelled out here instead of being left to -ffp-contract:
+//   centred_x          fl(x - c)            one subtraction;
+//   project_centred    fma(u, x, -c)        ONE rounding.  The reference rounds the product `U * batch` (src/vgan.py:616) before
+//                      any distance is taken, and this function used to ask for that with `#pragma clang fp contract(off)` --
+//                      but the library is built with -ffp-contract=fast, under which the back end fuses across the pragma: the
+//                      object code has always held v_fma_f32 / v_pk_fma_f32 here (read off the disassembly), and every recorded
+//                      result was computed with it.  It is written as what it is; the difference to the reference's form is
+//                      half an ulp of u * x, below the split-bf16 operand's own resolution;
+//   uncentred_x        fl(xc + c)           the batch entry as the backward's multiplier sees it: mul + mul_shift.
+__device__ __forceinline__ float centred_x(float x, float c) { return __fsub_rn(x, c); }
+__device__ __forceinline__ float project_centred(float u, float x, float c) { return __fmaf_rn(u, x, -c); }
+__device__ __forceinline__ float uncentred_x(float xc, float c) { return __fadd_rn(xc, c); }
+// the mask entry of a softmax value (src/models/Generator.py:20-21), tau = float32(1 / d)
+__device__ __forceinline__ float upper_mask(float s, float tau) { return s < tau ? s : 1.0f; }
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace vgan

@@ -37,6 +37,11 @@ class XXJob(ctypes.Structure):
                 ("ntiles", ctypes.c_int32)]
 
 
+class BwdRebuild(ctypes.Structure):
+    """struct vgan_bwd_rebuild (include/vgan_hip.h): what the 64-wide bf16x3 backward rebuilds its epilogue operands from."""
+    _fields_ = [("data", _p), ("xrow", _p), ("S", _p), ("center", _p), ("ldd", ctypes.c_int32), ("lds", ctypes.c_int32)]
+
+
 class AdadeltaLayer(ctypes.Structure):
     """struct vgan_adadelta_layer (include/vgan_hip.h)."""
     _fields_ = [("w_packed", _p), ("off_w", _i64), ("off_b", _i64), ("ldp", ctypes.c_int32), ("out", ctypes.c_int32),
@@ -92,6 +97,7 @@ SIGNATURES = {
     "vgan_mmd_backward_bf3_tile": (_i, [_i, _i, _i, _i]),
     "vgan_mmd_backward_bf3_rm": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _i, _i64, _i, _p, _p, _i, _p]),
     "vgan_mmd_backward_bf3_rm_xx": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _i, _i64, _p, _p, _p]),
+    "vgan_mmd_backward_bf3_rm_rebuild": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _i, _i64, _p, _p, _p]),
     "vgan_row_sqnorm": (_i, [_p, _i, _p, _i, _i, _p]),
     "vgan_adadelta_step": (_i, [_p, _p, _i, _i64, _p, _p, _i64, _f, _f, _f, _f, _f, _p]),
     "vgan_noise_normal": (_i, [_p, _i, _i, _i, _i, _u64, _p, _u64, _p]),
@@ -100,6 +106,8 @@ SIGNATURES = {
     "vgan_gemm_grouped": (_i, [_p, _i, _p]),
     "vgan_gemm_grouped_ex": (_i, [_p, _i, _p, _p]),
     "vgan_mask_project_forward_bf3": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "vgan_mask_project_forward_bf3_ex": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p, _i, _p,
+                                              _p]),
     "vgan_mse_grad": (_i, [_p, _i, _p, _i, _i, _i, _f, _p, _p, _i, _p]),
     "vgan_sum_f64": (_i, [_p, _i, ctypes.c_double, _p, _i, _p]),
     "vgan_rbf_kernel_matrix": (_i, [_p, _i, _i, _i, _p, _f, _p, _i, _p]),

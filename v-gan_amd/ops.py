@@ -149,6 +149,10 @@ class HipOps:
                                                       n, d, _ptr(center), int(bool(norm_split)),
                                                       ctypes.byref(chain) if chain is not None else None, self._stream()), "vgan_mask_project_forward")
 
+    # this provider has the launches of the bf16x3 step without an fp32 operand copy: mask_project_forward_bf3(write_z=, xrow=)
+    # and mmd_backward_bf3_rm_rebuild
+    bf3_rebuild = True
+
     def xx_job(self, Dh, Dl, dsq, tiles, bw, partial):
         """The X-X Gram tiles as a job for mask_project_forward_bf3 (`xx=`): Dh, Dl, dsq = split images / norms of the whole
         (centred) data set, tiles / partial = the X-X part of the tile table and of the partial buffer.  Raw pointers: the
@@ -156,13 +160,30 @@ class HipOps:
         assert tiles.is_contiguous() and partial.is_contiguous() and Dh.stride(0) == Dl.stride(0)
         return _lib.XXJob(_ptr(Dh), _ptr(Dl), _ptr(dsq), _ptr(tiles), _ptr(bw), _ptr(partial), Dh.stride(0), tiles.shape[0])
 
+    def bwd_rebuild(self, data, xrow, S, center):
+        """What mmd_backward_bf3_rm_rebuild forms its epilogue operands from (raw pointers: the tensors must outlive the job)."""
+        _mat(data, "data"), _mat(S, "S")
+        assert xrow.dtype == torch.int32 and xrow.is_contiguous() and center.is_contiguous()
+        return _lib.BwdRebuild(_ptr(data), _ptr(xrow), _ptr(S), _ptr(center), data.stride(0), S.stride(0))
+
     def mask_project_forward_bf3(self, logits, data, rows, S, Z, sq, Zh, Zl, ZTh, ZTl, row_cursor=None, row_batches=1, row_stride=0,
-                                 center=None, write_x=True, xx=None, chain=None):
-        """mask_project_forward + mmd_bf3_prepare in one launch (shape contract in include/vgan_hip.h; see bf3_fusable)."""
+                                 center=None, write_x=True, xx=None, chain=None, write_z=True, xrow=None):
+        """mask_project_forward + mmd_bf3_prepare in one launch (shape contract in include/vgan_hip.h; see bf3_fusable).
+        write_z=False: the fp32 operand Z is not written; xrow: int32 [n], receives the data-set row of every batch row."""
         _mat(data, "data"), _mat(Z, "Z"), _mat(S, "S")
         n, d = S.shape
         if logits is not None:
             _mat(logits, "logits")
+        if not write_z or xrow is not None:
+            _lib.check(self.lib.vgan_mask_project_forward_bf3_ex(_ptr(logits), logits.stride(0) if logits is not None else 0, _ptr(data),
+                                                                 data.stride(0), _ptr(rows), _ptr(row_cursor), int(row_batches),
+                                                                 int(row_stride), _ptr(S), _ptr(Z), Z.stride(0), _ptr(sq), _ptr(Zh), _ptr(Zl),
+                                                                 Zh.stride(0), _ptr(ZTh), _ptr(ZTl), ZTh.stride(0) if ZTh is not None else 0,
+                                                                 n, d, _ptr(center), int(bool(write_x)),
+                                                                 ctypes.byref(xx) if xx is not None else None,
+                                                                 ctypes.byref(chain) if chain is not None else None, int(bool(write_z)),
+                                                                 _ptr(xrow), self._stream()), "vgan_mask_project_forward_bf3_ex")
+            return
         _lib.check(self.lib.vgan_mask_project_forward_bf3(_ptr(logits), logits.stride(0) if logits is not None else 0, _ptr(data), data.stride(0), _ptr(rows),
                                                           _ptr(row_cursor), int(row_batches), int(row_stride), _ptr(S), _ptr(Z), Z.stride(0),
                                                           _ptr(sq), _ptr(Zh), _ptr(Zl), Zh.stride(0), _ptr(ZTh), _ptr(ZTl),
@@ -378,6 +399,18 @@ class HipOps:
                                                      ctypes.byref(finalize) if finalize is not None else None, _ptr(rs_part),
                                                      rs_part.stride(0) if rs_part is not None else 0, self._stream()),
                    "vgan_mmd_backward_bf3_rm")
+
+    def mmd_backward_bf3_rm_rebuild(self, Wh, Wl, Zh, Zl, zrows, nr, p, rebuild, out, splits=1, slab_stride=0, finalize=None, xx=None):
+        """mmd_backward_bf3_rm on 64-wide tiles with the epilogue operands rebuilt from `rebuild` (bwd_rebuild()) instead of read from
+        an fp32 Z and its X half: the same bits, without that copy (include/vgan_hip.h)."""
+        _mat(out, "out")
+        kn = (int(zrows) + 63) // 64 * 64
+        assert Wh.stride(0) >= kn and Zh.shape[0] >= zrows
+        _lib.check(self.lib.vgan_mmd_backward_bf3_rm_rebuild(_ptr(Wh), _ptr(Wl), Wh.stride(0), kn, _ptr(Zh), _ptr(Zl), Zh.stride(0), int(zrows),
+                                                             int(nr), int(p), ctypes.byref(rebuild), _ptr(out), out.stride(0), int(splits),
+                                                             int(slab_stride), ctypes.byref(finalize) if finalize is not None else None,
+                                                             ctypes.byref(xx) if xx is not None else None, self._stream()),
+                   "vgan_mmd_backward_bf3_rm_rebuild")
 
     def mmd_backward_bf3_tile(self, nr, p, splits=1, tile=0):
         """Tile edge (64 / 128) mmd_backward_bf3 runs for this shape (host-side query of the library's rule)."""

@@ -453,6 +453,21 @@ class NoKLStepEngine:
             late = self.tiles.shape[0] - self.n_main
             bwd_wgs = ((d + 63) // 64) * ((nl + 63) // 64) * self.bsplits + 1
             self.xx_late_in_backward = (ops.mmd_backward_bf3_tile(nl, d, self.bsplits, self.bwd_tile) == 64 and late <= 512 - bwd_wgs)
+        # The default bf16x3 step (fused forward, 64-wide Gram and backward tiles, row-major backward operand, one rank, no
+        # side stream) keeps no fp32 copy of its operand (`lean`).  The Gram reads the split images, and the only reader of Z
+        # in the step was the backward's epilogue; it now forms those two numbers per element from the data row, S and the
+        # centre -- the same bits (vgan_mmd_backward_bf3_rm_rebuild).  The forward writes `xrow`, the batch's data-set rows,
+        # because the step tail that rides in the backward launch advances the batch cursor while that launch runs.  Z is
+        # still written by every step taken before the bandwidth exists (the calibration reads it).  VGAN_Z_FP32=1 keeps the
+        # fp32 copy and the reading backward, for A/B runs.  MEASURED (MI355X, c3, alternating runs on one box,
+        # profiles/README.md): 0.1044 -> 0.1010 ms per step; the backward launch 25.9 -> 22.9 us, the forward 9.1 -> 8.7.
+        # (an ops provider says it has these launches with `bf3_rebuild`: a stand-in without them runs the step as before)
+        plain_bf3 = (getattr(ops, "bf3_rebuild", False) and self.bf3 and self.fused_prepare and self.gram_tile == 64 and
+                     self.rm_backward and world == 1 and not self.overlap and not self.front_sharded and
+                     ops.mmd_backward_bf3_tile(nl, d, self.bsplits, self.bwd_tile) == 64)
+        self.lean = plain_bf3 and os.environ.get("VGAN_Z_FP32", "0") != "1"
+        self.xrow = torch.zeros(n, dtype=torch.int32, device=self.dev) if self.lean else None
+        self._rebuild = None
         # the first-call bandwidth needs sum(L) over ALL pairs: computed by every rank from the full table (no collective)
         # (the calibration launch is the fp32 kernel: 64-wide tiles)
         self.tiles_cal = self.tiles if (world == 1 and self.gram_tile == 64 and not (self.overlap or self.xx_ride or self.xx_in_m4 or self.front_sharded)) else ops.build_tiles(n, 0, 0, 1, device=self.dev)
@@ -760,8 +775,12 @@ class NoKLStepEngine:
                     ntx = self.tiles.shape[0] - self.n_main
                     self._xx = ops.xx_job(self.Dh, self.Dl, self.dsq, self.tiles[self.n_main:], self.bw, self.partial[self.n_main:self.n_main + ntx])
                 xx = self._xx
-            ops.mask_project_forward_bf3(logits, self.data, self.perm, self.S, self.Z, self.sqn, self.Zh, self.Zl, self.ZTh, self.ZTl,
-                                         center=self.center, write_x=not self.x_ahead, xx=xx, **rowsel)
+            if self.lean:  # (Z is written while the bandwidth does not exist: the calibration reads it)
+                ops.mask_project_forward_bf3(logits, self.data, self.perm, self.S, self.Z, self.sqn, self.Zh, self.Zl, None, None,
+                                             center=self.center, xx=xx, write_z=not self.has_bw, xrow=self.xrow, **rowsel)
+            else:
+                ops.mask_project_forward_bf3(logits, self.data, self.perm, self.S, self.Z, self.sqn, self.Zh, self.Zl, self.ZTh, self.ZTl,
+                                             center=self.center, write_x=not self.x_ahead, xx=xx, **rowsel)
             return
         if self.x_ahead:  # the X half of Z / sq (and of the split images) is already in place
             ops.mask_project_forward(logits, self.data, self.perm, self.S, None, None, self.Z[n:], None, self.sqn[n:],
@@ -809,7 +828,12 @@ class NoKLStepEngine:
                 self._fin = ops.finalize_job(*fin_args)
         fin = self._fin
         if bf3:
-            if self.rm_backward:
+            if self.lean:
+                if self._rebuild is None:
+                    self._rebuild = ops.bwd_rebuild(self.data, self.xrow, self.S, self.center)
+                ops.mmd_backward_bf3_rm_rebuild(self.Wh, self.Wl, self.Zh, self.Zl, 2 * n, nl, d, self._rebuild, self.gU, self.bsplits, gstride,
+                                                fin, xx=self._late_xx_job() if self.xx_late_in_backward else None)
+            elif self.rm_backward:
                 ops.mmd_backward_bf3_rm(self.Wh, self.Wl, self.Zh, self.Zl, 2 * n, self.Z, n + lo, nl, d, self.Z[lo:lo + nl], self.gU,
                                         self.bsplits, gstride, fin, mul_shift=self.center, tile=self.bwd_tile,
                                         xx=self._late_xx_job() if self.xx_late_in_backward else None, rs_part=self.rs_part)
