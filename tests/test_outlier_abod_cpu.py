@@ -240,6 +240,14 @@ def test_class_is_exported_and_shares_the_pipeline_and_the_tail():
         owners = [c for c in vgan_amd.SubspaceABOD.__mro__ if name in vars(c)]
         assert len(owners) == 1 and owners[0] not in (vgan_amd.SubspaceABOD, vgan_amd.SubspaceEnsemble)
         assert getattr(vgan_amd.SubspaceABOD, name) is getattr(vgan_amd.SubspaceEnsemble, name)
+    for name in ["decision_function", "_require_fit"]:  # one copy for the three detectors, on the base
+        assert name in vars(outlier._SubspaceScorer)
+        for cls in (vgan_amd.SubspaceABOD, vgan_amd.SubspaceEnsemble, vgan_amd.SubspaceCBLOF, outlier._NeighborScorer):
+            assert name not in vars(cls)
+    for cls in (vgan_amd.SubspaceABOD, vgan_amd.SubspaceEnsemble, vgan_amd.SubspaceCBLOF):  # one attach rule, no flag of its own
+        assert not hasattr(cls, "_attached")
+    assert not hasattr(vgan_amd.SubspaceABOD(_mask(4, [[0, 1]]), [1.0]), "_attached")
+    assert not hasattr(vgan_amd.SubspaceEnsemble(_mask(4, [[0, 1]]), [1.0]), "_attached")
     assert "pyod" in vgan_amd.SubspaceABOD.__doc__ and "restatement" in vgan_amd.SubspaceABOD.__doc__
     with pytest.raises(ValueError, match="method must be 'knn', 'lof' or 'kde', got 'abod'"):
         vgan_amd.SubspaceEnsemble(_mask(4, [[0, 1]]), [1.0], method="abod")

@@ -266,6 +266,12 @@ def test_class_is_exported_and_ensemble_keeps_its_methods():
     assert issubclass(vgan_amd.SubspaceEnsemble, vgan_amd.outlier._SubspaceScorer)
     for name in ["_combine", "predict", "predict_proba", "threshold_", "labels_"]:  # shared, not copied
         assert name not in vars(vgan_amd.SubspaceCBLOF) and name not in vars(vgan_amd.SubspaceEnsemble)
+    for name in ["decision_function", "_require_fit"]:  # one copy for the three detectors, on the base
+        assert name in vars(vgan_amd.outlier._SubspaceScorer)
+        for cls in (vgan_amd.SubspaceCBLOF, vgan_amd.SubspaceEnsemble, vgan_amd.SubspaceABOD):
+            assert name not in vars(cls)
+    ens = vgan_amd.SubspaceCBLOF(_mask(4, [[0, 1]]), [1.0], n_clusters=2)
+    assert not hasattr(vgan_amd.SubspaceCBLOF, "_attached") and not hasattr(ens, "_attached")
     with pytest.raises(ValueError, match="method must be 'knn', 'lof' or 'kde', got 'cblof'"):
         vgan_amd.SubspaceEnsemble(_mask(4, [[0, 1]]), [1.0], method="cblof")
 

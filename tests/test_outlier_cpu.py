@@ -158,8 +158,12 @@ def test_planner_feature_lists_and_offsets():
     assert plan.feat[:8].tolist() == [1, 3, 0, 5, 9, 38, 39, 7]
     assert plan.feat[8:].tolist() == list(range(35))
     assert plan.feat.dtype == np.int32 and plan.col_off.dtype == np.int64
+    assert plan.given.tolist() == [0, 3, 1, 2]  # given subspace index -> processing position
+    np.testing.assert_array_equal(plan.order[plan.given], np.arange(plan.count))
+    np.testing.assert_array_equal(plan.given[plan.order], np.arange(plan.count))
     forced = SubspacePlan(m, engine="gram")
     assert forced.order.tolist() == [0, 1, 2, 3] and forced.gram.all()
+    assert forced.given.tolist() == [0, 1, 2, 3]
     assert not SubspacePlan(m, engine="exact").gram.any()
 
 
@@ -217,3 +221,59 @@ def test_bad_method_names_are_value_errors():
         vgan_amd.SubspaceEnsemble(np.ones((1, 3), bool), [1.0], method="iforest")
     with pytest.raises(ValueError, match="knn_method"):
         vgan_amd.SubspaceEnsemble(np.ones((1, 3), bool), [1.0], knn_method="max")
+
+
+# ---- the class without a GPU --------------------------------------------------------------------------------------------
+def _mask(d, feature_lists):
+    m = np.zeros((len(feature_lists), d), bool)
+    for s, feats in enumerate(feature_lists):
+        m[s, feats] = True
+    return m
+
+
+def test_defaults_and_constructor_keywords_without_a_gpu():
+    import inspect
+    import vgan_amd
+    params = inspect.signature(vgan_amd.SubspaceEnsemble.__init__).parameters
+    assert list(params)[1:] == ["subspaces", "proba", "method", "n_neighbors", "knn_method", "bandwidth", "engine", "splits",
+                                "workspace_bytes", "normalize", "combination", "contamination"]
+    ens = vgan_amd.SubspaceEnsemble(_mask(6, [[0, 1], [2, 3, 5]]), [0.25, 0.75])
+    assert (ens.method, ens.n_neighbors, ens.knn_method, ens.bandwidth) == ("knn", 5, "largest", 1.0)
+    assert (ens.engine, ens.splits, ens.workspace_bytes) == ("auto", None, 1 << 30)
+    assert ens.normalize is None and ens.combination == "sum" and ens.contamination == 0.1
+    assert ens.score_center_ is None and ens.score_scale_ is None and ens.plan.count == 2
+    assert ens.proba.dtype == np.float64 and ens.proba.tolist() == [0.25, 0.75]
+    ens = vgan_amd.SubspaceEnsemble(_mask(6, [[0, 1], [2, 3, 5]]), [0.5, 0.5], method="kde", n_neighbors=np.int64(7),
+                                    knn_method="median", bandwidth="scott", engine="gram", splits=3, workspace_bytes=1 << 20,
+                                    normalize="robust", combination="max", contamination=0.05)
+    assert (ens.method, ens.n_neighbors, ens.knn_method, ens.bandwidth) == ("kde", 7, "median", "scott")
+    assert (ens.engine, ens.splits, ens.workspace_bytes) == ("gram", 3, 1 << 20) and ens.plan.gram.all()
+    assert (ens.normalize, ens.combination, ens.contamination) == ("robust", "max", 0.05)
+    for kw, match in [(dict(splits=0), "splits"), (dict(splits=70000), "splits"), (dict(engine="fast"), "engine"),
+                      (dict(normalize="l2"), "normalize"), (dict(combination="mean"), "combination"),
+                      (dict(contamination=0.7), "contamination"), (dict(method="kde", bandwidth=-1.0), "bandwidth")]:
+        with pytest.raises(ValueError, match=match):
+            vgan_amd.SubspaceEnsemble(_mask(6, [[0, 1], [2, 3, 5]]), [0.5, 0.5], **kw)
+    with pytest.raises(ValueError, match="proba has 1 entries for 2 subspaces"):
+        vgan_amd.SubspaceEnsemble(_mask(6, [[0, 1], [2, 3, 5]]), [1.0])
+
+
+def test_fit_rejects_bad_data_before_the_device_is_touched():
+    """These raise ValueError with or without a GPU: on the CPU tier a call that reached the device would raise
+    VganHipError instead."""
+    import vgan_amd
+    m = _mask(6, [[0, 1], [2, 3, 5]])
+    X = np.random.default_rng(0).normal(size=(5, 6)).astype(np.float32)
+    with pytest.raises(ValueError, match=r"n_neighbors \+ 1 reference rows \(6\), got 5"):
+        vgan_amd.SubspaceEnsemble(m, [0.5, 0.5]).fit(X)
+    with pytest.raises(ValueError, match="KDE fit needs at least 2 reference rows, got 1"):
+        vgan_amd.SubspaceEnsemble(m, [0.5, 0.5], method="kde").fit(X[:1])
+    with pytest.raises(ValueError, match="X has 5 features, the subspaces 6"):
+        vgan_amd.SubspaceEnsemble(m, [0.5, 0.5], n_neighbors=3).fit(X[:, :5])
+    with pytest.raises(ValueError, match="2-d"):
+        vgan_amd.SubspaceEnsemble(m, [0.5, 0.5], n_neighbors=3).fit(X[0])
+    for call in ("decision_function", "predict", "kneighbors"):
+        with pytest.raises(RuntimeError, match="SubspaceEnsemble is not fitted"):
+            getattr(vgan_amd.SubspaceEnsemble(m, [0.5, 0.5]), call)(X)
+    with pytest.raises(ValueError, match="method must be 'linear' or 'unify'"):
+        vgan_amd.SubspaceEnsemble(m, [0.5, 0.5]).predict_proba(X, method="erf")

@@ -179,7 +179,6 @@ def cblof_baselines(row, ens, X, Xd, m, p, rows, C, iters, reps, t_fit, sklearn_
 
 
 def run_cblof(d, n, count, C, reps, iters, baselines=True, sklearn_sample=20):
-    from vgan_amd.outlier import ENGINES
     X, m, p = subspaces_for(d, n, count, seed=d + n + count)
     Xd = torch.as_tensor(X, device="cuda")
     S, dims = len(m), m.sum(axis=1)
@@ -212,15 +211,8 @@ def run_cblof(d, n, count, C, reps, iters, baselines=True, sklearn_sample=20):
     ops, dev = ens.ops, Xd.device
     jobs = []
     for first, cnt, gram in ens.plan.chunks(n, ens.workspace_bytes):
-        cols = int(ens.plan.col_off[first + cnt] - ens.plan.col_off[first])
-        Pq, sqq = ens._pack(Xd, first, cnt, gram, centred=True)
-        img = torch.empty(C * cols, dtype=torch.float32, device=dev)
-        img_sq = torch.empty(cnt, C, dtype=torch.float32, device=dev) if gram else None
-        ops.cluster_image(ens._centers, C, ens._table, first, cnt, ens._center, img, img_sq)
-        dd = ens.plan.dims[first:first + cnt]
-        ws = torch.empty(ops.cluster_lloyd_ws_bytes(n, C, cnt, int(dd.sum())) // 8, dtype=torch.float64, device=dev)
-        jobs.append((first, cnt, ENGINES["gram" if gram else "exact"], Pq, sqq, img, img_sq, int(dd.sum()), int(dd.max()), ws,
-                     torch.empty(cnt, n, 1, dtype=torch.int32, device=dev), torch.empty(cnt, n, dtype=torch.int32, device=dev)))
+        Pq, sqq, img, img_sq, label, ws, tot, mx, eng = ens._lloyd_buffers(Xd, first, cnt, gram)
+        jobs.append((first, cnt, eng, Pq, sqq, img, img_sq, tot, mx, ws, torch.empty(cnt, n, 1, dtype=torch.int32, device=dev), label))
     centers = ens._centers.clone()
     state = torch.zeros(3, S, dtype=torch.int32, device=dev)
 

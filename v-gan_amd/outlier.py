@@ -40,8 +40,13 @@ neighbours, the two-pass variance, the floor that degenerate rows take) is that 
 
 ``SubspaceCBLOF`` is the cluster-based detector: k-means over all subspaces at once and the cluster-based local outlier
 factor on its clusters (csrc/cluster.hip); its contract (initial centres, the E and M steps and their precision, the stop
-rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.  Both
-share the tail above (normalize, combination, contamination, predict) with ``SubspaceEnsemble`` through one base class.
+rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.
+
+The three classes differ in their scores only.  The constructor tail, the first touch of the device (at the first ``fit``,
+never in a constructor), the head and the tail of ``fit``, ``decision_function`` and the tail above (normalize,
+combination, contamination, predict) are ``_SubspaceScorer``; the neighbour search and its chunk loop are
+``_NeighborScorer``.  A new detector brings its own arguments, a row-count check (``_check_fit_rows``), ``_score`` and the
+extra attributes its ``fit`` publishes: the ``_SubspaceScorer`` docstring has the list.
 """
 import math
 import os
@@ -68,9 +73,17 @@ COMBINATIONS = {"sum": 0, "max": 1}  # VGAN_OUTLIER_COMBINE_*
 PROBA_METHODS = ("linear", "unify")
 
 
-def check_neighbors(k):
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_NEIGHBORS:
-        raise ValueError(f"n_neighbors must be an integer between 1 and {MAX_NEIGHBORS}, got {k!r}")
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _is_real(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def check_neighbors(k, least=1):
+    if not (_is_int(k) and least <= int(k) <= MAX_NEIGHBORS):
+        raise ValueError(f"n_neighbors must be an integer between {least} and {MAX_NEIGHBORS}, got {k!r}")
     return int(k)
 
 
@@ -87,7 +100,7 @@ def check_bandwidth(bandwidth):
         if bandwidth not in BANDWIDTH_RULES:
             raise ValueError(f"bandwidth must be a positive float, 'scott' or 'silverman', got {bandwidth!r}")
         return bandwidth
-    if isinstance(bandwidth, bool) or not isinstance(bandwidth, (int, float, np.integer, np.floating)):
+    if not _is_real(bandwidth):
         raise ValueError(f"bandwidth must be a positive float, 'scott' or 'silverman', got {bandwidth!r}")
     if not (np.isfinite(bandwidth) and bandwidth > 0):
         raise ValueError(f"bandwidth must be positive and finite, got {bandwidth!r}")
@@ -130,7 +143,7 @@ def check_combination(combination):
 
 def check_contamination(contamination):
     """A float in (0, 0.5] (pyod's range)."""
-    if isinstance(contamination, bool) or not isinstance(contamination, (int, float, np.integer, np.floating)):
+    if not _is_real(contamination):
         raise ValueError(f"contamination must be a float in (0, 0.5], got {contamination!r}")
     if not 0.0 < float(contamination) <= 0.5:  # False for nan
         raise ValueError(f"contamination must be in (0, 0.5], got {contamination!r}")
@@ -184,6 +197,7 @@ class SubspacePlan:
             raise ValueError(f"engine must be 'auto', 'exact' or 'gram', got {engine!r}")
         gram = dims >= gram_min_dims if engine == "auto" else np.full(len(dims), engine == "gram")
         self.order = np.argsort(gram, kind="stable").astype(np.int32)  # processing position -> subspace index
+        self.given = np.argsort(self.order)  # given subspace index -> processing position
         self.gram = gram[self.order]
         self.dims = dims[self.order].astype(np.int64)
         self.d = m.shape[1]
@@ -213,33 +227,79 @@ class SubspacePlan:
         return out
 
 
-def _device_matrix(X, d=None):
+def _matrix_shape(X, d):
+    """The shape of X, an array or a tensor on any device, after the checks every entry point makes on the host."""
+    shape = tuple(X.shape) if hasattr(X, "shape") else np.asarray(X).shape
+    if len(shape) != 2:
+        raise ValueError(f"X must be a 2-d matrix, got shape {shape}")
+    if shape[1] != d:
+        raise ValueError(f"X has {shape[1]} features, the subspaces {d}")
+    return shape
+
+
+def _device_matrix(X, d):
     X = torch.as_tensor(np.asarray(X) if not isinstance(X, torch.Tensor) else X)
-    if X.dim() != 2:
-        raise ValueError(f"X must be a 2-d matrix, got shape {tuple(X.shape)}")
-    if d is not None and X.shape[1] != d:
-        raise ValueError(f"X has {X.shape[1]} features, the subspaces {d}")
+    _matrix_shape(X, d)
     return X.to(device="cuda", dtype=torch.float32).contiguous()
 
 
 class _SubspaceScorer:
-    """What every per-subspace detector of this module shares: the device copy of the subspace table, the packed blocks,
-    and the tail after the [S, n] score matrix (statistics, transform, combination, threshold, predict).  A subclass
-    sets plan, proba, normalize, combination and contamination, calls _attach() once the device may be touched, keeps
-    the reference rows in _X and publishes decision_scores_."""
+    """What every per-subspace detector of this module shares: the constructor tail (_configure), the device copy of the
+    subspace table (_attach), the packed blocks, the head of fit (_begin_fit), the tail after the [S, n] score matrix
+    (statistics, transform, combination; _publish; threshold, predict) and decision_function.
 
-    _X = None
+    A detector provides: an __init__ that keeps its own arguments and calls _configure (no constructor touches the
+    device); _check_fit_rows(n), which raises ValueError when fit cannot work on n rows; _score(X, fitting) -> (float64
+    [n] ensemble scores, float32 [S, n] per-subspace scores in the given order), both on the device, which ends in
+    _combine(per, fitting); and a fit that runs X = _begin_fit(X), builds its fitted state, calls _score(..., fitting=True),
+    sets whatever attributes of its own it publishes and returns _publish(scores, per)."""
+
+    ops = None  # the library and the device tables below: set by _attach at the first fit
+    _fitted = False  # set by _publish
     _stats = None  # float64 [2, S] on the device (centres, scales), set by fit when normalize is given
     _decisions = None  # (threshold_, labels_), taken from decision_scores_ on first use
     score_center_ = score_scale_ = None
 
+    def _configure(self, subspaces, proba, engine, workspace_bytes, normalize, combination, contamination):
+        self.normalize = check_normalize(normalize)
+        self.combination = check_combination(combination)
+        self.contamination = check_contamination(contamination)
+        if engine == "auto":
+            engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
+        self.engine = engine
+        self.plan = SubspacePlan(subspaces, engine=engine)
+        self.proba = np.asarray(proba, dtype=np.float64).reshape(-1)
+        if self.proba.shape[0] != self.plan.count:
+            raise ValueError(f"proba has {self.proba.shape[0]} entries for {self.plan.count} subspaces")
+        self.workspace_bytes = int(workspace_bytes)
+
     def _attach(self):
+        if self.ops is not None:
+            return
         self.ops = default_ops()
         dev = "cuda"
         self._table = (torch.as_tensor(self.plan.feat, device=dev), torch.as_tensor(self.plan.feat_off, device=dev),
                        torch.as_tensor(self.plan.col_off, device=dev))
         self._rows = torch.as_tensor(self.plan.order, device=dev)
         self._proba = torch.as_tensor(self.proba, device=dev)
+
+    def _begin_fit(self, X):
+        """X on the device, after the host checks of its shape and row count; its column mean goes to _center."""
+        self._check_fit_rows(_matrix_shape(X, self.plan.d)[0])
+        self._attach()
+        X = _device_matrix(X, self.plan.d)
+        self._center = torch.empty(X.shape[1], dtype=torch.float32, device=X.device)
+        self.ops.col_mean(X, self._center)
+        return X
+
+    def _publish(self, scores, per):
+        self.decision_scores_ = scores.cpu().numpy()
+        self.per_subspace_scores_ = per.cpu().numpy()
+        if self.normalize is not None:
+            self.score_center_, self.score_scale_ = self._stats.cpu().numpy()
+        self._decisions = None
+        self._fitted = True
+        return self
 
     def _pack(self, X, first, count, gram, centred=None):
         """(packed block, squared row norms or None) of the chunk; centred on the column mean for the Gram engine, and for
@@ -284,8 +344,18 @@ class _SubspaceScorer:
         return self._decide()[1]
 
     def _require_fit(self):
-        if self._X is None:
+        if not self._fitted:
             raise RuntimeError(f"{type(self).__name__} is not fitted: call fit(X_train) first")
+
+    def decision_function(self, X, return_per_subspace=False):
+        """Ensemble scores of X against the fitted state (the reference set with nothing excluded, or the clusters),
+        float64 [n]; with return_per_subspace=True also the float32 [S, n] per-subspace scores (subspaces in the given
+        order)."""
+        self._require_fit()
+        scores, per = self._score(_device_matrix(X, self.plan.d), fitting=False)
+        if return_per_subspace:
+            return scores.cpu().numpy(), per.cpu().numpy()
+        return scores.cpu().numpy()
 
     def predict(self, X):
         """int [n]: 1 where decision_function(X) exceeds threshold_ (pyod's predict)."""
@@ -300,9 +370,20 @@ class _SubspaceScorer:
 
 
 class _NeighborScorer(_SubspaceScorer):
-    """The neighbour pipeline (pack -> knn -> refine) of the detectors that score a row from its k nearest reference rows:
-    a subclass sets n_neighbors, splits and workspace_bytes, and keeps the reference rows in _X and their column mean in
-    _center."""
+    """The neighbour pipeline (pack -> knn -> refine) of the detectors that score a row from its k nearest reference rows.
+    A detector on top of it also calls _configure_neighbors from its __init__ and keeps the reference rows that
+    _begin_fit returns in _X; _chunks is the chunk loop of whatever else sweeps the query rows over the reference rows."""
+
+    _X = None
+
+    def _configure_neighbors(self, n_neighbors, splits, least=1):
+        self.n_neighbors = check_neighbors(n_neighbors, least)
+        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
+            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
+        self.splits = splits
+
+    def _check_fit_rows(self, n):
+        check_reference_rows(n, self.n_neighbors, exclude_self=True)
 
     def _splits(self, nq, nr, count):
         if self.splits is not None:
@@ -310,24 +391,33 @@ class _NeighborScorer(_SubspaceScorer):
         blocks = -(-nq // 64) * count
         return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
 
+    def _blocks(self, Xq, first, count, gram):
+        Pr, sqr = self._pack(self._X, first, count, gram)
+        Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
+        return Pq, sqq, Pr, sqr
+
+    def _chunks(self, Xq):
+        """Yields (first, count, engine, nq, Pq, sqq, Pr, sqr) per chunk of the plan: the packed blocks and squared norms
+        of the nq query rows Xq and of the reference rows; Xq None is the reference set itself, whose blocks then serve as
+        both.  The generator keeps no reference to the blocks: they are freed when the consumer drops them."""
+        nr = self._X.shape[0]
+        nq = nr if Xq is None else Xq.shape[0]
+        for first, count, gram in self.plan.chunks(nr if Xq is None else nr + nq, self.workspace_bytes):
+            yield (first, count, ENGINES["gram" if gram else "exact"], nq, *self._blocks(Xq, first, count, gram))
+
     def _neighbors(self, Xq, kdist=None):
         """Yields (first, count, idx, dist) per chunk: the sorted refined lists [count, nq, k] of Xq (None: the reference
         set, self excluded).  kdist (fit only): [S, n] receives the k-th distances in processing order."""
         k, Xr = self.n_neighbors, self._X
         nr = Xr.shape[0]
-        nq = nr if Xq is None else Xq.shape[0]
-        rows = nr if Xq is None else nr + nq
-        for first, count, gram in self.plan.chunks(rows, self.workspace_bytes):
-            Pr, sqr = self._pack(Xr, first, count, gram)
-            Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
+        for first, count, engine, nq, Pq, sqq, Pr, sqr in self._chunks(Xq):
             J = self._splits(nq, nr, count)
             nbr = torch.empty(count, nq, k, dtype=torch.int32, device=Xr.device)
             part_d = part_i = None
             if J > 1:
                 part_d = torch.empty(count * J * nq * k, dtype=torch.float32, device=Xr.device)
                 part_i = torch.empty(count * J * nq * k, dtype=torch.int32, device=Xr.device)
-            self.ops.outlier_knn(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, k, Xq is None, ENGINES["gram" if gram else "exact"],
-                                 J, nbr, part_d, part_i)
+            self.ops.outlier_knn(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, k, Xq is None, engine, J, nbr, part_d, part_i)
             del Pq, Pr, sqq, sqr, part_d, part_i
             idx = torch.empty_like(nbr)
             dist = torch.empty(count, nq, k, dtype=torch.float32, device=Xr.device)
@@ -377,40 +467,28 @@ class SubspaceEnsemble(_NeighborScorer):
             raise ValueError(f"method must be 'knn', 'lof' or 'kde', got {method!r}")
         if knn_method not in KNN_METHODS:
             raise ValueError(f"knn_method must be one of {sorted(KNN_METHODS)}, got {knn_method!r}")
-        self.normalize = check_normalize(normalize)
-        self.combination = check_combination(combination)
-        self.contamination = check_contamination(contamination)
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        self._configure_neighbors(n_neighbors, splits)
         self.bandwidth = check_bandwidth(bandwidth) if method == "kde" else bandwidth
-        self.n_neighbors = check_neighbors(n_neighbors)
-        if engine == "auto":
-            engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
-        self.plan = SubspacePlan(subspaces, engine=engine)
-        p = np.asarray(proba, dtype=np.float64).reshape(-1)
-        if p.shape[0] != self.plan.count:
-            raise ValueError(f"proba has {p.shape[0]} entries for {self.plan.count} subspaces")
-        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
-            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
-        self.method, self.knn_method, self.engine, self.splits = method, knn_method, engine, splits
-        self.workspace_bytes = int(workspace_bytes)
-        self.proba = p
-        self._attach()
+        self.method, self.knn_method = method, knn_method
 
     # ---- pipeline --------------------------------------------------------------------------------
+    def _check_fit_rows(self, n):
+        if self.method == "kde":
+            check_kde_rows(n, exclude_self=True)
+        else:
+            super()._check_fit_rows(n)
+
     def _density(self, Xq):
         """float32 [S, nq]: -log p_s of Xq (None: the reference set, leave-one-out), rows in the given subspace order."""
         Xr = self._X
         nr = Xr.shape[0]
-        nq = nr if Xq is None else Xq.shape[0]
-        rows = nr if Xq is None else nr + nq
-        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xr.device)
-        for first, count, gram in self.plan.chunks(rows, self.workspace_bytes):
-            Pr, sqr = self._pack(Xr, first, count, gram)
-            Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
+        per = torch.empty(self.plan.count, nr if Xq is None else Xq.shape[0], dtype=torch.float32, device=Xr.device)
+        for first, count, engine, nq, Pq, sqq, Pr, sqr in self._chunks(Xq):
             pivot = torch.empty(count * nq, dtype=torch.int32, device=Xr.device)
             acc = torch.empty(count * nq, dtype=torch.int64, device=Xr.device)
-            self.ops.outlier_kde(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, self._bw, Xq is None,
-                                 ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count), pivot, acc, per,
-                                 self._rows[first:first + count])
+            self.ops.outlier_kde(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, self._bw, Xq is None, engine,
+                                 self._splits(nq, nr, count), pivot, acc, per, self._rows[first:first + count])
             del Pq, Pr, sqq, sqr
         return per
 
@@ -437,51 +515,19 @@ class SubspaceEnsemble(_NeighborScorer):
     def fit(self, X, y=None):
         """Keeps X resident as the reference set and scores it (self excluded): decision_scores_, float64 [n]; with
         normalize also score_center_ / score_scale_; threshold_ and labels_ from contamination."""
-        X = _device_matrix(X, self.plan.d)
-        if self.method == "kde":
-            check_kde_rows(X.shape[0], exclude_self=True)
-            self.bandwidth_ = resolve_bandwidth(self.bandwidth, X.shape[0], self.plan.dims[np.argsort(self.plan.order)])
-            self._bw = torch.as_tensor(self.bandwidth_[self.plan.order], device=X.device)
-        else:
-            check_reference_rows(X.shape[0], self.n_neighbors, exclude_self=True)
-        self._X = X
-        self._center = torch.empty(X.shape[1], dtype=torch.float32, device=X.device)
-        self.ops.col_mean(X, self._center)
+        self._X = X = self._begin_fit(X)
         n = X.shape[0]
-        if self.method == "lof":
+        if self.method == "kde":
+            self.bandwidth_ = resolve_bandwidth(self.bandwidth, n, self.plan.dims[self.plan.given])
+            self._bw = torch.as_tensor(self.bandwidth_[self.plan.order], device=X.device)
+        elif self.method == "lof":
             self._kdist = torch.empty(self.plan.count, n, dtype=torch.float32, device=X.device)
             self._lrd = torch.empty(self.plan.count, n, dtype=torch.float64, device=X.device)
-        scores, per = self._score(None, fitting=True)
-        self.decision_scores_ = scores.cpu().numpy()
-        self.per_subspace_scores_ = per.cpu().numpy()
-        if self.normalize is not None:
-            self.score_center_, self.score_scale_ = self._stats.cpu().numpy()
-        self._decisions = None
-        return self
-
-    def decision_function(self, X, return_per_subspace=False):
-        """Ensemble scores of X against the fitted reference set (nothing excluded), float64 [n]; with
-        return_per_subspace=True also the float32 [S, n] per-subspace scores (subspaces in the given order)."""
-        self._require_fit()
-        X = _device_matrix(X, self.plan.d)
-        if self.method == "kde":
-            check_kde_rows(self._X.shape[0], exclude_self=False)
-        else:
-            check_reference_rows(self._X.shape[0], self.n_neighbors, exclude_self=False)
-        scores, per = self._score(X, fitting=False)
-        if return_per_subspace:
-            return scores.cpu().numpy(), per.cpu().numpy()
-        return scores.cpu().numpy()
+        return self._publish(*self._score(None, fitting=True))
 
 
 # ---- angle-based scores (FastABOD) over the subspaces ----------------------------------------------------------------------
 ABOD_MIN_NEIGHBORS = 2  # one pair
-
-
-def check_abod_neighbors(k):
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not ABOD_MIN_NEIGHBORS <= int(k) <= MAX_NEIGHBORS:
-        raise ValueError(f"n_neighbors must be an integer between {ABOD_MIN_NEIGHBORS} and {MAX_NEIGHBORS}, got {k!r}")
-    return int(k)
 
 
 class SubspaceABOD(_NeighborScorer):
@@ -526,22 +572,8 @@ class SubspaceABOD(_NeighborScorer):
 
     def __init__(self, subspaces, proba, n_neighbors=10, engine="auto", splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
                  normalize=None, combination="sum", contamination=0.1):
-        self.normalize = check_normalize(normalize)
-        self.combination = check_combination(combination)
-        self.contamination = check_contamination(contamination)
-        self.n_neighbors = check_abod_neighbors(n_neighbors)
-        if engine == "auto":
-            engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
-        self.plan = SubspacePlan(subspaces, engine=engine)
-        p = np.asarray(proba, dtype=np.float64).reshape(-1)
-        if p.shape[0] != self.plan.count:
-            raise ValueError(f"proba has {p.shape[0]} entries for {self.plan.count} subspaces")
-        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
-            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
-        self.engine, self.splits = engine, splits
-        self.workspace_bytes = int(workspace_bytes)
-        self.proba = p
-        self._attached = False
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        self._configure_neighbors(n_neighbors, splits, least=ABOD_MIN_NEIGHBORS)
 
     def _score(self, Xq, fitting):
         """(ensemble scores float64 [n], per float32 [S, n] with the floor applied), both on the device."""
@@ -562,39 +594,11 @@ class SubspaceABOD(_NeighborScorer):
     def fit(self, X, y=None):
         """Keeps X resident as the reference set and scores it (self excluded): decision_scores_ (float64 [n]),
         per_subspace_scores_, score_floor_, n_degenerate_; with normalize also score_center_ / score_scale_."""
-        shape = tuple(X.shape) if hasattr(X, "shape") else np.asarray(X).shape
-        if len(shape) != 2:
-            raise ValueError(f"X must be a 2-d matrix, got shape {shape}")
-        if shape[1] != self.plan.d:
-            raise ValueError(f"X has {shape[1]} features, the subspaces {self.plan.d}")
-        check_reference_rows(shape[0], self.n_neighbors, exclude_self=True)
-        if not self._attached:
-            self._attach()
-            self._attached = True
-        X = _device_matrix(X, self.plan.d)
-        self._X = X
-        self._center = torch.empty(X.shape[1], dtype=torch.float32, device=X.device)
-        self.ops.col_mean(X, self._center)
+        self._X = self._begin_fit(X)
         scores, per = self._score(None, fitting=True)
-        self.decision_scores_ = scores.cpu().numpy()
-        self.per_subspace_scores_ = per.cpu().numpy()
         self.score_floor_ = self._floor.cpu().numpy()
         self.n_degenerate_ = self._n_degenerate.cpu().numpy().astype(np.int64)
-        if self.normalize is not None:
-            self.score_center_, self.score_scale_ = self._stats.cpu().numpy()
-        self._decisions = None
-        return self
-
-    def decision_function(self, X, return_per_subspace=False):
-        """Ensemble scores of X against the fitted reference set (nothing excluded), float64 [n]; with
-        return_per_subspace=True also the float32 [S, n] per-subspace scores (subspaces in the given order)."""
-        self._require_fit()
-        X = _device_matrix(X, self.plan.d)
-        check_reference_rows(self._X.shape[0], self.n_neighbors, exclude_self=False)
-        scores, per = self._score(X, fitting=False)
-        if return_per_subspace:
-            return scores.cpu().numpy(), per.cpu().numpy()
-        return scores.cpu().numpy()
+        return self._publish(scores, per)
 
 
 # ---- k-means + CBLOF over the subspaces ----------------------------------------------------------------------------------
@@ -602,14 +606,6 @@ MAX_CLUSTERS = 64  # VGAN_CLUSTER_MAX_CLUSTERS: the centres of a subspace are on
 # Lloyd iterations enqueued between two looks at the done flags.  An iteration after a subspace has finished costs its
 # launches an early return, a look costs a blocking copy: DESIGN.md section 9 has the measurement behind the value.
 POLL_STRIDE = 4
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
-def _is_real(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
 
 
 def check_cblof_params(n_clusters, alpha, beta, max_iter, tol):
@@ -761,23 +757,11 @@ class SubspaceCBLOF(_SubspaceScorer):
                  tol=1e-4, seed=0, engine="auto", workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum",
                  contamination=0.1):
         self.n_clusters, self.alpha, self.beta, self.max_iter, self.tol = check_cblof_params(n_clusters, alpha, beta, max_iter, tol)
-        self.normalize = check_normalize(normalize)
-        self.combination = check_combination(combination)
-        self.contamination = check_contamination(contamination)
-        if engine == "auto":
-            engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
-        self.plan = SubspacePlan(subspaces, engine=engine)
-        p = np.asarray(proba, dtype=np.float64).reshape(-1)
-        if p.shape[0] != self.plan.count:
-            raise ValueError(f"proba has {p.shape[0]} entries for {self.plan.count} subspaces")
-        self._given = np.argsort(self.plan.order)  # given subspace index -> processing position
-        self.init = check_kmeans_init(init, self.n_clusters, self.plan.dims[self._given])
-        self.use_weights, self.seed, self.engine = bool(use_weights), seed, engine
-        self.workspace_bytes = int(workspace_bytes)
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        self.init = check_kmeans_init(init, self.n_clusters, self.plan.dims[self.plan.given])
+        self.use_weights, self.seed = bool(use_weights), seed
         self.poll_stride = POLL_STRIDE
         self.keep_iteration_labels = False
-        self.proba = p
-        self._attached = False
 
     # ---- pipeline --------------------------------------------------------------------------------
     def _initial_centers(self, X, n):
@@ -801,6 +785,22 @@ class SubspaceCBLOF(_SubspaceScorer):
         var = np.concatenate([host[:, c:c + 64].astype(np.float64).var(axis=0) for c in range(0, host.shape[1], 64)])
         return np.array([self.tol * var[self.plan.feat[self.plan.feat_off[z]:self.plan.feat_off[z + 1]]].mean() for z in range(S)])
 
+    def _lloyd_buffers(self, X, first, count, gram):
+        """(Pq, sqq, img, img_sq, label, ws, sum of d_s, largest d_s, engine) of a chunk, as vgan_cluster_lloyd takes them:
+        the packed block of X, the float32 image of the current centres, the iteration labels (-1) and the workspace."""
+        n, C, dev = X.shape[0], self.n_clusters, X.device
+        # both engines get operands centred on the column mean here: a centre is a float64 mean, and rounding it to
+        # float32 about the mean instead of about 0 keeps that rounding small on data with a large offset
+        cols = int(self.plan.col_off[first + count] - self.plan.col_off[first])
+        dims = self.plan.dims[first:first + count]
+        Pq, sqq = self._pack(X, first, count, gram, centred=True)
+        img = torch.empty(C * cols, dtype=torch.float32, device=dev)
+        img_sq = torch.empty(count, C, dtype=torch.float32, device=dev) if gram else None
+        self.ops.cluster_image(self._centers, C, self._table, first, count, self._center, img, img_sq)
+        label = torch.full((count, n), -1, dtype=torch.int32, device=dev)
+        ws = torch.empty(self.ops.cluster_lloyd_ws_bytes(n, C, count, int(dims.sum())) // 8, dtype=torch.float64, device=dev)
+        return Pq, sqq, img, img_sq, label, ws, int(dims.sum()), int(dims.max()), ENGINES["gram" if gram else "exact"]
+
     def _lloyd(self, X):
         """Chunks outermost, iterations inside: a chunk is packed once.  The host enqueues poll_stride iterations at a
         time and then reads the chunk's done flags through one pinned buffer."""
@@ -812,23 +812,12 @@ class SubspaceCBLOF(_SubspaceScorer):
         flags = torch.empty(S, dtype=torch.int32).pin_memory()
         stream = torch.cuda.current_stream()
         for first, count, gram in self.plan.chunks(n, self.workspace_bytes):
-            # both engines get operands centred on the column mean here: a centre is a float64 mean, and rounding it to
-            # float32 about the mean instead of about 0 keeps that rounding small on data with a large offset
-            cols = int(self.plan.col_off[first + count] - self.plan.col_off[first])
-            dims = self.plan.dims[first:first + count]
-            Pq, sqq = self._pack(X, first, count, gram, centred=True)
-            img = torch.empty(C * cols, dtype=torch.float32, device=dev)
-            img_sq = torch.empty(count, C, dtype=torch.float32, device=dev) if gram else None
-            center = self._center
-            self.ops.cluster_image(self._centers, C, self._table, first, count, center, img, img_sq)
-            label = torch.full((count, n), -1, dtype=torch.int32, device=dev)
-            ws = torch.empty(self.ops.cluster_lloyd_ws_bytes(n, C, count, int(dims.sum())) // 8, dtype=torch.float64, device=dev)
+            Pq, sqq, img, img_sq, label, ws, total, widest, engine = self._lloyd_buffers(X, first, count, gram)
             launched = 0
             while launched < self.max_iter:
                 it = min(max(1, int(self.poll_stride)), self.max_iter - launched)
-                self.ops.cluster_lloyd(Pq, sqq, X, self._table, first, count, int(dims.sum()), int(dims.max()), C,
-                                       ENGINES["gram" if gram else "exact"], center, self._tol_var, self._centers, img, img_sq,
-                                       label, self._changed, self._done, self._iters, ws, it)
+                self.ops.cluster_lloyd(Pq, sqq, X, self._table, first, count, total, widest, C, engine, self._center, self._tol_var,
+                                       self._centers, img, img_sq, label, self._changed, self._done, self._iters, ws, it)
                 launched += it
                 flags[:count].copy_(self._done[first:first + count], non_blocking=True)
                 stream.synchronize()
@@ -848,31 +837,24 @@ class SubspaceCBLOF(_SubspaceScorer):
                                label=label, score=per, score_row=self._rows)
         return per, label
 
-    def _require_fit(self):  # the centres, sizes and the large-cluster mask are the fitted state: X itself is not kept
-        if getattr(self, "_large", None) is None:
-            raise RuntimeError(f"{type(self).__name__} is not fitted: call fit(X_train) first")
+    def _score(self, X, fitting):
+        per, _ = self._final(X)
+        return self._combine(per, fitting), per
+
+    def _check_fit_rows(self, n):
+        if not isinstance(self.init, tuple) or self.init[0] == "rows":
+            resolve_kmeans_rows(self.init, n, self.n_clusters, self.plan.count, self.seed)  # its checks; the rows come later
+        elif n < self.n_clusters:
+            raise ValueError(f"fit needs at least n_clusters rows ({self.n_clusters}), got {n}")
 
     # ---- public surface --------------------------------------------------------------------------
     def fit(self, X, y=None):
         """k-means per subspace on X, then the CBLOF scores of X itself: decision_scores_ (float64 [n]),
         per_subspace_scores_, cluster_centers_, cluster_labels_, cluster_sizes_, large_cluster_mask_, n_iter_,
-        converged_, inertia_, all in the given subspace order."""
-        shape = tuple(X.shape) if hasattr(X, "shape") else np.asarray(X).shape
-        if len(shape) != 2:
-            raise ValueError(f"X must be a 2-d matrix, got shape {shape}")
-        if shape[1] != self.plan.d:
-            raise ValueError(f"X has {shape[1]} features, the subspaces {self.plan.d}")
-        if not isinstance(self.init, tuple) or self.init[0] == "rows":
-            resolve_kmeans_rows(self.init, shape[0], self.n_clusters, self.plan.count, self.seed)  # the checks, before the device
-        elif shape[0] < self.n_clusters:
-            raise ValueError(f"fit needs at least n_clusters rows ({self.n_clusters}), got {shape[0]}")
-        if not self._attached:
-            self._attach()
-            self._attached = True
-        X = _device_matrix(X, self.plan.d)
+        converged_, inertia_, all in the given subspace order.  The centres, the sizes and the large-cluster mask are the
+        fitted state: X itself is not kept."""
+        X = self._begin_fit(X)
         n, S, C, dev = X.shape[0], self.plan.count, self.n_clusters, X.device
-        self._center = torch.empty(X.shape[1], dtype=torch.float32, device=dev)
-        self.ops.col_mean(X, self._center)
         self._centers = torch.as_tensor(self._initial_centers(X, n), device=dev)
         self._tol_var = torch.as_tensor(self._tolerance(X), device=dev)
         self._lloyd(X)
@@ -884,9 +866,8 @@ class SubspaceCBLOF(_SubspaceScorer):
         sizes = self._sizes.cpu().numpy()
         large = np.stack([large_cluster_boundary(sizes[z], self.alpha, self.beta)[1] for z in range(S)])
         self._large = torch.as_tensor(large.astype(np.int32), device=dev)
-        per, _ = self._final(X)
-        scores = self._combine(per, fitting=True)
-        g = self._given
+        scores, per = self._score(X, fitting=True)
+        g = self.plan.given
         flat, off = self._centers.cpu().numpy(), C * self.plan.feat_off.astype(np.int64)
         self.cluster_centers_ = [flat[off[z]:off[z + 1]].reshape(C, -1).copy() for z in g]
         self.cluster_labels_ = labels.cpu().numpy()[g]
@@ -898,25 +879,10 @@ class SubspaceCBLOF(_SubspaceScorer):
         if self.keep_iteration_labels:
             self.last_iteration_labels_ = self._iteration_labels.cpu().numpy()[g]
             self._iteration_labels = None
-        self.decision_scores_ = scores.cpu().numpy()
-        self.per_subspace_scores_ = per.cpu().numpy()
-        if self.normalize is not None:
-            self.score_center_, self.score_scale_ = self._stats.cpu().numpy()
-        self._decisions = None
-        return self
-
-    def decision_function(self, X, return_per_subspace=False):
-        """Ensemble scores of X against the fitted clusters, float64 [n]; with return_per_subspace=True also the float32
-        [S, n] per-subspace CBLOF scores (subspaces in the given order)."""
-        self._require_fit()
-        per, _ = self._final(_device_matrix(X, self.plan.d))
-        scores = self._combine(per, fitting=False)
-        if return_per_subspace:
-            return scores.cpu().numpy(), per.cpu().numpy()
-        return scores.cpu().numpy()
+        return self._publish(scores, per)
 
     def predict_clusters(self, X):
         """int32 [S, n]: the nearest fitted centre of every row of X in every subspace (float64, (d2, index) order)."""
         self._require_fit()
         _, label = self._final(_device_matrix(X, self.plan.d), want_labels=True)
-        return label.cpu().numpy()[self._given]
+        return label.cpu().numpy()[self.plan.given]
