@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -64,6 +64,18 @@ struct vgan_xx_job;
 int vgan_linear_backward_params_xx_supported(int n, int in, int out); /* host-side query of that contract (1 / 0) */
 int vgan_linear_backward_params_xx(const float* dy, int lddy, const float* x, int ldx, float* dW, int lddw, int n, int in,
                                    int out, const struct vgan_xx_job* xx, vgan_stream_t stream);
+/* vgan_linear_backward_params (db == NULL, no slabs) on the 16-wave tall-skinny tiles with the contraction of every 32 x 32
+ * output tile cut over `parts` workgroups (1..8), part q over the batch rows [q kchunk, (q + 1) kchunk), kchunk = the rows per
+ * part rounded up to the 128-deep K tile, and combined INSIDE the launch: every part writes its partial tile to the workspace,
+ * the last one to arrive at the tile's ticket sums all parts in part order (deterministic, whoever arrives last), writes dW
+ * and resets the ticket.  For a long contraction over so few tiles that most of the chip would idle (the step's M_4: 50 tiles,
+ * K = 1024).  parts == 1 IS vgan_linear_backward_params.  parts > 1: the 16-wave kernel's contract (out, in, leading dimensions
+ * % 4 == 0, aligned bases) and a 16-byte aligned workspace of at least ..._ws_bytes(in, out, parts) bytes (0 for parts <= 1) that
+ * was ZEROED once before its first use and is not shared with a launch that may run at the same time; its first
+ * ceil(in/32) * ceil(out/32) int32 words are the tickets, which every launch leaves at 0. */
+int64_t vgan_linear_backward_params_ksplit_ws_bytes(int in, int out, int parts);
+int vgan_linear_backward_params_ksplit(const float* dy, int lddy, const float* x, int ldx, float* dW, int lddw, int n, int in,
+                                       int out, int parts, void* ws, int64_t ws_bytes, vgan_stream_t stream);
 /* dst[i] = sum over s < nslabs of src[s*slab_stride + i], in ascending s (bitwise reproducible) */
 int vgan_reduce_slabs(const float* src, int64_t slab_stride, int nslabs, float* dst, int64_t count,
                       vgan_stream_t stream);
@@ -398,6 +410,15 @@ typedef struct vgan_grouped_extras {
 } vgan_grouped_extras;
 int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras,
                          vgan_stream_t stream);
+/* vgan_gemm_grouped_ex with an in-launch K split per problem: kparts[i] (1..8) workgroups share each 32 x 32 tile of problem
+ * i and combine inside the launch as in vgan_linear_backward_params_ksplit (same workspace rules; the tickets, one int32 per tile
+ * of the split problems in problem order, lead the workspace).  kparts == NULL or all 1: exactly vgan_gemm_grouped_ex.  Otherwise
+ * the launch must be one the library runs on its 16-wave 32 x 32 tiles (every k >= 96, at most 256 tiles in all, the vector
+ * contract, no optimiser epilogue, no noise job; copy and fold jobs may ride) -- anything else is VGAN_ERR_ARG, as is kparts[i] > 1
+ * together with splitk > 1 (that form writes slabs of C for vgan_reduce_slabs).  extras may be NULL. */
+int64_t vgan_gemm_grouped_ksplit_ws_bytes(const vgan_gemm_problem* problems, int count, const int32_t* kparts);
+int vgan_gemm_grouped_ksplit(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras,
+                             const int32_t* kparts, void* ws, int64_t ws_bytes, vgan_stream_t stream);
 
 /* vgan_mask_project_forward fused with vgan_mmd_bf3_prepare for the training step: from logits [n, d] and the
  * batch rows it writes S [n, d], Z = [X ; U*X] ([2n, ldz] fp32), sq [2n] and the split images Zh, Zl [2n, kp],

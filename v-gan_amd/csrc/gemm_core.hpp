@@ -575,6 +575,69 @@ struct GemmTileKS {
     __device__ static __forceinline__ int col_of() { return threadIdx.x & 31; }
 };
 
+// ---- in-launch K split of GemmTileKS tiles ---------------------------------------------------------------------------
+// A long-K product on a handful of 32x32 tiles leaves most CUs idle while each busy one pulls its whole operand panels in,
+// one K tile of cold loads at a time.  Here a tile is computed by `parts` workgroups, part q over the contraction range
+// [q kchunk, (q + 1) kchunk) (kchunk a multiple of the K tile), and combined inside the launch, as TailSplit does for the wide
+// Gram (mmd_common.hpp, mmd_bf16.hip): every part writes its 4 KB partial tile to its slab with sc0 sc1 (write-through) stores,
+// each storing thread drains them (vmcnt(0)), and thread 0 takes the tile's relaxed device-scope ticket.  The part that draws
+// parts - 1 reads ALL slabs back in part order -- its own included, so the sum does not depend on who came last -- finishes
+// the tile and stores 0 to the ticket for the next launch.  Nobody waits or spins: no residency assumption.
+// MEASURED (MI355X, c3 step under the kernel trace, us per launch; profiles/README.md Round 5): M_4 (50 tiles, K = 1024)
+// 8.72 / 7.73 / 7.12 / 7.53 and the {M_3, M_2, M_1} launch (48 tiles, K = 788) 8.65 / 8.59 / 7.60 / 10.76 at 1 / 2 / 4 / 8
+// parts (8 parts of the latter are 385 workgroups: a second round).  A 256-deep K tile for the parts, so that a part of
+// 256 contraction indices is ONE memory latency instead of two, was slower (6.9 -> 7.3 and 7.4 -> 7.6 us at 4 parts): what
+// is left above the ~5 us floor is the combine's own chain (drain, ticket, slab read), not the K loop.
+// Workspace: [tickets: one int per split tile, zero before the first launch | slabs: tile-major, parts x 1024 floats].
+constexpr int kKSplitMaxParts = 8;
+constexpr int kKSplitSlabBytes = 32 * 32 * 4;
+static inline long ksplit_ticket_bytes(long tiles) { return (tiles * 4 + 255) / 256 * 256; }
+static inline int ksplit_kchunk(int k, int parts, int bk) { return ((k + parts - 1) / parts + bk - 1) / bk * bk; }
+
+struct KSplitWs {
+    float* slabs;
+    int* tickets;
+    int slab_bytes;  // whole slab region (< 2^31: buffer addressing)
+};
+
+// o[rr]: this thread's share of part `part`'s partial tile (NR * NTH == 1024).  Returns true in the workgroup that finishes the
+// tile, with o[] = the sum over the parts; `slot` = index of the tile among the launch's split tiles (ticket) and `slab0` = byte
+// offset of its first slab.  `lds` is the workgroup's one LDS array (free after run()): it carries the "I am last" broadcast.
+template <int NR, int NTH>
+__device__ __forceinline__ bool ksplit_finish(float (&o)[NR], const KSplitWs& ws, int slot, int slab0, int part, int parts, float* lds) {
+    static_assert(NR * NTH * 4 == kKSplitSlabBytes, "one 32x32 tile per workgroup");
+    const __amdgpu_buffer_rsrc_t slabs = __builtin_amdgcn_make_buffer_rsrc(ws.slabs, 0, ws.slab_bytes, 0x00020000);
+    constexpr int kCoherent = 17;  // aux: sc0 | sc1
+    const int mine = slab0 + part * kKSplitSlabBytes + (int)threadIdx.x * 4;
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[rr]), slabs, mine + rr * NTH * 4, 0, kCoherent);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // (also: every thread is done reading run()'s reduction scratch)
+    if (threadIdx.x == 0) {
+        const int old = __hip_atomic_fetch_add(ws.tickets + slot, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == parts - 1) __hip_atomic_store(ws.tickets + slot, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
+        lds[0] = old == parts - 1 ? 1.f : 0.f;
+    }
+    __syncthreads();
+    if (lds[0] == 0.f) return false;
+    // all loads in flight at once (one round trip, not `parts`): slots past the last part repeat it and are not added
+    float v[kKSplitMaxParts][NR];
+#pragma unroll
+    for (int q = 0; q < kKSplitMaxParts; ++q) {
+        const int theirs = slab0 + min(q, parts - 1) * kKSplitSlabBytes + (int)threadIdx.x * 4;
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) v[q][rr] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(slabs, theirs + rr * NTH * 4, 0, kCoherent));
+    }
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr) {
+        float s = v[0][rr];
+#pragma unroll
+        for (int q = 1; q < kKSplitMaxParts; ++q) s = q < parts ? s + v[q][rr] : s;
+        o[rr] = s;
+    }
+    return true;
+}
+
 template <int WM, int WN>
 __device__ __forceinline__ void zero_acc(f32x16 (&acc)[WM][WN]) {
 #pragma unroll

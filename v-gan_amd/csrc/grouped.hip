@@ -259,6 +259,70 @@ __global__ __launch_bounds__(1024, 1) void gemm_grouped_ks16_kernel(GroupedArgs 
     else tile_ks<MC, MC, 4, 16>(q, t, lds, x, qi);
 }
 
+// The same launch with some problems' contraction cut over several workgroups per tile and combined in the launch
+// (ksplit_finish, gemm_core.hpp).  A problem's workgroups are its tiles of part 0, then of part 1, ...
+struct GroupedKSplit {
+    KSplitWs ws;
+    int parts[VGAN_GEMM_MAX_GROUP], kchunk[VGAN_GEMM_MAX_GROUP];
+    int slot0[VGAN_GEMM_MAX_GROUP];  // first ticket of the problem
+    int slab0[VGAN_GEMM_MAX_GROUP];  // byte offset of its first slab
+};
+
+template <int LA, int LB>
+__device__ __forceinline__ void tile_ks_split(const vgan_gemm_problem& q, int t, int part, int parts, int kchunk, const KSplitWs& ws, int slot,
+                                              int slab0, float* lds) {
+    using G = GemmTileKS<QKS, LA, LB, 4, 16>;
+    const int gx = (q.n + 31) / 32;
+    const int m0 = (t / gx) * 32, n0 = (t % gx) * 32;
+    const int k0 = part * kchunk, klen = min(kchunk, q.k - k0);
+    float o[G::NR];
+    if (klen > 0) {  // (block-uniform)
+        const float* a = q.a + (LA == KC ? (long)k0 : (long)k0 * q.lda);
+        const float* b = q.b + (LB == KC ? (long)k0 : (long)k0 * q.ldb);
+        G::run(a, q.lda, b, q.ldb, m0, n0, q.m, q.n, klen, lds, o);
+    } else {
+#pragma unroll
+        for (int rr = 0; rr < G::NR; ++rr) o[rr] = 0.f;
+    }
+    if (!ksplit_finish<G::NR, G::NTH>(o, ws, slot, slab0, part, parts, lds)) return;
+    const int col = n0 + G::col_of();
+#pragma unroll
+    for (int rr = 0; rr < G::NR; ++rr) {
+        const int row = m0 + G::row_of(rr);
+        if (row < q.m && col < q.n) q.c[(long)row * q.ldc + col] = o[rr];
+    }
+}
+
+__global__ __launch_bounds__(1024, 1) void gemm_grouped_ks16_split_kernel(GroupedArgs g, GroupedExtras x, GroupedKSplit ks) {
+    constexpr int kLds = cmax(cmax(GemmTileKS<QKS, KC, MC, 4, 16>::kLdsFloats, GemmTileKS<QKS, MC, MC, 4, 16>::kLdsFloats),
+                              GemmTileKS<QKS, KC, KC, 4, 16>::kLdsFloats);
+    __shared__ __attribute__((aligned(16))) float lds[kLds];
+    if ((int)blockIdx.x >= g.tile_start[VGAN_GEMM_MAX_GROUP]) {
+        grouped_extra_jobs(x, blockIdx.x - g.tile_start[VGAN_GEMM_MAX_GROUP], g.count);
+        return;
+    }
+    int qi = 0;
+#pragma unroll
+    for (int i = 1; i < VGAN_GEMM_MAX_GROUP; ++i)
+        if (i < g.count && (int)blockIdx.x >= g.tile_start[i]) qi = i;
+    const vgan_gemm_problem& q = g.p[qi];
+    int t = blockIdx.x - g.tile_start[qi];
+    const int parts = ks.parts[qi];
+    if (parts <= 1) {  // (block-uniform)
+        if (q.kind == VGAN_GEMM_NN) tile_ks<KC, MC, 4, 16>(q, t, lds, x, qi);
+        else if (q.kind == VGAN_GEMM_NT) tile_ks<KC, KC, 4, 16>(q, t, lds, x, qi);
+        else tile_ks<MC, MC, 4, 16>(q, t, lds, x, qi);
+        return;
+    }
+    const int per = (g.tile_start[qi + 1] - g.tile_start[qi]) / parts;
+    const int part = t / per;
+    t %= per;
+    const int slot = ks.slot0[qi] + t, slab0 = ks.slab0[qi] + t * parts * kKSplitSlabBytes, kc = ks.kchunk[qi];
+    if (q.kind == VGAN_GEMM_NN) tile_ks_split<KC, MC>(q, t, part, parts, kc, ks.ws, slot, slab0, lds);
+    else if (q.kind == VGAN_GEMM_NT) tile_ks_split<KC, KC>(q, t, part, parts, kc, ks.ws, slot, slab0, lds);
+    else tile_ks_split<MC, MC>(q, t, part, parts, kc, ks.ws, slot, slab0, lds);
+}
+
 }  // namespace vgan
 
 using namespace vgan;
@@ -268,9 +332,34 @@ static inline int extra_grid(long work_items) {
     return (int)(g < 1 ? 1 : (g > 256 ? 256 : g));
 }
 
-extern "C" int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras,
-                                    vgan_stream_t stream) {
+// tickets and slabs an in-launch K split of these problems needs (0: nothing is split); -1: bad arguments
+static int64_t ksplit_need(const vgan_gemm_problem* problems, int count, const int32_t* kparts) {
+    if (!problems || count < 1 || count > VGAN_GEMM_MAX_GROUP) return -1;
+    long split_tiles = 0, slabs = 0;
+    for (int i = 0; i < count; ++i) {
+        const int parts = kparts ? kparts[i] : 1;
+        if (parts < 1 || parts > kKSplitMaxParts || problems[i].m <= 0 || problems[i].n <= 0) return -1;
+        if (parts == 1) continue;
+        const long t32 = (long)((problems[i].m + 31) / 32) * ((problems[i].n + 31) / 32);
+        split_tiles += t32;
+        slabs += t32 * parts;
+    }
+    return split_tiles == 0 ? 0 : ksplit_ticket_bytes(split_tiles) + slabs * kKSplitSlabBytes;
+}
+
+static int grouped_launch(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras, const int32_t* kparts, void* ws,
+                          int64_t ws_bytes, vgan_stream_t stream) {
     VGAN_CHECK_ARG(problems && count >= 1 && count <= VGAN_GEMM_MAX_GROUP);
+    bool ksplit = false;
+    for (int i = 0; i < count && kparts != nullptr; ++i) {
+        VGAN_CHECK_ARG(kparts[i] >= 1 && kparts[i] <= kKSplitMaxParts);
+        VGAN_CHECK_ARG(kparts[i] == 1 || problems[i].splitk <= 1);  // slabs of C for the caller, or the in-launch combine: not both
+        ksplit = ksplit || kparts[i] > 1;
+    }
+    if (ksplit) {
+        const int64_t need = ksplit_need(problems, count, kparts);
+        VGAN_CHECK_ARG(need > 0 && need < (1ll << 31) && ws != nullptr && aligned16(ws) && ws_bytes >= need);
+    }
     GroupedArgs g{};
     GroupedExtras x{};
     g.count = count;
@@ -361,15 +450,33 @@ extern "C" int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count
         kmin = problems[i].k < kmin ? problems[i].k : kmin;
         t32 += ((problems[i].m + 31) / 32) * ((problems[i].n + 31) / 32);
     }
-    if (vec && kmin >= 96 && t32 <= 256 && !epi && x.noise_blocks == 0 && !any_split) {  // (copy and fold jobs ride in this variant too)
-        int acc = 0;
+    const bool ks16 = vec && kmin >= 96 && t32 <= 256 && !epi && x.noise_blocks == 0 && !any_split;  // (copy and fold jobs ride in this variant too)
+    VGAN_CHECK_ARG(!ksplit || ks16);  // the in-launch K split exists for the 16-wave launch only
+    if (ks16) {
+        GroupedKSplit ks{};
+        int acc = 0, slots = 0, slab_bytes = 0;
         for (int i = 0; i < count; ++i) {
+            const int tiles_i = ((problems[i].m + 31) / 32) * ((problems[i].n + 31) / 32);
+            const int parts = ksplit ? kparts[i] : 1;
             g.ks[i] = 1;
             g.tile_start[i] = acc;
-            acc += ((problems[i].m + 31) / 32) * ((problems[i].n + 31) / 32);
+            acc += tiles_i * parts;
+            ks.parts[i] = parts;
+            if (parts > 1) {
+                ks.kchunk[i] = ksplit_kchunk(problems[i].k, parts, QKS);
+                ks.slot0[i] = slots;
+                ks.slab0[i] = slab_bytes;
+                slots += tiles_i;
+                slab_bytes += tiles_i * parts * kKSplitSlabBytes;
+            }
         }
         for (int i = count; i <= VGAN_GEMM_MAX_GROUP; ++i) g.tile_start[i] = acc;
-        hipLaunchKernelGGL(gemm_grouped_ks16_kernel, dim3(acc + surplus), dim3(1024), 0, (hipStream_t)stream, g, x);
+        if (ksplit) {
+            ks.ws = KSplitWs{reinterpret_cast<float*>(static_cast<char*>(ws) + ksplit_ticket_bytes(slots)), static_cast<int*>(ws), slab_bytes};
+            hipLaunchKernelGGL(gemm_grouped_ks16_split_kernel, dim3(acc + surplus), dim3(1024), 0, (hipStream_t)stream, g, x, ks);
+        } else {
+            hipLaunchKernelGGL(gemm_grouped_ks16_kernel, dim3(acc + surplus), dim3(1024), 0, (hipStream_t)stream, g, x);
+        }
         VGAN_CHECK_LAUNCH();
         return VGAN_OK;
     }
@@ -381,6 +488,21 @@ extern "C" int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count
     else hipLaunchKernelGGL((gemm_grouped_kernel<1, false>), grid, block, 0, st, g, x);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
+}
+
+extern "C" int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras,
+                                    vgan_stream_t stream) {
+    return grouped_launch(problems, count, extras, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int64_t vgan_gemm_grouped_ksplit_ws_bytes(const vgan_gemm_problem* problems, int count, const int32_t* kparts) {
+    const int64_t need = ksplit_need(problems, count, kparts);
+    return need < 0 ? 0 : need;
+}
+
+extern "C" int vgan_gemm_grouped_ksplit(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras,
+                                        const int32_t* kparts, void* ws, int64_t ws_bytes, vgan_stream_t stream) {
+    return grouped_launch(problems, count, extras, kparts, ws, ws_bytes, stream);
 }
 
 extern "C" int vgan_gemm_grouped(const vgan_gemm_problem* problems, int count, vgan_stream_t stream) {

@@ -144,6 +144,32 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void linear_bwd_params_ks
         if (row < out && col < in) dW[(long)row * lddw + col] = o[rr];
     }
 }
+// The 16-wave product with every tile's contraction cut over gridDim.z workgroups, combined in the launch (ksplit_finish,
+// gemm_core.hpp): blockIdx.z is the slowest grid index, so the tiles of part 0 are dispatched first, then part 1, ...
+__global__ __launch_bounds__(1024, 1) void linear_bwd_params_ks_split_kernel(const float* __restrict__ dy, int lddy,
+                                                                            const float* __restrict__ x, int ldx, float* __restrict__ dW,
+                                                                            int lddw, int n, int in, int out, int kchunk, KSplitWs ws) {
+    using G = GemmTileKS<KSBK, MC, MC, 4, 16>;
+    __shared__ __attribute__((aligned(16))) float lds[G::kLdsFloats];
+    const int m0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
+    const int part = blockIdx.z, parts = gridDim.z;
+    const int k0 = part * kchunk, klen = min(kchunk, n - k0);
+    float o[G::NR];
+    if (klen > 0) {  // (block-uniform)
+        G::run(dy + (long)k0 * lddy, lddy, x + (long)k0 * ldx, ldx, m0, n0, out, in, klen, lds, o);
+    } else {  // more parts than K tiles: this one adds zeros
+#pragma unroll
+        for (int rr = 0; rr < G::NR; ++rr) o[rr] = 0.f;
+    }
+    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
+    if (!ksplit_finish<G::NR, G::NTH>(o, ws, tile, tile * parts * kKSplitSlabBytes, part, parts, lds)) return;
+    const int col = n0 + G::col_of();
+#pragma unroll
+    for (int rr = 0; rr < G::NR; ++rr) {
+        const int row = m0 + G::row_of(rr);
+        if (row < out && col < in) dW[(long)row * lddw + col] = o[rr];
+    }
+}
 // The same tall-skinny product with the X-X tiles of the Gram riding behind it (mmd_xx.hpp): the M_4 launch of the training
 // step is long (8.5 us), occupies ~50 of the 256 CUs and is not L2-bound, and by then the X half of the split operand is
 // L2 / Infinity-Cache warm -- the carrier the cold-operand experiments of mmd_xx.hpp were missing.  1-D grid: product tiles
@@ -269,6 +295,31 @@ extern "C" int vgan_linear_backward_params(const float* dy, int lddy, const floa
     if (x_nslabs > 1) { if (vec) VGAN_BWP(4, true); else VGAN_BWP(1, true); }
     else { if (vec) VGAN_BWP(4, false); else VGAN_BWP(1, false); }
 #undef VGAN_BWP
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int64_t vgan_linear_backward_params_ksplit_ws_bytes(int in, int out, int parts) {
+    if (in <= 0 || out <= 0 || parts <= 1 || parts > kKSplitMaxParts) return 0;
+    const long tiles = (long)((in + 31) / 32) * ((out + 31) / 32);
+    return ksplit_ticket_bytes(tiles) + tiles * parts * kKSplitSlabBytes;
+}
+
+extern "C" int vgan_linear_backward_params_ksplit(const float* dy, int lddy, const float* x, int ldx, float* dW, int lddw, int n, int in,
+                                                  int out, int parts, void* ws, int64_t ws_bytes, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(parts >= 1 && parts <= kKSplitMaxParts);
+    if (parts == 1) return vgan_linear_backward_params(dy, lddy, x, ldx, 1, 0, dW, lddw, nullptr, n, in, out, 1, 0, stream);
+    VGAN_CHECK_ARG(dy && x && dW && n > 0 && in > 0 && out > 0 && lddy >= out && ldx >= in && lddw >= in);
+    // the shape contract of the 16-wave tall-skinny kernel
+    VGAN_CHECK_ARG((out % 4 == 0) && (lddy % 4 == 0) && (in % 4 == 0) && (ldx % 4 == 0) && aligned16(dy) && aligned16(x));
+    const int64_t need = vgan_linear_backward_params_ksplit_ws_bytes(in, out, parts);
+    VGAN_CHECK_ARG(ws != nullptr && aligned16(ws) && ws_bytes >= need && need < (1ll << 31));
+    const int gx = (in + 31) / 32, gy = (out + 31) / 32;
+    VGAN_CHECK_ARG(gy <= 65535);
+    const long tb = ksplit_ticket_bytes((long)gx * gy);
+    const KSplitWs k{reinterpret_cast<float*>(static_cast<char*>(ws) + tb), static_cast<int*>(ws), (int)(need - tb)};
+    hipLaunchKernelGGL(linear_bwd_params_ks_split_kernel, dim3(gx, gy, parts), dim3(1024), 0, (hipStream_t)stream, dy, lddy, x, ldx, dW, lddw, n,
+                       in, out, ksplit_kchunk(n, parts, KSBK), k);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }

@@ -67,6 +67,8 @@ SIGNATURES = {
     "vgan_linear_forward": (_i, [_p, _i, _i, _i64, _p, _i, _p, _p, _i, _i, _i, _i, _p]),
     "vgan_linear_backward_input": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
     "vgan_linear_backward_params": (_i, [_p, _i, _p, _i, _i, _i64, _p, _i, _p, _i, _i, _i, _i, _i64, _p]),
+    "vgan_linear_backward_params_ksplit_ws_bytes": (_i64, [_i, _i, _i]),
+    "vgan_linear_backward_params_ksplit": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "vgan_linear_backward_params_xx_supported": (_i, [_i, _i, _i]),
     "vgan_linear_backward_params_xx": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p]),
     "vgan_reduce_slabs": (_i, [_p, _i64, _i, _p, _i64, _p]),
@@ -105,6 +107,8 @@ SIGNATURES = {
     "vgan_adadelta_step_packed": (_i, [_p, _p, _p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _p, _i, _i, _i, _i, _u64, _p, _p]),
     "vgan_gemm_grouped": (_i, [_p, _i, _p]),
     "vgan_gemm_grouped_ex": (_i, [_p, _i, _p, _p]),
+    "vgan_gemm_grouped_ksplit_ws_bytes": (_i64, [_p, _i, _p]),
+    "vgan_gemm_grouped_ksplit": (_i, [_p, _i, _p, _p, _p, _i64, _p]),
     "vgan_mask_project_forward_bf3": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
     "vgan_mask_project_forward_bf3_ex": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p, _i, _p,
                                               _p]),

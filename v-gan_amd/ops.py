@@ -94,6 +94,26 @@ class HipOps:
                                                         _ptr(dW), dW.stride(0), _ptr(db), n, kin, out, int(splits), int(slab_stride),
                                                         self._stream()), "vgan_linear_backward_params")
 
+    def linear_backward_params_ksplit_ws_bytes(self, kin, out, parts):
+        return int(self.lib.vgan_linear_backward_params_ksplit_ws_bytes(int(kin), int(out), int(parts)))
+
+    def ksplit_workspace(self, nbytes, device=None):
+        """A zeroed workspace for the in-launch K split (tickets first, then slabs): allocate once, never share between
+        launches that may overlap."""
+        return torch.zeros(max(int(nbytes), 16) // 4 + 4, dtype=torch.int32, device=device or "cuda")
+
+    def linear_backward_params_ksplit(self, dy, x, dW, parts, ws):
+        """linear_backward_params (no bias, no slabs) with every output tile's contraction cut over `parts` workgroups and
+        combined inside the launch (deterministic); `ws` = ksplit_workspace(linear_backward_params_ksplit_ws_bytes(...)) or None
+        for parts == 1, which is linear_backward_params itself."""
+        _mat(dy, "dy"), _mat(x, "x"), _mat(dW, "dW")
+        n, out = dy.shape
+        kin = x.shape[1]
+        assert x.shape[0] == n and dW.shape == (out, kin)
+        _lib.check(self.lib.vgan_linear_backward_params_ksplit(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dW), dW.stride(0), n, kin, out,
+                                                               int(parts), _ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(),
+                                                               self._stream()), "vgan_linear_backward_params_ksplit")
+
     def linear_backward_params_xx_supported(self, n, kin, out):
         return bool(self.lib.vgan_linear_backward_params_xx_supported(int(n), int(kin), int(out)))
 
@@ -152,6 +172,7 @@ class HipOps:
     # this provider has the launches of the bf16x3 step without an fp32 operand copy: mask_project_forward_bf3(write_z=, xrow=)
     # and mmd_backward_bf3_rm_rebuild
     bf3_rebuild = True
+    chain_ksplit = True  # linear_backward_params_ksplit and gemm_grouped(kparts=...)
 
     def xx_job(self, Dh, Dl, dsq, tiles, bw, partial):
         """The X-X Gram tiles as a job for mask_project_forward_bf3 (`xx=`): Dh, Dl, dsq = split images / norms of the whole
@@ -416,7 +437,7 @@ class HipOps:
         """Tile edge (64 / 128) mmd_backward_bf3 runs for this shape (host-side query of the library's rule)."""
         return int(self.lib.vgan_mmd_backward_bf3_tile(int(nr), int(p), int(splits), int(tile)))
 
-    def gemm_grouped(self, problems, copy=None, adadelta=None, noise=None, fold=None):
+    def gemm_grouped(self, problems, copy=None, adadelta=None, noise=None, fold=None, kparts=None, ksplit_ws=None):
         """problems: up to 4 tuples (kind, A, B, C) with kind in "NN" (C = A.B), "NT" (C = A.B^T), "TN" (C = A^T.B); 2-D float32
         tensors with unit inner stride.  One launch; the products must not depend on each other.  A fifth tuple element
         `splits` > 1 cuts the contraction into that many slices run by different workgroups: C is then a contiguous
@@ -426,8 +447,32 @@ class HipOps:
           adadelta = dict(p, sq, acc, lr, rho, eps, weight_decay, grad_scale, layers=[(w_packed, off_w, off_b, out, in) per
                      problem (+ one more with extra_grad)], extra_grad=None): the optimiser update in the products' epilogue;
           noise = dict(next_noise, noise_cols, noise_ones_col, seed, step_counter): the next step's noise draw;
-          fold = a finalize_job() run by one surplus workgroup (the late half of a split step tail)."""
+          fold = a finalize_job() run by one surplus workgroup (the late half of a split step tail).
+        kparts = one count (1..8) per problem: that many workgroups share each 32 x 32 tile of the problem's contraction and
+        combine inside the launch (vgan_gemm_grouped_ksplit; long-K launches on the 16-wave tiles only); `ksplit_ws` =
+        ksplit_workspace(gemm_grouped_ksplit_ws_bytes(problems, kparts))."""
         assert 1 <= len(problems) <= _lib.GEMM_MAX_GROUP
+        if kparts is not None and all(int(v) == 1 for v in kparts):
+            kparts = None
+        arr = self._gemm_problems(problems)
+        if kparts is None and copy is None and adadelta is None and noise is None and fold is None:
+            _lib.check(self.lib.vgan_gemm_grouped(arr, len(problems), self._stream()), "vgan_gemm_grouped")
+            return
+        x = self._grouped_extras(len(problems), copy, adadelta, noise, fold)
+        if kparts is not None:
+            assert len(kparts) == len(problems)
+            kp = (ctypes.c_int32 * len(problems))(*[int(v) for v in kparts])
+            _lib.check(self.lib.vgan_gemm_grouped_ksplit(arr, len(problems), ctypes.byref(x), kp, _ptr(ksplit_ws),
+                                                         0 if ksplit_ws is None else ksplit_ws.numel() * ksplit_ws.element_size(),
+                                                         self._stream()), "vgan_gemm_grouped_ksplit")
+            return
+        _lib.check(self.lib.vgan_gemm_grouped_ex(arr, len(problems), ctypes.byref(x), self._stream()), "vgan_gemm_grouped_ex")
+
+    def gemm_grouped_ksplit_ws_bytes(self, problems, kparts):
+        kp = (ctypes.c_int32 * len(problems))(*[int(v) for v in kparts])
+        return int(self.lib.vgan_gemm_grouped_ksplit_ws_bytes(self._gemm_problems(problems), len(problems), kp))
+
+    def _gemm_problems(self, problems):
         arr = (_lib.GemmProblem * len(problems))()
         for q, (kind, A, B, C, *rest) in zip(arr, problems):
             if kind == "NT2":  # C = (A . B^T) . D^T in one tile pass: (kind, A, B, C, D, scratch)
@@ -457,9 +502,9 @@ class HipOps:
             assert k == k2 and tuple(C.shape) == (m, n), (kind, tuple(A.shape), tuple(B.shape), tuple(C.shape))
             q.a, q.b, q.c, q.kind, q.m, q.n, q.k = A.data_ptr(), B.data_ptr(), C.data_ptr(), code, m, n, k
             q.lda, q.ldb, q.ldc = A.stride(0), B.stride(0), C.stride(0)
-        if copy is None and adadelta is None and noise is None and fold is None:
-            _lib.check(self.lib.vgan_gemm_grouped(arr, len(problems), self._stream()), "vgan_gemm_grouped")
-            return
+        return arr
+
+    def _grouped_extras(self, nproblems, copy, adadelta, noise, fold):
         x = _lib.GroupedExtras()
         if copy is not None:
             src, dst = copy
@@ -474,7 +519,7 @@ class HipOps:
             x.lr, x.rho, x.eps, x.weight_decay, x.grad_scale = (float(a["lr"]), float(a.get("rho", 0.9)), float(a.get("eps", 1e-6)),
                                                                 float(a.get("weight_decay", 0.0)), float(a.get("grad_scale", 1.0)))
             extra = a.get("extra_grad")
-            assert len(a["layers"]) == len(problems) + (1 if extra is not None else 0)
+            assert len(a["layers"]) == nproblems + (1 if extra is not None else 0)
             for L, (w, off_w, off_b, out, inp) in zip(x.layer, a["layers"]):
                 _mat(w, "w_packed")
                 L.w_packed, L.off_w, L.off_b, L.ldp, L.out, L.inp = w.data_ptr(), int(off_w), int(off_b), w.stride(0), int(out), int(inp)
@@ -488,7 +533,7 @@ class HipOps:
             x.seed, x.step_counter = int(noise["seed"]) & 0xFFFFFFFFFFFFFFFF, noise["step_counter"].data_ptr()
         if fold is not None:
             x.fold = ctypes.addressof(fold)
-        _lib.check(self.lib.vgan_gemm_grouped_ex(arr, len(problems), ctypes.byref(x), self._stream()), "vgan_gemm_grouped_ex")
+        return x
 
     def mse_grad(self, target, pred, gscale, part, g):
         """part[ceil(n/4)] (float64) = partial sums of (pred - target)^2; g = gscale * (pred - target)."""

@@ -88,6 +88,27 @@ def _best_boundary(n_main, total, slots, can_split):
     return best
 
 
+CHAIN_KPARTS_AUTO = 4  # the measured winner of {1, 2, 4, 8} for both launches it applies to
+
+
+def chain_kparts(want, tiles, k, chain_flops=False):
+    """Workgroups per 32 x 32 output tile for one long-K launch of the collapsed chain's backward (in-launch K split,
+    vgan_linear_backward_params_ksplit / vgan_gemm_grouped_ksplit).  `tiles` = the launch's 32 x 32 output tiles, `k` = its
+    shortest contraction; `want` = VGAN_CHAIN_KPARTS: "auto", or 1 | 2 | 4 | 8 to force a count (measurement knob).
+    "auto" splits only where it was measured to win (MI355X, profiles/README.md, Round 5): a launch of 32-64 tiles -- a fifth of
+    the chip -- with a contraction of 768 or more, i.e. the c3 step's M_4 (50 tiles, K = 1024) and its first chain-backward
+    launch (48 tiles, K = 788).  Everything else stays at 1: the c1 / c2 chains (1-12 tiles, K <= 512: not measured, and near the
+    ~5 us floor of a dependent launch already), the flop-minimal association of c4 / c5 (hundreds of tiles; its long products use slabs of C)."""
+    if want != "auto":
+        parts = int(want)
+        if parts not in (1, 2, 4, 8):
+            raise ValueError(f"VGAN_CHAIN_KPARTS must be auto, 1, 2, 4 or 8, got {want!r}")
+        return parts
+    if chain_flops or not (32 <= tiles <= 64 and k >= 768):
+        return 1
+    return CHAIN_KPARTS_AUTO
+
+
 class FlatParams:
     """Re-homes a module's parameters into one flat buffer (16-byte aligned offsets) so that Adadelta
     and the gradient all-reduce are single streaming passes.  ``module`` keeps working: each
@@ -453,6 +474,24 @@ class NoKLStepEngine:
             late = self.tiles.shape[0] - self.n_main
             bwd_wgs = ((d + 63) // 64) * ((nl + 63) // 64) * self.bsplits + 1
             self.xx_late_in_backward = (ops.mmd_backward_bf3_tile(nl, d, self.bsplits, self.bwd_tile) == 64 and late <= 512 - bwd_wgs)
+        # In-launch K split of the two long-K launches of the chain's backward (chain_kparts): M_4 = dlogits^T [z|1] unless the
+        # X-X tiles ride behind it, and {M_3, M_2, M_1} on the depth association.  One zeroed workspace each, for the engine's life.
+        self.m4_kparts = self.tn_kparts = 1
+        self.m4_ws = self.tn_ws = None
+        if self.mode == "collapsed" and getattr(ops, "chain_ksplit", False):
+            want_kp = os.environ.get("VGAN_CHAIN_KPARTS", "auto")
+            e = self.e
+            t32 = lambda rows, cols: ((rows + 31) // 32) * ((cols + 31) // 32)
+            if not (self.xx_in_m4 and not self.xx_late_in_backward):
+                self.m4_kparts = chain_kparts(want_kp, t32(dp, e[0]), nl, self.chain_flops)
+            tn_tiles = sum(t32(e[k], e[0]) for k in (3, 2, 1))
+            if not self.chain_flops and e[4] >= 96 and tn_tiles <= 256:  # (the library's 16-wave grouped launch: what can be split)
+                self.tn_kparts = chain_kparts(want_kp, tn_tiles, e[4])
+            if self.m4_kparts > 1:
+                self.m4_ws = ops.ksplit_workspace(ops.linear_backward_params_ksplit_ws_bytes(e[0], dp, self.m4_kparts), self.dev)
+            if self.tn_kparts > 1:
+                tn = [("TN", self.Wt[4], self.M[4], self.M[3]), ("TN", self.B3, self.M[4], self.M[2]), ("TN", self.B2, self.M[4], self.M[1])]
+                self.tn_ws = ops.ksplit_workspace(ops.gemm_grouped_ksplit_ws_bytes(tn, [self.tn_kparts] * 3), self.dev)
         # The default bf16x3 step (fused forward, 64-wide Gram and backward tiles, row-major backward operand, one rank, no
         # side stream) keeps no fp32 copy of its operand (`lean`).  The Gram reads the split images, and the only reader of Z
         # in the step was the backward's epilogue; it now forms those two numbers per element from the data row, S and the
@@ -702,10 +741,13 @@ class NoKLStepEngine:
             return
         e, d = self.e, self.d
         # M4[:d] = dlogits^T . [z|1]   (rows >= d stay zero: the homogeneous output coordinate carries no gradient)
-        # (the library runs this long contraction on its tall-skinny 16-wave tiles; row slabs + a reduction launch, or
-        # slab-summing staging loads in the consumers, were both measured slower)
+        # (the library runs this long contraction on its tall-skinny 16-wave tiles.  Cutting it over more workgroups pays only
+        # with the combine INSIDE the launch (m4_kparts, chain_kparts above): row slabs + a reduction launch, or slab-summing
+        # staging loads in the consumers, were both measured slower)
         if self.xx_in_m4 and not self.xx_late_in_backward:
             ops.linear_backward_params_xx(self.dlogits_pad, self.z_own, self.M[4][:self.dp], self._late_xx_job())
+        elif self.m4_kparts > 1:
+            ops.linear_backward_params_ksplit(self.dlogits_pad, self.z_own, self.M[4][:self.dp], self.m4_kparts, self.m4_ws)
         else:
             ops.linear_backward_params(self.dlogits_pad, self.z_own, self.M[4][:self.dp], None)  # pad columns are zero: rows d.. of M_4 too
         if dist:
@@ -731,9 +773,10 @@ class NoKLStepEngine:
             ops.gemm_grouped([("NT", M[2], At[1], Gt[2])])
             ops.adadelta_step_packed(self.fp.flat, self.pmap, self.Gt_all, self.Wt_all, self.fp.sq, self.fp.acc, **adadelta, **fused_noise)
             return
+        tn_split = dict(kparts=[self.tn_kparts] * 3, ksplit_ws=self.tn_ws) if self.tn_kparts > 1 else {}
         if not self.fuse_update:
             ops.gemm_grouped([("TN", self.Wt[4], M[4], M[3]), ("TN", self.B3, M[4], M[2]), ("TN", self.B2, M[4], M[1])],
-                             fold=self._fold if self.xx_in_m4 else None)
+                             fold=self._fold if self.xx_in_m4 else None, **tn_split)
             ops.gemm_grouped([("NT", M[4], At[3], Gt[4]), ("NT", M[3], At[2], Gt[3]), ("NT", M[2], At[1], Gt[2])])
             ops.adadelta_step_packed(self.fp.flat, self.pmap, self.Gt_all, self.Wt_all, self.fp.sq, self.fp.acc, **adadelta, **fused_noise)
             return
@@ -743,7 +786,7 @@ class NoKLStepEngine:
         # launch.  Wt_1 is also an OPERAND of that launch (At_1 = Wt_1 in Gt_2 = M_2 . At_1^T), so the launch before it
         # snapshots it (a copy job riding there) and the product reads the snapshot.
         ops.gemm_grouped([("TN", self.Wt[4], M[4], M[3]), ("TN", self.B3, M[4], M[2]), ("TN", self.B2, M[4], M[1])],
-                         copy=(self.Wt[1], self.At1s), fold=self._fold if self.xx_in_m4 else None)
+                         copy=(self.Wt[1], self.At1s), fold=self._fold if self.xx_in_m4 else None, **tn_split)
         w, off = self.widths, self.fp.offsets
         layers = [(self.Wt[k], off[2 * (k - 1)], off[2 * (k - 1) + 1], w[k], w[k - 1]) for k in (4, 3, 2, 1)]
         ops.gemm_grouped([("NT", M[4], At[3], Gt[4]), ("NT", M[3], At[2], Gt[3]), ("NT", M[2], self.At1s, Gt[2])],
