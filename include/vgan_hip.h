@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit and vgan_ecod_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -737,6 +737,45 @@ int vgan_cluster_final(const float* Xq, int ldq, int nq, int d, const int32_t* f
                        int n_clusters, const double* centers, const int32_t* large, int64_t* sizes, int use_weights,
                        int32_t* label, double* inertia_part, double* inertia, float* score, const int32_t* score_row,
                        int ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ECOD (Li, Zhao, Hu, Botta, Ionescu, Chen 2022; pyod's ECOD): empirical-CDF tail probabilities per feature, summed over
+ * the features of each subspace  (v-gan_amd/outlier.py: SubspaceECOD; kernels in csrc/outlier_ecod.hip).  All arithmetic
+ * is float64 on the float32 data; -0.0 counts as +0.0 everywhere.  n is the number of rows given to fit, 1 <= n <=
+ * VGAN_ECOD_MAX_ROWS.
+ * vgan_ecod_sort_columns: sorted [d, n_pad] float32 receives every column of X [n, d] (ldx) in ascending order, column f
+ *   at element f * n_pad; n_pad is the power of two with n <= n_pad < 2 n, and the entries past n are +inf.  A bitonic
+ *   network on orderable integer keys (runs of VGAN_ECOD_SORT_RUN keys in LDS, one launch per longer stride), in place in
+ *   `sorted`: no workspace.  The result is the unique ascending column (numpy.sort bit for bit once -0.0 is +0.0); the
+ *   network is data independent, so NaN input changes no trip count (a NaN sorts above or below every number by its sign).
+ * vgan_ecod_skew_sign: sign int8 [d] = the sign of the skewness of each column of a column-major image [d, ld] (n entries
+ *   a column; the sorted image serves): mu = sum(x) / n, m2 = sum((x - mu)^2), m3 = sum((x - mu)^3), two passes in a
+ *   fixed order; sign = 0 if m2 == 0, else -1 / 0 / +1 by m3.  The same bits from run to run.
+ * vgan_ecod_tail_counts: for the query rows Xq [rows, d] (ldq): cl [rows, d] = #{r : X[r, f] <= x} and cr [rows, d] =
+ *   #{r : X[r, f] >= x} (int32; upper_bound and n - lower_bound in the sorted column), by binary searches of a fixed
+ *   number of steps.  The counts are those among the n fitted rows: a new row is NOT counted (vgan_ecod_scores adds it).
+ * vgan_ecod_scores: from the counts, per (row, feature): ul = -log((cl + a) / (n + a)), ur = -log((cr + a) / (n + a)), a = 0
+ *   for query == 0 (fit: the row is among the n) and 1 otherwise (the row scored alone, appended to the n); the quotient
+ *   is one IEEE division, then log.  usk = ul if sign[f] < 0, ur if sign[f] > 0, ul + ur if sign[f] == 0.  With mask
+ *   float64 [d, ldm] (mask[f, s] = 1 if feature f belongs to subspace s, else 0; ldm >= S):
+ *     VGAN_ECOD_AGGREGATE_DIMENSION  score[s, i] = sum_f mask[f, s] max(ul, ur, usk)                      (pyod's code)
+ *     VGAN_ECOD_AGGREGATE_TAIL       score[s, i] = max(sum_f mask ul, sum_f mask ur, sum_f mask usk)       (the paper)
+ *   in float64 on the f64 matrix unit, f ascending, rounded to float32 into score [S, ld_score] (ld_score >= rows).
+ *   terms: float64 workspace of rows * d (DIMENSION) or 3 * rows * d (TAIL) elements.  The bits of score[s, i] depend on
+ *   the row's counts alone, not on its position in the call: any split of the rows over calls gives the same matrix.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_ECOD_SORT_RUN 2048
+#define VGAN_ECOD_MAX_ROWS 16777216 /* 2^24 */
+#define VGAN_ECOD_AGGREGATE_DIMENSION 0
+#define VGAN_ECOD_AGGREGATE_TAIL 1
+int vgan_ecod_sort_columns(const float* X, int ldx, int n, int d, float* sorted, int64_t n_pad, vgan_stream_t stream);
+int vgan_ecod_skew_sign(const float* sorted, int64_t ld, int n, int d, int8_t* sign, vgan_stream_t stream);
+int vgan_ecod_tail_counts(const float* Xq, int ldq, int rows, int d, const float* sorted, int64_t ld, int n, int32_t* cl,
+                          int32_t* cr, vgan_stream_t stream);
+int vgan_ecod_scores(const int32_t* cl, const int32_t* cr, int rows, int d, const int8_t* sign, int n, int query,
+                     int aggregate, const double* mask, int ldm, int S, double* terms, float* score, int64_t ld_score,
+                     vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

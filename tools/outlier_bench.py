@@ -19,6 +19,14 @@ difference of the two paths' ensemble scores.
     multiply-add rate of (b) from n sum_s k d_s 4 B and n sum_s k^2 d_s multiply-adds (the kernel pads k to 8, 16 or 32
     and forms the whole k x k matrix: the executed count is given as well).  --no-baselines leaves the torch path out
     (for a run under a profiler), --shape d,n,S picks one shape.
+  --method ecod: empirical-CDF scores (vgan_amd.SubspaceECOD, aggregate "dimension"): fit and decision_function (the
+    training rows as queries) against (a) a float64 torch restatement on the same GPU (torch.sort, torch.searchsorted,
+    the terms, one float64 matmul with the mask) and (b) numpy on the host (sort and searchsorted per feature, then a loop
+    over the subspaces); the fit split into its calls (sort, skew signs, tail counts, terms + product; the terms alone
+    from a call with a one-column mask); and the masked sums as the dense float64 product against the plain gather-sum
+    kernel of tools/ecod_gather.hip on the same terms (build it into tools/bin/libecod_gather.so first: its header has
+    the line), with the largest relative difference of the two.  product_s is terms + product minus terms alone: a
+    difference of two call times, not a kernel time.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -301,6 +309,135 @@ def run_abod(d, n, count, k, reps, baselines=True):
     return row
 
 
+def torch_ecod(X, mask64, n, sorted_cols=None, sign=None):
+    """The float64 torch restatement on the GPU: (scores [S, nq] float32, sorted, sign); sorted_cols None: the fit on X."""
+    fitting = sorted_cols is None
+    Xc = (X + 0.0).double()
+    if fitting:
+        sorted_cols = torch.sort(Xc, dim=0).values.t().contiguous()
+        mu = Xc.sum(dim=0) / n
+        e = Xc - mu
+        m2, m3 = (e * e).sum(dim=0), (e * e * e).sum(dim=0)
+        sign = torch.where(m2 == 0, torch.zeros_like(m3), torch.sign(m3))
+    q = Xc.t().contiguous()
+    cl = torch.searchsorted(sorted_cols, q, right=True).t()
+    cr = n - torch.searchsorted(sorted_cols, q, right=False).t()
+    a = 0 if fitting else 1
+    ul, ur = -torch.log((cl + a).double() / (n + a)), -torch.log((cr + a).double() / (n + a))
+    usk = torch.where(sign < 0, ul, torch.where(sign > 0, ur, ul + ur))
+    O = torch.maximum(torch.maximum(ul, ur), usk)
+    return (O @ mask64).t().float().contiguous(), sorted_cols, sign
+
+
+def numpy_ecod(X, m, p):
+    """numpy on the host: sort and searchsorted per feature, then one masked sum per subspace; float64 [n]."""
+    A = X.astype(np.float64) + 0.0
+    n, d = A.shape
+    mu = A.sum(axis=0) / n
+    m2, m3 = ((A - mu) ** 2).sum(axis=0), ((A - mu) ** 3).sum(axis=0)
+    sign = np.where(m2 == 0, 0.0, np.sign(m3))
+    O = np.empty_like(A)
+    for f in range(d):
+        col = np.sort(A[:, f])
+        ul = -np.log(np.searchsorted(col, A[:, f], side="right") / n)
+        ur = -np.log((n - np.searchsorted(col, A[:, f], side="left")) / n)
+        usk = ul if sign[f] < 0 else ur if sign[f] > 0 else ul + ur
+        O[:, f] = np.maximum(np.maximum(ul, ur), usk)
+    out = np.zeros(n)
+    for s in range(len(m)):
+        out += p[s] * O[:, np.flatnonzero(m[s])].sum(axis=1).astype(np.float32).astype(np.float64)
+    return out
+
+
+def load_gather():
+    import ctypes
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "libecod_gather.so")
+    if not os.path.exists(path):
+        raise SystemExit(f"{path} is missing: build it with the hipcc line in the header of tools/ecod_gather.hip")
+    fn = ctypes.CDLL(path).ecod_gather_sum
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                   ctypes.c_long, ctypes.c_void_p]
+    return fn
+
+
+def run_ecod(d, n, count, reps, baselines=True, random_masks=False):
+    """random_masks: `count` random subspaces (every feature with probability 0.3) on N(0, 1) data instead of a model's: the
+    product-against-gather comparison at a chosen S."""
+    from vgan_amd.outlier import ECOD_AGGREGATES
+    if random_masks:
+        rng = np.random.default_rng(d + n + count)
+        X = rng.normal(size=(n, d)).astype(np.float32)
+        m = rng.random((count, d)) < 0.3
+        m[np.arange(count), rng.integers(d, size=count)] = True
+        p = np.full(count, 1.0 / count)
+    else:
+        X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceECOD(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    ops, dev, inner = ens.ops, Xd.device, max(reps, 5)
+    rows = min(ens._chunk_rows(), n)
+    sorted_cols, sign = torch.empty_like(ens._sorted), torch.empty_like(ens._sign)
+    cl, cr = (torch.empty(rows * d, dtype=torch.int32, device=dev) for _ in range(2))
+    terms = torch.empty(rows * d, dtype=torch.float64, device=dev)
+    per = torch.empty(S, n, dtype=torch.float32, device=dev)
+    one = torch.ones(d, 1, dtype=torch.float64, device=dev)
+    per_one = torch.empty(1, n, dtype=torch.float32, device=dev)
+    agg = ECOD_AGGREGATES["dimension"]
+    t_sort, _ = timed(lambda: ops.ecod_sort_columns(Xd, sorted_cols), inner)
+    t_skew, _ = timed(lambda: ops.ecod_skew_sign(sorted_cols, n, sign), inner)
+    r1 = min(rows, n)  # the split below is taken on the first chunk and scaled by the number of rows
+    t_counts, _ = timed(lambda: ops.ecod_tail_counts(Xd[:r1], sorted_cols, n, cl, cr), inner)
+    t_scores, _ = timed(lambda: ops.ecod_scores(cl, cr, r1, sign, n, False, agg, ens._mask, terms, per[:, :r1]), inner)
+    t_terms, _ = timed(lambda: ops.ecod_scores(cl, cr, r1, sign, n, False, agg, one, terms, per_one[:, :r1]), inner)
+    gather = load_gather()
+    feat, feat_off = ens._table[0], ens._table[1]  # the processing order is the given order here
+    out_g = torch.empty(S, n, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def gather_sum():
+        rc = gather(terms.data_ptr(), r1, d, feat.data_ptr(), feat_off.data_ptr(), S, out_g.data_ptr(), n, stream)
+        assert rc == 0, rc
+
+    t_gather, _ = timed(gather_sum, inner)
+    ops.ecod_scores(cl, cr, r1, sign, n, False, agg, ens._mask, terms, per[:, :r1])
+    gather_sum()
+    a, b = per[:, :r1].double(), out_g[:, :r1].double()
+    scale = n / r1
+    t_product = max(t_scores - t_terms, 0.0)
+    row = {"method": "ecod", "d": d, "n": n, "S_sampled": None if random_masks else count, "S_distinct": S, "aggregate": "dimension",
+           "subspaces": "random, density 0.3" if random_masks else "approx_subspace_dist",
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "row_chunks": -(-n // rows), "fit_s": round(t_fit, 6), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6),
+           "decision_function_reps_s": td, "sort_s": round(t_sort, 6), "skew_s": round(t_skew, 6),
+           "counts_s": round(t_counts * scale, 6), "terms_and_product_s": round(t_scores * scale, 6),
+           "terms_alone_s": round(t_terms * scale, 6), "product_s": round(t_product * scale, 6),
+           "gather_sum_s": round(t_gather * scale, 6),
+           "product_over_gather": round(t_product / t_gather, 3) if t_gather > 0 else None,
+           "product_fp64_gflops": round(2.0 * r1 * d * S / max(t_product, 1e-9) / 1e9, 1),
+           "max_rel_diff_product_vs_gather": float(((a - b).abs() / b.abs().clamp(min=1e-300)).max())}
+    if baselines:
+        mask64 = ens._mask
+        t_tfit, ttf = timed(lambda: torch_ecod(Xd, mask64, n), reps)
+        want, sc, sg = torch_ecod(Xd, mask64, n)
+        t_tdec, ttd = timed(lambda: torch_ecod(Xd, mask64, n, sc, sg), reps)
+        got = torch.as_tensor(ens.per_subspace_scores_, device=dev).double()
+        rel = (got - want.double()).abs() / want.double().abs().clamp(min=1e-300)
+        t0 = time.perf_counter()
+        host = numpy_ecod(X, m, p)
+        t_host = time.perf_counter() - t0
+        row.update({"torch_fit_s": round(t_tfit, 6), "torch_fit_reps_s": ttf, "torch_decision_function_s": round(t_tdec, 6),
+                    "torch_decision_function_reps_s": ttd, "fit_speedup_vs_torch": round(t_tfit / t_fit, 2),
+                    "decision_function_speedup_vs_torch": round(t_tdec / t_dec, 2), "max_rel_diff_vs_torch": float(rel.max()),
+                    "skew_signs_agree_with_torch": bool((sg.cpu().numpy() == ens.skew_sign_).all()),
+                    "numpy_host_fit_s": round(t_host, 4), "fit_speedup_vs_numpy": round(t_host / t_fit, 1),
+                    "max_rel_diff_vs_numpy": float(np.max(np.abs(ens.decision_scores_ - host) / np.maximum(np.abs(host), 1e-300)))})
+    return row
+
+
 def host_normalized(per, proba, mode):
     """The numpy alternative to csrc/outlier_norm.hip: float64 statistics per row of per [S, n], transform, weighted sum."""
     x = per.astype(np.float64)
@@ -398,13 +535,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / ecod: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -441,6 +578,19 @@ def main():
             for k in (10, 32):
                 out["configs"].append(run_abod(d, n, count, k, args.reps, baselines=not args.no_baselines))
                 print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "ecod":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_ecod(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        if not args.shape:  # the dense product against the gather-sum at chosen S, small and wide
+            grid = [(10, 2000, 64), (784, 2000, 64)] if args.quick else [(10, 50_000, 64), (10, 50_000, 512), (784, 50_000, 64),
+                                                                         (784, 50_000, 512)]
+            out["product_vs_gather"] = [run_ecod(d, n, S, args.reps, baselines=False, random_masks=True) for d, n, S in grid]
         configs = []
     for d, n, count, k, with_base in configs:
         out["configs"].append(run_config(d, n, count, k, args.reps, with_base, args.method, bandwidth))

@@ -142,6 +142,10 @@ SIGNATURES = {
     "vgan_cluster_lloyd": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                 _p, _i64, _i, _p]),
     "vgan_cluster_final": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
+    "vgan_ecod_sort_columns": (_i, [_p, _i, _i, _i, _p, _i64, _p]),
+    "vgan_ecod_skew_sign": (_i, [_p, _i64, _i, _i, _p, _p]),
+    "vgan_ecod_tail_counts": (_i, [_p, _i, _i, _i, _p, _i64, _i, _p, _p, _p]),
+    "vgan_ecod_scores": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p, _p, _i64, _p]),
 }
 
 ABI_VERSION = 11

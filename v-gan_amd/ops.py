@@ -817,6 +817,43 @@ class HipOps:
                                                self._stream()), "vgan_cluster_final")
 
 
+    # ---- ECOD over subspaces (vgan_amd.outlier.SubspaceECOD) ------------------------------------------------
+    def ecod_sort_columns(self, X, sorted_cols):
+        """sorted_cols float32 [d, n_pad] (n_pad the power of two with n <= n_pad < 2 n): the ascending columns of X [n, d]."""
+        _mat(X, "X"), _vec(sorted_cols, "sorted_cols")
+        n, d = X.shape
+        assert sorted_cols.dim() == 2 and sorted_cols.shape[0] == d
+        _lib.check(self.lib.vgan_ecod_sort_columns(_ptr(X), X.stride(0), n, d, _ptr(sorted_cols), sorted_cols.shape[1], self._stream()),
+                   "vgan_ecod_sort_columns")
+
+    def ecod_skew_sign(self, sorted_cols, n, sign):
+        """sign int8 [d]: the skewness sign of the first n entries of every row of sorted_cols [d, ld]."""
+        _vec(sorted_cols, "sorted_cols"), _vec(sign, "sign", torch.int8)
+        d, ld = sorted_cols.shape
+        assert sign.numel() >= d
+        _lib.check(self.lib.vgan_ecod_skew_sign(_ptr(sorted_cols), ld, int(n), d, _ptr(sign), self._stream()), "vgan_ecod_skew_sign")
+
+    def ecod_tail_counts(self, Xq, sorted_cols, n, cl, cr):
+        """cl / cr int32 [rows, d]: how many of the n fitted values of each feature are <= / >= the query value."""
+        _mat(Xq, "Xq"), _vec(sorted_cols, "sorted_cols"), _vec(cl, "cl", torch.int32), _vec(cr, "cr", torch.int32)
+        rows, d = Xq.shape
+        assert sorted_cols.shape[0] == d and cl.numel() >= rows * d and cr.numel() >= rows * d
+        _lib.check(self.lib.vgan_ecod_tail_counts(_ptr(Xq), Xq.stride(0), rows, d, _ptr(sorted_cols), sorted_cols.shape[1], int(n),
+                                                  _ptr(cl), _ptr(cr), self._stream()), "vgan_ecod_tail_counts")
+
+    def ecod_scores(self, cl, cr, rows, sign, n, query, aggregate, mask, terms, score):
+        """score float32 [S, rows] (a view into the score matrix may be given) from the counts of `rows` rows; mask float64
+        [d, S]; terms: float64 workspace of rows * d (aggregate 0) or 3 * rows * d (aggregate 1) elements."""
+        _vec(cl, "cl", torch.int32), _vec(cr, "cr", torch.int32), _vec(sign, "sign", torch.int8), _mat(score, "score")
+        _vec(mask, "mask", torch.float64), _vec(terms, "terms", torch.float64)
+        d, S = mask.shape
+        assert cl.numel() >= rows * d and cr.numel() >= rows * d and sign.numel() >= d
+        assert terms.numel() >= (3 if aggregate else 1) * rows * d and score.shape[0] == S and score.shape[1] >= rows
+        _lib.check(self.lib.vgan_ecod_scores(_ptr(cl), _ptr(cr), int(rows), d, _ptr(sign), int(n), int(bool(query)), int(aggregate),
+                                             _ptr(mask), S, S, _ptr(terms), _ptr(score), score.stride(0), self._stream()),
+                   "vgan_ecod_scores")
+
+
 _default = None
 
 

@@ -42,7 +42,12 @@ neighbours, the two-pass variance, the floor that degenerate rows take) is that 
 factor on its clusters (csrc/cluster.hip); its contract (initial centres, the E and M steps and their precision, the stop
 rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.
 
-The three classes differ in their scores only.  The constructor tail, the first touch of the device (at the first ``fit``,
+``SubspaceECOD`` is the empirical-CDF detector (ECOD): per-feature tail probabilities from one sort per feature, summed
+over the features of each subspace as one dense float64 product with the 0/1 subspace mask (csrc/outlier_ecod.hip); it
+has no hyper-parameter and never sweeps pairs of rows.  Its contract (tail counts, the fit and the single-row-append
+rule, the skew sign, the two aggregates) is that class's docstring.
+
+The classes differ in their scores only.  The constructor tail, the first touch of the device (at the first ``fit``,
 never in a constructor), the head and the tail of ``fit``, ``decision_function`` and the tail above (normalize,
 combination, contamination, predict) are ``_SubspaceScorer``; the neighbour search and its chunk loop are
 ``_NeighborScorer``.  A new detector brings its own arguments, a row-count check (``_check_fit_rows``), ``_score`` and the
@@ -886,3 +891,117 @@ class SubspaceCBLOF(_SubspaceScorer):
         self._require_fit()
         _, label = self._final(_device_matrix(X, self.plan.d), want_labels=True)
         return label.cpu().numpy()[self.plan.given]
+
+
+# ---- ECOD: empirical-CDF tail probabilities over the subspaces ---------------------------------------------------------
+ECOD_MAX_ROWS = 1 << 24  # VGAN_ECOD_MAX_ROWS: the padded columns of the sort stay below 2^25 keys, the counts in int32
+ECOD_SORT_RUN = 2048  # VGAN_ECOD_SORT_RUN: keys of one LDS-resident run of the column sort
+ECOD_AGGREGATES = {"dimension": 0, "tail": 1}  # VGAN_ECOD_AGGREGATE_*
+
+
+def check_aggregate(aggregate):
+    if not (isinstance(aggregate, str) and aggregate in ECOD_AGGREGATES):
+        raise ValueError(f"aggregate must be 'dimension' or 'tail', got {aggregate!r}")
+    return aggregate
+
+
+def ecod_chunk_rows(d, n_subspaces, aggregate, workspace_bytes):
+    """Rows of one scoring chunk: the counts (two int32 [rows, d]), the float64 terms ([rows, d], three of them for "tail")
+    and the chunk's float32 scores [S, rows] fit in workspace_bytes; at least one row."""
+    planes = 3 if check_aggregate(aggregate) == "tail" else 1
+    return max(1, int(workspace_bytes) // (int(d) * (8 + 8 * planes) + 4 * int(n_subspaces)))
+
+
+class SubspaceECOD(_SubspaceScorer):
+    """Empirical-CDF outlier detector per subspace (ECOD: Li, Zhao, Hu, Botta, Ionescu, Chen 2022; pyod's ``ECOD``), combined
+    like the detectors of SubspaceEnsemble: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows; higher
+    is more outlying.  No hyper-parameter, no neighbour search, nothing n x n.
+
+    X is cast to float32; all arithmetic is float64 on those values, and -0.0 counts as +0.0.  n is the number of rows
+    given to ``fit``, 1 <= n <= ECOD_MAX_ROWS (2^24).  Per feature f, ``fit`` keeps the ascending column
+    (``sorted_columns_``, float32 [d, n]) and the sign of its skewness (``skew_sign_``, int [d]): mu = sum(x) / n, m2 =
+    sum((x - mu)^2), m3 = sum((x - mu)^3), g_f = 0 if m2 == 0 else sign(m3) (two passes, the same bits from run to run; a
+    constant column, where scipy's skew is NaN, has sign 0).
+
+    For a value x of feature f: cl = #{r : X[r, f] <= x}, cr = #{r : X[r, f] >= x} among the n fitted rows.
+    ``fit``: ul = -log(cl / n), ur = -log(cr / n) (the row counts itself).  ``decision_function``: ul = -log((cl + 1) /
+    (n + 1)), likewise ur: the score pyod gives a row scored alone, appended to the training set; it is never log 0 and
+    does not depend on the other rows of the batch, and the skew signs stay those of ``fit``.  So
+    ``decision_function(X_train)`` is not ``decision_scores_`` (as with SubspaceABOD).  The quotient is one IEEE division,
+    then log.  usk = ul if g_f < 0, ur if g_f > 0, ul + ur if g_f == 0.  Score of a row in subspace s (features F_s):
+
+        aggregate "dimension" (default, pyod's code):  sum_{f in F_s} max(ul, ur, usk)
+        aggregate "tail" (the paper's equation):       max(sum_f ul, sum_f ur, sum_f usk)
+
+    rounded to float32 into the [S, n] score matrix; normalize, combination, contamination, ``threshold_``, ``labels_``,
+    ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.
+
+    These rules are pyod's as its source is remembered here; pyod was not at hand to pin them (its ``decision_function``
+    concatenates the batch to the training set, which is deliberately not done here), so the definition above and its
+    numpy restatement in tests/test_outlier_ecod_cpu.py (counts pinned to scipy's rankdata, signs to scipy's skew) are
+    what binds, not pyod.
+
+    The tail terms do not depend on the subspace: they are formed once per row chunk and every subspace is a 0/1-masked
+    sum of them, one dense float64 product on the matrix unit.  workspace_bytes limits the counts, terms and scores of a
+    row chunk (ecod_chunk_rows).  The bits of a score depend on the row's counts alone: scores are bit-identical for every
+    workspace_bytes and from run to run.  NaN input leaves the scores unspecified and neither faults nor hangs.  All of it
+    runs in libvgan_hip.so (csrc/outlier_ecod.hip)."""
+
+    _host_sorted = None
+
+    def __init__(self, subspaces, proba, aggregate="dimension", workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None,
+                 combination="sum", contamination=0.1):
+        self.aggregate = check_aggregate(aggregate)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+
+    def _check_fit_rows(self, n):
+        if not 1 <= n <= ECOD_MAX_ROWS:
+            raise ValueError(f"ECOD fit needs between 1 and {ECOD_MAX_ROWS} rows, got {n}")
+
+    def _chunk_rows(self):
+        return ecod_chunk_rows(self.plan.d, self.plan.count, self.aggregate, self.workspace_bytes)
+
+    def _score(self, X, fitting):
+        nq, d = X.shape
+        S, dev = self.plan.count, X.device
+        rows = min(self._chunk_rows(), nq)
+        planes = 3 if self.aggregate == "tail" else 1
+        cl = torch.empty(rows * d, dtype=torch.int32, device=dev)
+        cr = torch.empty(rows * d, dtype=torch.int32, device=dev)
+        terms = torch.empty(planes * rows * d, dtype=torch.float64, device=dev)
+        per = torch.empty(S, nq, dtype=torch.float32, device=dev)
+        for r0 in range(0, nq, rows):
+            r1 = min(r0 + rows, nq)
+            self.ops.ecod_tail_counts(X[r0:r1], self._sorted, self._n, cl, cr)
+            self.ops.ecod_scores(cl, cr, r1 - r0, self._sign, self._n, not fitting, ECOD_AGGREGATES[self.aggregate], self._mask, terms,
+                                 per[:, r0:r1])
+        return self._combine(per, fitting), per
+
+    @property
+    def sorted_columns_(self):
+        """float32 [d, n]: the ascending columns of the fitted rows (-0.0 as +0.0); copied to the host on first use."""
+        self._require_fit()
+        if self._host_sorted is None:
+            self._host_sorted = self._sorted[:, :self._n].cpu().numpy()
+        return self._host_sorted
+
+    def fit(self, X, y=None):
+        """Sorts every column of X and takes its skew sign, then scores X itself by the fit rule: decision_scores_ (float64
+        [n]), per_subspace_scores_, skew_sign_, sorted_columns_; with normalize also score_center_ / score_scale_.  The
+        sorted columns and the signs are the fitted state: X itself is not kept."""
+        X = self._begin_fit(X)
+        n, d = X.shape
+        self._n, self._host_sorted = n, None
+        self._sorted = torch.empty(d, 1 << (n - 1).bit_length(), dtype=torch.float32, device=X.device)
+        self.ops.ecod_sort_columns(X, self._sorted)
+        self._sign = torch.empty(d, dtype=torch.int8, device=X.device)
+        self.ops.ecod_skew_sign(self._sorted, n, self._sign)
+        mask = np.zeros((d, self.plan.count), dtype=np.float64)  # column = given subspace index
+        for z, s in enumerate(self.plan.order):
+            mask[self.plan.feat[self.plan.feat_off[z]:self.plan.feat_off[z + 1]], s] = 1.0
+        self._mask = torch.as_tensor(mask, device=X.device)
+        scores, per = self._score(X, fitting=True)
+        self.skew_sign_ = self._sign.cpu().numpy().astype(np.int64)
+        return self._publish(scores, per)

@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceEnsemble
+from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -182,13 +182,18 @@ class _RunFolder:
         n_neighbors is not used there.
         method "abod" builds a SubspaceABOD (angle-based scores over the n_neighbors nearest neighbours, FastABOD; pyod's
         default there is 10): its keywords are engine, splits, workspace_bytes and the same normalize / combination /
-        contamination, e.g. outlier_ensemble(method="abod", n_neighbors=10, X=X)."""
+        contamination, e.g. outlier_ensemble(method="abod", n_neighbors=10, X=X).
+        method "ecod" builds a SubspaceECOD (empirical-CDF tail probabilities per feature, no hyper-parameter; pyod's
+        ECOD): its keywords are aggregate, workspace_bytes and the same normalize / combination / contamination, e.g.
+        outlier_ensemble(method="ecod", X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
             ens = SubspaceCBLOF(self.subspaces, self.proba, **kw)
         elif method == "abod":
             ens = SubspaceABOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
+        elif method == "ecod":
+            ens = SubspaceECOD(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
