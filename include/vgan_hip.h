@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit and vgan_ecod_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, vgan_ecod_* and vgan_iforest_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -776,6 +776,42 @@ int vgan_ecod_tail_counts(const float* Xq, int ldq, int rows, int d, const float
 int vgan_ecod_scores(const int32_t* cl, const int32_t* cr, int rows, int d, const int8_t* sign, int n, int query,
                      int aggregate, const double* mask, int ldm, int S, double* terms, float* score, int64_t ld_score,
                      vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Isolation forest (Liu, Ting, Zhou 2008; sklearn's IsolationForest, pyod's IForest): T random trees per subspace on psi
+ * sampled rows each; a row's score falls with its mean path length  (v-gan_amd/outlier.py: SubspaceIForest, whose docstring
+ * is the definition; kernels in csrc/outlier_iforest.hip).  L = ceil(log2 psi) is the depth limit, N = 2^(L + 1) the slots
+ * of a heap-numbered tree (root 1, children 2 i and 2 i + 1, slot 0 unused).  nodes is int32 [S, T, N, 2]: word 0 the split
+ * feature (a column of X; -1 a leaf, -2 an absent slot), word 1 the float32 threshold of an internal node (a row goes left
+ * iff x <= threshold), the sample rows of a leaf, 0 where absent.  2 <= psi <= VGAN_IFOREST_MAX_SAMPLES, 1 <= T <=
+ * VGAN_IFOREST_MAX_TREES; the three entries take the same (T, psi, L) and reject an L that is not ceil(log2 psi).
+ * vgan_iforest_build: the T trees of the subspaces first .. first + count - 1 of the table (feat, feat_off: the feature
+ *   lists, concatenated, and their offsets) from X [n, d] (ldx), 2 <= psi <= n <= 2^31 - 1, into their slots of nodes.
+ *   Tree (s, t) has the stream id = s T + t: its sample is rows feistel_perm(i, n, seed, id), i < psi (the permutation of
+ *   vgan_shuffle_index); a node of m rows at depth e is a leaf if m <= 1, e == L or no feature of the subspace varies on its
+ *   rows (float32 min == max, -0.0 as +0.0); otherwise the Philox4x32-10 words (w0, w1, ., .) of counter (node, 0,
+ *   0x49464F52, 0) and key (lo32(seed) ^ lo32(id), hi32(seed) ^ hi32(id) ^ 0x5bd1e995) choose the j-th varying feature in
+ *   ascending feature order, j = (w0 c) >> 32 for c varying features, and the threshold p = float32(lo + u (hi - lo)) with
+ *   u = (w1 + 0.5) 2^-32 and lo, hi the feature's min and max on the rows, in three separately rounded float64 operations;
+ *   p >= hi is replaced by lo.  One workgroup per tree, the rows in LDS; no workspace.  max_dims: no subspace of the range
+ *   has more features (at most VGAN_IFOREST_MAX_DIMS).  The trees depend on the row sets alone: the same bits from run
+ *   to run and for every split of the subspaces over calls.
+ * vgan_iforest_path_sums: sums int64 [count, ld_sums] (ld_sums >= rows): for every query row of Xq [rows, d] (ldq) and every
+ *   subspace of the range the total over its T trees of (e << 32) + cq[m], e the depth and m the size of the leaf the row
+ *   reaches; cq int64 [psi + 1] is the Q32 image of the average path length c(m), formed on the host (the device computes no
+ *   logarithm).  Integer sums: the same for every split of the rows or the subspaces over calls.  count <= 65535.
+ * vgan_iforest_scores: score float32 [count, ld_score] = float32(exp2(-(double(sum) / double(denom)))), denom = T cq[psi] > 0.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_IFOREST_MAX_SAMPLES 1024
+#define VGAN_IFOREST_MAX_TREES 1024
+#define VGAN_IFOREST_MAX_DIMS 8192
+int vgan_iforest_build(const float* X, int ldx, int64_t n, int d, const int32_t* feat, const int32_t* feat_off, int first,
+                       int count, int max_dims, int T, int psi, int L, uint64_t seed, int32_t* nodes, vgan_stream_t stream);
+int vgan_iforest_path_sums(const float* Xq, int ldq, int rows, int d, const int32_t* nodes, int first, int count, int T,
+                           int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums, vgan_stream_t stream);
+int vgan_iforest_scores(const int64_t* sums, int64_t ld_sums, int count, int rows, int64_t denom, float* score,
+                        int64_t ld_score, vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,11 @@ difference of the two paths' ensemble scores.
     kernel of tools/ecod_gather.hip on the same terms (build it into tools/bin/libecod_gather.so first: its header has
     the line), with the largest relative difference of the two.  product_s is terms + product minus terms alone: a
     difference of two call times, not a kernel time.
+  --method iforest: isolation forest (vgan_amd.SubspaceIForest, 100 trees on 256 rows each): fit and decision_function (the
+    training rows as queries); the fit split into its calls (build, path sums, scores); sklearn's IsolationForest(
+    n_estimators=100, n_jobs=16) fitted and scored per subspace on the CPUs for a sample of the subspaces, scaled to all of
+    them; and the kNN fit (k = 5) of SubspaceEnsemble on the same subspaces.  walk_steps_per_s counts S T n walks of the
+    measured mean depth.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -438,6 +443,58 @@ def run_ecod(d, n, count, reps, baselines=True, random_masks=False):
     return row
 
 
+def run_iforest(d, n, count, reps, baselines=True, sklearn_sample=8):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceIForest(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    ops, inner = ens.ops, max(reps, 5)
+    T, psi, L = ens.n_estimators, ens.max_samples_, ens.depth_limit_
+    trees = torch.empty_like(ens._trees)
+    sums = torch.empty(S * n, dtype=torch.int64, device="cuda")
+    per = torch.empty(S, n, dtype=torch.float32, device="cuda")
+    t_build, _ = timed(lambda: ops.iforest_build(Xd, ens._table, 0, S, int(dims.max()), psi, L, ens.seed, trees), inner)
+    t_sums, _ = timed(lambda: ops.iforest_path_sums(Xd, ens._trees, 0, S, psi, L, ens._cq, sums), inner)
+    t_scores, _ = timed(lambda: ops.iforest_scores(sums, S, n, ens._denom, per), inner)
+    depth = float((sums.view(S, n) >> 32).double().mean()) / T  # the mean number of steps of a walk
+    row = {"method": "iforest", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_estimators": T, "max_samples": psi,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "fit_s": round(t_fit, 6), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td,
+           "build_s": round(t_build, 6), "path_sums_s": round(t_sums, 6), "scores_s": round(t_scores, 6),
+           "tree_bytes": int(ens._trees.numel() * 4), "mean_depth": round(depth, 3),
+           "walk_steps_per_s": round(S * T * n * depth / t_sums / 1e9, 2), "walk_steps_unit": "1e9 steps / s",
+           "build_loads_nominal": float(psi) * float(dims.sum()) * T * L}
+    knn = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=5)
+    t_knn, tk = timed(lambda: knn.fit(Xd), reps)
+    row.update({"knn_fit_s": round(t_knn, 5), "knn_fit_reps_s": tk, "knn_over_iforest_fit": round(t_knn / t_fit, 2)})
+    if baselines:
+        try:
+            from sklearn.ensemble import IsolationForest
+            pick = np.unique(np.linspace(0, S - 1, min(S, sklearn_sample)).astype(int))
+            t_sk_fit = t_sk_score = 0.0
+            rank = []
+            for s in pick:
+                Xs = np.ascontiguousarray(X[:, np.flatnonzero(m[s])])
+                t0 = time.perf_counter()
+                model = IsolationForest(n_estimators=100, n_jobs=16, random_state=0).fit(Xs)
+                t1 = time.perf_counter()
+                theirs = -model.score_samples(Xs)
+                t_sk_score += time.perf_counter() - t1
+                t_sk_fit += t1 - t0
+                ours = ens.per_subspace_scores_[s].astype(np.float64)
+                rank.append(float(np.corrcoef(np.argsort(np.argsort(ours)), np.argsort(np.argsort(theirs)))[0, 1]))
+            scale = S / len(pick)
+            row.update({"sklearn_trees_s": round(t_sk_fit * scale, 4), "sklearn_score_s": round(t_sk_score * scale, 4),
+                        "sklearn_fit_and_score_s": round((t_sk_fit + t_sk_score) * scale, 4), "sklearn_subspaces_timed": int(len(pick)),
+                        "fit_speedup_vs_sklearn": round((t_sk_fit + t_sk_score) * scale / t_fit, 1),
+                        "rank_correlation_with_sklearn_min": round(min(rank), 4)})
+        except ImportError:
+            row["sklearn_fit_and_score_s"] = None
+    return row
+
+
 def host_normalized(per, proba, mode):
     """The numpy alternative to csrc/outlier_norm.hip: float64 statistics per row of per [S, n], transform, weighted sum."""
     x = per.astype(np.float64)
@@ -535,13 +592,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / ecod: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / ecod / iforest: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -591,6 +648,15 @@ def main():
             grid = [(10, 2000, 64), (784, 2000, 64)] if args.quick else [(10, 50_000, 64), (10, 50_000, 512), (784, 50_000, 64),
                                                                          (784, 50_000, 512)]
             out["product_vs_gather"] = [run_ecod(d, n, S, args.reps, baselines=False, random_masks=True) for d, n, S in grid]
+        configs = []
+    if args.method == "iforest":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_iforest(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     for d, n, count, k, with_base in configs:
         out["configs"].append(run_config(d, n, count, k, args.reps, with_base, args.method, bandwidth))

@@ -6,40 +6,7 @@
 
 namespace vgan {
 
-// ---- counter-based random permutation of [0, N): balanced Feistel network + cycle walking ---------------------------
-// A 2w-bit balanced Feistel network (2^(2w) >= N, < 4N) with a keyed 32-bit mixer as round function is a bijection of
-// [0, 2^(2w)) for ANY round function; walking the cycle until the value drops below N restricts it to a bijection of [0, N)
-// (expected < 4 evaluations).  Every index is computed independently: 16 B of state, no table, no sort, no atomics.
-__host__ __device__ inline unsigned feistel_mix(unsigned x, unsigned k) {
-    x ^= k;
-    x *= 0x9E3779B1u;
-    x ^= x >> 15;
-    x *= 0x85EBCA77u;
-    x ^= x >> 13;
-    x *= 0xC2B2AE3Du;
-    x ^= x >> 16;
-    return x;
-}
-constexpr int kFeistelRounds = 8;
-__host__ __device__ inline unsigned long long feistel_perm(unsigned long long i, unsigned long long N, int w, unsigned long long seed,
-                                                           unsigned long long epoch) {
-    const unsigned mask = (w >= 32) ? 0xFFFFFFFFu : ((1u << w) - 1u);
-    const unsigned k0 = (unsigned)seed ^ 0xA511E9B3u, k1 = (unsigned)(seed >> 32) ^ (unsigned)epoch, k2 = (unsigned)(epoch >> 32) ^ 0x63D83595u;
-    unsigned long long v = i;
-    do {
-        unsigned l = (unsigned)(v >> w) & mask, r = (unsigned)v & mask;
-#pragma unroll
-        for (int q = 0; q < kFeistelRounds; ++q) {
-            const unsigned f = feistel_mix(r, feistel_mix(k0 + 0x9E3779B9u * (unsigned)q, k1) ^ k2) & mask;
-            const unsigned nl = r;
-            r = l ^ f;
-            l = nl;
-        }
-        v = ((unsigned long long)l << w) | r;
-    } while (v >= N);
-    return v;
-}
-
+// ---- counter-based random permutation of [0, N): feistel_perm of vgan_common.hpp, one index per thread -------------------
 __global__ __launch_bounds__(kBlock) void shuffle_epoch_kernel(int* __restrict__ perm, long count, unsigned long long N, int w,
                                                               unsigned long long seed, unsigned long long epoch) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -120,12 +87,6 @@ __global__ __launch_bounds__(kBlock) void mask_unique_rank_kernel(const unsigned
 }  // namespace vgan
 
 using namespace vgan;
-
-static int feistel_half_bits(unsigned long long N) {
-    int w = 1;
-    while (w < 32 && (1ull << (2 * w)) < N) ++w;
-    return w;
-}
 
 extern "C" int vgan_shuffle_epoch(int32_t* perm, int64_t count, int64_t train_size, uint64_t seed, uint64_t epoch, vgan_stream_t stream) {
     VGAN_CHECK_ARG(perm && count > 0 && train_size > 0 && count <= train_size && train_size <= 0x7FFFFFFF);

@@ -148,6 +148,47 @@ __device__ __forceinline__ float uncentred_x(float xc, float c) { return __fadd_
 // the mask entry of a softmax value (src/models/Generator.py:20-21), tau = float32(1 / d)
 __device__ __forceinline__ float upper_mask(float s, float tau) { return s < tau ? s : 1.0f; }
 
+// ---- counter-based random permutation of [0, N): balanced Feistel network + cycle walking ---------------------------
+// A 2w-bit balanced Feistel network (2^(2w) >= N, < 4N) with a keyed 32-bit mixer as round function is a bijection of
+// [0, 2^(2w)) for ANY round function; walking the cycle until the value drops below N restricts it to a bijection of [0, N)
+// (expected < 4 evaluations).  Every index is computed independently: 16 B of state, no table, no sort, no atomics.
+__host__ __device__ inline unsigned feistel_mix(unsigned x, unsigned k) {
+    x ^= k;
+    x *= 0x9E3779B1u;
+    x ^= x >> 15;
+    x *= 0x85EBCA77u;
+    x ^= x >> 13;
+    x *= 0xC2B2AE3Du;
+    x ^= x >> 16;
+    return x;
+}
+constexpr int kFeistelRounds = 8;
+__host__ __device__ inline unsigned long long feistel_perm(unsigned long long i, unsigned long long N, int w, unsigned long long seed,
+                                                           unsigned long long epoch) {
+    const unsigned mask = (w >= 32) ? 0xFFFFFFFFu : ((1u << w) - 1u);
+    const unsigned k0 = (unsigned)seed ^ 0xA511E9B3u, k1 = (unsigned)(seed >> 32) ^ (unsigned)epoch, k2 = (unsigned)(epoch >> 32) ^ 0x63D83595u;
+    unsigned long long v = i;
+    do {
+        unsigned l = (unsigned)(v >> w) & mask, r = (unsigned)v & mask;
+#pragma unroll
+        for (int q = 0; q < kFeistelRounds; ++q) {
+            const unsigned f = feistel_mix(r, feistel_mix(k0 + 0x9E3779B9u * (unsigned)q, k1) ^ k2) & mask;
+            const unsigned nl = r;
+            r = l ^ f;
+            l = nl;
+        }
+        v = ((unsigned long long)l << w) | r;
+    } while (v >= N);
+    return v;
+}
+
+// w of feistel_perm for a range of N values: the smallest w <= 32 with 2^(2w) >= N
+inline int feistel_half_bits(unsigned long long N) {
+    int w = 1;
+    while (w < 32 && (1ull << (2 * w)) < N) ++w;
+    return w;
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace vgan

@@ -853,6 +853,37 @@ class HipOps:
                                              _ptr(mask), S, S, _ptr(terms), _ptr(score), score.stride(0), self._stream()),
                    "vgan_ecod_scores")
 
+    # ---- isolation forest over subspaces (vgan_amd.outlier.SubspaceIForest) ---------------------------------
+    def iforest_build(self, X, table, first, count, max_dims, psi, depth, seed, nodes):
+        """nodes int32 [S, T, N, 2] (N = 2^(depth + 1)) receives the T trees of the subspaces first .. first + count - 1,
+        built from X [n, d] on psi sampled rows each; max_dims: the most features of a subspace of the range."""
+        _mat(X, "X"), _vec(nodes, "nodes", torch.int32)
+        feat, feat_off, _ = table
+        n, d = X.shape
+        S, T = nodes.shape[:2]
+        assert nodes.dim() == 4 and nodes.shape[2] == 2 << depth and nodes.shape[3] == 2 and first + count <= S
+        _lib.check(self.lib.vgan_iforest_build(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), int(first), int(count),
+                                               int(max_dims), T, int(psi), int(depth), int(seed), _ptr(nodes), self._stream()),
+                   "vgan_iforest_build")
+
+    def iforest_path_sums(self, Xq, nodes, first, count, psi, depth, cq, sums):
+        """sums int64 [count, rows]: per query row of Xq and subspace of the range, the fixed-point path lengths summed over
+        the subspace's trees; cq int64 [psi + 1]: the Q32 average path lengths."""
+        _mat(Xq, "Xq"), _vec(nodes, "nodes", torch.int32), _vec(cq, "cq", torch.int64), _vec(sums, "sums", torch.int64)
+        rows, d = Xq.shape
+        S, T = nodes.shape[:2]
+        assert nodes.dim() == 4 and nodes.shape[2] == 2 << depth and nodes.shape[3] == 2 and first + count <= S
+        assert cq.numel() >= psi + 1 and sums.numel() >= count * rows
+        _lib.check(self.lib.vgan_iforest_path_sums(_ptr(Xq), Xq.stride(0), rows, d, _ptr(nodes), int(first), int(count), T, int(psi),
+                                                   int(depth), _ptr(cq), _ptr(sums), rows, self._stream()), "vgan_iforest_path_sums")
+
+    def iforest_scores(self, sums, count, rows, denom, score):
+        """score float32 [count, rows] (a view into the score matrix may be given) = exp2(-sums / denom)."""
+        _vec(sums, "sums", torch.int64), _mat(score, "score")
+        assert sums.numel() >= count * rows and score.shape[0] == count and score.shape[1] >= rows
+        _lib.check(self.lib.vgan_iforest_scores(_ptr(sums), int(rows), int(count), int(rows), int(denom), _ptr(score), score.stride(0),
+                                                self._stream()), "vgan_iforest_scores")
+
 
 _default = None
 

@@ -47,6 +47,11 @@ over the features of each subspace as one dense float64 product with the 0/1 sub
 has no hyper-parameter and never sweeps pairs of rows.  Its contract (tail counts, the fit and the single-row-append
 rule, the skew sign, the two aggregates) is that class's docstring.
 
+``SubspaceIForest`` is the isolation forest: random trees per subspace on a few hundred sampled rows each, built and walked
+on the device (csrc/outlier_iforest.hip), with path lengths summed in fixed point so that every result is free of any
+order; it never sweeps pairs of rows either.  Its contract (samples, node numbering, the leaf rule, the draws, the
+threshold, the fixed-point path length, the score) is that class's docstring.
+
 The classes differ in their scores only.  The constructor tail, the first touch of the device (at the first ``fit``,
 never in a constructor), the head and the tail of ``fit``, ``decision_function`` and the tail above (normalize,
 combination, contamination, predict) are ``_SubspaceScorer``; the neighbour search and its chunk loop are
@@ -1004,4 +1009,207 @@ class SubspaceECOD(_SubspaceScorer):
         self._mask = torch.as_tensor(mask, device=X.device)
         scores, per = self._score(X, fitting=True)
         self.skew_sign_ = self._sign.cpu().numpy().astype(np.int64)
+        return self._publish(scores, per)
+
+
+# ---- isolation forest: random trees over the subspaces -----------------------------------------------------------------
+IFOREST_MAX_TREES = 1024  # VGAN_IFOREST_MAX_TREES
+IFOREST_MAX_SAMPLES = 1024  # VGAN_IFOREST_MAX_SAMPLES: the sampled rows of a tree live in LDS
+IFOREST_MAX_DIMS = 8192  # VGAN_IFOREST_MAX_DIMS: features of one subspace (a bit per feature and wave in LDS)
+IFOREST_MAX_ROWS = (1 << 31) - 1
+IFOREST_AUTO_SAMPLES = 256  # max_samples="auto", sklearn's and pyod's default
+_IFOREST_MAX_RANGE = 65535  # subspaces of one launch (a grid dimension)
+EULER_GAMMA = 0.5772156649015329
+
+
+def check_estimators(n_estimators):
+    if not (_is_int(n_estimators) and 1 <= int(n_estimators) <= IFOREST_MAX_TREES):
+        raise ValueError(f"n_estimators must be an integer between 1 and {IFOREST_MAX_TREES}, got {n_estimators!r}")
+    return int(n_estimators)
+
+
+def check_max_samples(max_samples):
+    """ "auto" (256) or an integer between 2 and IFOREST_MAX_SAMPLES; fit takes min(max_samples, n)."""
+    if isinstance(max_samples, str) and max_samples == "auto":
+        return IFOREST_AUTO_SAMPLES
+    if not (_is_int(max_samples) and 2 <= int(max_samples) <= IFOREST_MAX_SAMPLES):
+        raise ValueError(f"max_samples must be 'auto' or an integer between 2 and {IFOREST_MAX_SAMPLES}, got {max_samples!r}")
+    return int(max_samples)
+
+
+def check_seed(seed):
+    if not (_is_int(seed) and 0 <= int(seed) < 1 << 64):
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    return int(seed)
+
+
+def iforest_path_table(psi):
+    """int64 [psi + 1]: cq[m] = rint(c(m) 2^32), c the average path length of an unsuccessful search in a binary search tree
+    of m rows: 0 for m <= 1, 1 for m = 2, else 2 (ln(m - 1) + EULER_GAMMA) - 2 (m - 1) / m, in float64."""
+    m = np.arange(psi + 1, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = 2.0 * (np.log(m - 1.0) + EULER_GAMMA) - 2.0 * (m - 1.0) / m
+    c[:2] = 0.0
+    if psi >= 2:
+        c[2] = 1.0
+    return np.rint(c * 4294967296.0).astype(np.int64)
+
+
+def iforest_chunks(n_subspaces, workspace_bytes):
+    """(subspaces of a range, rows of a row chunk): the transient buffers of scoring hold an int64 sum and a float32 score
+    per (subspace, row), 12 bytes.  All subspaces form one range and the rows are chunked while a row of every subspace
+    fits; below that the chunks are single rows and the subspaces are split into ranges, down to one subspace each."""
+    cells = max(1, int(workspace_bytes) // 12)
+    count = min(int(n_subspaces), cells, _IFOREST_MAX_RANGE)
+    return count, max(1, cells // count)
+
+
+class SubspaceIForest(_SubspaceScorer):
+    """Isolation forest per subspace (Liu, Ting, Zhou 2008; sklearn's ``IsolationForest``, pyod's ``IForest``), combined like
+    the other detectors of this module: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows; higher is
+    more outlying.  Nothing n x n: ``fit`` touches max_samples rows per tree, scoring is a short walk per (row, tree).  It is
+    invariant to a monotone rescaling of a feature.  There is no ``max_features`` (every feature of the subspace is a
+    candidate at every node: the subspaces are the feature bagging) and no ``bootstrap`` (a tree's sample has no repeats).
+
+    X is cast to float32.  n rows are given to ``fit``, 2 <= n <= 2^31 - 1; T = n_estimators (1 .. 1024); psi =
+    ``max_samples_`` = min(max_samples, n), max_samples "auto" (256) or 2 .. 1024; seed in [0, 2^64); a subspace has at most
+    IFOREST_MAX_DIMS (8192) features.
+
+    Tree (s, t), s the given subspace index, has the stream id = s T + t.  Its sample is the psi rows feistel_perm(i, n,
+    seed, id), i = 0 .. psi - 1 (the permutation of vgan_shuffle_index); only the set matters.  Nodes are heap-numbered: root
+    1, children 2 i and 2 i + 1; the depth limit is L = ``depth_limit_`` = ceil(log2 psi), so a tree has N = 2^(L + 1) slots,
+    slot 0 unused.  A node at depth e holding the row set R, m = |R|, is a leaf if m <= 1, or e == L, or no feature of F_s
+    varies on R (a feature is constant on R when its float32 min equals its max, -0.0 taken as +0.0).  Otherwise, with c the
+    number of varying features, the Philox4x32-10 words (w0, w1, ., .) of
+
+        counter (node, 0, 0x49464F52, 0),  key k0 = lo32(seed) ^ lo32(id),  k1 = hi32(seed) ^ hi32(id) ^ 0x5bd1e995
+
+    (the key convention of the noise stream) choose the split feature, the j-th varying feature in ascending feature
+    order with j = (w0 c) >> 32 in integers (uniform over the varying features: sklearn's distribution), and the threshold:
+    lo and hi the feature's min and max on R (-0.0 as +0.0), u = (w1 + 0.5) 2^-32 in float64, p = float32(lo + u (hi - lo)),
+    the difference, the product and the sum three separately rounded float64 operations; if p >= hi then p = lo (sklearn's
+    rule: both children are non-empty).  A row goes left iff x <= p, compared in float32.
+
+    Path lengths are fixed-point, so that their sums are exact and free of any order: c(m) = 0 for m <= 1, c(2) = 1, else
+    2 (ln(m - 1) + 0.5772156649015329) - 2 (m - 1) / m in float64 on the host; cq[m] = rint(c(m) 2^32) as int64 (a table the
+    host uploads: the device computes no logarithm).  A row reaching a leaf of depth e and size m in tree t contributes
+    (e << 32) + cq[m]; sum[s, i] is the int64 total over the T trees, and
+
+        score[s, i] = float32(exp2(-(double(sum[s, i]) / double(T cq[psi]))))
+
+    in (0, 1]: the paper's s(x, psi).  It equals minus sklearn's ``score_samples``; pyod's ``decision_scores_`` (sklearn's
+    ``decision_function`` negated) differ from it by a constant per fit, sklearn's ``offset_``.  A subspace whose features are
+    all constant scores exactly 0.5 everywhere.  ``fit`` scores the training rows through all trees, nothing excluded, so
+    ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.
+
+    All of the above depends on row sets only, never on a processing order: trees, sums and scores are bit-identical from
+    run to run and for every workspace_bytes, which bounds the transient buffers of scoring (iforest_chunks), not the trees;
+    the trees (8 bytes a slot: feature and threshold, or -1 and the leaf's size) are the fitted state, X is not kept.  NaN
+    input leaves the results unspecified and neither faults nor hangs: every loop is bounded by L and psi.
+
+    ``fit`` publishes, copied to the host on first use: ``tree_feature_`` int32 [S, T, N] (the split feature as a column of
+    X, -1 a leaf, -2 an absent slot), ``tree_threshold_`` float32 [S, T, N] (0 where the slot is not internal) and
+    ``tree_size_`` int32 [S, T, N] (the sample rows reaching the node, 0 where absent; those of an internal node are the sum
+    of its leaves'); and ``max_samples_``, ``depth_limit_``.  normalize, combination, contamination, ``threshold_``,
+    ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.  The definition above and its
+    numpy restatement in tests/test_outlier_iforest_cpu.py (pinned there to sklearn's path lengths and scores) are what
+    binds.  All of it runs in libvgan_hip.so (csrc/outlier_iforest.hip)."""
+
+    _host_trees = None
+
+    def __init__(self, subspaces, proba, n_estimators=100, max_samples="auto", seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
+                 normalize=None, combination="sum", contamination=0.1):
+        self.n_estimators = check_estimators(n_estimators)
+        self.max_samples = max_samples
+        self._max_samples = check_max_samples(max_samples)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > IFOREST_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceIForest takes at most {IFOREST_MAX_DIMS}")
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= IFOREST_MAX_ROWS:
+            raise ValueError(f"SubspaceIForest fit needs between 2 and {IFOREST_MAX_ROWS} rows, got {n}")
+
+    def _ranges(self):
+        count, rows = iforest_chunks(self.plan.count, self.workspace_bytes)
+        return [(first, min(count, self.plan.count - first)) for first in range(0, self.plan.count, count)], rows
+
+    def path_sums(self, X):
+        """int64 [S, n]: the fixed-point path-length sums of the rows of X over the trees of every subspace."""
+        self._require_fit()
+        X = _device_matrix(X, self.plan.d)
+        return self._sums(X, None).cpu().numpy()
+
+    def _sums(self, X, per):
+        """Walks X through the trees range by range and row chunk by row chunk; per None: returns the int64 sums [S, nq],
+        otherwise fills the float32 scores per [S, nq]."""
+        nq = X.shape[0]
+        ranges, rows = self._ranges()
+        rows = min(rows, nq)
+        out = torch.empty(self.plan.count, nq, dtype=torch.int64, device=X.device) if per is None else None
+        sums = torch.empty(ranges[0][1] * rows, dtype=torch.int64, device=X.device)
+        for first, count in ranges:
+            for r0 in range(0, nq, rows):
+                r1 = min(r0 + rows, nq)
+                self.ops.iforest_path_sums(X[r0:r1], self._trees, first, count, self.max_samples_, self.depth_limit_, self._cq, sums)
+                if per is None:
+                    out[first:first + count, r0:r1] = sums[:count * (r1 - r0)].view(count, r1 - r0)
+                else:
+                    self.ops.iforest_scores(sums, count, r1 - r0, self._denom, per[first:first + count, r0:r1])
+        return out
+
+    def _score(self, X, fitting):
+        per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
+        self._sums(X, per)
+        return self._combine(per, fitting), per
+
+    def _trees_on_host(self):
+        self._require_fit()
+        if self._host_trees is None:
+            nodes = self._trees.cpu().numpy()
+            feature = np.ascontiguousarray(nodes[..., 0])
+            word = np.ascontiguousarray(nodes[..., 1])
+            threshold = np.where(feature >= 0, word.view(np.float32), np.float32(0.0))
+            size = np.where(feature == -1, word, 0).astype(np.int32)
+            for e in range(self.depth_limit_ - 1, -1, -1):  # an internal node holds what its children hold
+                at = np.arange(1 << e, 2 << e)
+                inner = feature[..., at] >= 0
+                size[..., at] = np.where(inner, size[..., 2 * at] + size[..., 2 * at + 1], size[..., at])
+            self._host_trees = (feature, threshold, size)
+        return self._host_trees
+
+    @property
+    def tree_feature_(self):
+        """int32 [S, T, N]: the split feature of every heap slot as a column of X, -1 for a leaf, -2 for an absent slot."""
+        return self._trees_on_host()[0]
+
+    @property
+    def tree_threshold_(self):
+        """float32 [S, T, N]: the threshold of every internal node (a row goes left iff x <= threshold), 0 elsewhere."""
+        return self._trees_on_host()[1]
+
+    @property
+    def tree_size_(self):
+        """int32 [S, T, N]: the sample rows reaching every node, 0 where the slot is absent."""
+        return self._trees_on_host()[2]
+
+    def fit(self, X, y=None):
+        """Builds the T trees of every subspace on their samples of X, then scores X itself through them: decision_scores_
+        (float64 [n]), per_subspace_scores_, max_samples_, depth_limit_ and, on first use, tree_feature_ / tree_threshold_ /
+        tree_size_; with normalize also score_center_ / score_scale_.  The trees are the fitted state: X itself is not kept."""
+        X = self._begin_fit(X)
+        n = X.shape[0]
+        psi = min(self._max_samples, n)
+        self.max_samples_, self.depth_limit_, self._host_trees = psi, (psi - 1).bit_length(), None
+        cq = iforest_path_table(psi)
+        self._cq = torch.as_tensor(cq, device=X.device)
+        self._denom = self.n_estimators * int(cq[psi])
+        self._trees = torch.empty(self.plan.count, self.n_estimators, 2 << self.depth_limit_, 2, dtype=torch.int32, device=X.device)
+        for first, count in self._ranges()[0]:
+            self.ops.iforest_build(X, self._table, first, count, int(self.plan.dims[first:first + count].max()), psi, self.depth_limit_,
+                                   self.seed, self._trees)
+        scores, per = self._score(X, fitting=True)
         return self._publish(scores, per)

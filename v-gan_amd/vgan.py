@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble
+from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceIForest
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -185,7 +185,11 @@ class _RunFolder:
         contamination, e.g. outlier_ensemble(method="abod", n_neighbors=10, X=X).
         method "ecod" builds a SubspaceECOD (empirical-CDF tail probabilities per feature, no hyper-parameter; pyod's
         ECOD): its keywords are aggregate, workspace_bytes and the same normalize / combination / contamination, e.g.
-        outlier_ensemble(method="ecod", X=X); n_neighbors is not used there."""
+        outlier_ensemble(method="ecod", X=X); n_neighbors is not used there.
+        method "iforest" builds a SubspaceIForest (isolation forest: random trees on sampled rows, no sweep over pairs of
+        rows; sklearn's IsolationForest, pyod's IForest): its keywords are n_estimators, max_samples, seed, workspace_bytes
+        and the same normalize / combination / contamination, e.g. outlier_ensemble(method="iforest", n_estimators=100,
+        X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -194,6 +198,8 @@ class _RunFolder:
             ens = SubspaceABOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
         elif method == "ecod":
             ens = SubspaceECOD(self.subspaces, self.proba, **kw)
+        elif method == "iforest":
+            ens = SubspaceIForest(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
