@@ -271,7 +271,8 @@ int vgan_mmd_backward(const float* Wg, int ldw, const float* Z, int ldz, int wro
 int vgan_mmd_bf3_prepare(const float* Z, int ldz, int rows, int p, uint16_t* Zh, uint16_t* Zl, int kp,
                          uint16_t* ZTh, uint16_t* ZTl, int kn, vgan_stream_t stream);
 /* vgan_mmd_gram_colmax on the split operands; the gradient weights leave as a bf16 hi/lo pair Wh, Wl
- * [nr, ldw] (ldw >= 2n rounded up to 64; columns >= 2n must be pre-zeroed).  S may be NULL (no column job).
+ * [nr, ldw] (ldw >= 2n rounded up to 64 -- ldw % 8 == 0 and 16-byte aligned bases are checked: the epilogues store 16 bytes
+ * at a time wherever the element offset allows; columns >= 2n must be pre-zeroed).  S may be NULL (no column job).
  * tile = the edge the table was built with: 64, 128 (512-thread workgroups, half the L2->LDS bytes per flop; pays when the
  * table still has >~ 128 tiles) or 256 (256 x 128 tiles, 768-thread workgroups of 8 consumer + 4 loader waves, three K stages
  * of 32 in LDS, v_mfma_f32_16x16x32_bf16: c4 / c5 sizes).

@@ -434,3 +434,35 @@ def test_gram_launch_round_model_and_boundary():
         assert k == n_main or cost(k) <= cost(n_main) - 0.15 + 1e-9
     assert _best_boundary(772, 1256, 256, False) == 768   # c5, 8 ranks, 128-wide tiles: the four stragglers go over
     assert _best_boundary(388, 632, 256, True) == 388     # c5, 8 ranks, wide tiles: nothing to gain
+
+
+def test_no_garbage_collection_falls_inside_a_graph_capture():
+    """trainer.no_gc_while_capturing: a dead reference cycle (an earlier fit's engine and its captured graph) is collected before
+    the capture begins, the automatic collector rests inside it, and the caller's collector state comes back -- also after an
+    exception, and also when the caller had it switched off."""
+    import gc
+    import weakref
+    from vgan_amd.trainer import no_gc_while_capturing
+
+    class Node:
+        pass
+
+    a, b = Node(), Node()
+    a.other, b.other = b, a
+    gone = weakref.ref(a)
+    del a, b
+    assert gc.isenabled()
+    with no_gc_while_capturing():
+        assert gone() is None and not gc.isenabled()
+    assert gc.isenabled()
+    with pytest.raises(RuntimeError):
+        with no_gc_while_capturing():
+            raise RuntimeError("capture failed")
+    assert gc.isenabled()
+    gc.disable()
+    try:
+        with no_gc_while_capturing():
+            assert not gc.isenabled()
+        assert not gc.isenabled()
+    finally:
+        gc.enable()

@@ -148,7 +148,10 @@ __global__ __launch_bounds__(kBlock, BK == 64 ? 2 : 3) void mmd_gram_bf3_kernel(
                 hp[e] = (unsigned)h0 | ((unsigned)h1 << 16);
                 lp[e] = (unsigned)l0 | ((unsigned)l1 << 16);
             }
-            if (c_first + 15 < c_lim) {  // ldw % 8 == 0 and tile origins are multiples of 64: 32-byte aligned
+            // two 16-byte stores per image, taken only at a 16-byte aligned address: the host checks the bases and ldw % 8 == 0, but
+            // a tile's first column need not be a multiple of 8 (YY tiles start at column n + c, row-sharded tiles mirror from
+            // r0 = n + lo), so the element offset is tested; anything else leaves through the element loop below
+            if (c_first + 15 < c_lim && ((rowo + c_first) & 7) == 0) {
                 uint4* dh = reinterpret_cast<uint4*>(Wh + rowo + c_first);
                 uint4* dl = reinterpret_cast<uint4*>(Wl + rowo + c_first);
                 dh[0] = make_uint4(hp[0], hp[1], hp[2], hp[3]);
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(512, 2) void mmd_gram_bf3_big_kernel(const unsigned
                 hp[e] = (unsigned)h0 | ((unsigned)h1 << 16);
                 lp[e] = (unsigned)l0 | ((unsigned)l1 << 16);
             }
-            if (c_first + 15 < c_lim) {
+            if (c_first + 15 < c_lim && ((rowo + c_first) & 7) == 0) {  // 16-byte aligned (see mmd_gram_bf3_kernel)
                 uint4* dh = reinterpret_cast<uint4*>(Wh + rowo + c_first);
                 uint4* dl = reinterpret_cast<uint4*>(Wl + rowo + c_first);
                 dh[0] = make_uint4(hp[0], hp[1], hp[2], hp[3]);
@@ -428,7 +431,7 @@ __global__ __launch_bounds__(768, 3) void mmd_gram_bf3_wide_kernel(const unsigne
                 const float v1 = __uint_as_float((unsigned)h1 << 16) + __uint_as_float((unsigned)l1 << 16);
                 sums[e & 3] += (c_first + 2 * e < c_lim ? v0 : 0.f) + (c_first + 2 * e + 1 < c_lim ? v1 : 0.f);
             }
-            if (c_first + 15 < c_lim) {
+            if (c_first + 15 < c_lim && ((rowo + c_first) & 7) == 0) {  // 16-byte aligned (see mmd_gram_bf3_kernel)
                 uint4* dh = reinterpret_cast<uint4*>(Wh + rowo + c_first);
                 uint4* dl = reinterpret_cast<uint4*>(Wl + rowo + c_first);
                 dh[0] = make_uint4(hp[0], hp[1], hp[2], hp[3]);
@@ -785,7 +788,7 @@ extern "C" int vgan_mmd_gram_bf3(const uint16_t* Zh, const uint16_t* Zl, int kp,
                                  vgan_stream_t stream) {
     VGAN_CHECK_ARG(Zh && Zl && sq && bw && tiles && partial && n > 0 && ntiles > 0 && kp > 0 && kp % 64 == 0);
     VGAN_CHECK_ARG((Wh == nullptr) == (Wl == nullptr) && (reinterpret_cast<uintptr_t>(partial) & 15) == 0);
-    VGAN_CHECK_ARG(aligned16(Zh) && aligned16(Zl) && (Wh == nullptr || (aligned16(Wh) && aligned16(Wl))));
+    VGAN_CHECK_ARG(aligned16(Zh) && aligned16(Zl) && (Wh == nullptr || (aligned16(Wh) && aligned16(Wl) && ldw % 8 == 0)));
     ColmaxJob cj{};
     int extra = 0;
     if (S != nullptr) {

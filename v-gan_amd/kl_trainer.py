@@ -22,7 +22,7 @@ phase (src/vgan.py:319-320) while the decoder is re-enabled by every detector st
 """
 import torch
 
-from .trainer import ADADELTA_EPS, ADADELTA_RHO, FlatParams, _round4
+from .trainer import ADADELTA_EPS, ADADELTA_RHO, FlatParams, _round4, no_gc_while_capturing
 
 
 class CollapsedChain:
@@ -239,7 +239,7 @@ class KLStepEngine:
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(g):
+            with no_gc_while_capturing(), torch.cuda.graph(g):
                 for _ in range(steps):
                     body()
         except Exception as e:  # noqa: BLE001

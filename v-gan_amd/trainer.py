@@ -42,12 +42,30 @@ more than the overlap returns.  Re-measured on the final step with ONLY the X-X 
 loss, never a gradient) on a side stream that starts after the mask backward and joins at the end of the step:
 161 vs 138 us/step, although dropping those tiles outright would save 7 us.
 """
+import contextlib
+import gc
 import os
 
 import torch
 
 ADADELTA_RHO = 0.9   # torch.optim.Adadelta defaults used by the reference (src/vgan.py:567-568)
 ADADELTA_EPS = 1e-6
+
+
+@contextlib.contextmanager
+def no_gc_while_capturing():
+    """Around a HIP-graph capture.  Destroying a captured graph is not permitted while a stream captures, and torch terminates
+    the process when it happens: an engine of an earlier fit that sits in a dead reference cycle is destroyed by whichever
+    automatic garbage collection comes next, which may fall inside this capture (torch.cuda.graph no longer collects on
+    entry).  So the dead cycles are collected BEFORE the capture begins, and the automatic collector rests until it ends."""
+    was_enabled = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def _round4(v):
@@ -1102,7 +1120,7 @@ class NoKLStepEngine:
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(g):
+            with no_gc_while_capturing(), torch.cuda.graph(g):
                 for _ in range(steps):
                     self._step_body()
         except Exception as e:  # noqa: BLE001 -- any capture failure means "no graph", never "no training"
