@@ -814,6 +814,54 @@ int vgan_iforest_path_sums(const float* Xq, int ldq, int rows, int d, const int3
 int vgan_iforest_scores(const int64_t* sums, int64_t ld_sums, int count, int rows, int64_t denom, float* score,
                         int64_t ld_score, vgan_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mahalanobis / MCD outlier scores (sklearn's EmpiricalCovariance / ShrunkCovariance / OAS .mahalanobis; pyod's MCD up to the
+ * estimator): a float64 mean and covariance per subspace, the shrunk matrix's Cholesky factor inverted, and the squared
+ * distance as a triangular product  (v-gan_amd/outlier.py: SubspaceMahalanobis, whose docstring is the definition; kernels
+ * in csrc/outlier_maha.hip).  X is float32, all arithmetic float64.  Subspaces are positions of a SUBSPACE TABLE (feat,
+ * feat_off); sq_off int64 [S + 1] is the running sum of d_s^2: the d_s x d_s row-major matrices of subspace s (cov, L, W)
+ * start at element sq_off[s], its mean at element feat_off[s].  Every entry works on the range first .. first + count - 1
+ * (count <= 65535), max_dims >= every d_s of the range, d_s <= VGAN_MAHA_MAX_DIMS.  hcount int32 [S]: h_s, the rows of the
+ * support.  support uint8 [S, ld_support], 1 = the row is in H_s; NULL: every row (then h_s = n).
+ * vgan_maha_moments: mean = (1 / h_s) sum_{i in H_s} x_i and cov = C_s = (1 / h_s) sum_{i in H_s} (x_i - mu)(x_i - mu)^T (biased,
+ *   two passes, both triangles written) from X [n, d] (ldx), 2 <= n <= VGAN_MAHA_MAX_ROWS.  The rows are cut into slabs of
+ *   VGAN_MAHA_SLAB_ROWS rows by n alone; a slab's sum has a fixed order (the covariance on the f64 matrix unit, 16 x 16
+ *   tiles of the lower triangle) and the slabs are added in ascending order, so the bits do not depend on the workspace,
+ *   which only sets how many slabs and tiles one launch takes.  tiles int32 [n_tiles, 3]: (s, ti, tj), tj <= ti <
+ *   ceil(d_s / 16), every lower-triangle tile of every subspace of the range; total_dims = the sum of d_s over the range.
+ *   workspace: at least 8 * total_dims and at least 2048 bytes.
+ * vgan_maha_factor: per subspace m = tr C / d, alpha = shrinkage, or for VGAN_MAHA_SHRINKAGE_OAS: a = mean(C_ij^2), alpha = 1
+ *   if (h + 1)(a - m^2 / d) == 0 else min((a + m^2) / ((h + 1)(a - m^2 / d)), 1) (sklearn's oas); cov is overwritten with
+ *   Sigma = (1 - alpha) C + alpha m I; L receives its lower Cholesky factor (blocked right-looking, the trailing update on
+ *   the f64 matrix unit), W = L^-1 (lower triangular, zeros above).  status int32 [S] (zeroed by the caller before the
+ *   first call of a fit): bit 0 = tr C == 0 in this call (W = 0: every score is exactly 0), bit 1 = a pivot was not
+ *   positive and finite in this or an earlier call (L, W unspecified).  One workgroup per subspace.
+ * vgan_maha_scores: score[s, i] = float32(|| W_s (x_i - mu_s) ||^2) for the rows of Xq [rows, d] (ldq) into score [S,
+ *   ld_score], row s; the product on the f64 matrix unit, K in ascending order up to the diagonal, then the squares in
+ *   ascending order: the bits of an element do not depend on where its row sits in the call.
+ * vgan_maha_select: support[s, i] = 1 for the h_s rows with the smallest (score[s, i], i), -0.0 taken as +0.0, else 0;
+ *   changed[s] = 1 if that differs from what support held before, else 0.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_MAHA_MAX_DIMS 1024
+#define VGAN_MAHA_MAX_ROWS 16777216 /* 2^24 */
+#define VGAN_MAHA_SLAB_ROWS 1024
+#define VGAN_MAHA_SHRINKAGE_OAS (-1.0)
+#define VGAN_MAHA_STATUS_CONSTANT 1
+#define VGAN_MAHA_STATUS_PIVOT 2
+int vgan_maha_moments(const float* X, int ldx, int n, int d, const int32_t* feat, const int32_t* feat_off,
+                      const int64_t* sq_off, int first, int count, int total_dims, int max_dims, const int32_t* tiles,
+                      int n_tiles, const uint8_t* support, int64_t ld_support, const int32_t* hcount, double* mean,
+                      double* cov, void* workspace, int64_t workspace_bytes, vgan_stream_t stream);
+int vgan_maha_factor(double* cov, const int64_t* sq_off, const int32_t* feat_off, int first, int count, int max_dims,
+                     const int32_t* hcount, double shrinkage, double* L, double* W, double* alpha, int32_t* status,
+                     vgan_stream_t stream);
+int vgan_maha_scores(const float* Xq, int ldq, int rows, int d, const int32_t* feat, const int32_t* feat_off,
+                     const int64_t* sq_off, int first, int count, int max_dims, const double* mean, const double* W,
+                     float* score, int64_t ld_score, vgan_stream_t stream);
+int vgan_maha_select(const float* score, int64_t ld_score, int n, int first, int count, const int32_t* hcount,
+                     uint8_t* support, int64_t ld_support, int32_t* changed, vgan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,11 @@ difference of the two paths' ensemble scores.
     n_estimators=100, n_jobs=16) fitted and scored per subspace on the CPUs for a sample of the subspaces, scaled to all of
     them; and the kNN fit (k = 5) of SubspaceEnsemble on the same subspaces.  walk_steps_per_s counts S T n walks of the
     measured mean depth.
+  --method mahalanobis: covariance-based scores (vgan_amd.SubspaceMahalanobis, shrinkage 0.1): fit and decision_function (the
+    training rows as queries), classical and robust (max_csteps 30); the classical fit split into its calls (moments,
+    factor, scores); (a) a float64 torch restatement on the same GPU (per subspace: gather, mean, centred product,
+    torch.linalg.cholesky, solve_triangular, the squared column norms) and (b) sklearn's ShrunkCovariance(0.1).fit /
+    .mahalanobis per subspace on the host, for a sample of the subspaces scaled to all of them.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -495,6 +500,78 @@ def run_iforest(d, n, count, reps, baselines=True, sklearn_sample=8):
     return row
 
 
+def torch_maha(X, feats, alpha):
+    """float32 [S, n]: the squared Mahalanobis distances of the contract, float64 torch on the device, subspace by subspace."""
+    n = X.shape[0]
+    per = torch.empty(len(feats), n, dtype=torch.float32, device=X.device)
+    for s, f in enumerate(feats):
+        Z = X[:, f].double()
+        Z = Z - Z.mean(dim=0)
+        C = Z.T @ Z / n
+        Sigma = (1.0 - alpha) * C
+        Sigma.diagonal().add_(alpha * torch.trace(C) / C.shape[0])
+        L = torch.linalg.cholesky(Sigma)  # raises where the factor does not exist
+        Y = torch.linalg.solve_triangular(L, Z.T, upper=False)
+        per[s] = (Y * Y).sum(dim=0).float()
+    return per
+
+
+def run_maha(d, n, count, reps, baselines=True, sklearn_sample=8):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceMahalanobis(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    robust = vgan_amd.SubspaceMahalanobis(m, p, robust=True)
+    t_rob, tr = timed(lambda: robust.fit(Xd), reps)
+    inner = max(reps, 5)
+    ens._prepare(n, Xd.device)
+    hcount = torch.full((S,), n, dtype=torch.int32, device="cuda")
+    t_mom, _ = timed(lambda: ens._moments(Xd, None, hcount), inner)
+
+    def factor():  # the factor overwrites C with Sigma: every repetition starts from fresh moments
+        ens._moments(Xd, None, hcount)
+        ens._factor(hcount)
+    t_mf, _ = timed(factor, inner)
+    t_sc, _ = timed(lambda: ens._distances(Xd), inner)
+    ens.fit(Xd)
+    flops = 2.0 * n * float((dims.astype(np.float64) ** 2).sum())
+    row = {"method": "mahalanobis", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "d_s_min": int(dims.min()),
+           "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()), "fit_s": round(t_fit, 6), "fit_reps_s": tf,
+           "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td, "robust_fit_s": round(t_rob, 6),
+           "robust_fit_reps_s": tr, "robust_csteps_max": int(robust.n_csteps_.max()), "robust_converged": int(robust.converged_.sum()),
+           "moments_s": round(t_mom, 6), "factor_s": round(t_mf - t_mom, 6), "scores_s": round(t_sc, 6),
+           "scores_full_product_tflops": round(flops / t_sc / 1e12, 3), "moments_full_product_tflops": round(flops / t_mom / 1e12, 3),
+           "state_bytes": int(3 * 8 * (dims.astype(np.int64) ** 2).sum())}
+    if baselines:
+        feats = [torch.as_tensor(np.flatnonzero(m[s]), device="cuda") for s in range(S)]
+        ours = ens.per_subspace_scores_.astype(np.float64)
+        try:
+            t_torch, tt = timed(lambda: torch_maha(Xd, feats, 0.1), reps)
+            theirs = torch_maha(Xd, feats, 0.1).cpu().numpy().astype(np.float64)
+            row.update({"torch_f64_s": round(t_torch, 6), "torch_f64_reps_s": tt, "fit_speedup_vs_torch": round(t_torch / t_fit, 2),
+                        "max_rel_diff_vs_torch": float(np.max(np.abs(ours - theirs) / np.maximum(np.abs(theirs), 1e-300)))})
+        except RuntimeError as e:  # the baseline's own failure (hipBLAS could not allocate at d = 784, n = 5e4) is recorded, not hidden
+            row.update({"torch_f64_s": None, "torch_f64_error": str(e).splitlines()[0]})
+        try:
+            from sklearn.covariance import ShrunkCovariance
+            pick = np.unique(np.linspace(0, S - 1, min(S, sklearn_sample)).astype(int))
+            t_sk, worst = 0.0, 0.0
+            for s in pick:
+                Xs = np.ascontiguousarray(X[:, np.flatnonzero(m[s])]).astype(np.float64)
+                t0 = time.perf_counter()
+                dist = ShrunkCovariance(shrinkage=0.1).fit(Xs).mahalanobis(Xs)
+                t_sk += time.perf_counter() - t0
+                worst = max(worst, float(np.max(np.abs(ours[s] - dist) / np.maximum(np.abs(dist), 1e-300))))
+            scale = S / len(pick)
+            row.update({"sklearn_fit_and_score_s": round(t_sk * scale, 4), "sklearn_subspaces_timed": int(len(pick)),
+                        "fit_speedup_vs_sklearn": round(t_sk * scale / t_fit, 1), "max_rel_diff_vs_sklearn": worst})
+        except ImportError:
+            row["sklearn_fit_and_score_s"] = None
+    return row
+
+
 def host_normalized(per, proba, mode):
     """The numpy alternative to csrc/outlier_norm.hip: float64 statistics per row of per [S, n], transform, weighted sum."""
     x = per.astype(np.float64)
@@ -592,13 +669,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / ecod / iforest: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -656,6 +733,15 @@ def main():
             shapes = [tuple(int(v) for v in args.shape.split(","))]
         for d, n, count in shapes:
             out["configs"].append(run_iforest(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "mahalanobis":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_maha(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     for d, n, count, k, with_base in configs:

@@ -884,6 +884,57 @@ class HipOps:
         _lib.check(self.lib.vgan_iforest_scores(_ptr(sums), int(rows), int(count), int(rows), int(denom), _ptr(score), score.stride(0),
                                                 self._stream()), "vgan_iforest_scores")
 
+    # ---- Mahalanobis / MCD over subspaces (vgan_amd.outlier.SubspaceMahalanobis) ----------------------------
+    # table: (feat int32, feat_off int32 [S + 1], sq_off int64 [S + 1]); the matrices of subspace s start at sq_off[s]
+    def maha_moments(self, X, table, first, count, total_dims, max_dims, tiles, support, hcount, mean, cov, workspace):
+        """mean (float64, at feat_off[s]) and cov (float64 [d_s, d_s] at sq_off[s]) of the subspaces first .. first + count - 1
+        over the rows of X whose support byte is 1 (support uint8 [S, n]; None: every row); hcount int32 [S] their number;
+        tiles int32 [n_tiles, 3]: the lower-triangle tiles (s, ti, tj) of the range; workspace: float64."""
+        _mat(X, "X"), _vec(tiles, "tiles", torch.int32), _vec(hcount, "hcount", torch.int32)
+        _vec(mean, "mean", torch.float64), _vec(cov, "cov", torch.float64), _vec(workspace, "workspace", torch.float64)
+        feat, feat_off, sq_off = table
+        n, d = X.shape
+        if support is not None:
+            _vec(support, "support", torch.uint8)
+            assert support.dim() == 2 and support.shape[0] >= first + count and support.shape[1] == n
+        assert tiles.dim() == 2 and tiles.shape[1] == 3 and hcount.numel() >= first + count
+        _lib.check(self.lib.vgan_maha_moments(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(sq_off), int(first), int(count),
+                                              int(total_dims), int(max_dims), _ptr(tiles), tiles.shape[0], _ptr(support), n, _ptr(hcount),
+                                              _ptr(mean), _ptr(cov), _ptr(workspace), workspace.numel() * 8, self._stream()),
+                   "vgan_maha_moments")
+
+    def maha_factor(self, cov, table, first, count, max_dims, hcount, shrinkage, L, W, alpha, status):
+        """cov becomes the shrunk matrix (shrinkage in [0, 1], or -1 for OAS), L its lower Cholesky factor, W = L^-1; alpha
+        float64 [S] the shrinkage used; status int32 [S]: bit 0 a constant subspace, bit 1 a failed pivot (sticky)."""
+        for name, v in (("cov", cov), ("L", L), ("W", W), ("alpha", alpha)):
+            _vec(v, name, torch.float64)
+        _vec(hcount, "hcount", torch.int32), _vec(status, "status", torch.int32)
+        _, feat_off, sq_off = table
+        assert alpha.numel() >= first + count and status.numel() >= first + count and L.numel() >= cov.numel() <= W.numel()
+        _lib.check(self.lib.vgan_maha_factor(_ptr(cov), _ptr(sq_off), _ptr(feat_off), int(first), int(count), int(max_dims), _ptr(hcount),
+                                             float(shrinkage), _ptr(L), _ptr(W), _ptr(alpha), _ptr(status), self._stream()),
+                   "vgan_maha_factor")
+
+    def maha_scores(self, Xq, table, first, count, max_dims, mean, W, score):
+        """score float32 [S, rows] (a view into the score matrix may be given): rows first .. first + count - 1 receive the
+        squared Mahalanobis distances of the rows of Xq."""
+        _mat(Xq, "Xq"), _mat(score, "score"), _vec(mean, "mean", torch.float64), _vec(W, "W", torch.float64)
+        feat, feat_off, sq_off = table
+        rows, d = Xq.shape
+        assert score.shape[0] >= first + count and score.shape[1] >= rows
+        _lib.check(self.lib.vgan_maha_scores(_ptr(Xq), Xq.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(sq_off), int(first),
+                                             int(count), int(max_dims), _ptr(mean), _ptr(W), _ptr(score), score.stride(0), self._stream()),
+                   "vgan_maha_scores")
+
+    def maha_select(self, score, first, count, hcount, support, changed):
+        """support uint8 [S, n] = 1 on the hcount[s] rows with the smallest (score, row index); changed int32 [S]: whether
+        that differs from what support held."""
+        _mat(score, "score"), _vec(hcount, "hcount", torch.int32), _vec(support, "support", torch.uint8), _vec(changed, "changed", torch.int32)
+        n = score.shape[1]
+        assert support.dim() == 2 and support.shape[1] == n and min(score.shape[0], support.shape[0], changed.numel()) >= first + count
+        _lib.check(self.lib.vgan_maha_select(_ptr(score), score.stride(0), n, int(first), int(count), _ptr(hcount), _ptr(support), n,
+                                             _ptr(changed), self._stream()), "vgan_maha_select")
+
 
 _default = None
 

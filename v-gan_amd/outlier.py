@@ -52,6 +52,11 @@ on the device (csrc/outlier_iforest.hip), with path lengths summed in fixed poin
 order; it never sweeps pairs of rows either.  Its contract (samples, node numbering, the leaf rule, the draws, the
 threshold, the fixed-point path length, the score) is that class's docstring.
 
+``SubspaceMahalanobis`` is the covariance-based detector: a float64 mean and shrunk covariance per subspace, classical or by
+deterministic concentration steps (MCD), and the squared Mahalanobis distance as a triangular float64 product on the
+matrix unit (csrc/outlier_maha.hip); n d_s^2 per subspace.  Its contract (support, location, covariance, shrinkage and the
+OAS rule, the score, the degenerate cases, the C-steps, determinism) is that class's docstring.
+
 The classes differ in their scores only.  The constructor tail, the first touch of the device (at the first ``fit``,
 never in a constructor), the head and the tail of ``fit``, ``decision_function`` and the tail above (normalize,
 combination, contamination, predict) are ``_SubspaceScorer``; the neighbour search and its chunk loop are
@@ -1213,3 +1218,275 @@ class SubspaceIForest(_SubspaceScorer):
                                    self.seed, self._trees)
         scores, per = self._score(X, fitting=True)
         return self._publish(scores, per)
+
+
+# ---- Mahalanobis / MCD: covariance-based scores over the subspaces ------------------------------------------------------
+MAHA_MAX_DIMS = 1024  # VGAN_MAHA_MAX_DIMS: features of one subspace (its three d_s x d_s float64 matrices stay resident)
+MAHA_MAX_ROWS = 1 << 24  # VGAN_MAHA_MAX_ROWS
+MAHA_SLAB_ROWS = 1024  # VGAN_MAHA_SLAB_ROWS: rows of one slab of the moment sums, fixed: the partition depends on n alone
+MAHA_TILE = 16  # edge of a covariance tile (the f64 MFMA's)
+_MAHA_OAS = -1.0  # VGAN_MAHA_SHRINKAGE_OAS
+_MAHA_CONSTANT, _MAHA_PIVOT = 1, 2  # VGAN_MAHA_STATUS_*
+_MAHA_MAX_RANGE = 65535  # subspaces of one launch (a grid dimension)
+
+
+def check_shrinkage(shrinkage):
+    """A float in [0, 1] (sklearn's ShrunkCovariance) or "oas" (sklearn's OAS rule per subspace)."""
+    if isinstance(shrinkage, str):
+        if shrinkage != "oas":
+            raise ValueError(f"shrinkage must be a float in [0, 1] or 'oas', got {shrinkage!r}")
+        return shrinkage
+    if not _is_real(shrinkage) or not 0.0 <= float(shrinkage) <= 1.0:  # False for nan
+        raise ValueError(f"shrinkage must be a float in [0, 1] or 'oas', got {shrinkage!r}")
+    return float(shrinkage)
+
+
+def check_support_fraction(support_fraction):
+    """None (sklearn's rule from n and d_s) or a float in (0, 1]."""
+    if support_fraction is None:
+        return None
+    if not _is_real(support_fraction) or not 0.0 < float(support_fraction) <= 1.0:
+        raise ValueError(f"support_fraction must be None or a float in (0, 1], got {support_fraction!r}")
+    return float(support_fraction)
+
+
+def check_csteps(max_csteps):
+    if not (_is_int(max_csteps) and int(max_csteps) >= 1):
+        raise ValueError(f"max_csteps must be a positive integer, got {max_csteps!r}")
+    return int(max_csteps)
+
+
+def mcd_support_size(n, d_s, support_fraction=None):
+    """h_s, the rows of the MCD support of a subspace of d_s features among n rows: min(n, ceil((n + d_s + 1) / 2)) when
+    support_fraction is None (sklearn's rule), otherwise int(support_fraction n); ValueError if that is below 2."""
+    n, d_s = int(n), int(d_s)
+    if support_fraction is None:
+        return min(n, (n + d_s + 2) // 2)
+    h = int(check_support_fraction(support_fraction) * n)
+    if h < 2:
+        raise ValueError(f"support_fraction {support_fraction!r} leaves {h} of {n} rows in the support, at least 2 are needed")
+    return h
+
+
+def maha_ranges(dims, workspace_bytes):
+    """(the float64 cells of the moment workspace, [(first, count)]): consecutive subspace ranges whose slab sums (8 bytes a
+    feature) fit in workspace_bytes; the workspace is never smaller than one subspace's sums or one 16 x 16 tile."""
+    dims = [int(v) for v in dims]
+    cells = max(int(workspace_bytes) // 8, max(dims), MAHA_TILE * MAHA_TILE)
+    out, first = [], 0
+    while first < len(dims):
+        end, used = first, 0
+        while end < len(dims) and end - first < _MAHA_MAX_RANGE and (end == first or used + dims[end] <= cells):
+            used += dims[end]
+            end += 1
+        out.append((first, end - first))
+        first = end
+    return cells, out
+
+
+def maha_tiles(dims, first, count):
+    """int32 [n_tiles, 3]: (s, ti, tj), tj <= ti < ceil(d_s / 16), for the subspaces first .. first + count - 1."""
+    rows = []
+    for s in range(first, first + count):
+        t = -(-int(dims[s]) // MAHA_TILE)
+        ti, tj = np.tril_indices(t)
+        rows.append(np.stack([np.full(ti.shape, s), ti, tj], axis=1))
+    return np.concatenate(rows).astype(np.int32)
+
+
+class SubspaceMahalanobis(_SubspaceScorer):
+    """Squared Mahalanobis distance per subspace under a shrunk covariance, classical or, with robust=True, under a
+    deterministic minimum-covariance-determinant estimate (pyod's "linear" family: ``MCD``, and ``PCA`` with all components;
+    sklearn's ``EmpiricalCovariance`` / ``ShrunkCovariance`` / ``OAS`` ``.mahalanobis``), combined like the other detectors
+    of this module: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying.  The
+    score accounts for the correlation between the features of a subspace, has no neighbour count, bandwidth or tree count,
+    and costs n d_s^2 per subspace, nothing n x n.
+
+    X is cast to float32; all arithmetic is float64 on those values.  n rows are given to ``fit``, 2 <= n <= MAHA_MAX_ROWS
+    (2^24); a subspace has at most MAHA_MAX_DIMS (1024) features.  Per subspace s (features F_s, d_s of them) and its
+    support H_s of h_s rows (every row, h_s = n, when not robust):
+
+        mu_s = (1 / h_s) sum_{i in H_s} x_i                                     the location
+        C_s = (1 / h_s) sum_{i in H_s} (x_i - mu_s)(x_i - mu_s)^T               biased, two passes (sklearn's EmpiricalCovariance)
+        Sigma_s = (1 - alpha_s) C_s + alpha_s (tr C_s / d_s) I                  sklearn's ShrunkCovariance
+
+    shrinkage is alpha_s for every subspace, a float in [0, 1], or "oas" (sklearn's ``oas``): m = tr C_s / d_s, a = the mean
+    of the squared entries of C_s, alpha_s = 1 if (h_s + 1)(a - m^2 / d_s) == 0, otherwise min((a + m^2) / ((h_s + 1)(a -
+    m^2 / d_s)), 1).  The default 0.1 is there because constant columns are normal in this project's data (image borders).
+
+    Score: (x - mu_s)^T Sigma_s^-1 (x - mu_s), sklearn's ``.mahalanobis`` and pyod's MCD ``decision_scores_`` up to the
+    estimator, computed as ||W_s (x - mu_s)||^2 with W_s = L_s^-1 and L_s the lower Cholesky factor of Sigma_s, so it is never
+    negative; rounded to float32 into the [S, n] score matrix.  d^2 grows linearly with d_s, so ``normalize`` is what to
+    reach for when subspaces of mixed size are summed.  normalize, combination, contamination, ``threshold_``, ``labels_``,
+    ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.  ``fit`` scores the training rows with
+    nothing excluded: ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.
+
+    Degenerate cases go through a per-subspace status word that the host reads once after ``fit``.  tr C_s == 0 (every
+    feature constant on the support): every score of that subspace is exactly 0.  A Cholesky pivot that is not positive and
+    finite: ``fit`` raises ValueError naming the subspace.  That can only happen with alpha_s = 0 on a singular C_s (or
+    non-finite input); the converse does not hold: rounding can leave a singular matrix a tiny positive pivot, which then
+    passes with huge scores, so with duplicated or constant features use shrinkage > 0.
+
+    robust=True is a concentration MCD from a single start, deterministic: (1) start from the all-rows estimate; (2) score
+    all rows; (3) the new support is the h_s rows with the smallest (float32 score as stored, row index); (4) re-estimate
+    mu_s, C_s, alpha_s, W_s on it; repeat from (2) until a support does not change (``converged_[s]``) or max_csteps
+    re-estimates have run; ``n_csteps_[s]`` counts the re-estimates.  h_s = mcd_support_size(n, d_s, support_fraction): min(n,
+    ceil((n + d_s + 1) / 2)), sklearn's rule, or int(support_fraction n), ValueError below 2.  The published scores are those
+    under the final estimate.  Not reproduced: sklearn's random multi-start FastMCD, its consistency correction and its
+    reweighting step; Ledoit-Wolf shrinkage.  Limits: with shrinkage the determinant argument for monotone convergence does
+    not hold strictly, max_csteps is the bound; and a single classical start breaks down under heavy clustered
+    contamination (on the CPU restatement, 1000 x 67 with 30 % of the rows shifted by +6 keeps 124 outliers among the 534 rows
+    of the support and ranks them below the inliers).
+
+    Determinism: the moment sums run over slabs of MAHA_SLAB_ROWS rows cut by n alone, each in a fixed order, added in
+    ascending slab order; no float atomics.  Scores, supports and every published array are bit-identical from run to run
+    and for every workspace_bytes, which limits the slab partials of the moments (maha_ranges: ranges of subspaces, inside
+    a range as many slabs and tiles a launch as fit), not the fitted state: mu_s and three d_s x d_s float64 matrices
+    (Sigma_s, L_s, W_s) per subspace stay on the device; X is not kept.
+
+    ``fit`` publishes, in the given subspace order and fetched from the device on first use: ``location_`` (list of S
+    float64 [d_s]), ``covariance_`` (list of S float64 [d_s, d_s], the shrunk matrix), ``shrinkage_`` (float64 [S]) and, when
+    robust, ``support_`` (bool [S, n]), ``n_csteps_`` (int [S]) and ``converged_`` (bool [S]).  The definition above and its
+    numpy restatement in tests/test_outlier_maha_cpu.py (pinned there to sklearn) are what binds.  All of it runs in
+    libvgan_hip.so (csrc/outlier_maha.hip)."""
+
+    _host_state = None
+
+    def __init__(self, subspaces, proba, shrinkage=0.1, robust=False, support_fraction=None, max_csteps=30,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        self.shrinkage = check_shrinkage(shrinkage)
+        self.robust = bool(robust)
+        self.support_fraction = check_support_fraction(support_fraction)
+        self.max_csteps = check_csteps(max_csteps)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > MAHA_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceMahalanobis takes at most {MAHA_MAX_DIMS}")
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= MAHA_MAX_ROWS:
+            raise ValueError(f"SubspaceMahalanobis fit needs between 2 and {MAHA_MAX_ROWS} rows, got {n}")
+        if self.robust:
+            for d_s in np.unique(self.plan.dims):
+                mcd_support_size(n, d_s, self.support_fraction)
+
+    def _prepare(self, n, dev):
+        """The tables, the fitted state (mu, and Sigma, L, W at sq_off) and the moment workspace for n rows."""
+        S, dims = self.plan.count, self.plan.dims
+        self._fitted, self._host_state = False, None
+        self._sq_off = np.concatenate([[0], np.cumsum(dims * dims)]).astype(np.int64)
+        cells, self._ranges = maha_ranges(dims, self.workspace_bytes)
+        self._tiles = [torch.as_tensor(maha_tiles(dims, first, count), device=dev) for first, count in self._ranges]
+        self._mtable = (self._table[0], self._table[1], torch.as_tensor(self._sq_off, device=dev))
+        widest = max(int(dims[first:first + count].sum()) for first, count in self._ranges)
+        slabs = -(-n // MAHA_SLAB_ROWS)
+        most = max(slabs * widest, slabs * MAHA_TILE * MAHA_TILE * max(int(t.shape[0]) for t in self._tiles))
+        self._ws = torch.empty(min(cells, most), dtype=torch.float64, device=dev)
+        self._mean = torch.empty(int(dims.sum()), dtype=torch.float64, device=dev)
+        self._cov, self._L, self._W = (torch.empty(int(self._sq_off[-1]), dtype=torch.float64, device=dev) for _ in range(3))
+        self._alpha = torch.empty(S, dtype=torch.float64, device=dev)
+        self._status = torch.zeros(S, dtype=torch.int32, device=dev)
+
+    def _moments(self, X, support, hcount):
+        """mu and C of every subspace over the rows of its support (None: every row), range by range."""
+        for (first, count), tiles in zip(self._ranges, self._tiles):
+            dims = self.plan.dims[first:first + count]
+            self.ops.maha_moments(X, self._mtable, first, count, int(dims.sum()), int(dims.max()), tiles, support, hcount, self._mean,
+                                  self._cov, self._ws)
+
+    def _factor(self, hcount):
+        """alpha, Sigma (over C), L and W of every subspace from its C."""
+        alpha = _MAHA_OAS if self.shrinkage == "oas" else self.shrinkage
+        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
+            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+            self.ops.maha_factor(self._cov, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), hcount, alpha,
+                                 self._L, self._W, self._alpha, self._status)
+
+    def _estimate(self, X, support, hcount):
+        self._moments(X, support, hcount)
+        self._factor(hcount)
+
+    def _distances(self, X):
+        """float32 [S, nq] on the device: the squared distances of the rows of X under the current estimate."""
+        per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
+        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
+            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+            self.ops.maha_scores(X, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), self._mean, self._W, per)
+        return per
+
+    def _score(self, X, fitting):
+        per = self._distances(X)
+        return self._combine(per, fitting), per
+
+    def _concentrate(self, X, per):
+        """The C-steps; returns the scores under the final estimate."""
+        S, n, dev = self.plan.count, X.shape[0], X.device
+        self._support = torch.ones(S, n, dtype=torch.uint8, device=dev)
+        changed = torch.empty(S, dtype=torch.int32, device=dev)
+        converged, steps = np.zeros(S, dtype=bool), np.zeros(S, dtype=np.int64)
+        for step in range(self.max_csteps):
+            for first in range(0, S, _MAHA_MAX_RANGE):
+                self.ops.maha_select(per, first, min(_MAHA_MAX_RANGE, S - first), self._h, self._support, changed)
+            converged |= changed.cpu().numpy() == 0  # a converged support gives the same estimate again, bit for bit
+            if converged.all():
+                break
+            steps[~converged] += 1
+            self._estimate(X, self._support, self._h)
+            per = self._distances(X)
+        self.n_csteps_, self.converged_ = steps, converged
+        return per
+
+    def _fetch(self):
+        self._require_fit()
+        if self._host_state is None:
+            mean, cov = self._mean.cpu().numpy(), self._cov.cpu().numpy()
+            off, sq = self.plan.feat_off, self._sq_off
+            d = self.plan.dims
+            self._host_state = ([mean[off[s]:off[s + 1]].copy() for s in range(self.plan.count)],
+                                [cov[sq[s]:sq[s + 1]].reshape(int(d[s]), int(d[s])).copy() for s in range(self.plan.count)],
+                                self._alpha.cpu().numpy(), self._support.cpu().numpy().astype(bool) if self.robust else None)
+        return self._host_state
+
+    @property
+    def location_(self):
+        """List of S float64 [d_s]: mu_s of the final estimate."""
+        return self._fetch()[0]
+
+    @property
+    def covariance_(self):
+        """List of S float64 [d_s, d_s]: the shrunk matrix Sigma_s of the final estimate."""
+        return self._fetch()[1]
+
+    @property
+    def shrinkage_(self):
+        """float64 [S]: alpha_s of the final estimate."""
+        return self._fetch()[2]
+
+    @property
+    def support_(self):
+        """bool [S, n]: the rows of the final support (robust=True only)."""
+        if not self.robust:
+            raise AttributeError("support_ is published with robust=True only")
+        return self._fetch()[3]
+
+    def fit(self, X, y=None):
+        """Estimates mu_s and Sigma_s of every subspace (with robust=True by C-steps), then scores X itself: decision_scores_
+        (float64 [n]), per_subspace_scores_, location_, covariance_, shrinkage_ and, when robust, support_, n_csteps_,
+        converged_; with normalize also score_center_ / score_scale_.  Raises ValueError for a subspace whose Cholesky
+        factor does not exist."""
+        X = self._begin_fit(X)
+        n, S = X.shape[0], self.plan.count
+        self._prepare(n, X.device)
+        self._estimate(X, None, torch.full((S,), n, dtype=torch.int32, device=X.device))
+        per = self._distances(X)
+        if self.robust:
+            h = [mcd_support_size(n, d_s, self.support_fraction) for d_s in self.plan.dims]
+            self._h = torch.as_tensor(np.array(h, dtype=np.int32), device=X.device)
+            per = self._concentrate(X, per)
+        failed = np.flatnonzero(self._status.cpu().numpy() & _MAHA_PIVOT)
+        if failed.size:
+            raise ValueError(f"subspace {int(failed[0])}: its covariance has no Cholesky factor (a pivot was not positive and finite: "
+                             f"the features are linearly dependent on the support); use shrinkage > 0")
+        del self._ws, self._L
+        return self._publish(self._combine(per, True), per)

@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceIForest
+from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceIForest, SubspaceMahalanobis
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -189,7 +189,12 @@ class _RunFolder:
         method "iforest" builds a SubspaceIForest (isolation forest: random trees on sampled rows, no sweep over pairs of
         rows; sklearn's IsolationForest, pyod's IForest): its keywords are n_estimators, max_samples, seed, workspace_bytes
         and the same normalize / combination / contamination, e.g. outlier_ensemble(method="iforest", n_estimators=100,
-        X=X); n_neighbors is not used there."""
+        X=X); n_neighbors is not used there.
+        method "mahalanobis" builds a SubspaceMahalanobis (squared Mahalanobis distance under a shrunk covariance per
+        subspace; sklearn's ShrunkCovariance / OAS .mahalanobis) and method "mcd" the same with robust=True (a
+        deterministic single-start concentration MCD; pyod's MCD up to the estimator): its keywords are shrinkage,
+        support_fraction, max_csteps, workspace_bytes and the same normalize / combination / contamination, e.g.
+        outlier_ensemble(method="mcd", normalize="zscore", X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -200,6 +205,10 @@ class _RunFolder:
             ens = SubspaceECOD(self.subspaces, self.proba, **kw)
         elif method == "iforest":
             ens = SubspaceIForest(self.subspaces, self.proba, **kw)
+        elif method == "mahalanobis":
+            ens = SubspaceMahalanobis(self.subspaces, self.proba, **kw)
+        elif method == "mcd":
+            ens = SubspaceMahalanobis(self.subspaces, self.proba, robust=True, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
