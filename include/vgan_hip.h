@@ -862,6 +862,60 @@ int vgan_maha_scores(const float* Xq, int ldq, int rows, int d, const int32_t* f
 int vgan_maha_select(const float* score, int64_t ld_score, int n, int first, int count, const int32_t* hcount,
                      uint8_t* support, int64_t ld_support, int32_t* changed, vgan_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gaussian-mixture outlier scores (sklearn's GaussianMixture with covariance_type "full", n_init 1; pyod's GMM): EM for
+ * n_components = C full-covariance Gaussians per subspace and score = -log sum_c w_c N(x; mu_c, Sigma_c)  (v-gan_amd/outlier.py:
+ * SubspaceGMM, whose docstring is the definition; kernels in csrc/outlier_gmm.hip).  X is float32, all arithmetic float64.
+ * The (subspace, component) pairs are the entries e = s C + c of an EXPANDED subspace table: feat holds the feature list of
+ * every subspace C times, feat_off int32 [S C + 1] and sq_off int64 [S C + 1] (running sum of d_s^2) accordingly; mean at
+ * feat_off[e], cov / L / W at sq_off[e], nk, weights, log_weights, logdet and the factor's status at e.  With that table
+ * vgan_maha_factor(shrinkage = 0) on the entries first C .. (first + count) C - 1 gives L and W of every component and leaves
+ * cov as it is.  Every entry below works on the SUBSPACES first .. first + count - 1, count C <= 65535, 1 <= C <=
+ * VGAN_GMM_MAX_COMPONENTS, max_dims >= every d_s of the range, d_s <= VGAN_MAHA_MAX_DIMS.  resp float64 [count, C, n]: the
+ * responsibilities of the range.  done int32 [S] (NULL: none): a subspace whose flag is not 0 is frozen, its workgroups
+ * return at once and nothing of it is written.
+ * vgan_gmm_moments: nk_c = sum_i r_ic + 10 eps, mu_c = sum_i r_ic x_i / nk_c, cov = Sigma_c = sum_i r_ic (x_i - mu_c)(x_i -
+ *   mu_c)^T / nk_c + reg_covar I (two passes, both triangles written), weights = nk_c / sum_c nk_c (c ascending), log_weights
+ *   its logarithm; from X [n, d] (ldx), 2 <= n <= VGAN_MAHA_MAX_ROWS.  The rows are cut into slabs of VGAN_MAHA_SLAB_ROWS
+ *   rows by n alone; a slab's sum has a fixed order (the covariance on the f64 matrix unit with A = r (x - mu), B = x - mu)
+ *   and the slabs are added in ascending order, so the bits do not depend on the workspace.  tiles int32 [n_tiles, 3]: (e,
+ *   ti, tj), tj <= ti < ceil(d_e / 16), every lower-triangle tile of every entry of the range; total_dims = the sum of d_e
+ *   over the entries of the range.  workspace: at least 8 (total_dims + count C) and at least 2048 bytes.
+ * vgan_gmm_logdet: logdet[e] = sum_j log L_e[j, j], a fixed order.
+ * vgan_gmm_estep: lp_ic = -0.5 (d_s log 2pi + ||W_c (x_i - mu_c)||^2) - logdet_c + log w_c for the rows of Xq [rows, d] (ldq),
+ *   the product as in vgan_maha_scores with the float64 square sum kept; ln_i = logsumexp_c lp_ic (the maximum subtracted,
+ *   c ascending).  resp (or NULL) receives exp(lp_ic - ln_i), evaluated as exp(lp_ic - max) / sum_c exp(lp_ic - max) so that a row
+ *   sums to 1 within a few ulps whatever the size of ln_i; score (or NULL; float32 [S, ld_score], row s) receives
+ *   float32(-ln_i); lb_partial (or NULL; float64 [count, ceil(rows / 64)], needs resp) the sum of ln_i over each 64 rows in a
+ *   fixed order.  At least one of resp and score is given.  The bits of a row do not depend on where it sits in the call.
+ *   d and max_dims are only range-checked here (ldq >= d > 0, 1 <= max_dims <= VGAN_MAHA_MAX_DIMS): the kernel's LDS need does
+ *   not depend on d_s, so max_dims sizes nothing, and the entries of feat are the caller's to keep below d, as for
+ *   vgan_maha_scores.  Both stay in the signature so that the entry reads like the other subspace-table entries.
+ * vgan_gmm_converge: per subspace that is not done: if any status[e] of it is not 0: done = VGAN_GMM_DONE_FAILED.  Otherwise,
+ *   for iteration >= 1: lb = (sum of lb_partial, each slab of VGAN_MAHA_SLAB_ROWS rows in order, the slabs ascending) / n,
+ *   n_iter = iteration, lower_bound = lb; |lb - lb_prev| < tol sets done = VGAN_GMM_DONE_CONVERGED, otherwise lb_prev = lb
+ *   (the caller starts lb_prev at -inf).  iteration 0 only looks at the status (lb_partial may be NULL).  lb_partial is
+ *   overwritten.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_GMM_MAX_COMPONENTS 32
+#define VGAN_GMM_DONE_CONVERGED 1
+#define VGAN_GMM_DONE_FAILED 2
+int vgan_gmm_moments(const float* X, int ldx, int n, int d, const int32_t* feat, const int32_t* feat_off,
+                     const int64_t* sq_off, int n_components, int first, int count, int total_dims, int max_dims,
+                     const int32_t* tiles, int n_tiles, const double* resp, const int32_t* done, double reg_covar, double* nk,
+                     double* weights, double* log_weights, double* mean, double* cov, void* workspace,
+                     int64_t workspace_bytes, vgan_stream_t stream);
+int vgan_gmm_logdet(const double* L, const int32_t* feat_off, const int64_t* sq_off, int n_components, int first, int count,
+                    double* logdet, vgan_stream_t stream);
+int vgan_gmm_estep(const float* Xq, int ldq, int rows, int d, const int32_t* feat, const int32_t* feat_off,
+                   const int64_t* sq_off, int n_components, int first, int count, int max_dims, const double* mean,
+                   const double* W, const double* logdet, const double* log_weights, const int32_t* done, double* resp,
+                   double* lb_partial, float* score, int64_t ld_score, vgan_stream_t stream);
+int vgan_gmm_converge(double* lb_partial, int n, int n_components, int first, int count, const int32_t* status, double tol,
+                      int iteration, int32_t* done, int32_t* n_iter, double* lower_bound, double* lb_prev,
+                      vgan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,12 @@ difference of the two paths' ensemble scores.
     factor, scores); (a) a float64 torch restatement on the same GPU (per subspace: gather, mean, centred product,
     torch.linalg.cholesky, solve_triangular, the squared column norms) and (b) sklearn's ShrunkCovariance(0.1).fit /
     .mahalanobis per subspace on the host, for a sample of the subspaces scaled to all of them.
+  --method gmm: Gaussian-mixture scores (vgan_amd.SubspaceGMM, C = 4, reg_covar 1e-6) from random start labels with tol = 0
+    and max_iter = 10, so that every path runs the same ten EM iterations: fit and decision_function (the training rows as
+    queries); one iteration split into its calls (E step, moments, factor + log-determinants), the E step's rate counted as
+    the full product 2 n C sum d_s^2 (what vgan_maha_scores is counted as in outlier_maha_bench.json); and sklearn's
+    GaussianMixture(max_iter=10, tol=0) from the same start (weights, means and precisions after the first M step) on the
+    host for a sample of the subspaces, scaled to all of them.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -572,6 +578,65 @@ def run_maha(d, n, count, reps, baselines=True, sklearn_sample=8):
     return row
 
 
+def run_gmm(d, n, count, reps, baselines=True, sklearn_sample=3, C=4, iters=10):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    labels = np.random.default_rng(0).integers(0, C, size=n)
+    ens = vgan_amd.SubspaceGMM(m, p, n_components=C, init=labels, tol=0.0, max_iter=iters)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    ours = ens.per_subspace_scores_.astype(np.float64)
+    # one iteration, call by call, on the state the start leaves (the responsibilities a range finds are the last range's)
+    inner = max(reps, 5)
+    ens._prepare(n, Xd.device)
+    ens._em_start(Xd, torch.as_tensor(np.broadcast_to(labels, (S, n)).copy(), device="cuda"))
+    ranges = range(len(ens._ranges))
+    t_e, _ = timed(lambda: [ens._e_step(Xd, i) for i in ranges], inner)
+    t_mom, _ = timed(lambda: [ens._moments(Xd, i) for i in ranges], inner)
+    t_fac, _ = timed(lambda: [ens._factor(i) for i in ranges], inner)
+    flops = 2.0 * n * C * float((dims.astype(np.float64) ** 2).sum())
+    row = {"method": "gmm", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_components": C, "em_iterations": iters,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()), "ranges": len(ens._ranges),
+           "fit_s": round(t_fit, 6), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td,
+           "estep_s": round(t_e, 6), "moments_s": round(t_mom, 6), "factor_s": round(t_fac, 6),
+           "estep_full_product_tflops": round(flops / t_e / 1e12, 3), "moments_full_product_tflops": round(flops / t_mom / 1e12, 3),
+           "iteration_share_estep_moments_factor": [round(t / (t_e + t_mom + t_fac), 3) for t in (t_e, t_mom, t_fac)],
+           "state_bytes": int(2 * 8 * C * (dims.astype(np.int64) ** 2).sum())}
+    if baselines:
+        try:
+            import warnings
+            from sklearn.mixture import GaussianMixture
+            pick = np.unique(np.linspace(0, S - 1, min(S, sklearn_sample)).astype(int))
+            R = np.zeros((n, C))
+            R[np.arange(n), labels] = 1.0
+            nk = R.sum(axis=0) + 10.0 * np.finfo(np.float64).eps
+            t_sk, worst = 0.0, 0.0
+            for s in pick:
+                Xs = np.ascontiguousarray(X[:, np.flatnonzero(m[s])]).astype(np.float64)
+                mu = R.T @ Xs / nk[:, None]
+                prec = []
+                for c in range(C):
+                    E = Xs - mu[c]
+                    Sigma = (R[:, c] * E.T) @ E / nk[c]
+                    Sigma.flat[::Xs.shape[1] + 1] += 1e-6
+                    prec.append(np.linalg.inv(Sigma))
+                gm = GaussianMixture(n_components=C, reg_covar=1e-6, tol=0.0, max_iter=iters, weights_init=nk / nk.sum(), means_init=mu,
+                                     precisions_init=np.stack(prec))
+                t0 = time.perf_counter()
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")  # ten iterations at tol = 0 do not converge, by design
+                    theirs = -gm.fit(Xs).score_samples(Xs)
+                t_sk += time.perf_counter() - t0
+                worst = max(worst, float(np.max(np.abs(ours[s] - theirs) / np.maximum(np.abs(theirs), 1e-300))))
+            scale = S / len(pick)
+            row.update({"sklearn_fit_and_score_s": round(t_sk * scale, 4), "sklearn_subspaces_timed": int(len(pick)),
+                        "fit_speedup_vs_sklearn": round(t_sk * scale / (t_fit + t_dec), 1), "max_rel_diff_vs_sklearn": worst})
+        except ImportError:
+            row["sklearn_fit_and_score_s"] = None
+    return row
+
+
 def host_normalized(per, proba, mode):
     """The numpy alternative to csrc/outlier_norm.hip: float64 statistics per row of per [S, n], transform, weighted sum."""
     x = per.astype(np.float64)
@@ -669,13 +734,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -742,6 +807,15 @@ def main():
             shapes = [tuple(int(v) for v in args.shape.split(","))]
         for d, n, count in shapes:
             out["configs"].append(run_maha(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "gmm":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_gmm(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     for d, n, count, k, with_base in configs:

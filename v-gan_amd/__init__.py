@@ -8,8 +8,9 @@ from . import lib  # noqa: F401
 from .modules import (Generator_big, upper_softmax, Encoder, Decoder, Detector, RBF,  # noqa: F401
                       MMDLossConstrained)
 from .vgan import VGAN, VGAN_no_kl  # noqa: F401
-from .outlier import SubspaceEnsemble, SubspaceCBLOF, SubspaceABOD, SubspaceECOD, SubspaceIForest, SubspaceMahalanobis  # noqa: F401
+from .outlier import (SubspaceEnsemble, SubspaceCBLOF, SubspaceABOD, SubspaceECOD, SubspaceIForest, SubspaceMahalanobis,  # noqa: F401
+                      SubspaceGMM)
 
 __all__ = ["VGAN", "VGAN_no_kl", "Generator_big", "upper_softmax", "Encoder", "Decoder", "Detector", "RBF",
-           "MMDLossConstrained", "SubspaceEnsemble", "SubspaceCBLOF", "SubspaceABOD", "SubspaceECOD", "SubspaceIForest", "SubspaceMahalanobis",
-           "lib"]
+           "MMDLossConstrained", "SubspaceEnsemble", "SubspaceCBLOF", "SubspaceABOD", "SubspaceECOD", "SubspaceIForest",
+           "SubspaceMahalanobis", "SubspaceGMM", "lib"]

@@ -935,6 +935,80 @@ class HipOps:
         _lib.check(self.lib.vgan_maha_select(_ptr(score), score.stride(0), n, int(first), int(count), _ptr(hcount), _ptr(support), n,
                                              _ptr(changed), self._stream()), "vgan_maha_select")
 
+    # ---- Gaussian mixtures over subspaces (vgan_amd.outlier.SubspaceGMM) ------------------------------------
+    # table: the EXPANDED table (feat int32, feat_off int32 [S C + 1], sq_off int64 [S C + 1]) of the entries e = s C + c;
+    # first / count are subspaces; done int32 [S] or None
+    def gmm_moments(self, X, table, n_components, first, count, total_dims, max_dims, tiles, resp, done, reg_covar, nk, weights,
+                    log_weights, mean, cov, workspace):
+        """nk, weights, log_weights (float64 [S C]), mean (at feat_off[e]) and cov (at sq_off[e]) of the subspaces first ..
+        first + count - 1 that are not done, from X and the responsibilities resp (float64, count C n values); tiles int32
+        [n_tiles, 3]: the lower-triangle tiles (e, ti, tj) of the range; total_dims: the sum of d_e over its entries."""
+        _mat(X, "X"), _vec(tiles, "tiles", torch.int32), _vec(resp, "resp", torch.float64), _vec(workspace, "workspace", torch.float64)
+        for name, v in (("nk", nk), ("weights", weights), ("log_weights", log_weights), ("mean", mean), ("cov", cov)):
+            _vec(v, name, torch.float64)
+        if done is not None:
+            _vec(done, "done", torch.int32)
+            assert done.numel() >= first + count
+        feat, feat_off, sq_off = table
+        n, d = X.shape
+        entries = (first + count) * n_components
+        assert tiles.dim() == 2 and tiles.shape[1] == 3 and resp.numel() >= count * n_components * n
+        assert feat_off.numel() > entries and min(nk.numel(), weights.numel(), log_weights.numel()) >= entries
+        _lib.check(self.lib.vgan_gmm_moments(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(sq_off), int(n_components),
+                                             int(first), int(count), int(total_dims), int(max_dims), _ptr(tiles), tiles.shape[0], _ptr(resp),
+                                             _ptr(done), float(reg_covar), _ptr(nk), _ptr(weights), _ptr(log_weights), _ptr(mean),
+                                             _ptr(cov), _ptr(workspace), workspace.numel() * 8, self._stream()), "vgan_gmm_moments")
+
+    def gmm_logdet(self, L, table, n_components, first, count, logdet):
+        """logdet float64 [S C]: sum_j log L_e[j, j] of the entries of the subspaces first .. first + count - 1."""
+        _vec(L, "L", torch.float64), _vec(logdet, "logdet", torch.float64)
+        _, feat_off, sq_off = table
+        assert logdet.numel() >= (first + count) * n_components < feat_off.numel()
+        _lib.check(self.lib.vgan_gmm_logdet(_ptr(L), _ptr(feat_off), _ptr(sq_off), int(n_components), int(first), int(count), _ptr(logdet),
+                                            self._stream()), "vgan_gmm_logdet")
+
+    def gmm_estep(self, Xq, table, n_components, first, count, max_dims, mean, W, logdet, log_weights, done=None, resp=None,
+                  lb_partial=None, score=None):
+        """The E step of the subspaces first .. first + count - 1 that are not done on the rows of Xq: resp (float64, count C
+        rows values) the responsibilities, lb_partial (float64, count ceil(rows / 64) values) the sums of ln_i per 64 rows,
+        score (float32 [S, rows], a view into the score matrix may be given) float32(-ln_i) in rows first .. of it."""
+        _mat(Xq, "Xq")
+        for name, v in (("mean", mean), ("W", W), ("logdet", logdet), ("log_weights", log_weights)):
+            _vec(v, name, torch.float64)
+        feat, feat_off, sq_off = table
+        rows, d = Xq.shape
+        assert feat_off.numel() > (first + count) * n_components <= min(logdet.numel(), log_weights.numel())
+        if done is not None:
+            _vec(done, "done", torch.int32)
+            assert done.numel() >= first + count
+        if resp is not None:
+            _vec(resp, "resp", torch.float64)
+            assert resp.numel() >= count * n_components * rows
+        if lb_partial is not None:
+            _vec(lb_partial, "lb_partial", torch.float64)
+            assert lb_partial.numel() >= count * ((rows + 63) // 64)
+        if score is not None:
+            _mat(score, "score")
+            assert score.shape[0] >= first + count and score.shape[1] >= rows
+        _lib.check(self.lib.vgan_gmm_estep(_ptr(Xq), Xq.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(sq_off), int(n_components),
+                                           int(first), int(count), int(max_dims), _ptr(mean), _ptr(W), _ptr(logdet), _ptr(log_weights),
+                                           _ptr(done), _ptr(resp), _ptr(lb_partial), _ptr(score),
+                                           score.stride(0) if score is not None else 0, self._stream()), "vgan_gmm_estep")
+
+    def gmm_converge(self, lb_partial, n, n_components, first, count, status, tol, iteration, done, n_iter, lower_bound, lb_prev):
+        """sklearn's stop rule per subspace of the range, on the device: done / n_iter int32 [S], lower_bound / lb_prev float64
+        [S]; status int32 [S C] is the factor's; iteration 0 only turns a failed status into a done flag."""
+        _vec(status, "status", torch.int32), _vec(done, "done", torch.int32), _vec(n_iter, "n_iter", torch.int32)
+        _vec(lower_bound, "lower_bound", torch.float64), _vec(lb_prev, "lb_prev", torch.float64)
+        if lb_partial is not None:
+            _vec(lb_partial, "lb_partial", torch.float64)
+            assert lb_partial.numel() >= count * ((n + 63) // 64)
+        assert status.numel() >= (first + count) * n_components
+        assert min(done.numel(), n_iter.numel(), lower_bound.numel(), lb_prev.numel()) >= first + count
+        _lib.check(self.lib.vgan_gmm_converge(_ptr(lb_partial), int(n), int(n_components), int(first), int(count), _ptr(status), float(tol),
+                                              int(iteration), _ptr(done), _ptr(n_iter), _ptr(lower_bound), _ptr(lb_prev), self._stream()),
+                   "vgan_gmm_converge")
+
 
 _default = None
 

@@ -57,6 +57,11 @@ deterministic concentration steps (MCD), and the squared Mahalanobis distance as
 matrix unit (csrc/outlier_maha.hip); n d_s^2 per subspace.  Its contract (support, location, covariance, shrinkage and the
 OAS rule, the score, the degenerate cases, the C-steps, determinism) is that class's docstring.
 
+``SubspaceGMM`` is the probabilistic mixture: EM for a few full-covariance Gaussians per subspace, the stop rule decided per
+subspace on the device, and the negative log-likelihood as the score (csrc/outlier_gmm.hip, with the factor of
+csrc/outlier_maha.hip on the (subspace, component) pairs and the k-means start of csrc/cluster.hip); n C d_s^2 per
+iteration.  Its contract (the start, the M and E steps, the loop, freezing, failures, determinism) is that class's docstring.
+
 The classes differ in their scores only.  The constructor tail, the first touch of the device (at the first ``fit``,
 never in a constructor), the head and the tail of ``fit``, ``decision_function`` and the tail above (normalize,
 combination, contamination, predict) are ``_SubspaceScorer``; the neighbour search and its chunk loop are
@@ -1490,3 +1495,316 @@ class SubspaceMahalanobis(_SubspaceScorer):
                              f"the features are linearly dependent on the support); use shrinkage > 0")
         del self._ws, self._L
         return self._publish(self._combine(per, True), per)
+
+
+# ---- Gaussian mixtures: EM per subspace, the negative log-likelihood as the score ------------------------------------
+GMM_MAX_COMPONENTS = 32  # VGAN_GMM_MAX_COMPONENTS: the log probabilities of a row's components live in LDS
+_GMM_CONVERGED, _GMM_FAILED = 1, 2  # VGAN_GMM_DONE_*
+_GMM_ROW_BLOCK = 64  # rows of one E-step workgroup: the lower bound is summed per block, then per slab
+
+
+def check_gmm_params(n_components, reg_covar, tol, max_iter, kmeans_max_iter):
+    if not (_is_int(n_components) and 1 <= int(n_components) <= GMM_MAX_COMPONENTS):
+        raise ValueError(f"n_components must be an integer between 1 and {GMM_MAX_COMPONENTS}, got {n_components!r}")
+    if not (_is_real(reg_covar) and np.isfinite(reg_covar) and float(reg_covar) >= 0.0):
+        raise ValueError(f"reg_covar must be a finite float >= 0, got {reg_covar!r}")
+    if not (_is_real(tol) and np.isfinite(tol) and float(tol) >= 0.0):
+        raise ValueError(f"tol must be a finite float >= 0, got {tol!r}")
+    if not (_is_int(max_iter) and int(max_iter) >= 1):
+        raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
+    if not (_is_int(kmeans_max_iter) and int(kmeans_max_iter) >= 1):
+        raise ValueError(f"kmeans_max_iter must be a positive integer, got {kmeans_max_iter!r}")
+    return int(n_components), float(reg_covar), float(tol), int(max_iter), int(kmeans_max_iter)
+
+
+def check_gmm_init(init, n_components, n_subspaces):
+    """init as the constructor can judge it, without the data: "kmeans", or an integer array of labels [n] or [S, n] with
+    values in [0, n_components).  Returns "kmeans" or ("labels", int64 [n] or [S, n])."""
+    if isinstance(init, str):
+        if init != "kmeans":
+            raise ValueError(f"init must be 'kmeans' or an integer array of labels, got {init!r}")
+        return "kmeans"
+    labels = _index_array(init)
+    if labels is None:
+        raise ValueError(f"init must be 'kmeans' or an integer array of labels, got {type(init).__name__}")
+    labels = np.asarray(labels, dtype=np.int64)
+    if labels.ndim not in (1, 2) or (labels.ndim == 2 and labels.shape[0] != n_subspaces):
+        raise ValueError(f"init labels must have shape (n,) or ({n_subspaces}, n), got {labels.shape}")
+    if (labels < 0).any() or (labels >= n_components).any():
+        raise ValueError(f"init labels must lie in [0, {n_components}), got {int(labels.min())} .. {int(labels.max())}")
+    return "labels", np.ascontiguousarray(labels)
+
+
+def resolve_gmm_labels(init, n, n_subspaces):
+    """int64 [S, n]: the labels of ("labels", array) for n data rows, an [n] array repeated for every subspace."""
+    labels = init[1]
+    if labels.shape[-1] != n:
+        raise ValueError(f"init labels cover {labels.shape[-1]} rows, fit was given {n}")
+    return np.broadcast_to(labels, (n_subspaces, n))
+
+
+def gmm_table(feat, feat_off, n_components):
+    """(feat int32, feat_off int32 [S C + 1], sq_off int64 [S C + 1]): the expanded subspace table whose entry e = s C + c is
+    component c of subspace s: the feature list of s repeated C times, the running sums of d_s and of d_s^2 accordingly."""
+    feat, feat_off, C = np.asarray(feat), np.asarray(feat_off), int(n_components)
+    lists = [feat[feat_off[s]:feat_off[s + 1]] for s in range(len(feat_off) - 1)]
+    dims = np.repeat(np.diff(feat_off).astype(np.int64), C)
+    return (np.concatenate([np.tile(f, C) for f in lists]).astype(np.int32), np.concatenate([[0], np.cumsum(dims)]).astype(np.int32),
+            np.concatenate([[0], np.cumsum(dims * dims)]).astype(np.int64))
+
+
+def gmm_ranges(dims, n_components, n, workspace_bytes):
+    """(the float64 cells of the moment workspace, [(first, count)]): consecutive subspace ranges whose responsibilities (8 C n
+    bytes a subspace) fit in workspace_bytes, whose slab sums (C (d_s + 1) float64 a subspace) fit in the workspace and
+    whose C count entries fit one launch; a range is never smaller than one subspace, the workspace never smaller than one
+    subspace's sums or one 16 x 16 tile."""
+    dims, C = [int(v) for v in dims], int(n_components)
+    need = [C * (v + 1) for v in dims]
+    cells = max(int(workspace_bytes) // 8, max(need), MAHA_TILE * MAHA_TILE)
+    most = max(1, min(int(workspace_bytes) // (8 * C * int(n)), _MAHA_MAX_RANGE // C))
+    out, first = [], 0
+    while first < len(dims):
+        end, used = first, 0
+        while end < len(dims) and end - first < most and (end == first or used + need[end] <= cells):
+            used += need[end]
+            end += 1
+        out.append((first, end - first))
+        first = end
+    return cells, out
+
+
+class SubspaceGMM(_SubspaceScorer):
+    """Negative log-likelihood per subspace under a Gaussian mixture of n_components = C full-covariance components fitted
+    by EM (pyod's ``GMM``; sklearn's ``GaussianMixture(covariance_type="full", n_init=1)`` and minus its ``score_samples``),
+    combined like the other detectors of this module: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new
+    rows; higher is more outlying.  A single covariance per subspace (SubspaceMahalanobis) is blind to rows that fall between
+    the modes of multi-modal data; the mixture sees them at n C d_s^2 per EM iteration, nothing n x n, and keeps C small
+    matrices per subspace.
+
+    X is cast to float32; all arithmetic is float64 on those values.  n rows are given to ``fit``, max(2, C) <= n <=
+    MAHA_MAX_ROWS (2^24); a subspace has at most MAHA_MAX_DIMS (1024) features; 1 <= C <= GMM_MAX_COMPONENTS (32).  Per
+    subspace s (features F_s, d_s of them) and component c:
+
+        start    hard labels l_i in [0, C) become one-hot responsibilities r_ic; one M step follows.
+        M step   nk_c = sum_i r_ic + 10 eps (eps the float64 machine epsilon);  mu_c = sum_i r_ic x_i / nk_c;
+                 Sigma_c = sum_i r_ic (x_i - mu_c)(x_i - mu_c)^T / nk_c + reg_covar I  (two passes);  w_c = nk_c / sum_c nk_c.
+        E step   lp_ic = -0.5 (d_s log 2pi + ||W_c (x_i - mu_c)||^2) - sum_j log L_c[j, j] + log w_c, L_c the lower Cholesky
+                 factor of Sigma_c and W_c = L_c^-1;  ln_i = logsumexp_c lp_ic (the maximum subtracted first);
+                 r_ic = exp(lp_ic - ln_i), evaluated as exp(lp_ic - max) / sum_c exp(lp_ic - max): the same number without the
+                 half ulp of ln_i, so that a row of responsibilities sums to 1 within a few ulps;  lb = (1 / n) sum_i ln_i.
+        loop     lb_prev = -inf; for it = 1 .. max_iter: E step (lb), M step, then |lb - lb_prev| < tol stops the subspace at
+                 this it (``converged_[s]``), otherwise lb_prev = lb.  ``n_iter_[s]`` = it; ``lower_bound_[s]`` is the last lb,
+                 which belongs to the parameters before the last M step, as in sklearn.  tol = 0 never fires and runs
+                 max_iter iterations.  No warning is raised.
+        score    -ln_i under the final parameters, rounded to float32 into the [S, n] score matrix.
+
+    init "kmeans" (default) takes the labels from SubspaceCBLOF(subspaces, proba, n_clusters=C, init="random", seed=seed,
+    max_iter=kmeans_max_iter) fitted on the same X (its ``cluster_labels_``); with C = 1 every label is 0 and no k-means
+    runs.  Or an integer array of labels [n] or [S, n] (given subspace order).  An empty component follows the formulas: mu
+    = 0, Sigma = reg_covar I, w about 2e-15 / n, as sklearn's would.  normalize, combination, contamination, ``threshold_``,
+    ``labels_``, ``predict`` (outlier labels), ``predict_proba`` and return_per_subspace are the shared tail.  ``fit`` scores
+    the training rows with nothing left out: ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.
+
+    Failures: a Cholesky pivot that is not positive and finite, or tr Sigma_c == 0, can only occur with reg_covar = 0.  The
+    device marks such a subspace done so that it does not hold up the loop; ``fit`` reads the status once at the end and
+    raises ValueError naming the subspace and the component.
+
+    Freezing and determinism: the device decides the stop of a subspace at the exact iteration and a stopped subspace keeps
+    its parameters bit for bit while the others go on; the host only looks at the done flags every ``poll_stride``
+    iterations (an attribute, default POLL_STRIDE; no result depends on it).  The moment and lower-bound sums run over slabs
+    of MAHA_SLAB_ROWS rows cut by n alone, each in a fixed order, added in ascending order; no float atomics; an element of
+    the E step sees k ascending wherever its row sits.  Every published array and score is bit-identical from run to run,
+    for every workspace_bytes, for every poll_stride, and for a subspace fitted alone or together with others.
+    workspace_bytes limits the responsibilities of a range of subspaces (8 C n bytes a subspace, never less than one
+    subspace) and the slab partials of the moments (gmm_ranges); iterations are outermost, the ranges inside them.  The
+    fitted state stays on the device: mu_c, Sigma_c, W_c, the log-determinants and the log-weights; X is not kept.
+
+    ``fit`` publishes, in the given subspace order: ``weights_`` (float64 [S, C]), ``means_`` (list of S float64 [C, d_s]),
+    ``covariances_`` (list of S float64 [C, d_s, d_s]), ``n_iter_`` (int [S]), ``converged_`` (bool [S]) and
+    ``lower_bound_`` (float64 [S]); and ``kmeans_labels_`` (int [S, n]): the start labels that init "kmeans" took from the
+    k-means, None after every other fit (explicit labels, or C = 1, where no k-means runs).  Not built: covariance_type other than "full", n_init > 1, k-means++ starts,
+    warm_start, AIC / BIC and the prediction of components.  The definition above and its numpy restatement in
+    tests/test_outlier_gmm_cpu.py (pinned there to sklearn) are what binds.  All of it runs in libvgan_hip.so
+    (csrc/outlier_gmm.hip, the Cholesky factor and its inverse in csrc/outlier_maha.hip, the k-means start in
+    csrc/cluster.hip)."""
+
+    _host_state = None
+
+    def __init__(self, subspaces, proba, n_components=2, reg_covar=1e-6, tol=1e-3, max_iter=100, init="kmeans", kmeans_max_iter=30,
+                 seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        self.n_components, self.reg_covar, self.tol, self.max_iter, self.kmeans_max_iter = check_gmm_params(
+            n_components, reg_covar, tol, max_iter, kmeans_max_iter)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > MAHA_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceGMM takes at most {MAHA_MAX_DIMS}")
+        self.init = check_gmm_init(init, self.n_components, self.plan.count)
+        self.seed = check_seed(seed)
+        self._subspaces = np.asarray(subspaces).astype(bool)
+        self.poll_stride = POLL_STRIDE
+
+    def _check_fit_rows(self, n):
+        if not max(2, self.n_components) <= n <= MAHA_MAX_ROWS:
+            raise ValueError(f"SubspaceGMM fit needs between {max(2, self.n_components)} (n_components, and at least 2) and "
+                             f"{MAHA_MAX_ROWS} rows, got {n}")
+        if self.init != "kmeans":
+            resolve_gmm_labels(self.init, n, self.plan.count)
+
+    def _prepare(self, n, dev):
+        """The expanded table, the fitted state (per entry e = s C + c: mu at feat_off[e]; Sigma, L, W at sq_off[e]; nk, w,
+        log w, the log-determinant, the factor's status), the loop's flags and the buffers of a range for n rows."""
+        S, C, dims = self.plan.count, self.n_components, self.plan.dims
+        self._fitted, self._host_state = False, None
+        feat, feat_off, sq_off = gmm_table(self.plan.feat, self.plan.feat_off, C)
+        self._efeat_off, self._esq_off = feat_off, sq_off
+        self._etable = tuple(torch.as_tensor(v, device=dev) for v in (feat, feat_off, sq_off))
+        cells, self._ranges = gmm_ranges(dims, C, n, self.workspace_bytes)
+        edims = np.repeat(dims, C)
+        self._tiles = [torch.as_tensor(maha_tiles(edims, first * C, count * C), device=dev) for first, count in self._ranges]
+        widest = max(C * int((dims[first:first + count] + 1).sum()) for first, count in self._ranges)
+        slabs = -(-n // MAHA_SLAB_ROWS)
+        most = max(slabs * widest, slabs * MAHA_TILE * MAHA_TILE * max(int(t.shape[0]) for t in self._tiles))
+        f64 = dict(dtype=torch.float64, device=dev)
+        self._ws = torch.empty(min(cells, most), **f64)
+        largest = max(count for _, count in self._ranges)
+        self._resp = torch.empty(largest * C * n, **f64)
+        self._lbpart = torch.empty(largest * -(-n // _GMM_ROW_BLOCK), **f64)
+        self._mean = torch.empty(int(feat_off[-1]), **f64)
+        self._cov, self._L, self._W = (torch.empty(int(sq_off[-1]), **f64) for _ in range(3))
+        self._nk, self._weights, self._logw, self._logdet, self._alpha = (torch.empty(S * C, **f64) for _ in range(5))
+        self._status = torch.zeros(S * C, dtype=torch.int32, device=dev)
+        self._hcount = torch.full((S * C,), n, dtype=torch.int32, device=dev)  # the factor reads it for the OAS rule only
+        self._done = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._iters = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._lb = torch.full((S,), float("nan"), **f64)
+        self._lb_prev = torch.full((S,), float("-inf"), **f64)
+
+    def _start_labels(self, X):
+        """int64 [S, n] on the device: the hard labels the first M step starts from."""
+        S, n, C = self.plan.count, X.shape[0], self.n_components
+        self.kmeans_labels_ = None  # a refit never shows the labels of an earlier one
+        if self.init != "kmeans":
+            return torch.as_tensor(resolve_gmm_labels(self.init, n, S).copy(), device=X.device)  # broadcast_to gives a read-only view
+        if C == 1:
+            return torch.zeros(S, n, dtype=torch.int64, device=X.device)
+        km = SubspaceCBLOF(self._subspaces, self.proba, n_clusters=C, init="random", seed=self.seed, max_iter=self.kmeans_max_iter)
+        self.kmeans_labels_ = km.fit(X).cluster_labels_
+        return torch.as_tensor(self.kmeans_labels_.astype(np.int64), device=X.device)
+
+    def _moments(self, X, i):
+        """nk, w, log w, mu and Sigma of range i from the responsibilities in _resp."""
+        (first, count), C = self._ranges[i], self.n_components
+        dims = self.plan.dims[first:first + count]
+        self.ops.gmm_moments(X, self._etable, C, first, count, C * int(dims.sum()), int(dims.max()), self._tiles[i], self._resp, self._done,
+                             self.reg_covar, self._nk, self._weights, self._logw, self._mean, self._cov, self._ws)
+
+    def _factor(self, i):
+        """L, W = L^-1 and the log-determinants of range i.  Shrinkage 0 leaves the covariance as it is, so a frozen subspace
+        gets the same matrices again."""
+        (first, count), C = self._ranges[i], self.n_components
+        self.ops.maha_factor(self._cov, self._etable, first * C, count * C, int(self.plan.dims[first:first + count].max()), self._hcount,
+                             0.0, self._L, self._W, self._alpha, self._status)
+        self.ops.gmm_logdet(self._L, self._etable, C, first, count, self._logdet)
+
+    def _converge(self, i, iteration, n):
+        """The stop rule of `iteration` for range i (0: only a failed factor is looked at)."""
+        first, count = self._ranges[i]
+        self.ops.gmm_converge(self._lbpart if iteration else None, n, self.n_components, first, count, self._status, self.tol, iteration,
+                              self._done, self._iters, self._lb, self._lb_prev)
+
+    def _m_step(self, X, i, iteration):
+        self._moments(X, i)
+        self._factor(i)
+        self._converge(i, iteration, X.shape[0])
+
+    def _e_step(self, X, i):
+        (first, count), C = self._ranges[i], self.n_components
+        self.ops.gmm_estep(X, self._etable, C, first, count, int(self.plan.dims[first:first + count].max()), self._mean, self._W,
+                           self._logdet, self._logw, done=self._done, resp=self._resp, lb_partial=self._lbpart)
+
+    def _em_start(self, X, labels):
+        """The one-hot responsibilities of the labels (int64 [S, n] on the device) and the first M step, range by range."""
+        C, n = self.n_components, X.shape[0]
+        for i, (first, count) in enumerate(self._ranges):
+            resp = self._resp[:count * C * n].view(count, C, n)
+            resp.zero_()
+            resp.scatter_(1, labels[first:first + count].unsqueeze(1), 1.0)
+            self._m_step(X, i, 0)
+
+    def _em(self, X, labels):
+        """Iterations outermost, ranges inside.  The host enqueues poll_stride iterations at a time and then reads the done
+        flags through one pinned buffer; the device has stopped every subspace at its own iteration."""
+        S = self.plan.count
+        self._em_start(X, labels)
+        flags = torch.empty(S, dtype=torch.int32).pin_memory()
+        stream = torch.cuda.current_stream()
+        launched = 0
+        while launched < self.max_iter:
+            steps = min(max(1, int(self.poll_stride)), self.max_iter - launched)
+            for it in range(launched + 1, launched + steps + 1):
+                for i in range(len(self._ranges)):
+                    self._e_step(X, i)
+                    self._m_step(X, i, it)
+            launched += steps
+            flags.copy_(self._done, non_blocking=True)
+            stream.synchronize()
+            if bool((flags != 0).all()):
+                break
+
+    def _score(self, X, fitting):
+        C = self.n_components
+        per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
+        for first in range(0, self.plan.count, _MAHA_MAX_RANGE // C):
+            count = min(_MAHA_MAX_RANGE // C, self.plan.count - first)
+            self.ops.gmm_estep(X, self._etable, C, first, count, int(self.plan.dims[first:first + count].max()), self._mean, self._W,
+                               self._logdet, self._logw, score=per)
+        return self._combine(per, fitting), per
+
+    def _fetch(self):
+        self._require_fit()
+        if self._host_state is None:
+            S, C, d = self.plan.count, self.n_components, self.plan.dims
+            mean, cov = self._mean.cpu().numpy(), self._cov.cpu().numpy()
+            off, sq = self._efeat_off, self._esq_off
+            self._host_state = (self._weights.cpu().numpy().reshape(S, C).copy(),
+                                [mean[off[s * C]:off[(s + 1) * C]].reshape(C, int(d[s])).copy() for s in range(S)],
+                                [cov[sq[s * C]:sq[(s + 1) * C]].reshape(C, int(d[s]), int(d[s])).copy() for s in range(S)])
+        return self._host_state
+
+    @property
+    def weights_(self):
+        """float64 [S, C]: w_c of the final parameters."""
+        return self._fetch()[0]
+
+    @property
+    def means_(self):
+        """List of S float64 [C, d_s]: mu_c of the final parameters."""
+        return self._fetch()[1]
+
+    @property
+    def covariances_(self):
+        """List of S float64 [C, d_s, d_s]: Sigma_c of the final parameters (reg_covar on the diagonal)."""
+        return self._fetch()[2]
+
+    def fit(self, X, y=None):
+        """EM per subspace on X from the start labels, then the scores of X itself under the final parameters:
+        decision_scores_ (float64 [n]), per_subspace_scores_, weights_, means_, covariances_, n_iter_, converged_,
+        lower_bound_; with normalize also score_center_ / score_scale_.  Raises ValueError for a component whose covariance
+        has no Cholesky factor."""
+        X = self._begin_fit(X)
+        labels = self._start_labels(X)
+        self._prepare(X.shape[0], X.device)
+        self._em(X, labels)
+        C = self.n_components
+        self.n_iter_ = self._iters.cpu().numpy().astype(np.int64)
+        self.converged_ = self._done.cpu().numpy() == _GMM_CONVERGED
+        self.lower_bound_ = self._lb.cpu().numpy()
+        failed = np.flatnonzero(self._status.cpu().numpy())
+        if failed.size:
+            raise ValueError(f"subspace {int(failed[0]) // C}, component {int(failed[0]) % C}: its covariance has no Cholesky factor (a "
+                             f"pivot was not positive and finite, or its trace is 0: the features are linearly dependent on the rows "
+                             f"of the component); use reg_covar > 0")
+        del self._ws, self._L, self._resp, self._lbpart
+        scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)

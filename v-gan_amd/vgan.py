@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceIForest, SubspaceMahalanobis
+from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceIForest, SubspaceMahalanobis
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -194,7 +194,11 @@ class _RunFolder:
         subspace; sklearn's ShrunkCovariance / OAS .mahalanobis) and method "mcd" the same with robust=True (a
         deterministic single-start concentration MCD; pyod's MCD up to the estimator): its keywords are shrinkage,
         support_fraction, max_csteps, workspace_bytes and the same normalize / combination / contamination, e.g.
-        outlier_ensemble(method="mcd", normalize="zscore", X=X); n_neighbors is not used there."""
+        outlier_ensemble(method="mcd", normalize="zscore", X=X); n_neighbors is not used there.
+        method "gmm" builds a SubspaceGMM (a Gaussian mixture of n_components full covariances per subspace fitted by EM,
+        scored by the negative log-likelihood; sklearn's GaussianMixture, pyod's GMM): its keywords are n_components,
+        reg_covar, tol, max_iter, init, kmeans_max_iter, seed, workspace_bytes and the same normalize / combination /
+        contamination, e.g. outlier_ensemble(method="gmm", n_components=3, X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -209,6 +213,8 @@ class _RunFolder:
             ens = SubspaceMahalanobis(self.subspaces, self.proba, **kw)
         elif method == "mcd":
             ens = SubspaceMahalanobis(self.subspaces, self.proba, robust=True, **kw)
+        elif method == "gmm":
+            ens = SubspaceGMM(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
