@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, vgan_ecod_* and vgan_iforest_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_* and vgan_loda_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -777,6 +777,60 @@ int vgan_ecod_tail_counts(const float* Xq, int ldq, int rows, int d, const float
 int vgan_ecod_scores(const int32_t* cl, const int32_t* cr, int rows, int d, const int8_t* sign, int n, int query,
                      int aggregate, const double* mask, int ldm, int S, double* terms, float* score, int64_t ld_score,
                      vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Histogram outlier scores: HBOS (Goldstein and Dengel 2012; pyod's HBOS) and LODA (Pevny 2016; pyod's LODA) over the
+ * subspaces  (v-gan_amd/outlier.py: SubspaceHBOS and SubspaceLODA, whose docstrings are the definitions; kernels in
+ * csrc/outlier_hist.hip).  They replace numpy.histogram per feature (HBOS) and per random projection (LODA) and the
+ * numpy.digitize / searchsorted lookups of pyod's scoring.  A COLUMN is a feature of X (HBOS: P = d) or the projected value
+ * of one projection of one subspace (LODA: P = S k, column s k + j).  All arithmetic is float64 on the float32 data; -0.0
+ * counts as +0.0.  2 <= B <= VGAN_HIST_MAX_BINS bins; at most VGAN_HIST_MAX_ROWS rows a call.
+ * keys uint64 [P, 2]: order-preserving integer keys of a column's float64 minimum and maximum, gathered with integer
+ *   atomics (exact in any order).  edges float64 [P, B + 1]; counts int32 [P, B].
+ * vgan_hist_column_range: keys of the d columns of X [n, d] (ldx); sets them first.
+ * vgan_hist_edges: lo, hi from the keys (lo == hi: lo - 0.5, lo + 0.5, numpy.histogram's rule), step = (hi - lo) / B,
+ *   e_j = j * step + lo in two roundings, e_B = hi: numpy.linspace(lo, hi, B + 1) bit for bit.
+ * vgan_hist_column_counts: counts of the d columns of X: the bin of x is #{j in 1 .. B - 1 : e_j <= x} (numpy.histogram's;
+ *   a value outside [lo, hi] falls into the first or last bin), by a search of a fixed number of steps; LDS integer
+ *   histograms flushed with integer atomics.  Zeroes counts first.
+ * vgan_hbos_scores: for the query rows Xq [rows, d] (ldq): T[i, f] = table[f, bin(x)], or table[f, B] where x <
+ *   limits[f, 0] or x > limits[f, 1]; table float64 [d, B + 1] (term_f[0 .. B - 1], then the out-of-range term) and limits
+ *   float64 [d, 2] are built on the host from the counts (hbos_term_table).  Then score[s, i] = sum_f mask[f, s] T[i, f]
+ *   on the f64 matrix unit, f ascending, rounded to float32 into score [S, ld_score]: the product of vgan_ecod_scores.
+ *   terms: float64 workspace of rows * d elements.  The bits of score[s, i] depend on the row alone.
+ * vgan_hist_reset: keys (may be NULL) to (above every key, below every key), counts (may be NULL) to 0: before the first
+ *   of the vgan_loda_range / vgan_loda_counts calls that accumulate into them over row chunks.
+ * vgan_loda_*: P is the PACKED block (vgan_outlier_pack, not centred) of `rows` rows for the subspaces first .. first + count
+ *   - 1 of the table (count <= 65535; max_dims >= every round4(d_s) of the range, at most VGAN_LODA_MAX_DIMS).  Subspace s
+ *   has k projections of m_s = moff[s + 1] - moff[s] nonzeros each (moff int64 [S + 1]); nonzero t of projection j is
+ *   pidx / pw [k * moff[s] + t * k + j]: a position within the subspace (clamped to it) and a float64 weight.  z = (((0 + w_0
+ *   x_0) + w_1 x_1) + ...), every product and sum rounded on its own.  1 <= k <= VGAN_LODA_MAX_PROJECTIONS.
+ *   vgan_loda_range merges the keys of z over the rows into keys [S k, 2]; vgan_loda_counts adds the bins of z to counts
+ *   [S k, B]; vgan_loda_scores writes score[s, i] = float32((1 / k) sum_j terms[s k + j, bin(z_j)]) into score [S, ld_score]
+ *   (terms float64 [S k, B], built on the host: loda_term_table), the sum in an order fixed by k alone.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_HIST_MAX_BINS 256
+#define VGAN_HIST_MAX_ROWS 16777216 /* 2^24: the counts stay in int32 */
+#define VGAN_LODA_MAX_PROJECTIONS 1024
+#define VGAN_LODA_MAX_DIMS 8192 /* packed features of one subspace: a row of it is staged in LDS */
+int vgan_hist_column_range(const float* X, int ldx, int n, int d, uint64_t* keys, vgan_stream_t stream);
+int vgan_hist_edges(const uint64_t* keys, int64_t P, int B, double* edges, vgan_stream_t stream);
+int vgan_hist_column_counts(const float* X, int ldx, int n, int d, const double* edges, int B, int32_t* counts,
+                            vgan_stream_t stream);
+int vgan_hbos_scores(const float* Xq, int ldq, int rows, int d, const double* edges, int B, const double* table,
+                     const double* limits, const double* mask, int ldm, int S, double* terms, float* score, int64_t ld_score,
+                     vgan_stream_t stream);
+int vgan_hist_reset(uint64_t* keys, int64_t P, int32_t* counts, int64_t cells, vgan_stream_t stream);
+int vgan_loda_range(const float* P, int rows, const int32_t* feat_off, const int64_t* col_off, int first, int count,
+                    int max_dims, const int32_t* pidx, const double* pw, const int64_t* moff, int k, uint64_t* keys,
+                    vgan_stream_t stream);
+int vgan_loda_counts(const float* P, int rows, const int32_t* feat_off, const int64_t* col_off, int first, int count,
+                     int max_dims, const int32_t* pidx, const double* pw, const int64_t* moff, int k, const double* edges,
+                     int B, int32_t* counts, vgan_stream_t stream);
+int vgan_loda_scores(const float* P, int rows, const int32_t* feat_off, const int64_t* col_off, int first, int count,
+                     int max_dims, const int32_t* pidx, const double* pw, const int64_t* moff, int k, const double* edges,
+                     int B, const double* terms, float* score, int64_t ld_score, vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Isolation forest (Liu, Ting, Zhou 2008; sklearn's IsolationForest, pyod's IForest): T random trees per subspace on psi

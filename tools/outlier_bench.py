@@ -43,6 +43,12 @@ difference of the two paths' ensemble scores.
     the full product 2 n C sum d_s^2 (what vgan_maha_scores is counted as in outlier_maha_bench.json); and sklearn's
     GaussianMixture(max_iter=10, tol=0) from the same start (weights, means and precisions after the first M step) on the
     host for a sample of the subspaces, scaled to all of them.
+  --method hbos / --method loda: the histogram scores (vgan_amd.SubspaceHBOS, 10 bins; vgan_amd.SubspaceLODA, 100
+    projections of 10 bins) on the shapes of the ECOD leg: fit and decision_function (the training rows as queries); the
+    fit split into its stages (HBOS: range, edges, count, lookup + product, the lookup alone from a call with a one-column
+    mask; LODA: whole passes over the chunks, each with its packing: pack alone, range, count, projection + lookup + mean);
+    (a) a float64 torch restatement on the same GPU and (b) numpy on the host (numpy.histogram and searchsorted per
+    column; LODA for a sample of the subspaces, scaled to all of them); and the ECOD fit on the same subspaces.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -454,6 +460,207 @@ def run_ecod(d, n, count, reps, baselines=True, random_masks=False):
     return row
 
 
+def torch_histograms(Z, B):
+    """(edges [P, B + 1], counts [P, B]) of the columns of the float64 matrix Z [n, P], in torch on the device."""
+    lo, hi = Z.min(dim=0).values, Z.max(dim=0).values
+    same = lo == hi
+    lo, hi = torch.where(same, lo - 0.5, lo), torch.where(same, hi + 0.5, hi)
+    step = (hi - lo) / B
+    edges = torch.arange(B + 1, dtype=torch.float64, device=Z.device)[None, :] * step[:, None] + lo[:, None]
+    edges[:, B] = hi
+    bins = torch.searchsorted(edges[:, 1:B].contiguous(), Z.t().contiguous(), right=True)
+    counts = torch.zeros(Z.shape[1], B, dtype=torch.int64, device=Z.device).scatter_add_(1, bins, torch.ones_like(bins))
+    return edges, counts
+
+
+def torch_hbos(X, mask64, B, alpha, tol):
+    """float32 [S, n]: the float64 torch restatement of the HBOS fit on the GPU."""
+    Z = (X + 0.0).double()
+    n = Z.shape[0]
+    edges, counts = torch_histograms(Z, B)
+    step = (edges[:, B] - edges[:, 0]) / B
+    dens = counts.double() / (n * step)[:, None]
+    term = -torch.log2(dens + alpha)
+    rare = -torch.log2(dens.min(dim=1).values + alpha)
+    bins = torch.searchsorted(edges[:, 1:B].contiguous(), Z.t().contiguous(), right=True)
+    T = torch.gather(term, 1, bins)
+    outside = (Z.t() < (edges[:, 0] - tol * step)[:, None]) | (Z.t() > (edges[:, B] + tol * step)[:, None])
+    T = torch.where(outside, rare[:, None], T)
+    return (mask64.t() @ T).float().contiguous()
+
+
+def numpy_hbos(X, m, p, B, alpha, tol):
+    """numpy on the host: numpy.histogram and searchsorted per feature, then one masked sum per subspace; float64 [n]."""
+    A = X.astype(np.float64) + 0.0
+    n, d = A.shape
+    T = np.empty_like(A)
+    for f in range(d):
+        counts, edges = np.histogram(A[:, f], bins=B)
+        step = (edges[-1] - edges[0]) / B
+        dens = counts / (n * step)
+        T[:, f] = -np.log2(dens + alpha)[np.searchsorted(edges[1:B], A[:, f], side="right")]  # the fitted rows are never outside
+    out = np.zeros(n)
+    for s in range(len(m)):
+        out += p[s] * T[:, np.flatnonzero(m[s])].sum(axis=1).astype(np.float32).astype(np.float64)
+    return out
+
+
+def hist_row_head(method, d, n, count, S, dims, ens, Xd, reps):
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    return {"method": method, "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_bins": ens.n_bins,
+            "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+            "fit_s": round(t_fit, 6), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td}
+
+
+def ecod_beside(row, m, p, Xd, reps):
+    ecod = vgan_amd.SubspaceECOD(m, p)
+    t_ecod, te = timed(lambda: ecod.fit(Xd), reps)
+    row.update({"ecod_fit_s": round(t_ecod, 6), "ecod_fit_reps_s": te, "ecod_over_fit": round(t_ecod / row["fit_s"], 2)})
+
+
+def run_hbos(d, n, count, reps, baselines=True):
+    from vgan_amd.outlier import hbos_chunk_rows, hbos_term_table
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceHBOS(m, p)
+    row = hist_row_head("hbos", d, n, count, S, dims, ens, Xd, reps)
+    ops, dev, inner, B = ens.ops, Xd.device, max(reps, 5), ens.n_bins
+    rows = min(hbos_chunk_rows(d, S, ens.workspace_bytes), n)
+    keys = torch.empty(d, 2, dtype=torch.int64, device=dev)
+    edges, counts = torch.empty_like(ens._edges), torch.empty(d, B, dtype=torch.int32, device=dev)
+    terms = torch.empty(rows * d, dtype=torch.float64, device=dev)
+    per = torch.empty(S, n, dtype=torch.float32, device=dev)
+    one = torch.ones(d, 1, dtype=torch.float64, device=dev)
+    per_one = torch.empty(1, n, dtype=torch.float32, device=dev)
+    t_range, _ = timed(lambda: ops.hist_column_range(Xd, keys), inner)
+    t_edges, _ = timed(lambda: ops.hist_edges(keys, B, edges), inner)
+    t_count, _ = timed(lambda: ops.hist_column_counts(Xd, edges, counts), inner)
+    t_scores, _ = timed(lambda: ops.hbos_scores(Xd[:rows], ens._edges, ens._terms, ens._limits, ens._mask, terms, per[:, :rows]), inner)
+    t_lookup, _ = timed(lambda: ops.hbos_scores(Xd[:rows], ens._edges, ens._terms, ens._limits, one, terms, per_one[:, :rows]), inner)
+    t0 = time.perf_counter()
+    hbos_term_table(counts.cpu().numpy(), edges.cpu().numpy(), n, ens.alpha, ens.tol)
+    t_host = time.perf_counter() - t0
+    scale = n / rows  # the split of scoring is taken on the first chunk and scaled by the number of rows
+    t_product = max(t_scores - t_lookup, 0.0)
+    row.update({"row_chunks": -(-n // rows), "range_s": round(t_range, 6), "edges_s": round(t_edges, 6), "count_s": round(t_count, 6),
+                "count_copy_and_host_table_s": round(t_host, 6), "lookup_and_product_s": round(t_scores * scale, 6),
+                "lookup_alone_s": round(t_lookup * scale, 6), "product_s": round(t_product * scale, 6),
+                "range_gb_s": round(4.0 * n * d / t_range / 1e9, 1), "count_gb_s": round(4.0 * n * d / t_count / 1e9, 1),
+                "product_fp64_gflops": round(2.0 * rows * d * S / max(t_product, 1e-9) / 1e9, 1)})
+    ecod_beside(row, m, p, Xd, reps)
+    if baselines:
+        t_torch, tt = timed(lambda: torch_hbos(Xd, ens._mask, B, ens.alpha, ens.tol), reps)
+        want = torch_hbos(Xd, ens._mask, B, ens.alpha, ens.tol).double()
+        got = torch.as_tensor(ens.per_subspace_scores_, device=dev).double()
+        t0 = time.perf_counter()
+        host = numpy_hbos(X, m, p, B, ens.alpha, ens.tol)
+        t_np = time.perf_counter() - t0
+        row.update({"torch_fit_s": round(t_torch, 6), "torch_fit_reps_s": tt, "fit_speedup_vs_torch": round(t_torch / row["fit_s"], 2),
+                    "max_abs_diff_vs_torch": float((got - want).abs().max()), "numpy_host_fit_s": round(t_np, 4),
+                    "fit_speedup_vs_numpy": round(t_np / row["fit_s"], 1),
+                    "max_abs_diff_vs_numpy": float(np.max(np.abs(ens.decision_scores_ - host)))})
+    return row
+
+
+def torch_loda(X, feats, features, weights, B):
+    """float32 [S, n]: a float64 torch restatement of the LODA fit on the GPU, subspace by subspace (a dense projection
+    matrix and one matmul: its z differ from the contract's in the last bits, so a value may change its bin)."""
+    n = X.shape[0]
+    out = torch.empty(len(feats), n, dtype=torch.float32, device=X.device)
+    for s, f in enumerate(feats):
+        k, d_s = features[s].shape[0], len(f)
+        W = np.zeros((d_s, k))
+        W[features[s], np.arange(k)[:, None]] = weights[s]
+        Z = X[:, torch.as_tensor(f, device=X.device)].double() @ torch.as_tensor(W, device=X.device)
+        edges, counts = torch_histograms(Z, B)
+        term = -torch.log((counts.double() + 1e-12) / (n + B * 1e-12))
+        bins = torch.searchsorted(edges[:, 1:B].contiguous(), Z.t().contiguous(), right=True)
+        out[s] = torch.gather(term, 1, bins).mean(dim=0).float()
+    return out
+
+
+def numpy_loda_one(Xs, features, weights, B):
+    n, k = Xs.shape[0], features.shape[0]
+    W = np.zeros((Xs.shape[1], k))
+    W[features, np.arange(k)[:, None]] = weights
+    Z = Xs.astype(np.float64) @ W
+    total = np.zeros(n)
+    for j in range(k):
+        counts, edges = np.histogram(Z[:, j], bins=B)
+        total += -np.log((counts + 1e-12) / (n + B * 1e-12))[np.searchsorted(edges[1:B], Z[:, j], side="right")]
+    return total / k
+
+
+def run_loda(d, n, count, reps, baselines=True, numpy_sample=8):
+    from vgan_amd.outlier import loda_chunks, loda_projections, loda_term_table
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceLODA(m, p)
+    row = hist_row_head("loda", d, n, count, S, dims, ens, Xd, reps)
+    ops, dev, inner = ens.ops, Xd.device, max(reps, 5)
+    k, B = ens.n_projections, ens.n_bins
+    rows, ranges = loda_chunks(ens.plan.dims, n, ens.workspace_bytes)
+    keys = torch.empty(S, k, 2, dtype=torch.int64, device=dev)
+    counts = torch.empty(S, k, B, dtype=torch.int32, device=dev)
+    per = torch.empty(S, n, dtype=torch.float32, device=dev)
+
+    def pack_pass():
+        for _ in ens._blocks(Xd):
+            pass
+
+    def range_pass():
+        ops.hist_reset(keys=keys)
+        for packed, r, _, first, cnt, width in ens._blocks(Xd):
+            ops.loda_range(packed, r, ens._table, first, cnt, width, ens._proj, keys)
+
+    def count_pass():
+        ops.hist_reset(counts=counts)
+        for packed, r, _, first, cnt, width in ens._blocks(Xd):
+            ops.loda_counts(packed, r, ens._table, first, cnt, width, ens._proj, ens._edges, counts)
+
+    def score_pass():
+        for packed, r, r0, first, cnt, width in ens._blocks(Xd):
+            ops.loda_scores(packed, r, ens._table, first, cnt, width, ens._proj, ens._edges, ens._terms, per[:, r0:r0 + r])
+
+    t0 = time.perf_counter()
+    loda_projections(ens.plan.dims, k, ens.seed)
+    t_draw = time.perf_counter() - t0
+    t_pack, _ = timed(pack_pass, inner)
+    t_range, _ = timed(range_pass, inner)
+    t_count, _ = timed(count_pass, inner)
+    t_score, _ = timed(score_pass, inner)
+    t0 = time.perf_counter()
+    loda_term_table(counts.cpu().numpy(), n)
+    t_host = time.perf_counter() - t0
+    nonzeros = float(sum(f.size for f in ens.projection_features_))  # sum_s k m_s
+    row.update({"n_projections": k, "row_chunks": -(-n // rows), "subspace_ranges": len(ranges), "draw_projections_host_s": round(t_draw, 4),
+                "pack_pass_s": round(t_pack, 6), "range_pass_s": round(t_range, 6), "count_pass_s": round(t_count, 6),
+                "score_pass_s": round(t_score, 6), "count_copy_and_host_table_s": round(t_host, 6),
+                "projection_fp64_gflops_of_score_pass": round(2.0 * n * nonzeros / max(t_score - t_pack, 1e-9) / 1e9, 1)})
+    ecod_beside(row, m, p, Xd, reps)
+    if baselines:
+        feats = [np.flatnonzero(m[s]) for s in range(S)]
+        args = (Xd, feats, ens.projection_features_, ens.projection_weights_, B)
+        t_torch, tt = timed(lambda: torch_loda(*args), reps)
+        want = torch_loda(*args).double()
+        got = torch.as_tensor(ens.per_subspace_scores_, device=dev).double()
+        pick = np.unique(np.linspace(0, S - 1, min(S, numpy_sample)).astype(int))
+        t0 = time.perf_counter()
+        diff = 0.0
+        for s in pick:
+            host = numpy_loda_one(X[:, feats[s]], ens.projection_features_[s], ens.projection_weights_[s], B)
+            diff = max(diff, float(np.abs(host - ens.per_subspace_scores_[s]).mean()))
+        t_np = (time.perf_counter() - t0) * S / len(pick)
+        row.update({"torch_fit_s": round(t_torch, 6), "torch_fit_reps_s": tt, "fit_speedup_vs_torch": round(t_torch / row["fit_s"], 2),
+                    "mean_abs_diff_vs_torch": float((got - want).abs().mean()), "numpy_host_fit_s": round(t_np, 4),
+                    "numpy_subspaces_timed": int(len(pick)), "fit_speedup_vs_numpy": round(t_np / row["fit_s"], 1),
+                    "mean_abs_diff_vs_numpy_max": diff})
+    return row
+
+
 def run_iforest(d, n, count, reps, baselines=True, sklearn_sample=8):
     X, m, p = subspaces_for(d, n, count, seed=d + n + count)
     Xd = torch.as_tensor(X, device="cuda")
@@ -734,13 +941,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm / hbos / loda: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm / hbos / loda: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -790,6 +997,15 @@ def main():
             grid = [(10, 2000, 64), (784, 2000, 64)] if args.quick else [(10, 50_000, 64), (10, 50_000, 512), (784, 50_000, 64),
                                                                          (784, 50_000, 512)]
             out["product_vs_gather"] = [run_ecod(d, n, S, args.reps, baselines=False, random_masks=True) for d, n, S in grid]
+        configs = []
+    if args.method in ("hbos", "loda"):
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append((run_hbos if args.method == "hbos" else run_loda)(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "iforest":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),

@@ -146,6 +146,14 @@ SIGNATURES = {
     "vgan_ecod_skew_sign": (_i, [_p, _i64, _i, _i, _p, _p]),
     "vgan_ecod_tail_counts": (_i, [_p, _i, _i, _i, _p, _i64, _i, _p, _p, _p]),
     "vgan_ecod_scores": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p, _p, _i64, _p]),
+    "vgan_hist_column_range": (_i, [_p, _i, _i, _i, _p, _p]),
+    "vgan_hist_edges": (_i, [_p, _i64, _i, _p, _p]),
+    "vgan_hist_column_counts": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
+    "vgan_hbos_scores": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p, _i, _i, _p, _p, _i64, _p]),
+    "vgan_hist_reset": (_i, [_p, _i64, _p, _i64, _p]),
+    "vgan_loda_range": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
+    "vgan_loda_counts": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p]),
+    "vgan_loda_scores": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _p]),
     "vgan_iforest_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p]),
     "vgan_iforest_path_sums": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, _p]),
     "vgan_iforest_scores": (_i, [_p, _i64, _i, _i, _i64, _p, _i64, _p]),

@@ -853,6 +853,91 @@ class HipOps:
                                              _ptr(mask), S, S, _ptr(terms), _ptr(score), score.stride(0), self._stream()),
                    "vgan_ecod_scores")
 
+    # ---- histogram scores over subspaces (vgan_amd.outlier.SubspaceHBOS / SubspaceLODA) ----------------------
+    # keys: int64 [P, 2] holding the library's uint64 order-preserving keys of a column's minimum and maximum
+    def hist_column_range(self, X, keys):
+        """keys [d, 2]: the keys of the minimum and maximum of every column of X [n, d] (set first: nothing is merged)."""
+        _mat(X, "X"), _vec(keys, "keys", torch.int64)
+        n, d = X.shape
+        assert keys.numel() >= 2 * d
+        _lib.check(self.lib.vgan_hist_column_range(_ptr(X), X.stride(0), n, d, _ptr(keys), self._stream()), "vgan_hist_column_range")
+
+    def hist_edges(self, keys, n_bins, edges):
+        """edges float64 [P, n_bins + 1] = numpy.linspace(lo, hi, n_bins + 1) of every column's range (lo == hi: +-0.5)."""
+        _vec(keys, "keys", torch.int64), _vec(edges, "edges", torch.float64)
+        P = edges.numel() // (int(n_bins) + 1)
+        assert edges.numel() == P * (int(n_bins) + 1) and keys.numel() >= 2 * P
+        _lib.check(self.lib.vgan_hist_edges(_ptr(keys), P, int(n_bins), _ptr(edges), self._stream()), "vgan_hist_edges")
+
+    def hist_column_counts(self, X, edges, counts):
+        """counts int32 [d, B] (zeroed first): how many values of every column of X [n, d] fall into each bin of edges
+        float64 [d, B + 1]."""
+        _mat(X, "X"), _vec(edges, "edges", torch.float64), _vec(counts, "counts", torch.int32)
+        n, d = X.shape
+        B = edges.shape[-1] - 1
+        assert edges.numel() == d * (B + 1) and counts.numel() >= d * B
+        _lib.check(self.lib.vgan_hist_column_counts(_ptr(X), X.stride(0), n, d, _ptr(edges), B, _ptr(counts), self._stream()),
+                   "vgan_hist_column_counts")
+
+    def hbos_scores(self, Xq, edges, table, limits, mask, terms, score):
+        """score float32 [S, rows] (a view into the score matrix may be given) of the rows of Xq: the masked sums of the
+        looked-up terms; table float64 [d, B + 1], limits float64 [d, 2], mask float64 [d, S]; terms: float64 workspace of
+        rows * d elements."""
+        _mat(Xq, "Xq"), _mat(score, "score")
+        for name, t in (("edges", edges), ("table", table), ("limits", limits), ("mask", mask), ("terms", terms)):
+            _vec(t, name, torch.float64)
+        rows, d = Xq.shape
+        B = edges.shape[-1] - 1
+        S = mask.shape[1]
+        assert edges.numel() == d * (B + 1) and table.numel() == d * (B + 1) and limits.numel() == 2 * d and mask.shape[0] == d
+        assert terms.numel() >= rows * d and score.shape[0] == S and score.shape[1] >= rows
+        _lib.check(self.lib.vgan_hbos_scores(_ptr(Xq), Xq.stride(0), rows, d, _ptr(edges), B, _ptr(table), _ptr(limits), _ptr(mask), S, S,
+                                             _ptr(terms), _ptr(score), score.stride(0), self._stream()), "vgan_hbos_scores")
+
+    def hist_reset(self, keys=None, counts=None):
+        """keys to (above every key, below every key) and counts to 0, before the LODA calls that merge into them."""
+        if keys is not None:
+            _vec(keys, "keys", torch.int64)
+        if counts is not None:
+            _vec(counts, "counts", torch.int32)
+        _lib.check(self.lib.vgan_hist_reset(_ptr(keys), 0 if keys is None else keys.numel() // 2, _ptr(counts),
+                                            0 if counts is None else counts.numel(), self._stream()), "vgan_hist_reset")
+
+    # packed: the packed block (outlier_pack, not centred) of `rows` rows for the subspaces first .. first + count - 1;
+    # proj: (pidx int32, pw float64, moff int64 [S + 1], k): the projections' nonzeros, t-major per subspace
+    def loda_range(self, packed, rows, table, first, count, max_dims, proj, keys):
+        """Merges the keys of the projected values of the block's rows into keys [S, k, 2]."""
+        _vec(packed, "packed"), _vec(keys, "keys", torch.int64)
+        _, feat_off, col_off = table
+        pidx, pw, moff, k = proj
+        assert keys.numel() >= 2 * (first + count) * k
+        _lib.check(self.lib.vgan_loda_range(_ptr(packed), int(rows), _ptr(feat_off), _ptr(col_off), int(first), int(count), int(max_dims),
+                                            _ptr(pidx), _ptr(pw), _ptr(moff), int(k), _ptr(keys), self._stream()), "vgan_loda_range")
+
+    def loda_counts(self, packed, rows, table, first, count, max_dims, proj, edges, counts):
+        """Adds the bins of the projected values of the block's rows to counts int32 [S, k, B]; edges float64 [S, k, B + 1]."""
+        _vec(packed, "packed"), _vec(edges, "edges", torch.float64), _vec(counts, "counts", torch.int32)
+        _, feat_off, col_off = table
+        pidx, pw, moff, k = proj
+        B = edges.shape[-1] - 1
+        assert edges.numel() >= (first + count) * k * (B + 1) and counts.numel() >= (first + count) * k * B
+        _lib.check(self.lib.vgan_loda_counts(_ptr(packed), int(rows), _ptr(feat_off), _ptr(col_off), int(first), int(count), int(max_dims),
+                                             _ptr(pidx), _ptr(pw), _ptr(moff), int(k), _ptr(edges), B, _ptr(counts), self._stream()),
+                   "vgan_loda_counts")
+
+    def loda_scores(self, packed, rows, table, first, count, max_dims, proj, edges, terms, score):
+        """score float32 [S, rows] (a view into the score matrix, all S rows of it): rows first .. first + count - 1 receive
+        the mean of terms float64 [S, k, B] at the bins of the projected values."""
+        _vec(packed, "packed"), _vec(edges, "edges", torch.float64), _vec(terms, "terms", torch.float64), _mat(score, "score")
+        _, feat_off, col_off = table
+        pidx, pw, moff, k = proj
+        B = edges.shape[-1] - 1
+        assert edges.numel() >= (first + count) * k * (B + 1) and terms.numel() >= (first + count) * k * B
+        assert score.shape[0] >= first + count and score.shape[1] >= rows
+        _lib.check(self.lib.vgan_loda_scores(_ptr(packed), int(rows), _ptr(feat_off), _ptr(col_off), int(first), int(count), int(max_dims),
+                                             _ptr(pidx), _ptr(pw), _ptr(moff), int(k), _ptr(edges), B, _ptr(terms), _ptr(score),
+                                             score.stride(0), self._stream()), "vgan_loda_scores")
+
     # ---- isolation forest over subspaces (vgan_amd.outlier.SubspaceIForest) ---------------------------------
     def iforest_build(self, X, table, first, count, max_dims, psi, depth, seed, nodes):
         """nodes int32 [S, T, N, 2] (N = 2^(depth + 1)) receives the T trees of the subspaces first .. first + count - 1,

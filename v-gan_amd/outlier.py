@@ -62,6 +62,12 @@ subspace on the device, and the negative log-likelihood as the score (csrc/outli
 csrc/outlier_maha.hip on the (subspace, component) pairs and the k-means start of csrc/cluster.hip); n C d_s^2 per
 iteration.  Its contract (the start, the M and E steps, the loop, freezing, failures, determinism) is that class's docstring.
 
+``SubspaceHBOS`` and ``SubspaceLODA`` are the histogram detectors, linear in n: equal-width histograms (numpy.linspace's
+edges, numpy.histogram's counts, exact integer sums) of every feature (HBOS: -log2 densities summed over a subspace's
+features, the dense float64 product of ``SubspaceECOD``) or of sparse random projections of every subspace (LODA: the mean
+-log bin probability; the projected values are never stored) (csrc/outlier_hist.hip).  Their contracts (range, edges,
+bins, the out-of-range rule, the host draw of the projections and its rounding) are those classes' docstrings.
+
 The classes differ in their scores only.  The constructor tail, the first touch of the device (at the first ``fit``,
 never in a constructor), the head and the tail of ``fit``, ``decision_function`` and the tail above (normalize,
 combination, contamination, predict) are ``_SubspaceScorer``; the neighbour search and its chunk loop are
@@ -1019,6 +1025,288 @@ class SubspaceECOD(_SubspaceScorer):
         self._mask = torch.as_tensor(mask, device=X.device)
         scores, per = self._score(X, fitting=True)
         self.skew_sign_ = self._sign.cpu().numpy().astype(np.int64)
+        return self._publish(scores, per)
+
+
+# ---- histogram scores: HBOS and LODA over the subspaces ------------------------------------------------------------------
+HIST_MAX_BINS = 256  # VGAN_HIST_MAX_BINS: the bin search runs eight halvings
+HIST_MAX_ROWS = 1 << 24  # VGAN_HIST_MAX_ROWS: the counts stay in int32
+LODA_MAX_PROJECTIONS = 1024  # VGAN_LODA_MAX_PROJECTIONS: the (min, max) pairs of a subspace's projections live in LDS
+LODA_MAX_DIMS = 8192  # VGAN_LODA_MAX_DIMS: packed features of one subspace (a row of it is staged in LDS)
+_LODA_MAX_RANGE = 65535  # subspaces of one launch (a grid dimension)
+_LODA_FLOOR = 1e-12  # what LODA adds to every count before the logarithm
+
+
+def check_bins(n_bins):
+    if not (_is_int(n_bins) and 2 <= int(n_bins) <= HIST_MAX_BINS):
+        raise ValueError(f"n_bins must be an integer between 2 and {HIST_MAX_BINS}, got {n_bins!r}")
+    return int(n_bins)
+
+
+def check_hbos_params(alpha, tol):
+    if not (_is_real(alpha) and np.isfinite(alpha) and alpha > 0):
+        raise ValueError(f"alpha must be a positive number, got {alpha!r}")
+    if not (_is_real(tol) and np.isfinite(tol) and tol >= 0):
+        raise ValueError(f"tol must be a non-negative number, got {tol!r}")
+    return float(alpha), float(tol)
+
+
+def check_projections(n_projections):
+    if not (_is_int(n_projections) and 1 <= int(n_projections) <= LODA_MAX_PROJECTIONS):
+        raise ValueError(f"n_projections must be an integer between 1 and {LODA_MAX_PROJECTIONS}, got {n_projections!r}")
+    return int(n_projections)
+
+
+def hbos_chunk_rows(d, n_subspaces, workspace_bytes):
+    """Rows of one HBOS scoring chunk: the float64 terms [rows, d] and the chunk's float32 scores [S, rows] fit in
+    workspace_bytes; at least one row."""
+    return max(1, int(workspace_bytes) // (8 * int(d) + 4 * int(n_subspaces)))
+
+
+def hbos_term_table(counts, edges, n, alpha, tol):
+    """(table float64 [d, B + 1], limits float64 [d, 2]) from the counts [d, B] and edges [d, B + 1] of n fitted rows: step =
+    (e_B - e_0) / B, dens[b] = count_b / (n step), table[:, b] = -log2(dens[b] + alpha) for b < B and table[:, B] = -log2(min_b
+    dens[b] + alpha), the term of a value outside the limits (e_0 - tol step, e_B + tol step)."""
+    counts, edges = np.asarray(counts, dtype=np.float64), np.asarray(edges, dtype=np.float64)
+    B = counts.shape[-1]
+    lo, hi = edges[..., 0], edges[..., -1]
+    step = (hi - lo) / B
+    dens = counts / (float(n) * step)[..., None]
+    table = np.concatenate([-np.log2(dens + alpha), -np.log2(dens.min(axis=-1) + alpha)[..., None]], axis=-1)
+    return table, np.stack([lo - tol * step, hi + tol * step], axis=-1)
+
+
+def loda_term_table(counts, n):
+    """float64 [..., B]: -log(p[b]) with p[b] = (count_b + 1e-12) / (n + B 1e-12), from the counts [..., B] of n fitted rows."""
+    counts = np.asarray(counts, dtype=np.float64)
+    return -np.log((counts + _LODA_FLOOR) / (float(n) + counts.shape[-1] * _LODA_FLOOR))
+
+
+def loda_projections(dims, n_projections, seed):
+    """(features, weights): per subspace of d_s = dims[s] features an int64 [k, m_s] array of positions within the subspace
+    (ascending, distinct) and a float64 [k, m_s] array of weights, m_s = max(1, floor(sqrt(d_s))), drawn from rng =
+    numpy.random.default_rng(seed) subspace by subspace and j = 0 .. k - 1: sort(rng.choice(d_s, m_s, replace=False)), then
+    rng.standard_normal(m_s)."""
+    rng = np.random.default_rng(seed)
+    k = int(n_projections)
+    features, weights = [], []
+    for d_s in np.asarray(dims, dtype=np.int64).reshape(-1):
+        m = max(1, math.isqrt(int(d_s)))
+        f, w = np.empty((k, m), dtype=np.int64), np.empty((k, m), dtype=np.float64)
+        for j in range(k):
+            f[j] = np.sort(rng.choice(int(d_s), m, replace=False))
+            w[j] = rng.standard_normal(m)
+        features.append(f)
+        weights.append(w)
+    return features, weights
+
+
+def loda_chunks(dims, n, workspace_bytes):
+    """(rows of a row chunk, [(first, count)] subspace ranges): the transient buffer of a LODA launch is the packed block of
+    its rows and subspaces, float32 [rows, round4(d_s)] per subspace.  All subspaces form one range and the rows are chunked
+    while a row of every subspace fits: rows = min(n, workspace_bytes // (4 sum_s round4(d_s))); below that the chunks are
+    single rows and a range takes consecutive subspaces while their rows fit (at least one; never more than 65535)."""
+    widths = _round4(np.asarray(dims).reshape(-1))
+    limit = int(workspace_bytes)
+    rows = int(min(int(n), max(1, limit // (4 * int(widths.sum())))))
+    ranges, first = [], 0
+    while first < len(widths):
+        end, used = first, 0
+        while end < len(widths) and end - first < _LODA_MAX_RANGE:
+            need = rows * int(widths[end]) * 4
+            if end > first and used + need > limit:
+                break
+            used += need
+            end += 1
+        ranges.append((first, end - first))
+        first = end
+    return rows, ranges
+
+
+class SubspaceHBOS(_SubspaceScorer):
+    """Histogram-based outlier score per subspace (HBOS: Goldstein and Dengel 2012; pyod's ``HBOS`` with a fixed number of
+    bins), combined like the other detectors of this module: ``fit`` sets ``decision_scores_``, ``decision_function`` scores
+    new rows; higher is more outlying.  Linear in n: no neighbour search, no sort, nothing n x n.
+
+    X is cast to float32; all arithmetic is float64 on those values, and -0.0 counts as +0.0.  n is the number of rows
+    given to ``fit``, 1 <= n <= HIST_MAX_ROWS (2^24); B = n_bins, an integer from 2 to 256 (pyod's "auto" is not built);
+    alpha > 0; tol >= 0.
+
+    The histogram of a column of n values: lo, hi its minimum and maximum (lo == hi: lo - 0.5, lo + 0.5, numpy's rule); step
+    = (hi - lo) / B; edges e_j = j * step + lo for j = 0 .. B with two roundings (the product, then the sum) and e_B = hi:
+    ``numpy.linspace(lo, hi, B + 1)`` bit for bit.  The bin of a value x is #{j in 1 .. B - 1 : e_j <= x}: the bin
+    ``numpy.histogram(col, bins=B)`` counts x in; a value outside [lo, hi] falls into the first or the last bin.  count_b is
+    the number of fitted values in bin b.
+
+    Every feature f gets one histogram of its fitted column: dens_f[b] = count_b / (n step_f), term_f[b] = -log2(dens_f[b] +
+    alpha).  A scored value x of feature f takes term_f[bin(x)], except where x < lo_f - tol step_f or x > hi_f + tol step_f:
+    there it takes -log2(min_b dens_f[b] + alpha).  The score of a row in subspace s is the sum of its terms over the
+    features of s, rounded to float32 into the [S, n] score matrix; scores may be negative.  ``fit`` excludes nothing, so
+    ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.
+
+    ``fit`` publishes ``bin_edges_`` (float64 [d, B + 1]) and ``histograms_`` (int64 [d, B]); normalize, combination,
+    contamination, ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.
+
+    These rules are pyod's as its source is remembered here; pyod was not at hand to pin them, so the definition above and
+    its numpy restatement in tests/test_outlier_hist_cpu.py (edges pinned to numpy.linspace, counts to numpy.histogram) are
+    what binds, not pyod.
+
+    The terms do not depend on the subspace: the term tables are built on the host in float64 from the integer counts
+    (hbos_term_table) and uploaded; per row chunk the terms are looked up and every subspace is a 0/1-masked sum of them,
+    the dense float64 product on the matrix unit that SubspaceECOD runs.  workspace_bytes limits the terms and scores of a
+    row chunk (hbos_chunk_rows).  Counts are integer sums and the bits of a score depend on the row alone: scores and
+    published arrays are bit-identical for every workspace_bytes, from run to run and for a subspace fitted alone or with
+    others.  NaN or infinite input leaves the scores unspecified and neither faults nor hangs.  All of it runs in
+    libvgan_hip.so (csrc/outlier_hist.hip)."""
+
+    def __init__(self, subspaces, proba, n_bins=10, alpha=0.1, tol=0.5, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None,
+                 combination="sum", contamination=0.1):
+        self.n_bins = check_bins(n_bins)
+        self.alpha, self.tol = check_hbos_params(alpha, tol)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+
+    def _check_fit_rows(self, n):
+        if not 1 <= n <= HIST_MAX_ROWS:
+            raise ValueError(f"SubspaceHBOS fit needs between 1 and {HIST_MAX_ROWS} rows, got {n}")
+
+    def _score(self, X, fitting):
+        nq, d = X.shape
+        S, dev = self.plan.count, X.device
+        rows = min(hbos_chunk_rows(d, S, self.workspace_bytes), nq)
+        terms = torch.empty(rows * d, dtype=torch.float64, device=dev)
+        per = torch.empty(S, nq, dtype=torch.float32, device=dev)
+        for r0 in range(0, nq, rows):
+            r1 = min(r0 + rows, nq)
+            self.ops.hbos_scores(X[r0:r1], self._edges, self._terms, self._limits, self._mask, terms, per[:, r0:r1])
+        return self._combine(per, fitting), per
+
+    def fit(self, X, y=None):
+        """One histogram per column of X (range, edges, integer counts on the device; the term table on the host), then
+        scores X itself: decision_scores_ (float64 [n]), per_subspace_scores_, bin_edges_, histograms_; with normalize also
+        score_center_ / score_scale_.  The edges and the term table are the fitted state: X itself is not kept."""
+        X = self._begin_fit(X)
+        n, d = X.shape
+        B, dev = self.n_bins, X.device
+        keys = torch.empty(d, 2, dtype=torch.int64, device=dev)
+        self.ops.hist_column_range(X, keys)
+        self._edges = torch.empty(d, B + 1, dtype=torch.float64, device=dev)
+        self.ops.hist_edges(keys, B, self._edges)
+        counts = torch.empty(d, B, dtype=torch.int32, device=dev)
+        self.ops.hist_column_counts(X, self._edges, counts)
+        self.bin_edges_ = self._edges.cpu().numpy()
+        self.histograms_ = counts.cpu().numpy().astype(np.int64)
+        table, limits = hbos_term_table(self.histograms_, self.bin_edges_, n, self.alpha, self.tol)
+        self._terms, self._limits = torch.as_tensor(table, device=dev), torch.as_tensor(limits, device=dev)
+        mask = np.zeros((d, self.plan.count), dtype=np.float64)  # column = given subspace index
+        for z, s in enumerate(self.plan.order):
+            mask[self.plan.feat[self.plan.feat_off[z]:self.plan.feat_off[z + 1]], s] = 1.0
+        self._mask = torch.as_tensor(mask, device=dev)
+        scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)
+
+
+class SubspaceLODA(_SubspaceScorer):
+    """Lightweight on-line detector of anomalies per subspace (LODA: Pevny 2016; pyod's ``LODA`` with a fixed number of
+    bins), combined like the other detectors of this module: ``fit`` sets ``decision_scores_``, ``decision_function`` scores
+    new rows; higher is more outlying.  Linear in n.  A projection restricted to a subspace's features is the detector's own
+    idea, sparse projections as feature bagging, with the subspaces choosing the bag.
+
+    X is cast to float32; all arithmetic is float64 on those values.  n is the number of rows given to ``fit``, 1 <= n <=
+    HIST_MAX_ROWS (2^24); k = n_projections, 1 .. 1024; B = n_bins, an integer from 2 to 256 (pyod's "auto" is not built);
+    seed a non-negative integer; a subspace has at most LODA_MAX_DIMS (8192) features.
+
+    Subspace s has d_s features and m_s = max(1, floor(sqrt(d_s))) nonzeros per projection.  The projections are drawn on
+    the host, once, by loda_projections(dims, k, seed): rng = numpy.random.default_rng(seed); over the subspaces in the
+    given order and j = 0 .. k - 1: idx = sort(rng.choice(d_s, m_s, replace=False)), then w = rng.standard_normal(m_s).
+    ``fit`` publishes them as ``projection_features_`` (a list of S int arrays [k, m_s], positions within the subspace) and
+    ``projection_weights_`` (S float64 arrays [k, m_s]).  The projected value of a row is z = (((0 + w_0 x_{f_0}) + w_1
+    x_{f_1}) + ...), the nonzeros in ascending feature order, every product and every sum rounded on its own: in numpy,
+    acc = acc + w[t] * x[:, f_t].
+
+    Projection (s, j) gets one histogram of the n fitted z values, by the rules of SubspaceHBOS: lo, hi the minimum and
+    maximum (lo == hi: lo - 0.5, lo + 0.5); step = (hi - lo) / B; e_j = j * step + lo in two roundings, e_B = hi
+    (numpy.linspace bit for bit); the bin of z is #{j in 1 .. B - 1 : e_j <= z} (numpy.histogram's bin; outside [lo, hi]
+    the first or last bin).  p[b] = (count_b + 1e-12) / (n + B 1e-12).  The score of a row in subspace s is (1 / k) sum_j
+    -log(p_{s,j}[bin(z_{s,j})]), rounded to float32 into the [S, n] score matrix; it is never negative.  ``fit`` excludes
+    nothing, so ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.
+
+    ``fit`` publishes ``bin_edges_`` (float64 [S, k, B + 1]) and ``histograms_`` (int64 [S, k, B]); normalize, combination,
+    contamination, ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.
+
+    These rules are pyod's as its source is remembered here and are not pinned against pyod; its ``limits[:n_bins - 1]``
+    lookup looks like an off-by-one and is deliberately not reproduced.  The definition above and its numpy restatement in
+    tests/test_outlier_hist_cpu.py are what binds.
+
+    Nothing n x S x k is stored: z is recomputed by the range, the count and the scoring pass.  workspace_bytes limits the
+    packed block of a launch (loda_chunks: a row chunk and a range of subspaces).  Minima, maxima and counts are integer
+    atomics, the log-probability tables are built on the host in float64 (loda_term_table) and uploaded, and the sum over j
+    runs in an order fixed by k alone: scores and published arrays are bit-identical for every workspace_bytes, from run to
+    run and, given the same projections, for a subspace fitted alone or with others.  NaN or infinite input leaves the
+    scores unspecified and neither faults nor hangs.  All of it runs in libvgan_hip.so (csrc/outlier_hist.hip)."""
+
+    _proj = None  # (pidx, pw, moff, k) on the device, set by the first fit
+
+    def __init__(self, subspaces, proba, n_projections=100, n_bins=10, seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
+                 normalize=None, combination="sum", contamination=0.1):
+        self.n_projections = check_projections(n_projections)
+        self.n_bins = check_bins(n_bins)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > LODA_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceLODA takes at most {LODA_MAX_DIMS}")
+
+    def _check_fit_rows(self, n):
+        if not 1 <= n <= HIST_MAX_ROWS:
+            raise ValueError(f"SubspaceLODA fit needs between 1 and {HIST_MAX_ROWS} rows, got {n}")
+
+    def _blocks(self, X):
+        """Yields (packed block, rows, first row, first subspace, count, widest packed subspace) over the chunks of X."""
+        rows, ranges = loda_chunks(self.plan.dims, X.shape[0], self.workspace_bytes)
+        for first, count in ranges:
+            width = int(_round4(self.plan.dims[first:first + count]).max())
+            for r0 in range(0, X.shape[0], rows):
+                r1 = min(r0 + rows, X.shape[0])
+                yield self._pack(X[r0:r1], first, count, False)[0], r1 - r0, r0, first, count, width
+
+    def _score(self, X, fitting):
+        per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
+        for packed, rows, r0, first, count, width in self._blocks(X):
+            self.ops.loda_scores(packed, rows, self._table, first, count, width, self._proj, self._edges, self._terms, per[:, r0:r0 + rows])
+        return self._combine(per, fitting), per
+
+    def fit(self, X, y=None):
+        """Draws the projections on the host, takes the range and the integer counts of every projected column on the
+        device and the log-probability tables on the host, then scores X itself: decision_scores_ (float64 [n]),
+        per_subspace_scores_, projection_features_, projection_weights_, bin_edges_, histograms_; with normalize also
+        score_center_ / score_scale_.  The projections, edges and tables are the fitted state: X itself is not kept."""
+        X = self._begin_fit(X)
+        n, dev = X.shape[0], X.device
+        S, k, B = self.plan.count, self.n_projections, self.n_bins
+        if self._proj is None:  # they depend on the constructor's arguments alone: a second fit keeps them
+            features, weights = loda_projections(self.plan.dims, k, self.seed)
+            self.projection_features_, self.projection_weights_ = features, weights
+            moff = np.concatenate([[0], np.cumsum([f.shape[1] for f in features])]).astype(np.int64)
+            self._proj = (torch.as_tensor(np.concatenate([f.T.reshape(-1) for f in features]).astype(np.int32), device=dev),  # t-major
+                          torch.as_tensor(np.concatenate([w.T.reshape(-1) for w in weights]), device=dev),
+                          torch.as_tensor(moff, device=dev), k)
+        keys = torch.empty(S, k, 2, dtype=torch.int64, device=dev)
+        self.ops.hist_reset(keys=keys)
+        for packed, rows, _, first, count, width in self._blocks(X):
+            self.ops.loda_range(packed, rows, self._table, first, count, width, self._proj, keys)
+        self._edges = torch.empty(S, k, B + 1, dtype=torch.float64, device=dev)
+        self.ops.hist_edges(keys, B, self._edges)
+        counts = torch.empty(S, k, B, dtype=torch.int32, device=dev)
+        self.ops.hist_reset(counts=counts)
+        for packed, rows, _, first, count, width in self._blocks(X):
+            self.ops.loda_counts(packed, rows, self._table, first, count, width, self._proj, self._edges, counts)
+        self.bin_edges_ = self._edges.cpu().numpy()
+        self.histograms_ = counts.cpu().numpy().astype(np.int64)
+        self._terms = torch.as_tensor(loda_term_table(self.histograms_, n), device=dev)
+        scores, per = self._score(X, fitting=True)
         return self._publish(scores, per)
 
 

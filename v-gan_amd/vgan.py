@@ -14,7 +14,8 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceIForest, SubspaceMahalanobis
+from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
+                      SubspaceMahalanobis)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -198,7 +199,15 @@ class _RunFolder:
         method "gmm" builds a SubspaceGMM (a Gaussian mixture of n_components full covariances per subspace fitted by EM,
         scored by the negative log-likelihood; sklearn's GaussianMixture, pyod's GMM): its keywords are n_components,
         reg_covar, tol, max_iter, init, kmeans_max_iter, seed, workspace_bytes and the same normalize / combination /
-        contamination, e.g. outlier_ensemble(method="gmm", n_components=3, X=X); n_neighbors is not used there."""
+        contamination, e.g. outlier_ensemble(method="gmm", n_components=3, X=X); n_neighbors is not used there.
+        method "hbos" builds a SubspaceHBOS (one equal-width histogram per feature, the score the sum of -log2(density +
+        alpha) over the features of a subspace; pyod's HBOS): its keywords are n_bins, alpha, tol, workspace_bytes and the
+        same normalize / combination / contamination, e.g. outlier_ensemble(method="hbos", n_bins=10, X=X); n_neighbors is
+        not used there.
+        method "loda" builds a SubspaceLODA (sparse random projections of each subspace with a histogram on each, the
+        score the mean -log of the bin probabilities; pyod's LODA): its keywords are n_projections, n_bins, seed,
+        workspace_bytes and the same normalize / combination / contamination, e.g. outlier_ensemble(method="loda",
+        n_projections=100, X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -215,6 +224,10 @@ class _RunFolder:
             ens = SubspaceMahalanobis(self.subspaces, self.proba, robust=True, **kw)
         elif method == "gmm":
             ens = SubspaceGMM(self.subspaces, self.proba, **kw)
+        elif method == "hbos":
+            ens = SubspaceHBOS(self.subspaces, self.proba, **kw)
+        elif method == "loda":
+            ens = SubspaceLODA(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
