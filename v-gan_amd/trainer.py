@@ -41,12 +41,17 @@ on side streams) replays SLOWER than the plain chain (357 vs 313 us/step): each 
 more than the overlap returns.  Re-measured on the final step with ONLY the X-X block sums (which feed the reported
 loss, never a gradient) on a side stream that starts after the mask backward and joins at the end of the step:
 161 vs 138 us/step, although dropping those tiles outright would save 7 us.
+
+Which launches a step is made of is decided in step_plan.py (plan_step; the VGAN_* measurement knobs are listed on its Knobs
+class); the engine below allocates for that plan and runs it.
 """
 import contextlib
 import gc
 import os
 
 import torch
+
+from .step_plan import CHAIN_KPARTS_AUTO, Knobs, _best_boundary, _launch_rounds, _round4, chain_kparts, plan_step  # noqa: F401 (re-exported)
 
 ADADELTA_RHO = 0.9   # torch.optim.Adadelta defaults used by the reference (src/vgan.py:567-568)
 ADADELTA_EPS = 1e-6
@@ -66,65 +71,6 @@ def no_gc_while_capturing():
     finally:
         if was_enabled:
             gc.enable()
-
-
-def _round4(v):
-    return (v + 3) // 4 * 4
-
-
-def _launch_rounds(tiles, slots, can_split):
-    """Time of a Gram launch of `tiles` tiles in units of one full round of `slots` resident workgroups.  A partial last round
-    is NOT a whole round: with at most half the slots busy a tile runs about twice as fast (c5 wide tiles: 256 tiles 183 us,
-    272 tiles 276, 384 tiles 290; c4: 101, 153, 159), and the wide kernel's K split of a short last round (gram_tail_ws) brings
-    a remainder of up to an eighth / a quarter of the slots down to ~0.25 / ~0.4 of a round (c5: 16 tiles +28 us, 64 tiles +60)."""
-    if tiles <= 0:
-        return 0.0
-    full, r = divmod(tiles, slots)
-    if r == 0:
-        return float(full)
-    x = r / slots
-    last = 0.55 if x <= 0.5 else 0.55 + 0.9 * (x - 0.5)
-    if can_split and x <= 0.125:
-        last = 0.25
-    elif can_split and x <= 0.25:
-        last = 0.4
-    elif can_split and x <= 0.5:
-        last = 0.5
-    return full + last
-
-
-def _best_boundary(n_main, total, slots, can_split):
-    """First-part size <= n_main (tiles may only move to the SECOND launch, which runs after the all-gather and can take any tile)
-    that minimises the modelled time of the two launches; the boundary moves only for a gain of at least 0.15 round (the
-    model is not finer than that), and among equals as little as possible, so that most work stays beside the all-gather."""
-    cost = lambda k: _launch_rounds(k, slots, can_split) + _launch_rounds(total - k, slots, can_split)
-    best, best_cost = n_main, cost(n_main)
-    for k in range(n_main - 1, max(n_main - slots, 0), -1):
-        c = cost(k)
-        if c < best_cost - 1e-9 and c <= cost(n_main) - 0.15:
-            best, best_cost = k, c
-    return best
-
-
-CHAIN_KPARTS_AUTO = 4  # the measured winner of {1, 2, 4, 8} for both launches it applies to
-
-
-def chain_kparts(want, tiles, k, chain_flops=False):
-    """Workgroups per 32 x 32 output tile for one long-K launch of the collapsed chain's backward (in-launch K split,
-    vgan_linear_backward_params_ksplit / vgan_gemm_grouped_ksplit).  `tiles` = the launch's 32 x 32 output tiles, `k` = its
-    shortest contraction; `want` = VGAN_CHAIN_KPARTS: "auto", or 1 | 2 | 4 | 8 to force a count (measurement knob).
-    "auto" splits only where it was measured to win (MI355X, profiles/README.md, Round 5): a launch of 32-64 tiles -- a fifth of
-    the chip -- with a contraction of 768 or more, i.e. the c3 step's M_4 (50 tiles, K = 1024) and its first chain-backward
-    launch (48 tiles, K = 788).  Everything else stays at 1: the c1 / c2 chains (1-12 tiles, K <= 512: not measured, and near the
-    ~5 us floor of a dependent launch already), the flop-minimal association of c4 / c5 (hundreds of tiles; its long products use slabs of C)."""
-    if want != "auto":
-        parts = int(want)
-        if parts not in (1, 2, 4, 8):
-            raise ValueError(f"VGAN_CHAIN_KPARTS must be auto, 1, 2, 4 or 8, got {want!r}")
-        return parts
-    if chain_flops or not (32 <= tiles <= 64 and k >= 768):
-        return 1
-    return CHAIN_KPARTS_AUTO
 
 
 class FlatParams:
@@ -161,19 +107,14 @@ class NoKLStepEngine:
                  seed=777, noise="device", rank=0, world=1, group=None, use_graph=True, loss_accum_scale=None,
                  generator_mode=None, force_exchange=False, mmd_precision=None, center_operand=True, overlap_exchange=None,
                  fuse_update=None, front=None, chain_assoc=None):
+        """Decides the step's schedule (step_plan.plan_step: every decision, its reasons and its measurements are there) and
+        allocates the buffers that schedule needs."""
         self.ops = ops
         self.dev = data.device
         self.rank, self.world, self.group = rank, world, group
-        # take the data-parallel exchange path (collectives included) even with one rank: lets a single GPU exercise it
-        self.exchange = world > 1 or bool(force_exchange)
         n = self.n = int(batch_size)
-        if n % world != 0:
-            raise ValueError(f"global batch {n} must be divisible by the number of ranks {world}")
-        nl = self.nl = n // world
-        self.lo = rank * nl
         self.data = data
         d = self.d = data.shape[1]
-        dp = self.dp = _round4(d)
         self.nb = int(batches_per_epoch)
         self.lr, self.wd, self.pen = float(lr), float(weight_decay), float(penalty_weight)
         self.seed = int(seed)
@@ -186,54 +127,42 @@ class NoKLStepEngine:
         self.steps_done = 0
         self._xx_primed = False  # overlap mode: have the X-X sums of the upcoming batch been computed?
         self._coalesce = None    # sharded front: may the gathers share one collective launch?  (probed at first use)
-        self.mode = generator_mode or os.environ.get("VGAN_GENERATOR", "collapsed")
-        if self.mode not in ("collapsed", "layered"):
-            raise ValueError(f"generator_mode must be 'collapsed' or 'layered', got {self.mode!r}")
-        # collapsed mode, opt-in (VGAN_FUSE_UPDATE=1): Adadelta in the epilogue of the last chain launch instead of a launch of
-        # its own.  Built, parity-tested and measured on MI355X at c3 (same box, alternating runs): 8 358-8 444 steps/s fused vs
-        # 8 424-8 529 separate -- the 127 tiles of that launch stream the 8 MB of optimiser state with far less memory-level
-        # parallelism than the 1 600 workgroups of the streaming kernel (12.5 us vs 5.1 + 5.3 us), which costs more than the
-        # removed launch boundary returns.  Kept off by default.
-        self.fuse_update = (os.environ.get("VGAN_FUSE_UPDATE", "0") == "1") if fuse_update is None else bool(fuse_update)
-        # Data-parallel FRONT of the step (generator forward, mask, projection, operand split -- O(n d) work):
-        #   "replicated"  every rank produces all n rows of U and Y itself (module docstring): no exchange before the Gram; right
-        #                 while the front is a handful of microseconds (c3: ~10 us);
-        #   "sharded"     SURVEY 8e steps 1-2: a rank runs the logits product, mask / projection and operand split for ITS n/G rows
-        #                 only and the ranks all-gather the Y rows of the operand (split images or fp32 rows, their norms, and the
-        #                 column arg-max keys of the rows, which the step tail folds by max exactly like its own chunks).  The X half
-        #                 of the operand needs no parameter, so every rank gathers it from the resident data set itself, and the
-        #                 tiles that read no other rank's Y rows (XY and X-X: ~60 % of a rank's table) run BESIDE the all-gather.
-        #   "auto"        sharded when there is an exchange at all and n d >= 2^22 (c4 / c5; at those sizes the replicated front
-        #                 is 25-40 % of a 1/8 shard's step).
-        # Replicas stay bit-identical (every rank sees the same gathered bytes and the same all-reduced M_4); results agree with
-        # the replicated front to fp32 rounding of the logits product (its tile shape follows the row count).
-        want_front = front or os.environ.get("VGAN_DP_FRONT", "auto")
-        if want_front not in ("auto", "replicated", "sharded"):
-            raise ValueError(f"front must be 'auto', 'replicated' or 'sharded', got {want_front!r}")
-        if want_front == "sharded" and not (self.exchange and self.mode == "collapsed"):
-            raise ValueError("front='sharded' needs a data-parallel engine (world > 1 or force_exchange) with the collapsed generator")
-        self.front_sharded = (self.exchange and self.mode == "collapsed" and
-                              (want_front == "sharded" or (want_front == "auto" and n * data.shape[1] >= (1 << 22))))
-
         lin = [m for m in generator.main if isinstance(m, torch.nn.Linear)]
         assert len(lin) == 4
         L = self.L = lin[0].in_features
         self.widths = [L] + [m.out_features for m in lin]
-        params = [q for m in lin for q in (m.weight, m.bias)]
+        tables = {}  # host tile tables the plan counted: the chosen one is not built twice
+        self.plan = plan_step(ops, n=n, d=d, data_stride=data.stride(0), latent=L, widths=self.widths, world=world, rank=rank,
+                              force_exchange=force_exchange, generator_mode=generator_mode, mmd_precision=mmd_precision,
+                              overlap_exchange=overlap_exchange, fuse_update=fuse_update, front=front, chain_assoc=chain_assoc,
+                              knobs=Knobs.from_env(), host_tables=tables)
+        vars(self).update(vars(self.plan))  # the step methods read the decisions as plain attributes: self.mode, self.bf3, ...
+        self._alloc_generator([q for m in lin for q in (m.weight, m.bias)])
+        self._alloc_mmd(center_operand)
+        self.perm = torch.zeros(self.nb, n, dtype=torch.int32, device=self.dev)
+        # the NEXT epoch's table, staged while the current epoch runs (stage_epoch_batches / begin_epoch)
+        self.perm_next = torch.zeros_like(self.perm)
+        self.epoch_staged = False
+        self._alloc_carriers()
+        self._alloc_tiles(tables[self.gram_tile, self.tile_split])
+        self._hist, self._hist_n, self._hist_events = None, 0, []  # per-epoch mean losses kept on the device (close_epoch)
+        self._read_stream, self._loss_host = None, None
+        self.accum_scale = (1.0 / self.nb) if loss_accum_scale is None else float(loss_accum_scale)
+        if self.front_sharded and data.is_cuda and self._collect().is_initialized():
+            self._coalesce = self._probe_coalescing(self._collect())  # here, eagerly: the first exchange may run inside a capture
+
+    def _alloc_generator(self, params):
+        """Flat parameters, noise / logits of all batch rows, and the generator's chain (collapsed) or activations (layered)."""
+        ops, n, nl, d, L, e = self.ops, self.n, self.nl, self.d, self.L, self.e
+        f32 = dict(dtype=torch.float32, device=self.dev)
         self.fp = FlatParams(params, self.dev)
         self.W = [self.fp.view(self.fp.flat, 2 * k) for k in range(4)]
         self.b = [self.fp.view(self.fp.flat, 2 * k + 1) for k in range(4)]
-
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        # products that contract over the batch rows are cut into row slices ("slabs", summed in fixed order)
-        # so that a launch with a small output still fills the chip
-        self.splits = max(1, min(8, nl // 128))
-        self.e = [_round4(w + 1) for w in self.widths]  # padded homogeneous widths
-        self.za = torch.zeros(n, self.e[0], **f32)       # [z | 1 | 0-pad] for ALL batch rows (noise stream is replicated)
+        self.za = torch.zeros(n, e[0], **f32)       # [z | 1 | 0-pad] for ALL batch rows (noise stream is replicated)
         self.za[:, L] = 1.0
         self.z_own = self.za[self.lo:self.lo + nl]
-        self.logits = torch.zeros(n, d, **f32)           # all rows on every rank (replicated front, see the module docstring)
-        self.chain_flops = False
+        self.logits = torch.zeros(n, d, **f32)      # all rows on every rank (replicated front, see the module docstring)
+        self._chain = None  # logits job of the mask / projection launch (chain_in_mask), built at first use
         if self.mode == "layered":
             self.gslab = torch.zeros(self.splits, self.fp.total, **f32) if self.splits > 1 else None
             gbase = self.gslab[0] if self.splits > 1 else self.fp.grad
@@ -242,69 +171,43 @@ class NoKLStepEngine:
             self.acts = [self.za[:, :L]] + [torch.zeros(n, w, **f32) for w in self.widths[1:4]] + [self.logits]
             self.acts_own = [a[self.lo:self.lo + nl] for a in self.acts]
             self.dacts = [None] + [torch.zeros(nl, w, **f32) for w in self.widths[1:4]]
-        else:
-            e = self.e
-            # packed weights Wt_k = [[W_k, b_k],[0, 1]] and packed gradients Gt_k = [dW_k | db_k] share ONE offset table, so
-            # Adadelta can read the gradient of a flat element and write its updated value through a single index map
-            poff = [0]
-            for k in range(1, 5):
-                poff.append(poff[-1] + e[k] * e[k - 1])
-            self.Wt_all = torch.zeros(poff[-1], **f32)
-            self.Gt_all = torch.zeros(poff[-1], **f32)
-            self.Wt = [None] + [self.Wt_all[poff[k - 1]:poff[k]].view(e[k], e[k - 1]) for k in range(1, 5)]
-            self.Gt = [None] + [self.Gt_all[poff[k - 1]:poff[k]].view(e[k], e[k - 1]) for k in range(1, 5)]
-            self.At = [None, self.Wt[1]] + [torch.zeros(e[k], e[0], **f32) for k in range(2, 5)]  # Wt_k .. Wt_1 (At_1 = Wt_1)
-            self.M = [None, self.Gt[1]] + [torch.zeros(e[k], e[0], **f32) for k in range(2, 5)]   # M_1 IS Gt_1 (At_0 = I)
-            # suffix products B_3 = Wt_4 Wt_3 and B_2 = B_3 Wt_2: with them every M_k is one product away from M_4 and At_4 one
-            # product away from At_2, so the chain is 3 + 2 dependent launches instead of 4 + 3 (each ~5 us whatever its size)
-            self.B3 = torch.zeros(e[4], e[2], **f32)
-            self.B2 = torch.zeros(e[4], e[1], **f32)
-            self.At1s = torch.zeros(e[1], e[0], **f32)  # snapshot of Wt_1 for the launch that also updates it (fuse_update)
-            # Association of the chain.  "depth" (above: suffix products, 3 + 2 dependent launches) buys latency with flops -- the
-            # product B_3 = Wt_4 Wt_3 alone is 2 e4 e3 e2 flop, 17 GFLOP of the 37 the chain costs at c5 (555 us of an 8.2 ms
-            # step, replicated on every rank of a data-parallel run).  "flops" keeps every product an [e_k, e_{k-1}] x
-            # [e_{k-1}, e0] one (At_k = Wt_k At_{k-1}, M_{k-1} = Wt_k^T M_k): 3 + 4 dependent launches, 17 GFLOP at c5.
-            # "auto": flops once the suffix product passes 1 GFLOP (c4: 2.2, c3: 0.12).
-            want_assoc = chain_assoc or os.environ.get("VGAN_CHAIN_ASSOC", "auto")
-            if want_assoc not in ("auto", "depth", "flops"):
-                raise ValueError(f"chain_assoc must be 'auto', 'depth' or 'flops', got {want_assoc!r}")
-            self.chain_flops = want_assoc == "flops" or (want_assoc == "auto" and 2.0 * e[4] * e[3] * e[2] >= 1e9)
-            if self.chain_flops:
-                self.fuse_update = False  # (the fused optimiser epilogue is written for the depth-first launches)
-                # Products with a long contraction over few 64 x 64 output tiles (c5: M_3 = Wt_4^T M_4 is 165 tiles of K = 4100 on
-                # 256 CUs, 116 us for 4.4 GFLOP) are cut into K slices run by different workgroups -- ~1000 work items per
-                # product -- whose partial slabs a small launch sums in fixed order (no atomics: replicas stay bit-identical).
-                def split_of(m, n_, k):
-                    t64 = ((m + 63) // 64) * ((n_ + 63) // 64)
-                    return 1 if 2.0 * m * n_ * k < 2.5e8 else max(1, min(8, 1024 // t64, k // 256))
-                self.fwd_split = {k: split_of(e[k], e[0], e[k - 1]) for k in (2, 3, 4)}       # At_k = Wt_k At_{k-1}
-                self.bwd_split = {k: split_of(e[k - 1], e[0], e[k]) for k in (4, 3, 2)}       # M_{k-1} = Wt_k^T M_k
-                if os.environ.get("VGAN_CHAIN_SPLITK", "1") != "1":  # measurement knob
-                    self.fwd_split, self.bwd_split = {k: 1 for k in (2, 3, 4)}, {k: 1 for k in (4, 3, 2)}
-                need = max([self.fwd_split[k] * e[k] * e[0] for k in (2, 3, 4)] + [self.bwd_split[k] * e[k - 1] * e[0] for k in (4, 3, 2)])
-                self.chain_ws = torch.zeros(need, **f32)
-            pmap = torch.full((self.fp.total,), -1, dtype=torch.int32)
-            for k in range(1, 5):
-                wk, wk1 = self.widths[k], self.widths[k - 1]
-                r = torch.arange(wk, dtype=torch.int32)[:, None] * e[k - 1]
-                ow, ob = self.fp.offsets[2 * (k - 1)], self.fp.offsets[2 * (k - 1) + 1]
-                pmap[ow:ow + wk * wk1] = (poff[k - 1] + r + torch.arange(wk1, dtype=torch.int32)[None, :]).reshape(-1)
-                pmap[ob:ob + wk] = (poff[k - 1] + r + wk1).reshape(-1)
-            self.pmap = pmap.to(self.dev)
-            self.pack_layers = [(self.W[k - 1], self.b[k - 1], self.Wt[k]) for k in range(1, 5)]
-            self.unpack_layers = [(self.fp.view(self.fp.grad, 2 * (k - 1)), self.fp.view(self.fp.grad, 2 * (k - 1) + 1), self.Gt[k])
-                                  for k in range(1, 5)]
-            ops.homogeneous_pack(self.pack_layers, unpack=False)  # once; afterwards Adadelta keeps Wt current
+            return
+        # packed weights Wt_k = [[W_k, b_k],[0, 1]] and packed gradients Gt_k = [dW_k | db_k] share ONE offset table, so
+        # Adadelta can read the gradient of a flat element and write its updated value through a single index map
+        poff = [0]
+        for k in range(1, 5):
+            poff.append(poff[-1] + e[k] * e[k - 1])
+        self.Wt_all = torch.zeros(poff[-1], **f32)
+        self.Gt_all = torch.zeros(poff[-1], **f32)
+        self.Wt = [None] + [self.Wt_all[poff[k - 1]:poff[k]].view(e[k], e[k - 1]) for k in range(1, 5)]
+        self.Gt = [None] + [self.Gt_all[poff[k - 1]:poff[k]].view(e[k], e[k - 1]) for k in range(1, 5)]
+        self.At = [None, self.Wt[1]] + [torch.zeros(e[k], e[0], **f32) for k in range(2, 5)]  # Wt_k .. Wt_1 (At_1 = Wt_1)
+        self.M = [None, self.Gt[1]] + [torch.zeros(e[k], e[0], **f32) for k in range(2, 5)]   # M_1 IS Gt_1 (At_0 = I)
+        # suffix products B_3 = Wt_4 Wt_3 and B_2 = B_3 Wt_2: with them every M_k is one product away from M_4 and At_4 one
+        # product away from At_2, so the chain is 3 + 2 dependent launches instead of 4 + 3 (each ~5 us whatever its size)
+        self.B3 = torch.zeros(e[4], e[2], **f32)
+        self.B2 = torch.zeros(e[4], e[1], **f32)
+        self.At1s = torch.zeros(e[1], e[0], **f32)  # snapshot of Wt_1 for the launch that also updates it (fuse_update)
+        if self.chain_flops:  # one workspace for the K-slice slabs of whichever product is running
+            need = max([self.fwd_split[k] * e[k] * e[0] for k in (2, 3, 4)] + [self.bwd_split[k] * e[k - 1] * e[0] for k in (4, 3, 2)])
+            self.chain_ws = torch.zeros(need, **f32)
+        pmap = torch.full((self.fp.total,), -1, dtype=torch.int32)
+        for k in range(1, 5):
+            wk, wk1 = self.widths[k], self.widths[k - 1]
+            r = torch.arange(wk, dtype=torch.int32)[:, None] * e[k - 1]
+            ow, ob = self.fp.offsets[2 * (k - 1)], self.fp.offsets[2 * (k - 1) + 1]
+            pmap[ow:ow + wk * wk1] = (poff[k - 1] + r + torch.arange(wk1, dtype=torch.int32)[None, :]).reshape(-1)
+            pmap[ob:ob + wk] = (poff[k - 1] + r + wk1).reshape(-1)
+        self.pmap = pmap.to(self.dev)
+        self.pack_layers = [(self.W[k - 1], self.b[k - 1], self.Wt[k]) for k in range(1, 5)]
+        self.unpack_layers = [(self.fp.view(self.fp.grad, 2 * (k - 1)), self.fp.view(self.fp.grad, 2 * (k - 1) + 1), self.Gt[k])
+                              for k in range(1, 5)]
+        ops.homogeneous_pack(self.pack_layers, unpack=False)  # once; afterwards Adadelta keeps Wt current
 
-        # "fp32": Gram/backward products on the fp32 MFMA; "bf16x3": split-bf16 operands on the (16x faster) bf16 MFMA,
-        # three products per term, fp32 accumulate (~3e-7 relative on a Gram entry; parity tests hold it to the same
-        # 1e-4 bar).  "auto" keeps fp32 for small problems, where the operand-preparation launch would not pay.
-        self.precision = mmd_precision or os.environ.get("VGAN_MMD_PRECISION", "auto")
-        if self.precision not in ("auto", "fp32", "bf16x3"):
-            raise ValueError(f"mmd_precision must be 'auto', 'fp32' or 'bf16x3', got {self.precision!r}")
-        if self.precision == "auto":
-            self.precision = "bf16x3" if 2 * n * d >= (1 << 20) else "fp32"
-        self.bf3 = self.precision == "bf16x3"
+    def _alloc_mmd(self, center_operand):
+        """The MMD operand [X - c ; U*X - c] with its norms and split images, the gradient weights and what the mask backward reads."""
+        n, nl, d, dp = self.n, self.nl, self.d, self.dp
+        f32, i16 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int16, device=self.dev)
         # The MMD operand is CENTRED: Z = [X - c ; U*X - c] with c = the per-feature mean of the data set (once per fit).
         # cdist(Z, Z)**2 and the backward expression sum_j W_ij (z_i - z_j) are translation invariant, so nothing changes in
         # exact arithmetic, but a feature's common offset mu no longer costs (mu/sigma)^2 of the operands' mantissa in
@@ -312,241 +215,71 @@ class NoKLStepEngine:
         # product rule needs the batch itself: the backward kernels add c back to their multiplier (`mul_shift`).
         self.center = torch.zeros(dp, **f32)
         if center_operand:
-            ops.col_mean(data, self.center)
-        self.bwd_tile = int(os.environ.get("VGAN_BWD_TILE", "0"))  # measurement knob: force the 64- / 128-wide bf16x3 backward tile
-        self._fin = None  # finalize job (raw pointers of the tensors below), built at first use
+            self.ops.col_mean(self.data, self.center)
         self.S = torch.zeros(n, d, **f32)
         self.S_own = self.S[self.lo:self.lo + nl]
         self.Z = torch.zeros(2 * n, dp, **f32)
         self.sqn = torch.zeros(2 * n, **f32)   # bf16x3 mode: norms of the split values hi + lo (what its Gram multiplies)
         self.sq_cal = torch.zeros(2 * n, **f32) if self.bf3 else self.sqn  # fp32 norms for the (fp32) calibration launch
         self.Wg = torch.zeros(nl, 2 * n, **f32)
-        # The backward GEMM contracts over the 2n rows of Z; it can be sliced into row slabs that the mask-backward kernel
-        # sums.  Measured at c3: 2 slabs pay for the split-bf16 kernel (24.3 vs 29.6 us; 3 and 4 spill into a second round
-        # of workgroups), none do for the fp32 kernel.  Small problems have only a handful of output tiles with a long K
-        # loop each (c2: 24 tiles, 26 us of an 84 us step), so the slab count also grows until the launch fills the chip.
-        out_tiles = ((nl + 63) // 64) * ((d + 63) // 64)
-        # (a slab keeps at least one 64-deep K tile: at c1 -- two output tiles, K = 256 -- four slabs of one K tile beat one
-        #  workgroup looping over four, 23.5 k vs 21.9 k steps/s; 8 and 16 slabs at c2: the consumer's slab loop costs more than it saves)
-        auto_splits = max(2 if self.bf3 else 1, min(4, 256 // max(out_tiles, 1), max(1, (2 * n) // 64)))
-        # (the 256 x 128 loader-wave tiles of c4 / c5 fill the chip without slabs: c5 3.27 ms with two slabs, 3.16 with one)
-        rm = self.front_sharded or os.environ.get("VGAN_BWD_OPERAND", "rowmajor") != "transposed"  # (self.rm_backward, set below)
-        if self.bf3 and rm and self.bwd_tile in (0, 256) and ops.mmd_backward_bf3_tile(nl, d, 1, self.bwd_tile) == 256:
-            auto_splits = 1
-        self.bsplits = max(1, int(os.environ.get("VGAN_BWD_SPLITS", str(auto_splits))))
         self.gU_slabs = torch.zeros(self.bsplits, nl, dp, **f32)
         self.gU = self.gU_slabs[0]
         # [nl, d] view of a zero-padded [nl, dp] buffer: the M_4 product reads the padded matrix (vector loads for any d)
         self.dlogits_pad = torch.zeros(nl, dp, **f32)
         self.dlogits = self.dlogits_pad[:, :d]
-        # MMD arithmetic: "fp32" (fp32 MFMA, default) or "bf16x3" (split-bf16 operands on the bf16 MFMA, see
-        # csrc/mmd_bf16.hip: ~3e-7 relative on a Gram entry at K = 784, a third of the time)
-        self.rm_backward = True
-        if self.precision == "bf16x3":
-            i16 = dict(dtype=torch.int16, device=self.dev)
-            self.kp, self.kn = (d + 63) // 64 * 64, (2 * n + 63) // 64 * 64
+        if self.bf3:
             self.Zh, self.Zl = torch.zeros(2 * n, self.kp, **i16), torch.zeros(2 * n, self.kp, **i16)
-            # The backward product W . Z reads the SAME row-major images as the Gram (vgan_mmd_backward_bf3_rm: B fragments by
-            # transposed LDS reads), so the operand preparation writes no transposed copy of Z (6.6 MB of scattered 16-byte stores
-            # per step at c3).  VGAN_BWD_OPERAND=transposed keeps the round-1 form (ZTh / ZTl) for measurement.
-            self.rm_backward = self.front_sharded or os.environ.get("VGAN_BWD_OPERAND", "rowmajor") != "transposed"
-            if self.rm_backward:
+            if self.rm_backward:  # the backward reads the Gram's row-major images: no transposed copy of Z
                 self.ZTh = self.ZTl = None
             else:
                 self.ZTh, self.ZTl = torch.zeros(self.kp, self.kn, **i16), torch.zeros(self.kp, self.kn, **i16)
             self.Wh, self.Wl = torch.zeros(nl, self.kn, **i16), torch.zeros(nl, self.kn, **i16)
-        self.fused_prepare = (self.bf3 and not self.front_sharded and ops.bf3_fusable(n, d, self.logits.stride(0), data.stride(0), dp) and
-                              os.environ.get("VGAN_FUSED_PREPARE", "1") == "1")
-        # collapsed generator, opt-in (VGAN_CHAIN_IN_MASK=1): the logits product inside the mask / projection launch (one wave per
-        # batch row, the row's logits live in its registers anyway): one launch and 2 n d x 4 bytes of traffic less per step.
-        # MEASURED (MI355X, c3, same box, alternating runs): 8 029-8 038 steps/s fused vs 8 371-8 455 separate (fp32 mode 5 873 vs
-        # 6 316).  Every workgroup has to stage all of At_4 (163 KB, transposed through LDS in four chunks, each a dependent
-        # global load + barrier) for its 8 rows: the carrying launch grows from 9.5 to 21.8 us, more than the 5.2 us launch it
-        # replaces.  Off by default.
-        self.chain_in_mask = (self.mode == "collapsed" and not self.front_sharded and ops.chain_fusable(n, d, data.stride(0), dp) and
-                              (not self.bf3 or self.fused_prepare) and os.environ.get("VGAN_CHAIN_IN_MASK", "0") == "1")
-        self._chain = None
-        # collapsed generator, depth-first association, opt-in (VGAN_LOGITS_2STAGE=1): the logits product as the second half of a
-        # two-stage tile (see _generator_forward) -- one dependent launch less per step.  MEASURED (MI355X, c3, same box,
-        # alternating runs): 9 285, 9 265 steps/s against 9 702, 9 715 with the three-launch forward (fp32 mode 6 324-6 337 vs
-        # 6 522-6 544): the two carrying launches grow by more than the 5.1 us launch they replace (a two-stage tile is three
-        # dependent K loops and a workgroup barrier deep; the logits as a K = 200 product over 208 tiles is no longer a 5 us
-        # launch's worth riding in a 6.8 us one).  Off by default.
-        self.two_stage_logits = (self.mode == "collapsed" and not self.chain_flops and not self.chain_in_mask and not self.front_sharded and
-                                 os.environ.get("VGAN_LOGITS_2STAGE", "0") == "1")
-        if self.two_stage_logits:
-            e2 = self.e[2]
-            self.T = torch.zeros(n, e2, **f32)  # [z|1] . At_2^T
-            self.T_ws = torch.zeros(((n + 63) // 64) * ((e2 + 63) // 64) * 64 * _round4(self.e[1]), **f32)
-        self.perm = torch.zeros(self.nb, n, dtype=torch.int32, device=self.dev)
-        # the NEXT epoch's table, staged while the current epoch runs (stage_epoch_batches / begin_epoch)
-        self.perm_next = torch.zeros_like(self.perm)
-        self.epoch_staged = False
-        # Gram tile edge: the split-bf16 Gram has a 128x128 variant (half the L2 -> LDS bytes per flop, one 512-thread
-        # workgroup per CU).  Measured: c5 330 vs 273 TFLOP/s algorithmic, c3 (136 tiles of 128) no gain (26.3 vs 25.6 us),
-        # so it is used once its table fills the chip twice over and the row shard is a whole number of tiles.
-        self.gram_tile = 64
-        want = os.environ.get("VGAN_GRAM_TILE", "auto")
-        if self.bf3 and nl % 128 == 0 and want in ("auto", "128"):
-            if want == "128" or len(ops.build_tiles(n, 1, rank, world, device=self.dev, tile=128)) >= 512:
-                self.gram_tile = 128
-        # ... and a 256 x 128 variant with dedicated loader waves (csrc/gemm_bf3w.hpp: 3/4 of the fill bytes per flop, three
-        # K stages in LDS, v_mfma_f32_16x16x32_bf16; main loop +17-19 % over the 128 x 128 one on warm operands), used once ITS
-        # table fills the chip twice over (c4: 1 056 tiles, c5: 4 160)
-        if self.bf3 and nl % 256 == 0 and want in ("auto", "256"):
-            if want == "256" or len(ops.build_tiles(n, 1, rank, world, device=self.dev, tile=256)) >= 512:
-                self.gram_tile = 256
-        # one 768-thread workgroup holds a CU, so a table runs in rounds of 256 tiles; the library splits a short last round over
-        # K when it is lent this workspace (include/vgan_hip.h, tail_ws: c4's 1 040 tiles = 4 rounds + 16 tiles)
-        self.gram_tail_ws = (ops.gram_tail_workspace(self.dev)
-                             if self.gram_tile == 256 and os.environ.get("VGAN_GRAM_TAIL", "1") != "0" else None)
-        # ... and its epilogue leaves the row sums of W per 128-column slot, which the 256 x 128 backward kernel folds instead of
-        # summing W's rows from LDS with its loader waves (-5 % of that launch at c5)
-        self.rs_part = None
-        if (self.gram_tile == 256 and self.rm_backward and n % 128 == 0 and os.environ.get("VGAN_RS_FROM_GRAM", "1") != "0"
-                and ops.mmd_backward_bf3_tile(nl, d, self.bsplits, self.bwd_tile) == 256):
-            self.rs_part = torch.zeros((2 * n + 127) // 128, nl, **f32)
-        # Overlap of the step's tail with the only work of the NEXT step that needs no updated parameter: the X half of its
-        # operand (gather, centre, split) and the X-X tiles of its Gram, which feed nothing but the reported loss.  They run on
-        # a side stream that forks right after the MMD backward launch (whose riding step tail has advanced the batch cursor)
-        # and joins at the end of the step -- concurrent with the mask backward, the M_4 contraction, the gradient all-reduce of
-        # a data-parallel run, the chain backward and the optimiser, all of which are small launches that leave most CUs
-        # idle.  The table is laid out as [XY and YY tiles | XX tiles]: the step's Gram launch covers the first part (392
-        # instead of 528 tiles at n = 1024: no second round on the 512 resident slots), the side launch the second, and the
-        # step tail folds both (one table, one partial buffer).  overlap_exchange=False: the plain one-stream schedule with
-        # the XX tiles inside the Gram launch; "serial": the overlapped schedule's launches on ONE stream (measurement aid).
-        if overlap_exchange is None and os.environ.get("VGAN_OVERLAP") is not None:  # measurement knob: 1 | 0 | serial
-            overlap_exchange = {"1": True, "0": False}.get(os.environ["VGAN_OVERLAP"], os.environ["VGAN_OVERLAP"])
-        # MEASURED (MI355X, c3, same box, profiles/r02_overlap_schedules.txt): the side-stream schedule LOSES on this stack --
-        # 6 843-6 972 steps/s against 8 259-8 529 plain on one GPU; emulated 1/8 shard 120 us against 87 (plain) and 105 (same
-        # launches on one stream).  The Gram does drop from 24.2 to 14.2 us without its 136 X-X tiles, but two kernels running
-        # side by side inside the graph slow each other (M_4 product 8.5 -> 13.0 us, mask backward 5.1 -> 6.9) and the fork /
-        # join is not free.  The default is therefore the plain schedule; the option stays for stacks where streams are cheap.
-        self.overlap = False if overlap_exchange is None else bool(overlap_exchange)
-        if self.front_sharded and self.overlap:
-            raise ValueError("overlap_exchange and front='sharded' are two schedules of the same exchange: choose one")
-        self._side = torch.cuda.Stream(device=self.dev) if (self.overlap and data.is_cuda and overlap_exchange != "serial") else None
-        # with the X half of the operand produced ahead of the step, the mask / projection launch writes the Y half only
-        self.x_ahead = self.overlap and (not self.bf3 or self.rm_backward)
-        # bf16x3 mode, fused forward: the X-X tiles (sums only, independent of everything the step computes) ride in the mask /
-        # projection launch as surplus workgroups, reading the batch's rows through the index table from split images of the
-        # whole data set prepared ONCE here (csrc/mmd_xx.hpp).  The Gram launch keeps the XY and YY tiles: 392 instead of 528 at
-        # n = 1024, one round on the chip's 512 resident slots instead of two.  Riding wants every workgroup of the launch
-        # resident at once (a tile's workgroup holds 74 KB of LDS: two per CU).
-        self.xx_ride = False
-        self._xx = None
-        # MEASURED (MI355X, c3, same box, alternating runs): 8 266-8 319 steps/s riding vs 8 399-8 512 with the tiles inside the
-        # Gram launch.  The Gram does shrink (24.2 -> 17.5 us) but the carrying launch grows from 9.4 to 18.3 us: gathered from
-        # the data set's images the tiles' operand is HBM-cold (in the Gram it is the L2-hot image the forward has just
-        # written) and their K loop becomes latency-bound.  Opt-in (VGAN_XX_RIDE=1), off by default.
-        if (self.fused_prepare and self.gram_tile == 64 and not self.overlap and self.rm_backward and
-                os.environ.get("VGAN_XX_RIDE", "0") == "1"):
-            split, n_main = ops.build_tiles(n, 1, rank, world, device=self.dev, tile=64, split_xx=True)
-            xx_tiles = split.shape[0] - n_main
-            self.xx_ride = xx_tiles > 0 and 8 * ((n // 8 + 7) // 8) + xx_tiles <= 512  # two workgroups per CU (74 KB of LDS each)
-        if self.xx_ride:
-            i16 = dict(dtype=torch.int16, device=self.dev)
-            rows_total = data.shape[0]
-            self.Dh, self.Dl = torch.zeros(rows_total, self.kp, **i16), torch.zeros(rows_total, self.kp, **i16)
-            self.dsq = torch.zeros(rows_total, **f32)
-            ops.gather_rows_split(data, None, self.center, None, self.dsq, True, self.Dh, self.Dl, n=rows_total)
-        # X-X tiles outside the Gram launch, on a warm operand (the step's own Zh / Zl X half, identity row map).  `xx_in_m4` =
-        # "some X-X tiles are computed LATER in the step than the launch that carries the step tail" (the tail is then split);
-        # their carrier is the MMD backward launch when it has room (`xx_late_in_backward`), else the M_4 launch.
-        self.xx_in_m4 = (self.bf3 and self.mode == "collapsed" and self.gram_tile == 64 and not self.overlap and not self.xx_ride and
-                         not self.front_sharded and
-                         ops.linear_backward_params_xx_supported(nl, self.e[0], dp) and os.environ.get("VGAN_XX_IN_M4", "1") == "1")
-        self._xx_m4 = self._fold = None
-        if self.front_sharded:
-            # [XY and X-X tiles | YY tiles]: the first part reads this rank's own Y rows and X columns only and runs while the
-            # other ranks' Y rows are still on their way (`_loss_backward_update_sharded`)
-            self.tiles, self.n_main = ops.build_tiles(n, 1, rank, world, device=self.dev, tile=self.gram_tile, split="yy_last")
-            # Both launches run in rounds of `slots` resident workgroups (128-wide tiles: one 512-thread workgroup per CU; 64-wide:
-            # two), so a first part of 3 x 256 + 4 tiles pays a fourth round for the four (c5, 8 ranks: 772 + 484 tiles, 352 + 198
-            # us against ~100 us per round).  The boundary may move DOWN freely -- the second launch runs after the all-gather and
-            # can take any tile -- so the tail of the first part goes over when the second part has free slots for it.
-            # `_best_boundary` puts it where the modelled time of the two launches is least (128-wide tiles, c5, 8 ranks:
-            # 772 + 484 -> 768 + 488).
-            slots = 256 if self.gram_tile >= 128 else (512 if self.bf3 else 1024)  # (fp32 kernel: 36 KB of LDS, four workgroups per CU)
-            self.n_main = _best_boundary(self.n_main, self.tiles.shape[0], slots, self.gram_tail_ws is not None)
-        elif self.overlap or self.xx_ride or self.xx_in_m4:
-            self.tiles, self.n_main = ops.build_tiles(n, 1, rank, world, device=self.dev, tile=self.gram_tile, split_xx=True)
-            if self.xx_in_m4:
-                # ... but only the X-X tiles the Gram launch has no free slot for: at two 74 KB workgroups per CU the chip holds
-                # 512 tiles at once, and a CU works through two of them in 13.3-14.1 us whether its neighbour has one or two
-                # (tools/ablate_bf3_glds.hip: 392 tiles 13.3 us, 512 tiles 14.1 us).  c3: 392 XY + YY tiles + 120 of the 136 X-X
-                # tiles in the Gram launch, 16 left over.
-                slots = int(os.environ.get("VGAN_GRAM_SLOTS", "512"))  # (tests force a split at small sizes with this)
-                self.n_main = min(self.tiles.shape[0], max(self.n_main, slots))
-                if self.n_main == self.tiles.shape[0]:
-                    self.xx_in_m4 = False  # everything fits the one launch: no carrier, one tail
-        else:
-            self.tiles = ops.build_tiles(n, 1, rank, world, device=self.dev, tile=self.gram_tile)
-            self.n_main = self.tiles.shape[0]
-        # The few X-X tiles left over (c3: 16) ride in the MMD BACKWARD launch when it has free slots for them: that launch fills
-        # 416 of the 512 slots for 25 us, so eight-microsecond tiles on the other slots cost nothing, whereas behind M_4 even 16
-        # tiles stretch the launch from 8.5 to 12.1 us (a lone tile's latency, not their number).  The late half of the split
-        # tail (first chain launch of the backward) picks their sums up either way.
-        self.xx_late_in_backward = False
-        if self.xx_in_m4 and self.rm_backward and os.environ.get("VGAN_XX_LATE", "backward") == "backward":
-            late = self.tiles.shape[0] - self.n_main
-            bwd_wgs = ((d + 63) // 64) * ((nl + 63) // 64) * self.bsplits + 1
-            self.xx_late_in_backward = (ops.mmd_backward_bf3_tile(nl, d, self.bsplits, self.bwd_tile) == 64 and late <= 512 - bwd_wgs)
-        # In-launch K split of the two long-K launches of the chain's backward (chain_kparts): M_4 = dlogits^T [z|1] unless the
-        # X-X tiles ride behind it, and {M_3, M_2, M_1} on the depth association.  One zeroed workspace each, for the engine's life.
-        self.m4_kparts = self.tn_kparts = 1
-        self.m4_ws = self.tn_ws = None
-        if self.mode == "collapsed" and getattr(ops, "chain_ksplit", False):
-            want_kp = os.environ.get("VGAN_CHAIN_KPARTS", "auto")
-            e = self.e
-            t32 = lambda rows, cols: ((rows + 31) // 32) * ((cols + 31) // 32)
-            if not (self.xx_in_m4 and not self.xx_late_in_backward):
-                self.m4_kparts = chain_kparts(want_kp, t32(dp, e[0]), nl, self.chain_flops)
-            tn_tiles = sum(t32(e[k], e[0]) for k in (3, 2, 1))
-            if not self.chain_flops and e[4] >= 96 and tn_tiles <= 256:  # (the library's 16-wave grouped launch: what can be split)
-                self.tn_kparts = chain_kparts(want_kp, tn_tiles, e[4])
-            if self.m4_kparts > 1:
-                self.m4_ws = ops.ksplit_workspace(ops.linear_backward_params_ksplit_ws_bytes(e[0], dp, self.m4_kparts), self.dev)
-            if self.tn_kparts > 1:
-                tn = [("TN", self.Wt[4], self.M[4], self.M[3]), ("TN", self.B3, self.M[4], self.M[2]), ("TN", self.B2, self.M[4], self.M[1])]
-                self.tn_ws = ops.ksplit_workspace(ops.gemm_grouped_ksplit_ws_bytes(tn, [self.tn_kparts] * 3), self.dev)
-        # The default bf16x3 step (fused forward, 64-wide Gram and backward tiles, row-major backward operand, one rank, no
-        # side stream) keeps no fp32 copy of its operand (`lean`).  The Gram reads the split images, and the only reader of Z
-        # in the step was the backward's epilogue; it now forms those two numbers per element from the data row, S and the
-        # centre -- the same bits (vgan_mmd_backward_bf3_rm_rebuild).  The forward writes `xrow`, the batch's data-set rows,
-        # because the step tail that rides in the backward launch advances the batch cursor while that launch runs.  Z is
-        # still written by every step taken before the bandwidth exists (the calibration reads it).  VGAN_Z_FP32=1 keeps the
-        # fp32 copy and the reading backward, for A/B runs.  MEASURED (MI355X, c3, alternating runs on one box,
-        # profiles/README.md): 0.1044 -> 0.1010 ms per step; the backward launch 25.9 -> 22.9 us, the forward 9.1 -> 8.7.
-        # (an ops provider says it has these launches with `bf3_rebuild`: a stand-in without them runs the step as before)
-        plain_bf3 = (getattr(ops, "bf3_rebuild", False) and self.bf3 and self.fused_prepare and self.gram_tile == 64 and
-                     self.rm_backward and world == 1 and not self.overlap and not self.front_sharded and
-                     ops.mmd_backward_bf3_tile(nl, d, self.bsplits, self.bwd_tile) == 64)
-        self.lean = plain_bf3 and os.environ.get("VGAN_Z_FP32", "0") != "1"
-        self.xrow = torch.zeros(n, dtype=torch.int32, device=self.dev) if self.lean else None
-        self._rebuild = None
-        # the first-call bandwidth needs sum(L) over ALL pairs: computed by every rank from the full table (no collective)
-        # (the calibration launch is the fp32 kernel: 64-wide tiles)
-        self.tiles_cal = self.tiles if (world == 1 and self.gram_tile == 64 and not (self.overlap or self.xx_ride or self.xx_in_m4 or self.front_sharded)) else ops.build_tiles(n, 0, 0, 1, device=self.dev)
+
+    def _alloc_tiles(self, host_table):
+        """The Gram's tile table(s) -- `host_table`: the plan's, as ops.build_tiles returned it for plan.gram_tile and
+        plan.tile_split --, the block sums they produce and the step tail's bookkeeping."""
+        ops, n, nl, d, rank = self.ops, self.n, self.nl, self.d, self.rank
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.tiles = (host_table[0] if self.tile_split else host_table).to(self.dev)
+        self.tiles_cal = self.tiles if self.cal_shares_tiles else ops.build_tiles(n, 0, 0, 1, device=self.dev)
         self.partial = torch.zeros(max(self.tiles.shape[0], self.tiles_cal.shape[0]), 4, **f32)
         self.stats = torch.zeros(4, dtype=torch.float64, device=self.dev)
         self.bw = torch.zeros(1, **f32)
         self.has_bw = False
         self.loss = torch.zeros(1, **f32)
         self.loss_accum = torch.zeros(1, **f32)
-        self._hist, self._hist_n, self._hist_events = None, 0, []  # per-epoch mean losses kept on the device (close_epoch)
-        self._read_stream, self._loss_host = None, None
-        self.accum_scale = (1.0 / self.nb) if loss_accum_scale is None else float(loss_accum_scale)
         self.step_counter = torch.zeros(1, dtype=torch.int64, device=self.dev)
-        # column arg-max keys of topk(U, 1, 0): per 64-row chunk, folded by max in the step tail.  Sharded front: one slice of
-        # chunks per rank (its rows' keys carry GLOBAL row numbers), all-gathered with the Y rows; the tail folds them all.
-        self.col_chunks = (world * ops.colmax_chunks(nl)) if self.front_sharded else ops.colmax_chunks(n)
         self.colpart = torch.zeros(self.col_chunks * d, dtype=torch.int64, device=self.dev)
         own = ops.colmax_chunks(nl) * d
         self.colpart_own = self.colpart[rank * own:(rank + 1) * own] if self.front_sharded else self.colpart
         self.colkey = torch.zeros(d, dtype=torch.int64, device=self.dev)
-        if self.front_sharded and data.is_cuda and self._collect().is_initialized():
-            self._coalesce = self._probe_coalescing(self._collect())  # here, eagerly: the first exchange may run inside a capture
+        self._fin = self._fold = None  # finalize jobs (raw pointers of the tensors above), built at first use
+
+    def _alloc_carriers(self):
+        """What only some schedules need: workspaces, the side stream, and the operands of work that rides in another launch."""
+        ops, n, nl, dp, e = self.ops, self.n, self.nl, self.dp, self.e
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        if self.two_stage_logits:
+            self.T = torch.zeros(n, e[2], **f32)  # [z|1] . At_2^T
+            self.T_ws = torch.zeros(((n + 63) // 64) * ((e[2] + 63) // 64) * 64 * _round4(e[1]), **f32)
+        self.gram_tail_ws = ops.gram_tail_workspace(self.dev) if self.gram_tail else None
+        self.rs_part = torch.zeros((2 * n + 127) // 128, nl, **f32) if self.rs_from_gram else None
+        self._side = torch.cuda.Stream(device=self.dev) if (self.side_stream and self.data.is_cuda) else None
+        self._xx = self._xx_m4 = self._rebuild = None  # jobs riding in another launch, built at first use
+        if self.xx_ride:  # split images of the whole (centred) data set, prepared ONCE here
+            i16 = dict(dtype=torch.int16, device=self.dev)
+            rows_total = self.data.shape[0]
+            self.Dh, self.Dl = torch.zeros(rows_total, self.kp, **i16), torch.zeros(rows_total, self.kp, **i16)
+            self.dsq = torch.zeros(rows_total, **f32)
+            ops.gather_rows_split(self.data, None, self.center, None, self.dsq, True, self.Dh, self.Dl, n=rows_total)
+        # one zeroed workspace per K-split launch of the chain's backward, for the engine's life
+        self.m4_ws = self.tn_ws = None
+        if self.m4_kparts > 1:
+            self.m4_ws = ops.ksplit_workspace(ops.linear_backward_params_ksplit_ws_bytes(e[0], dp, self.m4_kparts), self.dev)
+        if self.tn_kparts > 1:
+            tn = [("TN", self.Wt[4], self.M[4], self.M[3]), ("TN", self.B3, self.M[4], self.M[2]), ("TN", self.B2, self.M[4], self.M[1])]
+            self.tn_ws = ops.ksplit_workspace(ops.gemm_grouped_ksplit_ws_bytes(tn, [self.tn_kparts] * 3), self.dev)
+        self.xrow = torch.zeros(n, dtype=torch.int32, device=self.dev) if self.lean else None  # lean step: the batch's data-set rows
 
     # ---- host-side controls ---------------------------------------------------------------------
     def set_epoch_batches(self, idx):
@@ -864,13 +597,12 @@ class NoKLStepEngine:
         ops, n, nl, lo, d = self.ops, self.n, self.nl, self.lo, self.d
         dist = self._collect() if self.exchange else None
         gstride = nl * self.dp
-        bf3 = self.precision == "bf16x3"
-        if bf3 and not self.fused_prepare:
+        if self.bf3 and not self.fused_prepare:
             if self.x_ahead:
                 ops.mmd_bf3_prepare(self.Z[n:], n, d, self.Zh[n:], self.Zl[n:])
             else:
                 ops.mmd_bf3_prepare(self.Z, 2 * n, d, self.Zh, self.Zl, self.ZTh, self.ZTl)
-        if bf3:
+        if self.bf3:
             ops.mmd_gram_bf3(self.Zh, self.Zl, self.sqn, n, self.bw, self.tiles[:self.n_main], self.Wh, self.Wl, n + lo, self.partial, self.S, 0,
                              self.colpart, True, tile=self.gram_tile, tail_ws=self.gram_tail_ws, rs_part=self.rs_part)
         else:
@@ -888,7 +620,7 @@ class NoKLStepEngine:
             else:
                 self._fin = ops.finalize_job(*fin_args)
         fin = self._fin
-        if bf3:
+        if self.bf3:
             if self.lean:
                 if self._rebuild is None:
                     self._rebuild = ops.bwd_rebuild(self.data, self.xrow, self.S, self.center)
