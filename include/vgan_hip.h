@@ -970,6 +970,46 @@ int vgan_gmm_converge(double* lb_partial, int n, int n_components, int first, in
                       int iteration, int32_t* done, int32_t* n_iter, double* lower_bound, double* lb_prev,
                       vgan_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PCA outlier scores (pyod's PCA as its documentation describes it; sklearn's StandardScaler + PCA for the spectrum): the
+ * eigenpairs of the covariance or correlation matrix of every subspace and score = sum_j w_j y_j^2, y = V D^-1 (x - mu)
+ * (v-gan_amd/outlier.py: SubspacePCA, whose docstring is the definition; kernels in csrc/outlier_pca.hip).  mean and cov come
+ * from vgan_maha_moments; the SUBSPACE TABLE (feat, feat_off, sq_off), first, count (<= 65535) and max_dims (>= every d_s of
+ * the range, d_s <= VGAN_MAHA_MAX_DIMS) are as for the vgan_maha_* entries.  All arithmetic is float64.
+ * vgan_pca_eigen: per subspace scale_k = sqrt(C_kk), a scale of exactly 0 replaced by 1, and M_ij = C_ij / (scale_i scale_j)
+ *   when standardize is 1; scale_k = 1 and M = C when it is 0.  M = V^T diag(evals) V by a cyclic two-sided Jacobi method
+ *   with a fixed parallel order: a sweep is n - 1 rounds of a round-robin tournament on n = d_s rounded up to even players
+ *   (round r: position 0 holds player n - 1, position k >= 1 player (k - 1 + r) mod (n - 1); pair i = the players (a, b) at
+ *   positions i and n - 1 - i; a pair with a player >= d_s rests).  A pair is skipped when |m_ab| <= 2^-53 sqrt(|m_aa m_bb|);
+ *   otherwise zeta = (m_bb - m_aa) / (2 m_ab), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), c = 1 / sqrt(1 + t^2), s = c t, every
+ *   pair of the round from the matrix as the previous round left it.  The rotations of a round act on disjoint index pairs;
+ *   M <- J^T M J is evaluated per 2 x 2 block (pair I, pair J), I <= J, as R_I^T (B R_J) with R = [c s; -s c], the mirror image
+ *   written with it, the block I = I set to diag(m_aa - t m_ab, m_bb + t m_ab); the rows a, b of V turn as c v_a - s v_b, s v_a
+ *   + c v_b.  A sweep in which no pair rotated ends the subspace; at most max_sweeps (>= 1) sweeps run.  sweeps int32 [S]: the
+ *   sweeps run, the last, rotation-free one included.  status int32 [S] (written, not accumulated): bit 0 = tr M == 0, bit
+ *   1 = max_sweeps sweeps ran and the last one still rotated.  evals (float64 at feat_off[s]) = the diagonal of the final M
+ *   in descending order, ties by the ascending diagonal position; V (float64 [d_s, d_s] at sq_off[s]): row j the unit
+ *   eigenvector of evals[j], signed so that its entry of largest magnitude (the lowest index on a tie) is positive.  scale
+ *   float64 at feat_off[s].  cov is overwritten and unspecified afterwards.  One workgroup per subspace; M and V live in
+ *   LDS for d_s <= VGAN_PCA_LDS_DIMS and in cov / V beyond.  The order is fixed, so the bits are.
+ * vgan_pca_scores: score[s, i] = float32(sum_j wt_j y_ij^2), y_ij = sum_k V_s[j, k] ((x_ik - mu_k) inv_scale_k), for the rows of
+ *   Xq [rows, d] (ldq) into score [S, ld_score], row s.  inv_scale and wt are float64 at feat_off[s]; wt_j is the weight of
+ *   component j, 0 for a component outside the wanted set.  The product runs on the f64 matrix unit, K in ascending order
+ *   over all d_s; a 16-row tile of V whose weights are all 0 is skipped, which depends on wt alone.  The squares are added
+ *   per residue j mod 4 in ascending j, then the four as (r0 + r1) + (r2 + r3): the bits of an element do not depend on where
+ *   its row sits in the call.
+ * Both return VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_PCA_LDS_DIMS 48
+#define VGAN_PCA_STATUS_CONSTANT 1
+#define VGAN_PCA_STATUS_NOT_CONVERGED 2
+int vgan_pca_eigen(double* cov, const int64_t* sq_off, const int32_t* feat_off, int first, int count, int max_dims,
+                   int standardize, int max_sweeps, double* scale, double* evals, double* V, int32_t* sweeps, int32_t* status,
+                   vgan_stream_t stream);
+int vgan_pca_scores(const float* Xq, int ldq, int rows, int d, const int32_t* feat, const int32_t* feat_off,
+                    const int64_t* sq_off, int first, int count, int max_dims, const double* mean, const double* inv_scale,
+                    const double* V, const double* wt, float* score, int64_t ld_score, vgan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

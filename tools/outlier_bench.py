@@ -49,6 +49,12 @@ difference of the two paths' ensemble scores.
     mask; LODA: whole passes over the chunks, each with its packing: pack alone, range, count, projection + lookup + mean);
     (a) a float64 torch restatement on the same GPU and (b) numpy on the host (numpy.histogram and searchsorted per
     column; LODA for a sample of the subspaces, scaled to all of them); and the ECOD fit on the same subspaces.
+  --method pca: principal-component scores (vgan_amd.SubspacePCA: all components, weighted, standardised, shrinkage 0.1): fit
+    and decision_function (the training rows as queries); the fit split into its launches (moments, the Jacobi eigen
+    solve, the scoring product, the latter also with components="minor", n_components=0.9); SubspaceMahalanobis' fit and
+    its triangular scoring product at the same shape beside them; sklearn's StandardScaler + PCA fitted per subspace on the
+    host for a sample of the subspaces, scaled to all of them; and (eigen_by_width) the eigen solve alone on one subspace of
+    16, 64, 256 features and of the widest width the table held, with its sweep count.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -785,6 +791,86 @@ def run_maha(d, n, count, reps, baselines=True, sklearn_sample=8):
     return row
 
 
+def run_pca(d, n, count, reps, baselines=True, sklearn_sample=8):
+    """SubspacePCA (all components, weighted, standardised) at one shape: fit and decision_function, the eigen launch and the
+    scoring launch on their own, SubspaceMahalanobis beside them, sklearn's StandardScaler + PCA on a sample of subspaces."""
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspacePCA(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    inner = max(reps, 5)
+    t_sc, _ = timed(lambda: ens._distances(Xd), inner)
+    minor = vgan_amd.SubspacePCA(m, p, components="minor", n_components=0.9, weighted=False).fit(Xd)
+    t_minor, _ = timed(lambda: minor._distances(Xd), inner)
+    probe = vgan_amd.SubspacePCA(m, p)
+    probe._begin_fit(Xd)
+    probe._prepare(n, Xd.device)
+    t_mom, _ = timed(lambda: probe._moments(Xd), inner)
+
+    def eigen():  # the solver overwrites C: every repetition starts from fresh moments
+        probe._moments(Xd)
+        probe._eigen()
+    t_me, _ = timed(eigen, reps)
+    maha = vgan_amd.SubspaceMahalanobis(m, p)
+    t_maha_fit, _ = timed(lambda: maha.fit(Xd), reps)
+    t_maha_sc, _ = timed(lambda: maha._distances(Xd), inner)
+    flops = 2.0 * n * float((dims.astype(np.float64) ** 2).sum())
+    row = {"method": "pca", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "d_s_min": int(dims.min()),
+           "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()), "fit_s": round(t_fit, 6), "fit_reps_s": tf,
+           "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td, "moments_s": round(t_mom, 6),
+           "eigen_s": round(t_me - t_mom, 6), "scores_s": round(t_sc, 6), "scores_minor_0.9_s": round(t_minor, 6),
+           "scores_tflops": round(flops / t_sc / 1e12, 3), "sweeps_max": int(ens.n_sweeps_.max()),
+           "sweeps_median": float(np.median(ens.n_sweeps_)), "converged": int(ens.converged_.sum()),
+           "mahalanobis_fit_s": round(t_maha_fit, 6), "mahalanobis_scores_s": round(t_maha_sc, 6),
+           "scores_over_mahalanobis_scores": round(t_sc / t_maha_sc, 2), "state_bytes": int(8 * (dims.astype(np.int64) ** 2).sum())}
+    if baselines:
+        try:
+            from sklearn.decomposition import PCA
+            from sklearn.preprocessing import StandardScaler
+            pick = np.unique(np.linspace(0, S - 1, min(S, sklearn_sample)).astype(int))
+            t_sk, worst = 0.0, 0.0
+            for s in pick:
+                Xs = np.ascontiguousarray(X[:, np.flatnonzero(m[s])]).astype(np.float64)
+                t0 = time.perf_counter()
+                model = PCA().fit(StandardScaler().fit_transform(Xs))
+                t_sk += time.perf_counter() - t0
+                k = len(model.explained_variance_)
+                want = model.explained_variance_ * (n - 1) / n
+                worst = max(worst, float(np.max(np.abs(ens.explained_variance_[s][:k] - want)) / want[0]))
+            scale = S / len(pick)
+            row.update({"sklearn_fit_s": round(t_sk * scale, 4), "sklearn_subspaces_timed": int(len(pick)),
+                        "fit_speedup_vs_sklearn": round(t_sk * scale / t_fit, 1), "max_eigenvalue_diff_vs_sklearn_over_lambda_1": worst})
+        except ImportError:
+            row["sklearn_fit_s"] = None
+    return row
+
+
+def run_pca_widths(n, widths, reps):
+    """The eigen launch alone on one subspace of each width (the first features of a d = 784 synthetic set): time and sweeps."""
+    rows = []
+    for w in widths:
+        X = np.random.default_rng(784 + n).normal(size=(n, 784)).astype(np.float32)
+        X[:, 1] = X[:, 0] + 0.1 * X[:, 1]
+        m = np.zeros((1, 784), bool)
+        m[0, np.random.default_rng(w).choice(784, w, replace=False)] = True
+        Xd = torch.as_tensor(X, device="cuda")
+        probe = vgan_amd.SubspacePCA(m, [1.0])
+        probe._begin_fit(Xd)
+        probe._prepare(n, Xd.device)
+        t_mom, _ = timed(lambda: probe._moments(Xd), reps)
+
+        def eigen():
+            probe._moments(Xd)
+            probe._eigen()
+        t_me, _ = timed(eigen, reps)
+        rows.append({"d_s": int(w), "n": n, "eigen_s": round(t_me - t_mom, 6), "sweeps": int(probe._sweeps.cpu()[0]),
+                     "status": int(probe._status.cpu()[0])})
+        print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    return rows
+
+
 def run_gmm(d, n, count, reps, baselines=True, sklearn_sample=3, C=4, iters=10):
     X, m, p = subspaces_for(d, n, count, seed=d + n + count)
     Xd = torch.as_tensor(X, device="cuda")
@@ -941,13 +1027,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda", "pca"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm / hbos / loda: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm / hbos / loda: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1024,6 +1110,19 @@ def main():
         for d, n, count in shapes:
             out["configs"].append(run_maha(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "pca":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        widest = 0
+        for d, n, count in shapes:
+            out["configs"].append(run_pca(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+            widest = max(widest, out["configs"][-1]["d_s_max"])
+        if not args.shape:  # the solver alone per width: 16, 64, 256 and the widest subspace the table above held
+            out["eigen_by_width"] = run_pca_widths(2000 if args.quick else 10_000, sorted({16, 64, 256, widest}), args.reps)
         configs = []
     if args.method == "gmm":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),

@@ -161,6 +161,8 @@ SIGNATURES = {
     "vgan_maha_factor": (_i, [_p, _p, _p, _i, _i, _i, _p, ctypes.c_double, _p, _p, _p, _p, _p]),
     "vgan_maha_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _i64, _p]),
     "vgan_maha_select": (_i, [_p, _i64, _i, _i, _i, _p, _p, _i64, _p, _p]),
+    "vgan_pca_eigen": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "vgan_pca_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     "vgan_gmm_moments": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _p, ctypes.c_double, _p, _p, _p, _p, _p, _p,
                               _i64, _p]),
     "vgan_gmm_logdet": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),

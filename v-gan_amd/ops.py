@@ -1020,6 +1020,35 @@ class HipOps:
         _lib.check(self.lib.vgan_maha_select(_ptr(score), score.stride(0), n, int(first), int(count), _ptr(hcount), _ptr(support), n,
                                              _ptr(changed), self._stream()), "vgan_maha_select")
 
+    # ---- PCA over subspaces (vgan_amd.outlier.SubspacePCA); table as for the Mahalanobis entries ----------------------
+    def pca_eigen(self, cov, table, first, count, max_dims, standardize, max_sweeps, scale, evals, V, sweeps, status):
+        """The eigenpairs of cov (or, with standardize, of the correlation matrix) of the subspaces first .. first + count - 1 by
+        the fixed-order Jacobi sweeps: scale and evals (float64, at feat_off[s]; evals descending), V (float64 [d_s, d_s] at
+        sq_off[s], row j the j-th component, signed), sweeps and status int32 [S] (bit 0 tr M == 0, bit 1 not converged).
+        cov is overwritten."""
+        for name, v in (("cov", cov), ("scale", scale), ("evals", evals), ("V", V)):
+            _vec(v, name, torch.float64)
+        _vec(sweeps, "sweeps", torch.int32), _vec(status, "status", torch.int32)
+        _, feat_off, sq_off = table
+        assert sweeps.numel() >= first + count and status.numel() >= first + count and V.numel() >= cov.numel()
+        assert scale.numel() == evals.numel()
+        _lib.check(self.lib.vgan_pca_eigen(_ptr(cov), _ptr(sq_off), _ptr(feat_off), int(first), int(count), int(max_dims),
+                                           1 if standardize else 0, int(max_sweeps), _ptr(scale), _ptr(evals), _ptr(V), _ptr(sweeps),
+                                           _ptr(status), self._stream()), "vgan_pca_eigen")
+
+    def pca_scores(self, Xq, table, first, count, max_dims, mean, inv_scale, V, wt, score):
+        """score float32 [S, rows] (a view into the score matrix may be given): rows first .. first + count - 1 receive sum_j wt_j
+        y_j^2, y = V ((x - mean) inv_scale), of the rows of Xq; inv_scale and wt float64 at feat_off[s]."""
+        _mat(Xq, "Xq"), _mat(score, "score")
+        for name, v in (("mean", mean), ("inv_scale", inv_scale), ("V", V), ("wt", wt)):
+            _vec(v, name, torch.float64)
+        feat, feat_off, sq_off = table
+        rows, d = Xq.shape
+        assert score.shape[0] >= first + count and score.shape[1] >= rows and mean.numel() == inv_scale.numel() == wt.numel()
+        _lib.check(self.lib.vgan_pca_scores(_ptr(Xq), Xq.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(sq_off), int(first),
+                                            int(count), int(max_dims), _ptr(mean), _ptr(inv_scale), _ptr(V), _ptr(wt), _ptr(score),
+                                            score.stride(0), self._stream()), "vgan_pca_scores")
+
     # ---- Gaussian mixtures over subspaces (vgan_amd.outlier.SubspaceGMM) ------------------------------------
     # table: the EXPANDED table (feat int32, feat_off int32 [S C + 1], sq_off int64 [S C + 1]) of the entries e = s C + c;
     # first / count are subspaces; done int32 [S] or None

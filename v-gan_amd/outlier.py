@@ -57,6 +57,12 @@ deterministic concentration steps (MCD), and the squared Mahalanobis distance as
 matrix unit (csrc/outlier_maha.hip); n d_s^2 per subspace.  Its contract (support, location, covariance, shrinkage and the
 OAS rule, the score, the degenerate cases, the C-steps, determinism) is that class's docstring.
 
+``SubspacePCA`` is the principal-component detector: the moments of ``SubspaceMahalanobis``, the eigenpairs of every
+subspace's covariance or correlation matrix by a batched fixed-order Jacobi solver, and the weighted squared projections
+on the major, the minor or all components as a full float64 product on the matrix unit (csrc/outlier_pca.hip).  Its
+contract (scaling, order and sign of the eigenpairs, the component count and set, the weights, the degenerate cases,
+determinism) is that class's docstring.
+
 ``SubspaceGMM`` is the probabilistic mixture: EM for a few full-covariance Gaussians per subspace, the stop rule decided per
 subspace on the device, and the negative log-likelihood as the score (csrc/outlier_gmm.hip, with the factor of
 csrc/outlier_maha.hip on the (subspace, component) pairs and the k-means start of csrc/cluster.hip); n C d_s^2 per
@@ -1783,6 +1789,255 @@ class SubspaceMahalanobis(_SubspaceScorer):
                              f"the features are linearly dependent on the support); use shrinkage > 0")
         del self._ws, self._L
         return self._publish(self._combine(per, True), per)
+
+
+# ---- PCA: principal-component scores over the subspaces --------------------------------------------------------------
+PCA_COMPONENT_SETS = ("all", "major", "minor")
+PCA_LDS_DIMS = 48  # VGAN_PCA_LDS_DIMS: up to this width the eigensolver keeps M and V in LDS
+_PCA_CONSTANT, _PCA_NOT_CONVERGED = 1, 2  # VGAN_PCA_STATUS_*
+_PCA_U = 2.0 ** -53
+
+
+def check_pca_components(n_components, components):
+    """n_components: None, an integer >= 1 or a float in (0, 1); components: "all" (n_components must then be None),
+    "major" or "minor"."""
+    if components not in PCA_COMPONENT_SETS:
+        raise ValueError(f"components must be 'all', 'major' or 'minor', got {components!r}")
+    if n_components is not None:
+        if _is_int(n_components):
+            if int(n_components) < 1:
+                raise ValueError(f"n_components must be None, an integer >= 1 or a float in (0, 1), got {n_components!r}")
+            n_components = int(n_components)
+        elif _is_real(n_components) and 0.0 < float(n_components) < 1.0:  # False for nan
+            n_components = float(n_components)
+        else:
+            raise ValueError(f"n_components must be None, an integer >= 1 or a float in (0, 1), got {n_components!r}")
+        if components == "all":
+            raise ValueError(f"components='all' uses every component: n_components must be None, got {n_components!r}")
+    return n_components, components
+
+
+def check_pca_params(n_components, components, weighted, standardize, shrinkage, max_sweeps):
+    """The constructor's checks of SubspacePCA, usable without a device; returns the six values in their canonical types."""
+    n_components, components = check_pca_components(n_components, components)
+    for name, v in (("weighted", weighted), ("standardize", standardize)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False, got {v!r}")
+    if not _is_real(shrinkage) or not 0.0 <= float(shrinkage) <= 1.0:  # False for nan
+        raise ValueError(f"shrinkage must be a float in [0, 1], got {shrinkage!r}")
+    if not (_is_int(max_sweeps) and int(max_sweeps) >= 1):
+        raise ValueError(f"max_sweeps must be a positive integer, got {max_sweeps!r}")
+    return n_components, components, bool(weighted), bool(standardize), float(shrinkage), int(max_sweeps)
+
+
+def pca_variance_ratio(evals):
+    """float64 [d_s]: the eigenvalues clipped at 0 and divided by their sum; all 0 when that sum is 0."""
+    lam = np.maximum(np.asarray(evals, dtype=np.float64), 0.0)
+    total = lam.sum()
+    return lam / total if total > 0.0 else np.zeros_like(lam)
+
+
+def pca_component_count(evals, n_components):
+    """q_s: d_s for None, min(n_components, d_s) for an integer, and for a float f the smallest count whose cumulative
+    variance ratio exceeds f: numpy.searchsorted(numpy.cumsum(ratio), f, side="right") + 1, clipped to d_s (sklearn's rule)."""
+    d = len(evals)
+    if n_components is None:
+        return d
+    if _is_int(n_components):
+        return min(int(n_components), d)
+    return min(int(np.searchsorted(np.cumsum(pca_variance_ratio(evals)), float(n_components), side="right")) + 1, d)
+
+
+def pca_weights(evals, q, components, weighted, shrinkage):
+    """(wt float64 [d_s], degenerate bool): w_j for j in J_s ("all": every j; "major": j < q; "minor": j >= q) and 0 outside it.
+    w_j = 1 when not weighted, else 1 / ((1 - shrinkage) max(lambda_j, 0) + shrinkage tr / d_s) with tr the sum of the
+    eigenvalues as given.  tr == 0: every weight is 0.  degenerate: weighted with shrinkage 0 and a selected lambda_j <= 16
+    d_s 2^-53 lambda_1 (the weights are then not to be used)."""
+    lam = np.asarray(evals, dtype=np.float64)
+    d = lam.shape[0]
+    chosen = np.ones(d, dtype=bool) if components == "all" else np.arange(d) < q if components == "major" else np.arange(d) >= q
+    tr = float(lam.sum())
+    if tr == 0.0 or not chosen.any():
+        return np.zeros(d), False
+    if not weighted:
+        return chosen.astype(np.float64), False
+    if shrinkage == 0.0 and (lam[chosen] <= 16 * d * _PCA_U * lam[0]).any():
+        return np.zeros(d), True
+    shrunk = (1.0 - shrinkage) * np.maximum(lam, 0.0) + shrinkage * tr / d
+    wt = np.zeros(d)
+    wt[chosen] = 1.0 / shrunk[chosen]
+    return wt, False
+
+
+class SubspacePCA(_SubspaceScorer):
+    """Principal-component outlier scores per subspace (pyod's "linear" family: ``PCA``, as remembered, not pinned against
+    pyod; the spectrum is pinned to sklearn's ``StandardScaler`` + ``PCA`` in tests/test_outlier_pca_cpu.py): a row is scored by
+    how far it lies along the principal directions of its subspace, the dominant ones (components="major"), the small ones
+    (components="minor": with unit weights the reconstruction error off the dominant plane, the score that sees a broken
+    correlation structure) or all of them; combined like the other detectors of this module: ``fit`` sets
+    ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying.
+
+    X is cast to float32; all arithmetic is float64 on those values.  n rows are given to ``fit``, 2 <= n <= MAHA_MAX_ROWS
+    (2^24); a subspace has at most MAHA_MAX_DIMS (1024) features.  Per subspace s (features F_s, d_s of them):
+
+        mu_s = (1 / n) sum_i x_i,  C_s = (1 / n) sum_i (x_i - mu_s)(x_i - mu_s)^T     SubspaceMahalanobis' moments, bit for bit
+        scale_k = sqrt(C_kk), an exact 0 replaced by 1 (standardize=True), or 1       sklearn's StandardScaler rule
+        M_s = D^-1 C_s D^-1, D = diag(scale): M_ij = C_ij / (scale_i scale_j)          the correlation matrix; C_s itself if not
+        M_s = V^T Lambda V, lambda_1 >= lambda_2 >= ...                              rows of V are the components
+
+    Eigenvalues are in descending order, equal ones in the ascending order of the diagonal position the solver left them
+    at; every component is signed so that its entry of largest magnitude (the lowest index on a tie) is positive.  The
+    solver is a cyclic Jacobi method with a fixed parallel pair order (include/vgan_hip.h: vgan_pca_eigen has the order and
+    the rotation); it stops after the first sweep that rotates nothing (a pair is left alone when |m_pq| <= 2^-53
+    sqrt(|m_pp m_qq|)) or after max_sweeps sweeps; ``n_sweeps_[s]`` counts the sweeps run (the last, rotation-free one
+    included) and ``converged_[s]`` says whether that last sweep was reached.  A subspace that did not converge is still
+    scored with what the sweeps left.
+
+    Component count q_s (``n_components_``): d_s for n_components=None; min(n_components, d_s) for an integer >= 1; for a
+    float f in (0, 1) numpy.searchsorted(numpy.cumsum(ratio), f, side="right") + 1 clipped to d_s with ratio =
+    ``explained_variance_ratio_[s]`` (sklearn's rule), taken on the host from the fetched eigenvalues.  Component set J_s:
+    "all" every component (n_components must be None), "major" the first q_s, "minor" those after the first q_s.
+
+    Score of row i in subspace s: sum_{j in J_s} w_j y_ij^2 with y_i = V_s D_s^-1 (x_i[F_s] - mu_s), evaluated as V ((x - mu)
+    (1 / scale)).  w_j = 1 when weighted=False; otherwise w_j = 1 / lambda'_j, lambda'_j = (1 - shrinkage) max(lambda_j, 0) +
+    shrinkage tr(M_s) / d_s, with tr(M_s) taken as the float64 sum of the published eigenvalues: the spectrum of sklearn's
+    ``ShrunkCovariance``, so that components="all", weighted=True, standardize=False is SubspaceMahalanobis' score.  The
+    weights are built on the host (pca_weights) from the fetched eigenvalues.  The sum is rounded to float32 into the [S, n]
+    score matrix.  normalize, combination, contamination, ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and
+    return_per_subspace are the shared tail.  ``fit`` excludes nothing: ``decision_function(X_train)`` equals
+    ``decision_scores_`` bit for bit.
+
+    Special cases.  tr(M_s) == 0 (every feature constant), or an empty J_s ("minor" with q_s = d_s): every score of the
+    subspace is exactly 0.  weighted=True with shrinkage=0 and a selected lambda_j <= 16 d_s 2^-53 lambda_1: ``fit`` raises
+    ValueError naming the first such subspace (a constant or duplicated feature among the selected directions); use
+    shrinkage > 0, weighted=False or components="major".
+
+    Determinism: the moments are summed over slabs cut by n alone, the rotations of the solver have a fixed order, the
+    scoring product a fixed K order, and there is no float atomic: scores, eigenpairs and every published array are
+    bit-identical from run to run, for every workspace_bytes (which only limits the slab partials of the moments) and for a
+    subspace fitted alone or among others; the score of a row does not depend on where it sits in a call.  mu_s, 1 / scale,
+    the weights and V_s stay on the device; X is not kept.
+
+    ``fit`` publishes, in the given subspace order: ``explained_variance_`` (list of S float64 [d_s], the eigenvalues of M_s),
+    ``explained_variance_ratio_`` (the eigenvalues clipped at 0, divided by their sum; zeros when that is 0), ``components_``
+    (list of S float64 [d_s, d_s], rows are components; fetched on first use), ``location_``, ``scale_`` (lists of S float64
+    [d_s]), ``n_components_`` (int [S]), ``n_sweeps_`` (int [S]) and ``converged_`` (bool [S]).
+
+    Not built: randomized / truncated SVD solvers (every subspace gets its full spectrum), ``whiten``, pyod's
+    cdist-to-the-eigenvector arithmetic (the projection form above is the one its documentation describes) and incremental
+    fitting.  The definition above and its numpy restatement in tests/test_outlier_pca_cpu.py are what binds.  All of it runs
+    in libvgan_hip.so (csrc/outlier_pca.hip, the moments in csrc/outlier_maha.hip)."""
+
+    _components = None
+
+    def __init__(self, subspaces, proba, n_components=None, components="all", weighted=True, standardize=True, shrinkage=0.1,
+                 max_sweeps=30, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        (self.n_components, self.components, self.weighted, self.standardize, self.shrinkage,
+         self.max_sweeps) = check_pca_params(n_components, components, weighted, standardize, shrinkage, max_sweeps)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > MAHA_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspacePCA takes at most {MAHA_MAX_DIMS}")
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= MAHA_MAX_ROWS:
+            raise ValueError(f"SubspacePCA fit needs between 2 and {MAHA_MAX_ROWS} rows, got {n}")
+
+    def _prepare(self, n, dev):
+        """The tables, the fitted state (mu, scale, eigenvalues at feat_off; C and V at sq_off) and the moment workspace."""
+        S, dims = self.plan.count, self.plan.dims
+        self._fitted, self._components = False, None
+        self._sq_off = np.concatenate([[0], np.cumsum(dims * dims)]).astype(np.int64)
+        cells, self._ranges = maha_ranges(dims, self.workspace_bytes)
+        self._tiles = [torch.as_tensor(maha_tiles(dims, first, count), device=dev) for first, count in self._ranges]
+        self._mtable = (self._table[0], self._table[1], torch.as_tensor(self._sq_off, device=dev))
+        widest = max(int(dims[first:first + count].sum()) for first, count in self._ranges)
+        slabs = -(-n // MAHA_SLAB_ROWS)
+        most = max(slabs * widest, slabs * MAHA_TILE * MAHA_TILE * max(int(t.shape[0]) for t in self._tiles))
+        self._ws = torch.empty(min(cells, most), dtype=torch.float64, device=dev)
+        self._mean, self._scale, self._evals = (torch.empty(int(dims.sum()), dtype=torch.float64, device=dev) for _ in range(3))
+        self._cov, self._V = (torch.empty(int(self._sq_off[-1]), dtype=torch.float64, device=dev) for _ in range(2))
+        self._sweeps, self._status = (torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2))
+
+    def _moments(self, X):
+        """mu and C of every subspace over every row, range by range (SubspaceMahalanobis' launches)."""
+        hcount = torch.full((self.plan.count,), X.shape[0], dtype=torch.int32, device=X.device)
+        for (first, count), tiles in zip(self._ranges, self._tiles):
+            dims = self.plan.dims[first:first + count]
+            self.ops.maha_moments(X, self._mtable, first, count, int(dims.sum()), int(dims.max()), tiles, None, hcount, self._mean,
+                                  self._cov, self._ws)
+
+    def _eigen(self):
+        """scale, the eigenvalues and V of every subspace from its C, which is overwritten."""
+        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
+            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+            self.ops.pca_eigen(self._cov, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), self.standardize,
+                               self.max_sweeps, self._scale, self._evals, self._V, self._sweeps, self._status)
+
+    def _select(self, dev):
+        """Host: q_s and the weights from the fetched eigenvalues; uploads the weights and 1 / scale."""
+        S, off = self.plan.count, self.plan.feat_off
+        evals, scale = self._evals.cpu().numpy(), self._scale.cpu().numpy()
+        status = self._status.cpu().numpy()
+        self.explained_variance_ = [evals[off[s]:off[s + 1]].copy() for s in range(S)]
+        self.explained_variance_ratio_ = [pca_variance_ratio(lam) for lam in self.explained_variance_]
+        self.scale_ = [scale[off[s]:off[s + 1]].copy() for s in range(S)]
+        self.n_components_ = np.array([pca_component_count(lam, self.n_components) for lam in self.explained_variance_], dtype=np.int64)
+        self.n_sweeps_ = self._sweeps.cpu().numpy().astype(np.int64)
+        self.converged_ = (status & _PCA_NOT_CONVERGED) == 0
+        self._constant = (status & _PCA_CONSTANT) != 0
+        wt = np.zeros_like(evals)
+        for s in range(S):
+            if self._constant[s]:
+                continue
+            w, degenerate = pca_weights(self.explained_variance_[s], int(self.n_components_[s]), self.components, self.weighted,
+                                        self.shrinkage)
+            if degenerate:
+                raise ValueError(f"subspace {s}: a selected eigenvalue is at most 16 d_s 2^-53 of the largest (a constant or duplicated "
+                                 f"feature), so 1 / lambda is not a weight; use shrinkage > 0, weighted=False or components='major'")
+            wt[off[s]:off[s + 1]] = w
+        self._wt = torch.as_tensor(wt, device=dev)
+        self._inv_scale = torch.as_tensor(1.0 / scale, device=dev)
+
+    def _distances(self, X):
+        """float32 [S, nq] on the device: the weighted squared projections of the rows of X."""
+        per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
+        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
+            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+            self.ops.pca_scores(X, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), self._mean,
+                                self._inv_scale, self._V, self._wt, per)
+        return per
+
+    def _score(self, X, fitting):
+        per = self._distances(X)
+        return self._combine(per, fitting), per
+
+    @property
+    def components_(self):
+        """List of S float64 [d_s, d_s]: row j the j-th principal direction of M_s."""
+        self._require_fit()
+        if self._components is None:
+            V, sq, d = self._V.cpu().numpy(), self._sq_off, self.plan.dims
+            self._components = [V[sq[s]:sq[s + 1]].reshape(int(d[s]), int(d[s])).copy() for s in range(self.plan.count)]
+        return self._components
+
+    def fit(self, X, y=None):
+        """The moments, the eigenpairs, q_s and the weights of every subspace, then the scores of X itself: decision_scores_
+        (float64 [n]), per_subspace_scores_, explained_variance_, explained_variance_ratio_, components_, location_, scale_,
+        n_components_, n_sweeps_, converged_; with normalize also score_center_ / score_scale_.  Raises ValueError for a
+        subspace whose selected spectrum cannot be inverted (weighted=True, shrinkage=0)."""
+        X = self._begin_fit(X)
+        self._prepare(X.shape[0], X.device)
+        self._moments(X)
+        self._eigen()
+        off = self.plan.feat_off
+        mean = self._mean.cpu().numpy()
+        self.location_ = [mean[off[s]:off[s + 1]].copy() for s in range(self.plan.count)]
+        self._select(X.device)
+        del self._ws, self._cov
+        scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)
 
 
 # ---- Gaussian mixtures: EM per subspace, the negative log-likelihood as the score ------------------------------------

@@ -15,7 +15,7 @@ from torch.utils.data import DataLoader
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
 from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
-                      SubspaceMahalanobis)
+                      SubspaceMahalanobis, SubspacePCA)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -207,7 +207,12 @@ class _RunFolder:
         method "loda" builds a SubspaceLODA (sparse random projections of each subspace with a histogram on each, the
         score the mean -log of the bin probabilities; pyod's LODA): its keywords are n_projections, n_bins, seed,
         workspace_bytes and the same normalize / combination / contamination, e.g. outlier_ensemble(method="loda",
-        n_projections=100, X=X); n_neighbors is not used there."""
+        n_projections=100, X=X); n_neighbors is not used there.
+        method "pca" builds a SubspacePCA (the eigenpairs of each subspace's correlation or covariance matrix by a batched
+        Jacobi solver, the score the weighted squared projections on the major, the minor or all components; pyod's PCA):
+        its keywords are n_components, components, weighted, standardize, shrinkage, max_sweeps, workspace_bytes and the
+        same normalize / combination / contamination, e.g. outlier_ensemble(method="pca", components="minor",
+        n_components=3, weighted=False, X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -228,6 +233,8 @@ class _RunFolder:
             ens = SubspaceHBOS(self.subspaces, self.proba, **kw)
         elif method == "loda":
             ens = SubspaceLODA(self.subspaces, self.proba, **kw)
+        elif method == "pca":
+            ens = SubspacePCA(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
