@@ -1010,6 +1010,58 @@ int vgan_pca_scores(const float* Xq, int ldq, int rows, int d, const int32_t* fe
                     const int64_t* sq_off, int first, int count, int max_dims, const double* mean, const double* inv_scale,
                     const double* V, const double* wt, float* score, int64_t ld_score, vgan_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One-class SVM outlier scores (Schoelkopf et al. 2001; sklearn's OneClassSVM with the RBF kernel, shrinking off; pyod's
+ * OCSVM): K_s(x, y) = exp(-gamma_s d_s(x, y)^2), the dual min 1/2 a^T K a, 0 <= a_t <= 1, sum a = nu n by SMO, score = rho -
+ * sum_r a_r K_s(x_r, x) (v-gan_amd/outlier.py: SubspaceOCSVM, whose docstring is the definition; kernels in
+ * csrc/outlier_ocsvm.hip).  The packed blocks, squared norms, SUBSPACE TABLE (feat_off, col_off), first, count (<= 65535),
+ * engine and splits are those of vgan_outlier_kde; gamma float64 [S], indexed by first + z.  2 <= n <= VGAN_OCSVM_MAX_ROWS.
+ * vgan_ocsvm_kernel_matrix: K float32 [count, n, n]; K[z][c][q] = float32 exp of float32(-gamma_s d2(q, c)), d2 the engine's
+ *   float32 squared distance of query row q and reference row c of the one block P; the diagonal is exactly 1.  Every entry
+ *   is written once whatever splits is.
+ * vgan_ocsvm_init: libsvm's start for the chunk's count matrices: alpha[z][t] = 1 for t < m, a_m for t = m (m < n needs 0 <=
+ *   a_m < 1, m = n needs a_m = 0; m = 0 needs a_m > 0), 0 beyond; G[z][t] = sum over the rows r with alpha_r != 0, ascending,
+ *   of (double)K[z][r][t] alpha_r, every product and sum rounded; done[z] = n_iter[z] = 0.  alpha, G float64 [count, n].
+ * vgan_ocsvm_smo: at most `iterations` steps of WSS2 (Fan, Chen, Lin 2005) for every chunk subspace whose done[z] is 0, one
+ *   workgroup each, float64 with K widened, every operation rounded on its own (no FMA).  A step: stop with done =
+ *   VGAN_OCSVM_DONE_MAX_ITER if n_iter >= max_iter; i = the lowest index with the largest -G_t among alpha_t < 1, Gmax = -G_i,
+ *   Gmax2 = the largest G_t among alpha_t > 0; stop with done = VGAN_OCSVM_DONE_CONVERGED if there is no i or Gmax + Gmax2 <
+ *   tol; among alpha_t > 0 with b_t = Gmax + G_t > 0 and q_t = 2.0 - 2.0 K[i][t] (1e-12 if <= 0), j = the lowest index with the
+ *   smallest -(b_t b_t) / q_t, stop as converged if there is none; delta = (G_i - G_j) / q_j, s = alpha_i + alpha_j, alpha_i -=
+ *   delta, alpha_j += delta, libsvm's four clips for equal labels with C = 1; G_t = G_t + (K[i][t] da_i + K[j][t] da_j) for every
+ *   t; n_iter += 1.  A subspace that reaches max_iter updates inside a launch is flagged in that launch.  A stopped
+ *   subspace is not touched again.  storage: where alpha and G live during a launch and how wide the workgroup is:
+ *   VGAN_OCSVM_STORAGE_LDS (in LDS, 256 threads, n <= VGAN_OCSVM_LDS_ROWS), _GLOBAL (in place, 256 threads), _WIDE (in place,
+ *   1024 threads) or _AUTO (LDS when it fits, WIDE beyond); the results are the same bits.  tol > 0, max_iter >= 1,
+ *   iterations >= 1: no launch loops unbounded.
+ * vgan_ocsvm_rho: rho[z] = the mean of G_t over 0 < alpha_t < 1 (a fixed order); with no such row (max G over alpha_t = 1 + min
+ *   G over alpha_t = 0) / 2, and with one of the two sets empty as well the other one's bound.
+ * vgan_ocsvm_scores: score[score_row[z] (or z), q] = float32((rint(rho_s 2^44) - sum_r rint(alpha_r K_s(x_r, q) 2^44)) 2^-44) for
+ *   the nq rows of Pq against the nr fitted rows of Pr, K_s as in vgan_ocsvm_kernel_matrix without the diagonal rule, rows
+ *   with alpha_r = 0 skipped; alpha float64 [S, nr] and rho float64 [S] indexed by first + z.  acc uint64 [count nq] is
+ *   scratch.  The integer sum has no order: the bits do not depend on splits or on the chunk.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_OCSVM_MAX_ROWS 32768
+#define VGAN_OCSVM_LDS_ROWS 2048
+#define VGAN_OCSVM_DONE_CONVERGED 1
+#define VGAN_OCSVM_DONE_MAX_ITER 2
+#define VGAN_OCSVM_STORAGE_AUTO 0
+#define VGAN_OCSVM_STORAGE_GLOBAL 1
+#define VGAN_OCSVM_STORAGE_LDS 2
+#define VGAN_OCSVM_STORAGE_WIDE 3
+int vgan_ocsvm_kernel_matrix(const float* P, const float* sq, int n, const int32_t* feat_off, const int64_t* col_off, int first,
+                             int count, const double* gamma, int engine, int splits, float* K, vgan_stream_t stream);
+int vgan_ocsvm_init(const float* K, int n, int count, int m, double a_m, double* alpha, double* G, int32_t* done,
+                    int32_t* n_iter, vgan_stream_t stream);
+int vgan_ocsvm_smo(const float* K, int n, int count, double tol, int max_iter, int iterations, int storage, double* alpha,
+                   double* G, int32_t* done, int32_t* n_iter, vgan_stream_t stream);
+int vgan_ocsvm_rho(const double* alpha, const double* G, int n, int count, double* rho, vgan_stream_t stream);
+int vgan_ocsvm_scores(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
+                      const int32_t* feat_off, const int64_t* col_off, int first, int count, const double* gamma,
+                      const double* alpha, const double* rho, int engine, int splits, uint64_t* acc, float* score,
+                      const int32_t* score_row, int64_t ld_score, vgan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

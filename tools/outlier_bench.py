@@ -55,6 +55,12 @@ difference of the two paths' ensemble scores.
     its triangular scoring product at the same shape beside them; sklearn's StandardScaler + PCA fitted per subspace on the
     host for a sample of the subspaces, scaled to all of them; and (eigen_by_width) the eigen solve alone on one subspace of
     16, 64, 256 features and of the widest width the table held, with its sweep count.
+  --method ocsvm: one-class SVM scores (vgan_amd.SubspaceOCSVM, nu 0.1, gamma "scale", tol 1e-3, a 16 GiB workspace so that a
+    chunk holds many kernel matrices): fit and decision_function (the training rows as queries); the fit split into its
+    stages (kernel matrices, the SMO loop with its start and rho, scoring), each behind a synchronisation; the SMO steps
+    per subspace (minimum, median, maximum) and the time of one step of the longest subspace of a chunk; the SMO stage
+    with a and G in LDS (where they fit) and in place with 256 and with 1024 threads; and sklearn's OneClassSVM(kernel="rbf", shrinking=False) fitted and
+    scored per subspace on the host for a sample of the subspaces, scaled to all of them.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1004,6 +1010,74 @@ def normalize_launches(mode, reps, S=500, n=50_000):
             "host_numpy_s": round(t_host, 4), "max_abs_diff_vs_host": float(np.max(np.abs(out.cpu().numpy() - want)))}
 
 
+OCSVM_WORKSPACE = 16 << 30
+
+
+def run_ocsvm(d, n, count, reps, baselines=True, nu=0.1, sample=4):
+    from vgan_amd.outlier import OCSVM_LDS_ROWS, ocsvm_chunks
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    ens = vgan_amd.SubspaceOCSVM(m, p, nu=nu, workspace_bytes=OCSVM_WORKSPACE)
+    t_fit, fit_reps = timed(lambda: ens.fit(Xd), reps)
+    t_dec, dec_reps = timed(lambda: ens.decision_function(Xd), reps)
+    dims, iters = m.sum(axis=1), ens.n_iter_
+    chunks = ocsvm_chunks(ens.plan, n, OCSVM_WORKSPACE)
+    stages = {}
+
+    def staged(name, fn):
+        def wrapped(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **kw)
+            torch.cuda.synchronize()
+            stages[name] = stages.get(name, 0.0) + time.perf_counter() - t0
+            return out
+        return wrapped
+
+    def staged_fit(storage):
+        other = vgan_amd.SubspaceOCSVM(m, p, nu=nu, workspace_bytes=OCSVM_WORKSPACE)
+        other.storage = storage
+        for name, attr in (("kernel_matrix", "_kernel_matrix"), ("smo", "_smo"), ("scoring", "_score")):
+            setattr(other, attr, staged(name, getattr(other, attr)))
+        best = None
+        for _ in range(max(reps, 2)):  # the first pass warms up
+            stages.clear()
+            other.fit(Xd)
+            best = dict(stages) if best is None or stages["smo"] < best["smo"] else best
+        assert np.array_equal(other.dual_coef_, ens.dual_coef_) and np.array_equal(other.decision_scores_, ens.decision_scores_)
+        return {k: round(v, 5) for k, v in best.items()}
+
+    split = staged_fit("auto")
+    longest = sum(int(iters[ens.plan.order[first:first + cnt]].max()) for first, cnt, _ in chunks)  # steps on the critical path
+    row = {"method": "ocsvm", "d": d, "n": n, "nu": nu, "S_sampled": count, "S_distinct": int(len(m)), "d_s_min": int(dims.min()),
+           "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()), "gram_subspaces": int(ens.plan.gram.sum()),
+           "chunks": len(chunks), "kernel_matrix_bytes": 4 * n * n * int(len(m)), "fit_s": round(t_fit, 5), "fit_reps_s": fit_reps,
+           "decision_function_s": round(t_dec, 5), "decision_function_reps_s": dec_reps, "fit_stages_s": split,
+           "kernel_matrix_TFLOPs": round(2.0 * n * n * float(dims.sum()) / split["kernel_matrix"] / 1e12, 2),
+           "n_iter_min": int(iters.min()), "n_iter_median": float(np.median(iters)), "n_iter_max": int(iters.max()),
+           "n_support_median": float(np.median(ens.n_support_)), "converged": bool(ens.converged_.all()),
+           "smo_steps_total": int(iters.sum()), "smo_steps_on_the_critical_path": longest,
+           "smo_us_per_critical_step": round(split["smo"] / max(longest, 1) * 1e6, 2)}
+    row["smo_stage_s_by_storage"] = {where: staged_fit(where)["smo"]
+                                     for where in (("lds",) if n <= OCSVM_LDS_ROWS else ()) + ("global", "wide")}
+    if baselines:
+        from sklearn.svm import OneClassSVM
+        pick = np.unique(np.linspace(0, len(m) - 1, min(sample, len(m))).astype(int))
+        t_host, worst, host_iters = 0.0, 0.0, []
+        for s in pick:
+            Z = X[:, np.flatnonzero(m[s])].astype(np.float64)
+            t0 = time.perf_counter()
+            ref = OneClassSVM(kernel="rbf", gamma="scale", nu=nu, tol=1e-3, shrinking=False, cache_size=4000).fit(Z)
+            want = -ref.decision_function(Z)
+            t_host += time.perf_counter() - t0
+            host_iters.append(int(np.ravel(ref.n_iter_)[0]))
+            worst = max(worst, float(np.abs(ens.per_subspace_scores_[s] - want).max()))
+        row.update({"sklearn_subspaces_timed": [int(s) for s in pick], "sklearn_fit_and_score_s_scaled": round(t_host / len(pick) * len(m), 3),
+                    "sklearn_n_iter": host_iters, "device_n_iter_same_subspaces": [int(iters[s]) for s in pick],
+                    "max_abs_score_diff_vs_sklearn": worst, "speedup_vs_sklearn": round(t_host / len(pick) * len(m) / t_fit, 1)})
+    return row
+
+
 def sweep(n, reps):
     rng = np.random.default_rng(0)
     rows = []
@@ -1027,13 +1101,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda", "pca"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1123,6 +1197,14 @@ def main():
             widest = max(widest, out["configs"][-1]["d_s_max"])
         if not args.shape:  # the solver alone per width: 16, 64, 256 and the widest subspace the table above held
             out["eigen_by_width"] = run_pca_widths(2000 if args.quick else 10_000, sorted({16, 64, 256, widest}), args.reps)
+        configs = []
+    if args.method == "ocsvm":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 2000, 50), (10, 10_000, 50), (784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_ocsvm(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "gmm":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),

@@ -168,6 +168,11 @@ SIGNATURES = {
     "vgan_gmm_logdet": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     "vgan_gmm_estep": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "vgan_gmm_converge": (_i, [_p, _i, _i, _i, _i, _p, ctypes.c_double, _i, _p, _p, _p, _p, _p]),
+    "vgan_ocsvm_kernel_matrix": (_i, [_p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p]),
+    "vgan_ocsvm_init": (_i, [_p, _i, _i, _i, ctypes.c_double, _p, _p, _p, _p, _p]),
+    "vgan_ocsvm_smo": (_i, [_p, _i, _i, ctypes.c_double, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "vgan_ocsvm_rho": (_i, [_p, _p, _i, _i, _p, _p]),
+    "vgan_ocsvm_scores": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i64, _p]),
 }
 
 ABI_VERSION = 11

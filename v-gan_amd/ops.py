@@ -1123,6 +1123,58 @@ class HipOps:
                                               int(iteration), _ptr(done), _ptr(n_iter), _ptr(lower_bound), _ptr(lb_prev), self._stream()),
                    "vgan_gmm_converge")
 
+    # ---- one-class SVM over subspaces (vgan_amd.outlier.SubspaceOCSVM) ---------------------------------------
+    # K float32 [count, n, n], alpha / G float64 [count, n], done / n_iter int32 [count]: the arrays of one chunk.
+    def ocsvm_kernel_matrix(self, P, sq, n, table, first, count, gamma, engine, splits, K):
+        """K[z] = exp(-gamma[first + z] d2) of the packed block P against itself, the diagonal exactly 1."""
+        _vec(P, "P"), _vec(gamma, "gamma", torch.float64), _vec(K, "K")
+        assert K.numel() >= count * n * n and gamma.numel() >= first + count
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_ocsvm_kernel_matrix(_ptr(P), _ptr(sq), int(n), _ptr(feat_off), _ptr(col_off), int(first), int(count),
+                                                     _ptr(gamma), int(engine), int(splits), _ptr(K), self._stream()),
+                   "vgan_ocsvm_kernel_matrix")
+
+    def _ocsvm_state(self, K, alpha, G, done, n_iter):
+        _vec(K, "K"), _vec(alpha, "alpha", torch.float64), _vec(G, "G", torch.float64)
+        _vec(done, "done", torch.int32), _vec(n_iter, "n_iter", torch.int32)
+        if not (K.dim() == 3 and K.shape[1] == K.shape[2]):
+            raise ValueError(f"K: need [count, n, n], got {tuple(K.shape)}")
+        count, n = K.shape[0], K.shape[1]
+        assert alpha.shape == (count, n) and G.shape == (count, n) and done.numel() >= count and n_iter.numel() >= count
+        return count, n
+
+    def ocsvm_init(self, K, m, a_m, alpha, G, done, n_iter):
+        """libsvm's start: alpha = (1 x m, a_m, 0 ...), G = K alpha row after row, done = n_iter = 0."""
+        count, n = self._ocsvm_state(K, alpha, G, done, n_iter)
+        _lib.check(self.lib.vgan_ocsvm_init(_ptr(K), n, count, int(m), float(a_m), _ptr(alpha), _ptr(G), _ptr(done), _ptr(n_iter),
+                                            self._stream()), "vgan_ocsvm_init")
+
+    def ocsvm_smo(self, K, tol, max_iter, iterations, alpha, G, done, n_iter, storage=0):
+        """Enqueues at most `iterations` SMO steps for every subspace of the chunk that is not done; reads nothing back."""
+        count, n = self._ocsvm_state(K, alpha, G, done, n_iter)
+        _lib.check(self.lib.vgan_ocsvm_smo(_ptr(K), n, count, float(tol), int(max_iter), int(iterations), int(storage), _ptr(alpha),
+                                           _ptr(G), _ptr(done), _ptr(n_iter), self._stream()), "vgan_ocsvm_smo")
+
+    def ocsvm_rho(self, alpha, G, rho):
+        _vec(alpha, "alpha", torch.float64), _vec(G, "G", torch.float64), _vec(rho, "rho", torch.float64)
+        count, n = alpha.shape
+        assert G.shape == (count, n) and rho.numel() >= count
+        _lib.check(self.lib.vgan_ocsvm_rho(_ptr(alpha), _ptr(G), n, count, _ptr(rho), self._stream()), "vgan_ocsvm_rho")
+
+    def ocsvm_scores(self, Pq, sq_q, nq, Pr, sq_r, nr, table, first, count, gamma, alpha, rho, engine, splits, acc, score,
+                     score_row=None):
+        """score rows score_row = rho - sum_r alpha_r K(x_r, q) for the chunk; gamma / rho [S] and alpha [S, nr] are indexed by
+        first + z."""
+        _vec(gamma, "gamma", torch.float64), _vec(alpha, "alpha", torch.float64), _vec(rho, "rho", torch.float64)
+        _vec(acc, "acc", torch.int64), _mat(score, "score")
+        assert acc.numel() >= count * nq and alpha.shape[1] == nr and alpha.shape[0] >= first + count
+        assert gamma.numel() >= first + count and rho.numel() >= first + count
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_ocsvm_scores(_ptr(Pq), _ptr(sq_q), int(nq), _ptr(Pr), _ptr(sq_r), int(nr), _ptr(feat_off), _ptr(col_off),
+                                              int(first), int(count), _ptr(gamma), _ptr(alpha), _ptr(rho), int(engine), int(splits),
+                                              _ptr(acc), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
+                   "vgan_ocsvm_scores")
+
 
 _default = None
 

@@ -68,6 +68,12 @@ subspace on the device, and the negative log-likelihood as the score (csrc/outli
 csrc/outlier_maha.hip on the (subspace, component) pairs and the k-means start of csrc/cluster.hip); n C d_s^2 per
 iteration.  Its contract (the start, the M and E steps, the loop, freezing, failures, determinism) is that class's docstring.
 
+``SubspaceOCSVM`` is the boundary method: the one-class SVM with the RBF kernel, whose fitted state is a sparse subset of the
+rows.  The n x n float32 kernel matrix of every subspace comes from the distance engines, the dual is solved by SMO with one
+workgroup per subspace and a stop rule per subspace on the device, and the score is rho minus the kernel sum over the
+fitted rows in fixed point (csrc/outlier_ocsvm.hip); n^2 d_s for the matrix, n per SMO step.  Its contract (gamma, the
+matrix, the start, the step and its arithmetic, rho, the score, determinism, what is not built) is that class's docstring.
+
 ``SubspaceHBOS`` and ``SubspaceLODA`` are the histogram detectors, linear in n: equal-width histograms (numpy.linspace's
 edges, numpy.histogram's counts, exact integer sums) of every feature (HBOS: -log2 densities summed over a subspace's
 features, the dense float64 product of ``SubspaceECOD``) or of sparse random projections of every subspace (LODA: the mean
@@ -2350,4 +2356,257 @@ class SubspaceGMM(_SubspaceScorer):
                              f"of the component); use reg_covar > 0")
         del self._ws, self._L, self._resp, self._lbpart
         scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)
+
+
+OCSVM_MAX_ROWS = 1 << 15  # VGAN_OCSVM_MAX_ROWS: the fixed-point score sum stays below 2^63 and a kernel matrix below 2^32 bytes
+OCSVM_LDS_ROWS = 2048  # VGAN_OCSVM_LDS_ROWS: up to here a launch of the solver keeps a and G in LDS
+OCSVM_STORAGE = {"auto": 0, "global": 1, "lds": 2, "wide": 3}  # VGAN_OCSVM_STORAGE_*
+OCSVM_SMO_STRIDE = 128  # SMO steps of one launch
+OCSVM_GAMMA_RULES = ("scale", "auto")
+_OCSVM_CONVERGED = 1  # VGAN_OCSVM_DONE_CONVERGED
+
+
+def check_ocsvm_params(nu, gamma, tol, max_iter):
+    """nu in (0, 1]; gamma a positive finite float, "scale" or "auto"; tol > 0; max_iter None or an integer >= 1."""
+    if not (_is_real(nu) and 0.0 < float(nu) <= 1.0):  # False for nan
+        raise ValueError(f"nu must be a float in (0, 1], got {nu!r}")
+    if isinstance(gamma, str):
+        if gamma not in OCSVM_GAMMA_RULES:
+            raise ValueError(f"gamma must be a positive float, 'scale' or 'auto', got {gamma!r}")
+    elif not (_is_real(gamma) and np.isfinite(gamma) and gamma > 0):
+        raise ValueError(f"gamma must be a positive float, 'scale' or 'auto', got {gamma!r}")
+    else:
+        gamma = float(gamma)
+    if not (_is_real(tol) and np.isfinite(tol) and tol > 0):
+        raise ValueError(f"tol must be positive and finite, got {tol!r}")
+    if max_iter is not None and not (_is_int(max_iter) and 1 <= int(max_iter) < 2 ** 31):
+        raise ValueError(f"max_iter must be None or an integer between 1 and 2^31 - 1, got {max_iter!r}")
+    return float(nu), gamma, float(tol), None if max_iter is None else int(max_iter)
+
+
+def check_ocsvm_rows(n):
+    if not 2 <= n <= OCSVM_MAX_ROWS:
+        raise ValueError(f"the one-class SVM takes between 2 and {OCSVM_MAX_ROWS} fitted rows, got {n}")
+
+
+def ocsvm_gamma(gamma, dims, var=None):
+    """float64 [S]: gamma_s per subspace of dims (sizes d_s).  "scale": 1 / (d_s var_s), var_s the variance over all entries of
+    the subspace's block (var [S]), taken as 1.0 where it is 0 (sklearn's rule); "auto": 1 / d_s; a float: itself."""
+    d = np.asarray(dims, dtype=np.float64)
+    if gamma == "scale":
+        var = np.asarray(var, dtype=np.float64)
+        return 1.0 / (d * np.where(var == 0.0, 1.0, var))
+    if gamma == "auto":
+        return 1.0 / d
+    return np.full(d.shape, float(gamma), dtype=np.float64)
+
+
+def ocsvm_block_variance(col_mean, col_ssd, n, feats):
+    """The float64 variance over the n x d_s entries of the columns feats, from every column's mean and its sum of squared
+    deviations from that mean: (sum_f ssd_f + n sum_f (mean_f - mu)^2) / (n d_s), mu the mean of the column means."""
+    mean, ssd = np.asarray(col_mean, np.float64)[feats], np.asarray(col_ssd, np.float64)[feats]
+    mu = mean.mean()
+    return float((ssd.sum() + n * ((mean - mu) ** 2).sum()) / (n * len(feats)))
+
+
+def ocsvm_start(nu, n):
+    """(m, a_m) of libsvm's start: m = int(nu n) rows at 1 and, when m < n, row m at nu n - m (0.0 for m = n)."""
+    m = int(nu * n)
+    return m, (nu * n - m if m < n else 0.0)
+
+
+def ocsvm_chunks(plan, n, limit_bytes):
+    """[(first, count, gram)]: consecutive runs of the processing order, one engine each, whose n x n float32 kernel matrices
+    plus packed blocks (values and norms) fit in limit_bytes; a subspace that alone exceeds it forms a chunk of its own."""
+    out, first = [], 0
+    widths = _round4(plan.dims)
+    while first < plan.count:
+        end, used = first, 0
+        while end < plan.count and plan.gram[end] == plan.gram[first] and end - first < 65535:
+            need = int(n) * int(n) * 4 + int(n) * (int(widths[end]) + 1) * 4
+            if end > first and used + need > limit_bytes:
+                break
+            used += need
+            end += 1
+        out.append((first, end - first, bool(plan.gram[first])))
+        first = end
+    return out
+
+
+class SubspaceOCSVM(_SubspaceScorer):
+    """One-class SVM per subspace (Schoelkopf et al. 2001; sklearn's OneClassSVM(kernel="rbf", shrinking=False), pyod's OCSVM),
+    combined like the detectors of SubspaceEnsemble: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows,
+    higher is more outlying.  Only the RBF kernel is built: no linear, poly or sigmoid kernel (no coef0 / degree), no
+    shrinking, no kernel cache.  This docstring is the contract.
+
+    Kernel.  K_s(x, y) = exp(-gamma_s d_s(x, y)^2) on the raw features of subspace s.  gamma is a positive float, "scale" or
+    "auto".  "scale" is 1 / (d_s var), var the float64 variance over all n x d_s entries of the subspace's block, 1.0 where
+    that variance is 0 (sklearn's rule); "auto" is 1 / d_s.  The default is "scale": this project's data is not
+    standardised.  ``fit`` publishes ``gamma_``, float64 [S].  The per-column float64 means and sums of squared deviations
+    come from torch on the device and are combined per subspace on the host (ocsvm_block_variance).
+
+    Kernel matrix.  ``fit`` builds K, float32 [n, n], per subspace from the float32 distance engines (exact below
+    GRAM_MIN_DIMS, Gram above with operands centred on the column mean, as for KDE): an entry is the float32 exp of float32(-gamma_s
+    d2).  The diagonal is stored as exactly 1.  K need not be bitwise symmetric; every use below names its row.  Subspaces
+    are chunked so that count n n 4 bytes plus the packed blocks fit workspace_bytes; a subspace that alone exceeds it forms
+    a chunk of its own.  ``fit`` takes 2 to 2^15 rows.
+
+    Dual and start (libsvm's scaling).  Minimise 1/2 a^T K a subject to 0 <= a_t <= 1 and sum a = nu n, nu in (0, 1].  m =
+    int(nu n) on the host; a_t = 1 for t < m, a_m = nu n - m when m < n, the rest 0.  G = K a starts as the sum over the
+    nonzero rows r in ascending order, G_t += (double)K[r, t] a_r, every product and every sum rounded on its own.
+
+    Iteration: WSS2 of Fan, Chen and Lin 2005, all float64 with K widened from float32, every operation rounded on its own
+    (nothing is contracted into an FMA).
+      1. i is the lowest index with the largest -G_t among a_t < 1; Gmax = -G_i; Gmax2 is the largest G_t among a_t > 0.
+      2. Stop as converged if no such i exists or if Gmax + Gmax2 < tol.
+      3. Among t with a_t > 0 and b_t = Gmax + G_t > 0 take q_t = 2.0 - 2.0 K[i, t], and q_t = 1e-12 if q_t <= 0; j is the
+         lowest index with the smallest -(b_t b_t) / q_t.  Stop as converged if there is none.
+      4. delta = (G_i - G_j) / q_j, s = a_i + a_j, a_i -= delta, a_j += delta, then libsvm's four clips for equal labels, in
+         libsvm's order, with C = 1.
+      5. For every t, G_t = G_t + (K[i, t] da_i + K[j, t] da_j).
+      6. n_iter += 1.
+    (libsvm itself keeps the highest index on a tie of either selection; ties between float64 gradients of real data are
+    rare, and the lowest index is this class's rule.)  After max_iter updates the subspace stops with ``converged_`` False;
+    max_iter=None means 100 n.  Every subspace stops on its own and keeps a and G bit for bit while the others go on.
+
+    rho is the mean of G_t over 0 < a_t < 1.  With no such row it is (max G over a_t = 1 + min G over a_t = 0) / 2.  With one of
+    those two sets empty as well (nu = 1: every a_t is 1) it is the other side's bound: libsvm's formula is infinite there,
+    this is this class's own rule.
+
+    Score.  score_s(x) = rho_s - sum_r a_r K_s(x_r, x): minus sklearn's ``decision_function``, pyod's ``decision_scores_``.
+    ``fit`` keeps X resident and scores the training rows through the same sweep as ``decision_function``, excluding
+    nothing: ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.  The sweep is the distance engines over
+    all fitted rows (rows with a_r = 0 add no term; the diagonal rule of the kernel matrix does not apply).  Each term a_r K(q,
+    r) lies in [0, 1] and is added as rint(term 2^44) in 64-bit fixed point, exact below 2^63 for n <= 2^15; rho enters as
+    rint(rho 2^44), and the integer difference times 2^-44 is rounded to float32.  The sum has no order: scores are
+    bit-identical from run to run, for every splits and workspace_bytes, and for a subspace fitted alone or with others.  A
+    subspace whose features are all constant has K = 1 everywhere, takes 0 iterations and scores exactly 0.
+
+    Published: the common attributes; ``dual_coef_`` float64 [S, n]; ``support_``, a list of S index arrays (a_t > 0);
+    ``n_support_`` [S]; ``intercept_`` = -rho, float64 [S]; ``gamma_``; ``n_iter_`` [S]; ``converged_`` [S]; all in the given
+    subspace order.
+
+    engine, splits (the reference-row split of the kernel-matrix and scoring sweeps), normalize, combination and
+    contamination are those of SubspaceEnsemble.  Four attributes, set after construction, serve tests and measurements
+    and change no result: ``smo_stride`` (SMO steps of one launch, default OCSVM_SMO_STRIDE), ``poll_stride`` (launches
+    between two looks at the done flags, default POLL_STRIDE), ``storage`` ("auto", "lds", "global" or "wide": whether a launch
+    keeps a and G in LDS or in place, the latter with 256 or 1024 threads) and ``keep_kernel_matrix`` (True: ``fit`` also publishes ``kernel_matrix_``, a list of S float32 [n, n] arrays,
+    the matrices the solver read)."""
+
+    _X = None
+
+    def __init__(self, subspaces, proba, nu=0.5, gamma="scale", tol=1e-3, max_iter=None, engine="auto", splits=None,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        self.nu, self.gamma, self.tol, self.max_iter = check_ocsvm_params(nu, gamma, tol, max_iter)
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
+            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
+        self.splits = splits
+        self.smo_stride, self.poll_stride, self.storage = OCSVM_SMO_STRIDE, POLL_STRIDE, "auto"
+        self.keep_kernel_matrix = False
+
+    # ---- pipeline --------------------------------------------------------------------------------
+    def _check_fit_rows(self, n):
+        check_ocsvm_rows(n)
+
+    def _splits(self, nq, nr, count):
+        if self.splits is not None:
+            return int(self.splits)
+        blocks = -(-nq // 64) * count
+        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
+
+    def _resolve_gamma(self, X):
+        """float64 [S] in processing order."""
+        plan, var = self.plan, None
+        if self.gamma == "scale":
+            Xd = X.double()
+            mean = Xd.mean(dim=0)
+            ssd = ((Xd - mean) ** 2).sum(dim=0)
+            mean, ssd = mean.cpu().numpy(), ssd.cpu().numpy()
+            var = [ocsvm_block_variance(mean, ssd, X.shape[0], plan.feat[plan.feat_off[z]:plan.feat_off[z + 1]])
+                   for z in range(plan.count)]
+        return ocsvm_gamma(self.gamma, plan.dims, var)
+
+    def _kernel_matrix(self, X, first, count, gram):
+        n = X.shape[0]
+        P, sq = self._pack(X, first, count, gram)
+        K = torch.empty(count, n, n, dtype=torch.float32, device=X.device)
+        self.ops.ocsvm_kernel_matrix(P, sq, n, self._table, first, count, self._gamma, ENGINES["gram" if gram else "exact"],
+                                     self._splits(n, n, count), K)
+        return K
+
+    def _smo(self, K, first, count, max_iter, flags):
+        """The solver on the chunk's matrices: the start, then launches of smo_stride steps; the host looks at the chunk's
+        done flags through one pinned buffer every poll_stride launches.  At most max_iter steps are ever enqueued."""
+        n = K.shape[1]
+        a, g = self._alpha[first:first + count], self._G[first:first + count]
+        done, iters = self._done[first:first + count], self._iters[first:first + count]
+        self.ops.ocsvm_init(K, *ocsvm_start(self.nu, n), a, g, done, iters)
+        stream = torch.cuda.current_stream()
+        launched = 0
+        while launched < max_iter:
+            for _ in range(max(1, int(self.poll_stride))):
+                steps = min(max(1, int(self.smo_stride)), max_iter - launched)
+                if steps <= 0:
+                    break
+                self.ops.ocsvm_smo(K, self.tol, max_iter, steps, a, g, done, iters, OCSVM_STORAGE[self.storage])
+                launched += steps
+            flags[:count].copy_(done, non_blocking=True)
+            stream.synchronize()
+            if bool((flags[:count] != 0).all()):
+                break
+        self.ops.ocsvm_rho(a, g, self._rho[first:first + count])
+
+    def _score(self, Xq, fitting):
+        Xr = self._X
+        nr, nq = Xr.shape[0], Xq.shape[0]
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xr.device)
+        for first, count, gram in self.plan.chunks(nr if Xq is Xr else nr + nq, self.workspace_bytes):
+            Pr, sqr = self._pack(Xr, first, count, gram)
+            Pq, sqq = (Pr, sqr) if Xq is Xr else self._pack(Xq, first, count, gram)
+            acc = torch.empty(count * nq, dtype=torch.int64, device=Xr.device)
+            self.ops.ocsvm_scores(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, self._gamma, self._alpha, self._rho,
+                                  ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count), acc, per,
+                                  self._rows[first:first + count])
+            del Pq, Pr, sqq, sqr, acc
+        return self._combine(per, fitting), per
+
+    # ---- public surface --------------------------------------------------------------------------
+    def fit(self, X, y=None):
+        """The kernel matrices and the SMO loop per subspace of X, then the scores of X itself: decision_scores_ (float64 [n]),
+        per_subspace_scores_, dual_coef_, support_, n_support_, intercept_, gamma_, n_iter_, converged_; with normalize also
+        score_center_ / score_scale_.  X stays resident as the fitted rows."""
+        self._X = X = self._begin_fit(X)
+        n, S, dev = X.shape[0], self.plan.count, X.device
+        gamma = self._resolve_gamma(X)
+        self._gamma = torch.as_tensor(gamma, device=dev)
+        self._alpha = torch.empty(S, n, dtype=torch.float64, device=dev)
+        self._G = torch.empty(S, n, dtype=torch.float64, device=dev)
+        self._rho = torch.empty(S, dtype=torch.float64, device=dev)
+        self._done = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._iters = torch.zeros(S, dtype=torch.int32, device=dev)
+        max_iter = 100 * n if self.max_iter is None else self.max_iter
+        flags = torch.empty(S, dtype=torch.int32).pin_memory()
+        kept = [None] * S
+        for first, count, gram in ocsvm_chunks(self.plan, n, self.workspace_bytes):
+            K = self._kernel_matrix(X, first, count, gram)
+            self._smo(K, first, count, max_iter, flags)
+            if self.keep_kernel_matrix:
+                host = K.cpu().numpy()
+                for z in range(count):
+                    kept[int(self.plan.order[first + z])] = host[z]
+            del K
+        del self._G
+        scores, per = self._score(X, fitting=True)
+        g = self.plan.given
+        self.gamma_ = gamma[g]
+        self.dual_coef_ = self._alpha.cpu().numpy()[g]
+        self.support_ = [np.flatnonzero(a > 0.0) for a in self.dual_coef_]
+        self.n_support_ = np.array([len(s) for s in self.support_], dtype=np.int64)
+        self.intercept_ = -self._rho.cpu().numpy()[g]
+        self.n_iter_ = self._iters.cpu().numpy()[g].astype(np.int64)
+        self.converged_ = self._done.cpu().numpy()[g] == _OCSVM_CONVERGED
+        if self.keep_kernel_matrix:
+            self.kernel_matrix_ = kept
         return self._publish(scores, per)

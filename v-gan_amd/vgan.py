@@ -15,7 +15,7 @@ from torch.utils.data import DataLoader
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
 from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
-                      SubspaceMahalanobis, SubspacePCA)
+                      SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -212,7 +212,11 @@ class _RunFolder:
         Jacobi solver, the score the weighted squared projections on the major, the minor or all components; pyod's PCA):
         its keywords are n_components, components, weighted, standardize, shrinkage, max_sweeps, workspace_bytes and the
         same normalize / combination / contamination, e.g. outlier_ensemble(method="pca", components="minor",
-        n_components=3, weighted=False, X=X); n_neighbors is not used there."""
+        n_components=3, weighted=False, X=X); n_neighbors is not used there.
+        method "ocsvm" builds a SubspaceOCSVM (the one-class SVM with the RBF kernel per subspace, its dual solved by SMO on
+        the device, the score minus the decision value; sklearn's OneClassSVM, pyod's OCSVM): its keywords are nu, gamma, tol,
+        max_iter, engine, splits, workspace_bytes and the same normalize / combination / contamination, e.g.
+        outlier_ensemble(method="ocsvm", nu=0.1, X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -235,6 +239,8 @@ class _RunFolder:
             ens = SubspaceLODA(self.subspaces, self.proba, **kw)
         elif method == "pca":
             ens = SubspacePCA(self.subspaces, self.proba, **kw)
+        elif method == "ocsvm":
+            ens = SubspaceOCSVM(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
