@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_* and vgan_loda_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_* and vgan_loda_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -52,6 +52,8 @@ int vgan_linear_backward_input(const float* dy, int lddy, const float* W, int ld
  * splits > 1: the batch rows are cut into `splits` slices and slice s writes its PARTIAL result to
  * dW + s*slab_stride / db + s*slab_stride (elements); sum the slabs with vgan_reduce_slabs.  The
  * contraction runs over the batch while the outputs are small, so slicing is what fills the chip.
+ * A slice is ceil(n / splits) rows rounded up to a multiple of 4; slices past the last row are empty and
+ * their slabs (db included) are written as zeros, so the reducer may always sum `splits` slabs.
  * x may itself be given as x_nslabs unreduced slabs (see vgan_linear_forward). */
 int vgan_linear_backward_params(const float* dy, int lddy, const float* x, int ldx, int x_nslabs,
                                 int64_t x_slab_stride, float* dW, int lddw, float* db, int n, int in,
@@ -76,6 +78,47 @@ int vgan_linear_backward_params_xx(const float* dy, int lddy, const float* x, in
 int64_t vgan_linear_backward_params_ksplit_ws_bytes(int in, int out, int parts);
 int vgan_linear_backward_params_ksplit(const float* dy, int lddy, const float* x, int ldx, float* dW, int lddw, int n, int in,
                                        int out, int parts, void* ws, int64_t ws_bytes, vgan_stream_t stream);
+/* Host-side path queries (no launch, nothing dereferenced: only nullness and alignment of the pointers are looked at, so they
+ * work without a GPU).  Each takes its entry point's arguments without the stream and returns the code of the kernel
+ * instantiation that entry point launches for exactly those arguments, or a negative value where it returns VGAN_ERR_ARG.
+ * The entry points switch on the same function's value.  T64: 64 x 64 x 32 tiles (GemmTile, 256 threads); KS4 / KS16: 32 x 32
+ * tiles with every 128-deep K tile split over 4 / 16 waves (GemmTileKS); V4 / V1: operands staged 16 bytes / one float per
+ * lane (V1: some dimension, leading dimension or base address is no multiple of 4 floats); SLABS: the slab-summing stager. */
+enum vgan_linear_forward_path_code {
+    VGAN_LINEAR_FORWARD_T64_V4 = 0,       /* linear_fwd_kernel<4, false> */
+    VGAN_LINEAR_FORWARD_T64_V1 = 1,       /* linear_fwd_kernel<1, false> */
+    VGAN_LINEAR_FORWARD_T64_V4_SLABS = 2, /* linear_fwd_kernel<4, true>: x_nslabs > 1 */
+    VGAN_LINEAR_FORWARD_T64_V1_SLABS = 3, /* linear_fwd_kernel<1, true> */
+    VGAN_LINEAR_FORWARD_KS4_V4 = 4,       /* linear_fwd_ks_kernel<4, 4>: at most 32 64 x 64 tiles, in >= 128 */
+    VGAN_LINEAR_FORWARD_KS4_V1 = 5,       /* linear_fwd_ks_kernel<1, 4> */
+    VGAN_LINEAR_FORWARD_KS16_V4 = 6,      /* linear_fwd_ks_kernel<4, 16>: the same with in >= 512 */
+    VGAN_LINEAR_FORWARD_PATHS = 7
+};
+enum vgan_linear_backward_input_path_code {
+    VGAN_LINEAR_BACKWARD_INPUT_T64_V4 = 0, /* linear_bwd_input_kernel<4> */
+    VGAN_LINEAR_BACKWARD_INPUT_T64_V1 = 1, /* linear_bwd_input_kernel<1> */
+    VGAN_LINEAR_BACKWARD_INPUT_KS4_V4 = 2, /* linear_bwd_input_ks_kernel<4>: at most 32 64 x 64 tiles, out >= 128; `in` may be ragged
+                                            * when ldw >= round4(in): W's columns [in, round4(in)) are then read and never stored */
+    VGAN_LINEAR_BACKWARD_INPUT_KS4_V1 = 3, /* linear_bwd_input_ks_kernel<1> */
+    VGAN_LINEAR_BACKWARD_INPUT_PATHS = 4
+};
+enum vgan_linear_backward_params_path_code {
+    VGAN_LINEAR_BACKWARD_PARAMS_T64_V4 = 0,       /* linear_bwd_params_kernel<4, false> */
+    VGAN_LINEAR_BACKWARD_PARAMS_T64_V1 = 1,       /* linear_bwd_params_kernel<1, false> */
+    VGAN_LINEAR_BACKWARD_PARAMS_T64_V4_SLABS = 2, /* linear_bwd_params_kernel<4, true>: x_nslabs > 1 */
+    VGAN_LINEAR_BACKWARD_PARAMS_T64_V1_SLABS = 3, /* linear_bwd_params_kernel<1, true> */
+    VGAN_LINEAR_BACKWARD_PARAMS_KS4_V4 = 4,       /* linear_bwd_params_ks_kernel<4, 4>: db NULL, no slabs, n >= 128 over few tiles */
+    VGAN_LINEAR_BACKWARD_PARAMS_KS4_V1 = 5,       /* linear_bwd_params_ks_kernel<1, 4> */
+    VGAN_LINEAR_BACKWARD_PARAMS_KS16_V4 = 6,      /* linear_bwd_params_ks_kernel<4, 16>: the same with n >= 256 */
+    VGAN_LINEAR_BACKWARD_PARAMS_PATHS = 7
+};
+int vgan_linear_forward_path(const float* x, int ldx, int x_nslabs, int64_t x_slab_stride, const float* W, int ldw,
+                             const float* b, const float* y, int ldy, int n, int in, int out);
+int vgan_linear_backward_input_path(const float* dy, int lddy, const float* W, int ldw, const float* dx, int lddx, int n,
+                                    int in, int out);
+int vgan_linear_backward_params_path(const float* dy, int lddy, const float* x, int ldx, int x_nslabs, int64_t x_slab_stride,
+                                     const float* dW, int lddw, const float* db, int n, int in, int out, int splits,
+                                     int64_t slab_stride);
 /* dst[i] = sum over s < nslabs of src[s*slab_stride + i], in ascending s (bitwise reproducible) */
 int vgan_reduce_slabs(const float* src, int64_t slab_stride, int nslabs, float* dst, int64_t count,
                       vgan_stream_t stream);
@@ -417,6 +460,27 @@ int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count, const vga
  * the launch must be one the library runs on its 16-wave 32 x 32 tiles (every k >= 96, at most 256 tiles in all, the vector
  * contract, no optimiser epilogue, no noise job; copy and fold jobs may ride) -- anything else is VGAN_ERR_ARG, as is kparts[i] > 1
  * together with splitk > 1 (that form writes slabs of C for vgan_reduce_slabs).  extras may be NULL. */
+/* Host-side path query of the grouped launches (see vgan_linear_forward_path): the launch vgan_gemm_grouped (extras and kparts
+ * NULL), vgan_gemm_grouped_ex (kparts NULL) or vgan_gemm_grouped_ksplit makes for these arguments, or a negative value where
+ * they return VGAN_ERR_ARG (the K split's workspace, which the query is not given, aside).  The code names the launch, its vector
+ * width and whether the optimiser epilogue is instantiated; engine (may be NULL) receives the tile engine of each problem.
+ * The operand pointers inside `problems` are only tested for nullness and alignment. */
+enum vgan_gemm_grouped_path_code {
+    VGAN_GEMM_GROUPED_T256_V4 = 0,     /* gemm_grouped_kernel<4, false>: 256 threads, per problem 64 x 64 or 4-wave 32 x 32 tiles */
+    VGAN_GEMM_GROUPED_T256_V4_EPI = 1, /* gemm_grouped_kernel<4, true>: with the optimiser epilogue */
+    VGAN_GEMM_GROUPED_T256_V1 = 2,     /* gemm_grouped_kernel<1, false> */
+    VGAN_GEMM_GROUPED_T256_V1_EPI = 3, /* gemm_grouped_kernel<1, true> */
+    VGAN_GEMM_GROUPED_KS16 = 4,        /* gemm_grouped_ks16_kernel: every problem on 16-wave 32 x 32 tiles (vector width 4) */
+    VGAN_GEMM_GROUPED_KS16_SPLIT = 5,  /* gemm_grouped_ks16_split_kernel: the same with the in-launch K split */
+    VGAN_GEMM_GROUPED_PATHS = 6
+};
+enum vgan_gemm_engine {
+    VGAN_GEMM_ENGINE_T64 = 0, /* 64 x 64 x 32 tiles (also VGAN_GEMM_NT_NT and every problem with splitk > 1) */
+    VGAN_GEMM_ENGINE_KS4 = 1, /* 32 x 32 tiles, 4 waves: k >= 128 and at most 512 such tiles */
+    VGAN_GEMM_ENGINE_KS16 = 2 /* 32 x 32 tiles, 16 waves: every problem of a KS16 launch */
+};
+int vgan_gemm_grouped_path(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras, const int32_t* kparts,
+                           int32_t* engine /* [count] */);
 int64_t vgan_gemm_grouped_ksplit_ws_bytes(const vgan_gemm_problem* problems, int count, const int32_t* kparts);
 int vgan_gemm_grouped_ksplit(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras,
                              const int32_t* kparts, void* ws, int64_t ws_bytes, vgan_stream_t stream);

@@ -347,32 +347,54 @@ static int64_t ksplit_need(const vgan_gemm_problem* problems, int count, const i
     return split_tiles == 0 ? 0 : ksplit_ticket_bytes(split_tiles) + slabs * kKSplitSlabBytes;
 }
 
-static int grouped_launch(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras, const int32_t* kparts, void* ws,
-                          int64_t ws_bytes, vgan_stream_t stream) {
-    VGAN_CHECK_ARG(problems && count >= 1 && count <= VGAN_GEMM_MAX_GROUP);
+// ---- dispatch: grouped_plan validates the arguments and fills the kernels' argument blocks; its return value names the launch
+// (enum vgan_gemm_grouped_path_code) or is < 0 where the entry points return VGAN_ERR_ARG.  It launches nothing and dereferences
+// no operand pointer.  grouped_launch switches on that value and the host-side query vgan_gemm_grouped_path returns it, so the
+// query and the launch cannot disagree.  check_ws: the in-launch K split's workspace is validated too (the query has none).
+#define VGAN_PLAN_CHECK(cond)                                                       \
+    do {                                                                            \
+        if (!(cond)) {                                                              \
+            ::vgan::set_error("%s:%d: bad argument: %s", __FILE__, __LINE__, #cond); \
+            return -VGAN_ERR_ARG;                                                   \
+        }                                                                           \
+    } while (0)
+
+struct GroupedPlan {
+    GroupedArgs g{};
+    GroupedExtras x{};
+    GroupedKSplit ks{};
+    int blocks = 0;      // workgroups of the launch, riders included
+    int slots = 0;       // tickets of the in-launch K split
+    int slab_bytes = 0;  // and its slab region
+};
+
+static int grouped_plan(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras, const int32_t* kparts,
+                        const void* ws, int64_t ws_bytes, bool check_ws, GroupedPlan& plan) {
+    VGAN_PLAN_CHECK(problems && count >= 1 && count <= VGAN_GEMM_MAX_GROUP);
     bool ksplit = false;
     for (int i = 0; i < count && kparts != nullptr; ++i) {
-        VGAN_CHECK_ARG(kparts[i] >= 1 && kparts[i] <= kKSplitMaxParts);
-        VGAN_CHECK_ARG(kparts[i] == 1 || problems[i].splitk <= 1);  // slabs of C for the caller, or the in-launch combine: not both
+        VGAN_PLAN_CHECK(kparts[i] >= 1 && kparts[i] <= kKSplitMaxParts);
+        VGAN_PLAN_CHECK(kparts[i] == 1 || problems[i].splitk <= 1);  // slabs of C for the caller, or the in-launch combine: not both
         ksplit = ksplit || kparts[i] > 1;
     }
     if (ksplit) {
         const int64_t need = ksplit_need(problems, count, kparts);
-        VGAN_CHECK_ARG(need > 0 && need < (1ll << 31) && ws != nullptr && aligned16(ws) && ws_bytes >= need);
+        VGAN_PLAN_CHECK(need > 0 && need < (1ll << 31));
+        if (check_ws) VGAN_PLAN_CHECK(ws != nullptr && aligned16(ws) && ws_bytes >= need);
     }
-    GroupedArgs g{};
-    GroupedExtras x{};
+    GroupedArgs& g = plan.g;
+    GroupedExtras& x = plan.x;
     g.count = count;
     bool vec = true, any_split = false;
     int tiles = 0;
     for (int i = 0; i < count; ++i) {
         const vgan_gemm_problem& q = problems[i];
-        VGAN_CHECK_ARG(q.a && q.b && q.c && q.m > 0 && q.n > 0 && q.k > 0 && q.ldc >= q.n);
-        VGAN_CHECK_ARG(q.kind == VGAN_GEMM_NN || q.kind == VGAN_GEMM_NT || q.kind == VGAN_GEMM_TN || q.kind == VGAN_GEMM_NT_NT);
+        VGAN_PLAN_CHECK(q.a && q.b && q.c && q.m > 0 && q.n > 0 && q.k > 0 && q.ldc >= q.n);
+        VGAN_PLAN_CHECK(q.kind == VGAN_GEMM_NN || q.kind == VGAN_GEMM_NT || q.kind == VGAN_GEMM_TN || q.kind == VGAN_GEMM_NT_NT);
         const bool two = q.kind == VGAN_GEMM_NT_NT;
-        VGAN_CHECK_ARG(q.lda >= (q.kind == VGAN_GEMM_TN ? q.m : q.k) && q.ldb >= ((q.kind == VGAN_GEMM_NT || two) ? q.k : q.n));
+        VGAN_PLAN_CHECK(q.lda >= (q.kind == VGAN_GEMM_TN ? q.m : q.k) && q.ldb >= ((q.kind == VGAN_GEMM_NT || two) ? q.k : q.n));
         if (two) {
-            VGAN_CHECK_ARG(q.d && q.scratch && q.k2 > 0 && q.ldd >= q.k2 && q.splitk <= 1 && aligned16(q.scratch));
+            VGAN_PLAN_CHECK(q.d && q.scratch && q.k2 > 0 && q.ldd >= q.k2 && q.splitk <= 1 && aligned16(q.scratch));
             vec = vec && (q.k2 % 4 == 0) && (q.ldd % 4 == 0) && aligned16(q.d);
             any_split = true;  // (keeps the launch on the 64 x 64 tile kernel, without the optimiser epilogue)
         }
@@ -392,7 +414,7 @@ static int grouped_launch(const vgan_gemm_problem* problems, int count, const vg
         g.split[i] = q.splitk > 1 ? q.splitk : 1;
         if (g.split[i] > 1) {
             g.kchunk[i] = ((q.k + g.split[i] - 1) / g.split[i] + QBK - 1) / QBK * QBK;
-            VGAN_CHECK_ARG(g.split[i] <= 64 && (long)(g.split[i] - 1) * g.kchunk[i] < q.k);  // every slice holds work
+            VGAN_PLAN_CHECK(g.split[i] <= 64 && (long)(g.split[i] - 1) * g.kchunk[i] < q.k);  // every slice holds work
             g.ks[i] = 0;
             any_split = true;
         }
@@ -403,14 +425,14 @@ static int grouped_launch(const vgan_gemm_problem* problems, int count, const vg
     if (extras != nullptr) {
         const vgan_grouped_extras& e = *extras;
         if (e.copy_src != nullptr) {
-            VGAN_CHECK_ARG(e.copy_dst && e.copy_count > 0);
+            VGAN_PLAN_CHECK(e.copy_dst && e.copy_count > 0);
             x.copy_src = e.copy_src;
             x.copy_dst = e.copy_dst;
             x.copy_count = (long)e.copy_count;
             x.copy_blocks = extra_grid(e.copy_count);
         }
         if (e.adadelta) {
-            VGAN_CHECK_ARG(e.p && e.sq_avg && e.acc_delta && !any_split);  // (the optimiser epilogue needs the whole product)
+            VGAN_PLAN_CHECK(e.p && e.sq_avg && e.acc_delta && !any_split);  // (the optimiser epilogue needs the whole product)
             epi = true;
             x.adadelta = 1;
             x.p = e.p; x.sq = e.sq_avg; x.acc = e.acc_delta;
@@ -418,19 +440,19 @@ static int grouped_launch(const vgan_gemm_problem* problems, int count, const vg
             const int nl = count + (e.g_extra != nullptr ? 1 : 0);
             for (int i = 0; i < nl; ++i) {
                 const vgan_adadelta_layer& L = e.layer[i];
-                VGAN_CHECK_ARG(L.w_packed && L.out > 0 && L.in > 0 && L.ldp >= L.in + 1 && L.off_w >= 0 && L.off_b >= 0);
-                if (i < count) VGAN_CHECK_ARG(problems[i].m >= L.out && problems[i].n >= L.in + 1);
+                VGAN_PLAN_CHECK(L.w_packed && L.out > 0 && L.in > 0 && L.ldp >= L.in + 1 && L.off_w >= 0 && L.off_b >= 0);
+                if (i < count) VGAN_PLAN_CHECK(problems[i].m >= L.out && problems[i].n >= L.in + 1);
                 x.layer[i] = L;
             }
             if (e.g_extra != nullptr) {
-                VGAN_CHECK_ARG(e.ld_extra >= e.layer[count].in + 1);
+                VGAN_PLAN_CHECK(e.ld_extra >= e.layer[count].in + 1);
                 x.g_extra = e.g_extra;
                 x.ld_extra = e.ld_extra;
                 x.extra_blocks = extra_grid((long)e.layer[count].out * (e.layer[count].in + 1));
             }
         }
         if (e.next_noise != nullptr) {
-            VGAN_CHECK_ARG(e.noise_rows > 0 && e.noise_cols > 0 && e.noise_ld >= e.noise_cols && e.noise_ones_col < e.noise_ld);
+            VGAN_PLAN_CHECK(e.noise_rows > 0 && e.noise_cols > 0 && e.noise_ld >= e.noise_cols && e.noise_ones_col < e.noise_ld);
             x.z = e.next_noise;
             x.zrows = e.noise_rows; x.zcols = e.noise_cols; x.zld = e.noise_ld; x.zones = e.noise_ones_col;
             x.seed = (unsigned long long)e.seed;
@@ -438,7 +460,7 @@ static int grouped_launch(const vgan_gemm_problem* problems, int count, const vg
             x.noise_blocks = extra_grid(((long)e.noise_rows * e.noise_cols + 3) / 4);
         }
         if (e.fold != nullptr) {
-            VGAN_CHECK_ARG(finalize_job_ok(*e.fold));
+            VGAN_PLAN_CHECK(finalize_job_ok(*e.fold));
             x.fold = *e.fold;
             x.fold_blocks = 1;
         }
@@ -451,9 +473,9 @@ static int grouped_launch(const vgan_gemm_problem* problems, int count, const vg
         t32 += ((problems[i].m + 31) / 32) * ((problems[i].n + 31) / 32);
     }
     const bool ks16 = vec && kmin >= 96 && t32 <= 256 && !epi && x.noise_blocks == 0 && !any_split;  // (copy and fold jobs ride in this variant too)
-    VGAN_CHECK_ARG(!ksplit || ks16);  // the in-launch K split exists for the 16-wave launch only
+    VGAN_PLAN_CHECK(!ksplit || ks16);  // the in-launch K split exists for the 16-wave launch only
     if (ks16) {
-        GroupedKSplit ks{};
+        GroupedKSplit& ks = plan.ks;
         int acc = 0, slots = 0, slab_bytes = 0;
         for (int i = 0; i < count; ++i) {
             const int tiles_i = ((problems[i].m + 31) / 32) * ((problems[i].n + 31) / 32);
@@ -471,23 +493,51 @@ static int grouped_launch(const vgan_gemm_problem* problems, int count, const vg
             }
         }
         for (int i = count; i <= VGAN_GEMM_MAX_GROUP; ++i) g.tile_start[i] = acc;
-        if (ksplit) {
-            ks.ws = KSplitWs{reinterpret_cast<float*>(static_cast<char*>(ws) + ksplit_ticket_bytes(slots)), static_cast<int*>(ws), slab_bytes};
-            hipLaunchKernelGGL(gemm_grouped_ks16_split_kernel, dim3(acc + surplus), dim3(1024), 0, (hipStream_t)stream, g, x, ks);
-        } else {
-            hipLaunchKernelGGL(gemm_grouped_ks16_kernel, dim3(acc + surplus), dim3(1024), 0, (hipStream_t)stream, g, x);
-        }
-        VGAN_CHECK_LAUNCH();
-        return VGAN_OK;
+        plan.blocks = acc + surplus;
+        plan.slots = slots;
+        plan.slab_bytes = slab_bytes;
+        return ksplit ? VGAN_GEMM_GROUPED_KS16_SPLIT : VGAN_GEMM_GROUPED_KS16;
     }
-    const dim3 grid(tiles + surplus), block(kBlock);
+    plan.blocks = tiles + surplus;
+    if (vec) return epi ? VGAN_GEMM_GROUPED_T256_V4_EPI : VGAN_GEMM_GROUPED_T256_V4;
+    return epi ? VGAN_GEMM_GROUPED_T256_V1_EPI : VGAN_GEMM_GROUPED_T256_V1;
+}
+
+static int grouped_launch(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras, const int32_t* kparts, void* ws,
+                          int64_t ws_bytes, vgan_stream_t stream) {
+    GroupedPlan plan;
+    const int path = grouped_plan(problems, count, extras, kparts, ws, ws_bytes, true, plan);
+    if (path < 0) return VGAN_ERR_ARG;
+    const GroupedArgs& g = plan.g;
+    const GroupedExtras& x = plan.x;
+    const dim3 grid(plan.blocks);
     hipStream_t st = (hipStream_t)stream;
-    if (vec && epi) hipLaunchKernelGGL((gemm_grouped_kernel<4, true>), grid, block, 0, st, g, x);
-    else if (vec) hipLaunchKernelGGL((gemm_grouped_kernel<4, false>), grid, block, 0, st, g, x);
-    else if (epi) hipLaunchKernelGGL((gemm_grouped_kernel<1, true>), grid, block, 0, st, g, x);
-    else hipLaunchKernelGGL((gemm_grouped_kernel<1, false>), grid, block, 0, st, g, x);
+    switch (path) {
+        case VGAN_GEMM_GROUPED_KS16_SPLIT:
+            plan.ks.ws = KSplitWs{reinterpret_cast<float*>(static_cast<char*>(ws) + ksplit_ticket_bytes(plan.slots)), static_cast<int*>(ws),
+                                  plan.slab_bytes};
+            hipLaunchKernelGGL(gemm_grouped_ks16_split_kernel, grid, dim3(1024), 0, st, g, x, plan.ks);
+            break;
+        case VGAN_GEMM_GROUPED_KS16: hipLaunchKernelGGL(gemm_grouped_ks16_kernel, grid, dim3(1024), 0, st, g, x); break;
+        case VGAN_GEMM_GROUPED_T256_V4_EPI: hipLaunchKernelGGL((gemm_grouped_kernel<4, true>), grid, dim3(kBlock), 0, st, g, x); break;
+        case VGAN_GEMM_GROUPED_T256_V4: hipLaunchKernelGGL((gemm_grouped_kernel<4, false>), grid, dim3(kBlock), 0, st, g, x); break;
+        case VGAN_GEMM_GROUPED_T256_V1_EPI: hipLaunchKernelGGL((gemm_grouped_kernel<1, true>), grid, dim3(kBlock), 0, st, g, x); break;
+        default: hipLaunchKernelGGL((gemm_grouped_kernel<1, false>), grid, dim3(kBlock), 0, st, g, x); break;  // VGAN_GEMM_GROUPED_T256_V1
+    }
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
+}
+
+// per problem: the tile engine (enum vgan_gemm_engine) the launch named by the return value runs it on
+extern "C" int vgan_gemm_grouped_path(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras, const int32_t* kparts,
+                                      int32_t* engine) {
+    GroupedPlan plan;
+    const int path = grouped_plan(problems, count, extras, kparts, nullptr, 0, false, plan);
+    if (path < 0) return path;
+    const bool ks16 = path == VGAN_GEMM_GROUPED_KS16 || path == VGAN_GEMM_GROUPED_KS16_SPLIT;
+    for (int i = 0; i < count && engine != nullptr; ++i)
+        engine[i] = ks16 ? VGAN_GEMM_ENGINE_KS16 : plan.g.ks[i] ? VGAN_GEMM_ENGINE_KS4 : VGAN_GEMM_ENGINE_T64;
+    return path;
 }
 
 extern "C" int vgan_gemm_grouped_ex(const vgan_gemm_problem* problems, int count, const vgan_grouped_extras* extras,

@@ -218,83 +218,145 @@ static inline dim3 grid_for(int rows, int cols) { return dim3((cols + LBN - 1) /
 
 using namespace vgan;
 
+// ---- dispatch: every entry point takes its kernel from a *_plan function, and the host-side vgan_*_path queries return
+// the very same function's value -- the query and the launch cannot disagree.  A plan validates, launches nothing and
+// dereferences nothing (only nullness and alignment of the pointers are looked at); < 0: the entry point's VGAN_ERR_ARG.
+#define VGAN_PLAN_CHECK(cond)                                                       \
+    do {                                                                            \
+        if (!(cond)) {                                                              \
+            ::vgan::set_error("%s:%d: bad argument: %s", __FILE__, __LINE__, #cond); \
+            return -VGAN_ERR_ARG;                                                   \
+        }                                                                           \
+    } while (0)
+
+static int linear_forward_plan(const float* x, int ldx, int x_nslabs, int64_t x_slab_stride, const float* W, int ldw, const float* y,
+                               int ldy, int n, int in, int out) {
+    VGAN_PLAN_CHECK(x && W && y && n > 0 && in > 0 && out > 0 && ldx >= in && ldw >= in && ldy >= out && x_nslabs >= 1);
+    const bool vec = (in % 4 == 0) && (ldx % 4 == 0) && (ldw % 4 == 0) && aligned16(x) && aligned16(W) && (x_slab_stride % 4 == 0);
+    if (x_nslabs == 1 && use_ks(n, out, in))  // narrow output, long contraction
+        return vec && in >= 512 ? VGAN_LINEAR_FORWARD_KS16_V4 : vec ? VGAN_LINEAR_FORWARD_KS4_V4 : VGAN_LINEAR_FORWARD_KS4_V1;
+    if (x_nslabs > 1) return vec ? VGAN_LINEAR_FORWARD_T64_V4_SLABS : VGAN_LINEAR_FORWARD_T64_V1_SLABS;
+    return vec ? VGAN_LINEAR_FORWARD_T64_V4 : VGAN_LINEAR_FORWARD_T64_V1;
+}
+
+extern "C" int vgan_linear_forward_path(const float* x, int ldx, int x_nslabs, int64_t x_slab_stride, const float* W, int ldw,
+                                        const float* b, const float* y, int ldy, int n, int in, int out) {
+    (void)b;  // the bias never changes the kernel
+    return linear_forward_plan(x, ldx, x_nslabs, x_slab_stride, W, ldw, y, ldy, n, in, out);
+}
+
 extern "C" int vgan_linear_forward(const float* x, int ldx, int x_nslabs, int64_t x_slab_stride, const float* W, int ldw,
                                    const float* b, float* y, int ldy, int n, int in, int out, vgan_stream_t stream) {
-    VGAN_CHECK_ARG(x && W && y && n > 0 && in > 0 && out > 0 && ldx >= in && ldw >= in && ldy >= out && x_nslabs >= 1);
+    const int path = linear_forward_plan(x, ldx, x_nslabs, x_slab_stride, W, ldw, y, ldy, n, in, out);
+    if (path < 0) return VGAN_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = (in % 4 == 0) && (ldx % 4 == 0) && (ldw % 4 == 0) && aligned16(x) && aligned16(W) && (x_slab_stride % 4 == 0);
     const long xs = (long)x_slab_stride;
-    if (x_nslabs == 1 && use_ks(n, out, in)) {  // narrow output, long contraction
-        dim3 g((out + 31) / 32, (n + 31) / 32);
-        if (vec && in >= 512)
-            hipLaunchKernelGGL((linear_fwd_ks_kernel<4, 16>), g, dim3(1024), 0, s, x, ldx, W, ldw, b, y, ldy, n, in, out);
-        else if (vec)
-            hipLaunchKernelGGL((linear_fwd_ks_kernel<4, 4>), g, dim3(kBlock), 0, s, x, ldx, W, ldw, b, y, ldy, n, in, out);
-        else
-            hipLaunchKernelGGL((linear_fwd_ks_kernel<1, 4>), g, dim3(kBlock), 0, s, x, ldx, W, ldw, b, y, ldy, n, in, out);
-        VGAN_CHECK_LAUNCH();
-        return VGAN_OK;
-    }
+    const dim3 g((out + 31) / 32, (n + 31) / 32);
 #define VGAN_FWD(V, S) hipLaunchKernelGGL((linear_fwd_kernel<V, S>), grid_for(n, out), dim3(kBlock), 0, s, x, ldx, W, ldw, b, y, ldy, n, in, out, x_nslabs, xs)
-    if (x_nslabs > 1) { if (vec) VGAN_FWD(4, true); else VGAN_FWD(1, true); }
-    else { if (vec) VGAN_FWD(4, false); else VGAN_FWD(1, false); }
+#define VGAN_FWD_KS(V, NW) hipLaunchKernelGGL((linear_fwd_ks_kernel<V, NW>), g, dim3(64 * NW), 0, s, x, ldx, W, ldw, b, y, ldy, n, in, out)
+    switch (path) {
+        case VGAN_LINEAR_FORWARD_KS16_V4: VGAN_FWD_KS(4, 16); break;
+        case VGAN_LINEAR_FORWARD_KS4_V4: VGAN_FWD_KS(4, 4); break;
+        case VGAN_LINEAR_FORWARD_KS4_V1: VGAN_FWD_KS(1, 4); break;
+        case VGAN_LINEAR_FORWARD_T64_V4_SLABS: VGAN_FWD(4, true); break;
+        case VGAN_LINEAR_FORWARD_T64_V1_SLABS: VGAN_FWD(1, true); break;
+        case VGAN_LINEAR_FORWARD_T64_V4: VGAN_FWD(4, false); break;
+        default: VGAN_FWD(1, false); break;  // VGAN_LINEAR_FORWARD_T64_V1
+    }
 #undef VGAN_FWD
+#undef VGAN_FWD_KS
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }
 
-extern "C" int vgan_linear_backward_input(const float* dy, int lddy, const float* W, int ldw, float* dx, int lddx, int n, int in,
-                                          int out, vgan_stream_t stream) {
-    VGAN_CHECK_ARG(dy && W && dx && n > 0 && in > 0 && out > 0 && lddy >= out && ldw >= in && lddx >= in);
-    hipStream_t s = (hipStream_t)stream;
+static int linear_backward_input_plan(const float* dy, int lddy, const float* W, int ldw, const float* dx, int lddx, int n, int in,
+                                      int out) {
+    VGAN_PLAN_CHECK(dy && W && dx && n > 0 && in > 0 && out > 0 && lddy >= out && ldw >= in && lddx >= in);
     const bool vec_but_in = (out % 4 == 0) && (lddy % 4 == 0) && (ldw % 4 == 0) && aligned16(dy) && aligned16(W);
     const bool vec = vec_but_in && (in % 4 == 0);
     if (use_ks(n, in, out)) {
-        dim3 g((in + 31) / 32, (n + 31) / 32);
         const int in4 = (in + 3) / 4 * 4;  // W's rows are ldw long: a ragged last group of 4 columns is still inside the row
-        if (vec_but_in && ldw >= in4)
+        return vec_but_in && ldw >= in4 ? VGAN_LINEAR_BACKWARD_INPUT_KS4_V4 : VGAN_LINEAR_BACKWARD_INPUT_KS4_V1;
+    }
+    return vec ? VGAN_LINEAR_BACKWARD_INPUT_T64_V4 : VGAN_LINEAR_BACKWARD_INPUT_T64_V1;
+}
+
+extern "C" int vgan_linear_backward_input_path(const float* dy, int lddy, const float* W, int ldw, const float* dx, int lddx, int n,
+                                               int in, int out) {
+    return linear_backward_input_plan(dy, lddy, W, ldw, dx, lddx, n, in, out);
+}
+
+extern "C" int vgan_linear_backward_input(const float* dy, int lddy, const float* W, int ldw, float* dx, int lddx, int n, int in,
+                                          int out, vgan_stream_t stream) {
+    const int path = linear_backward_input_plan(dy, lddy, W, ldw, dx, lddx, n, in, out);
+    if (path < 0) return VGAN_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g((in + 31) / 32, (n + 31) / 32);
+    const int in4 = (in + 3) / 4 * 4;
+    switch (path) {
+        case VGAN_LINEAR_BACKWARD_INPUT_KS4_V4:
             hipLaunchKernelGGL(linear_bwd_input_ks_kernel<4>, g, dim3(kBlock), 0, s, dy, lddy, W, ldw, dx, lddx, n, in, out, in4);
-        else
+            break;
+        case VGAN_LINEAR_BACKWARD_INPUT_KS4_V1:
             hipLaunchKernelGGL(linear_bwd_input_ks_kernel<1>, g, dim3(kBlock), 0, s, dy, lddy, W, ldw, dx, lddx, n, in, out, in);
-    } else if (vec)
-        hipLaunchKernelGGL(linear_bwd_input_kernel<4>, grid_for(n, in), dim3(kBlock), 0, s, dy, lddy, W, ldw, dx, lddx, n, in, out);
-    else
-        hipLaunchKernelGGL(linear_bwd_input_kernel<1>, grid_for(n, in), dim3(kBlock), 0, s, dy, lddy, W, ldw, dx, lddx, n, in, out);
+            break;
+        case VGAN_LINEAR_BACKWARD_INPUT_T64_V4:
+            hipLaunchKernelGGL(linear_bwd_input_kernel<4>, grid_for(n, in), dim3(kBlock), 0, s, dy, lddy, W, ldw, dx, lddx, n, in, out);
+            break;
+        default:  // VGAN_LINEAR_BACKWARD_INPUT_T64_V1
+            hipLaunchKernelGGL(linear_bwd_input_kernel<1>, grid_for(n, in), dim3(kBlock), 0, s, dy, lddy, W, ldw, dx, lddx, n, in, out);
+            break;
+    }
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
+}
+
+static int linear_backward_params_plan(const float* dy, int lddy, const float* x, int ldx, int x_nslabs, int64_t x_slab_stride,
+                                       const float* dW, int lddw, const float* db, int n, int in, int out, int splits,
+                                       int64_t slab_stride) {
+    VGAN_PLAN_CHECK(dy && x && dW && n > 0 && in > 0 && out > 0 && lddy >= out && ldx >= in && lddw >= in && x_nslabs >= 1);
+    VGAN_PLAN_CHECK(splits >= 1 && splits <= 64 && (splits == 1 || slab_stride > 0));
+    const bool vec = (out % 4 == 0) && (lddy % 4 == 0) && (in % 4 == 0) && (ldx % 4 == 0) && aligned16(dy) && aligned16(x) &&
+                     (x_slab_stride % 4 == 0);
+    if (splits == 1 && x_nslabs == 1 && db == nullptr && use_ks_params(out, in, n))  // tall-skinny: no slabs needed at all
+        // long contraction: 16 waves per workgroup (see GemmTileKS)
+        return vec && n >= 256 ? VGAN_LINEAR_BACKWARD_PARAMS_KS16_V4 : vec ? VGAN_LINEAR_BACKWARD_PARAMS_KS4_V4 : VGAN_LINEAR_BACKWARD_PARAMS_KS4_V1;
+    if (x_nslabs > 1) return vec ? VGAN_LINEAR_BACKWARD_PARAMS_T64_V4_SLABS : VGAN_LINEAR_BACKWARD_PARAMS_T64_V1_SLABS;
+    return vec ? VGAN_LINEAR_BACKWARD_PARAMS_T64_V4 : VGAN_LINEAR_BACKWARD_PARAMS_T64_V1;
+}
+
+extern "C" int vgan_linear_backward_params_path(const float* dy, int lddy, const float* x, int ldx, int x_nslabs, int64_t x_slab_stride,
+                                                const float* dW, int lddw, const float* db, int n, int in, int out, int splits,
+                                                int64_t slab_stride) {
+    return linear_backward_params_plan(dy, lddy, x, ldx, x_nslabs, x_slab_stride, dW, lddw, db, n, in, out, splits, slab_stride);
 }
 
 extern "C" int vgan_linear_backward_params(const float* dy, int lddy, const float* x, int ldx, int x_nslabs, int64_t x_slab_stride,
                                            float* dW, int lddw, float* db, int n, int in, int out, int splits, int64_t slab_stride,
                                            vgan_stream_t stream) {
-    VGAN_CHECK_ARG(dy && x && dW && n > 0 && in > 0 && out > 0 && lddy >= out && ldx >= in && lddw >= in && x_nslabs >= 1);
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 64 && (splits == 1 || slab_stride > 0));
+    const int path = linear_backward_params_plan(dy, lddy, x, ldx, x_nslabs, x_slab_stride, dW, lddw, db, n, in, out, splits, slab_stride);
+    if (path < 0) return VGAN_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     // row slices are multiples of 4 rows so that every slice keeps the 16-byte alignment of the vector path
     int kchunk = (n + splits - 1) / splits;
     kchunk = (kchunk + 3) / 4 * 4;
-    const int nz = (n + kchunk - 1) / kchunk;
-    const bool vec = (out % 4 == 0) && (lddy % 4 == 0) && (in % 4 == 0) && (ldx % 4 == 0) && aligned16(dy) && aligned16(x) &&
-                     (x_slab_stride % 4 == 0);
     dim3 grid = grid_for(out, in);
-    grid.z = splits;  // slices beyond nz see klen <= 0 and write zeros, so the reducer may always sum `splits` slabs
-    (void)nz;
+    grid.z = splits;  // slices past the last row see klen <= 0 and write zeros, so the reducer may always sum `splits` slabs
     const long xs = (long)x_slab_stride;
-    if (splits == 1 && x_nslabs == 1 && db == nullptr && use_ks_params(out, in, n)) {  // tall-skinny: no slabs needed at all
-        dim3 g((in + 31) / 32, (out + 31) / 32);
-        if (vec && n >= 256)  // long contraction: 16 waves per workgroup (see GemmTileKS)
-            hipLaunchKernelGGL((linear_bwd_params_ks_kernel<4, 16>), g, dim3(1024), 0, s, dy, lddy, x, ldx, dW, lddw, n, in, out);
-        else if (vec)
-            hipLaunchKernelGGL((linear_bwd_params_ks_kernel<4, 4>), g, dim3(kBlock), 0, s, dy, lddy, x, ldx, dW, lddw, n, in, out);
-        else
-            hipLaunchKernelGGL((linear_bwd_params_ks_kernel<1, 4>), g, dim3(kBlock), 0, s, dy, lddy, x, ldx, dW, lddw, n, in, out);
-        VGAN_CHECK_LAUNCH();
-        return VGAN_OK;
-    }
+    const dim3 g((in + 31) / 32, (out + 31) / 32);
 #define VGAN_BWP(V, S) hipLaunchKernelGGL((linear_bwd_params_kernel<V, S>), grid, dim3(kBlock), 0, s, dy, lddy, x, ldx, dW, lddw, db, n, in, out, kchunk, (long)slab_stride, x_nslabs, xs)
-    if (x_nslabs > 1) { if (vec) VGAN_BWP(4, true); else VGAN_BWP(1, true); }
-    else { if (vec) VGAN_BWP(4, false); else VGAN_BWP(1, false); }
+#define VGAN_BWP_KS(V, NW) hipLaunchKernelGGL((linear_bwd_params_ks_kernel<V, NW>), g, dim3(64 * NW), 0, s, dy, lddy, x, ldx, dW, lddw, n, in, out)
+    switch (path) {
+        case VGAN_LINEAR_BACKWARD_PARAMS_KS16_V4: VGAN_BWP_KS(4, 16); break;
+        case VGAN_LINEAR_BACKWARD_PARAMS_KS4_V4: VGAN_BWP_KS(4, 4); break;
+        case VGAN_LINEAR_BACKWARD_PARAMS_KS4_V1: VGAN_BWP_KS(1, 4); break;
+        case VGAN_LINEAR_BACKWARD_PARAMS_T64_V4_SLABS: VGAN_BWP(4, true); break;
+        case VGAN_LINEAR_BACKWARD_PARAMS_T64_V1_SLABS: VGAN_BWP(1, true); break;
+        case VGAN_LINEAR_BACKWARD_PARAMS_T64_V4: VGAN_BWP(4, false); break;
+        default: VGAN_BWP(1, false); break;  // VGAN_LINEAR_BACKWARD_PARAMS_T64_V1
+    }
 #undef VGAN_BWP
+#undef VGAN_BWP_KS
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }

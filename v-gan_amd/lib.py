@@ -60,6 +60,13 @@ class GroupedExtras(ctypes.Structure):
 GEMM_NN, GEMM_NT, GEMM_TN, GEMM_NT_NT = 0, 1, 2, 3
 GEMM_MAX_GROUP = 4
 
+# the codes of the host-side path queries (the enums of include/vgan_hip.h, in order; tests/test_gemm_kernels_cpu.py compares)
+LINEAR_FORWARD_PATHS = ("T64_V4", "T64_V1", "T64_V4_SLABS", "T64_V1_SLABS", "KS4_V4", "KS4_V1", "KS16_V4")
+LINEAR_BACKWARD_INPUT_PATHS = ("T64_V4", "T64_V1", "KS4_V4", "KS4_V1")
+LINEAR_BACKWARD_PARAMS_PATHS = ("T64_V4", "T64_V1", "T64_V4_SLABS", "T64_V1_SLABS", "KS4_V4", "KS4_V1", "KS16_V4")
+GEMM_GROUPED_PATHS = ("T256_V4", "T256_V4_EPI", "T256_V1", "T256_V1_EPI", "KS16", "KS16_SPLIT")
+GEMM_ENGINES = ("T64", "KS4", "KS16")
+
 # name -> (restype, argtypes); must list every function declared in include/vgan_hip.h
 SIGNATURES = {
     "vgan_abi_version": (_i, []),
@@ -71,6 +78,9 @@ SIGNATURES = {
     "vgan_linear_backward_params_ksplit": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "vgan_linear_backward_params_xx_supported": (_i, [_i, _i, _i]),
     "vgan_linear_backward_params_xx": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p]),
+    "vgan_linear_forward_path": (_i, [_p, _i, _i, _i64, _p, _i, _p, _p, _i, _i, _i, _i]),
+    "vgan_linear_backward_input_path": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i]),
+    "vgan_linear_backward_params_path": (_i, [_p, _i, _p, _i, _i, _i64, _p, _i, _p, _i, _i, _i, _i, _i64]),
     "vgan_reduce_slabs": (_i, [_p, _i64, _i, _p, _i64, _p]),
     "vgan_mask_project_forward": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _i, _p, _p]),
     "vgan_col_mean": (_i, [_p, _i, _i, _i, _p, _p]),
@@ -107,6 +117,7 @@ SIGNATURES = {
     "vgan_adadelta_step_packed": (_i, [_p, _p, _p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _p, _i, _i, _i, _i, _u64, _p, _p]),
     "vgan_gemm_grouped": (_i, [_p, _i, _p]),
     "vgan_gemm_grouped_ex": (_i, [_p, _i, _p, _p]),
+    "vgan_gemm_grouped_path": (_i, [_p, _i, _p, _p, _p]),
     "vgan_gemm_grouped_ksplit_ws_bytes": (_i64, [_p, _i, _p]),
     "vgan_gemm_grouped_ksplit": (_i, [_p, _i, _p, _p, _p, _i64, _p]),
     "vgan_mask_project_forward_bf3": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
@@ -201,6 +212,13 @@ def load():
         raise VganHipError(f"ABI mismatch: library {lib.vgan_abi_version()} vs binding {ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def path_name(names, code, what):
+    """The name of a path query's code; a negative code is the entry point's VGAN_ERR_ARG."""
+    if code < 0:
+        raise VganHipError(f"{what}: bad arguments: " + load().vgan_last_error().decode(errors="replace"))
+    return names[code]
 
 
 def check(rc, what=""):

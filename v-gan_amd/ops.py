@@ -75,6 +75,13 @@ class HipOps:
         _lib.check(self.lib.vgan_linear_forward(_ptr(x), x.stride(0), int(x_nslabs), int(x_slab_stride), _ptr(W), W.stride(0),
                                                 _ptr(b), _ptr(y), y.stride(0), n, kin, out, self._stream()), "vgan_linear_forward")
 
+    def linear_forward_path(self, x, W, b, y, x_nslabs=1, x_slab_stride=0):
+        """The kernel linear_forward launches for exactly these arguments (lib.LINEAR_FORWARD_PATHS; host-side query)."""
+        n, kin = x.shape
+        return _lib.path_name(_lib.LINEAR_FORWARD_PATHS, self.lib.vgan_linear_forward_path(
+            _ptr(x), x.stride(0), int(x_nslabs), int(x_slab_stride), _ptr(W), W.stride(0), _ptr(b), _ptr(y), y.stride(0), n, kin,
+            W.shape[0]), "vgan_linear_forward_path")
+
     def linear_backward_input(self, dy, W, dx):
         _mat(dy, "dy"), _mat(W, "W"), _mat(dx, "dx")
         n, out = dy.shape
@@ -82,6 +89,12 @@ class HipOps:
         assert W.shape[0] == out and dx.shape == (n, kin)
         _lib.check(self.lib.vgan_linear_backward_input(_ptr(dy), dy.stride(0), _ptr(W), W.stride(0), _ptr(dx), dx.stride(0),
                                                        n, kin, out, self._stream()), "vgan_linear_backward_input")
+
+    def linear_backward_input_path(self, dy, W, dx):
+        """The kernel linear_backward_input launches for exactly these arguments (lib.LINEAR_BACKWARD_INPUT_PATHS)."""
+        n, out = dy.shape
+        return _lib.path_name(_lib.LINEAR_BACKWARD_INPUT_PATHS, self.lib.vgan_linear_backward_input_path(
+            _ptr(dy), dy.stride(0), _ptr(W), W.stride(0), _ptr(dx), dx.stride(0), n, W.shape[1], out), "vgan_linear_backward_input_path")
 
     def linear_backward_params(self, dy, x, dW, db, splits=1, slab_stride=0, x_nslabs=1, x_slab_stride=0):
         """splits > 1: dW/db are slab 0 of `splits` slabs `slab_stride` elements apart (partial sums).
@@ -93,6 +106,13 @@ class HipOps:
         _lib.check(self.lib.vgan_linear_backward_params(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), int(x_nslabs), int(x_slab_stride),
                                                         _ptr(dW), dW.stride(0), _ptr(db), n, kin, out, int(splits), int(slab_stride),
                                                         self._stream()), "vgan_linear_backward_params")
+
+    def linear_backward_params_path(self, dy, x, dW, db, splits=1, slab_stride=0, x_nslabs=1, x_slab_stride=0):
+        """The kernel linear_backward_params launches for exactly these arguments (lib.LINEAR_BACKWARD_PARAMS_PATHS)."""
+        n, out = dy.shape
+        return _lib.path_name(_lib.LINEAR_BACKWARD_PARAMS_PATHS, self.lib.vgan_linear_backward_params_path(
+            _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), int(x_nslabs), int(x_slab_stride), _ptr(dW), dW.stride(0), _ptr(db), n,
+            x.shape[1], out, int(splits), int(slab_stride)), "vgan_linear_backward_params_path")
 
     def linear_backward_params_ksplit_ws_bytes(self, kin, out, parts):
         return int(self.lib.vgan_linear_backward_params_ksplit_ws_bytes(int(kin), int(out), int(parts)))
@@ -467,6 +487,19 @@ class HipOps:
                                                          self._stream()), "vgan_gemm_grouped_ksplit")
             return
         _lib.check(self.lib.vgan_gemm_grouped_ex(arr, len(problems), ctypes.byref(x), self._stream()), "vgan_gemm_grouped_ex")
+
+    def gemm_grouped_path(self, problems, copy=None, adadelta=None, noise=None, fold=None, kparts=None):
+        """(launch, [engine per problem]) gemm_grouped makes for exactly these arguments (lib.GEMM_GROUPED_PATHS /
+        lib.GEMM_ENGINES; host-side query)."""
+        if kparts is not None and all(int(v) == 1 for v in kparts):
+            kparts = None
+        arr = self._gemm_problems(problems)
+        plain = copy is None and adadelta is None and noise is None and fold is None
+        x = None if plain else ctypes.byref(self._grouped_extras(len(problems), copy, adadelta, noise, fold))
+        kp = None if kparts is None else (ctypes.c_int32 * len(problems))(*[int(v) for v in kparts])
+        engine = (ctypes.c_int32 * len(problems))()
+        code = self.lib.vgan_gemm_grouped_path(arr, len(problems), x, kp, engine)
+        return _lib.path_name(_lib.GEMM_GROUPED_PATHS, code, "vgan_gemm_grouped_path"), [_lib.GEMM_ENGINES[e] for e in engine]
 
     def gemm_grouped_ksplit_ws_bytes(self, problems, kparts):
         kp = (ctypes.c_int32 * len(problems))(*[int(v) for v in kparts])
