@@ -711,6 +711,26 @@ int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out,
  *   (float64 [S]) = the smallest score of row s that is not NaN, 0 if every score is NaN; n_degenerate[s] (int32 [S]) =
  *   the number of NaN scores.  fit == 0: score_floor is read, n_degenerate is not touched (may be NULL).  Then every NaN
  *   of row s becomes (float)score_floor[s].  The call knows no subspace table: row s is whatever the caller stored there.
+ * vgan_outlier_cof_chain: the average chaining distance of the connectivity-based outlier factor (COF: Tang, Chen, Fu, Cheung
+ *   2002; pyod's COF) from the refined lists idx [count, nq, k] of vgan_outlier_refine and the raw rows Xq / Xr.  For chunk
+ *   subspace s and query row q let o_0 = q and o_1 .. o_k the listed reference rows in list order.  d2(a, b) = sum_{f in F_s}
+ *   (x_a[f] - x_b[f])^2 in float64 from the raw float32 values, features ascending, differences per feature (never
+ *   n_a + n_b - 2 G_ab).  chain VGAN_OUTLIER_COF_CHAIN_SBN (the paper's set-based nearest path): the set starts as {o_0};
+ *   step i = 1 .. k adds the remaining point with the smallest (d2 to the set, list position), where the d2 of a point to
+ *   the set is its minimum d2 over the set's members, and e_i = sqrt of that d2; the comparisons are made on d2 and a tie
+ *   goes to the lower list position.  VGAN_OUTLIER_COF_CHAIN_RANK: e_i = sqrt(min_{j < i} d2(o_i, o_j)), the points in list
+ *   order.  ac_out[z, q] (float64 [count, nq]) = sum_{i = 1 .. k} w_i e_i with w_i = 2 (k + 1 - i) / (k (k + 1)), float64,
+ *   i ascending, no atomics: the lists decide the bits.  An entry outside [0, nr) counts as a point at the origin (the
+ *   lists of vgan_outlier_refine hold none).  1 <= k <= VGAN_OUTLIER_MAX_K, nr >= k.
+ * vgan_outlier_cof_score: score[row, q] = ac_q[z, q] k / sum_{i = 1 .. k} ac_ref[z, idx[z, q, i]] (ac_q float64 [count, nq],
+ *   ac_ref float64 [count, nr]: the chaining distances of the reference rows at fit, self excluded), float64, i
+ *   ascending, stored as float32 (row and ld_score as for vgan_outlier_score); a value beyond the float32 range is stored
+ *   as FLT_MAX.  A zero denominator: the score is exactly 1 where ac_q is 0 too (a point mass among point masses: not
+ *   degenerate); where ac_q > 0 the row is DEGENERATE and its score is stored as NaN, for vgan_outlier_cof_ceiling.
+ * vgan_outlier_cof_ceiling: vgan_outlier_abod_floor with a maximum.  fit != 0: score_ceiling[s] (float64 [S]) = the largest
+ *   score of row s that is not NaN, 1 if every score is NaN; n_degenerate[s] (int32 [S]) = the number of NaN scores.
+ *   fit == 0: score_ceiling is read, n_degenerate is not touched (may be NULL).  Then every NaN of row s becomes
+ *   (float)score_ceiling[s].
  * ------------------------------------------------------------------------------------------- */
 #define VGAN_OUTLIER_MAX_K 32
 #define VGAN_OUTLIER_ENGINE_EXACT 0
@@ -744,6 +764,15 @@ int vgan_outlier_abod(const float* Xq, int ldq, int nq, const float* Xr, int ldr
                       const int32_t* score_row, int ld_score, vgan_stream_t stream);
 int vgan_outlier_abod_floor(float* score, int ld, int S, int n, int fit, double* score_floor, int32_t* n_degenerate,
                             vgan_stream_t stream);
+#define VGAN_OUTLIER_COF_CHAIN_SBN 0
+#define VGAN_OUTLIER_COF_CHAIN_RANK 1
+int vgan_outlier_cof_chain(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
+                           const int32_t* feat_off, int first, int count, const int32_t* idx, int k, int chain,
+                           double* ac_out, vgan_stream_t stream);
+int vgan_outlier_cof_score(const double* ac_q, int nq, const double* ac_ref, int nr, const int32_t* idx, int k, int count,
+                           float* score, const int32_t* score_row, int ld_score, vgan_stream_t stream);
+int vgan_outlier_cof_ceiling(float* score, int ld, int S, int n, int fit, double* score_ceiling, int32_t* n_degenerate,
+                             vgan_stream_t stream);
 #define VGAN_OUTLIER_NORM_ZSCORE 1
 #define VGAN_OUTLIER_NORM_ROBUST 2
 #define VGAN_OUTLIER_NORM_MINMAX 3

@@ -19,6 +19,13 @@ difference of the two paths' ensemble scores.
     multiply-add rate of (b) from n sum_s k d_s 4 B and n sum_s k^2 d_s multiply-adds (the kernel pads k to 8, 16 or 32
     and forms the whole k x k matrix: the executed count is given as well).  --no-baselines leaves the torch path out
     (for a run under a profiler), --shape d,n,S picks one shape.
+  --method cof: connectivity-based scores (vgan_amd.SubspaceCOF, the set-based nearest chain) at k = 10 and 32 on the shapes
+    of the ABOD leg: (a) its fit against the kNN fit with the same k on the same subspaces (cof_over_knn: what the chain,
+    the ratio and the ceiling add to the neighbour search); (b) the chain launches alone on the resident neighbour lists
+    against a torch baseline handed the same lists (gather, float64 torch.cdist from the differences, k vectorised arg-min
+    steps), with the largest relative difference of the two chaining distances; (c) the gather bandwidth and the float64
+    multiply-add rate of (b), nominal (k + 1)^2 and executed (8 T)^2 + 1 per row and feature.  --no-baselines and --shape
+    as for abod.
   --method ecod: empirical-CDF scores (vgan_amd.SubspaceECOD, aggregate "dimension"): fit and decision_function (the
     training rows as queries) against (a) a float64 torch restatement on the same GPU (torch.sort, torch.searchsorted,
     the terms, one float64 matmul with the mask) and (b) numpy on the host (sort and searchsorted per feature, then a loop
@@ -340,6 +347,82 @@ def run_abod(d, n, count, k, reps, baselines=True):
         row.update({"torch_s": round(t_base, 5), "torch_reps_s": tb, "launch_speedup_vs_torch": round(t_base / t_launch, 2),
                     "max_rel_diff_vs_torch": float(rel.max()) if rel.numel() else 0.0,
                     "nan_rows_agree": bool((torch.isnan(per) == torch.isnan(ref)).all())})
+    return row
+
+
+def baseline_cof(X, feats, idx, block=2048):
+    """torch on the same GPU from the same neighbour lists idx [n, k] of one subspace: the average chaining distance of the
+    set-based nearest path, float64 [n].  The pairwise distances come from the differences (no Gram form)."""
+    n, k = idx.shape
+    Xs = X[:, feats].double()
+    out = torch.empty(n, dtype=torch.float64, device=X.device)
+    w = torch.tensor([2.0 * (k + 1 - i) / (k * (k + 1)) for i in range(1, k + 1)], dtype=torch.float64, device=X.device)
+    for q0 in range(0, n, block):
+        P = torch.cat([Xs[q0:q0 + block, None, :], Xs[idx[q0:q0 + block].long()]], dim=1)
+        D2 = torch.cdist(P, P, compute_mode="donot_use_mm_for_euclid_dist") ** 2
+        rows = torch.arange(P.shape[0], device=X.device)
+        dist = D2[:, 0, 1:].clone()
+        taken = torch.zeros_like(dist, dtype=torch.bool)
+        ac = torch.zeros(P.shape[0], dtype=torch.float64, device=X.device)
+        for i in range(k):
+            m, j = dist.masked_fill(taken, float("inf")).min(dim=1)
+            ac += w[i] * m.sqrt()
+            taken[rows, j] = True
+            dist = torch.minimum(dist, D2[rows, j + 1, 1:])
+        out[q0:q0 + block] = ac
+    return out
+
+
+def run_cof(d, n, count, k, reps, baselines=True):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    cof = vgan_amd.SubspaceCOF(m, p, n_neighbors=k)
+    knn = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=k)
+    t_cof, tc = timed(lambda: cof.fit(Xd), reps)
+    t_knn, tk = timed(lambda: knn.fit(Xd), reps)
+    # the launches alone, on the resident lists of the fit
+    lists = [(first, cnt, idx) for first, cnt, idx, _ in cof._neighbors(None)]
+    ac = torch.empty(S, n, dtype=torch.float64, device="cuda")
+    per = torch.empty(S, n, dtype=torch.float32, device="cuda")
+
+    def chain_launches():
+        for first, cnt, idx in lists:
+            cof.ops.outlier_cof_chain(Xd, Xd, cof._table, first, cnt, idx, k, 0, ac[first:first + cnt])
+
+    def score_launches():
+        for first, cnt, idx in lists:
+            cof.ops.outlier_cof_score(ac[first:first + cnt], ac[first:first + cnt], idx, k, per, cof._rows[first:first + cnt])
+
+    t_launch, tl = timed(chain_launches, max(reps, 5))
+    t_score, _ = timed(score_launches, max(reps, 5))
+    kp = 8 if k <= 8 else 16 if k <= 16 else 32
+    gather_bytes = 4.0 * n * (k + 1) * float(dims.sum())
+    row = {"method": "cof", "chain": "sbn", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "k": k,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "cof_fit_s": round(t_cof, 5), "cof_fit_reps_s": tc, "knn_fit_s": round(t_knn, 5), "knn_fit_reps_s": tk,
+           "cof_added_s": round(t_cof - t_knn, 5), "cof_over_knn": round(t_cof / t_knn, 3),
+           "chain_launch_s": round(t_launch, 6), "chain_launch_reps_s": tl, "chain_launch_over_knn_fit": round(t_launch / t_knn, 4),
+           "score_launch_s": round(t_score, 6), "n_degenerate": int(cof.n_degenerate_.sum()),
+           "gather_bytes": gather_bytes, "gather_GBps": round(gather_bytes / t_launch / 1e9, 1),
+           "fp64_fma_nominal": float(n) * (k + 1) * (k + 1) * float(dims.sum()),
+           "fp64_fma_nominal_per_s": round(float(n) * (k + 1) * (k + 1) * float(dims.sum()) / t_launch / 1e12, 3),
+           "fp64_fma_executed_per_s": round(float(n) * (kp * kp + 1) * float(dims.sum()) / t_launch / 1e12, 3)}
+    if baselines:
+        order = cof.plan.order
+        feats = [torch.as_tensor(np.flatnonzero(m[s]), device="cuda") for s in range(S)]
+        want = torch.empty(S, n, dtype=torch.float64, device="cuda")
+
+        def torch_path():
+            for first, cnt, idx in lists:
+                for z in range(cnt):
+                    want[first + z] = baseline_cof(Xd, feats[int(order[first + z])], idx[z])
+
+        t_base, tb = timed(torch_path, reps)
+        chain_launches()
+        rel = (ac - want).abs() / want.abs().clamp(min=1e-300)
+        row.update({"torch_s": round(t_base, 5), "torch_reps_s": tb, "launch_speedup_vs_torch": round(t_base / t_launch, 2),
+                    "max_rel_diff_vs_torch": float(rel.max())})
     return row
 
 
@@ -1101,13 +1184,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1133,6 +1216,16 @@ def main():
         for d, n, count in shapes:
             for C in (8, 64):
                 out["configs"].append(run_cblof(d, n, count, C, args.reps, args.iters, baselines=not args.no_baselines))
+                print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "cof":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            for k in (10, 32):
+                out["configs"].append(run_cof(d, n, count, k, args.reps, baselines=not args.no_baselines))
                 print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "abod":

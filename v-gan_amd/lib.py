@@ -145,6 +145,9 @@ SIGNATURES = {
     "vgan_outlier_combine": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "vgan_outlier_abod": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _i, _p]),
     "vgan_outlier_abod_floor": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
+    "vgan_outlier_cof_chain": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p]),
+    "vgan_outlier_cof_score": (_i, [_p, _i, _p, _i, _p, _i, _i, _p, _p, _i, _p]),
+    "vgan_outlier_cof_ceiling": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "vgan_outlier_score_stats_ws_bytes": (_i64, [_i, _i, _i]),
     "vgan_outlier_score_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
     "vgan_outlier_combine_normalized": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),

@@ -775,6 +775,38 @@ class HipOps:
         _lib.check(self.lib.vgan_outlier_abod_floor(_ptr(score), score.stride(0), S, n, int(n_degenerate is not None),
                                                     _ptr(score_floor), _ptr(n_degenerate), self._stream()), "vgan_outlier_abod_floor")
 
+    def outlier_cof_chain(self, Xq, Xr, table, first, count, idx, k, chain, ac_out):
+        """Average chaining distances (COF) of the refined lists idx [count, nq, k] into ac_out, float64 [count, nq]; chain is
+        a VGAN_OUTLIER_COF_CHAIN_* value."""
+        _mat(Xq, "Xq"), _mat(Xr, "Xr"), _vec(idx, "idx", torch.int32), _vec(ac_out, "ac_out", torch.float64)
+        feat, feat_off, _ = table
+        assert Xq.shape[1] == Xr.shape[1] and idx.numel() >= count * Xq.shape[0] * k and ac_out.numel() >= count * Xq.shape[0]
+        _lib.check(self.lib.vgan_outlier_cof_chain(_ptr(Xq), Xq.stride(0), Xq.shape[0], _ptr(Xr), Xr.stride(0), Xr.shape[0],
+                                                   Xq.shape[1], _ptr(feat), _ptr(feat_off), int(first), int(count), _ptr(idx), int(k),
+                                                   int(chain), _ptr(ac_out), self._stream()), "vgan_outlier_cof_chain")
+
+    def outlier_cof_score(self, ac_q, ac_ref, idx, k, score, score_row=None):
+        """COF scores ac_q k / sum ac_ref[idx] of the lists idx [count, nq, k] (ac_q [count, nq], ac_ref [count, nr], float64,
+        contiguous) into rows score_row of score; NaN marks a degenerate row."""
+        _vec(ac_q, "ac_q", torch.float64), _vec(ac_ref, "ac_ref", torch.float64), _vec(idx, "idx", torch.int32), _mat(score, "score")
+        assert ac_q.dim() == 2 and ac_ref.dim() == 2 and ac_q.shape[0] == ac_ref.shape[0]
+        count, nq = ac_q.shape
+        assert idx.numel() >= count * nq * k
+        _lib.check(self.lib.vgan_outlier_cof_score(_ptr(ac_q), nq, _ptr(ac_ref), ac_ref.shape[1], _ptr(idx), int(k), count, _ptr(score),
+                                                   _ptr(score_row), score.stride(0), self._stream()), "vgan_outlier_cof_score")
+
+    def outlier_cof_ceiling(self, score, score_ceiling, n_degenerate=None):
+        """outlier_abod_floor with a maximum: n_degenerate given (fit) takes score_ceiling [S] and n_degenerate [S] from score
+        [S, n]; either way the NaN scores of row s become score_ceiling[s]."""
+        _mat(score, "score"), _vec(score_ceiling, "score_ceiling", torch.float64)
+        S, n = score.shape
+        assert score_ceiling.numel() >= S
+        if n_degenerate is not None:
+            _vec(n_degenerate, "n_degenerate", torch.int32)
+            assert n_degenerate.numel() >= S
+        _lib.check(self.lib.vgan_outlier_cof_ceiling(_ptr(score), score.stride(0), S, n, int(n_degenerate is not None),
+                                                     _ptr(score_ceiling), _ptr(n_degenerate), self._stream()), "vgan_outlier_cof_ceiling")
+
     def outlier_score_stats(self, score, mode, center, scale):
         """center / scale (float64 [S]) of the rows of score [S, n]; mode is a VGAN_OUTLIER_NORM_* value."""
         _mat(score, "score"), _vec(center, "center", torch.float64), _vec(scale, "scale", torch.float64)

@@ -38,6 +38,11 @@ transform and the combination run there too (csrc/outlier_norm.hip), on the scor
 of the distance-weighted angles under which it sees pairs of its neighbours (csrc/outlier_abod.hip); its contract (usable
 neighbours, the two-pass variance, the floor that degenerate rows take) is that class's docstring.
 
+``SubspaceCOF`` is the connectivity-based detector (COF): on the same neighbour lists it replaces the density of LOF by the
+average chaining distance, the cost of walking from a row through its k neighbours along nearest-set edges
+(csrc/outlier_cof.hip); its contract (pairwise distances, the two chains, the weights, the ratio against the fitted rows,
+the zero-denominator rules and the ceiling degenerate rows take) is that class's docstring.
+
 ``SubspaceCBLOF`` is the cluster-based detector: k-means over all subspaces at once and the cluster-based local outlier
 factor on its clusters (csrc/cluster.hip); its contract (initial centres, the E and M steps and their precision, the stop
 rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.
@@ -635,6 +640,101 @@ class SubspaceABOD(_NeighborScorer):
         self._X = self._begin_fit(X)
         scores, per = self._score(None, fitting=True)
         self.score_floor_ = self._floor.cpu().numpy()
+        self.n_degenerate_ = self._n_degenerate.cpu().numpy().astype(np.int64)
+        return self._publish(scores, per)
+
+
+# ---- connectivity-based scores (COF) over the subspaces ------------------------------------------------------------------------
+COF_CHAINS = {"sbn": 0, "rank": 1}  # VGAN_OUTLIER_COF_CHAIN_*
+
+
+class SubspaceCOF(_NeighborScorer):
+    """Connectivity-based outlier factor per subspace (COF: Tang, Chen, Fu, Cheung 2002; pyod's ``COF``), combined like
+    the detectors of SubspaceEnsemble: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows; higher is
+    more outlying.  Where kNN and LOF read the radius of a neighbourhood, COF reads the cost of walking through it: a row
+    just off a thin, sparse structure (a line, a curve, a strongly correlated pair of features) looks to LOF like any row
+    of that structure, while its chain has to start with one long edge.
+
+    Per subspace s (features F_s), query row q and its refined neighbour list o_1 .. o_k: the very lists SubspaceEnsemble
+    and SubspaceABOD build (``fit`` excludes q's own index, ``decision_function`` nothing; ties by (float32 distance,
+    index); list position 1 is the nearest; ``kneighbors`` hands them out).  Let o_0 = q.
+
+    Pairwise distances.  d2(a, b) = sum_{f in F_s} (x_a[f] - x_b[f])^2 in float64 from the raw float32 values, features
+    in ascending order, for all pairs of the k + 1 points (differences per feature, never n_a + n_b - 2 <a, b>).
+
+    Chain, ``chain="sbn"`` (default; the paper's set-based nearest path).  Start with the set {o_0}.  For i = 1 .. k, add
+    the remaining point with the smallest (d2 to the set, list position), the d2 of a point to the set being its minimum
+    d2 over the set's members; e_i = sqrt of that d2.  Comparisons are made on d2, never on the square root; a tie goes
+    to the lower list position.
+
+    Chain, ``chain="rank"``.  e_i = sqrt(min_{j < i} d2(o_i, o_j)): the points are taken in list order and nothing is
+    selected.  This is pyod's ``_cof_fast`` as its source is remembered here; pyod was not at hand to pin it, so the
+    definition above and its numpy restatement in tests/test_outlier_cof_cpu.py are what binds, not pyod.
+
+    Average chaining distance.  ac(q) = sum_{i = 1 .. k} w_i e_i with w_i = 2 (k + 1 - i) / (k (k + 1)), all float64, i
+    ascending, no atomics and no order that depends on the launch.
+
+    Score.  score_s(q) = ac(q) k / sum_{i = 1 .. k} ac_fit(o_i), where ac_fit are the chaining distances of the fitted
+    rows computed at ``fit`` (self excluded).  ``fit`` runs two passes (ac of every row, then the ratio);
+    ``decision_function`` computes ac of the new rows and reads the stored ac_fit (the split LOF has with its lrd).  The
+    score is stored as float32 in the [S, n] score matrix; a value beyond the float32 range is stored as the largest
+    finite float32, never inf.  The score is scale free like LOF (inliers sit around 1), so it sums across subspaces of
+    mixed width without ``normalize``.
+
+    Zero denominators (duplicates: common in narrow subspaces of discrete features).  Denominator 0 and ac(q) = 0: the
+    score is exactly 1, the row is a point mass among point masses, and it is not degenerate.  Denominator 0 and
+    ac(q) > 0: the row is DEGENERATE and takes the ceiling of its subspace, ``score_ceiling_[s]``: the largest float32
+    score among the non-degenerate rows of the subspace at ``fit`` (1 if there is none).  ``fit`` publishes
+    ``score_ceiling_`` (float64 [S]) and ``n_degenerate_`` (int [S]) in the given subspace order; ``decision_function``
+    applies the stored ceiling and computes none of its own (SubspaceABOD's floor, with max in place of min).
+
+    ``decision_function(X_train)`` is not ``decision_scores_``: there every row is its own nearest neighbour and the
+    first edge of its chain is 0 (the remark of SubspaceABOD and of the KDE of SubspaceEnsemble, for the same reason).
+
+    n_neighbors: 1 .. 32 (default 20, pyod's).  chain: "sbn" or "rank".  engine, splits, workspace_bytes: as for
+    SubspaceEnsemble.  normalize, combination, contamination, ``threshold_``, ``labels_``, ``predict``,
+    ``predict_proba``, return_per_subspace: the shared tail; ``per_subspace_scores_`` are the raw scores with the ceiling
+    applied.  ``fit`` also publishes ``ac_dist_`` (float64 [S, n], given subspace order): the chaining distances of the
+    fitted rows.  Given the same neighbour lists ``ac_dist_`` and the scores are bit-identical from run to run, and the
+    lists do not depend on splits or workspace_bytes.  The chain, the ratio and the ceiling run in libvgan_hip.so
+    (csrc/outlier_cof.hip)."""
+
+    def __init__(self, subspaces, proba, n_neighbors=20, chain="sbn", engine="auto", splits=None,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        if not (isinstance(chain, str) and chain in COF_CHAINS):
+            raise ValueError(f"chain must be 'sbn' or 'rank', got {chain!r}")
+        self.chain = chain
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        self._configure_neighbors(n_neighbors, splits)
+
+    def _score(self, Xq, fitting):
+        """(ensemble scores float64 [n], per float32 [S, n] with the ceiling applied), both on the device.  Each chunk runs
+        both passes: the chaining distances of a subspace depend on that subspace's lists alone."""
+        k, dev = self.n_neighbors, self._X.device
+        nq = self._X.shape[0] if Xq is None else Xq.shape[0]
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=dev)
+        for first, count, idx, _ in self._neighbors(Xq):
+            ac_ref = self._ac[first:first + count]  # processing order, like _lrd
+            ac = ac_ref if fitting else torch.empty(count, nq, dtype=torch.float64, device=dev)
+            self.ops.outlier_cof_chain(self._X if Xq is None else Xq, self._X, self._table, first, count, idx, k,
+                                       COF_CHAINS[self.chain], ac)
+            self.ops.outlier_cof_score(ac, ac_ref, idx, k, per, self._rows[first:first + count])
+        if fitting:
+            self._ceiling = torch.empty(self.plan.count, dtype=torch.float64, device=dev)
+            self._n_degenerate = torch.empty(self.plan.count, dtype=torch.int32, device=dev)
+            self.ops.outlier_cof_ceiling(per, self._ceiling, self._n_degenerate)
+        else:
+            self.ops.outlier_cof_ceiling(per, self._ceiling)
+        return self._combine(per, fitting), per
+
+    def fit(self, X, y=None):
+        """Keeps X resident as the reference set and scores it (self excluded): decision_scores_ (float64 [n]),
+        per_subspace_scores_, ac_dist_, score_ceiling_, n_degenerate_; with normalize also score_center_ / score_scale_."""
+        self._X = X = self._begin_fit(X)
+        self._ac = torch.empty(self.plan.count, X.shape[0], dtype=torch.float64, device=X.device)
+        scores, per = self._score(None, fitting=True)
+        self.ac_dist_ = self._ac[torch.as_tensor(self.plan.given, device=X.device)].cpu().numpy()
+        self.score_ceiling_ = self._ceiling.cpu().numpy()
         self.n_degenerate_ = self._n_degenerate.cpu().numpy().astype(np.int64)
         return self._publish(scores, per)
 

@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
+from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
                       SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
@@ -216,13 +216,19 @@ class _RunFolder:
         method "ocsvm" builds a SubspaceOCSVM (the one-class SVM with the RBF kernel per subspace, its dual solved by SMO on
         the device, the score minus the decision value; sklearn's OneClassSVM, pyod's OCSVM): its keywords are nu, gamma, tol,
         max_iter, engine, splits, workspace_bytes and the same normalize / combination / contamination, e.g.
-        outlier_ensemble(method="ocsvm", nu=0.1, X=X); n_neighbors is not used there."""
+        outlier_ensemble(method="ocsvm", nu=0.1, X=X); n_neighbors is not used there.
+        method "cof" builds a SubspaceCOF (the connectivity-based outlier factor over the n_neighbors nearest neighbours: the
+        average chaining distance of a row against that of its neighbours; pyod's COF, whose default there is 20): its
+        keywords are chain ("sbn" or "rank"), engine, splits, workspace_bytes and the same normalize / combination /
+        contamination, e.g. outlier_ensemble(method="cof", n_neighbors=20, X=X)."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
             ens = SubspaceCBLOF(self.subspaces, self.proba, **kw)
         elif method == "abod":
             ens = SubspaceABOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
+        elif method == "cof":
+            ens = SubspaceCOF(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
         elif method == "ecod":
             ens = SubspaceECOD(self.subspaces, self.proba, **kw)
         elif method == "iforest":
