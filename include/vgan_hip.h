@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_* and vgan_loda_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_* and vgan_inne_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -960,6 +960,44 @@ int vgan_iforest_path_sums(const float* Xq, int ldq, int rows, int d, const int3
                            int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums, vgan_stream_t stream);
 int vgan_iforest_scores(const int64_t* sums, int64_t ld_sums, int count, int rows, int64_t denom, float* score,
                         int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * iNNE, isolation by nearest-neighbour ensembles (Bandaragoda, Ting, Albrecht, Liu, Wells 2018; pyod's INNE): T estimators
+ * per subspace, each psi sampled rows (the centres) with a hypersphere around every centre that reaches its nearest other
+ * centre; a row takes from an estimator the isolation ratio of the smallest sphere that covers it, 1 where none does
+ * (v-gan_amd/outlier.py: SubspaceINNE, whose docstring is the definition; kernels in csrc/outlier_inne.hip).
+ * 2 <= psi <= VGAN_INNE_MAX_SAMPLES, 1 <= T <= VGAN_INNE_MAX_ESTIMATORS.  The fitted state is four arrays [S, T, psi]:
+ * rows int32 (the centres as rows of X, in draw order), r2 float64 (squared radii), nn int32 (the position of the nearest
+ * other centre) and rho float64 (the isolation ratios); X itself stays with the caller and is read again at scoring.
+ * d2(a, b): over the features of the subspace in ascending order, float64, acc = 0: diff = double(a_f) - double(b_f),
+ *   p = diff * diff, acc = acc + p, three separately rounded operations (no fma).  Always differences per feature.
+ * vgan_inne_build: the T estimators of the subspaces first .. first + count - 1 of the table (feat, feat_off: the feature
+ *   lists, concatenated, and their offsets) from X [n, d] (ldx), 2 <= psi <= n <= 2^31 - 1, into their slots of the four
+ *   arrays.  Estimator (s, t) has the stream id = s T + t: centre j is row feistel_perm(j, n, seed, id), j < psi (the
+ *   permutation of vgan_shuffle_index), in that order.  nn_j is the position i != j with the smallest (d2(c_j, c_i), i),
+ *   r2_j = d2(c_j, c_nn_j); comparisons on d2, never on square roots.  With eps = 2^-52, ratio VGAN_INNE_RATIO_SQUARED:
+ *   rho_j = 1.0 - (r2[nn_j] + eps) / (r2_j + eps); VGAN_INNE_RATIO_DISTANCE: the same on sqrt(r2); float64, every
+ *   operation rounded on its own.  One workgroup per estimator, the row indices in LDS, the psi x psi matrix is never
+ *   stored; no workspace.  max_dims: no subspace of the range has more features (at most VGAN_INNE_MAX_DIMS).  The same
+ *   bits from run to run and for every split of the subspaces over calls.  count <= 65535.
+ * vgan_inne_scores: score float32 [count, ld_score] (ld_score >= nq): for every query row x of Xq [nq, d] (ldq) and every
+ *   subspace of the range float32(sum_t iso_t / double(T)), the sum in float64 with t ascending; iso_t = rho_j of the centre
+ *   j of estimator t with the smallest (r2_j, j) among those with d2(x, c_j) <= r2_j, 1.0 where there is none.  X [n, d]
+ *   (ldx) is the matrix the estimators were built from (the centres are read from it by row index).  No atomics, no
+ *   workspace: the same bits for every split of the rows or the subspaces over calls.  count <= 65535.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_INNE_MAX_SAMPLES 1024
+#define VGAN_INNE_MAX_ESTIMATORS 1024
+#define VGAN_INNE_MAX_DIMS 8192
+#define VGAN_INNE_RATIO_SQUARED 0
+#define VGAN_INNE_RATIO_DISTANCE 1
+int vgan_inne_build(const float* X, int ldx, int64_t n, int d, const int32_t* feat, const int32_t* feat_off, int first,
+                    int count, int max_dims, int T, int psi, int ratio, uint64_t seed, int32_t* rows, double* r2, int32_t* nn,
+                    double* rho, vgan_stream_t stream);
+int vgan_inne_scores(const float* Xq, int ldq, int nq, int d, const float* X, int ldx, int64_t n, const int32_t* feat,
+                     const int32_t* feat_off, int first, int count, int max_dims, int T, int psi, const int32_t* rows,
+                     const double* r2, const double* rho, float* score, int64_t ld_score, vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mahalanobis / MCD outlier scores (sklearn's EmpiricalCovariance / ShrunkCovariance / OAS .mahalanobis; pyod's MCD up to the

@@ -39,6 +39,13 @@ difference of the two paths' ensemble scores.
     n_estimators=100, n_jobs=16) fitted and scored per subspace on the CPUs for a sample of the subspaces, scaled to all of
     them; and the kNN fit (k = 5) of SubspaceEnsemble on the same subspaces.  walk_steps_per_s counts S T n walks of the
     measured mean depth.
+  --method inne: nearest-neighbour isolation scores (vgan_amd.SubspaceINNE, 200 estimators of 8 centres each) on the shapes of
+    the isolation-forest leg: fit and decision_function (the training rows as queries); the fit split into its calls
+    (build, scores), with the float64 rate of the scoring pass counted as three operations per (row, centre, feature); the
+    numpy restatement of the definition on 16 CPU threads (the estimators dealt to the threads; the build in full, the
+    scores on 2 000 rows scaled to n) for a sample of the subspaces scaled to all of them, and whether its scores are
+    bit-equal to the device's; the kNN fit (k = 5) of SubspaceEnsemble on the same subspaces; and the scoring pass over
+    subspaces of scattered columns against subspaces of neighbouring columns (what a packed copy would offer).
   --method mahalanobis: covariance-based scores (vgan_amd.SubspaceMahalanobis, shrinkage 0.1): fit and decision_function (the
     training rows as queries), classical and robust (max_csteps 30); the classical fit split into its calls (moments,
     factor, scores); (a) a float64 torch restatement on the same GPU (per subspace: gather, mean, centred product,
@@ -1179,18 +1186,124 @@ def sweep(n, reps):
     return rows
 
 
+def numpy_inne_one(Xs, rows, Q, threads=16):
+    """The restatement of SubspaceINNE for one subspace (Xs: its columns of X; rows int [T, psi]: the centres the device drew;
+    Q: the query rows): float64, a loop over the features, the estimators dealt to `threads` threads.  (seconds of the build,
+    seconds of the scores, the scores [len(Q)])."""
+    from concurrent.futures import ThreadPoolExecutor
+    T, psi = rows.shape
+    eps = 2.0 ** -52
+
+    def d2(A, B):
+        acc = np.zeros((A.shape[0], B.shape[0]))
+        diff = np.empty_like(acc)
+        for f in range(A.shape[1]):
+            np.subtract(A[:, None, f], B[None, :, f], out=diff)
+            np.multiply(diff, diff, out=diff)
+            np.add(acc, diff, out=acc)
+        return acc
+
+    def build(t):
+        C = Xs[rows[t]].astype(np.float64)
+        D = d2(C, C)
+        D[np.arange(psi), np.arange(psi)] = np.inf
+        nn = D.argmin(axis=1)
+        r2 = D[np.arange(psi), nn]
+        return C, r2, 1.0 - (r2[nn] + eps) / (r2 + eps)
+
+    def score(t):
+        C, r2, rho = spheres[t]
+        covered = d2(Q64, C) <= r2[None, :]
+        at = np.where(covered, r2[None, :], np.inf).argmin(axis=1)
+        return np.where(covered.any(axis=1), rho[at], 1.0)
+
+    Q64 = Q.astype(np.float64)
+    with ThreadPoolExecutor(threads) as pool:
+        t0 = time.perf_counter()
+        spheres = list(pool.map(build, range(T)))
+        t1 = time.perf_counter()
+        iso = list(pool.map(score, range(T)))
+        t2 = time.perf_counter()
+    total = np.zeros(len(Q))
+    for v in iso:
+        total = total + v
+    return t1 - t0, t2 - t1, total / float(T)
+
+
+def run_inne(d, n, count, reps, baselines=True, numpy_sample=2, numpy_rows=2000):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceINNE(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    ops, inner = ens.ops, max(reps, 5)
+    T, psi = ens.n_estimators, ens.max_samples_
+    state = tuple(torch.empty_like(a) for a in ens._state)
+    per = torch.empty(S, n, dtype=torch.float32, device="cuda")
+    ratio = vgan_amd.outlier.INNE_RATIOS[ens.ratio]
+    t_build, _ = timed(lambda: ops.inne_build(ens._X, ens._table, 0, S, int(dims.max()), ratio, ens.seed, state), inner)
+    t_scores, _ = timed(lambda: ops.inne_scores(ens._X, ens._X, ens._table, 0, S, int(dims.max()), ens._state, per), inner)
+    pair_features = float(n) * T * psi * float(dims.sum())  # (row, centre, feature) triples of one scoring pass
+    row = {"method": "inne", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_estimators": T, "max_samples": psi, "ratio": ens.ratio,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "fit_s": round(t_fit, 6), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td,
+           "build_s": round(t_build, 6), "scores_s": round(t_scores, 6), "state_bytes": int(S * T * psi * vgan_amd.outlier.INNE_STATE_BYTES),
+           "scores_fp64_tflops": round(3.0 * pair_features / t_scores / 1e12, 3),
+           "scores_fp64_note": "three float64 operations per (row, centre, feature)"}
+    knn = vgan_amd.SubspaceEnsemble(m, p, method="knn", n_neighbors=5)
+    t_knn, tk = timed(lambda: knn.fit(Xd), reps)
+    row.update({"knn_fit_s": round(t_knn, 5), "knn_fit_reps_s": tk, "knn_over_inne_fit": round(t_knn / t_fit, 2)})
+    if baselines:
+        pick = np.unique(np.linspace(0, S - 1, min(S, numpy_sample)).astype(int))
+        nq = min(n, numpy_rows)
+        t_np_build = t_np_scores = 0.0
+        equal = True
+        for s in pick:
+            Xs = np.ascontiguousarray(X[:, np.flatnonzero(m[s])])
+            tb, ts, host = numpy_inne_one(Xs, ens.center_rows_[s].astype(np.int64), Xs[:nq])
+            t_np_build, t_np_scores = t_np_build + tb, t_np_scores + ts * n / nq
+            equal = equal and bool(np.array_equal(host.astype(np.float32), ens.per_subspace_scores_[s, :nq]))
+        scale = S / len(pick)
+        row.update({"numpy_16_threads_build_s": round(t_np_build * scale, 4), "numpy_16_threads_scores_s": round(t_np_scores * scale, 4),
+                    "numpy_16_threads_fit_s": round((t_np_build + t_np_scores) * scale, 4), "numpy_subspaces_timed": int(len(pick)),
+                    "numpy_rows_timed": int(nq), "fit_speedup_vs_numpy": round((t_np_build + t_np_scores) * scale / t_fit, 1),
+                    "scores_bit_equal_to_numpy": equal})
+    return row
+
+
+def run_inne_gather(n, width, S, reps, d=784):
+    """The scoring pass over S subspaces of `width` features each of a d-wide matrix, the features scattered over the columns
+    (what the subspaces look like) against one run of neighbouring columns (what a packed copy would offer, up to the row
+    stride): whether gathering Xq[row, feat[f]] as given costs anything."""
+    rng = np.random.default_rng(n + width + S)
+    X = torch.as_tensor(rng.normal(size=(n, d)).astype(np.float32), device="cuda")
+    out = {"n": n, "d": d, "d_s": width, "S": S}
+    for name in ("scattered", "neighbouring"):
+        m = np.zeros((S, d), bool)
+        for s in range(S):
+            cols = np.sort(rng.choice(d, width, replace=False)) if name == "scattered" else np.arange(width) + (s * 7) % (d - width)
+            m[s, cols] = True
+        ens = vgan_amd.SubspaceINNE(m, np.full(S, 1.0 / S)).fit(X)
+        per = torch.empty(S, n, dtype=torch.float32, device="cuda")
+        t, ts = timed(lambda: ens.ops.inne_scores(ens._X, ens._X, ens._table, 0, S, width, ens._state, per), max(reps, 5))
+        out[name + "_scores_s"], out[name + "_scores_reps_s"] = round(t, 6), ts
+    out["scattered_over_neighbouring"] = round(out["scattered_scores_s"] / out["neighbouring_scores_s"], 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / mahalanobis / gmm / hbos / loda / pca / ocsvm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1268,6 +1381,18 @@ def main():
         for d, n, count in shapes:
             out["configs"].append(run_iforest(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "inne":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),
+                                                                         (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_inne(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        if not args.shape:  # the gather of the query features as given against neighbouring columns, narrow and three feature tiles wide
+            grid = [(2000, 8, 16), (2000, 80, 16)] if args.quick else [(50_000, 8, 64), (50_000, 80, 64)]
+            out["gather_vs_neighbouring_columns"] = [run_inne_gather(n, width, S, args.reps) for n, width, S in grid]
         configs = []
     if args.method == "mahalanobis":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),

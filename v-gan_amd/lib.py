@@ -171,6 +171,8 @@ SIGNATURES = {
     "vgan_iforest_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p]),
     "vgan_iforest_path_sums": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, _p]),
     "vgan_iforest_scores": (_i, [_p, _i64, _i, _i, _i64, _p, _i64, _p]),
+    "vgan_inne_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p, _p, _p, _p]),
+    "vgan_inne_scores": (_i, [_p, _i, _i, _i, _p, _i, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]),
     "vgan_maha_moments": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _i64, _p, _p, _p, _p, _i64, _p]),
     "vgan_maha_factor": (_i, [_p, _p, _p, _i, _i, _i, _p, ctypes.c_double, _p, _p, _p, _p, _p]),
     "vgan_maha_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _i64, _p]),

@@ -1034,6 +1034,37 @@ class HipOps:
         _lib.check(self.lib.vgan_iforest_scores(_ptr(sums), int(rows), int(count), int(rows), int(denom), _ptr(score), score.stride(0),
                                                 self._stream()), "vgan_iforest_scores")
 
+    # ---- iNNE over subspaces (vgan_amd.outlier.SubspaceINNE) -----------------------------------------------
+    # state: (rows int32, r2 float64, nn int32, rho float64), each [S, T, psi]
+    def inne_build(self, X, table, first, count, max_dims, ratio, seed, state):
+        """state receives the T estimators of the subspaces first .. first + count - 1, built from X [n, d] on psi sampled
+        rows each; max_dims: the most features of a subspace of the range; ratio: VGAN_INNE_RATIO_*."""
+        rows, r2, nn, rho = state
+        _mat(X, "X"), _vec(rows, "rows", torch.int32), _vec(nn, "nn", torch.int32)
+        _vec(r2, "r2", torch.float64), _vec(rho, "rho", torch.float64)
+        feat, feat_off, _ = table
+        n, d = X.shape
+        S, T, psi = rows.shape
+        assert r2.shape == rows.shape and nn.shape == rows.shape and rho.shape == rows.shape and first + count <= S
+        _lib.check(self.lib.vgan_inne_build(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), int(first), int(count), int(max_dims),
+                                            T, psi, int(ratio), int(seed), _ptr(rows), _ptr(r2), _ptr(nn), _ptr(rho), self._stream()),
+                   "vgan_inne_build")
+
+    def inne_scores(self, Xq, X, table, first, count, max_dims, state, score):
+        """score float32 [count, nq] (a view into the score matrix may be given): per query row of Xq and subspace of the
+        range, the mean isolation score over the subspace's estimators; X [n, d]: the matrix they were built from."""
+        rows, r2, _, rho = state
+        _mat(Xq, "Xq"), _mat(X, "X"), _mat(score, "score")
+        _vec(rows, "rows", torch.int32), _vec(r2, "r2", torch.float64), _vec(rho, "rho", torch.float64)
+        feat, feat_off, _ = table
+        nq, d = Xq.shape
+        S, T, psi = rows.shape
+        assert X.shape[1] == d and r2.shape == rows.shape and rho.shape == rows.shape and first + count <= S
+        assert score.shape[0] == count and score.shape[1] >= nq
+        _lib.check(self.lib.vgan_inne_scores(_ptr(Xq), Xq.stride(0), nq, d, _ptr(X), X.stride(0), X.shape[0], _ptr(feat), _ptr(feat_off),
+                                             int(first), int(count), int(max_dims), T, psi, _ptr(rows), _ptr(r2), _ptr(rho), _ptr(score),
+                                             score.stride(0), self._stream()), "vgan_inne_scores")
+
     # ---- Mahalanobis / MCD over subspaces (vgan_amd.outlier.SubspaceMahalanobis) ----------------------------
     # table: (feat int32, feat_off int32 [S + 1], sq_off int64 [S + 1]); the matrices of subspace s start at sq_off[s]
     def maha_moments(self, X, table, first, count, total_dims, max_dims, tiles, support, hcount, mean, cov, workspace):

@@ -57,6 +57,12 @@ on the device (csrc/outlier_iforest.hip), with path lengths summed in fixed poin
 order; it never sweeps pairs of rows either.  Its contract (samples, node numbering, the leaf rule, the draws, the
 threshold, the fixed-point path length, the score) is that class's docstring.
 
+``SubspaceINNE`` is the nearest-neighbour isolation ensemble (iNNE): per subspace a few hundred estimators of a handful of
+sampled rows each, a hypersphere around every sampled row that reaches its nearest other one, and per query row the
+isolation ratio of the smallest sphere that covers it (csrc/outlier_inne.hip); local and rotation free where the isolation
+forest is global and axis-aligned, and scale free in [0, 1].  Its contract (the sample and its order, the squared distance
+and its rounding, radius and nearest centre, the two ratios, the covering rule, the score) is that class's docstring.
+
 ``SubspaceMahalanobis`` is the covariance-based detector: a float64 mean and shrunk covariance per subspace, classical or by
 deterministic concentration steps (MCD), and the squared Mahalanobis distance as a triangular float64 product on the
 matrix unit (csrc/outlier_maha.hip); n d_s^2 per subspace.  Its contract (support, location, covariance, shrinkage and the
@@ -1621,6 +1627,159 @@ class SubspaceIForest(_SubspaceScorer):
         for first, count in self._ranges()[0]:
             self.ops.iforest_build(X, self._table, first, count, int(self.plan.dims[first:first + count].max()), psi, self.depth_limit_,
                                    self.seed, self._trees)
+        scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)
+
+
+# ---- iNNE: isolation by nearest-neighbour ensembles over the subspaces ---------------------------------------------------
+INNE_MAX_ESTIMATORS = 1024  # VGAN_INNE_MAX_ESTIMATORS
+INNE_MAX_SAMPLES = 1024  # VGAN_INNE_MAX_SAMPLES: the centres of an estimator live in LDS
+INNE_MAX_DIMS = 8192  # VGAN_INNE_MAX_DIMS: features of one subspace
+INNE_MAX_ROWS = (1 << 31) - 1
+INNE_AUTO_SAMPLES = 8  # max_samples="auto", pyod's default
+INNE_RATIOS = {"squared": 0, "distance": 1}  # VGAN_INNE_RATIO_*
+INNE_STATE_BYTES = 24  # per centre: int32 row, float64 r2, int32 nn, float64 rho
+_INNE_MAX_RANGE = 65535  # subspaces of one launch (a grid dimension)
+
+
+def check_inne_samples(max_samples):
+    """ "auto" (8) or an integer between 2 and INNE_MAX_SAMPLES; fit takes min(max_samples, n)."""
+    if isinstance(max_samples, str) and max_samples == "auto":
+        return INNE_AUTO_SAMPLES
+    if not (_is_int(max_samples) and 2 <= int(max_samples) <= INNE_MAX_SAMPLES):
+        raise ValueError(f"max_samples must be 'auto' or an integer between 2 and {INNE_MAX_SAMPLES}, got {max_samples!r}")
+    return int(max_samples)
+
+
+def check_inne_ratio(ratio):
+    if not (isinstance(ratio, str) and ratio in INNE_RATIOS):
+        raise ValueError(f"ratio must be 'squared' or 'distance', got {ratio!r}")
+    return ratio
+
+
+class SubspaceINNE(_SubspaceScorer):
+    """Isolation by nearest-neighbour ensembles per subspace (iNNE: Bandaragoda, Ting, Albrecht, Liu, Wells 2018; pyod's
+    ``INNE``), combined like the other detectors of this module: ``fit`` sets ``decision_scores_``, ``decision_function``
+    scores new rows; higher is more outlying.  Where the isolation forest cuts along single features with a global score,
+    iNNE isolates with hyperspheres around a few sampled rows and compares the radius of the sphere that catches a row with
+    the radius of that sphere's own nearest neighbour: the score is local and invariant to a rotation of the subspace.  It
+    is scale free in [0, 1], so like LOF and COF it sums across subspaces of mixed width without ``normalize``.  ``fit``
+    touches T psi^2 pairs of rows per subspace, scoring n T psi.  pyod was not at hand: the rules below are the paper's
+    and pyod's as their source is remembered here, not pinned against pyod, so the definition below and its numpy
+    restatement in tests/test_outlier_inne_cpu.py are what binds.  Not built: pyod's contamination-shifted sign
+    conventions, and ``max_samples`` as a fraction of n.
+
+    X is cast to float32.  n rows are given to ``fit``, 2 <= n <= 2^31 - 1; T = n_estimators (1 .. 1024, default 200:
+    pyod's); psi = ``max_samples_`` = min(max_samples, n), max_samples "auto" (8: pyod's) or 2 .. 1024; seed in [0, 2^64); a
+    subspace has at most INNE_MAX_DIMS (8192) features.
+
+    Sample.  Estimator (s, t), s the given subspace index, has the stream id = s T + t.  Its centres are the rows c_j =
+    feistel_perm(j, n, seed, id), j = 0 .. psi - 1, in that order (the permutation of vgan_shuffle_index, as
+    SubspaceIForest uses it); the position j breaks ties below, so the order matters and not only the set.
+
+    Squared distance.  d2(a, b) runs over the features of F_s in ascending order with acc = 0.0 in float64; per feature
+    diff = double(a_f) - double(b_f), p = diff * diff, acc = acc + p: three separately rounded operations, no fused
+    multiply-add.  Always differences per feature, never |a|^2 + |b|^2 - 2 <a, b>.
+
+    Radius and nearest centre.  For centre j, nn_j is the position i != j with the smallest (d2(c_j, c_i), i), and r2_j =
+    d2(c_j, c_nn_j).  Comparisons are on d2, never on square roots.
+
+    Ratio.  With eps = 2^-52, ``ratio="squared"`` (default; pyod's arithmetic as remembered): rho_j = 1.0 - (r2[nn_j] + eps)
+    / (r2_j + eps); ``ratio="distance"`` (the paper's): the same with sqrt(r2) in place of r2.  Float64, each operation
+    rounded on its own.  r2[nn_j] <= r2_j always, so rho is in [0, 1].
+
+    Isolation score of a row x in estimator (s, t).  Among the centres with d2(x, c_j) <= r2_j (x is covered), the one with
+    the smallest (r2_j, j) gives iso = rho_j; if no centre covers x, iso = 1.0.
+
+    Score.  score[s, i] = float32(sum_t iso_t / double(T)): the sum in float64 with t ascending, one division, one rounding
+    to float32; in [0, 1].  ``fit`` scores the training rows through all estimators with nothing excluded (as pyod does), so
+    ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.
+
+    Consequences.  A subspace of constant features has every r2 = 0 and every row covered, rho = 1 - eps / eps = 0: it
+    scores exactly 0.  A row that coincides with a centre whose r2 is 0 is covered by it.  A row covered by nothing in any
+    estimator scores exactly 1.  NaN input leaves the results unspecified and neither faults nor hangs: every loop is
+    bounded by psi, T and d_s, and a false comparison means "not covered".
+
+    Fitted state.  X stays resident, as for the neighbour detectors: the centres are read from it by row index.  Beside it
+    an estimator keeps 24 bytes per centre (int32 row, float64 r2, int32 nn, float64 rho): 24 T psi bytes per subspace,
+    38 400 with the defaults.  ``fit`` publishes, in the given subspace order and copied to the host on first use:
+    ``center_rows_`` int32 [S, T, psi], ``radius_sq_`` float64 [S, T, psi], ``center_nn_`` int32 [S, T, psi] (positions),
+    ``isolation_ratio_`` float64 [S, T, psi]; and ``max_samples_``.  normalize, combination, contamination,
+    ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.
+
+    Nothing above depends on a processing order: the state and the scores are bit-identical from run to run.  Scoring needs
+    no transient buffer beside the [S, n] score matrix every detector returns, so ``workspace_bytes`` (kept for the shared
+    constructor tail) bounds nothing here and changes no result.  All of it runs in libvgan_hip.so (csrc/outlier_inne.hip)."""
+
+    _host_state = None
+
+    def __init__(self, subspaces, proba, n_estimators=200, max_samples="auto", ratio="squared", seed=0,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        self.n_estimators = check_estimators(n_estimators)
+        self.max_samples = max_samples
+        self._max_samples = check_inne_samples(max_samples)
+        self.ratio = check_inne_ratio(ratio)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > INNE_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceINNE takes at most {INNE_MAX_DIMS}")
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= INNE_MAX_ROWS:
+            raise ValueError(f"SubspaceINNE fit needs between 2 and {INNE_MAX_ROWS} rows, got {n}")
+
+    def _ranges(self):
+        """[(first, count)]: the subspaces of one launch (a grid dimension bounds them)."""
+        return [(first, min(_INNE_MAX_RANGE, self.plan.count - first)) for first in range(0, self.plan.count, _INNE_MAX_RANGE)]
+
+    def _score(self, Xq, fitting):
+        per = torch.empty(self.plan.count, Xq.shape[0], dtype=torch.float32, device=Xq.device)
+        for first, count in self._ranges():
+            self.ops.inne_scores(Xq, self._X, self._table, first, count, int(self.plan.dims[first:first + count].max()), self._state,
+                                 per[first:first + count])
+        return self._combine(per, fitting), per
+
+    def _state_on_host(self):
+        self._require_fit()
+        if self._host_state is None:
+            self._host_state = tuple(a.cpu().numpy() for a in self._state)
+        return self._host_state
+
+    @property
+    def center_rows_(self):
+        """int32 [S, T, psi]: the centres of every estimator as rows of the fitted X, in draw order."""
+        return self._state_on_host()[0]
+
+    @property
+    def radius_sq_(self):
+        """float64 [S, T, psi]: the squared radius of every centre's sphere, d2 to its nearest other centre."""
+        return self._state_on_host()[1]
+
+    @property
+    def center_nn_(self):
+        """int32 [S, T, psi]: the position within its estimator of every centre's nearest other centre."""
+        return self._state_on_host()[2]
+
+    @property
+    def isolation_ratio_(self):
+        """float64 [S, T, psi]: rho of every centre, in [0, 1]."""
+        return self._state_on_host()[3]
+
+    def fit(self, X, y=None):
+        """Keeps X resident, builds the T estimators of every subspace on their samples of it, then scores X itself through
+        them: decision_scores_ (float64 [n]), per_subspace_scores_, max_samples_ and, on first use, center_rows_ / radius_sq_
+        / center_nn_ / isolation_ratio_; with normalize also score_center_ / score_scale_."""
+        self._X = X = self._begin_fit(X)
+        psi = min(self._max_samples, X.shape[0])
+        self.max_samples_, self._host_state = psi, None
+        shape = (self.plan.count, self.n_estimators, psi)
+        kinds = (torch.int32, torch.float64, torch.int32, torch.float64)  # rows, r2, nn, rho
+        self._state = tuple(torch.empty(shape, dtype=dt, device=X.device) for dt in kinds)
+        for first, count in self._ranges():
+            self.ops.inne_build(X, self._table, first, count, int(self.plan.dims[first:first + count].max()), INNE_RATIOS[self.ratio],
+                                self.seed, self._state)
         scores, per = self._score(X, fitting=True)
         return self._publish(scores, per)
 

@@ -15,7 +15,7 @@ from torch.utils.data import DataLoader
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
 from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
-                      SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA)
+                      SubspaceINNE, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -220,7 +220,12 @@ class _RunFolder:
         method "cof" builds a SubspaceCOF (the connectivity-based outlier factor over the n_neighbors nearest neighbours: the
         average chaining distance of a row against that of its neighbours; pyod's COF, whose default there is 20): its
         keywords are chain ("sbn" or "rank"), engine, splits, workspace_bytes and the same normalize / combination /
-        contamination, e.g. outlier_ensemble(method="cof", n_neighbors=20, X=X)."""
+        contamination, e.g. outlier_ensemble(method="cof", n_neighbors=20, X=X).
+        method "inne" builds a SubspaceINNE (isolation by nearest-neighbour ensembles: hyperspheres around a few sampled rows
+        per estimator, the score the isolation ratio of the smallest sphere that covers a row; pyod's INNE): its keywords are
+        n_estimators, max_samples, ratio ("squared" or "distance"), seed, workspace_bytes and the same normalize /
+        combination / contamination, e.g. outlier_ensemble(method="inne", n_estimators=200, X=X); n_neighbors is not used
+        there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -233,6 +238,8 @@ class _RunFolder:
             ens = SubspaceECOD(self.subspaces, self.proba, **kw)
         elif method == "iforest":
             ens = SubspaceIForest(self.subspaces, self.proba, **kw)
+        elif method == "inne":
+            ens = SubspaceINNE(self.subspaces, self.proba, **kw)
         elif method == "mahalanobis":
             ens = SubspaceMahalanobis(self.subspaces, self.proba, **kw)
         elif method == "mcd":
