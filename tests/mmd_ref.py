@@ -42,8 +42,27 @@ backward: out = 2 (rs_i z_ij - acc_ij) mul_ij, rs_i = sum_k W_ik, acc_ij = sum_k
     2 K 2^-23 (sum_k |W_ik| |z_ij| + sum_k |W_ik Z_kj|) |mul_ij|, plus 8u (|rs_i z_ij| + |acc_ij|) |mul_ij| for the epilogue's
     four roundings (product, difference, mul + shift, final product), doubled.
 
+split-bf16 backward (backward_bf3_ref / backward_bf3_bound): the kernels are GIVEN the four bf16 images Wh, Wl [nr, K] and
+    Zh, Zl [K, p] and the fp32 row z the epilogue reads, and compute, in float32,
+        acc_ij = sum_k (Wh_ik Zh_kj + Wh_ik Zl_kj + Wl_ik Zh_kj)     (three MFMA products per k; Wl.Zl is NOT formed)
+        rs_i   = sum_k (Wh_ik + Wl_ik)                              (2 K terms)
+        out_ij = 2 (rs_i z_ij - acc_ij) (mul_ij + shift_j)
+    The reference is that expression in float64 on the same images (as gram_bf3 does for the Gram: the dropped term is on both
+    sides).  Every product of two bf16 values is exact in float32, so only the summations round: a float32 sum of m terms t_k
+    in ANY order is within m u sum |t_k| to first order, m 2^-23 sum |t_k| with the factor 2 of margin used throughout this file
+    (check_product of test_chain_ksplit_gpu.py).  rs has m = 2 K terms |Wh| and |Wl|; acc has m = 3 K terms whose magnitudes
+    sum to at most (|Wh| + |Wl|) . (|Zh| + |Zl|) (that also counts |Wl Zl|, 2^-16 of the total).  K is the PADDED length of the
+    slab's K range, which is what the loops run over.  Carried through out = 2 (...) m:
+        2 * 2^-23 * (2 K sum_k (|Wh| + |Wl|)_ik |z_ij|  +  3 K ((|Wh| + |Wl|) . (|Zh| + |Zl|))_ij) |mul_ij + shift_j|
+        + 8u (|rs_i z_ij| + |acc_ij|) |mul_ij + shift_j|          (the epilogue's four roundings, doubled, as for `backward`)
+    With the row sums handed in (rs_part: S slot cells per row, summed in float32) the first term is S sum_s |cell_s| |z| in
+    place of 2 K sum_k (...).  With both hi images zero acc is exactly zero and the second term is left out (exact_acc).
+    CAP_BWD_BF3: max(bound) <= 2e-3 max |want| for every case of the GPU tier (tests/test_mmd_bwd_bf3_cpu.py).
+
 A vacuous bound hides errors: every case asserts max(bound) <= cap * max |W| (cap_ok) before it looks at a kernel's output.
 """
+import functools
+
 import numpy as np
 
 from oracle import vgan_oracle as orc
@@ -285,3 +304,142 @@ def emulate_gram_fp32(Z32, sq32, n, bw32, mults=None):
         K = K + e
         dk = (e * (f(1) / sc) + dk).astype(f)
     return K.astype(f), ((-sgn * f(2) / nn) * dk).astype(f)
+
+
+# ------------------------------------------------------------------------------------------------ split-bf16 backward product
+CAP_BWD_BF3 = 2e-3
+# (n, p) of tests/test_mmd_bwd_bf3_gpu.py, the smallest shapes that reach each schedule (N = 2n rows of Z, kn = N padded to 64):
+# (32, 7) one K tile, p < 64, odd ldz; (33, 64) two K tiles, zrows 2 past a tile; (65, 65) three, one column into a second
+# panel; (100, 130) kp = 192 < 256: the 128-wide kernel's clamp of feature rows; (65, 40) and (130, 130) ragged on 256 x 128
+# tiles; (128, 130) nr = 128 and nr = 256 on them
+BWD_BF3_CASES = [(32, 7), (33, 64), (65, 65), (100, 130), (130, 200), (65, 40), (130, 130), (128, 130)]
+BWD_BF3_WIDE = [(65, 40), (130, 130), (128, 130)]  # tile 256 is forced here (row-major operand only)
+BWD_BF3_MULS = ["none", "mul", "mul+shift"]
+BWD_BF3_MUTATIONS = ["Wh.Zl dropped", "Wl.Zh dropped", "Wl.Zl added", "row sum over Wh only"]
+
+
+# The kernels are handed raw images, so the test is free in them.  Most rows of W are a true split (hi = bf16(w), lo = bf16(w - hi),
+# |lo| <= 2^-9 |hi|): there Wl.Zl is 2^-16 of the product against a bound of about K 2^-22 of it, and no element-wise bound can see
+# that term added.  Three rows of every W are therefore SMALL (2^-20 of the others) with a lo image as large as the hi image: on
+# them each of the three products, and the fourth that must not be formed, weighs as much as the whole, and an error there is
+# far below any tolerance scaled by max |want| -- the wrong element in a small-magnitude row that a global criterion lets pass.
+BWD_BF3_SMALL = 2.0 ** -20
+
+
+def bwd_bf3_small_rows(nr):
+    return [1, nr // 2, nr - 1]
+
+
+def pad64(v):
+    return (int(v) + 63) // 64 * 64
+
+
+def bwd_bf3_ranges(n):
+    """(nr, wrow0) as in test_fp32_backward_direct: the Y half, all rows, and from n = 64 on a shard."""
+    return [(n, n), (2 * n, 0)] + ([(32, n + 32)] if n >= 64 else [])
+
+
+def bwd_bf3_splits(n):
+    """1, 2, 3 and 40 slabs (live < splits: empty slabs); kn = 256 also 4: klen = 64, two stages of the 256-wide loop."""
+    return [1, 2, 3, 40] + ([4] if pad64(2 * n) == 256 else [])
+
+
+def bf3_slabs(kn, splits):
+    """kchunk, live and the [k0, k1) column ranges of the live slabs, as launch_backward_bf3 cuts them (whole K tiles of 64)."""
+    kchunk = ((kn // 64 + splits - 1) // splits) * 64
+    live = (kn + kchunk - 1) // kchunk
+    return kchunk, live, [(s * kchunk, min((s + 1) * kchunk, kn)) for s in range(live)]
+
+
+def bf16_bits(x):
+    """The uint16 images of a float32 array that holds bf16 values."""
+    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    assert not (b & 0xFFFF).any()
+    return (b >> 16).astype(np.uint16)
+
+
+def bf16_from_bits(b):
+    return (np.asarray(b).view(np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def bwd_bf3_data(n, p):
+    """The operands of a case, read-only: fp32 Z [N, p]; its split images zh, zl [kn, p] as float64 (rows past N zero); per
+    row range W's split images wh, wl [nr, kn] (columns past N zero), mul [nr, p] and shift [p] as float32."""
+    rng = np.random.default_rng(10007 * n + p)
+    N, kn = 2 * n, pad64(2 * n)
+    Z = rng.normal(size=(N, p)).astype(np.float32)
+    zh, zl = np.zeros((kn, p)), np.zeros((kn, p))
+    zh[:N], zl[:N] = split_bf16(Z)
+    ranges = []
+    for nr, wrow0 in bwd_bf3_ranges(n):
+        W = (rng.normal(size=(nr, N)) * 1e-3).astype(np.float32)
+        wh, wl = np.zeros((nr, kn)), np.zeros((nr, kn))
+        wh[:, :N], wl[:, :N] = split_bf16(W)
+        for r in bwd_bf3_small_rows(nr):
+            wh[r, :N] = split_bf16(rng.normal(size=N) * 1e-3 * BWD_BF3_SMALL)[0]
+            wl[r, :N] = split_bf16(rng.normal(size=N) * 2e-3 * BWD_BF3_SMALL)[0]
+        mul =rng.normal(size=(nr, p)).astype(np.float32)
+        shift = rng.normal(size=(p,)).astype(np.float32)
+        ranges.append(dict(nr=nr, wrow0=wrow0, wh=wh, wl=wl, mul=mul, shift=shift))
+    for a in [Z, zh, zl] + [r[k] for r in ranges for k in ("wh", "wl", "mul", "shift")]:
+        a.setflags(write=False)
+    return dict(n=n, p=p, N=N, kn=kn, kp=pad64(p), Z=Z, zh=zh, zl=zl, ranges=ranges)
+
+
+def bwd_bf3_mul64(rg, variant):
+    """mul + shift in float64, or None."""
+    if variant == "none":
+        return None
+    m = rg["mul"].astype(np.float64)
+    return m + rg["shift"].astype(np.float64) if variant == "mul+shift" else m
+
+
+def backward_bf3_ref(wh, wl, zh, zl, zrow, mul64=None, k0=0, k1=None, rs=None):
+    """Module docstring, 'split-bf16 backward', over the columns [k0, k1) of W = rows of Z.  zrow: the fp32 rows of Z the
+    epilogue reads, [nr, p] float64.  rs [nr]: row sums handed in (rs_part) instead of summed from the images."""
+    k1 = wh.shape[1] if k1 is None else k1
+    a, b, c, d = wh[:, k0:k1], wl[:, k0:k1], zh[k0:k1], zl[k0:k1]
+    acc = a @ c + a @ d + b @ c
+    r = (a + b).sum(1) if rs is None else np.asarray(rs, dtype=np.float64)
+    out = 2.0 * (r[:, None] * zrow - acc)
+    return out if mul64 is None else out * mul64
+
+
+def backward_bf3_bound(wh, wl, zh, zl, zrow, mul64=None, k0=0, k1=None, rs_cells=None, exact_acc=False):
+    """Module docstring, 'split-bf16 backward'.  K = k1 - k0, padded.  rs_cells [S, nr]: the slot cells the row sum is folded from."""
+    k1 = wh.shape[1] if k1 is None else k1
+    a, b, c, d = wh[:, k0:k1], wl[:, k0:k1], zh[k0:k1], zl[k0:k1]
+    K = k1 - k0
+    az = np.abs(zrow)
+    aw = np.abs(a) + np.abs(b)
+    acc = a @ c + a @ d + b @ c
+    if rs_cells is None:
+        rs, rs_term = (a + b).sum(1), 2.0 * K * aw.sum(1)
+    else:
+        cells = np.asarray(rs_cells, dtype=np.float64)
+        rs, rs_term = cells.sum(0), cells.shape[0] * np.abs(cells).sum(0)
+    prod_term = 0.0 if exact_acc else 3.0 * K * (aw @ (np.abs(c) + np.abs(d)))
+    bound = 2.0 * 2.0 ** -23 * (rs_term[:, None] * az + prod_term) + 8.0 * U * (np.abs(rs)[:, None] * az + np.abs(acc))
+    return bound if mul64 is None else bound * np.abs(mul64)
+
+
+def emulate_backward_bf3(wh, wl, zh, zl, zrow, mul32=None, shift32=None, k0=0, k1=None, mutation=None):
+    """A float32 numpy emulation of the kernels' arithmetic (float32 products and sums, the epilogue's four roundings), with
+    one of BWD_BF3_MUTATIONS applied."""
+    f = np.float32
+    k1 = wh.shape[1] if k1 is None else k1
+    a, b, c, d = (x.astype(f) for x in (wh[:, k0:k1], wl[:, k0:k1], zh[k0:k1], zl[k0:k1]))
+    acc = np.zeros((a.shape[0], c.shape[1]), dtype=f)  # small terms first
+    if mutation == "Wl.Zl added":
+        acc = acc + b @ d
+    if mutation != "Wl.Zh dropped":
+        acc = acc + b @ c
+    if mutation != "Wh.Zl dropped":
+        acc = acc + a @ d
+    acc = (acc + a @ c).astype(f)
+    rs = (a.sum(1) if mutation == "row sum over Wh only" else (a + b).sum(1)).astype(f)
+    out = f(2) * (rs[:, None] * zrow.astype(f) - acc)
+    if mul32 is not None:
+        out = out * (mul32 + shift32 if shift32 is not None else mul32)
+    return out.astype(f)

@@ -772,7 +772,8 @@ def test_backward_bf3_rowmajor_operand_equals_transposed_operand(ops, n, d, nr_o
     """vgan_mmd_backward_bf3_rm (B fragments out of Z's ROW-MAJOR split images by ds_read_b64_tr_b16) against
     vgan_mmd_backward_bf3 on the transposed copies of the same images: the same products in the same order, so the outputs
     must be bit-identical -- 64- and 128-wide tiles, ragged row counts, feature counts that are no multiple of the tile,
-    split-K slabs, gradient rows for the Y half or for all rows, multiplier with shift."""
+    split-K slabs, gradient rows for the Y half or for all rows, multiplier with shift.
+    (Per element and per slab against float64, at the tile and K edges: tests/test_mmd_bwd_bf3_gpu.py.)"""
     rng = np.random.default_rng(n + d)
     N = 2 * n
     kp, kn = (d + 63) // 64 * 64, (N + 63) // 64 * 64
@@ -1353,7 +1354,8 @@ def test_backward_bf3_wide_tiles(ops, n, d, nr_of, splits):
     """vgan_mmd_backward_bf3_rm on 256 x 128 output tiles (GemmBF3Wide::run_bt: 8 consumer + 4 loader waves, B fragments by
     transposed LDS reads of Z's row-major images, row sums of W taken by the loader waves from the landed LDS image) against
     float64 on the same split operands and against the 64-wide kernel: ragged rows, features no multiple of the tile, split-K
-    slabs, gradient rows for the Y half or all rows, multiplier with shift; twice the same bits."""
+    slabs, gradient rows for the Y half or all rows, multiplier with shift; twice the same bits.
+    (Per element and per slab against float64, at the tile and K edges: tests/test_mmd_bwd_bf3_gpu.py.)"""
     rng = np.random.default_rng(n + d)
     N = 2 * n
     kp, kn = (d + 63) // 64 * 64, (N + 63) // 64 * 64

@@ -408,7 +408,9 @@ class HipOps:
 
     def mmd_backward_bf3(self, Wh, Wl, ZTh, ZTl, Z, wrow0, nr, p, mul, out, splits=1, slab_stride=0, finalize=None, mul_shift=None,
                          tile=0):
-        """tile: 0 = the library's choice between its 64- and 128-wide tiles, or 64 / 128 to force one."""
+        """out = 2 (rowsum(W) z - W . Z) (mul + mul_shift) on the TRANSPOSED split images ZTh, ZTl [kp, kn].  tile: 0 = the library's
+        rule (mmd_backward_bf3_tile), or 64 / 128 / 256 to force one.  The 256 x 128 tiles read the row-major operand only: on the
+        transposed images a rule or a request of 256 runs the 128-wide kernel instead (same bits as tile=128)."""
         _mat(Z, "Z"), _mat(out, "out")
         ldmul = mul.stride(0) if mul is not None else 0
         _lib.check(self.lib.vgan_mmd_backward_bf3(_ptr(Wh), _ptr(Wl), Wh.stride(0), _ptr(ZTh), _ptr(ZTl), ZTh.stride(0),
@@ -421,7 +423,8 @@ class HipOps:
                             tile=0, xx=None, rs_part=None):
         """mmd_backward_bf3 on the ROW-MAJOR split images Zh, Zl [>= zrows, kp] (no transposed copies of Z).  xx: an xx_job() whose
         X-X Gram tiles ride in the launch as surplus workgroups (64-wide tiles only).  rs_part: the per-slot row sums of W a
-        tile-256 mmd_gram_bf3 launch left (include/vgan_hip.h)."""
+        tile-256 mmd_gram_bf3 launch left (include/vgan_hip.h); read by the 256 x 128 tiles only, and only when every K slab is a
+        whole number of 128-column slots.  tile: 0 = the rule of mmd_backward_bf3_tile, or 64 / 128 / 256 to force one."""
         _mat(Z, "Z"), _mat(out, "out")
         ldmul = mul.stride(0) if mul is not None else 0
         kn = (int(zrows) + 63) // 64 * 64
@@ -454,7 +457,9 @@ class HipOps:
                    "vgan_mmd_backward_bf3_rm_rebuild")
 
     def mmd_backward_bf3_tile(self, nr, p, splits=1, tile=0):
-        """Tile edge (64 / 128) mmd_backward_bf3 runs for this shape (host-side query of the library's rule)."""
+        """Tile edge mmd_backward_bf3_rm runs for this shape (host-side query of the library's rule): a forced 64 / 128 / 256 as
+        given; else 256 (256 x 128 tiles) once nr >= 256 and ceil(p / 128) * ceil(nr / 256) * splits >= 256; else 128 once
+        ceil(p / 128) * ceil(nr / 128) * splits >= 512; else 64.  mmd_backward_bf3 (transposed images) runs 128 where this says 256."""
         return int(self.lib.vgan_mmd_backward_bf3_tile(int(nr), int(p), int(splits), int(tile)))
 
     def gemm_grouped(self, problems, copy=None, adadelta=None, noise=None, fold=None, kparts=None, ksplit_ws=None):
