@@ -150,6 +150,36 @@ def entries(ens, flat, s, shape):
 
 
 # ---- moments ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [64, 65, 1025, 2051])
+def test_one_component_moments_are_the_classical_moments_bit_for_bit(n):
+    """C = 1, every responsibility 1 and reg_covar = 0 against vgan_maha_moments with no support on the same data: both run
+    the core of csrc/outlier_moments.hpp, and the weighted instantiation then does nothing the plain one does not.  1.0 x is
+    x; nk = n + 10 eps rounds to n (half an ulp of an n >= 32 is at least 2^-48 = 16 eps); + 0.0 leaves a diagonal element, a
+    sum of squares and never -0.0, as it is.  mean and cov are compared bit for bit."""
+    import torch
+    import vgan_amd
+    sizes = [1, 16, 17, 33, 65]
+    rng = np.random.default_rng(n)
+    mask = np.zeros((len(sizes), D), bool)
+    for s, size in enumerate(sizes):
+        mask[s, rng.choice(D, size, replace=False)] = True
+    X = raw_data(n, D, seed=n)
+    gm, Xd = prepared(mask, X, 1, reg_covar=0.0)
+    assert len(gm._ranges) == 1
+    gm._resp.fill_(1.0)
+    gm._moments(Xd, 0)
+    maha = vgan_amd.SubspaceMahalanobis(mask, np.full(len(sizes), 1.0 / len(sizes)))
+    maha._begin_fit(X)
+    maha._prepare(n, Xd.device)
+    maha._moments(Xd, None, torch.full((len(sizes),), n, dtype=torch.int32, device=Xd.device))
+    assert (gm._nk.cpu().numpy() == float(n)).all()
+    for name in ("_mean", "_cov"):
+        got, want = getattr(gm, name).cpu().numpy(), getattr(maha, name).cpu().numpy()
+        assert got.shape == want.shape and got.dtype == want.dtype == np.float64
+        differs = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
+        assert differs.size == 0, (name, int(differs[0]), got[differs[0]].hex(), want[differs[0]].hex())
+
+
 @pytest.mark.parametrize("frozen", [None, 3])
 @pytest.mark.parametrize("n", ROWS)
 def test_moments_are_within_the_summation_bound(n, frozen):
@@ -362,8 +392,9 @@ def test_the_mixture_ranks_the_planted_rows_on_the_device():
 
 
 def test_one_component_is_the_mahalanobis_detector():
-    """C = 1, reg_covar = 0 against SubspaceMahalanobis(shrinkage=0) on full-rank data: 2 score - d_s log 2pi - 2 sum log diag L is
-    its d^2.  Both published numbers are float32: the score carries half an ulp of its own size, doubled by the factor 2, d^2
+    """C = 1, reg_covar = 0 against SubspaceMahalanobis(shrinkage=0) on full-rank data: the covariance is the same to the bit
+    (the responsibilities after an E step are exp(0) / 1 = 1.0, and the moments are one code path), and 2 score - d_s log 2pi - 2
+    sum log diag L is its d^2.  Both published numbers are float32: the score carries half an ulp of its own size, doubled by the factor 2, d^2
     half an ulp of its own, so the bar is 2 float32 ulps of the larger of |score| and d^2."""
     import vgan_amd
     rng = np.random.default_rng(21)
@@ -376,7 +407,7 @@ def test_one_component_is_the_mahalanobis_detector():
     assert (gm.n_iter_ == 2).all() and gm.converged_.all() and (gm.weights_ == 1.0).all()
     for s in range(3):
         d = int(mask[s].sum())
-        np.testing.assert_allclose(gm.covariances_[s][0], maha.covariance_[s], rtol=1e-12, atol=1e-13)
+        np.testing.assert_array_equal(gm.covariances_[s][0], maha.covariance_[s])  # one code path: the same bits
         logdet = np.log(np.diag(np.linalg.cholesky(gm.covariances_[s][0]))).sum()
         score = gm.per_subspace_scores_[s].astype(np.float64)
         d2 = maha.per_subspace_scores_[s].astype(np.float64)

@@ -82,30 +82,20 @@ __global__ __launch_bounds__(kBlock) void ecod_sort_global_kernel(uint32_t* __re
     }
 }
 
-// float64 sum over the workgroup in a fixed order, valid in every thread
-__device__ __forceinline__ double ecod_block_sum(double v, double* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(kBlock) void ecod_skew_kernel(const float* __restrict__ sorted, long ld, int n, int8_t* __restrict__ sign) {
     __shared__ double red[kBlock / kWave];
     const float* col = sorted + (long)blockIdx.x * ld;
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += kBlock) s += (double)col[i];
-    const double mu = ecod_block_sum(s, red) / (double)n;
+    const double mu = block_sum_all(s, red) / (double)n;
     double m2 = 0.0, m3 = 0.0;
     for (int i = threadIdx.x; i < n; i += kBlock) {
         const double e = (double)col[i] - mu, e2 = e * e;
         m2 += e2;
         m3 += e2 * e;
     }
-    m2 = ecod_block_sum(m2, red);
-    m3 = ecod_block_sum(m3, red);
+    m2 = block_sum_all(m2, red);
+    m3 = block_sum_all(m3, red);
     if (threadIdx.x == 0) sign[blockIdx.x] = m2 == 0.0 ? 0 : (int8_t)((m3 > 0.0) - (m3 < 0.0));
 }
 

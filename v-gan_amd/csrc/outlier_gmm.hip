@@ -9,16 +9,14 @@
 // unchanged.  A subspace whose done flag is set is frozen: the workgroups of the moments and of the E step that belong to it
 // return at once, and the factor re-emits its matrices from an unchanged covariance.
 //
-//   moments  the slab / tile decomposition of vgan_maha_moments with the responsibility as a row weight.  sum: a thread per
-//            feature adds r_ic x_i over the rows of a slab in order, one more thread adds r_ic (nk); the slab partials are
-//            added in ascending order; a workgroup per subspace then forms nk + 10 eps, w, log w and divides the means.  cov: a
-//            workgroup per (lower-triangle 16 x 16 tile, slab), four rows per v_mfma_f64_16x16x4_f64 with A = r_ic (x_i -
-//            mu_c), B = (x_i - mu_c), gathered and centred on the fly; the combine divides by nk and adds reg_covar on the
-//            diagonal.
+//   moments  the sum, covariance-tile, combine and chunking core of outlier_moments.hpp (which vgan_maha_moments runs on too)
+//            with the responsibility as the row weight.  sum: r_ic x_i over the rows of a slab in order, one more thread adds
+//            r_ic (nk); the slab partials are added in ascending order; a workgroup per subspace then forms nk + 10 eps, w, log w
+//            and divides the means.  cov: A = r_ic (x_i - mu_c), B = (x_i - mu_c); the combine divides by nk and adds reg_covar
+//            on the diagonal.
 //   logdet   a workgroup per entry: sum_j log L[j, j] in a fixed order.
-//   estep    a workgroup per (subspace, 64 rows), a wave 16 rows, loops over the C components.  A component is the triangular
-//            product of vgan_maha_scores (K slabs of 32 through LDS at a row stride of 34 doubles, K blocks above the diagonal
-//            of a 16-wide tile and tiles wholly past d_s skipped, squared and summed in the registers, the float64 d^2 never rounded); its log
+//   estep    a workgroup per (subspace, 64 rows), a wave 16 rows, loops over the C components.  A component is the staged
+//            lower-triangular product of outlier_moments.hpp (vgan_maha_scores', the float64 d^2 never rounded); its log
 //            probability goes to LDS [32][64].  The lane that owns a row then takes the maximum, the sum of exponentials (c
 //            ascending) and ln_i, writes the responsibilities (as exp(lp - max) / sum) and / or float32(-ln_i), and the
 //            workgroup writes the sum of its 64 ln_i (a fixed butterfly over the 16 rows of a wave, the four waves in order).
@@ -27,20 +25,13 @@
 #include <float.h>
 #include <math.h>
 
-#include <algorithm>
-
-#include "vgan_common.hpp"
+#include "outlier_moments.hpp"
 
 namespace vgan {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kGmmSlab = VGAN_MAHA_SLAB_ROWS;  // rows of a moment slab
-constexpr int kGmmT = 16;                      // tile edge of the f64 MFMA
-constexpr int kGmmBR = 64, kGmmBI = 64, kGmmKC = 32;  // estep: rows, columns of Y and K per staged slab
 constexpr int kGmmMaxC = VGAN_GMM_MAX_COMPONENTS;
 constexpr double kGmmLog2Pi = 1.8378770664093454835606594728112;
-static_assert(kGmmSlab % kGmmBR == 0, "a slab is a whole number of E-step workgroups");
+static_assert(kMomSlab % kMomBR == 0, "a slab is a whole number of E-step workgroups");
 
 // part[slab, entry feature]: sum over the rows of the slab of r x, rows in order; part[slab, total_dims + entry]: sum of r
 __global__ __launch_bounds__(kBlock) void gmm_sum_kernel(const float* __restrict__ X, long ldx, int n, const int32_t* __restrict__ feat,
@@ -50,21 +41,9 @@ __global__ __launch_bounds__(kBlock) void gmm_sum_kernel(const float* __restrict
     const int rel = blockIdx.y, e = first * C + rel;
     if (done && done[e / C]) return;
     const int f0 = feat_off[e], ds = feat_off[e + 1] - f0, base = f0 - feat_off[first * C];
-    const long r0 = (long)(slab0 + blockIdx.x) * kGmmSlab;
-    const int rows = (int)min((long)kGmmSlab, (long)n - r0);
-    const double* w = resp + (long)rel * n + r0;
+    const long r0 = (long)(slab0 + blockIdx.x) * kMomSlab;
     double* out = part + (long)blockIdx.x * (total_dims + entries);
-    for (int f = threadIdx.x; f <= ds; f += kBlock) {
-        double a = 0.0;
-        if (f < ds) {
-            const float* col = X + r0 * ldx + feat[f0 + f];
-            for (int r = 0; r < rows; ++r) a += w[r] * (double)col[(long)r * ldx];
-            out[base + f] = a;
-        } else {
-            for (int r = 0; r < rows; ++r) a += w[r];
-            out[total_dims + rel] = a;
-        }
-    }
+    moment_sum_slab(X, ldx, n, feat, f0, ds, r0, WeightedRows{resp + (long)rel * n + r0}, out + base, out + total_dims + rel);
 }
 
 // mean, nk (+)= the slab partials in ascending order (raw sums: gmm_weights_kernel finishes them)
@@ -79,9 +58,7 @@ __global__ __launch_bounds__(kBlock) void gmm_sum_combine_kernel(const double* _
     if (f > ds) return;
     double* dst = f < ds ? mean + f0 + f : nk + e;
     const double* src = part + (f < ds ? base + f : total_dims + rel);
-    double a = first_chunk ? 0.0 : *dst;
-    for (int q = 0; q < nslabs; ++q) a += src[(long)q * (total_dims + entries)];
-    *dst = a;
+    *dst = slab_total(first_chunk ? 0.0 : *dst, src, nslabs, total_dims + entries);
 }
 
 // per subspace: nk_c = sum + 10 eps, w_c = nk_c / sum_c nk_c (c ascending), log w_c, mu_c = sum / nk_c
@@ -115,39 +92,12 @@ __global__ __launch_bounds__(kBlock) void gmm_cov_kernel(const float* __restrict
                                                          const int32_t* __restrict__ feat_off, const int32_t* __restrict__ tiles, int first,
                                                          int C, const double* __restrict__ resp, const int32_t* __restrict__ done, int slab0,
                                                          const double* __restrict__ mean, double* __restrict__ part) {
-    __shared__ double red[kBlock / kWave][kGmmT * kGmmT];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int32_t* tl = tiles + 3L * blockIdx.x;
-    const int e = tl[0], ti = tl[1], tj = tl[2];
+    const int e = tl[0];
     if (done && done[e / C]) return;
-    const int f0 = feat_off[e], ds = feat_off[e + 1] - f0;
-    const int fa = ti * kGmmT + (lane & 15), fb = tj * kGmmT + (lane & 15);
-    const bool va = fa < ds, vb = fb < ds;
-    const int ca = va ? feat[f0 + fa] : 0, cb = vb ? feat[f0 + fb] : 0;
-    const double ma = va ? mean[f0 + fa] : 0.0, mb = vb ? mean[f0 + fb] : 0.0;
-    const double* w = resp + (long)(e - first * C) * n;
-    const long rbase = (long)(slab0 + blockIdx.y) * kGmmSlab + (long)wave * (kGmmSlab / 4);
-    const long rend = min((long)n, rbase + kGmmSlab / 4);
-    f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (long r16 = rbase; r16 < rend; r16 += 16) {  // the same trip count for the whole wave; rows past rend are zero operands
-        double a[4], b[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const long row = r16 + 4 * q + (lane >> 4);
-            const bool ok = row < rend;
-            const double r = ok ? w[row] : 0.0;
-            a[q] = (ok && va) ? r * ((double)X[row * ldx + ca] - ma) : 0.0;
-            b[q] = (ok && vb) ? (double)X[row * ldx + cb] - mb : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[q], acc, 0, 0, 0);
-    }
-    // f64 result layout: column = lane & 15, row = (lane >> 4) + 4 i
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][((lane >> 4) + 4 * i) * kGmmT + (lane & 15)] = acc[i];
-    __syncthreads();
-    const int t = threadIdx.x;
-    part[((long)blockIdx.y * gridDim.x + blockIdx.x) * (kGmmT * kGmmT) + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    const int f0 = feat_off[e];
+    moment_cov_tile(X, ldx, n, feat, f0, feat_off[e + 1] - f0, tl[1], tl[2], WeightedRows{resp + (long)(e - first * C) * n},
+                    slab0 + blockIdx.y, mean, part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (kMomT * kMomT));
 }
 
 // cov (+)= the slab partials in ascending order, lower triangle and its mirror; the last call divides by nk and adds reg_covar
@@ -159,11 +109,11 @@ __global__ __launch_bounds__(kBlock) void gmm_cov_combine_kernel(const double* _
     const int e = tl[0], t = threadIdx.x;
     if (done && done[e / C]) return;
     const int ds = feat_off[e + 1] - feat_off[e];
-    const int i = tl[1] * kGmmT + t / kGmmT, j = tl[2] * kGmmT + t % kGmmT;
+    const int i = tl[1] * kMomT + t / kMomT, j = tl[2] * kMomT + t % kMomT;
     if (i >= ds || j >= ds || j > i) return;
     double* S = cov + sq_off[e];
-    double a = first_chunk ? 0.0 : S[(long)i * ds + j];
-    for (int q = 0; q < nslabs; ++q) a += part[((long)q * gridDim.x + blockIdx.x) * (kGmmT * kGmmT) + t];
+    double a = slab_total(first_chunk ? 0.0 : S[(long)i * ds + j], part + (long)blockIdx.x * (kMomT * kMomT) + t, nslabs,
+                          (long)gridDim.x * (kMomT * kMomT));
     if (last) {
         a /= nk[e];
         if (i == j) a += reg_covar;
@@ -191,64 +141,22 @@ __global__ __launch_bounds__(kBlock) void gmm_estep_kernel(const float* __restri
                                                            const double* __restrict__ logdet, const double* __restrict__ logw,
                                                            const int32_t* __restrict__ done, double* __restrict__ resp,
                                                            double* __restrict__ lbpart, int nblocks, float* __restrict__ score, long ld_score) {
-    // a row stride of 34 doubles: the 32 lanes of a half-wave (16 rows x 2 k) read 32 different bank pairs
-    __shared__ double zs[kGmmBR][kGmmKC + 2];  // centred rows [row][k]
-    __shared__ double ws[kGmmBI][kGmmKC + 2];  // W [i][k]
-    __shared__ double lps[kGmmMaxC][kGmmBR];   // log w_c N(x_row; c): written and read by the lane that owns the row
+    __shared__ double lps[kGmmMaxC][kMomBR];  // log w_c N(x_row; c): written and read by the lane that owns the row
     __shared__ double red[kBlock / kWave];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = first + blockIdx.y;
     if (done && done[s]) return;
-    const long r0 = (long)blockIdx.x * kGmmBR;
-    const int slot = wave * kGmmT + (lane & 15);
+    const long r0 = (long)blockIdx.x * kMomBR;
+    const int slot = wave * kMomT + (lane & 15);
     for (int c = 0; c < C; ++c) {
         const int e = s * C + c;
         const int f0 = feat_off[e], d = feat_off[e + 1] - f0;
-        const double* W = Wall + sq_off[e];
-        double total = 0.0;
-        for (int i0 = 0; i0 < d; i0 += kGmmBI) {
-            f64x4 acc[kGmmBI / kGmmT];
-#pragma unroll
-            for (int t = 0; t < kGmmBI / kGmmT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-            const int kend = min(d, i0 + kGmmBI);
-            for (int k0 = 0; k0 < kend; k0 += kGmmKC) {
-                __syncthreads();  // the previous slab has been read
-                for (int q = tid; q < kGmmBR * kGmmKC; q += kBlock) {
-                    const int rr = q / kGmmKC, kk = q % kGmmKC;
-                    const bool ok = r0 + rr < rows && k0 + kk < d;
-                    zs[rr][kk] = ok ? (double)Xq[(r0 + rr) * ldq + feat[f0 + k0 + kk]] - mean[f0 + k0 + kk] : 0.0;
-                }
-                for (int q = tid; q < kGmmBI * kGmmKC; q += kBlock) {
-                    const int ii = q / kGmmKC, kk = q % kGmmKC;
-                    const bool ok = i0 + ii < d && k0 + kk <= i0 + ii;
-                    ws[ii][kk] = ok ? W[(long)(i0 + ii) * d + k0 + kk] : 0.0;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int t = 0; t < kGmmBI / kGmmT; ++t) {
-                    const int top = i0 + t * kGmmT + kGmmT - 1;  // the last column of the tile: K blocks past it are above the diagonal
-                    if (top - (kGmmT - 1) >= d) break;           // the tile lies wholly past d_s (the same for the whole workgroup)
-#pragma unroll
-                    for (int ks = 0; ks < kGmmKC; ks += 4) {
-                        if (k0 + ks > top) break;
-                        const int kk = ks + (lane >> 4);
-                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ws[t * kGmmT + (lane & 15)][kk], zs[slot][kk], acc[t], 0, 0, 0);
-                    }
-                }
-            }
-            // result layout: column = lane & 15 (the data row), row = (lane >> 4) + 4 j (the column i of Y)
-#pragma unroll
-            for (int t = 0; t < kGmmBI / kGmmT; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) total += acc[t][j] * acc[t][j];
-        }
-        total += __shfl_xor(total, 16, 64);
-        total += __shfl_xor(total, 32, 64);
-        if (lane < kGmmT) lps[c][slot] = -0.5 * ((double)d * kGmmLog2Pi + total) - logdet[e] + logw[e];
+        const double total = tri_product_sqnorm(Xq, ldq, rows, r0, feat, f0, d, mean, Wall + sq_off[e]);
+        if (lane < kMomT) lps[c][slot] = -0.5 * ((double)d * kGmmLog2Pi + total) - logdet[e] + logw[e];
     }
     double ln = 0.0;
     const long row = r0 + slot;
-    if (lane < kGmmT && row < rows) {
+    if (lane < kMomT && row < rows) {
         double m = lps[0][slot];
         for (int c = 1; c < C; ++c) m = fmax(m, lps[c][slot]);
         double sum = 0.0;
@@ -275,7 +183,7 @@ __global__ __launch_bounds__(kBlock) void gmm_converge_kernel(double* __restrict
                                                               double* __restrict__ lower_bound, double* __restrict__ lb_prev) {
     const int s = first + blockIdx.x, tid = threadIdx.x;
     if (done[s]) return;  // the same for the whole workgroup: thread 0 writes it only after the last barrier
-    constexpr int per = kGmmSlab / kGmmBR;
+    constexpr int per = kMomSlab / kMomBR;
     double* part = lbpart + (long)blockIdx.x * nblocks;
     const int nslabs = (nblocks + per - 1) / per;
     if (it > 0) {
@@ -325,40 +233,32 @@ extern "C" int vgan_gmm_moments(const float* X, int ldx, int n, int d, const int
     const int C = n_components, entries = count * C;
     VGAN_CHECK_ARG(max_dims >= 1 && max_dims <= VGAN_MAHA_MAX_DIMS && total_dims >= entries && total_dims <= (int64_t)entries * max_dims);
     VGAN_CHECK_ARG(n_tiles >= entries);
-    VGAN_CHECK_ARG(workspace_bytes >= 8 * ((int64_t)total_dims + entries) && workspace_bytes >= 8 * kGmmT * kGmmT);
+    VGAN_CHECK_ARG(workspace_bytes >= 8 * ((int64_t)total_dims + entries) && workspace_bytes >= 8 * kMomT * kMomT);
     const hipStream_t st = (hipStream_t)stream;
     double* part = static_cast<double*>(workspace);
-    const int64_t cells = workspace_bytes / 8;
-    const int nslabs = (n + kGmmSlab - 1) / kGmmSlab;
-
-    const int64_t width = (int64_t)total_dims + entries;
-    const int per_sum = (int)std::min<int64_t>(nslabs, cells / width);
     const dim3 mgrid((max_dims + 1 + kBlock - 1) / kBlock, entries);
-    for (int j0 = 0; j0 < nslabs; j0 += per_sum) {
-        const int nj = std::min(per_sum, nslabs - j0);
-        hipLaunchKernelGGL(gmm_sum_kernel, dim3(nj, entries), dim3(kBlock), 0, st, X, (long)ldx, n, feat, feat_off, first, C, resp, done, j0,
-                           part, total_dims, entries);
-        hipLaunchKernelGGL(gmm_sum_combine_kernel, mgrid, dim3(kBlock), 0, st, part, nj, total_dims, entries, feat_off, first, C, done, mean, nk,
-                           j0 == 0 ? 1 : 0);
-        VGAN_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(gmm_weights_kernel, dim3(count), dim3(kBlock), 0, st, feat_off, first, C, done, mean, nk, weights, log_weights);
-    VGAN_CHECK_LAUNCH();
-    const int64_t tile_cells = kGmmT * kGmmT;
-    const int per_tiles = (int)std::min<int64_t>(n_tiles, cells / tile_cells);
-    const int per_cov = (int)std::min<int64_t>(std::min(nslabs, 65535), cells / (tile_cells * per_tiles));
-    for (int t0 = 0; t0 < n_tiles; t0 += per_tiles) {
-        const int nt = std::min(per_tiles, n_tiles - t0);
-        for (int j0 = 0; j0 < nslabs; j0 += per_cov) {
-            const int nj = std::min(per_cov, nslabs - j0);
+    return moment_chunks(
+        n, workspace_bytes / 8, (int64_t)total_dims + entries, n_tiles,
+        [&](int j0, int nj, int first_chunk, int last) {
+            hipLaunchKernelGGL(gmm_sum_kernel, dim3(nj, entries), dim3(kBlock), 0, st, X, (long)ldx, n, feat, feat_off, first, C, resp, done, j0,
+                               part, total_dims, entries);
+            hipLaunchKernelGGL(gmm_sum_combine_kernel, mgrid, dim3(kBlock), 0, st, part, nj, total_dims, entries, feat_off, first, C, done, mean,
+                               nk, first_chunk);
+            VGAN_CHECK_LAUNCH();
+            if (last) {  // the sums are whole: nk, the weights and the means
+                hipLaunchKernelGGL(gmm_weights_kernel, dim3(count), dim3(kBlock), 0, st, feat_off, first, C, done, mean, nk, weights, log_weights);
+                VGAN_CHECK_LAUNCH();
+            }
+            return VGAN_OK;
+        },
+        [&](int t0, int nt, int j0, int nj, int first_chunk, int last) {
             hipLaunchKernelGGL(gmm_cov_kernel, dim3(nt, nj), dim3(kBlock), 0, st, X, (long)ldx, n, feat, feat_off, tiles + 3L * t0, first, C, resp,
                                done, j0, mean, part);
             hipLaunchKernelGGL(gmm_cov_combine_kernel, dim3(nt), dim3(kBlock), 0, st, part, nj, tiles + 3L * t0, feat_off, sq_off, C, done, nk,
-                               reg_covar, cov, j0 == 0 ? 1 : 0, j0 + nj == nslabs ? 1 : 0);
+                               reg_covar, cov, first_chunk, last);
             VGAN_CHECK_LAUNCH();
-        }
-    }
-    return VGAN_OK;
+            return VGAN_OK;
+        });
 }
 
 extern "C" int vgan_gmm_logdet(const double* L, const int32_t* feat_off, const int64_t* sq_off, int n_components, int first, int count,
@@ -378,7 +278,7 @@ extern "C" int vgan_gmm_estep(const float* Xq, int ldq, int rows, int d, const i
     VGAN_CHECK_ARG((resp || score) && (!score || ld_score >= rows) && (!lb_partial || resp));
     VGAN_CHECK_ARG(d > 0 && ldq >= d && rows > 0 && rows <= VGAN_MAHA_MAX_ROWS);
     VGAN_CHECK_ARG(max_dims >= 1 && max_dims <= VGAN_MAHA_MAX_DIMS);
-    const int nblocks = (rows + kGmmBR - 1) / kGmmBR;
+    const int nblocks = (rows + kMomBR - 1) / kMomBR;
     hipLaunchKernelGGL(gmm_estep_kernel, dim3(nblocks, count), dim3(kBlock), 0, (hipStream_t)stream, Xq, (long)ldq, rows, feat, feat_off, sq_off,
                        first, n_components, mean, W, logdet, log_weights, done, resp, lb_partial, nblocks, score, (long)ld_score);
     VGAN_CHECK_LAUNCH();
@@ -390,7 +290,7 @@ extern "C" int vgan_gmm_converge(double* lb_partial, int n, int n_components, in
                                  vgan_stream_t stream) {
     VGAN_CHECK_ARG(status && done && n_iter && lower_bound && lb_prev && gmm_range_ok(first, count, n_components));
     VGAN_CHECK_ARG(n >= 2 && n <= VGAN_MAHA_MAX_ROWS && tol >= 0.0 && iteration >= 0 && (iteration == 0 || lb_partial));
-    hipLaunchKernelGGL(gmm_converge_kernel, dim3(count), dim3(kBlock), 0, (hipStream_t)stream, lb_partial, (n + kGmmBR - 1) / kGmmBR, n, first,
+    hipLaunchKernelGGL(gmm_converge_kernel, dim3(count), dim3(kBlock), 0, (hipStream_t)stream, lb_partial, (n + kMomBR - 1) / kMomBR, n, first,
                        n_components, status, tol, iteration, done, n_iter, lower_bound, lb_prev);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;

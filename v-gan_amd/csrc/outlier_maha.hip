@@ -3,12 +3,10 @@
 // is float64 on the float32 data; every sum has a fixed order and there is no float atomic, so every published bit is the
 // same from run to run and for every workspace.  The contract is the header's and the SubspaceMahalanobis docstring.
 //
-//   moments  rows are cut into slabs of kMahaSlab rows, by n alone.  sum: a thread per feature adds the supported rows of
-//            a slab in order; cov: a workgroup per (lower-triangle 16 x 16 tile, slab), each wave 256 rows of the slab, four
-//            rows per v_mfma_f64_16x16x4_f64 with A = B^T = the centred rows gathered through the feature table (a row
-//            outside the support, past n or past d_s is a zero operand), the four waves added in order.  The slab partials
-//            go to the workspace and one thread per element adds them in ascending slab order, so the workspace decides
-//            how many slabs a launch takes and never the order of a sum.
+//   moments  rows are cut into slabs of kMomSlab rows, by n alone; the sum, covariance-tile, combine and chunking core is
+//            outlier_moments.hpp's with the support as the row policy (a row outside it is a zero operand).  The slab
+//            partials go to the workspace and one thread per element adds them in ascending slab order, so the workspace
+//            decides how many slabs a launch takes and never the order of a sum; the last combine divides by h_s.
 //   factor   one workgroup per subspace: trace and sum of squares (fixed block reductions), the shrinkage alpha (given or
 //            OAS), Sigma = (1 - alpha) C + alpha (tr C / d) I written over C, then a blocked right-looking Cholesky with
 //            16-wide blocks: the diagonal block is factored in LDS, the panel below it by one thread per row (a 16-step
@@ -16,39 +14,16 @@
 //            instructions a tile, the waves taking tiles in turn).  The panel itself stays in global memory: at d_s = 1024
 //            it is 1008 x 16 doubles = 126 KB, more than a workgroup's static LDS, and the one CU that runs this workgroup
 //            holds it in its cache.  L is then inverted into W a thread per column (forward substitution, k ascending).
-//   scores   a workgroup per (subspace, 64 rows), a wave 16 rows.  Y = Z W^T is formed 64 columns i at a time (four f64
-//            accumulators a wave); for each such group K runs in staged slabs of kMahaKC = 32 up to the group's diagonal:
-//            Z [64 rows, 32] (gathered, centred) and W [64, 32] go through LDS, zero filled past d_s and the rows.  K blocks
-//            above the diagonal of a 16-wide tile are skipped.  Staging K slabs was chosen over a narrower row tile: the LDS
-//            need (34 KB) does not grow with d_s, four workgroups fit a CU, and W is read once per 64 rows instead of once
-//            per 16.  Y is squared and summed in the registers; the float32 store is the only rounding below float64.
-//            An element sees k = 0, 1, 2, ... and then i = 0, 1, 2, ... in the same order wherever its row sits.
+//   scores   a workgroup per (subspace, 64 rows), a wave 16 rows: outlier_moments.hpp's staged lower-triangular product
+//            (34 KB of LDS whatever d_s, so four workgroups fit a CU); the float32 store is the only rounding below float64.
 //   select   one workgroup per subspace: a four-pass radix select on order-preserving keys finds the key of rank h - 1 and
 //            how many rows of that key are wanted; an ordered sweep then marks every smaller key and the first wanted rows of
 //            the equal one in row order, and compares with the previous support.  Integer LDS atomics only.
 #include <math.h>
 
-#include <algorithm>
-
-#include "vgan_common.hpp"
+#include "outlier_moments.hpp"
 
 namespace vgan {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMahaSlab = VGAN_MAHA_SLAB_ROWS;  // rows of a moment slab
-constexpr int kMahaT = 16;                      // tile edge of the f64 MFMA
-constexpr int kMahaBR = 64, kMahaBI = 64, kMahaKC = 32;  // scores: rows, columns of Y and K per staged slab
-
-// float64 sum over the workgroup in a fixed order, valid in every thread
-__device__ __forceinline__ double maha_block_sum(double v, double* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return r;
-}
 
 // part[slab, feature]: the sum of the supported rows of the slab, rows in order
 __global__ __launch_bounds__(kBlock) void maha_sum_kernel(const float* __restrict__ X, long ldx, int n, const int32_t* __restrict__ feat,
@@ -57,19 +32,9 @@ __global__ __launch_bounds__(kBlock) void maha_sum_kernel(const float* __restric
                                                           double* __restrict__ part, int total_dims) {
     const int s = first + blockIdx.y;
     const int f0 = feat_off[s], ds = feat_off[s + 1] - f0, base = f0 - feat_off[first];
-    const long r0 = (long)(slab0 + blockIdx.x) * kMahaSlab;
-    const int rows = (int)min((long)kMahaSlab, (long)n - r0);
-    const uint8_t* sup = support ? support + (long)s * ld_sup + r0 : nullptr;
-    double* out = part + (long)blockIdx.x * total_dims + base;
-    for (int f = threadIdx.x; f < ds; f += kBlock) {
-        const float* col = X + r0 * ldx + feat[f0 + f];
-        double a = 0.0;
-        for (int r = 0; r < rows; ++r) {
-            const double v = (double)col[(long)r * ldx];
-            a += (!sup || sup[r]) ? v : 0.0;
-        }
-        out[f] = a;
-    }
+    const long r0 = (long)(slab0 + blockIdx.x) * kMomSlab;
+    moment_sum_slab(X, ldx, n, feat, f0, ds, r0, SupportRows{support ? support + (long)s * ld_sup + r0 : nullptr},
+                    part + (long)blockIdx.x * total_dims + base, nullptr);
 }
 
 // mean (+)= the slab partials in ascending order; the last call divides by h_s
@@ -81,8 +46,7 @@ __global__ __launch_bounds__(kBlock) void maha_mean_combine_kernel(const double*
     const int f0 = feat_off[s], ds = feat_off[s + 1] - f0, base = f0 - feat_off[first];
     const int f = blockIdx.x * kBlock + threadIdx.x;
     if (f >= ds) return;
-    double a = first_chunk ? 0.0 : mean[f0 + f];
-    for (int q = 0; q < nslabs; ++q) a += part[(long)q * total_dims + base + f];
+    double a = slab_total(first_chunk ? 0.0 : mean[f0 + f], part + base + f, nslabs, total_dims);
     if (last) a /= (double)hcount[s];
     mean[f0 + f] = a;
 }
@@ -92,37 +56,10 @@ __global__ __launch_bounds__(kBlock) void maha_cov_kernel(const float* __restric
                                                           const int32_t* __restrict__ feat_off, const int32_t* __restrict__ tiles,
                                                           const uint8_t* __restrict__ support, long ld_sup, int slab0,
                                                           const double* __restrict__ mean, double* __restrict__ part) {
-    __shared__ double red[kBlock / kWave][kMahaT * kMahaT];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int32_t* tl = tiles + 3L * blockIdx.x;
-    const int s = tl[0], ti = tl[1], tj = tl[2];
-    const int f0 = feat_off[s], ds = feat_off[s + 1] - f0;
-    const int fa = ti * kMahaT + (lane & 15), fb = tj * kMahaT + (lane & 15);
-    const bool va = fa < ds, vb = fb < ds;
-    const int ca = va ? feat[f0 + fa] : 0, cb = vb ? feat[f0 + fb] : 0;
-    const double ma = va ? mean[f0 + fa] : 0.0, mb = vb ? mean[f0 + fb] : 0.0;
-    const uint8_t* sup = support ? support + (long)s * ld_sup : nullptr;
-    const long rbase = (long)(slab0 + blockIdx.y) * kMahaSlab + (long)wave * (kMahaSlab / 4);
-    const long rend = min((long)n, rbase + kMahaSlab / 4);
-    f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (long r16 = rbase; r16 < rend; r16 += 16) {  // the same trip count for the whole wave; rows past rend are zero operands
-        double a[4], b[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {  // the loads of sixteen rows are in flight before the first product needs one
-            const long row = r16 + 4 * q + (lane >> 4);
-            const bool ok = row < rend && (!sup || sup[row]);
-            a[q] = (ok && va) ? (double)X[row * ldx + ca] - ma : 0.0;
-            b[q] = (ok && vb) ? (double)X[row * ldx + cb] - mb : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[q], acc, 0, 0, 0);
-    }
-    // f64 result layout: column = lane & 15, row = (lane >> 4) + 4 i
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][((lane >> 4) + 4 * i) * kMahaT + (lane & 15)] = acc[i];
-    __syncthreads();
-    const int e = threadIdx.x;
-    part[((long)blockIdx.y * gridDim.x + blockIdx.x) * (kMahaT * kMahaT) + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+    const int s = tl[0], f0 = feat_off[s];
+    moment_cov_tile(X, ldx, n, feat, f0, feat_off[s + 1] - f0, tl[1], tl[2], SupportRows{support ? support + (long)s * ld_sup : nullptr},
+                    slab0 + blockIdx.y, mean, part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (kMomT * kMomT));
 }
 
 // cov (+)= the slab partials in ascending order, lower triangle and its mirror; the last call divides by h_s
@@ -133,11 +70,11 @@ __global__ __launch_bounds__(kBlock) void maha_cov_combine_kernel(const double* 
     const int32_t* tl = tiles + 3L * blockIdx.x;
     const int s = tl[0], e = threadIdx.x;
     const int ds = feat_off[s + 1] - feat_off[s];
-    const int i = tl[1] * kMahaT + e / kMahaT, j = tl[2] * kMahaT + e % kMahaT;
+    const int i = tl[1] * kMomT + e / kMomT, j = tl[2] * kMomT + e % kMomT;
     if (i >= ds || j >= ds || j > i) return;
     double* C = cov + sq_off[s];
-    double a = first_chunk ? 0.0 : C[(long)i * ds + j];
-    for (int q = 0; q < nslabs; ++q) a += part[((long)q * gridDim.x + blockIdx.x) * (kMahaT * kMahaT) + e];
+    double a = slab_total(first_chunk ? 0.0 : C[(long)i * ds + j], part + (long)blockIdx.x * (kMomT * kMomT) + e, nslabs,
+                          (long)gridDim.x * (kMomT * kMomT));
     if (last) a /= (double)hcount[s];
     C[(long)i * ds + j] = a;
     C[(long)j * ds + i] = a;
@@ -149,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void maha_factor_kernel(double* cov, const 
                                                              const int32_t* __restrict__ hcount, double shrink, double* Lall, double* Wall,
                                                              double* __restrict__ alpha_out, int32_t* __restrict__ status) {
     __shared__ double red[kBlock / kWave];
-    __shared__ double blk[kMahaT][kMahaT + 1];
+    __shared__ double blk[kMomT][kMomT + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = first + blockIdx.x;
     const int d = feat_off[s + 1] - feat_off[s];
@@ -164,8 +101,8 @@ __global__ __launch_bounds__(kBlock) void maha_factor_kernel(double* cov, const 
         const double c = C[e];
         sq += c * c;
     }
-    tr = maha_block_sum(tr, red);
-    sq = maha_block_sum(sq, red);
+    tr = block_sum_all(tr, red);
+    sq = block_sum_all(sq, red);
     const double m = tr / (double)d;
     double alpha = shrink;
     if (shrink < 0.0) {  // OAS
@@ -193,15 +130,15 @@ __global__ __launch_bounds__(kBlock) void maha_factor_kernel(double* cov, const 
     }
     __syncthreads();
 
-    const int T = (d + kMahaT - 1) / kMahaT;
+    const int T = (d + kMomT - 1) / kMomT;
     const int r = tid >> 4, c = tid & 15;
     bool failed = false;
-    for (int k0 = 0; k0 < d && !failed; k0 += kMahaT) {
-        const int nb = min(kMahaT, d - k0);
+    for (int k0 = 0; k0 < d && !failed; k0 += kMomT) {
+        const int nb = min(kMomT, d - k0);
         // the diagonal block, padded with the identity
         blk[r][c] = (r < nb && c < nb) ? L[(long)(k0 + r) * d + k0 + c] : (r == c ? 1.0 : 0.0);
         __syncthreads();
-        for (int j = 0; j < kMahaT; ++j) {
+        for (int j = 0; j < kMomT; ++j) {
             const double p = blk[j][j];
             if (!(p > 0.0 && p < INFINITY)) {  // the same value in every thread
                 failed = true;
@@ -217,33 +154,33 @@ __global__ __launch_bounds__(kBlock) void maha_factor_kernel(double* cov, const 
         if (failed) break;
         if (r < nb && c < nb) L[(long)(k0 + r) * d + k0 + c] = c <= r ? blk[r][c] : 0.0;
         // the panel below the block: row i solves x L_kk^T = A[i, k0 : k0 + 16]
-        for (int i = k0 + kMahaT + tid; i < d; i += kBlock) {
+        for (int i = k0 + kMomT + tid; i < d; i += kBlock) {
             double* row = L + (long)i * d + k0;
-            double x[kMahaT];
+            double x[kMomT];
 #pragma unroll
-            for (int q = 0; q < kMahaT; ++q) x[q] = row[q];
+            for (int q = 0; q < kMomT; ++q) x[q] = row[q];
 #pragma unroll
-            for (int q = 0; q < kMahaT; ++q) {
+            for (int q = 0; q < kMomT; ++q) {
                 double v = x[q];
 #pragma unroll
                 for (int p = 0; p < q; ++p) v -= x[p] * blk[q][p];
                 x[q] = v / blk[q][q];
             }
 #pragma unroll
-            for (int q = 0; q < kMahaT; ++q) row[q] = x[q];
+            for (int q = 0; q < kMomT; ++q) row[q] = x[q];
         }
         __syncthreads();  // the panel is visible to the workgroup
         // the trailing lower triangle, tile (ti, tj) with k0 / 16 < tj <= ti < T: A -= P_ti P_tj^T
-        const int kb = k0 / kMahaT, cnt = T - kb - 1, ntile = cnt * (cnt + 1) / 2;
+        const int kb = k0 / kMomT, cnt = T - kb - 1, ntile = cnt * (cnt + 1) / 2;
         for (int q = wave; q < ntile; q += kBlock / kWave) {
             int a = (int)((sqrtf(8.f * (float)q + 1.f) - 1.f) * 0.5f);
             while ((a + 1) * (a + 2) / 2 <= q) ++a;
             while (a * (a + 1) / 2 > q) --a;
             const int ti = kb + 1 + a, tj = kb + 1 + q - a * (a + 1) / 2;
-            const int ia = ti * kMahaT + (lane & 15), ib = tj * kMahaT + (lane & 15);
+            const int ia = ti * kMomT + (lane & 15), ib = tj * kMomT + (lane & 15);
             f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int ks = 0; ks < kMahaT; ks += 4) {
+            for (int ks = 0; ks < kMomT; ks += 4) {
                 const int kk = k0 + ks + (lane >> 4);
                 const double pa = ia < d ? L[(long)ia * d + kk] : 0.0;
                 const double pb = ib < d ? L[(long)ib * d + kk] : 0.0;
@@ -251,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void maha_factor_kernel(double* cov, const 
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const int i = ti * kMahaT + (lane >> 4) + 4 * t, j = tj * kMahaT + (lane & 15);
+                const int i = ti * kMomT + (lane >> 4) + 4 * t, j = tj * kMomT + (lane & 15);
                 if (i < d && j < d && j <= i) L[(long)i * d + j] -= acc[t];
             }
         }
@@ -279,54 +216,12 @@ __global__ __launch_bounds__(kBlock) void maha_scores_kernel(const float* __rest
                                                              const int32_t* __restrict__ feat_off, const int64_t* __restrict__ sq_off,
                                                              int first, const double* __restrict__ mean, const double* __restrict__ Wall,
                                                              float* __restrict__ score, long ld_score) {
-    // a row stride of 34 doubles: the 32 lanes of a half-wave (16 rows x 2 k) read 32 different bank pairs
-    __shared__ double zs[kMahaBR][kMahaKC + 2];  // centred rows [row][k]
-    __shared__ double ws[kMahaBI][kMahaKC + 2];  // W [i][k]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = first + blockIdx.y;
     const int f0 = feat_off[s], d = feat_off[s + 1] - f0;
-    const double* W = Wall + sq_off[s];
-    const long r0 = (long)blockIdx.x * kMahaBR;
-    double total = 0.0;
-    for (int i0 = 0; i0 < d; i0 += kMahaBI) {
-        f64x4 acc[kMahaBI / kMahaT];
-#pragma unroll
-        for (int t = 0; t < kMahaBI / kMahaT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-        const int kend = min(d, i0 + kMahaBI);
-        for (int k0 = 0; k0 < kend; k0 += kMahaKC) {
-            __syncthreads();  // the previous slab has been read
-            for (int e = tid; e < kMahaBR * kMahaKC; e += kBlock) {
-                const int rr = e / kMahaKC, kk = e % kMahaKC;
-                const bool ok = r0 + rr < rows && k0 + kk < d;
-                zs[rr][kk] = ok ? (double)Xq[(r0 + rr) * ldq + feat[f0 + k0 + kk]] - mean[f0 + k0 + kk] : 0.0;
-            }
-            for (int e = tid; e < kMahaBI * kMahaKC; e += kBlock) {
-                const int ii = e / kMahaKC, kk = e % kMahaKC;
-                const bool ok = i0 + ii < d && k0 + kk <= i0 + ii;
-                ws[ii][kk] = ok ? W[(long)(i0 + ii) * d + k0 + kk] : 0.0;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < kMahaBI / kMahaT; ++t) {
-                const int top = i0 + t * kMahaT + kMahaT - 1;  // the last column of the tile: K blocks past it are above the diagonal
-#pragma unroll
-                for (int ks = 0; ks < kMahaKC; ks += 4) {
-                    if (k0 + ks > top) break;
-                    const int kk = ks + (lane >> 4);
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ws[t * kMahaT + (lane & 15)][kk], zs[wave * kMahaT + (lane & 15)][kk],
-                                                                  acc[t], 0, 0, 0);
-                }
-            }
-        }
-        // result layout: column = lane & 15 (the data row), row = (lane >> 4) + 4 j (the column i of Y)
-#pragma unroll
-        for (int t = 0; t < kMahaBI / kMahaT; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) total += acc[t][j] * acc[t][j];
-    }
-    total += __shfl_xor(total, 16, 64);
-    total += __shfl_xor(total, 32, 64);
-    const long row = r0 + wave * kMahaT + (lane & 15);
+    const long r0 = (long)blockIdx.x * kMomBR;
+    const double total = tri_product_sqnorm(Xq, ldq, rows, r0, feat, f0, d, mean, Wall + sq_off[s]);
+    const long row = r0 + wave * kMomT + (lane & 15);
     if (lane < 16 && row < rows) score[(long)s * ld_score + row] = (float)total;
 }
 
@@ -415,37 +310,28 @@ extern "C" int vgan_maha_moments(const float* X, int ldx, int n, int d, const in
     VGAN_CHECK_ARG(d > 0 && ldx >= d && n >= 2 && n <= VGAN_MAHA_MAX_ROWS && maha_range_ok(first, count));
     VGAN_CHECK_ARG(max_dims >= 1 && max_dims <= VGAN_MAHA_MAX_DIMS && total_dims >= count && total_dims <= (int64_t)count * max_dims);
     VGAN_CHECK_ARG(n_tiles >= count && (!support || ld_support >= n));
-    VGAN_CHECK_ARG(workspace_bytes >= 8 * (int64_t)total_dims && workspace_bytes >= 8 * kMahaT * kMahaT);
+    VGAN_CHECK_ARG(workspace_bytes >= 8 * (int64_t)total_dims && workspace_bytes >= 8 * kMomT * kMomT);
     const hipStream_t st = (hipStream_t)stream;
     double* part = static_cast<double*>(workspace);
-    const int64_t cells = workspace_bytes / 8;
-    const int nslabs = (n + kMahaSlab - 1) / kMahaSlab;
-
-    const int per_sum = (int)std::min<int64_t>(nslabs, cells / total_dims);
     const dim3 mgrid((max_dims + kBlock - 1) / kBlock, count);
-    for (int j0 = 0; j0 < nslabs; j0 += per_sum) {
-        const int nj = std::min(per_sum, nslabs - j0);
-        hipLaunchKernelGGL(maha_sum_kernel, dim3(nj, count), dim3(kBlock), 0, st, X, (long)ldx, n, feat, feat_off, first, support,
-                           (long)ld_support, j0, part, total_dims);
-        hipLaunchKernelGGL(maha_mean_combine_kernel, mgrid, dim3(kBlock), 0, st, part, nj, total_dims, feat_off, first, hcount, mean,
-                           j0 == 0 ? 1 : 0, j0 + nj == nslabs ? 1 : 0);
-        VGAN_CHECK_LAUNCH();
-    }
-    const int64_t tile_cells = kMahaT * kMahaT;
-    const int per_tiles = (int)std::min<int64_t>(n_tiles, cells / tile_cells);
-    const int per_cov = (int)std::min<int64_t>(std::min(nslabs, 65535), cells / (tile_cells * per_tiles));
-    for (int t0 = 0; t0 < n_tiles; t0 += per_tiles) {
-        const int nt = std::min(per_tiles, n_tiles - t0);
-        for (int j0 = 0; j0 < nslabs; j0 += per_cov) {
-            const int nj = std::min(per_cov, nslabs - j0);
+    return moment_chunks(
+        n, workspace_bytes / 8, total_dims, n_tiles,
+        [&](int j0, int nj, int first_chunk, int last) {
+            hipLaunchKernelGGL(maha_sum_kernel, dim3(nj, count), dim3(kBlock), 0, st, X, (long)ldx, n, feat, feat_off, first, support,
+                               (long)ld_support, j0, part, total_dims);
+            hipLaunchKernelGGL(maha_mean_combine_kernel, mgrid, dim3(kBlock), 0, st, part, nj, total_dims, feat_off, first, hcount, mean,
+                               first_chunk, last);
+            VGAN_CHECK_LAUNCH();
+            return VGAN_OK;
+        },
+        [&](int t0, int nt, int j0, int nj, int first_chunk, int last) {
             hipLaunchKernelGGL(maha_cov_kernel, dim3(nt, nj), dim3(kBlock), 0, st, X, (long)ldx, n, feat, feat_off, tiles + 3L * t0, support,
                                (long)ld_support, j0, mean, part);
             hipLaunchKernelGGL(maha_cov_combine_kernel, dim3(nt), dim3(kBlock), 0, st, part, nj, tiles + 3L * t0, feat_off, sq_off, hcount, cov,
-                               j0 == 0 ? 1 : 0, j0 + nj == nslabs ? 1 : 0);
+                               first_chunk, last);
             VGAN_CHECK_LAUNCH();
-        }
-    }
-    return VGAN_OK;
+            return VGAN_OK;
+        });
 }
 
 extern "C" int vgan_maha_factor(double* cov, const int64_t* sq_off, const int32_t* feat_off, int first, int count, int max_dims,
@@ -466,7 +352,7 @@ extern "C" int vgan_maha_scores(const float* Xq, int ldq, int rows, int d, const
     VGAN_CHECK_ARG(Xq && feat && feat_off && sq_off && mean && W && score && maha_range_ok(first, count));
     VGAN_CHECK_ARG(d > 0 && ldq >= d && rows > 0 && rows <= VGAN_MAHA_MAX_ROWS && ld_score >= rows);
     VGAN_CHECK_ARG(max_dims >= 1 && max_dims <= VGAN_MAHA_MAX_DIMS);
-    const dim3 grid((rows + kMahaBR - 1) / kMahaBR, count);
+    const dim3 grid((rows + kMomBR - 1) / kMomBR, count);
     hipLaunchKernelGGL(maha_scores_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, Xq, (long)ldq, rows, feat, feat_off, sq_off, first, mean,
                        W, score, (long)ld_score);
     VGAN_CHECK_LAUNCH();

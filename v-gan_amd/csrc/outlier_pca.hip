@@ -22,23 +22,19 @@
 //            Then lambda_j = m_jj; rank_j = #{k : lambda_k > lambda_j or (lambda_k == lambda_j and k < j)} (descending, ties by
 //            the ascending diagonal position); a wave per component finds the entry of largest magnitude (lowest index on a
 //            tie) and writes the row to its rank, negated if that entry is negative.
-//   scores   maha_scores_kernel's staging (a workgroup per (subspace, 64 rows), 64 components a group, K in staged slabs of
-//            32 through LDS) with a full K range, z_k = (x_k - mu_k) inv_scale_k, and the weights of the group in LDS: a 16-row
+//   scores   the staging of outlier_moments.hpp's triangular product and its constants (a workgroup per (subspace, 64 rows), 64
+//            components a group, K in staged slabs of 32 through LDS) with a full K range, z_k = (x_k - mu_k) inv_scale_k, and the weights of the group in LDS: a 16-row
 //            tile of V whose weights are all 0 issues no MFMA, a group of 64 without weight is not staged.  A lane adds w_j
 //            y_j^2 over its components in ascending order (j = (lane >> 4) + 4 i of each tile, tiles ascending), then the
 //            four lane groups are added as (g + g^1) + (g^2 + g^3).  Which tiles are skipped depends on wt alone.
 #include <math.h>
 
-#include "vgan_common.hpp"
+#include "outlier_moments.hpp"
 
 namespace vgan {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kPcaLds = VGAN_PCA_LDS_DIMS;               // the widest subspace whose M and V live in LDS
 constexpr int kPcaMaxPairs = VGAN_MAHA_MAX_DIMS / 2;     // pairs of a round
-constexpr int kPcaT = 16;                                // tile edge of the f64 MFMA
-constexpr int kPcaBR = 64, kPcaBI = 64, kPcaKC = 32;     // scores: rows, components and K per staged slab
 constexpr double kPcaU = 1.1102230246251565e-16;         // 2^-53
 
 __device__ __forceinline__ int pca_player(int pos, int r, int n) { return pos == 0 ? n - 1 : (pos - 1 + r) % (n - 1); }
@@ -223,65 +219,65 @@ __global__ __launch_bounds__(kBlock) void pca_scores_kernel(const float* __restr
                                                             const double* __restrict__ Vall, const double* __restrict__ wt,
                                                             float* __restrict__ score, long ld_score) {
     // a row stride of 34 doubles: the 32 lanes of a half-wave (16 rows x 2 k) read 32 different bank pairs
-    __shared__ double zs[kPcaBR][kPcaKC + 2];  // standardised rows [row][k]
-    __shared__ double vs[kPcaBI][kPcaKC + 2];  // V [j][k]
-    __shared__ double wl[kPcaBI];              // the weights of the group
+    __shared__ double zs[kMomBR][kMomKC + 2];  // standardised rows [row][k]
+    __shared__ double vs[kMomBI][kMomKC + 2];  // V [j][k]
+    __shared__ double wl[kMomBI];              // the weights of the group
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = first + blockIdx.y;
     const int f0 = feat_off[s], d = feat_off[s + 1] - f0;
     const double* V = Vall + sq_off[s];
-    const long r0 = (long)blockIdx.x * kPcaBR;
+    const long r0 = (long)blockIdx.x * kMomBR;
     double total = 0.0;
-    for (int i0 = 0; i0 < d; i0 += kPcaBI) {
+    for (int i0 = 0; i0 < d; i0 += kMomBI) {
         __syncthreads();  // the previous group's weights have been read
-        if (tid < kPcaBI) wl[tid] = i0 + tid < d ? wt[f0 + i0 + tid] : 0.0;
+        if (tid < kMomBI) wl[tid] = i0 + tid < d ? wt[f0 + i0 + tid] : 0.0;
         __syncthreads();
-        bool act[kPcaBI / kPcaT], any = false;
+        bool act[kMomBI / kMomT], any = false;
 #pragma unroll
-        for (int t = 0; t < kPcaBI / kPcaT; ++t) {
+        for (int t = 0; t < kMomBI / kMomT; ++t) {
             act[t] = false;
-            for (int q = 0; q < kPcaT; ++q) act[t] |= wl[t * kPcaT + q] != 0.0;
+            for (int q = 0; q < kMomT; ++q) act[t] |= wl[t * kMomT + q] != 0.0;
             any |= act[t];
         }
         if (!any) continue;  // the same in every thread: it depends on wt alone
-        f64x4 acc[kPcaBI / kPcaT];
+        f64x4 acc[kMomBI / kMomT];
 #pragma unroll
-        for (int t = 0; t < kPcaBI / kPcaT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-        for (int k0 = 0; k0 < d; k0 += kPcaKC) {
+        for (int t = 0; t < kMomBI / kMomT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+        for (int k0 = 0; k0 < d; k0 += kMomKC) {
             __syncthreads();  // the previous slab has been read
-            for (int e = tid; e < kPcaBR * kPcaKC; e += kBlock) {
-                const int rr = e / kPcaKC, kk = e % kPcaKC;
+            for (int e = tid; e < kMomBR * kMomKC; e += kBlock) {
+                const int rr = e / kMomKC, kk = e % kMomKC;
                 const bool ok = r0 + rr < rows && k0 + kk < d;
                 zs[rr][kk] = ok ? ((double)Xq[(r0 + rr) * ldq + feat[f0 + k0 + kk]] - mean[f0 + k0 + kk]) * inv_scale[f0 + k0 + kk] : 0.0;
             }
-            for (int e = tid; e < kPcaBI * kPcaKC; e += kBlock) {
-                const int ii = e / kPcaKC, kk = e % kPcaKC;
+            for (int e = tid; e < kMomBI * kMomKC; e += kBlock) {
+                const int ii = e / kMomKC, kk = e % kMomKC;
                 const bool ok = i0 + ii < d && k0 + kk < d;
                 vs[ii][kk] = ok ? V[(long)(i0 + ii) * d + k0 + kk] : 0.0;
             }
             __syncthreads();
 #pragma unroll
-            for (int t = 0; t < kPcaBI / kPcaT; ++t) {
+            for (int t = 0; t < kMomBI / kMomT; ++t) {
                 if (!act[t]) continue;
 #pragma unroll
-                for (int ks = 0; ks < kPcaKC; ks += 4) {
+                for (int ks = 0; ks < kMomKC; ks += 4) {
                     const int kk = ks + (lane >> 4);
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(vs[t * kPcaT + (lane & 15)][kk], zs[wave * kPcaT + (lane & 15)][kk], acc[t],
+                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(vs[t * kMomT + (lane & 15)][kk], zs[wave * kMomT + (lane & 15)][kk], acc[t],
                                                                   0, 0, 0);
                 }
             }
         }
         // result layout: column = lane & 15 (the data row), row = (lane >> 4) + 4 j (the component)
 #pragma unroll
-        for (int t = 0; t < kPcaBI / kPcaT; ++t) {
+        for (int t = 0; t < kMomBI / kMomT; ++t) {
             if (!act[t]) continue;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) total += wl[t * kPcaT + (lane >> 4) + 4 * j] * (acc[t][j] * acc[t][j]);
+            for (int j = 0; j < 4; ++j) total += wl[t * kMomT + (lane >> 4) + 4 * j] * (acc[t][j] * acc[t][j]);
         }
     }
     total += __shfl_xor(total, 16, 64);
     total += __shfl_xor(total, 32, 64);
-    const long row = r0 + wave * kPcaT + (lane & 15);
+    const long row = r0 + wave * kMomT + (lane & 15);
     if (lane < 16 && row < rows) score[(long)s * ld_score + row] = (float)total;
 }
 
@@ -308,7 +304,7 @@ extern "C" int vgan_pca_scores(const float* Xq, int ldq, int rows, int d, const 
     VGAN_CHECK_ARG(Xq && feat && feat_off && sq_off && mean && inv_scale && V && wt && score && pca_range_ok(first, count));
     VGAN_CHECK_ARG(d > 0 && ldq >= d && rows > 0 && rows <= VGAN_MAHA_MAX_ROWS && ld_score >= rows);
     VGAN_CHECK_ARG(max_dims >= 1 && max_dims <= VGAN_MAHA_MAX_DIMS);
-    const dim3 grid((rows + kPcaBR - 1) / kPcaBR, count);
+    const dim3 grid((rows + kMomBR - 1) / kMomBR, count);
     hipLaunchKernelGGL(pca_scores_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, Xq, (long)ldq, rows, feat, feat_off, sq_off, first, mean,
                        inv_scale, V, wt, score, (long)ld_score);
     VGAN_CHECK_LAUNCH();

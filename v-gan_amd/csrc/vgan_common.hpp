@@ -69,6 +69,12 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     __syncthreads();
     return ((red[0] + red[1]) + red[2]) + red[3];
 }
+// the same sum, valid in every thread; red may be written again at once
+__device__ __forceinline__ double block_sum_all(double v, double* red) {
+    const double r = block_sum(v, red);
+    __syncthreads();
+    return r;
+}
 
 // Column-max key: U > 0 always, so its IEEE bits order like the value; ties go to the LOWEST row.
 __device__ __forceinline__ unsigned long long colkey_pack(float u, unsigned row) {

@@ -1858,7 +1858,63 @@ def maha_tiles(dims, first, count):
     return np.concatenate(rows).astype(np.int32)
 
 
-class SubspaceMahalanobis(_SubspaceScorer):
+def _launch_ranges(n_subspaces, most=_MAHA_MAX_RANGE):
+    """(first, count) of consecutive launches over n_subspaces subspaces, at most `most` (a grid dimension) each."""
+    for first in range(0, n_subspaces, most):
+        yield first, min(most, n_subspaces - first)
+
+
+def _split_state(flat, off, shapes=None):
+    """The pieces flat[off[i]:off[i + 1]] of a flat fitted-state array as a list of copies, piece i reshaped to shapes[i]."""
+    parts = [flat[off[i]:off[i + 1]].copy() for i in range(len(off) - 1)]
+    return parts if shapes is None else [p.reshape(shape) for p, shape in zip(parts, shapes)]
+
+
+class _MomentScorer(_SubspaceScorer):
+    """What the covariance detectors (SubspaceMahalanobis, SubspacePCA, SubspaceGMM) share on the host: the constructor
+    tail, the layout of the moment launches of csrc/outlier_moments.hpp, and the plain moments themselves."""
+
+    def _configure_moments(self, subspaces, proba, workspace_bytes, normalize, combination, contamination):
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > MAHA_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, {type(self).__name__} takes at most {MAHA_MAX_DIMS}")
+
+    def _moment_layout(self, n, dev, n_components=None):
+        """(device table (feat, feat_off, sq_off), host feat_off, host sq_off, ranges [(first, count)] of subspaces, the
+        device tile table of every range, the float64 workspace) of the moment launches for n rows; with n_components = C
+        the tables are the expanded ones of gmm_table and a subspace's slab sums are its C (d_s + 1)."""
+        dims, C = self.plan.dims, n_components or 1
+        if n_components is None:
+            feat, feat_off, sq_off = None, self.plan.feat_off, np.concatenate([[0], np.cumsum(dims * dims)]).astype(np.int64)
+            cells, ranges = maha_ranges(dims, self.workspace_bytes)
+            need = dims
+        else:
+            feat, feat_off, sq_off = gmm_table(self.plan.feat, self.plan.feat_off, C)
+            cells, ranges = gmm_ranges(dims, C, n, self.workspace_bytes)
+            need = C * (dims + 1)
+        tiles = [maha_tiles(np.repeat(dims, C), first * C, count * C) for first, count in ranges]
+        widest = max(int(need[first:first + count].sum()) for first, count in ranges)
+        slabs = -(-n // MAHA_SLAB_ROWS)
+        most = max(slabs * widest, slabs * MAHA_TILE * MAHA_TILE * max(t.shape[0] for t in tiles))
+        # the uploads come last: a copy to the device waits for the work in flight (the column mean of _begin_fit), and the
+        # host work above then runs beside it
+        table = self._table[:2] if feat is None else tuple(torch.as_tensor(v, device=dev) for v in (feat, feat_off))
+        return (table + (torch.as_tensor(sq_off, device=dev),), feat_off, sq_off, ranges, [torch.as_tensor(t, device=dev) for t in tiles],
+                torch.empty(min(cells, most), dtype=torch.float64, device=dev))
+
+    def _moments(self, X, support=None, hcount=None):
+        """mu and C of every subspace over the rows of its support (None: every row, h_s = n), range by range."""
+        if hcount is None:
+            hcount = torch.full((self.plan.count,), X.shape[0], dtype=torch.int32, device=X.device)
+        for (first, count), tiles in zip(self._ranges, self._tiles):
+            dims = self.plan.dims[first:first + count]
+            self.ops.maha_moments(X, self._mtable, first, count, int(dims.sum()), int(dims.max()), tiles, support, hcount, self._mean,
+                                  self._cov, self._ws)
+
+
+class SubspaceMahalanobis(_MomentScorer):
     """Squared Mahalanobis distance per subspace under a shrunk covariance, classical or, with robust=True, under a
     deterministic minimum-covariance-determinant estimate (pyod's "linear" family: ``MCD``, and ``PCA`` with all components;
     sklearn's ``EmpiricalCovariance`` / ``ShrunkCovariance`` / ``OAS`` ``.mahalanobis``), combined like the other detectors
@@ -1922,11 +1978,7 @@ class SubspaceMahalanobis(_SubspaceScorer):
         self.robust = bool(robust)
         self.support_fraction = check_support_fraction(support_fraction)
         self.max_csteps = check_csteps(max_csteps)
-        # no distance engine here: "exact" for every subspace keeps the processing order the given order
-        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
-        del self.engine
-        if int(self.plan.dims.max()) > MAHA_MAX_DIMS:
-            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceMahalanobis takes at most {MAHA_MAX_DIMS}")
+        self._configure_moments(subspaces, proba, workspace_bytes, normalize, combination, contamination)
 
     def _check_fit_rows(self, n):
         if not 2 <= n <= MAHA_MAX_ROWS:
@@ -1939,31 +1991,16 @@ class SubspaceMahalanobis(_SubspaceScorer):
         """The tables, the fitted state (mu, and Sigma, L, W at sq_off) and the moment workspace for n rows."""
         S, dims = self.plan.count, self.plan.dims
         self._fitted, self._host_state = False, None
-        self._sq_off = np.concatenate([[0], np.cumsum(dims * dims)]).astype(np.int64)
-        cells, self._ranges = maha_ranges(dims, self.workspace_bytes)
-        self._tiles = [torch.as_tensor(maha_tiles(dims, first, count), device=dev) for first, count in self._ranges]
-        self._mtable = (self._table[0], self._table[1], torch.as_tensor(self._sq_off, device=dev))
-        widest = max(int(dims[first:first + count].sum()) for first, count in self._ranges)
-        slabs = -(-n // MAHA_SLAB_ROWS)
-        most = max(slabs * widest, slabs * MAHA_TILE * MAHA_TILE * max(int(t.shape[0]) for t in self._tiles))
-        self._ws = torch.empty(min(cells, most), dtype=torch.float64, device=dev)
+        self._mtable, _, self._sq_off, self._ranges, self._tiles, self._ws = self._moment_layout(n, dev)
         self._mean = torch.empty(int(dims.sum()), dtype=torch.float64, device=dev)
         self._cov, self._L, self._W = (torch.empty(int(self._sq_off[-1]), dtype=torch.float64, device=dev) for _ in range(3))
         self._alpha = torch.empty(S, dtype=torch.float64, device=dev)
         self._status = torch.zeros(S, dtype=torch.int32, device=dev)
 
-    def _moments(self, X, support, hcount):
-        """mu and C of every subspace over the rows of its support (None: every row), range by range."""
-        for (first, count), tiles in zip(self._ranges, self._tiles):
-            dims = self.plan.dims[first:first + count]
-            self.ops.maha_moments(X, self._mtable, first, count, int(dims.sum()), int(dims.max()), tiles, support, hcount, self._mean,
-                                  self._cov, self._ws)
-
     def _factor(self, hcount):
         """alpha, Sigma (over C), L and W of every subspace from its C."""
         alpha = _MAHA_OAS if self.shrinkage == "oas" else self.shrinkage
-        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
-            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+        for first, count in _launch_ranges(self.plan.count):
             self.ops.maha_factor(self._cov, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), hcount, alpha,
                                  self._L, self._W, self._alpha, self._status)
 
@@ -1974,8 +2011,7 @@ class SubspaceMahalanobis(_SubspaceScorer):
     def _distances(self, X):
         """float32 [S, nq] on the device: the squared distances of the rows of X under the current estimate."""
         per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
-        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
-            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+        for first, count in _launch_ranges(self.plan.count):
             self.ops.maha_scores(X, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), self._mean, self._W, per)
         return per
 
@@ -1990,8 +2026,8 @@ class SubspaceMahalanobis(_SubspaceScorer):
         changed = torch.empty(S, dtype=torch.int32, device=dev)
         converged, steps = np.zeros(S, dtype=bool), np.zeros(S, dtype=np.int64)
         for step in range(self.max_csteps):
-            for first in range(0, S, _MAHA_MAX_RANGE):
-                self.ops.maha_select(per, first, min(_MAHA_MAX_RANGE, S - first), self._h, self._support, changed)
+            for first, count in _launch_ranges(S):
+                self.ops.maha_select(per, first, count, self._h, self._support, changed)
             converged |= changed.cpu().numpy() == 0  # a converged support gives the same estimate again, bit for bit
             if converged.all():
                 break
@@ -2004,11 +2040,8 @@ class SubspaceMahalanobis(_SubspaceScorer):
     def _fetch(self):
         self._require_fit()
         if self._host_state is None:
-            mean, cov = self._mean.cpu().numpy(), self._cov.cpu().numpy()
-            off, sq = self.plan.feat_off, self._sq_off
-            d = self.plan.dims
-            self._host_state = ([mean[off[s]:off[s + 1]].copy() for s in range(self.plan.count)],
-                                [cov[sq[s]:sq[s + 1]].reshape(int(d[s]), int(d[s])).copy() for s in range(self.plan.count)],
+            self._host_state = (_split_state(self._mean.cpu().numpy(), self.plan.feat_off),
+                                _split_state(self._cov.cpu().numpy(), self._sq_off, [(d, d) for d in self.plan.dims]),
                                 self._alpha.cpu().numpy(), self._support.cpu().numpy().astype(bool) if self.robust else None)
         return self._host_state
 
@@ -2134,7 +2167,7 @@ def pca_weights(evals, q, components, weighted, shrinkage):
     return wt, False
 
 
-class SubspacePCA(_SubspaceScorer):
+class SubspacePCA(_MomentScorer):
     """Principal-component outlier scores per subspace (pyod's "linear" family: ``PCA``, as remembered, not pinned against
     pyod; the spectrum is pinned to sklearn's ``StandardScaler`` + ``PCA`` in tests/test_outlier_pca_cpu.py): a row is scored by
     how far it lies along the principal directions of its subspace, the dominant ones (components="major"), the small ones
@@ -2199,11 +2232,7 @@ class SubspacePCA(_SubspaceScorer):
                  max_sweeps=30, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
         (self.n_components, self.components, self.weighted, self.standardize, self.shrinkage,
          self.max_sweeps) = check_pca_params(n_components, components, weighted, standardize, shrinkage, max_sweeps)
-        # no distance engine here: "exact" for every subspace keeps the processing order the given order
-        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
-        del self.engine
-        if int(self.plan.dims.max()) > MAHA_MAX_DIMS:
-            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspacePCA takes at most {MAHA_MAX_DIMS}")
+        self._configure_moments(subspaces, proba, workspace_bytes, normalize, combination, contamination)
 
     def _check_fit_rows(self, n):
         if not 2 <= n <= MAHA_MAX_ROWS:
@@ -2213,30 +2242,14 @@ class SubspacePCA(_SubspaceScorer):
         """The tables, the fitted state (mu, scale, eigenvalues at feat_off; C and V at sq_off) and the moment workspace."""
         S, dims = self.plan.count, self.plan.dims
         self._fitted, self._components = False, None
-        self._sq_off = np.concatenate([[0], np.cumsum(dims * dims)]).astype(np.int64)
-        cells, self._ranges = maha_ranges(dims, self.workspace_bytes)
-        self._tiles = [torch.as_tensor(maha_tiles(dims, first, count), device=dev) for first, count in self._ranges]
-        self._mtable = (self._table[0], self._table[1], torch.as_tensor(self._sq_off, device=dev))
-        widest = max(int(dims[first:first + count].sum()) for first, count in self._ranges)
-        slabs = -(-n // MAHA_SLAB_ROWS)
-        most = max(slabs * widest, slabs * MAHA_TILE * MAHA_TILE * max(int(t.shape[0]) for t in self._tiles))
-        self._ws = torch.empty(min(cells, most), dtype=torch.float64, device=dev)
+        self._mtable, _, self._sq_off, self._ranges, self._tiles, self._ws = self._moment_layout(n, dev)
         self._mean, self._scale, self._evals = (torch.empty(int(dims.sum()), dtype=torch.float64, device=dev) for _ in range(3))
         self._cov, self._V = (torch.empty(int(self._sq_off[-1]), dtype=torch.float64, device=dev) for _ in range(2))
         self._sweeps, self._status = (torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2))
 
-    def _moments(self, X):
-        """mu and C of every subspace over every row, range by range (SubspaceMahalanobis' launches)."""
-        hcount = torch.full((self.plan.count,), X.shape[0], dtype=torch.int32, device=X.device)
-        for (first, count), tiles in zip(self._ranges, self._tiles):
-            dims = self.plan.dims[first:first + count]
-            self.ops.maha_moments(X, self._mtable, first, count, int(dims.sum()), int(dims.max()), tiles, None, hcount, self._mean,
-                                  self._cov, self._ws)
-
     def _eigen(self):
         """scale, the eigenvalues and V of every subspace from its C, which is overwritten."""
-        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
-            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+        for first, count in _launch_ranges(self.plan.count):
             self.ops.pca_eigen(self._cov, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), self.standardize,
                                self.max_sweeps, self._scale, self._evals, self._V, self._sweeps, self._status)
 
@@ -2245,9 +2258,9 @@ class SubspacePCA(_SubspaceScorer):
         S, off = self.plan.count, self.plan.feat_off
         evals, scale = self._evals.cpu().numpy(), self._scale.cpu().numpy()
         status = self._status.cpu().numpy()
-        self.explained_variance_ = [evals[off[s]:off[s + 1]].copy() for s in range(S)]
+        self.explained_variance_ = _split_state(evals, off)
         self.explained_variance_ratio_ = [pca_variance_ratio(lam) for lam in self.explained_variance_]
-        self.scale_ = [scale[off[s]:off[s + 1]].copy() for s in range(S)]
+        self.scale_ = _split_state(scale, off)
         self.n_components_ = np.array([pca_component_count(lam, self.n_components) for lam in self.explained_variance_], dtype=np.int64)
         self.n_sweeps_ = self._sweeps.cpu().numpy().astype(np.int64)
         self.converged_ = (status & _PCA_NOT_CONVERGED) == 0
@@ -2268,8 +2281,7 @@ class SubspacePCA(_SubspaceScorer):
     def _distances(self, X):
         """float32 [S, nq] on the device: the weighted squared projections of the rows of X."""
         per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
-        for first in range(0, self.plan.count, _MAHA_MAX_RANGE):
-            count = min(_MAHA_MAX_RANGE, self.plan.count - first)
+        for first, count in _launch_ranges(self.plan.count):
             self.ops.pca_scores(X, self._mtable, first, count, int(self.plan.dims[first:first + count].max()), self._mean,
                                 self._inv_scale, self._V, self._wt, per)
         return per
@@ -2283,8 +2295,7 @@ class SubspacePCA(_SubspaceScorer):
         """List of S float64 [d_s, d_s]: row j the j-th principal direction of M_s."""
         self._require_fit()
         if self._components is None:
-            V, sq, d = self._V.cpu().numpy(), self._sq_off, self.plan.dims
-            self._components = [V[sq[s]:sq[s + 1]].reshape(int(d[s]), int(d[s])).copy() for s in range(self.plan.count)]
+            self._components = _split_state(self._V.cpu().numpy(), self._sq_off, [(d, d) for d in self.plan.dims])
         return self._components
 
     def fit(self, X, y=None):
@@ -2296,9 +2307,7 @@ class SubspacePCA(_SubspaceScorer):
         self._prepare(X.shape[0], X.device)
         self._moments(X)
         self._eigen()
-        off = self.plan.feat_off
-        mean = self._mean.cpu().numpy()
-        self.location_ = [mean[off[s]:off[s + 1]].copy() for s in range(self.plan.count)]
+        self.location_ = _split_state(self._mean.cpu().numpy(), self.plan.feat_off)
         self._select(X.device)
         del self._ws, self._cov
         scores, per = self._score(X, fitting=True)
@@ -2381,7 +2390,7 @@ def gmm_ranges(dims, n_components, n, workspace_bytes):
     return cells, out
 
 
-class SubspaceGMM(_SubspaceScorer):
+class SubspaceGMM(_MomentScorer):
     """Negative log-likelihood per subspace under a Gaussian mixture of n_components = C full-covariance components fitted
     by EM (pyod's ``GMM``; sklearn's ``GaussianMixture(covariance_type="full", n_init=1)`` and minus its ``score_samples``),
     combined like the other detectors of this module: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new
@@ -2442,11 +2451,7 @@ class SubspaceGMM(_SubspaceScorer):
                  seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
         self.n_components, self.reg_covar, self.tol, self.max_iter, self.kmeans_max_iter = check_gmm_params(
             n_components, reg_covar, tol, max_iter, kmeans_max_iter)
-        # no distance engine here: "exact" for every subspace keeps the processing order the given order
-        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
-        del self.engine
-        if int(self.plan.dims.max()) > MAHA_MAX_DIMS:
-            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceGMM takes at most {MAHA_MAX_DIMS}")
+        self._configure_moments(subspaces, proba, workspace_bytes, normalize, combination, contamination)
         self.init = check_gmm_init(init, self.n_components, self.plan.count)
         self.seed = check_seed(seed)
         self._subspaces = np.asarray(subspaces).astype(bool)
@@ -2462,19 +2467,11 @@ class SubspaceGMM(_SubspaceScorer):
     def _prepare(self, n, dev):
         """The expanded table, the fitted state (per entry e = s C + c: mu at feat_off[e]; Sigma, L, W at sq_off[e]; nk, w,
         log w, the log-determinant, the factor's status), the loop's flags and the buffers of a range for n rows."""
-        S, C, dims = self.plan.count, self.n_components, self.plan.dims
+        S, C = self.plan.count, self.n_components
         self._fitted, self._host_state = False, None
-        feat, feat_off, sq_off = gmm_table(self.plan.feat, self.plan.feat_off, C)
+        self._etable, feat_off, sq_off, self._ranges, self._tiles, self._ws = self._moment_layout(n, dev, C)
         self._efeat_off, self._esq_off = feat_off, sq_off
-        self._etable = tuple(torch.as_tensor(v, device=dev) for v in (feat, feat_off, sq_off))
-        cells, self._ranges = gmm_ranges(dims, C, n, self.workspace_bytes)
-        edims = np.repeat(dims, C)
-        self._tiles = [torch.as_tensor(maha_tiles(edims, first * C, count * C), device=dev) for first, count in self._ranges]
-        widest = max(C * int((dims[first:first + count] + 1).sum()) for first, count in self._ranges)
-        slabs = -(-n // MAHA_SLAB_ROWS)
-        most = max(slabs * widest, slabs * MAHA_TILE * MAHA_TILE * max(int(t.shape[0]) for t in self._tiles))
         f64 = dict(dtype=torch.float64, device=dev)
-        self._ws = torch.empty(min(cells, most), **f64)
         largest = max(count for _, count in self._ranges)
         self._resp = torch.empty(largest * C * n, **f64)
         self._lbpart = torch.empty(largest * -(-n // _GMM_ROW_BLOCK), **f64)
@@ -2563,8 +2560,7 @@ class SubspaceGMM(_SubspaceScorer):
     def _score(self, X, fitting):
         C = self.n_components
         per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
-        for first in range(0, self.plan.count, _MAHA_MAX_RANGE // C):
-            count = min(_MAHA_MAX_RANGE // C, self.plan.count - first)
+        for first, count in _launch_ranges(self.plan.count, _MAHA_MAX_RANGE // C):
             self.ops.gmm_estep(X, self._etable, C, first, count, int(self.plan.dims[first:first + count].max()), self._mean, self._W,
                                self._logdet, self._logw, score=per)
         return self._combine(per, fitting), per
@@ -2573,11 +2569,9 @@ class SubspaceGMM(_SubspaceScorer):
         self._require_fit()
         if self._host_state is None:
             S, C, d = self.plan.count, self.n_components, self.plan.dims
-            mean, cov = self._mean.cpu().numpy(), self._cov.cpu().numpy()
-            off, sq = self._efeat_off, self._esq_off
             self._host_state = (self._weights.cpu().numpy().reshape(S, C).copy(),
-                                [mean[off[s * C]:off[(s + 1) * C]].reshape(C, int(d[s])).copy() for s in range(S)],
-                                [cov[sq[s * C]:sq[(s + 1) * C]].reshape(C, int(d[s]), int(d[s])).copy() for s in range(S)])
+                                _split_state(self._mean.cpu().numpy(), self._efeat_off[::C], [(C, v) for v in d]),
+                                _split_state(self._cov.cpu().numpy(), self._esq_off[::C], [(C, v, v) for v in d]))
         return self._host_state
 
     @property
