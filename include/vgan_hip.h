@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_* and vgan_inne_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_* and vgan_sos_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1192,6 +1192,56 @@ int vgan_ocsvm_scores(const float* Pq, const float* sq_q, int nq, const float* P
                       const int32_t* feat_off, const int64_t* col_off, int first, int count, const double* gamma,
                       const double* alpha, const double* rho, int engine, int splits, uint64_t* acc, float* score,
                       const int32_t* score_row, int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Stochastic outlier selection (Janssens, Huszar, Postma, van den Herik 2012; pyod's SOS; the perplexity search of t-SNE):
+ * every fitted row i gets a width beta_i at which the entropy of its affinities exp(-beta_i (D[i, j] - dmin_i)) over the other
+ * rows equals log(perplexity); a row's score is the probability that no fitted row binds to it (v-gan_amd/outlier.py:
+ * SubspaceSOS, whose docstring is the definition; kernels in csrc/outlier_sos.hip).  The packed blocks, squared norms, SUBSPACE
+ * TABLE (feat_off, col_off), first, count (<= 65535), engine and splits are those of vgan_outlier_kde.  VGAN_SOS_MIN_ROWS <= n
+ * <= VGAN_SOS_MAX_ROWS.  metric: VGAN_SOS_METRIC_EUCLIDEAN (a dissimilarity is sqrtf of the engine's float32 d2) or
+ * _SQEUCLIDEAN (d2 itself).
+ * vgan_sos_distance_matrix: D float32 [count, n, n]; D[z][c][q] = the dissimilarity of query row q and reference row c of the one
+ *   block P.  Every entry is written once whatever splits is; the diagonal is written and never read by the entries below.
+ * vgan_sos_fit: for every row i of the chunk's count matrices, all float64 with D widened, every operation rounded on its own (no
+ *   FMA): dmin = min_j D[i][j] and m = the number of j with D[i][j] = dmin, over j != i.  m >= perplexity: beta = inf, Z = m,
+ *   n_iter = 0, flags = VGAN_SOS_FLAG_DEGENERATE.  Otherwise beta = 1, lo = 0, hi = inf and, at every step, a_j = exp(-(beta e_j)),
+ *   e_j = D[i][j] - dmin, Z = sum a_j, diff = (log(Z) + beta ((sum e_j a_j) / Z)) - log(perplexity), the logarithm of perplexity
+ *   taken once on the host; stop if |diff| <= tol; stop with flags = VGAN_SOS_FLAG_UNCONVERGED if max_iter updates have run;
+ *   diff > 0: lo = beta, beta = 2 beta while hi is inf, else (beta + hi) / 2; diff <= 0: hi = beta, beta = (beta + lo) / 2; n_iter
+ *   counts the updates.  beta, dmin, Z float64 [count, n] (Z at the final beta), n_iter, flags int32 [count, n].  The order of the
+ *   two sums is the kernel's own.  storage: VGAN_SOS_STORAGE_WAVE (a row's entries in the registers of one wave, four rows per
+ *   workgroup, n <= VGAN_SOS_WAVE_ROWS), _BLOCK (in those of a workgroup of 1024 threads) or _AUTO (WAVE where it fits).
+ *   1 < perplexity < n - 1, tol > 0 and finite, max_iter >= 1: no launch loops unbounded.
+ * vgan_sos_fit_scores: score[score_row[z] (or z), j] = float32(exp(-(sum_{i != j} rint(min(-log1p(-min(a_i / Z_i, 1)), 128) 2^40))
+ *   2^-40)) with a_i = exp(-(beta_i (D[z][j][i] - dmin_i))), or for beta_i = inf 1 if D[z][j][i] <= dmin_i, else 0: the fitted
+ *   rows scored from the chunk's stored matrices; beta, dmin, Z float64 [count, n].
+ * vgan_sos_scores: the same for the nq new rows of Pq against the nr fitted rows of Pr, the dissimilarity from the engine with
+ *   the new row as query, no row left out and the term min(log1p(a_i / Z_i), 128): the new row appended to the fitted set.  beta,
+ *   dmin, Z float64 [S, nr] indexed by first + z.  acc uint64 [count nq] is scratch.
+ * The integer sums have no order: the bits of a score do not depend on splits or on the chunk.  Every entry returns
+ * VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_SOS_MIN_ROWS 3
+#define VGAN_SOS_MAX_ROWS 32768
+#define VGAN_SOS_WAVE_ROWS 2048
+#define VGAN_SOS_METRIC_EUCLIDEAN 0
+#define VGAN_SOS_METRIC_SQEUCLIDEAN 1
+#define VGAN_SOS_STORAGE_AUTO 0
+#define VGAN_SOS_STORAGE_WAVE 1
+#define VGAN_SOS_STORAGE_BLOCK 2
+#define VGAN_SOS_FLAG_DEGENERATE 1
+#define VGAN_SOS_FLAG_UNCONVERGED 2
+int vgan_sos_distance_matrix(const float* P, const float* sq, int n, const int32_t* feat_off, const int64_t* col_off, int first,
+                             int count, int metric, int engine, int splits, float* D, vgan_stream_t stream);
+int vgan_sos_fit(const float* D, int n, int count, double perplexity, double tol, int max_iter, int storage, double* beta,
+                 double* dmin, double* Z, int32_t* n_iter, int32_t* flags, vgan_stream_t stream);
+int vgan_sos_fit_scores(const float* D, int n, int count, const double* beta, const double* dmin, const double* Z, float* score,
+                        const int32_t* score_row, int64_t ld_score, vgan_stream_t stream);
+int vgan_sos_scores(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
+                    const int32_t* feat_off, const int64_t* col_off, int first, int count, int metric, const double* beta,
+                    const double* dmin, const double* Z, int engine, int splits, uint64_t* acc, float* score,
+                    const int32_t* score_row, int64_t ld_score, vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,12 @@ difference of the two paths' ensemble scores.
     per subspace (minimum, median, maximum) and the time of one step of the longest subspace of a chunk; the SMO stage
     with a and G in LDS (where they fit) and in place with 256 and with 1024 threads; and sklearn's OneClassSVM(kernel="rbf", shrinking=False) fitted and
     scored per subspace on the host for a sample of the subspaces, scaled to all of them.
+  --method sos: stochastic outlier selection (vgan_amd.SubspaceSOS, perplexity 30, tol 1e-5, a 16 GiB workspace) on the shapes of
+    the OCSVM leg: fit and decision_function (the training rows as queries); the fit split into its stages (dissimilarity
+    matrices, the perplexity search, the scores from the stored matrices), each behind a synchronisation; the search steps per
+    row (mean, maximum) and the float64 exponentials per second of the search; the search with a row per wave (where it fits)
+    and per workgroup of 1024 threads; the same rules in numpy on the host with 16 threads (matrix, search and scores
+    separately) for a sample of the subspaces, scaled to all of them; and the LOF fit (k = 20) on the same rows.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1168,6 +1174,130 @@ def run_ocsvm(d, n, count, reps, baselines=True, nu=0.1, sample=4):
     return row
 
 
+def numpy_sos_one(Xs, perplexity, tol=1e-5, max_iter=200, threads=16, block=256):
+    """(scores float64 [n], steps per row, seconds of matrix / search / scores): SubspaceSOS's rules for one subspace in numpy,
+    float64 throughout, blocks of rows spread over a pool of `threads` threads (numpy's exp and sums release the GIL)."""
+    from concurrent.futures import ThreadPoolExecutor
+    n = Xs.shape[0]
+    t0 = time.perf_counter()
+    sq = (Xs * Xs).sum(axis=1)
+    Dm = np.sqrt(np.maximum(sq[:, None] + sq[None, :] - 2.0 * (Xs @ Xs.T), 0.0))
+    np.fill_diagonal(Dm, np.inf)
+    t1 = time.perf_counter()
+    log_perplexity = np.log(perplexity)
+    beta, dmin, Z, steps = np.ones(n), Dm.min(axis=1), np.empty(n), np.zeros(n, np.int64)
+
+    def search(lo_row):
+        rows = slice(lo_row, min(n, lo_row + block))
+        E = Dm[rows] - dmin[rows, None]
+        m = (E == 0.0).sum(axis=1)
+        b, lo, hi = beta[rows].copy(), np.zeros(E.shape[0]), np.full(E.shape[0], np.inf)
+        z, it = m.astype(np.float64), np.zeros(E.shape[0], np.int64)
+        b[m >= perplexity] = np.inf
+        act = np.flatnonzero(m < perplexity)
+        while act.size:
+            e = E[act]
+            a = np.exp(-(b[act, None] * e))
+            zz = a.sum(axis=1)
+            with np.errstate(invalid="ignore"):
+                ss = np.where(a > 0.0, e * a, 0.0).sum(axis=1)  # the row's own entry: inf times 0
+            diff = (np.log(zz) + b[act] * (ss / zz)) - log_perplexity
+            z[act] = zz
+            go = (np.abs(diff) > tol) & (it[act] < max_iter)
+            act, up, bb = act[go], diff[go] > 0.0, b[act][go]
+            lo_old, hi_old = lo[act], hi[act]
+            lo[act], hi[act] = np.where(up, bb, lo_old), np.where(up, hi_old, bb)
+            b[act] = np.where(up, np.where(np.isinf(hi_old), 2.0 * bb, (bb + hi_old) / 2.0), (bb + lo_old) / 2.0)
+            it[act] += 1
+        beta[rows], Z[rows], steps[rows] = b, z, it + (m < perplexity)
+
+    with ThreadPoolExecutor(threads) as pool:
+        list(pool.map(search, range(0, n, block)))
+        t2 = time.perf_counter()
+        deg = np.isinf(beta)
+        total = np.zeros(n)
+
+        def terms(lo_row):  # fitted rows lo_row ..: their terms for every scored row
+            rows = slice(lo_row, min(n, lo_row + block))
+            E = Dm[rows] - dmin[rows, None]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                a = np.where(deg[rows, None], (E <= 0.0).astype(np.float64), np.exp(-(np.where(deg[rows], 0.0, beta[rows])[:, None] * E)))
+                return np.minimum(-np.log1p(-np.minimum(a / Z[rows, None], 1.0)), 128.0).sum(axis=0)
+
+        for part in pool.map(terms, range(0, n, block)):
+            total += part
+    return np.exp(-total), steps, (t1 - t0, t2 - t1, time.perf_counter() - t2)
+
+
+def run_sos(d, n, count, reps, baselines=True, perplexity=30.0, sample=2):
+    from vgan_amd.outlier import SOS_WAVE_ROWS, sos_chunks
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    ens = vgan_amd.SubspaceSOS(m, p, perplexity=perplexity, workspace_bytes=OCSVM_WORKSPACE)
+    t_fit, fit_reps = timed(lambda: ens.fit(Xd), reps)
+    t_dec, dec_reps = timed(lambda: ens.decision_function(Xd), reps)
+    dims = m.sum(axis=1)
+    stages = {}
+
+    def staged(name, fn):
+        def wrapped(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **kw)
+            torch.cuda.synchronize()
+            stages[name] = stages.get(name, 0.0) + time.perf_counter() - t0
+            return out
+        return wrapped
+
+    def staged_fit(storage):
+        other = vgan_amd.SubspaceSOS(m, p, perplexity=perplexity, workspace_bytes=OCSVM_WORKSPACE)
+        other.storage = storage
+        for name, attr in (("matrix", "_distance_matrix"), ("search", "_search"), ("scores", "_score_fitted")):
+            setattr(other, attr, staged(name, getattr(other, attr)))
+        best = None
+        for _ in range(max(reps, 2)):  # the first pass warms up
+            stages.clear()
+            other.fit(Xd)
+            best = dict(stages) if best is None or stages["search"] < best["search"] else best
+        assert np.array_equal(other.beta_, ens.beta_) and np.array_equal(other.decision_scores_, ens.decision_scores_)
+        return {k: round(v, 5) for k, v in best.items()}
+
+    split = staged_fit("auto")
+    searched = np.isfinite(ens.beta_)
+    evaluations = float((ens.n_iter_[searched] + 1).sum())  # an evaluation of the entropy per update, and the one that stops
+    row = {"method": "sos", "d": d, "n": n, "perplexity": perplexity, "S_sampled": count, "S_distinct": int(len(m)),
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "gram_subspaces": int(ens.plan.gram.sum()), "chunks": len(sos_chunks(ens.plan, n, OCSVM_WORKSPACE)),
+           "distance_matrix_bytes": 4 * n * n * int(len(m)), "fit_s": round(t_fit, 5), "fit_reps_s": fit_reps,
+           "decision_function_s": round(t_dec, 5), "decision_function_reps_s": dec_reps, "fit_stages_s": split,
+           "matrix_TFLOPs": round(2.0 * n * n * float(dims.sum()) / split["matrix"] / 1e12, 2),
+           "search_steps_per_row_mean": round(evaluations / max(int(searched.sum()), 1), 2),
+           "search_steps_per_row_max": int(ens.n_iter_.max()) + 1, "n_degenerate": int(ens.n_degenerate_.sum()),
+           "n_unconverged": int(ens.n_unconverged_.sum()),
+           "search_f64_exp_per_s": round(evaluations * (n - 1) / split["search"], 0),
+           "scores_f64_exp_per_s": round(float(len(m)) * n * (n - 1) / split["scores"], 0)}
+    row["search_stage_s_by_storage"] = {where: staged_fit(where)["search"] for where in (("wave",) if n <= SOS_WAVE_ROWS else ()) + ("block",)}
+    lof = vgan_amd.SubspaceEnsemble(m, p, method="lof", n_neighbors=20)
+    row["lof_k20_fit_s"], row["lof_k20_fit_reps_s"] = timed(lambda: lof.fit(Xd), reps)
+    row["lof_k20_fit_s"] = round(row["lof_k20_fit_s"], 5)
+    if baselines:
+        pick = np.unique(np.linspace(0, len(m) - 1, min(sample, len(m))).astype(int))
+        host, worst, host_steps = np.zeros(3), 0.0, 0.0
+        for s in pick:
+            scores, steps, times = numpy_sos_one(X[:, np.flatnonzero(m[s])].astype(np.float64), perplexity)
+            host += times
+            host_steps += float(steps.sum())
+            worst = max(worst, float(np.abs(ens.per_subspace_scores_[s] - scores).max()))
+        scale = len(m) / len(pick)
+        row.update({"numpy16_subspaces_timed": [int(s) for s in pick],
+                    "numpy16_stages_s_scaled": {k: round(float(v) * scale, 3) for k, v in zip(("matrix", "search", "scores"), host)},
+                    "numpy16_fit_s_scaled": round(float(host.sum()) * scale, 3),
+                    "numpy16_search_f64_exp_per_s": round(host_steps * (n - 1) / host[1], 0),
+                    "max_abs_score_diff_vs_numpy": worst, "speedup_vs_numpy16": round(float(host.sum()) * scale / t_fit, 1),
+                    "search_speedup_vs_numpy16": round(float(host[1]) * scale / split["search"], 1)})
+    return row
+
+
 def sweep(n, reps):
     rng = np.random.default_rng(0)
     rows = []
@@ -1297,13 +1427,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1422,6 +1552,14 @@ def main():
             shapes = [tuple(int(v) for v in args.shape.split(","))]
         for d, n, count in shapes:
             out["configs"].append(run_ocsvm(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "sos":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 2000, 50), (10, 10_000, 50), (784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_sos(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "gmm":

@@ -189,9 +189,13 @@ SIGNATURES = {
     "vgan_ocsvm_smo": (_i, [_p, _i, _i, ctypes.c_double, _i, _i, _i, _p, _p, _p, _p, _p]),
     "vgan_ocsvm_rho": (_i, [_p, _p, _i, _i, _p, _p]),
     "vgan_ocsvm_scores": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i64, _p]),
+    "vgan_sos_distance_matrix": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "vgan_sos_fit": (_i, [_p, _i, _i, ctypes.c_double, ctypes.c_double, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "vgan_sos_fit_scores": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    "vgan_sos_scores": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i64, _p]),
 }
 
-ABI_VERSION = 11
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_sos_* ones last) leave it
 _lib = None
 
 

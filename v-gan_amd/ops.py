@@ -1276,6 +1276,55 @@ class HipOps:
                                               _ptr(acc), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
                    "vgan_ocsvm_scores")
 
+    # ---- stochastic outlier selection over subspaces (vgan_amd.outlier.SubspaceSOS) --------------------------
+    # D float32 [count, n, n] and beta / dmin / Z float64, n_iter / flags int32 [count, n]: the arrays of one chunk.
+    def sos_distance_matrix(self, P, sq, n, table, first, count, metric, engine, splits, D):
+        """D[z][c][q] = the dissimilarity (metric 0: sqrtf(d2), 1: d2) of rows q and c of the packed block P."""
+        _vec(P, "P"), _vec(D, "D")
+        assert D.numel() >= count * n * n
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_sos_distance_matrix(_ptr(P), _ptr(sq), int(n), _ptr(feat_off), _ptr(col_off), int(first), int(count),
+                                                     int(metric), int(engine), int(splits), _ptr(D), self._stream()),
+                   "vgan_sos_distance_matrix")
+
+    def _sos_state(self, D, beta, dmin, Z):
+        _vec(D, "D"), _vec(beta, "beta", torch.float64), _vec(dmin, "dmin", torch.float64), _vec(Z, "Z", torch.float64)
+        if not (D.dim() == 3 and D.shape[1] == D.shape[2]):
+            raise ValueError(f"D: need [count, n, n], got {tuple(D.shape)}")
+        count, n = D.shape[0], D.shape[1]
+        assert beta.shape == (count, n) and dmin.shape == (count, n) and Z.shape == (count, n)
+        return count, n
+
+    def sos_fit(self, D, perplexity, tol, max_iter, beta, dmin, Z, n_iter, flags, storage=0):
+        """The perplexity search of every row of the chunk's matrices: beta, dmin, Z, the updates run and the flags (1: a
+        degenerate row, 2: max_iter updates ran)."""
+        count, n = self._sos_state(D, beta, dmin, Z)
+        _vec(n_iter, "n_iter", torch.int32), _vec(flags, "flags", torch.int32)
+        assert n_iter.shape == (count, n) and flags.shape == (count, n)
+        _lib.check(self.lib.vgan_sos_fit(_ptr(D), n, count, float(perplexity), float(tol), int(max_iter), int(storage), _ptr(beta),
+                                         _ptr(dmin), _ptr(Z), _ptr(n_iter), _ptr(flags), self._stream()), "vgan_sos_fit")
+
+    def sos_fit_scores(self, D, beta, dmin, Z, score, score_row=None):
+        """score rows score_row = the scores of the fitted rows themselves, from the chunk's stored matrices."""
+        count, n = self._sos_state(D, beta, dmin, Z)
+        _mat(score, "score")
+        assert score.shape[1] >= n
+        _lib.check(self.lib.vgan_sos_fit_scores(_ptr(D), n, count, _ptr(beta), _ptr(dmin), _ptr(Z), _ptr(score), _ptr(score_row),
+                                                score.stride(0), self._stream()), "vgan_sos_fit_scores")
+
+    def sos_scores(self, Pq, sq_q, nq, Pr, sq_r, nr, table, first, count, metric, beta, dmin, Z, engine, splits, acc, score,
+                   score_row=None):
+        """score rows score_row = the scores of the nq new rows for the chunk; beta / dmin / Z [S, nr] are indexed by first + z."""
+        _vec(beta, "beta", torch.float64), _vec(dmin, "dmin", torch.float64), _vec(Z, "Z", torch.float64)
+        _vec(acc, "acc", torch.int64), _mat(score, "score")
+        assert acc.numel() >= count * nq and beta.shape[1] == nr and beta.shape[0] >= first + count
+        assert dmin.shape == beta.shape and Z.shape == beta.shape
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_sos_scores(_ptr(Pq), _ptr(sq_q), int(nq), _ptr(Pr), _ptr(sq_r), int(nr), _ptr(feat_off), _ptr(col_off),
+                                            int(first), int(count), int(metric), _ptr(beta), _ptr(dmin), _ptr(Z), int(engine),
+                                            int(splits), _ptr(acc), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
+                   "vgan_sos_scores")
+
 
 _default = None
 

@@ -85,6 +85,13 @@ workgroup per subspace and a stop rule per subspace on the device, and the score
 fitted rows in fixed point (csrc/outlier_ocsvm.hip); n^2 d_s for the matrix, n per SMO step.  Its contract (gamma, the
 matrix, the start, the step and its arithmetic, rho, the score, determinism, what is not built) is that class's docstring.
 
+``SubspaceSOS`` is the affinity-based detector (stochastic outlier selection): every fitted row gets a kernel width of its
+own, found by the perplexity search of t-SNE on its row of the n x n float32 dissimilarity matrix (the matrix plumbing of
+``SubspaceOCSVM``), and a row's score is the probability that no fitted row picks it as a neighbour, a product over the
+fitted rows formed as a sum of logarithms in fixed point (csrc/outlier_sos.hip); n^2 d_s for the matrix, about 30 n^2 float64
+exponentials for the search.  Its contract (the matrix, the shift, degenerate rows, the search, the two score forms,
+determinism) is that class's docstring.
+
 ``SubspaceHBOS`` and ``SubspaceLODA`` are the histogram detectors, linear in n: equal-width histograms (numpy.linspace's
 edges, numpy.histogram's counts, exact integer sums) of every feature (HBOS: -log2 densities summed over a subspace's
 features, the dense float64 product of ``SubspaceECOD``) or of sparse random projections of every subspace (LODA: the mean
@@ -2863,3 +2870,193 @@ class SubspaceOCSVM(_SubspaceScorer):
         if self.keep_kernel_matrix:
             self.kernel_matrix_ = kept
         return self._publish(scores, per)
+
+
+SOS_MIN_ROWS = 3  # VGAN_SOS_MIN_ROWS: 1 < perplexity < n - 1 needs three rows
+SOS_MAX_ROWS = 1 << 15  # VGAN_SOS_MAX_ROWS: the fixed-point score sum stays below 2^63 and a row of the matrix fits the LDS of a CU
+SOS_WAVE_ROWS = 2048  # VGAN_SOS_WAVE_ROWS: up to here the search gives a row to one wave, beyond to a workgroup of 1024 threads
+SOS_METRICS = {"euclidean": 0, "sqeuclidean": 1}  # VGAN_SOS_METRIC_*
+SOS_STORAGE = {"auto": 0, "wave": 1, "block": 2}  # VGAN_SOS_STORAGE_*
+_SOS_DEGENERATE, _SOS_UNCONVERGED = 1, 2  # VGAN_SOS_FLAG_*
+
+
+def check_sos_params(perplexity, metric, tol, max_iter):
+    """perplexity a finite float > 1 (fit checks it against n); metric "euclidean" or "sqeuclidean"; tol > 0 and finite; max_iter
+    an integer >= 1."""
+    if not (_is_real(perplexity) and np.isfinite(perplexity) and float(perplexity) > 1.0):
+        raise ValueError(f"perplexity must be a finite float above 1, got {perplexity!r}")
+    if not (isinstance(metric, str) and metric in SOS_METRICS):
+        raise ValueError(f"metric must be 'euclidean' or 'sqeuclidean', got {metric!r}")
+    if not (_is_real(tol) and np.isfinite(tol) and tol > 0):
+        raise ValueError(f"tol must be positive and finite, got {tol!r}")
+    if not (_is_int(max_iter) and 1 <= int(max_iter) < 2 ** 31):
+        raise ValueError(f"max_iter must be an integer between 1 and 2^31 - 1, got {max_iter!r}")
+    return float(perplexity), metric, float(tol), int(max_iter)
+
+
+def check_sos_rows(n):
+    if not SOS_MIN_ROWS <= n <= SOS_MAX_ROWS:
+        raise ValueError(f"stochastic outlier selection takes between {SOS_MIN_ROWS} and {SOS_MAX_ROWS} fitted rows, got {n}")
+
+
+def check_sos_perplexity(perplexity, n):
+    """1 < perplexity < n - 1: between the entropy of one neighbour and that of all n - 1 other rows."""
+    if not 1.0 < perplexity < n - 1:
+        raise ValueError(f"perplexity must lie strictly between 1 and n - 1 = {n - 1}, got {perplexity!r}")
+
+
+def sos_chunks(plan, n, limit_bytes):
+    """[(first, count, gram)]: the chunks of ocsvm_chunks, whose n x n float32 matrices and packed blocks these are too."""
+    return ocsvm_chunks(plan, n, limit_bytes)
+
+
+def sos_constant_score(n):
+    """What every row of a subspace of constant features scores, up to the fixed-point grid: each of the n - 1 other rows
+    binds to it with probability 1 / (n - 1)."""
+    return np.float32((1.0 - 1.0 / (n - 1)) ** (n - 1))
+
+
+class SubspaceSOS(_SubspaceScorer):
+    """Stochastic outlier selection per subspace (Janssens, Huszar, Postma, van den Herik 2012; pyod's SOS; the perplexity
+    search is t-SNE's, sklearn's ``_binary_search_perplexity``), combined like the detectors of SubspaceEnsemble: ``fit`` sets
+    ``decision_scores_``, ``decision_function`` scores new rows, higher is more outlying.  A score is a probability in [0, 1]
+    and needs no ``normalize`` to be summed across subspaces of mixed width.  pyod's metrics other than the two below, a
+    precomputed dissimilarity matrix and any truncated affinity matrix for more than 2^15 rows are not built.  This
+    docstring is the contract.
+
+    Dissimilarity matrix.  ``fit`` builds D_s, float32 [n, n], per subspace from the float32 distance engines (exact below
+    GRAM_MIN_DIMS, Gram above with operands centred on the column mean, as for KDE and OCSVM).  metric "euclidean" (the
+    default, pyod's): an entry is sqrtf of the engine's float32 d2; "sqeuclidean" (the paper's exp(-d^2 / 2 sigma^2)): d2
+    itself.  D[i, j] is the engine's value with row j as the query and row i as the reference row.  The diagonal is never
+    read.  D need not be bitwise symmetric; every use below names its row.  Subspaces are chunked so that count n n 4 bytes
+    plus the packed blocks fit workspace_bytes (sos_chunks); a subspace that alone exceeds it forms a chunk of its own.  ``fit``
+    takes 3 to 2^15 rows and keeps X resident.  perplexity is a float with 1 < perplexity < n - 1: the constructor checks
+    perplexity > 1 and finite, ``fit``, which knows n, the rest.  tol > 0 and finite; max_iter an integer of 1 or more.
+
+    Per fitted row i, all float64 with D widened from float32, every operation rounded on its own (nothing is contracted
+    into an FMA): over j != i, dmin_i = min_j D[i, j], e_j = D[i, j] - dmin_i >= 0, and m_i the number of j with e_j = 0.  The
+    shift changes neither the binding probabilities nor the entropy; it takes the place of pyod's "divide beta by 10 on NaN"
+    branch, because the row sum can no longer underflow to 0.
+
+    Degenerate rows.  If m_i >= perplexity the entropy can never fall to log(perplexity) (duplicates in narrow subspaces of
+    discrete features, constant subspaces).  Then beta_i = inf, Z_i = m_i, n_iter = 0, and the row's affinity to a row at
+    dissimilarity d is 1 if d <= dmin_i, else 0: the uniform distribution over its tied nearest rows.  ``n_degenerate_[s]``
+    counts these rows.
+
+    Search for the other rows.  beta = 1, lo = 0, hi = inf.  At each step a_j = exp(-(beta e_j)), Z = sum_j a_j, H = log(Z) +
+    beta ((sum_j e_j a_j) / Z) and diff = H - log(perplexity), the last logarithm taken once on the host (the C library's).  Stop
+    if |diff| <= tol; otherwise stop if max_iter updates have run, and the row counts in ``n_unconverged_[s]``; otherwise, if
+    diff > 0: lo = beta, and beta = 2 beta while hi is inf, else (beta + hi) / 2; if diff <= 0: hi = beta, and beta = (beta + lo) /
+    2.  This is pyod's loop and sklearn's.  The order of the two sums is the implementation's own.  Z_i and dmin_i, taken at
+    the final beta, are part of the fitted state.
+
+    Scores.  For a row q at dissimilarity d_i to fitted row i, a_i = exp(-(beta_i (d_i - dmin_i))), or the degenerate rule.  At
+    ``fit`` row j reads d_i = D[j, i], its own row of the matrix, leaves i = j out and binds with b = min(a_i / Z_i, 1), the
+    term t_i = -log1p(-b).  ``decision_function`` scores a new row alone, as appended to the fitted set and visible to the
+    fitted rows with their widths as fitted (the stance of ECOD's): b = a_i / (Z_i + a_i), so t_i = log1p(a_i / Z_i), which is
+    inf where a_i overflows; d_i comes from the engine with the new row as query.  Either way the term is min(t_i, 128), added
+    as rint(term 2^40) in 64-bit fixed point, exact below 2^63 for n <= 2^15 (the device of the OCSVM scores).  The
+    per-subspace score is float32(exp(-(sum 2^-40))): the probability that no fitted row binds to the row.  The sum has no
+    order: scores are bit-identical from run to run, for every splits and workspace_bytes, and for a subspace fitted alone or
+    with others.  ``decision_function(X_train)`` is not ``decision_scores_``: there every row meets itself at dissimilarity
+    0.  A subspace of constant features scores float32((1 - 1/(n-1))^(n-1)) up to the fixed-point grid, the same for every row
+    (sos_constant_score).
+
+    Published: the common attributes; ``beta_`` float64 [S, n]; ``n_iter_`` int32 [S, n]; ``n_degenerate_`` and
+    ``n_unconverged_`` int64 [S]; all in the given subspace order.
+
+    engine, splits (the reference-row split of the matrix and scoring sweeps), normalize, combination and contamination are
+    those of SubspaceEnsemble.  Two attributes, set after construction, serve tests and measurements and change no result:
+    ``storage`` ("auto", "wave" or "block": whether the search gives a row to one wave or to a workgroup of 1024 threads; "wave"
+    takes at most SOS_WAVE_ROWS rows) and ``keep_distance_matrix`` (True: ``fit`` also publishes ``distance_matrix_``, a list of S
+    float32 [n, n] arrays, the matrices the search read)."""
+
+    _X = None
+
+    def __init__(self, subspaces, proba, perplexity=4.5, metric="euclidean", tol=1e-5, max_iter=200, engine="auto", splits=None,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        self.perplexity, self.metric, self.tol, self.max_iter = check_sos_params(perplexity, metric, tol, max_iter)
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
+            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
+        self.splits = splits
+        self.storage = "auto"
+        self.keep_distance_matrix = False
+
+    # ---- pipeline --------------------------------------------------------------------------------
+    def _check_fit_rows(self, n):
+        check_sos_rows(n)
+        check_sos_perplexity(self.perplexity, n)
+
+    def _splits(self, nq, nr, count):
+        if self.splits is not None:
+            return int(self.splits)
+        blocks = -(-nq // 64) * count
+        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
+
+    def _distance_matrix(self, X, first, count, gram):
+        n = X.shape[0]
+        P, sq = self._pack(X, first, count, gram)
+        D = torch.empty(count, n, n, dtype=torch.float32, device=X.device)
+        self.ops.sos_distance_matrix(P, sq, n, self._table, first, count, SOS_METRICS[self.metric],
+                                     ENGINES["gram" if gram else "exact"], self._splits(n, n, count), D)
+        return D
+
+    def _search(self, D, first, count, iters, flags):
+        """The perplexity search of every row of the chunk's matrices."""
+        rng = slice(first, first + count)
+        self.ops.sos_fit(D, self.perplexity, self.tol, self.max_iter, self._beta[rng], self._dmin[rng], self._Z[rng], iters[rng],
+                         flags[rng], SOS_STORAGE[self.storage])
+
+    def _score_fitted(self, D, first, count, per):
+        """The scores of the fitted rows themselves, from the chunk's stored matrices."""
+        rng = slice(first, first + count)
+        self.ops.sos_fit_scores(D, self._beta[rng], self._dmin[rng], self._Z[rng], per, self._rows[rng])
+
+    def _score(self, Xq, fitting):
+        """The new-row form; fit scores its own rows from the stored matrices, chunk by chunk (_score_fitted)."""
+        Xr = self._X
+        nr, nq = Xr.shape[0], Xq.shape[0]
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xr.device)
+        for first, count, gram in self.plan.chunks(nr + nq, self.workspace_bytes):
+            Pr, sqr = self._pack(Xr, first, count, gram)
+            Pq, sqq = self._pack(Xq, first, count, gram)
+            acc = torch.empty(count * nq, dtype=torch.int64, device=Xr.device)
+            self.ops.sos_scores(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, SOS_METRICS[self.metric], self._beta, self._dmin,
+                                self._Z, ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count), acc, per,
+                                self._rows[first:first + count])
+            del Pq, Pr, sqq, sqr, acc
+        return self._combine(per, fitting), per
+
+    # ---- public surface --------------------------------------------------------------------------
+    def fit(self, X, y=None):
+        """The dissimilarity matrices, the perplexity search of every row and the scores of X itself: decision_scores_ (float64
+        [n]), per_subspace_scores_, beta_, n_iter_, n_degenerate_, n_unconverged_; with normalize also score_center_ /
+        score_scale_.  X stays resident as the fitted rows."""
+        self._X = X = self._begin_fit(X)
+        n, S, dev = X.shape[0], self.plan.count, X.device
+        self._beta = torch.empty(S, n, dtype=torch.float64, device=dev)
+        self._dmin = torch.empty(S, n, dtype=torch.float64, device=dev)
+        self._Z = torch.empty(S, n, dtype=torch.float64, device=dev)
+        iters = torch.empty(S, n, dtype=torch.int32, device=dev)
+        flags = torch.empty(S, n, dtype=torch.int32, device=dev)
+        per = torch.empty(S, n, dtype=torch.float32, device=dev)
+        kept = [None] * S
+        for first, count, gram in sos_chunks(self.plan, n, self.workspace_bytes):
+            D = self._distance_matrix(X, first, count, gram)
+            self._search(D, first, count, iters, flags)
+            self._score_fitted(D, first, count, per)
+            if self.keep_distance_matrix:
+                host = D.cpu().numpy()
+                for z in range(count):
+                    kept[int(self.plan.order[first + z])] = host[z]
+            del D
+        g = self.plan.given
+        self.beta_ = self._beta.cpu().numpy()[g]
+        self.n_iter_ = iters.cpu().numpy()[g]
+        flags = flags.cpu().numpy()[g]
+        self.n_degenerate_ = (flags == _SOS_DEGENERATE).sum(axis=1).astype(np.int64)
+        self.n_unconverged_ = (flags == _SOS_UNCONVERGED).sum(axis=1).astype(np.int64)
+        if self.keep_distance_matrix:
+            self.distance_matrix_ = kept
+        return self._publish(self._combine(per, fitting=True), per)

@@ -15,7 +15,7 @@ from torch.utils.data import DataLoader
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
 from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
-                      SubspaceINNE, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA)
+                      SubspaceINNE, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOS)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -225,7 +225,12 @@ class _RunFolder:
         per estimator, the score the isolation ratio of the smallest sphere that covers a row; pyod's INNE): its keywords are
         n_estimators, max_samples, ratio ("squared" or "distance"), seed, workspace_bytes and the same normalize /
         combination / contamination, e.g. outlier_ensemble(method="inne", n_estimators=200, X=X); n_neighbors is not used
-        there."""
+        there.
+        method "sos" builds a SubspaceSOS (stochastic outlier selection: a kernel width per fitted row from the perplexity
+        search of t-SNE, the score the probability that no fitted row picks the row as a neighbour; pyod's SOS): its keywords
+        are perplexity, metric ("euclidean" or "sqeuclidean"), tol, max_iter, engine, splits, workspace_bytes and the same
+        normalize / combination / contamination, e.g. outlier_ensemble(method="sos", perplexity=4.5, X=X); n_neighbors is not
+        used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -254,6 +259,8 @@ class _RunFolder:
             ens = SubspacePCA(self.subspaces, self.proba, **kw)
         elif method == "ocsvm":
             ens = SubspaceOCSVM(self.subspaces, self.proba, **kw)
+        elif method == "sos":
+            ens = SubspaceSOS(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
