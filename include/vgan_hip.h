@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_* and vgan_sos_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -960,6 +960,56 @@ int vgan_iforest_path_sums(const float* Xq, int ldq, int rows, int d, const int3
                            int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums, vgan_stream_t stream);
 int vgan_iforest_scores(const int64_t* sums, int64_t ld_sums, int count, int rows, int64_t denom, float* score,
                         int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Deep isolation forest (Xu, Pang, Wang, Wang, TKDE 2023; pyod's DIF): r randomly initialised, never trained MLPs per
+ * subspace map its rows to representations of q columns, and T isolation trees are grown on every representation
+ * (v-gan_amd/outlier.py: SubspaceDIF, whose docstring is the definition; kernels in csrc/outlier_dif.hip and, for the trees,
+ * csrc/outlier_iforest.hip).  BLOCK b = s r + j is representation j of subspace s of the table (feat, feat_off).  Its net has
+ * the layer sizes K_0 = d_s = feat_off[s + 1] - feat_off[s], hidden[0 .. n_hidden - 1], q; no bias; the activation after every
+ * layer but the last.  Limits: 1 <= r <= VGAN_DIF_MAX_NETS, 0 <= n_hidden <= VGAN_DIF_MAX_HIDDEN (hidden is a HOST array, NULL
+ * only when n_hidden is 0), 1 <= hidden[l] <= VGAN_DIF_MAX_WIDTH, 1 <= q <= VGAN_DIF_MAX_OUT, count <= 65535 blocks a call.
+ * The weights of the blocks first .. first + count - 1 live in one float32 buffer W (16-byte aligned): block first + z starts at
+ *   W + w_off[z] (w_off int64 [count] on the device, multiples of 8), its layers follow one another, layer l stored
+ *   quad-major as [ld_l / 4][K_{l+1}][4] with ld_l = K_l rounded up to 8: W_l[o, i] at ((i >> 2) K_{l+1} + o) 4 + (i & 3), and
+ *   FINITE values (vgan_dif_weights writes zeros) in the pad positions i >= K_l.
+ * vgan_dif_weights: zeroes W[0 .. total) and writes W_l[o, i] = float32((2 u - 1) c_l) of every block of the range: u = (w + 0.5)
+ *   2^-32 in float64, w the word e & 3, e = o K_l + i, of Philox4x32-10 at counter (lo32(e >> 2), hi32(e >> 2), 0x44494600 + l, 0)
+ *   and key (lo32(seed) ^ lo32(b), hi32(seed) ^ hi32(b) ^ 0x5bd1e995), b the absolute block; c_l = scale[s (n_hidden + 1) + l]
+ *   (float64 on the device, formed on the host as 1 / sqrt(K_l): the device computes no square root).
+ * vgan_dif_represent: R float32 [count, rows, q]: the net of every block of the range applied to z restricted to the features
+ *   of its subspace, z = float32((double(x) - double(lo_f)) / (double(hi_f) - double(lo_f))), 0 where hi_f == lo_f (lo, hi
+ *   float32 [d]), read from X [rows, d] (ldx) through the feature list; rows <= VGAN_DIF_MAX_ROWS.  Products accumulate in
+ *   float32 on the fp32-input matrix unit, every element one chain over k in an order fixed by k alone; tanh is
+ *   float32(tanh(double(a))), relu max(a, 0).  One workgroup per (block, VGAN_DIF_ROW_TILE rows); layer 0 is staged
+ *   VGAN_DIF_K_TILE features at a time, the later activations stay in LDS.  An element of R depends on its row, block and
+ *   column alone: the same bits for every split of the rows or blocks over calls.
+ * vgan_iforest_build_blocks / vgan_iforest_path_sums_blocks: vgan_iforest_build / vgan_iforest_path_sums with one matrix PER
+ *   BLOCK instead of one feature list per subspace: block first + z reads R + z block_stride as [n, q] (rows of q floats;
+ *   block_stride >= n q), every column a candidate, the stored split feature a column 0 .. q - 1; nodes is int32 [blocks, T, N, 2]
+ *   indexed by the ABSOLUTE block, and tree (b, t) has the stream id b T + t.  sums int64 [count, ld_sums].  Same rules, same
+ *   kernels and the same (T, psi, L) checks as the subspace entries.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_DIF_MAX_NETS 256
+#define VGAN_DIF_MAX_HIDDEN 3
+#define VGAN_DIF_MAX_WIDTH 512
+#define VGAN_DIF_MAX_OUT 64
+#define VGAN_DIF_MAX_ROWS 16777216 /* 2^24 */
+#define VGAN_DIF_ROW_TILE 32
+#define VGAN_DIF_K_TILE 64
+#define VGAN_DIF_ACT_TANH 0
+#define VGAN_DIF_ACT_RELU 1
+int vgan_dif_weights(const int32_t* feat_off, int r, int first, int count, int n_hidden, const int32_t* hidden, int q,
+                     const double* scale, uint64_t seed, float* W, const int64_t* w_off, int64_t total, vgan_stream_t stream);
+int vgan_dif_represent(const float* X, int ldx, int rows, int d, const int32_t* feat, const int32_t* feat_off, const float* lo,
+                       const float* hi, int r, int first, int count, int n_hidden, const int32_t* hidden, int q, int activation,
+                       const float* W, const int64_t* w_off, float* R, vgan_stream_t stream);
+int vgan_iforest_build_blocks(const float* R, int64_t block_stride, int64_t n, int q, int first, int count, int T, int psi, int L,
+                              uint64_t seed, int32_t* nodes, vgan_stream_t stream);
+int vgan_iforest_path_sums_blocks(const float* Rq, int64_t block_stride, int rows, int q, const int32_t* nodes, int first,
+                                  int count, int T, int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums,
+                                  vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * iNNE, isolation by nearest-neighbour ensembles (Bandaragoda, Ting, Albrecht, Liu, Wells 2018; pyod's INNE): T estimators

@@ -81,6 +81,15 @@ difference of the two paths' ensemble scores.
     row (mean, maximum) and the float64 exponentials per second of the search; the search with a row per wave (where it fits)
     and per workgroup of 1024 threads; the same rules in numpy on the host with 16 threads (matrix, search and scores
     separately) for a sample of the subspaces, scaled to all of them; and the LOF fit (k = 20) on the same rows.
+  --method dif: deep isolation forest (vgan_amd.SubspaceDIF at its defaults: 50 random nets d_s -> 500 -> 100 -> 20 per subspace,
+    6 trees of 256 rows on each) on d = 10 at n = 10^4 and d = 784 at n = 10^4 and 5 10^4, S = 50 sampled: fit and
+    decision_function (the training rows as queries); one pass over all blocks split into its calls, each behind a
+    synchronisation (weights, representation, tree build, walk), with the fp32 rate of the representation against the
+    fp32-matrix peak; the same rows through SubspaceIForest with n_estimators = 300 = r T; the same layers run UNFUSED on the
+    library's other pieces for a sample of the subspaces (torch scales and gathers the subspace once, then per block and
+    layer one vgan_gemm_grouped product on the weights of vgan_dif_weights and torch.tanh), scaled to all of them; and numpy
+    (float32 products and tanh) plus sklearn's IsolationForest(6 trees, n_jobs=16) per block on 16 CPU threads for 2
+    subspaces and 2 000 rows, scaled to all rows and subspaces.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1422,18 +1431,156 @@ def run_inne_gather(n, width, S, reps, d=784):
     return out
 
 
+def dif_stage_times(ens, Xd):
+    """Seconds of one pass over all blocks as fit makes it, per call, each behind a synchronisation."""
+    from vgan_amd.outlier import dif_chunks
+    n, q, r = Xd.shape[0], ens.representation_dim, ens.n_representations
+    blocks, _ = dif_chunks(ens._weight_bytes, q, n, ens.workspace_bytes, whole_rows=True)
+    n_blocks = ens.plan.count * r
+    blocks = min(blocks, n_blocks)
+    W = torch.empty(blocks * (ens._weight_bytes // 4), dtype=torch.float32, device="cuda")
+    R = torch.empty(blocks * n * q, dtype=torch.float32, device="cuda")
+    sums = torch.empty(blocks * n, dtype=torch.int64, device="cuda")
+    trees = torch.empty_like(ens._flat_trees)
+    t = {"weights_s": 0.0, "represent_s": 0.0, "build_s": 0.0, "walk_s": 0.0}
+
+    def lap(name, fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        t[name] += time.perf_counter() - t0
+
+    for first in range(0, n_blocks, blocks):
+        count = min(blocks, n_blocks - first)
+        box = {}
+        lap("weights_s", lambda: box.update(w=ens._weights(first, count, W)))
+        w_off = box["w"][1]
+        Rc = R[:count * n * q].view(count, n, q)
+        lap("represent_s", lambda: ens.ops.dif_represent(Xd, ens._table, ens._lo, ens._hi, ens._net, first, count, W, w_off, Rc))
+        lap("build_s", lambda: ens.ops.iforest_build_blocks(Rc, first, ens.max_samples_, ens.depth_limit_, ens.seed, trees))
+        lap("walk_s", lambda: ens.ops.iforest_path_sums_blocks(Rc, trees, first, ens.max_samples_, ens.depth_limit_, ens._cq, sums))
+    return {k: round(v, 6) for k, v in t.items()}, blocks
+
+
+def dif_unfused(ens, Xd, pick):
+    """(seconds, largest |difference| to the fused R) of the representations of the subspaces `pick` through one grouped-GEMM
+    launch per block and layer with torch.tanh between them, on a scaled and gathered copy of the subspace."""
+    r, q, n = ens.n_representations, ens.representation_dim, Xd.shape[0]
+    widths = ens.hidden + (q,)
+    worst, total = 0.0, 0.0
+    for s in pick:
+        cols = torch.as_tensor(ens.plan.feat[ens.plan.feat_off[s]:ens.plan.feat_off[s + 1]].astype(np.int64), device="cuda")
+        d_s = int(cols.numel())
+        flat, _ = ens._weights(s * r, r)
+        size, mats = flat.numel() // r, []
+        for j in range(r):  # the library keeps a layer quad-major for its own forward: row-major copies for the grouped products
+            at, k = j * size, d_s
+            for w in widths:
+                ld = (k + 7) // 8 * 8
+                mats.append(flat[at:at + w * ld].view(ld // 4, w, 4).permute(1, 0, 2).reshape(w, ld).contiguous())
+                at, k = at + w * ld, w
+        acts = [torch.empty(n, w, dtype=torch.float32, device="cuda") for w in widths]
+
+        def run():
+            lo, hi = ens._lo[cols].double(), ens._hi[cols].double()
+            Z = torch.where(hi == lo, torch.zeros((), dtype=torch.float64, device="cuda"), (Xd[:, cols].double() - lo) / (hi - lo)).float()
+            for j in range(r):
+                k, h = d_s, Z
+                for layer, w in enumerate(widths):
+                    ens.ops.gemm_grouped([("NT", h, mats[j * len(widths) + layer][:, :k], acts[layer])])
+                    if layer + 1 < len(widths):
+                        torch.tanh_(acts[layer]) if ens.activation == "tanh" else torch.relu_(acts[layer])
+                    k, h = w, acts[layer]
+
+        t, _ = timed(run, 3)
+        total += t
+        fused = torch.as_tensor(ens.representation(Xd, s, r - 1), device="cuda")
+        worst = max(worst, float((fused - acts[-1]).abs().max()))
+    return total, worst
+
+
+def dif_host(X, ens, pick, rows, threads=16):
+    """Seconds of numpy (float32 products, tanh) and sklearn's IsolationForest per block on the host for the subspaces `pick` and
+    the first `rows` rows: (representation, trees and scores)."""
+    from sklearn.ensemble import IsolationForest
+    r = ens.n_representations
+    t_rep = t_forest = 0.0
+    lo, hi = ens.feature_min_.astype(np.float64), ens.feature_max_.astype(np.float64)
+    for s in pick:
+        cols = ens.plan.feat[ens.plan.feat_off[s]:ens.plan.feat_off[s + 1]]
+        weights = [ens.layer_weights(s, j) for j in range(r)]
+        t0 = time.perf_counter()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            Z = np.where(hi[cols] == lo[cols], 0.0, (X[:rows, cols].astype(np.float64) - lo[cols]) / (hi[cols] - lo[cols])).astype(np.float32)
+        reps = []
+        for j in range(r):
+            h = Z
+            for layer, w in enumerate(weights[j]):
+                h = h @ w.T
+                if layer + 1 < len(weights[j]):
+                    h = np.tanh(h) if ens.activation == "tanh" else np.maximum(h, 0)
+            reps.append(h)
+        t1 = time.perf_counter()
+        for h in reps:
+            forest = IsolationForest(n_estimators=ens.n_estimators, max_samples=min(256, rows), n_jobs=threads, random_state=0).fit(h)
+            forest.score_samples(h)
+        t_rep, t_forest = t_rep + t1 - t0, t_forest + time.perf_counter() - t1
+    return t_rep, t_forest
+
+
+def run_dif(d, n, count, reps, baselines=True, sample=2, host_rows=2000):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceDIF(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    r, T, q = ens.n_representations, ens.n_estimators, ens.representation_dim
+    widths = (0,) + ens.hidden + (q,)
+    inner = sum(a * b for a, b in zip(widths[1:-1], widths[2:]))
+    flop = 2.0 * n * r * float((dims * widths[1] + inner).sum())
+    stages, blocks = dif_stage_times(ens, Xd)
+    row = {"method": "dif", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_representations": r, "n_estimators": T,
+           "max_samples": ens.max_samples_, "hidden": list(ens.hidden), "representation_dim": q, "activation": ens.activation,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "fit_s": round(t_fit, 6), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td,
+           "blocks_per_chunk": blocks, **stages, "represent_flop": flop,
+           "represent_fp32_tflops": round(flop / stages["represent_s"] / 1e12, 2),
+           "represent_fraction_of_fp32_matrix_peak": round(flop / stages["represent_s"] / FP32_PEAK, 4),
+           "state_bytes": int(ens._trees.numel() * 4 + 2 * 4 * d)}
+    forest = vgan_amd.SubspaceIForest(m, p, n_estimators=min(r * T, 1024))
+    t_if, ti = timed(lambda: forest.fit(Xd), reps)
+    row.update({"iforest_trees": forest.n_estimators, "iforest_fit_s": round(t_if, 6), "iforest_fit_reps_s": ti,
+                "dif_over_iforest_fit": round(t_fit / t_if, 2)})
+    if baselines:
+        pick = np.unique(np.linspace(0, S - 1, min(S, sample)).astype(int))
+        share = float((dims[pick] * widths[1] + inner).sum()) / float((dims * widths[1] + inner).sum())  # of the flop
+        t_un, diff = dif_unfused(ens, Xd, pick)
+        nq = min(n, host_rows)
+        t_rep, t_forest = dif_host(X, ens, pick, nq)
+        row.update({"unfused_subspaces_timed": int(len(pick)), "unfused_represent_s": round(t_un / share, 6),
+                    "unfused_over_fused_represent": round(t_un / share / stages["represent_s"], 2),
+                    "unfused_largest_abs_difference": diff,
+                    "host_subspaces_timed": int(len(pick)), "host_rows_timed": int(nq),
+                    "numpy_16_threads_represent_s": round(t_rep / share * n / nq, 3),
+                    "sklearn_16_threads_trees_s": round(t_forest * S / len(pick) * n / nq, 3),
+                    "fit_speedup_vs_host": round((t_rep / share + t_forest * S / len(pick)) * n / nq / t_fit, 1)})
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1560,6 +1707,14 @@ def main():
             shapes = [tuple(int(v) for v in args.shape.split(","))]
         for d, n, count in shapes:
             out["configs"].append(run_sos(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "dif":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (784, 10_000, 50), (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_dif(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "gmm":

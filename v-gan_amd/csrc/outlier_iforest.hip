@@ -19,6 +19,10 @@
 //            given) per step; the depth of the leaf is read off its heap number.  A row's contribution (depth << 32) +
 //            cq[size] is an integer, so the int64 total does not depend on any order or grouping.
 //   scores   float32(exp2(-(double(sum) / double(denom)))), denom = T cq[psi].
+//   blocks   vgan_iforest_build_blocks / vgan_iforest_path_sums_blocks run the same two kernels on one matrix PER BLOCK
+//            (SubspaceDIF: block b grows its trees on its own representation R[b], [n, q], every column a candidate): the
+//            matrix of block b starts block_stride elements after that of block b - 1 and there is no feature table (feat
+//            NULL: the features are the columns 0 .. q - 1).  The subspace entries pass block_stride = 0 and their table.
 #include "optim_common.hpp"
 #include "vgan_common.hpp"
 
@@ -44,7 +48,7 @@ __device__ __forceinline__ float if_wave_min(float v) {
 __global__ __launch_bounds__(kBlock) void iforest_build_kernel(const float* __restrict__ X, long ldx, unsigned long long n,
                                                                const int32_t* __restrict__ feat, const int32_t* __restrict__ feat_off,
                                                                int first, int T, int psi, int L, int w, unsigned long long seed,
-                                                               int2* __restrict__ nodes) {
+                                                               int2* __restrict__ nodes, long block_stride, int block_cols) {
     __shared__ int rows[2][kIfMaxSamples];
     __shared__ int2 tree[kIfMaxSlots];
     __shared__ unsigned short seg_start[kIfMaxSlots], seg_count[kIfMaxSlots];
@@ -53,7 +57,9 @@ __global__ __launch_bounds__(kBlock) void iforest_build_kernel(const float* __re
     const int s = first + (int)(blockIdx.x / (unsigned)T), t = (int)(blockIdx.x % (unsigned)T);
     const unsigned long long id = (unsigned long long)s * (unsigned long long)T + (unsigned long long)t;
     const int N = 2 << L;
-    const int off = feat_off[s], ds = min(feat_off[s + 1] - off, kIfMaxDims);
+    // feat NULL: block s reads its own matrix of block_cols columns, all of them candidates
+    const int off = feat ? feat_off[s] : 0, ds = feat ? min(feat_off[s + 1] - off, kIfMaxDims) : block_cols;
+    X += (long)(s - first) * block_stride;
     const unsigned k0 = (unsigned)seed ^ (unsigned)id, k1 = (unsigned)(seed >> 32) ^ (unsigned)(id >> 32) ^ 0x5bd1e995u;
 
     for (int i = tid; i < psi; i += kBlock) rows[0][i] = (int)feistel_perm((unsigned long long)i, n, w, seed, id);
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void iforest_build_kernel(const float* __re
             if (m > 1 && e < L) {
                 for (int q = 0; q * 64 < ds; ++q) {
                     const int f = q * 64 + lane;
-                    const long col = f < ds ? feat[off + f] : 0;
+                    const long col = f < ds ? (feat ? feat[off + f] : f) : 0;
                     float lo = INFINITY, hi = -INFINITY;
                     if (f < ds)
                         for (int r = 0; r < m; ++r) {
@@ -103,7 +109,8 @@ __global__ __launch_bounds__(kBlock) void iforest_build_kernel(const float* __re
                 mask = varying[wave][++q];
             }
             for (; j > 0; --j) mask &= mask - 1;
-            const long col = feat[off + q * 64 + (__ffsll((long long)mask) - 1)];
+            const int pos = q * 64 + (__ffsll((long long)mask) - 1);
+            const long col = feat ? feat[off + pos] : pos;
             float lo = INFINITY, hi = -INFINITY;
             for (int r = lane; r < m; r += 64) {
                 const float x = if_value(X[(long)src[s0 + r] * ldx + col]);
@@ -150,12 +157,14 @@ __global__ __launch_bounds__(kBlock) void iforest_build_kernel(const float* __re
 template <int R>
 __global__ __launch_bounds__(kBlock) void iforest_sums_kernel(const float* __restrict__ Xq, long ldq, int rows, int d,
                                                               const int2* __restrict__ nodes, int first, int T, int psi, int L,
-                                                              const int64_t* __restrict__ cq, int64_t* __restrict__ sums, long ld_sums) {
+                                                              const int64_t* __restrict__ cq, int64_t* __restrict__ sums, long ld_sums,
+                                                              long block_stride) {
     __shared__ __attribute__((aligned(16))) int2 group[kIfGroupSlots];
     const int tid = threadIdx.x;
     const int N = 2 << L, per_group = kIfGroupSlots / N;
     const int z = blockIdx.y;
     const int2* trees = nodes + (long)(first + z) * T * N;
+    Xq += (long)z * block_stride;
     const long r0 = (long)blockIdx.x * (R * kBlock) + tid;
     long row[R];
     int64_t total[R];
@@ -221,7 +230,20 @@ extern "C" int vgan_iforest_build(const float* X, int ldx, int64_t n, int d, con
     VGAN_CHECK_ARG(iforest_shape_ok(T, psi, L) && psi <= n && (int64_t)count * T <= 0x7FFFFFFFLL);
     hipLaunchKernelGGL(iforest_build_kernel, dim3((unsigned)(count * T)), dim3(kBlock), 0, (hipStream_t)stream, X, (long)ldx,
                        (unsigned long long)n, feat, feat_off, first, T, psi, L, feistel_half_bits((unsigned long long)n),
-                       (unsigned long long)seed, reinterpret_cast<int2*>(nodes));
+                       (unsigned long long)seed, reinterpret_cast<int2*>(nodes), 0L, 0);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_iforest_build_blocks(const float* R, int64_t block_stride, int64_t n, int q, int first, int count, int T, int psi,
+                                         int L, uint64_t seed, int32_t* nodes, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(R && nodes && q >= 1 && q <= kIfMaxDims && n >= 2 && n <= 0x7FFFFFFFLL && block_stride >= n * q);
+    VGAN_CHECK_ARG(first >= 0 && count > 0 && iforest_shape_ok(T, psi, L) && psi <= n);
+    VGAN_CHECK_ARG((int64_t)count * T <= 0x7FFFFFFFLL && ((int64_t)first + count) * T <= 0x7FFFFFFFLL);
+    hipLaunchKernelGGL(iforest_build_kernel, dim3((unsigned)(count * T)), dim3(kBlock), 0, (hipStream_t)stream, R, (long)q,
+                       (unsigned long long)n, (const int32_t*)nullptr, (const int32_t*)nullptr, first, T, psi, L,
+                       feistel_half_bits((unsigned long long)n), (unsigned long long)seed, reinterpret_cast<int2*>(nodes),
+                       (long)block_stride, q);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }
@@ -236,10 +258,28 @@ extern "C" int vgan_iforest_path_sums(const float* Xq, int ldq, int rows, int d,
     const int2* tn = reinterpret_cast<const int2*>(nodes);
     if (blocks4 * count >= 512)
         hipLaunchKernelGGL(iforest_sums_kernel<4>, dim3((unsigned)blocks4, count), dim3(kBlock), 0, st, Xq, (long)ldq, rows, d, tn, first, T,
-                           psi, L, cq, sums, (long)ld_sums);
+                           psi, L, cq, sums, (long)ld_sums, 0L);
     else
         hipLaunchKernelGGL(iforest_sums_kernel<1>, dim3((unsigned)blocks1, count), dim3(kBlock), 0, st, Xq, (long)ldq, rows, d, tn, first, T,
-                           psi, L, cq, sums, (long)ld_sums);
+                           psi, L, cq, sums, (long)ld_sums, 0L);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_iforest_path_sums_blocks(const float* Rq, int64_t block_stride, int rows, int q, const int32_t* nodes, int first,
+                                             int count, int T, int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums,
+                                             vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Rq && nodes && cq && sums && rows > 0 && q >= 1 && q <= kIfMaxDims && block_stride >= (int64_t)rows * q);
+    VGAN_CHECK_ARG(first >= 0 && count > 0 && count <= 65535 && iforest_shape_ok(T, psi, L) && ld_sums >= rows);
+    const long blocks4 = ((long)rows + 4 * kBlock - 1) / (4 * kBlock), blocks1 = ((long)rows + kBlock - 1) / kBlock;
+    const hipStream_t st = (hipStream_t)stream;
+    const int2* tn = reinterpret_cast<const int2*>(nodes);
+    if (blocks4 * count >= 512)
+        hipLaunchKernelGGL(iforest_sums_kernel<4>, dim3((unsigned)blocks4, count), dim3(kBlock), 0, st, Rq, (long)q, rows, q, tn, first, T,
+                           psi, L, cq, sums, (long)ld_sums, (long)block_stride);
+    else
+        hipLaunchKernelGGL(iforest_sums_kernel<1>, dim3((unsigned)blocks1, count), dim3(kBlock), 0, st, Rq, (long)q, rows, q, tn, first, T,
+                           psi, L, cq, sums, (long)ld_sums, (long)block_stride);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }

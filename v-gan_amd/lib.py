@@ -171,6 +171,10 @@ SIGNATURES = {
     "vgan_iforest_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p]),
     "vgan_iforest_path_sums": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, _p]),
     "vgan_iforest_scores": (_i, [_p, _i64, _i, _i, _i64, _p, _i64, _p]),
+    "vgan_iforest_build_blocks": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _i, _i, _u64, _p, _p]),
+    "vgan_iforest_path_sums_blocks": (_i, [_p, _i64, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, _p]),
+    "vgan_dif_weights": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _u64, _p, _p, _i64, _p]),
+    "vgan_dif_represent": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p]),
     "vgan_inne_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p, _p, _p, _p]),
     "vgan_inne_scores": (_i, [_p, _i, _i, _i, _p, _i, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]),
     "vgan_maha_moments": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _i64, _p, _p, _p, _p, _i64, _p]),
@@ -195,7 +199,7 @@ SIGNATURES = {
     "vgan_sos_scores": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i64, _p]),
 }
 
-ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_sos_* ones last) leave it
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_dif_* and vgan_iforest_*_blocks ones last) leave it
 _lib = None
 
 

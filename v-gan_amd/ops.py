@@ -1039,6 +1039,55 @@ class HipOps:
         _lib.check(self.lib.vgan_iforest_scores(_ptr(sums), int(rows), int(count), int(rows), int(denom), _ptr(score), score.stride(0),
                                                 self._stream()), "vgan_iforest_scores")
 
+    def iforest_build_blocks(self, R, first, psi, depth, seed, nodes):
+        """nodes int32 [blocks, T, N, 2] receives the T trees of the blocks first .. first + count - 1, block first + z grown
+        on its own matrix R[z] of R float32 [count, n, q] (every column a candidate); stream id = block T + tree."""
+        _vec(R, "R"), _vec(nodes, "nodes", torch.int32)
+        count, n, q = R.shape
+        B, T = nodes.shape[:2]
+        assert nodes.dim() == 4 and nodes.shape[2] == 2 << depth and nodes.shape[3] == 2 and first + count <= B
+        _lib.check(self.lib.vgan_iforest_build_blocks(_ptr(R), n * q, n, q, int(first), count, T, int(psi), int(depth), int(seed),
+                                                      _ptr(nodes), self._stream()), "vgan_iforest_build_blocks")
+
+    def iforest_path_sums_blocks(self, Rq, nodes, first, psi, depth, cq, sums):
+        """sums int64 [count, rows]: the rows of Rq float32 [count, rows, q], block by block, walked through the trees of the
+        blocks first .. first + count - 1."""
+        _vec(Rq, "Rq"), _vec(nodes, "nodes", torch.int32), _vec(cq, "cq", torch.int64), _vec(sums, "sums", torch.int64)
+        count, rows, q = Rq.shape
+        B, T = nodes.shape[:2]
+        assert nodes.dim() == 4 and nodes.shape[2] == 2 << depth and nodes.shape[3] == 2 and first + count <= B
+        assert cq.numel() >= psi + 1 and sums.numel() >= count * rows
+        _lib.check(self.lib.vgan_iforest_path_sums_blocks(_ptr(Rq), rows * q, rows, q, _ptr(nodes), int(first), count, T, int(psi),
+                                                          int(depth), _ptr(cq), _ptr(sums), rows, self._stream()),
+                   "vgan_iforest_path_sums_blocks")
+
+    # ---- deep isolation forest over subspaces (vgan_amd.outlier.SubspaceDIF) --------------------------------
+    # net: (r, hidden tuple, q, activation code); w_off: int64 [count] on the device, the blocks' offsets into W
+    def dif_weights(self, feat_off, net, first, count, scale, seed, W, w_off, total):
+        """W float32 [>= total]: zeroed, then the Philox weights of the blocks first .. first + count - 1 (layer l of a block
+        quad-major as [round8(K_l) / 4][K_{l+1}][4]); scale float64 [S, layers]: c_l = 1 / sqrt(K_l) per subspace."""
+        _vec(feat_off, "feat_off", torch.int32), _vec(scale, "scale", torch.float64), _vec(W, "W"), _vec(w_off, "w_off", torch.int64)
+        r, hidden, q, _ = net
+        assert W.numel() >= total and w_off.numel() >= count and scale.numel() >= (feat_off.numel() - 1) * (len(hidden) + 1)
+        assert (first + count - 1) // r < feat_off.numel() - 1
+        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
+        _lib.check(self.lib.vgan_dif_weights(_ptr(feat_off), int(r), int(first), int(count), len(hidden), harr, int(q), _ptr(scale),
+                                             int(seed), _ptr(W), _ptr(w_off), int(total), self._stream()), "vgan_dif_weights")
+
+    def dif_represent(self, X, table, lo, hi, net, first, count, W, w_off, R):
+        """R float32 [count, rows, q]: the nets of the blocks first .. first + count - 1 (weights W at w_off) applied to the
+        min-max scaled rows of X [rows, d] restricted to the features of the block's subspace."""
+        _mat(X, "X"), _vec(lo, "lo"), _vec(hi, "hi"), _vec(W, "W"), _vec(w_off, "w_off", torch.int64), _vec(R, "R")
+        feat, feat_off, _ = table
+        rows, d = X.shape
+        r, hidden, q, act = net
+        assert lo.numel() == d and hi.numel() == d and w_off.numel() >= count and R.numel() >= count * rows * q
+        assert (first + count - 1) // r < feat_off.numel() - 1
+        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
+        _lib.check(self.lib.vgan_dif_represent(_ptr(X), X.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(lo), _ptr(hi), int(r),
+                                               int(first), int(count), len(hidden), harr, int(q), int(act), _ptr(W), _ptr(w_off),
+                                               _ptr(R), self._stream()), "vgan_dif_represent")
+
     # ---- iNNE over subspaces (vgan_amd.outlier.SubspaceINNE) -----------------------------------------------
     # state: (rows int32, r2 float64, nn int32, rho float64), each [S, T, psi]
     def inne_build(self, X, table, first, count, max_dims, ratio, seed, state):

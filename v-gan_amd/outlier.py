@@ -92,6 +92,13 @@ fitted rows formed as a sum of logarithms in fixed point (csrc/outlier_sos.hip);
 exponentials for the search.  Its contract (the matrix, the shift, degenerate rows, the search, the two score forms,
 determinism) is that class's docstring.
 
+``SubspaceDIF`` is the learned-representation detector without the learning (deep isolation forest): per subspace an ensemble
+of randomly initialised, never trained MLPs, regenerated from the seed by a counter-based generator, maps the min-max scaled
+rows to small representations in one fused fp32 matrix-unit forward that keeps every activation in LDS
+(csrc/outlier_dif.hip), and the trees of ``SubspaceIForest`` are grown on every representation and pooled per subspace
+(the block entries of csrc/outlier_iforest.hip).  Its contract (scaling, the nets and their weights, the representation and
+its precision, the trees and the pooled score, determinism, what is not built) is that class's docstring.
+
 ``SubspaceHBOS`` and ``SubspaceLODA`` are the histogram detectors, linear in n: equal-width histograms (numpy.linspace's
 edges, numpy.histogram's counts, exact integer sums) of every feature (HBOS: -log2 densities summed over a subspace's
 features, the dense float64 product of ``SubspaceECOD``) or of sparse random projections of every subspace (LODA: the mean
@@ -3060,3 +3067,302 @@ class SubspaceSOS(_SubspaceScorer):
         if self.keep_distance_matrix:
             self.distance_matrix_ = kept
         return self._publish(self._combine(per, fitting=True), per)
+
+
+# ---- deep isolation forest: isolation trees on random-MLP representations of the subspaces ------------------------------
+DIF_MAX_REPRESENTATIONS = 256  # VGAN_DIF_MAX_NETS
+DIF_MAX_HIDDEN = 3  # VGAN_DIF_MAX_HIDDEN
+DIF_MAX_WIDTH = 512  # VGAN_DIF_MAX_WIDTH: an activation tile of 32 rows stays in LDS
+DIF_MAX_DIM = 64  # VGAN_DIF_MAX_OUT
+DIF_MAX_DIMS = 8192  # features of one subspace
+DIF_MAX_ROWS = 1 << 24  # VGAN_DIF_MAX_ROWS (and VGAN_HIST_MAX_ROWS: the column range)
+DIF_ROW_TILE = 32  # VGAN_DIF_ROW_TILE: rows of one workgroup of the forward
+DIF_K_TILE = 64  # VGAN_DIF_K_TILE: features of one staged tile of layer 0
+DIF_ACTIVATIONS = {"tanh": 0, "relu": 1}  # VGAN_DIF_ACT_*
+DIF_PHILOX_TAG = 0x44494600  # counter word 2 of a weight draw is DIF_PHILOX_TAG + layer
+_DIF_MAX_RANGE = 65535  # blocks of one launch (a grid dimension)
+
+
+def check_representations(n_representations):
+    if not (_is_int(n_representations) and 1 <= int(n_representations) <= DIF_MAX_REPRESENTATIONS):
+        raise ValueError(f"n_representations must be an integer between 1 and {DIF_MAX_REPRESENTATIONS}, got {n_representations!r}")
+    return int(n_representations)
+
+
+def check_hidden(hidden):
+    """A tuple of 0 to DIF_MAX_HIDDEN widths, each 1 .. DIF_MAX_WIDTH; () is a random linear projection."""
+    try:
+        widths = tuple(hidden)
+    except TypeError:
+        raise ValueError(f"hidden must be a tuple of at most {DIF_MAX_HIDDEN} widths, got {hidden!r}") from None
+    if len(widths) > DIF_MAX_HIDDEN:
+        raise ValueError(f"hidden must hold at most {DIF_MAX_HIDDEN} widths, got {len(widths)}")
+    for w in widths:
+        if not (_is_int(w) and 1 <= int(w) <= DIF_MAX_WIDTH):
+            raise ValueError(f"a hidden width must be an integer between 1 and {DIF_MAX_WIDTH}, got {w!r}")
+    return tuple(int(w) for w in widths)
+
+
+def check_representation_dim(representation_dim):
+    if not (_is_int(representation_dim) and 1 <= int(representation_dim) <= DIF_MAX_DIM):
+        raise ValueError(f"representation_dim must be an integer between 1 and {DIF_MAX_DIM}, got {representation_dim!r}")
+    return int(representation_dim)
+
+
+def check_activation(activation):
+    if activation not in DIF_ACTIVATIONS:
+        raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
+    return activation
+
+
+def dif_block_floats(dims, hidden, q):
+    """int64, like dims: the float32 elements of one block's weights for a subspace of that many features: layer l stored as
+    [K_l rounded up to 8, in quads][K_{l+1}][4], layer after layer (include/vgan_hip.h)."""
+    k = (np.asarray(dims, dtype=np.int64) + 7) // 8 * 8
+    total = np.zeros_like(k)
+    for width in tuple(hidden) + (q,):
+        total = total + width * k
+        k = np.int64((width + 7) // 8 * 8)
+    return total
+
+
+def dif_chunks(weight_bytes, q, rows, workspace_bytes, whole_rows=False):
+    """(blocks of a chunk, rows of a row chunk).  Per block the transient buffers hold its weights (weight_bytes: those of
+    the widest subspace), and per row q float32 of R and one int64 sum, 4 q + 8 bytes.  While a block with all `rows` rows
+    fits, as many blocks as fit form a chunk (at most 65535, a grid dimension) and the rows are not chunked; below that a
+    chunk is one block and the rows are chunked, down to single rows; a row chunk never exceeds DIF_MAX_ROWS.  whole_rows (fit: the trees of a block are grown on its
+    whole R) never chunks the rows and raises ValueError, naming the bytes, when one block's R does not fit."""
+    ws, per_row = int(workspace_bytes), 4 * int(q) + 8
+    if not whole_rows:
+        rows = min(int(rows), DIF_MAX_ROWS)  # rows of one launch
+    if whole_rows and int(rows) * 4 * int(q) > ws:
+        raise ValueError(f"SubspaceDIF fit needs {int(rows) * 4 * int(q)} bytes of workspace for the representation of one block "
+                         f"({rows} rows x {q} columns, float32), workspace_bytes is {ws}")
+    block = int(weight_bytes) + int(rows) * per_row
+    if whole_rows or block <= ws:
+        return max(1, min(ws // block, _DIF_MAX_RANGE)), int(rows)
+    return 1, max(1, min((ws - int(weight_bytes)) // per_row, int(rows)))
+
+
+class SubspaceDIF(_SubspaceScorer):
+    """Deep isolation forest per subspace (Xu, Pang, Wang, Wang: "Deep Isolation Forest for Anomaly Detection", TKDE 2023;
+    pyod's ``DIF``), combined like the other detectors of this module: an ensemble of randomly initialised, never trained
+    MLPs maps the rows of a subspace to small representations, and isolation trees are grown on every representation.
+    Axis-parallel cuts in a random non-linear representation are oblique, curved cuts in the data, so rows that break a
+    correlation structure while staying inside every marginal range are isolated early, where the plain isolation forest
+    finds them late.  Like every isolation method it does not find outliers that sit INSIDE the data (the centre of a ring).
+    Nothing is trained and no weight is stored: the nets are regenerated from the seed.  The defaults are pyod's
+    (n_ensemble 50, n_estimators 6, max_samples 256, hidden_neurons [500, 100], representation_dim 20, tanh, no bias).  Not
+    built: the paper's deviation-enhanced score (DEAS), pyod's ``skip_connection``, other activations.
+
+    Sizes.  X is cast to float32.  S subspaces, r = n_representations (1 .. 256), T = n_estimators (1 .. 1024); psi =
+    ``max_samples_`` = min(max_samples, n), max_samples "auto" (256) or 2 .. 1024 (SubspaceIForest's rule); q =
+    representation_dim (1 .. 64); hidden a tuple of 0 to 3 widths, each 1 .. 512 (() is a random linear projection);
+    activation "tanh" or "relu"; seed in [0, 2^64); a subspace has at most 8192 features; ``fit`` takes 2 .. 2^24 rows.
+
+    Scaling.  At ``fit``, per feature f, lo_f and hi_f are the float32 min and max over the fitted rows, -0.0 taken as +0.0
+    (``feature_min_``, ``feature_max_``, float32 [d]); z = float32((double(x) - double(lo_f)) / (double(hi_f) - double(lo_f))),
+    exactly 0 for a constant column.  New rows use the stored lo and hi and are not clipped.  (The data here is not
+    standardised, and an unscaled input saturates tanh.)
+
+    Nets.  Block b = s r + j is representation j of the given subspace index s.  Its net has the layer sizes K_0 = d_s, the
+    hidden widths, q; no bias; the activation after every layer but the last; no skip connection.  The weight W_l[o, i] of
+    block b has the linear index e = o K_l + i (for layer 0, i is the position in the subspace's ascending feature list).
+    With the Philox4x32-10 words of
+
+        counter (lo32(e >> 2), hi32(e >> 2), 0x44494600 + l, 0),  key k0 = lo32(seed) ^ lo32(b),  k1 = hi32(seed) ^ hi32(b) ^ 0x5bd1e995
+
+    (the key convention of the noise stream and of SubspaceIForest), w = word e & 3, u = (w + 0.5) 2^-32 in float64 and
+    W = float32((2 u - 1) c_l), c_l = 1 / sqrt(K_l) formed on the host in float64: torch's default ``nn.Linear`` init,
+    U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)).  The nets are keyed by the subspace's POSITION: a subspace fitted alone (position
+    0) gets other nets than the same subspace at position 3.
+
+    Representation.  R[b, i, :] is the net of block b applied to z of row i restricted to F_s.  Products accumulate in
+    float32 on the fp32-input matrix unit; tanh is float32(tanh(double(a))) of the float32 pre-activation a, relu is
+    max(a, 0).  An element of R depends on its row, its block and its column only: it is bit-identical from run to run, for
+    every split of the rows or blocks over launches (so for every workspace_bytes) and whichever other blocks share a launch.
+
+    Trees.  For every block, T trees are grown on the float32 matrix R[b] [n, q], all q columns candidates, by the rules
+    of SubspaceIForest exactly (sampling by feistel_perm, the Philox node words, thresholds, the depth limit L = ceil(log2
+    psi), leaves), with the stream id = b T + t.  sum[b, i] is that class's int64 fixed-point path sum, and the subspace pools
+    its r T trees:
+
+        score[s, i] = float32(exp2(-(double(sum_j sum[s r + j, i]) / double(r T cq[psi]))))
+
+    in (0, 1].  A subspace of constant features has R = 0, every tree one leaf of psi rows, and scores exactly 0.5.
+    ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.  Scores, trees and R are bit-identical from run to
+    run and for every workspace_bytes, which bounds the transient buffers (dif_chunks: weights, R and sums of a chunk of
+    blocks), not the trees; ``fit`` raises ValueError, naming the bytes, when the R of one block does not fit it.  NaN input
+    leaves the results unspecified and neither faults nor hangs.
+
+    Fitted state: the trees, lo, hi and the seed; no weights and no X.  ``fit`` publishes, copied to the host on first use,
+    ``tree_feature_`` int32 [S, r, T, N] (the split column of the representation, 0 .. q - 1; -1 a leaf, -2 an absent slot),
+    ``tree_threshold_`` float32 and ``tree_size_`` int32 of the same shape, N = 2^(L + 1); and ``max_samples_``,
+    ``depth_limit_``, ``feature_min_``, ``feature_max_``.  ``representation(X, s, j)`` returns R of block s r + j as float32
+    [n, q] and ``layer_weights(s, j)`` its weights as float32 [K_{l + 1}, K_l] per layer: both are for inspection and tests.
+    normalize, combination, contamination, ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and
+    return_per_subspace are the shared tail.  pyod is not pinned here: this definition and its numpy restatement in
+    tests/test_outlier_dif_cpu.py are what binds.  All of it runs in libvgan_hip.so (csrc/outlier_dif.hip for the weights and
+    the fused forward, csrc/outlier_iforest.hip for the trees)."""
+
+    _host_trees = None
+
+    def __init__(self, subspaces, proba, n_representations=50, n_estimators=6, max_samples="auto", hidden=(500, 100),
+                 representation_dim=20, activation="tanh", seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None,
+                 combination="sum", contamination=0.1):
+        self.n_representations = check_representations(n_representations)
+        self.n_estimators = check_estimators(n_estimators)
+        self.max_samples = max_samples
+        self._max_samples = check_max_samples(max_samples)
+        self.hidden = check_hidden(hidden)
+        self.representation_dim = check_representation_dim(representation_dim)
+        self.activation = check_activation(activation)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        if int(self.plan.dims.max()) > DIF_MAX_DIMS:
+            raise ValueError(f"a subspace has {int(self.plan.dims.max())} features, SubspaceDIF takes at most {DIF_MAX_DIMS}")
+        self._net = (self.n_representations, self.hidden, self.representation_dim, DIF_ACTIVATIONS[self.activation])
+        self._block_floats = dif_block_floats(self.plan.dims, self.hidden, self.representation_dim)  # per subspace
+        self._weight_bytes = 4 * int(self._block_floats.max())
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= DIF_MAX_ROWS:
+            raise ValueError(f"SubspaceDIF fit needs between 2 and {DIF_MAX_ROWS} rows, got {n}")
+
+    def _attach(self):
+        if self.ops is not None:
+            return
+        super()._attach()
+        widths = np.asarray(self.hidden + (self.representation_dim,), dtype=np.float64)
+        scale = np.empty((self.plan.count, len(widths)), dtype=np.float64)
+        scale[:, 0] = 1.0 / np.sqrt(self.plan.dims.astype(np.float64))
+        scale[:, 1:] = 1.0 / np.sqrt(widths[:-1])
+        self._scale = torch.as_tensor(scale, device="cuda")
+
+    def _weights(self, first, count, W=None):
+        """(W, w_off) of the blocks first .. first + count - 1, W filled on the device."""
+        sizes = self._block_floats[np.arange(first, first + count) // self.n_representations]
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        total = int(off[-1])
+        if W is None:
+            W = torch.empty(total, dtype=torch.float32, device="cuda")
+        w_off = torch.as_tensor(off[:-1].astype(np.int64), device="cuda")
+        self.ops.dif_weights(self._table[1], self._net, first, count, self._scale, self.seed, W, w_off, total)
+        return W, w_off
+
+    def layer_weights(self, s, j):
+        """The weights of representation j of subspace s: a list of float32 [K_{l + 1}, K_l], one per layer."""
+        s, j = int(s), int(j)
+        if not (0 <= s < self.plan.count and 0 <= j < self.n_representations):
+            raise ValueError(f"no representation {j} of subspace {s}: {self.plan.count} subspaces of {self.n_representations}")
+        self._attach()
+        flat = self._weights(s * self.n_representations + j, 1)[0].cpu().numpy()
+        out, at, k = [], 0, int(self.plan.dims[s])
+        for width in self.hidden + (self.representation_dim,):
+            ld = (k + 7) // 8 * 8
+            out.append(flat[at:at + width * ld].reshape(ld // 4, width, 4).transpose(1, 0, 2).reshape(width, ld)[:, :k].copy())
+            at, k = at + width * ld, width
+        return out
+
+    def representation(self, X, s, j):
+        """float32 [n, q]: R of block s r + j for the rows of X, scaled by the fitted lo and hi."""
+        self._require_fit()
+        s, j = int(s), int(j)
+        if not (0 <= s < self.plan.count and 0 <= j < self.n_representations):
+            raise ValueError(f"no representation {j} of subspace {s}: {self.plan.count} subspaces of {self.n_representations}")
+        X = _device_matrix(X, self.plan.d)
+        b = s * self.n_representations + j
+        W, w_off = self._weights(b, 1)
+        R = torch.empty(1, X.shape[0], self.representation_dim, dtype=torch.float32, device=X.device)
+        self.ops.dif_represent(X, self._table, self._lo, self._hi, self._net, b, 1, W, w_off, R)
+        return R[0].cpu().numpy()
+
+    def path_sums(self, X):
+        """int64 [S, n]: the fixed-point path-length sums of the rows of X over the r T trees of every subspace."""
+        self._require_fit()
+        return self._pooled_sums(_device_matrix(X, self.plan.d), build=False).cpu().numpy()
+
+    def _pooled_sums(self, X, build):
+        """int64 [S, nq]: the path sums of the rows of X pooled over the r blocks of every subspace, chunk of blocks by chunk
+        of blocks and row chunk by row chunk; build: grows the trees of every block on its R first (all rows in one chunk)."""
+        nq, dev = X.shape[0], X.device
+        r, q, psi, L = self.n_representations, self.representation_dim, self.max_samples_, self.depth_limit_
+        blocks, rows = dif_chunks(self._weight_bytes, q, nq, self.workspace_bytes, whole_rows=build)
+        n_blocks = self.plan.count * r
+        blocks = min(blocks, n_blocks)
+        pooled = torch.zeros(self.plan.count, nq, dtype=torch.int64, device=dev)
+        W = torch.empty(blocks * (self._weight_bytes // 4), dtype=torch.float32, device=dev)
+        R = torch.empty(blocks * rows * q, dtype=torch.float32, device=dev)
+        sums = torch.empty(blocks * rows, dtype=torch.int64, device=dev)
+        for first in range(0, n_blocks, blocks):
+            count = min(blocks, n_blocks - first)
+            _, w_off = self._weights(first, count, W)
+            owner = torch.arange(first, first + count, device=dev) // r
+            for r0 in range(0, nq, rows):
+                m = min(rows, nq - r0)
+                Rc = R[:count * m * q].view(count, m, q)
+                self.ops.dif_represent(X[r0:r0 + m], self._table, self._lo, self._hi, self._net, first, count, W, w_off, Rc)
+                if build:
+                    self.ops.iforest_build_blocks(Rc, first, psi, L, self.seed, self._flat_trees)
+                self.ops.iforest_path_sums_blocks(Rc, self._flat_trees, first, psi, L, self._cq, sums)
+                pooled[:, r0:r0 + m].index_add_(0, owner, sums[:count * m].view(count, m))  # int64: exact in any order
+        return pooled
+
+    def _scores(self, X, fitting):
+        pooled = self._pooled_sums(X, build=fitting)
+        per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
+        for s0 in range(0, self.plan.count, _IFOREST_MAX_RANGE):
+            s1 = min(s0 + _IFOREST_MAX_RANGE, self.plan.count)
+            self.ops.iforest_scores(pooled[s0:s1], s1 - s0, X.shape[0], self._denom, per[s0:s1])
+        return self._combine(per, fitting), per
+
+    def _score(self, X, fitting):
+        return self._scores(X, False)
+
+    _trees_on_host = SubspaceIForest._trees_on_host
+
+    @property
+    def tree_feature_(self):
+        """int32 [S, r, T, N]: the split column of the representation of every heap slot, -1 for a leaf, -2 for an absent slot."""
+        return self._trees_on_host()[0]
+
+    @property
+    def tree_threshold_(self):
+        """float32 [S, r, T, N]: the threshold of every internal node (a row goes left iff R <= threshold), 0 elsewhere."""
+        return self._trees_on_host()[1]
+
+    @property
+    def tree_size_(self):
+        """int32 [S, r, T, N]: the sample rows reaching every node, 0 where the slot is absent."""
+        return self._trees_on_host()[2]
+
+    def fit(self, X, y=None):
+        """Takes the column ranges of X, then block by block regenerates the net, forms R for all rows, grows the T trees on
+        it and walks the rows through them: decision_scores_ (float64 [n]), per_subspace_scores_, max_samples_, depth_limit_,
+        feature_min_, feature_max_ and, on first use, tree_feature_ / tree_threshold_ / tree_size_; with normalize also
+        score_center_ / score_scale_.  The trees, lo and hi are the fitted state: neither X nor any weight is kept."""
+        n = _matrix_shape(X, self.plan.d)[0]
+        self._check_fit_rows(n)
+        dif_chunks(self._weight_bytes, self.representation_dim, n, self.workspace_bytes, whole_rows=True)  # raises before the device is touched
+        X = self._begin_fit(X)
+        d, dev = X.shape[1], X.device
+        keys = torch.empty(d, 2, dtype=torch.int64, device=dev)
+        self.ops.hist_column_range(X, keys)  # keys of the float64 images of the float32 min and max, -0.0 as +0.0
+        k = keys.cpu().numpy().view(np.uint64)
+        bits = np.where(k >> np.uint64(63), k & np.uint64(0x7FFFFFFFFFFFFFFF), ~k)
+        lo_hi = np.ascontiguousarray(bits).view(np.float64).astype(np.float32)
+        self.feature_min_, self.feature_max_ = lo_hi[:, 0].copy(), lo_hi[:, 1].copy()
+        self._lo, self._hi = torch.as_tensor(self.feature_min_, device=dev), torch.as_tensor(self.feature_max_, device=dev)
+        psi = min(self._max_samples, n)
+        self.max_samples_, self.depth_limit_, self._host_trees = psi, (psi - 1).bit_length(), None
+        cq = iforest_path_table(psi)
+        self._cq = torch.as_tensor(cq, device=dev)
+        self._denom = self.n_representations * self.n_estimators * int(cq[psi])
+        self._trees = torch.empty(self.plan.count, self.n_representations, self.n_estimators, 2 << self.depth_limit_, 2,
+                                  dtype=torch.int32, device=dev)
+        self._flat_trees = self._trees.view(self.plan.count * self.n_representations, self.n_estimators, 2 << self.depth_limit_, 2)
+        self._fitted = False
+        scores, per = self._scores(X, True)
+        return self._publish(scores, per)

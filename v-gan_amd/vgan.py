@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
+from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
                       SubspaceINNE, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOS)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
@@ -230,7 +230,12 @@ class _RunFolder:
         search of t-SNE, the score the probability that no fitted row picks the row as a neighbour; pyod's SOS): its keywords
         are perplexity, metric ("euclidean" or "sqeuclidean"), tol, max_iter, engine, splits, workspace_bytes and the same
         normalize / combination / contamination, e.g. outlier_ensemble(method="sos", perplexity=4.5, X=X); n_neighbors is not
-        used there."""
+        used there.
+        method "dif" builds a SubspaceDIF (deep isolation forest: isolation trees on the representations of an ensemble of
+        random, never trained MLPs per subspace; pyod's DIF): its keywords are n_representations, n_estimators, max_samples,
+        hidden, representation_dim, activation ("tanh" or "relu"), seed, workspace_bytes and the same normalize /
+        combination / contamination, e.g. outlier_ensemble(method="dif", n_representations=50, X=X); n_neighbors is not used
+        there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -261,6 +266,8 @@ class _RunFolder:
             ens = SubspaceOCSVM(self.subspaces, self.proba, **kw)
         elif method == "sos":
             ens = SubspaceSOS(self.subspaces, self.proba, **kw)
+        elif method == "dif":
+            ens = SubspaceDIF(self.subspaces, self.proba, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
