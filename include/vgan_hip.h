@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1292,6 +1292,48 @@ int vgan_sos_scores(const float* Pq, const float* sq_q, int nq, const float* Pr,
                     const int32_t* feat_off, const int64_t* col_off, int first, int count, int metric, const double* beta,
                     const double* dmin, const double* Z, int engine, int splits, uint64_t* acc, float* score,
                     const int32_t* score_row, int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Subspace outlier degree (SOD: Kriegel, Kroeger, Schubert, Zimek 2009; pyod's SOD): a row is judged against the rows that
+ * share the most nearest neighbours with it, in the features in which those rows vary little (v-gan_amd/outlier.py:
+ * SubspaceSOD, whose docstring is the definition; kernels in csrc/outlier_sod.hip).  Lists are the refined lists of
+ * vgan_outlier_refine, int32 [count, rows, k], 1 <= k <= VGAN_OUTLIER_MAX_K; count <= 65535.
+ * vgan_sod_reverse_lists: the reverse lists of the fit-time lists idx [count, n, k] as a CSR per subspace: RN(m) = the rows
+ *   whose list holds m = rn_rows[z, rn_off[z, m] .. rn_off[z, m + 1]) (rn_off int32 [count, n + 1], rn_rows int32 [count, n k]),
+ *   by an integer count, an exclusive scan and a fill.  The order of the rows inside one RN(m) is not specified: only integer
+ *   counts are formed from it.  cursor int32 [count, n] is scratch.  k < n <= VGAN_SOD_MAX_ROWS.  An entry outside [0, n) is
+ *   skipped (the lists of vgan_outlier_refine hold none).
+ * vgan_sod_reference_sets: refset[z, q, 0 .. ref_set) (int32 [count, nq, ref_set]) = the first ref_set fitted rows j in the
+ *   order (SNN(q, j) descending, j ascending), SNN(q, j) = |N(q) n N(j)| with N(q) = idxq[z, q, .] and N(j) the fit-time list
+ *   behind the CSR; rows with SNN = 0 take part.  exclude_self != 0 (fit: nq == nr, query q is fitted row q): j = q is left
+ *   out.  n_unshared (int32 [count], may be NULL): the number of query rows whose set took a row with SNN = 0.  The counts
+ *   are integers held as packed bytes in LDS, a table of one byte per fitted row, which is what bounds nr <=
+ *   VGAN_SOD_MAX_ROWS; the sets do not depend on the launch.  1 <= ref_set <= VGAN_SOD_MAX_REF, ref_set <= nr (nr - 1 with
+ *   exclude_self), k < nr.
+ * vgan_sod_score: per chunk subspace s = first + z (features F_s ascending, d_s of them; SUBSPACE TABLE feat / feat_off) and
+ *   query row q with R = refset[z, q, .]: mu_f = (sum_{r in R, in order} Xr[r, f]) / ref_set, v_f = (sum_{r in R, in order}
+ *   (Xr[r, f] - mu_f)^2) / ref_set, float64 from the raw float32 values, every operation rounded on its own (no FMA).  V =
+ *   sum_f v_f in this shape: 64 partial sums, partial l over the positions l, l + 64, ... of F_s ascending, then the partials
+ *   in order l = 0 .. 63.  T = (alpha V) / d_s; f is relevant iff v_f < T; r = the number of relevant features; Q = the sum
+ *   of (Xq[q, f] - mu_f)^2 over the relevant f in the same shape.  score = sqrt(Q / r) (VGAN_SOD_FORM_PYOD) or sqrt(Q) / r
+ *   (VGAN_SOD_FORM_PAPER), 0 where r = 0, rounded once to float32 (row and ld_score as for vgan_outlier_score).
+ *   n_relevant[z, q] = r (int32 [count, nq]).  mask (uint32 [count, nq, mask_words], may be NULL): bit i % 32 of word i / 32
+ *   is set iff position i of F_s is relevant; words at or past mask_words are not written, words past ceil(d_s / 64) 2 are
+ *   left as they are.  An entry of refset outside [0, nr) counts as a row at the origin.  0 < alpha <= 1.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_SOD_MAX_ROWS 32768
+#define VGAN_SOD_MAX_REF 64
+#define VGAN_SOD_FORM_PYOD 0
+#define VGAN_SOD_FORM_PAPER 1
+int vgan_sod_reverse_lists(const int32_t* idx, int n, int k, int count, int32_t* rn_off, int32_t* rn_rows, int32_t* cursor,
+                           vgan_stream_t stream);
+int vgan_sod_reference_sets(const int32_t* idxq, int nq, const int32_t* rn_off, const int32_t* rn_rows, int nr, int k, int count,
+                            int ref_set, int exclude_self, int32_t* refset, int32_t* n_unshared, vgan_stream_t stream);
+int vgan_sod_score(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
+                   const int32_t* feat_off, int first, int count, const int32_t* refset, int ref_set, double alpha, int form,
+                   float* score, const int32_t* score_row, int ld_score, int32_t* n_relevant, uint32_t* mask, int mask_words,
+                   vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

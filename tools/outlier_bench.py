@@ -90,6 +90,12 @@ difference of the two paths' ensemble scores.
     layer one vgan_gemm_grouped product on the weights of vgan_dif_weights and torch.tanh), scaled to all of them; and numpy
     (float32 products and tanh) plus sklearn's IsolationForest(6 trees, n_jobs=16) per block on 16 CPU threads for 2
     subspaces and 2 000 rows, scaled to all rows and subspaces.
+  --method sod: the subspace outlier degree (vgan_amd.SubspaceSOD) at d = 784, S = 50 sampled, n = 2000 and 10^4, with pyod's
+    defaults (n_neighbors 20, ref_set 10, alpha 0.8) and with (32, 31, 0.3): fit and decision_function (the training rows as
+    new rows) beside the LOF fit with the same n_neighbors on the same rows; the fit split into the neighbour lists (pack,
+    search, refine) and, launched alone on the resident lists, the reverse lists, the reference sets and the scores; the
+    LDS increments per second of the reference sets (sum over m of |RN(m)|^2) and the gather bandwidth of the scores (every
+    reference value is read four times).
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1569,18 +1575,67 @@ def run_dif(d, n, count, reps, baselines=True, sample=2, host_rows=2000):
     return row
 
 
+def run_sod(d, n, count, k, ref_set, alpha, reps):
+    """SubspaceSOD fit and decision_function (the training rows as new rows), the fit split into its stages on the resident
+    lists, beside the LOF fit with the same n_neighbors on the same rows in the same run."""
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    sod = vgan_amd.SubspaceSOD(m, p, n_neighbors=k, ref_set=ref_set, alpha=alpha)
+    lof = vgan_amd.SubspaceEnsemble(m, p, method="lof", n_neighbors=k)
+    t_fit, tf = timed(lambda: sod.fit(Xd), reps)
+    t_lof, tl = timed(lambda: lof.fit(Xd), reps)
+    t_dec, td = timed(lambda: sod.decision_function(Xd), reps)
+    t_lists, _ = timed(lambda: [None for _ in sod._neighbors(None)], reps)
+    lists = [(first, cnt, idx) for first, cnt, idx, _ in sod._neighbors(None)]
+    cursor = torch.empty(S, n, dtype=torch.int32, device="cuda")
+    per = torch.empty(S, n, dtype=torch.float32, device="cuda")
+
+    def reverse_launches():
+        for first, cnt, idx in lists:
+            sod.ops.sod_reverse_lists(idx, sod._rn_off[first:first + cnt], sod._rn_rows[first:first + cnt], cursor[:cnt])
+
+    def set_launches():
+        for first, cnt, idx in lists:
+            sod._sets(idx, first, cnt, sod._ref[first:first + cnt], sod._unshared[first:first + cnt])
+
+    def score_launches():
+        for first, cnt, idx in lists:
+            sod.ops.sod_score(sod._X, sod._X, sod._table, first, cnt, sod._ref[first:first + cnt], alpha, 0, per,
+                              sod._rows[first:first + cnt], sod._n_rel[first:first + cnt])
+
+    t_rev, _ = timed(reverse_launches, max(reps, 5))
+    t_sets, ts = timed(set_launches, max(reps, 5))
+    t_score, tsc = timed(score_launches, max(reps, 5))
+    rn = (sod._rn_off[:, 1:] - sod._rn_off[:, :-1]).double()
+    # the scoring launch reads every reference row's feature four times (two sums, formed for V and again for the mask and Q)
+    gather_bytes = 4.0 * 4.0 * n * ref_set * float(dims.sum())
+    increments = float((rn * rn).sum())  # sum over m of |RN(m)|^2: a row x adds |RN(m)| for each m in N(x)
+    return {"method": "sod", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_neighbors": k, "ref_set": ref_set, "alpha": alpha,
+            "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+            "sod_fit_s": round(t_fit, 5), "sod_fit_reps_s": tf, "lof_fit_s": round(t_lof, 5), "lof_fit_reps_s": tl,
+            "sod_over_lof": round(t_fit / t_lof, 3), "decision_function_s": round(t_dec, 5), "decision_function_reps_s": td,
+            "lists_s": round(t_lists, 5), "reverse_lists_s": round(t_rev, 6), "reference_sets_s": round(t_sets, 6),
+            "reference_sets_reps_s": ts, "scores_s": round(t_score, 6), "scores_reps_s": tsc,
+            "sod_stages_over_lists": round((t_rev + t_sets + t_score) / t_lists, 3),
+            "reverse_list_max": int(rn.max()), "increments": increments,
+            "increments_per_s": round(increments / t_sets / 1e9, 3), "n_unshared": int(sod.n_unshared_.sum()),
+            "n_relevant_median": float(np.median(sod.n_relevant_)),
+            "score_gather_bytes": gather_bytes, "score_gather_GBps": round(gather_bytes / t_score / 1e9, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
     ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / sod: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1708,6 +1763,15 @@ def main():
         for d, n, count in shapes:
             out["configs"].append(run_sos(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "sod":
+        shapes = [(784, 2000, 10)] if args.quick else [(784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            for k, ref_set, alpha in ((20, 10, 0.8), (32, 31, 0.3)):
+                out["configs"].append(run_sod(d, n, count, k, ref_set, alpha, args.reps))
+                print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "dif":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (784, 10_000, 50), (784, 50_000, 50)]

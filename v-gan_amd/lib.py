@@ -197,9 +197,12 @@ SIGNATURES = {
     "vgan_sos_fit": (_i, [_p, _i, _i, ctypes.c_double, ctypes.c_double, _i, _i, _p, _p, _p, _p, _p, _p]),
     "vgan_sos_fit_scores": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     "vgan_sos_scores": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i64, _p]),
+    "vgan_sod_reverse_lists": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "vgan_sod_reference_sets": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "vgan_sod_score": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, ctypes.c_double, _i, _p, _p, _i, _p, _p, _i, _p]),
 }
 
-ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_dif_* and vgan_iforest_*_blocks ones last) leave it
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_sod_* ones last) leave it
 _lib = None
 
 

@@ -1374,6 +1374,52 @@ class HipOps:
                                             int(splits), _ptr(acc), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
                    "vgan_sos_scores")
 
+    # ---- subspace outlier degree over subspaces (vgan_amd.outlier.SubspaceSOD) -------------------------------
+    # Lists are int32 [count, rows, k]; the reverse lists of a chunk are rn_off int32 [count, n + 1], rn_rows int32 [count, n k].
+    def sod_reverse_lists(self, idx, rn_off, rn_rows, cursor):
+        """The reverse lists of the fit-time lists idx [count, n, k] as a CSR per subspace; cursor int32 [count, n] is scratch."""
+        for t, name in ((idx, "idx"), (rn_off, "rn_off"), (rn_rows, "rn_rows"), (cursor, "cursor")):
+            _vec(t, name, torch.int32)
+        count, n, k = idx.shape
+        assert rn_off.numel() >= count * (n + 1) and rn_rows.numel() >= count * n * k and cursor.numel() >= count * n
+        _lib.check(self.lib.vgan_sod_reverse_lists(_ptr(idx), n, k, count, _ptr(rn_off), _ptr(rn_rows), _ptr(cursor), self._stream()),
+                   "vgan_sod_reverse_lists")
+
+    def sod_reference_sets(self, idxq, rn_off, rn_rows, nr, exclude_self, refset, n_unshared=None):
+        """refset [count, nq, ref_set] = the first ref_set fitted rows by (shared neighbours descending, index ascending) of the
+        lists idxq [count, nq, k] against the reverse lists; n_unshared [count] (fit) counts the sets that took a row sharing
+        nothing."""
+        for t, name in ((idxq, "idxq"), (rn_off, "rn_off"), (rn_rows, "rn_rows"), (refset, "refset")):
+            _vec(t, name, torch.int32)
+        count, nq, k = idxq.shape
+        assert refset.dim() == 3 and refset.shape[:2] == (count, nq)
+        assert rn_off.numel() >= count * (nr + 1) and rn_rows.numel() >= count * nr * k
+        if n_unshared is not None:
+            _vec(n_unshared, "n_unshared", torch.int32)
+            assert n_unshared.numel() >= count
+        _lib.check(self.lib.vgan_sod_reference_sets(_ptr(idxq), nq, _ptr(rn_off), _ptr(rn_rows), int(nr), k, count, refset.shape[2],
+                                                    int(bool(exclude_self)), _ptr(refset), _ptr(n_unshared), self._stream()),
+                   "vgan_sod_reference_sets")
+
+    def sod_score(self, Xq, Xr, table, first, count, refset, alpha, form, score, score_row, n_relevant, mask=None):
+        """SOD scores of the reference sets refset [count, nq, ref_set] into rows score_row of score, n_relevant int32 [count, nq];
+        mask (int32 [count, nq, words], optional) receives the packed relevance bits over the positions of each subspace."""
+        _mat(Xq, "Xq"), _mat(Xr, "Xr"), _vec(refset, "refset", torch.int32), _mat(score, "score")
+        _vec(n_relevant, "n_relevant", torch.int32)
+        feat, feat_off, _ = table
+        nq = Xq.shape[0]
+        assert Xq.shape[1] == Xr.shape[1] and refset.dim() == 3 and refset.shape[:2] == (count, nq)
+        assert n_relevant.numel() >= count * nq and score.shape[1] >= nq
+        words = 0
+        if mask is not None:
+            _vec(mask, "mask", torch.int32)
+            assert mask.dim() == 3 and mask.shape[:2] == (count, nq)
+            words = mask.shape[2]
+        _lib.check(self.lib.vgan_sod_score(_ptr(Xq), Xq.stride(0), nq, _ptr(Xr), Xr.stride(0), Xr.shape[0], Xq.shape[1], _ptr(feat),
+                                           _ptr(feat_off), int(first), int(count), _ptr(refset), refset.shape[2], float(alpha),
+                                           int(form), _ptr(score), _ptr(score_row), score.stride(0), _ptr(n_relevant), _ptr(mask),
+                                           int(words), self._stream()), "vgan_sod_score")
+
 
 _default = None
 

@@ -43,6 +43,14 @@ average chaining distance, the cost of walking from a row through its k neighbou
 (csrc/outlier_cof.hip); its contract (pairwise distances, the two chains, the weights, the ratio against the fitted rows,
 the zero-denominator rules and the ceiling degenerate rows take) is that class's docstring.
 
+``SubspaceSOD`` is the subspace outlier degree (SOD), the project's own idea one level down: each row chooses the features
+in which it is judged.  From the same neighbour lists it takes, per row, the fitted rows that share the most nearest
+neighbours with it (a sparse integer product over the reverse lists, counted in LDS), keeps the features of the subspace in
+which that reference set varies little, and measures the row's distance to the reference mean in those features only
+(csrc/outlier_sod.hip).  Its contract (lists, shared neighbours and the order among equals, the moments and their
+rounding, the summation shape, the threshold, the two score forms, r = 0, new rows, determinism, what is not built) is
+that class's docstring.
+
 ``SubspaceCBLOF`` is the cluster-based detector: k-means over all subspaces at once and the cluster-based local outlier
 factor on its clusters (csrc/cluster.hip); its contract (initial centres, the E and M steps and their precision, the stop
 rules, the final float64 assignment, large and small clusters, the score, determinism) is that class's docstring.
@@ -459,21 +467,25 @@ class _NeighborScorer(_SubspaceScorer):
         Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
         return Pq, sqq, Pr, sqr
 
-    def _chunks(self, Xq):
+    def _chunks(self, Xq, only=None):
         """Yields (first, count, engine, nq, Pq, sqq, Pr, sqr) per chunk of the plan: the packed blocks and squared norms
         of the nq query rows Xq and of the reference rows; Xq None is the reference set itself, whose blocks then serve as
-        both.  The generator keeps no reference to the blocks: they are freed when the consumer drops them."""
+        both.  only: a processing position, for the one chunk of that subspace alone.  The generator keeps no reference to
+        the blocks: they are freed when the consumer drops them."""
         nr = self._X.shape[0]
         nq = nr if Xq is None else Xq.shape[0]
-        for first, count, gram in self.plan.chunks(nr if Xq is None else nr + nq, self.workspace_bytes):
+        chunks = self.plan.chunks(nr if Xq is None else nr + nq, self.workspace_bytes) if only is None else [
+            (only, 1, bool(self.plan.gram[only]))]
+        for first, count, gram in chunks:
             yield (first, count, ENGINES["gram" if gram else "exact"], nq, *self._blocks(Xq, first, count, gram))
 
-    def _neighbors(self, Xq, kdist=None):
+    def _neighbors(self, Xq, kdist=None, only=None):
         """Yields (first, count, idx, dist) per chunk: the sorted refined lists [count, nq, k] of Xq (None: the reference
-        set, self excluded).  kdist (fit only): [S, n] receives the k-th distances in processing order."""
+        set, self excluded).  kdist (fit only): [S, n] receives the k-th distances in processing order.  only: as for
+        _chunks."""
         k, Xr = self.n_neighbors, self._X
         nr = Xr.shape[0]
-        for first, count, engine, nq, Pq, sqq, Pr, sqr in self._chunks(Xq):
+        for first, count, engine, nq, Pq, sqq, Pr, sqr in self._chunks(Xq, only):
             J = self._splits(nq, nr, count)
             nbr = torch.empty(count, nq, k, dtype=torch.int32, device=Xr.device)
             part_d = part_i = None
@@ -3366,3 +3378,172 @@ class SubspaceDIF(_SubspaceScorer):
         self._fitted = False
         scores, per = self._scores(X, True)
         return self._publish(scores, per)
+
+
+# ---- subspace outlier degree (SOD) over the subspaces ---------------------------------------------------------------------------
+SOD_MAX_ROWS = 1 << 15  # VGAN_SOD_MAX_ROWS: the shared-neighbour counts of all fitted rows are one byte each in a 32 KiB LDS table
+SOD_MAX_REF = 64  # VGAN_SOD_MAX_REF
+SOD_FORMS = {"pyod": 0, "paper": 1}  # VGAN_SOD_FORM_*
+SOD_LANES = 64  # partial sums of V and Q: the summation shape of the class docstring
+
+
+def check_sod_params(ref_set, alpha, form):
+    if not (_is_int(ref_set) and 1 <= int(ref_set) <= SOD_MAX_REF):
+        raise ValueError(f"ref_set must be an integer between 1 and {SOD_MAX_REF}, got {ref_set!r}")
+    if not (_is_real(alpha) and 0.0 < float(alpha) <= 1.0):
+        raise ValueError(f"alpha must be a number in (0, 1], got {alpha!r}")
+    if not (isinstance(form, str) and form in SOD_FORMS):
+        raise ValueError(f"form must be 'pyod' or 'paper', got {form!r}")
+    return int(ref_set), float(alpha), form
+
+
+class SubspaceSOD(_NeighborScorer):
+    """Subspace outlier degree per subspace (SOD: Kriegel, Kroeger, Schubert, Zimek 2009; pyod's ``SOD``), combined like the
+    detectors of SubspaceEnsemble: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows; higher is more
+    outlying.  Every distance detector here weighs all d_s features of a subspace alike, so a row that departs in two or
+    three of several hundred, in a direction in which its own neighbourhood is tight, is drowned by the spread of the
+    rest.  SOD lets each row choose the features in which it is judged: those in which the rows most similar to it vary
+    little.  It also says in which features a row is an outlier (``relevant_features``).
+
+    Everything is per subspace s, with features F_s in ascending order and d_s = |F_s|.
+
+    1. Lists.  N(j) is the refined neighbour list of fitted row j at ``fit``: the n_neighbors nearest fitted rows, j itself
+       excluded, ordered by (float32 distance, index): the very lists of SubspaceEnsemble (``kneighbors``).  For a new row q,
+       N(q) is its list among the fitted rows with nothing excluded.
+    2. Shared neighbours.  SNN(x, j) = |N(x) n N(j)|, the lists taken as sets of row indices, for every fitted j; at ``fit``
+       j != x.
+    3. Reference set.  R(x) is the first ref_set fitted rows in the order (SNN descending, row index ascending).  Rows with
+       SNN = 0 take part in that order: a set that cannot be filled from rows that share something takes the lowest
+       indices that share nothing, and ``n_unshared_[s]`` counts the fitted rows whose set had to.  A new row is scored
+       alone against the fitted state, whatever else is in the batch (the stance of SubspaceECOD and SubspaceSOS), so
+       ``decision_function(X_train)`` is not ``decision_scores_``: there a row's list starts with the row itself, and the
+       row may sit in its own reference set.
+    4. Moments, float64 from the raw float32 values, every difference, square, sum and quotient rounded on its own (no
+       fused multiply-add), the rows r of R(x) in the order of R:
+           mu_f = (sum_r X[r, f]) / ref_set,      v_f = (sum_r (X[r, f] - mu_f)^2) / ref_set.
+    5. Threshold.  V = sum_{f in F_s} v_f in this shape: 64 partial sums, partial l the sequential sum over the positions
+       l, l + 64, l + 128, ... of F_s (ascending), starting from 0; then the 64 partials added sequentially in the order
+       l = 0 .. 63, starting from 0 (``numpy.cumsum`` of the strided slices, then of the partials).  T = (alpha V) / d_s.
+       Feature f is relevant iff v_f < T, strictly; r is the number of relevant features.
+    6. Score.  Q = the sum of (x_f - mu_f)^2 over the relevant features in the same shape (a feature that is not relevant
+       adds nothing).  form "pyod": sqrt(Q / r); form "paper": sqrt(Q) / r; r = 0 gives 0 (pyod's rule): a reference set of
+       identical rows has r = 0, and so has a subspace of constant features.  The per-subspace score is that float64 value
+       rounded once to float32.
+
+    These are pyod's rules and the paper's as they are remembered here, made definite where they leave a choice (the order
+    among equal SNN, rows that share nothing, the summation shape, new rows).  pyod was not at hand to pin them, so the
+    definition above and its numpy restatement in tests/test_outlier_sod_cpu.py are what binds, not pyod.  Not built:
+    pyod's transductive ``decision_function`` (it ranks the new rows among themselves), reference sets by distance,
+    n_neighbors above 32, weights on the reference rows.
+
+    n_neighbors: 1 .. 32 (default 20, pyod's).  ref_set: 1 .. 64 (default 10, pyod's); it is not tied to n_neighbors, the
+    ranking runs over all fitted rows.  alpha: in (0, 1] (default 0.8, pyod's).  The defaults are pyod's; variances taken
+    from ten rows are noisy, and when few features matter a larger ref_set with a smaller alpha (31 and 0.3) is what works
+    (README).  form: "pyod" or "paper".  ``fit`` needs at least max(n_neighbors, ref_set) + 1 rows and takes at most
+    SOD_MAX_ROWS = 2^15: the shared-neighbour counts of all fitted rows live as one byte each in a table in LDS, and 2^15 rows
+    are the 32 KiB of it that still leave four workgroups a compute unit.  engine, splits, workspace_bytes: as for
+    SubspaceEnsemble.  normalize, combination, contamination, ``threshold_``, ``labels_``, ``predict``, ``predict_proba``,
+    return_per_subspace: the shared tail.
+
+    ``fit`` publishes, in the given subspace order: ``reference_set_`` (int32 [S, n, ref_set]), ``n_relevant_`` (int32
+    [S, n]) and ``n_unshared_`` (int [S]).  ``reference_set(X)`` returns the sets of new rows, ``relevant_features(s, X=None)``
+    the features of subspace s in which each row was judged, bool [n, d] in the model's feature coordinates.
+
+    The fitted state keeps, besides X, the reverse lists (for every fitted m the rows whose list holds m, a CSR per
+    subspace built from the lists by an integer count, a scan and a fill): about 4 S n n_neighbors bytes, and 4 S n ref_set
+    for the sets.  The lists themselves are not read again after ``fit`` and are not kept (``kneighbors`` forms them anew),
+    which halves the 8 S n n_neighbors bytes that keeping both would take.  SNN is a sparse integer product over the
+    reverse lists, O(n_neighbors mean|RN|) per row and never an n x n sweep; counts are integers, so reference sets, ``n_relevant_``, the relevance masks and the scores are bit-identical from run to
+    run, for every splits and workspace_bytes, and for a subspace fitted alone or with others.  The kernels are in
+    libvgan_hip.so (csrc/outlier_sod.hip)."""
+
+    def __init__(self, subspaces, proba, n_neighbors=20, ref_set=10, alpha=0.8, form="pyod", engine="auto", splits=None,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        self.ref_set, self.alpha, self.form = check_sod_params(ref_set, alpha, form)
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        self._configure_neighbors(n_neighbors, splits)
+
+    def _check_fit_rows(self, n):
+        least = max(self.n_neighbors, self.ref_set) + 1
+        if n < least:
+            raise ValueError(f"need at least max(n_neighbors, ref_set) + 1 = {least} fitted rows, got {n}")
+        if n > SOD_MAX_ROWS:
+            raise ValueError(f"SubspaceSOD fits at most SOD_MAX_ROWS = {SOD_MAX_ROWS} rows, got {n}")
+
+    def _sets(self, idx, first, count, out=None, n_unshared=None):
+        """int32 [count, nq, ref_set]: the reference sets of the lists idx against the fitted reverse lists of the chunk; with
+        n_unshared (fit) idx are the fitted lists themselves and a row is left out of its own set."""
+        if out is None:
+            out = torch.empty(count, idx.shape[1], self.ref_set, dtype=torch.int32, device=idx.device)
+        self.ops.sod_reference_sets(idx, self._rn_off[first:first + count], self._rn_rows[first:first + count], self._X.shape[0],
+                                    n_unshared is not None, out, n_unshared)
+        return out
+
+    def _score(self, Xq, fitting):
+        """(ensemble scores float64 [n], per float32 [S, n]), both on the device.  A chunk runs every stage: a subspace's sets
+        depend on its own lists alone."""
+        dev, n = self._X.device, self._X.shape[0]
+        nq = n if Xq is None else Xq.shape[0]
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=dev)
+        for first, count, idx, _ in self._neighbors(Xq):
+            if fitting:
+                cursor = torch.empty(count, n, dtype=torch.int32, device=dev)
+                self.ops.sod_reverse_lists(idx, self._rn_off[first:first + count], self._rn_rows[first:first + count], cursor)
+                ref = self._sets(idx, first, count, self._ref[first:first + count], self._unshared[first:first + count])
+                n_rel = self._n_rel[first:first + count]
+            else:
+                ref = self._sets(idx, first, count)
+                n_rel = torch.empty(count, nq, dtype=torch.int32, device=dev)
+            self.ops.sod_score(self._X if Xq is None else Xq, self._X, self._table, first, count, ref, self.alpha,
+                               SOD_FORMS[self.form], per, self._rows[first:first + count], n_rel)
+        return self._combine(per, fitting), per
+
+    def fit(self, X, y=None):
+        """Keeps X and the reverse lists resident and scores X (self excluded): decision_scores_ (float64 [n]),
+        per_subspace_scores_, reference_set_, n_relevant_, n_unshared_; with normalize also score_center_ / score_scale_."""
+        self._X = X = self._begin_fit(X)
+        S, n, k, dev = self.plan.count, X.shape[0], self.n_neighbors, X.device
+        self._rn_off = torch.empty(S, n + 1, dtype=torch.int32, device=dev)  # processing order, like everything below
+        self._rn_rows = torch.empty(S, n * k, dtype=torch.int32, device=dev)
+        self._ref = torch.empty(S, n, self.ref_set, dtype=torch.int32, device=dev)
+        self._n_rel = torch.empty(S, n, dtype=torch.int32, device=dev)
+        self._unshared = torch.empty(S, dtype=torch.int32, device=dev)
+        scores, per = self._score(None, fitting=True)
+        given = torch.as_tensor(self.plan.given, device=dev)
+        self.reference_set_ = self._ref[given].cpu().numpy()
+        self.n_relevant_ = self._n_rel[given].cpu().numpy()
+        self.n_unshared_ = self._unshared[given].cpu().numpy().astype(np.int64)
+        return self._publish(scores, per)
+
+    def reference_set(self, X):
+        """int32 [S, n, ref_set], given subspace order: the reference sets of the new rows X among the fitted rows."""
+        self._require_fit()
+        Xq = _device_matrix(X, self.plan.d)
+        out = torch.empty(self.plan.count, Xq.shape[0], self.ref_set, dtype=torch.int32, device=Xq.device)
+        for first, count, idx, _ in self._neighbors(Xq):
+            out[self._rows[first:first + count].long()] = self._sets(idx, first, count)
+        return out.cpu().numpy()
+
+    def relevant_features(self, s, X=None):
+        """bool [n, d] in the model's feature coordinates: the features of subspace s (its index in the given order) in
+        which each row was judged; X None: the fitted rows, from reference_set_.  Row i has n_relevant_[s, i] of them."""
+        self._require_fit()
+        if not (_is_int(s) and 0 <= int(s) < self.plan.count):
+            raise ValueError(f"s must be a subspace index between 0 and {self.plan.count - 1}, got {s!r}")
+        pos = int(self.plan.given[int(s)])
+        dev = self._X.device
+        if X is None:
+            Xq, ref = self._X, self._ref[pos:pos + 1]
+        else:
+            Xq = _device_matrix(X, self.plan.d)
+            ref = self._sets(next(self._neighbors(Xq, only=pos))[2], pos, 1)
+        nq, ds = Xq.shape[0], int(self.plan.dims[pos])
+        words = 2 * (-(-ds // SOD_LANES))
+        mask = torch.zeros(1, nq, words, dtype=torch.int32, device=dev)
+        scratch = torch.empty(1, nq, dtype=torch.float32, device=dev)
+        self.ops.sod_score(Xq, self._X, self._table, pos, 1, ref.contiguous(), self.alpha, SOD_FORMS[self.form], scratch, None,
+                           torch.empty(1, nq, dtype=torch.int32, device=dev), mask)
+        bits = np.unpackbits(mask[0].cpu().numpy().view(np.uint8), axis=1, bitorder="little")[:, :ds].astype(bool)
+        out = np.zeros((nq, self.plan.d), dtype=bool)
+        out[:, self.plan.feat[self.plan.feat_off[pos]:self.plan.feat_off[pos + 1]]] = bits
+        return out

@@ -15,7 +15,7 @@ from torch.utils.data import DataLoader
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
 from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
-                      SubspaceINNE, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOS)
+                      SubspaceINNE, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOD, SubspaceSOS)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -235,7 +235,12 @@ class _RunFolder:
         random, never trained MLPs per subspace; pyod's DIF): its keywords are n_representations, n_estimators, max_samples,
         hidden, representation_dim, activation ("tanh" or "relu"), seed, workspace_bytes and the same normalize /
         combination / contamination, e.g. outlier_ensemble(method="dif", n_representations=50, X=X); n_neighbors is not used
-        there."""
+        there.
+        method "sod" builds a SubspaceSOD (the subspace outlier degree: a row's reference set is the fitted rows that share
+        the most of its n_neighbors nearest neighbours, and it is judged in the features in which that set varies little;
+        pyod's SOD, whose default there is 20): its keywords are ref_set, alpha, form ("pyod" or "paper"), engine, splits,
+        workspace_bytes and the same normalize / combination / contamination, e.g.
+        outlier_ensemble(method="sod", n_neighbors=32, ref_set=31, alpha=0.3, X=X)."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -268,6 +273,8 @@ class _RunFolder:
             ens = SubspaceSOS(self.subspaces, self.proba, **kw)
         elif method == "dif":
             ens = SubspaceDIF(self.subspaces, self.proba, **kw)
+        elif method == "sod":
+            ens = SubspaceSOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
         else:
             ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
