@@ -502,7 +502,9 @@ int vgan_gemm_grouped_ksplit(const vgan_gemm_problem* problems, int count, const
  * chain (may be NULL; needs ZTh == NULL): as in vgan_mask_project_forward.
  * vgan_mask_project_forward_bf3_ex: the same launch with two more arguments.  write_z == 0: the fp32 operand Z is not written
  * (Z may be NULL; S, sq and the split images are written as always) -- for steps whose backward is
- * vgan_mmd_backward_bf3_rm_rebuild.  xrow (may be NULL): int32 [n], receives the data-set row of every batch row. */
+ * vgan_mmd_backward_bf3_rm_rebuild.  xrow (may be NULL): int32 [n], receives the data-set row of every batch row.
+ * Without ZTh, xx and chain and with 256 < d <= 1024 the launch runs one batch row per workgroup (d / 256 rounded up waves)
+ * instead of one per wave; every output is bit for bit the same. */
 typedef struct vgan_xx_job {
     const uint16_t* Dh;
     const uint16_t* Dl;

@@ -206,6 +206,10 @@ __global__ __launch_bounds__(kBlock) void mask_forward_vec_kernel(const float* _
     }
 }
 
+// One chunk's term of a split row's norm: the squares of the four values hi + lo, summed pairwise.  Both bf3 forward kernels take
+// it from here so that they agree bit for bit (-ffp-contract=fast may contract the squares and adds; one form, one code).
+__device__ __forceinline__ float norm_term4(const float (&z)[4]) { return (z[0] * z[0] + z[1] * z[1]) + (z[2] * z[2] + z[3] * z[3]); }
+
 // ---- the same forward fused with the operand preparation of the bf16x3 MMD kernels (vgan_mmd_bf3_prepare) -----------
 // A workgroup owns 8 consecutive batch rows (two per wave) and emits, besides everything mask_forward_vec_kernel emits,
 // the split images of both the X row and the Y = U*X row: row-major (Zh, Zl) straight from registers, transposed
@@ -224,7 +228,10 @@ __global__ __launch_bounds__(512) void mask_forward_bf3_kernel(const float* __re
                                                                  unsigned short* __restrict__ ZTl, int kn, int n, int d,
                                                                  const float* __restrict__ center, int write_x, int mask_blocks,
                                                                  XXJob xx, LogitsChain ch, int write_z, int* __restrict__ xrow) {
-    constexpr int R = 8;  // rows per workgroup = waves per workgroup (512 threads; 4 rows in 256 threads measured the same: 11.7 us)
+    // rows per workgroup = waves per workgroup (512 threads).  The lean launch (no transposed images) at n = 1024, d = 784:
+    // 8.80 us; with 4 rows in 256 threads, 256 workgroups over all CUs, 7.93 us; with a workgroup per row
+    // (mask_forward_bf3_split_kernel below, which that launch now goes to) 6.1-6.2 us.  The transposed store needs R = 8.
+    constexpr int R = 8;
     if constexpr (XX) {
         __shared__ __attribute__((aligned(16))) char xx_lds[GemmBF3<64>::kLdsBytes];
         __shared__ float xx_red[4];
@@ -303,8 +310,8 @@ __global__ __launch_bounds__(512) void mask_forward_bf3_kernel(const float* __re
                         xn[e] = bf16_val(h[0][e]) + bf16_val(l[0][e]);
                         yn[e] = bf16_val(h[1][e]) + bf16_val(l[1][e]);
                     }
-                    nx += (xn[0] * xn[0] + xn[1] * xn[1]) + (xn[2] * xn[2] + xn[3] * xn[3]);
-                    ny += (yn[0] * yn[0] + yn[1] * yn[1]) + (yn[2] * yn[2] + yn[3] * yn[3]);
+                    nx += norm_term4(xn);
+                    ny += norm_term4(yn);
 #pragma unroll
                     for (int im = 0; im < 2; ++im) {  // 0: X row i, 1: Y row n + i
                         const uint2 ph = make_uint2((unsigned)h[im][0] | ((unsigned)h[im][1] << 16), (unsigned)h[im][2] | ((unsigned)h[im][3] << 16));
@@ -351,6 +358,108 @@ __global__ __launch_bounds__(512) void mask_forward_bf3_kernel(const float* __re
         unsigned short* dst = ((im & 1) ? ZTl : ZTh) + (long)j * kn + (im >> 1) * n + i0;
         *reinterpret_cast<uint4*>(dst) = make_uint4(w0[0], w0[1], w0[2], w0[3]);
         *reinterpret_cast<uint4*>(dst + kn) = make_uint4(w1[0], w1[1], w1[2], w1[3]);
+    }
+}
+
+// ---- the lean fused forward (no transposed images, no riders, no logits chain) with one batch row per workgroup -------------
+// mask_forward_bf3_kernel gives a row to one wave, which walks its NT chunks in turn: at n = 1024 that is 128 workgroups on
+// half the CUs and ~1 100 VALU instructions in series per row.  Here a row has a workgroup of NT waves, and wave w owns what
+// iteration t = w of that loop gives to each lane (q = lane + 64 w), computed by the same lane with the same expressions.
+// The results are bit-identical: the old kernel folds a per-lane value over t = 0 .. NT-1 in ascending order and then runs a
+// wave butterfly, so each wave leaves its lane's chunk term in LDS and every wave that needs the row value folds the NT
+// terms of its lane in that same order before the same butterfly (per-wave reductions combined afterwards would
+// reassociate the sums).  A chunk without a valid element contributes what the old loop contributed: -inf to the max,
+// four exp(-inf) = 0 to the sum, and 0.f to the non-negative norm partials (exact).
+// Three exchanges: {max, X norm terms -- they do not depend on the softmax}, sum, Y norm terms.  Every wave reaches every
+// barrier: the grid is exactly n workgroups, nothing returns early, and q < nq guards stores only (loads are clamped).
+#ifndef VGAN_MASK_FWD_SPLIT
+#define VGAN_MASK_FWD_SPLIT 1  // 0: a control build that sends every shape to mask_forward_bf3_kernel
+#endif
+template <int NT>
+__global__ __launch_bounds__(64 * NT) void mask_forward_bf3_split_kernel(const float* __restrict__ logits, int ldl, const float* __restrict__ data,
+                                                                         int ldd, RowSel rows, float* __restrict__ S, float* __restrict__ Z,
+                                                                         int ldz, float* __restrict__ sq, unsigned short* __restrict__ Zh,
+                                                                         unsigned short* __restrict__ Zl, int kp, int n, int d,
+                                                                         const float* __restrict__ center, int write_x, int write_z,
+                                                                         int* __restrict__ xrow) {
+    __shared__ float red_m[NT][64], red_nx[NT][64], red_s[NT][64], red_ny[NT][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nq = d >> 2;
+    const int i = blockIdx.x;  // (uniform)
+    const int q = lane + 64 * wave, qc = min(q, nq - 1);
+    const bool ok = q < nq;
+    const float tau = 1.0f / (float)d;
+    // the logits and the centre do not wait for the row lookup (cursor -> epoch table -> data row): asked for first, they
+    // are in flight during it (measured: 6.43 -> 6.2 us per launch at n = 1024, d = 784)
+    float4 v = reinterpret_cast<const float4*>(logits + (long)i * ldl)[qc];
+    const float4 cv = center ? reinterpret_cast<const float4*>(center)[qc] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const long src = rows(i);
+    const float4 xv = reinterpret_cast<const float4*>(data + src * ldd)[qc];
+    if (xrow != nullptr && threadIdx.x == 0) xrow[i] = (int)src;
+    if (!ok) v = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    // X half: independent of the softmax
+    const float4 x4c = make_float4(centred_x(xv.x, cv.x), centred_x(xv.y, cv.y), centred_x(xv.z, cv.z), centred_x(xv.w, cv.w));
+    const float xs[4] = {x4c.x, x4c.y, x4c.z, x4c.w};
+    unsigned short h[4], l[4];
+    float xn[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        split_bf16(xs[e], h[e], l[e]);
+        xn[e] = bf16_val(h[e]) + bf16_val(l[e]);
+    }
+    if (ok && write_x) {
+        if (write_z) reinterpret_cast<float4*>(Z + (long)i * ldz)[q] = x4c;
+        const long grow = (long)i * kp + 4 * q;
+        *reinterpret_cast<uint2*>(Zh + grow) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
+        *reinterpret_cast<uint2*>(Zl + grow) = make_uint2((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16));
+    }
+    red_m[wave][lane] = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+    red_nx[wave][lane] = ok ? norm_term4(xn) : 0.f;
+    __syncthreads();
+    float m = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) m = fmaxf(m, red_m[t][lane]);
+    m = wave_max(m);
+    v.x = expf(v.x - m); v.y = expf(v.y - m); v.z = expf(v.z - m); v.w = expf(v.w - m);
+    red_s[wave][lane] = (v.x + v.y) + (v.z + v.w);
+    __syncthreads();
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sum += red_s[t][lane];
+    sum = wave_sum(sum);
+    const float4 s4 = make_float4(v.x / sum, v.y / sum, v.z / sum, v.w / sum);
+    const float4 u4 = make_float4(upper_mask(s4.x, tau), upper_mask(s4.y, tau), upper_mask(s4.z, tau), upper_mask(s4.w, tau));
+    const float4 y4 = make_float4(project_centred(u4.x, xv.x, cv.x), project_centred(u4.y, xv.y, cv.y), project_centred(u4.z, xv.z, cv.z),
+                                  project_centred(u4.w, xv.w, cv.w));
+    const float ys[4] = {y4.x, y4.y, y4.z, y4.w};
+    float yn[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        split_bf16(ys[e], h[e], l[e]);
+        yn[e] = bf16_val(h[e]) + bf16_val(l[e]);
+    }
+    if (ok) {
+        reinterpret_cast<float4*>(S + (long)i * d)[q] = s4;
+        if (write_z) reinterpret_cast<float4*>(Z + (long)(n + i) * ldz)[q] = y4;
+        const long grow = (long)(n + i) * kp + 4 * q;
+        *reinterpret_cast<uint2*>(Zh + grow) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
+        *reinterpret_cast<uint2*>(Zl + grow) = make_uint2((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16));
+    }
+    red_ny[wave][lane] = ok ? norm_term4(yn) : 0.f;
+    __syncthreads();  // the last barrier: only wave 0 has work left
+    if (wave == 0) {
+        float nx = 0.f, ny = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            nx += red_nx[t][lane];
+            ny += red_ny[t][lane];
+        }
+        nx = wave_sum(nx);
+        ny = wave_sum(ny);
+        if (lane == 0) {
+            if (write_x) sq[i] = nx;
+            sq[n + i] = ny;
+        }
     }
 }
 
@@ -644,6 +753,18 @@ extern "C" int vgan_mask_project_forward_bf3_ex(const float* logits, int ldl, co
                                         : (chain != nullptr ? (size_t)kChainK * chain_pitch(d) * sizeof(float) : 0);
     hipStream_t st = (hipStream_t)stream;
     const int nt = (d / 4 + 63) / 64;
+#if VGAN_MASK_FWD_SPLIT
+    // the lean forward of a row wider than one chunk: one row per workgroup of nt waves (mask_forward_bf3_split_kernel)
+    if (ZTh == nullptr && xxjob == nullptr && chain == nullptr && nt >= 2) {
+#define VGAN_LAUNCH_SPLIT(NT)                                                                                                       \
+    hipLaunchKernelGGL((mask_forward_bf3_split_kernel<NT>), dim3(n), dim3(64 * NT), 0, st, logits, ldl, data, ldd, sel, S, Z, ldz, sq, \
+                       Zh, Zl, kp, n, d, center, write_x, write_z, xrow)
+        if (nt == 2) VGAN_LAUNCH_SPLIT(2); else if (nt == 3) VGAN_LAUNCH_SPLIT(3); else VGAN_LAUNCH_SPLIT(4);
+#undef VGAN_LAUNCH_SPLIT
+        VGAN_CHECK_LAUNCH();
+        return VGAN_OK;
+    }
+#endif
     // (dynamic LDS above 64 KB -- d close to 1024 -- needs the opt-in; setting it is idempotent and cheap)
 #define VGAN_LAUNCH_K3(NT, XXF, CHF)                                                                                                \
     do {                                                                                                                            \
