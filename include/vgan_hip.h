@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1336,6 +1336,44 @@ int vgan_sod_score(const float* Xq, int ldq, int nq, const float* Xr, int ldr, i
                    const int32_t* feat_off, int first, int count, const int32_t* refset, int ref_set, double alpha, int form,
                    float* score, const int32_t* score_row, int ld_score, int32_t* n_relevant, uint32_t* mask, int mask_words,
                    vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Kernel PCA novelty scores (Hoffmann 2007: the reconstruction error in feature space; sklearn's KernelPCA for the
+ * decomposition; pyod's KPCA): K_s(x, y) = exp(-gamma_s d_s(x, y)^2) over m landmark rows, the eigenpairs of the centred
+ * kernel matrix, score = max(pot - sum_j w_j y_j^2, 0) (v-gan_amd/outlier.py: SubspaceKPCA, whose docstring is the
+ * definition; kernels in csrc/outlier_kpca.hip).  The kernel matrix is vgan_ocsvm_kernel_matrix's on the packed landmark
+ * block and the eigenpairs are vgan_pca_eigen's (standardize 0) with the synthetic tables feat_off = [0, m, 2 m, ...] and
+ * sq_off = [0, m^2, 2 m^2, ...].  The packed blocks, squared norms, SUBSPACE TABLE (feat_off, col_off), first, count (<=
+ * 65535), engine and splits are those of vgan_outlier_kde; gamma float64 [S], indexed by first + z.  2 <= m <=
+ * VGAN_KPCA_MAX_LANDMARKS (the eigensolver's VGAN_MAHA_MAX_DIMS).
+ * vgan_kpca_center: K float32 [count, m, m].  Only the entries K[z][r][c] with r <= c are read; K' is the symmetric matrix
+ *   they define.  col_mean[z][c] (float64 [count, m]) = (the sum of K'[r][c] over r ascending) / m; total[z] (float64 [count]) =
+ *   (the sum of col_mean[z][c] over c ascending) / m; Kc[z][i][j] (float64 [count, m, m], the layout vgan_pca_eigen reads with
+ *   the synthetic sq_off) = ((K'[i][j] - col_mean_j) - col_mean_i) + total for i <= j, written to both places: Kc is symmetric
+ *   to the bit.  Every operation is rounded on its own; there is no product.
+ * vgan_kpca_kernel_rows: R float32 [count, nq, m]; R[z][q][c] = float32 exp of float32(-gamma_s d2(q, c)), d2 the engine's
+ *   float32 squared distance of query row q of Pq and landmark row c of Pr (vgan_ocsvm_kernel_matrix's entry without the
+ *   diagonal rule).  Every entry is written once whatever splits is.  0 < nq <= VGAN_MAHA_MAX_ROWS.
+ * vgan_kpca_row_means: mean[r] (float64 [rows]) of every row of R [rows, m] (rows = count nq of a block): 64 partial sums,
+ *   partial l over the columns l, l + 64, ... ascending, combined by the xor butterfly (p_l += p_{l ^ o} for o = 32, 16, 8, 4,
+ *   2, 1), then divided by m.
+ * vgan_kpca_scores: score[score_row[z] (or z), i] = float32(max(pot_i - proj_i, 0)) for the rows of R [count, rows, m] with
+ *   row_mean [count, rows]: z_c = ((R[z][i][c] - row_mean_i) - col_mean_c) + total, y_j = sum_c V[j][c] z_c on the f64 matrix unit
+ *   (c ascending), proj = sum_j wt_j y_j^2 in vgan_pca_scores' order and with its skip rules (they depend on wt alone), pot =
+ *   (1 - 2 row_mean_i) + total.  col_mean, wt (float64 [S, m]), total (float64 [S]) and V (float64 [S, m, m], row j = component
+ *   j) are indexed by first + z.  ld_score >= rows.
+ * Every sum has one order: the bits of an element do not depend on the launch, the chunk or splits.  Every entry returns
+ * VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_KPCA_MAX_LANDMARKS 1024
+int vgan_kpca_center(const float* K, int m, int count, double* col_mean, double* total, double* Kc, vgan_stream_t stream);
+int vgan_kpca_kernel_rows(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int m,
+                          const int32_t* feat_off, const int64_t* col_off, int first, int count, const double* gamma, int engine,
+                          int splits, float* R, vgan_stream_t stream);
+int vgan_kpca_row_means(const float* R, int64_t rows, int m, double* mean, vgan_stream_t stream);
+int vgan_kpca_scores(const float* R, int rows, int m, int first, int count, const double* row_mean, const double* col_mean,
+                     const double* total, const double* V, const double* wt, float* score, const int32_t* score_row,
+                     int64_t ld_score, vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,12 @@ difference of the two paths' ensemble scores.
     search, refine) and, launched alone on the resident lists, the reverse lists, the reference sets and the scores; the
     LDS increments per second of the reference sets (sum over m of |RN(m)|^2) and the gather bandwidth of the scores (every
     reference value is read four times).
+  --method kpca: kernel PCA novelty scores (vgan_amd.SubspaceKPCA at its defaults, a 16 GiB workspace) at d = 784, S = 50 sampled, n
+    = 2000 and 10^4, with 256 landmarks (max_samples="auto") and with 1024: fit and decision_function (the training rows as
+    queries); one fit and one decision_function split into their calls, each behind a synchronisation (packing, landmark
+    kernel matrix, centring, eigensolver, kernel rows, row means plus scores), with the sweeps taken; the SubspacePCA and
+    SubspaceOCSVM (nu 0.1) fits on the same rows; and sklearn's KernelPCA(eigen_solver="dense") fitted on the landmark rows
+    and transforming all rows per subspace on 16 host threads for a sample of the subspaces, scaled to all of them.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1189,6 +1195,78 @@ def run_ocsvm(d, n, count, reps, baselines=True, nu=0.1, sample=4):
     return row
 
 
+class _StagedOps:
+    """The kernel provider with every call of the named entries behind a synchronisation, its time added to a stage."""
+
+    def __init__(self, ops, names, stages):
+        self._ops, self._names, self._stages = ops, names, stages
+
+    def __getattr__(self, name):
+        fn = getattr(self._ops, name)
+        stage = self._names.get(name)
+        if stage is None:
+            return fn
+
+        def wrapped(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **kw)
+            torch.cuda.synchronize()
+            self._stages[stage] = self._stages.get(stage, 0.0) + time.perf_counter() - t0
+            return out
+        return wrapped
+
+
+KPCA_STAGES = {"ocsvm_kernel_matrix": "kernel_matrix", "kpca_center": "centring", "pca_eigen": "eigen", "kpca_kernel_rows": "kernel_rows",
+               "kpca_row_means": "scores", "kpca_scores": "scores", "outlier_pack": "pack"}
+
+
+def run_kpca(d, n, count, reps, baselines=True, max_samples="auto", sample=4):
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    ens = vgan_amd.SubspaceKPCA(m, p, max_samples=max_samples, workspace_bytes=OCSVM_WORKSPACE)
+    t_fit, fit_reps = timed(lambda: ens.fit(Xd), reps)
+    t_dec, dec_reps = timed(lambda: ens.decision_function(Xd), reps)
+    dims, L = m.sum(axis=1), len(ens.landmark_rows_)
+    stages = {}
+    other = vgan_amd.SubspaceKPCA(m, p, max_samples=max_samples, workspace_bytes=OCSVM_WORKSPACE)
+    other._attach()
+    other.ops = _StagedOps(other.ops, KPCA_STAGES, stages)
+    other.fit(Xd)
+    assert np.array_equal(other.decision_scores_, ens.decision_scores_)
+    fit_stages = {k: round(v, 5) for k, v in stages.items()}
+    stages.clear()
+    other.decision_function(Xd)
+    dec_stages = {k: round(v, 5) for k, v in stages.items()}
+    row = {"method": "kpca", "d": d, "n": n, "landmarks": L, "S_sampled": count, "S_distinct": int(len(m)), "d_s_min": int(dims.min()),
+           "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()), "gram_subspaces": int(ens.plan.gram.sum()),
+           "fit_s": round(t_fit, 5), "fit_reps_s": fit_reps, "decision_function_s": round(t_dec, 5), "decision_function_reps_s": dec_reps,
+           "fit_stages_s": fit_stages, "decision_function_stages_s": dec_stages,
+           "eigen_share_of_fit": round(fit_stages["eigen"] / sum(fit_stages.values()), 3),
+           "sweeps_min": int(ens.n_sweeps_.min()), "sweeps_median": float(np.median(ens.n_sweeps_)), "sweeps_max": int(ens.n_sweeps_.max()),
+           "converged": bool(ens.converged_.all()), "n_usable_median": float(np.median(ens.n_usable_)),
+           "kernel_rows_TFLOPs": round(2.0 * n * L * float(dims.sum()) / dec_stages["kernel_rows"] / 1e12, 2),
+           "scores_f64_TFLOPs": round(2.0 * n * L * float(ens.n_components_.sum()) / dec_stages["scores"] / 1e12, 2)}
+    if baselines:
+        from sklearn.decomposition import KernelPCA
+        from threadpoolctl import threadpool_limits
+        row["pca_fit_s"] = round(timed(lambda: vgan_amd.SubspacePCA(m, p).fit(Xd), reps)[0], 5)
+        row["ocsvm_fit_s"] = round(timed(lambda: vgan_amd.SubspaceOCSVM(m, p, nu=0.1, workspace_bytes=OCSVM_WORKSPACE).fit(Xd), reps)[0], 5)
+        pick = np.unique(np.linspace(0, len(m) - 1, min(sample, len(m))).astype(int))
+        t_host = 0.0
+        with threadpool_limits(limits=16):
+            for s in pick:
+                Z = X[:, np.flatnonzero(m[s])].astype(np.float64)
+                t0 = time.perf_counter()
+                ref = KernelPCA(kernel="rbf", gamma=float(ens.gamma_[s]), eigen_solver="dense").fit(Z[ens.landmark_rows_])
+                ref.transform(Z)
+                t_host += time.perf_counter() - t0
+        row.update({"sklearn_subspaces_timed": [int(s) for s in pick], "sklearn_threads": 16,
+                    "sklearn_fit_and_transform_s_scaled": round(t_host / len(pick) * len(m), 3),
+                    "speedup_vs_sklearn": round(t_host / len(pick) * len(m) / (t_fit + t_dec), 1)})
+    return row
+
+
 def numpy_sos_one(Xs, perplexity, tol=1e-5, max_iter=200, threads=16, block=256):
     """(scores float64 [n], steps per row, seconds of matrix / search / scores): SubspaceSOS's rules for one subspace in numpy,
     float64 throughout, blocks of rows spread over a pool of `threads` threads (numpy's exp and sums release the GIL)."""
@@ -1629,13 +1707,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / kpca: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / sod: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / sod / kpca: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1755,6 +1833,15 @@ def main():
         for d, n, count in shapes:
             out["configs"].append(run_ocsvm(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "kpca":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for max_samples in ("auto",) if args.quick else ("auto", 1024):
+            for d, n, count in shapes:
+                out["configs"].append(run_kpca(d, n, count, args.reps, baselines=not args.no_baselines, max_samples=max_samples))
+                print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "sos":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 2000, 50), (10, 10_000, 50), (784, 2000, 50), (784, 10_000, 50)]

@@ -13,6 +13,10 @@ constexpr int kOLd = kOFB + 4;  // LDS row stride of those blocks (36 / 4 = 9 od
 
 __device__ __forceinline__ bool cand_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
 
+// An RBF kernel entry from an engine's d2 (outlier_ocsvm.hip, outlier_kpca.hip): float32 exp(-gamma d2), the argument formed
+// in float64 and rounded once
+__device__ __forceinline__ float rbf_entry(double gamma, float d2) { return expf((float)(-gamma * (double)d2)); }
+
 // LDS of the distance producer's engine: the Gram tile's operand images and a 64 x 65 d2 tile, or the exact engine's
 // two 64-row x 32-feature operand blocks
 template <bool GRAM>

@@ -1,0 +1,177 @@
+// Kernel PCA novelty scores over the subspaces (Hoffmann 2007: the reconstruction error in feature space; sklearn's KernelPCA
+// for the decomposition; v-gan_amd/outlier.py: SubspaceKPCA, whose docstring is the contract).
+//
+// Per subspace s with K_s(x, y) = exp(-gamma_s d_s(x, y)^2) and m landmark rows:
+//   1. kernel matrix  vgan_ocsvm_kernel_matrix (outlier_ocsvm.hip) on the packed landmark block: K float32 [m, m].
+//   2. center         K' = the symmetric matrix of the entries K[r][c], r <= c.  colmean_c = (the float64 sum of K'[r][c], r
+//                     ascending) / m, one thread per column; tot = (the sum of colmean_c, c ascending) / m, one thread per
+//                     subspace; Kc[i][j] = ((K'[i][j] - colmean_j) - colmean_i) + tot for i <= j, a thread per element, which
+//                     reads the upper-triangle entry of its pair: both places get the same bits.  No products: every
+//                     operation is rounded on its own.
+//   3. eigen          vgan_pca_eigen (outlier_pca.hip) on Kc with standardize = 0.
+//   4. kernel rows    the distance producer (outlier_dist.hpp, both engines) of the query rows against the packed landmark
+//                     block; the consumer stores rbf_entry row-major by query row, float32 [rows, m], no diagonal rule.
+//                     Lane l of a wave holds query row q0 + l and 16 neighbouring columns: a lane writes 64 consecutive bytes.
+//   5. row means      a wave per row: lane l adds the columns l, l + 64, ... in ascending order in float64, the 64 partials
+//                     combine by the xor butterfly 32, 16, 8, 4, 2, 1, and the sum is divided by m.
+//   6. scores         outlier_moments.hpp's weighted projection (the staging of pca_scores_kernel) with the operand z_c = ((k_c
+//                     - rowmean) - colmean_c) + tot formed while staging; score = float32(max(pot - proj, 0)), pot = (1 - 2
+//                     rowmean) + tot.
+// Every sum has one order and there is no atomic, so every published bit is the same from run to run.
+#include <math.h>
+
+#include "outlier_dist.hpp"
+#include "outlier_moments.hpp"
+
+namespace vgan {
+
+// the entry (r, c) of K': the upper-triangle entry of the pair
+__device__ __forceinline__ double kpca_sym(const float* __restrict__ K, int m, int r, int c) {
+    return (double)(r <= c ? K[(long)r * m + c] : K[(long)c * m + r]);
+}
+
+__global__ void kpca_col_mean_kernel(const float* __restrict__ K, int m, double* __restrict__ col_mean) {
+    const int z = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= m) return;
+    const float* Kz = K + (long)z * m * m;
+    double sum = 0.0;
+    for (int r = 0; r < m; ++r) sum += kpca_sym(Kz, m, r, c);
+    col_mean[(long)z * m + c] = sum / (double)m;
+}
+
+__global__ void kpca_total_kernel(const double* __restrict__ col_mean, int m, int count, double* __restrict__ total) {
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= count) return;
+    const double* cm = col_mean + (long)z * m;
+    double sum = 0.0;
+    for (int c = 0; c < m; ++c) sum += cm[c];
+    total[z] = sum / (double)m;
+}
+
+__global__ void kpca_center_kernel(const float* __restrict__ K, int m, const double* __restrict__ col_mean,
+                                   const double* __restrict__ total, double* __restrict__ Kc) {
+    const int z = blockIdx.y;
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x, mm = (long)m * m;
+    if (e >= mm) return;
+    const int r = (int)(e / m), c = (int)(e % m);
+    const int i = min(r, c), j = max(r, c);
+    const double* cm = col_mean + (long)z * m;
+    Kc[(long)z * mm + e] = (((double)K[(long)z * mm + (long)i * m + j] - cm[j]) - cm[i]) + total[z];
+}
+
+// R[z][q][c] = rbf_entry(gamma_s, d2(q, c)): the rectangular sibling of ocsvm_kernel_matrix_kernel, stored by query row
+template <bool GRAM>
+__global__ __launch_bounds__(kBlock, 2) void kpca_kernel_rows_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
+                                                                     const float* __restrict__ Pr, const float* __restrict__ sqr, int m,
+                                                                     const int32_t* __restrict__ feat_off,
+                                                                     const int64_t* __restrict__ col_off, int first, int splits,
+                                                                     const double* __restrict__ gamma, float* __restrict__ R) {
+    __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
+    const int z = blockIdx.z, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * kOTile + lane;
+    const double g = gamma[first + z];
+    float* Rq = R + ((long)z * nq + q) * m;
+    outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, m, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
+        if (q >= nq) return;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = c0 + j;
+            if (c < m) Rq[c] = rbf_entry(g, d2[j]);
+        }
+    });
+}
+
+// mean[row] of the rows of R [rows, m]: a wave per row
+__global__ __launch_bounds__(kBlock) void kpca_row_means_kernel(const float* __restrict__ R, long rows, int m, double* __restrict__ mean) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long row = (long)blockIdx.x * (kBlock / kWave) + wave;
+    if (row >= rows) return;
+    const float* Rr = R + row * m;
+    double sum = 0.0;
+    for (int c = lane; c < m; c += kWave) sum += (double)Rr[c];
+    sum = wave_sum(sum);
+    if (lane == 0) mean[row] = sum / (double)m;
+}
+
+__global__ __launch_bounds__(kBlock) void kpca_scores_kernel(const float* __restrict__ R, int rows, int m, int first,
+                                                             const double* __restrict__ row_mean, const double* __restrict__ col_mean,
+                                                             const double* __restrict__ total, const double* __restrict__ Vall,
+                                                             const double* __restrict__ wt, float* __restrict__ score,
+                                                             const int32_t* __restrict__ score_row, long ld_score) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int z = blockIdx.y, s = first + z;
+    const long r0 = (long)blockIdx.x * kMomBR;
+    const float* Rz = R + (long)z * rows * m;
+    const double* rm = row_mean + (long)z * rows;
+    const double* cm = col_mean + (long)s * m;
+    const double tot = total[s];
+    const double proj = weighted_projection_sqnorm(rows, r0, m, Vall + (long)s * m * m, wt + (long)s * m, [&](long row, int k) {
+        return (((double)Rz[row * m + k] - rm[row]) - cm[k]) + tot;
+    });
+    const long row = r0 + wave * kMomT + (lane & 15);
+    if (lane < 16 && row < rows) {
+        const double pot = (1.0 - 2.0 * rm[row]) + tot;
+        score[(long)(score_row ? score_row[z] : z) * ld_score + row] = (float)fmax(pot - proj, 0.0);
+    }
+}
+
+}  // namespace vgan
+
+using namespace vgan;
+
+static bool kpca_shape_ok(int m, int count) { return m >= 2 && m <= VGAN_KPCA_MAX_LANDMARKS && count > 0 && count <= 65535; }
+
+extern "C" int vgan_kpca_center(const float* K, int m, int count, double* col_mean, double* total, double* Kc,
+                                vgan_stream_t stream) {
+    VGAN_CHECK_ARG(K && col_mean && total && Kc && kpca_shape_ok(m, count));
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(kpca_col_mean_kernel, dim3((m + 63) / 64, count), dim3(64), 0, st, K, m, col_mean);
+    VGAN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kpca_total_kernel, dim3((count + 63) / 64), dim3(64), 0, st, col_mean, m, count, total);
+    VGAN_CHECK_LAUNCH();
+    const long mm = (long)m * m;
+    hipLaunchKernelGGL(kpca_center_kernel, dim3((unsigned)((mm + 255) / 256), count), dim3(256), 0, st, K, m, col_mean, total, Kc);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_kpca_kernel_rows(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int m,
+                                     const int32_t* feat_off, const int64_t* col_off, int first, int count, const double* gamma,
+                                     int engine, int splits, float* R, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && gamma && R && first >= 0 && kpca_shape_ok(m, count));
+    VGAN_CHECK_ARG(nq > 0 && nq <= VGAN_MAHA_MAX_ROWS);
+    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
+    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
+    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(Pq) && aligned16(Pr));
+    const dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
+    const hipStream_t st = (hipStream_t)stream;
+    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
+        hipLaunchKernelGGL(kpca_kernel_rows_kernel<true>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, m, feat_off, col_off, first,
+                           splits, gamma, R);
+    else
+        hipLaunchKernelGGL(kpca_kernel_rows_kernel<false>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, m, feat_off, col_off, first,
+                           splits, gamma, R);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_kpca_row_means(const float* R, int64_t rows, int m, double* mean, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(R && mean && m >= 2 && m <= VGAN_KPCA_MAX_LANDMARKS);
+    VGAN_CHECK_ARG(rows > 0 && rows <= (int64_t)65535 * VGAN_MAHA_MAX_ROWS && (rows + 3) / 4 <= 0x7fffffffL);
+    hipLaunchKernelGGL(kpca_row_means_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(kBlock), 0, (hipStream_t)stream, R, (long)rows, m,
+                       mean);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_kpca_scores(const float* R, int rows, int m, int first, int count, const double* row_mean,
+                                const double* col_mean, const double* total, const double* V, const double* wt, float* score,
+                                const int32_t* score_row, int64_t ld_score, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(R && row_mean && col_mean && total && V && wt && score && first >= 0 && kpca_shape_ok(m, count));
+    VGAN_CHECK_ARG(rows > 0 && rows <= VGAN_MAHA_MAX_ROWS && ld_score >= rows);
+    const dim3 grid((rows + kMomBR - 1) / kMomBR, count);
+    hipLaunchKernelGGL(kpca_scores_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, R, rows, m, first, row_mean, col_mean, total, V, wt,
+                       score, score_row, (long)ld_score);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}

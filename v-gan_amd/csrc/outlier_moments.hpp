@@ -1,6 +1,7 @@
 // The float64 moment and triangular-product core of the covariance detectors: Mahalanobis / MCD (outlier_maha.hip), the
-// Gaussian mixtures (outlier_gmm.hip) and, for the constants, PCA (outlier_pca.hip).  "Every published bit is the same from
-// run to run and for every workspace" holds because each sum below is written once and has one order.
+// Gaussian mixtures (outlier_gmm.hip) and, for the weighted projection at the end, PCA and kernel PCA (outlier_pca.hip,
+// outlier_kpca.hip).  "Every published bit is the same from run to run and for every workspace" holds because each sum
+// below is written once and has one order.
 //
 //   rows     a row-weight policy says how a row enters a moment sum.  SupportRows: a 0/1 support mask or none; a row outside
 //            the support is a zero operand and no multiply is added.  WeightedRows: a responsibility r; the row enters the
@@ -190,6 +191,73 @@ __device__ __forceinline__ double tri_product_sqnorm(const float* __restrict__ X
         for (int t = 0; t < kMomBI / kMomT; ++t)
 #pragma unroll
             for (int j = 0; j < 4; ++j) total += acc[t][j] * acc[t][j];
+    }
+    total += __shfl_xor(total, 16, 64);
+    total += __shfl_xor(total, 32, 64);
+    return total;
+}
+
+// sum_j w_j y_j^2, y_j = sum_k V[j][k] z_k, of the row r0 + wave * 16 + (lane & 15), valid in every lane: the staging of
+// tri_product_sqnorm with a full K range (V [d, d] is dense, row j a component), z(row, k) the operand of row < rows at k < d
+// and the weights wt [d] of 64 components at a time in LDS.  A 16-row tile of V whose weights are all 0 issues no MFMA, a
+// group of 64 without weight is not staged: which ones are skipped depends on wt alone.  A lane adds w_j y_j^2 over its
+// components in ascending order (j = (lane >> 4) + 4 i of each tile, tiles ascending), then the four lane groups are added as
+// (g + g^1) + (g^2 + g^3).  Every thread of the workgroup calls it (outlier_pca.hip, outlier_kpca.hip).  34 KB of LDS.
+template <class Operand>
+__device__ __forceinline__ double weighted_projection_sqnorm(int rows, long r0, int d, const double* __restrict__ V,
+                                                             const double* __restrict__ wt, Operand&& z) {
+    // a row stride of 34 doubles: the 32 lanes of a half-wave (16 rows x 2 k) read 32 different bank pairs
+    __shared__ double zs[kMomBR][kMomKC + 2];  // operand rows [row][k]
+    __shared__ double vs[kMomBI][kMomKC + 2];  // V [j][k]
+    __shared__ double wl[kMomBI];              // the weights of the group
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double total = 0.0;
+    for (int i0 = 0; i0 < d; i0 += kMomBI) {
+        __syncthreads();  // the previous group's weights have been read
+        if (tid < kMomBI) wl[tid] = i0 + tid < d ? wt[i0 + tid] : 0.0;
+        __syncthreads();
+        bool act[kMomBI / kMomT], any = false;
+#pragma unroll
+        for (int t = 0; t < kMomBI / kMomT; ++t) {
+            act[t] = false;
+            for (int q = 0; q < kMomT; ++q) act[t] |= wl[t * kMomT + q] != 0.0;
+            any |= act[t];
+        }
+        if (!any) continue;  // the same in every thread: it depends on wt alone
+        f64x4 acc[kMomBI / kMomT];
+#pragma unroll
+        for (int t = 0; t < kMomBI / kMomT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+        for (int k0 = 0; k0 < d; k0 += kMomKC) {
+            __syncthreads();  // the previous slab has been read
+            for (int e = tid; e < kMomBR * kMomKC; e += kBlock) {
+                const int rr = e / kMomKC, kk = e % kMomKC;
+                const bool ok = r0 + rr < rows && k0 + kk < d;
+                zs[rr][kk] = ok ? z(r0 + rr, k0 + kk) : 0.0;
+            }
+            for (int e = tid; e < kMomBI * kMomKC; e += kBlock) {
+                const int ii = e / kMomKC, kk = e % kMomKC;
+                const bool ok = i0 + ii < d && k0 + kk < d;
+                vs[ii][kk] = ok ? V[(long)(i0 + ii) * d + k0 + kk] : 0.0;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int t = 0; t < kMomBI / kMomT; ++t) {
+                if (!act[t]) continue;
+#pragma unroll
+                for (int ks = 0; ks < kMomKC; ks += 4) {
+                    const int kk = ks + (lane >> 4);
+                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(vs[t * kMomT + (lane & 15)][kk], zs[wave * kMomT + (lane & 15)][kk], acc[t],
+                                                                  0, 0, 0);
+                }
+            }
+        }
+        // result layout: column = lane & 15 (the data row), row = (lane >> 4) + 4 j (the component)
+#pragma unroll
+        for (int t = 0; t < kMomBI / kMomT; ++t) {
+            if (!act[t]) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) total += wl[t * kMomT + (lane >> 4) + 4 * j] * (acc[t][j] * acc[t][j]);
+        }
     }
     total += __shfl_xor(total, 16, 64);
     total += __shfl_xor(total, 32, 64);

@@ -29,9 +29,6 @@ __device__ __forceinline__ double mul_rounded(double a, double b) {
     return p;
 }
 
-// float32 exp(-gamma d2): the argument is formed in float64 and rounded once
-__device__ __forceinline__ float rbf_entry(double gamma, float d2) { return expf((float)(-gamma * (double)d2)); }
-
 // K[z][c][q] = exp(-gamma_s d2(q, c)), 1 on the diagonal.  Lane l of a wave holds row q0 + l of 16 columns: the entry of
 // the pair (q, c) goes to row c, so that the 64 lanes of a store write 64 consecutive floats.
 template <bool GRAM>

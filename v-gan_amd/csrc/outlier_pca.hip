@@ -22,11 +22,11 @@
 //            Then lambda_j = m_jj; rank_j = #{k : lambda_k > lambda_j or (lambda_k == lambda_j and k < j)} (descending, ties by
 //            the ascending diagonal position); a wave per component finds the entry of largest magnitude (lowest index on a
 //            tie) and writes the row to its rank, negated if that entry is negative.
-//   scores   the staging of outlier_moments.hpp's triangular product and its constants (a workgroup per (subspace, 64 rows), 64
-//            components a group, K in staged slabs of 32 through LDS) with a full K range, z_k = (x_k - mu_k) inv_scale_k, and the weights of the group in LDS: a 16-row
-//            tile of V whose weights are all 0 issues no MFMA, a group of 64 without weight is not staged.  A lane adds w_j
-//            y_j^2 over its components in ascending order (j = (lane >> 4) + 4 i of each tile, tiles ascending), then the
-//            four lane groups are added as (g + g^1) + (g^2 + g^3).  Which tiles are skipped depends on wt alone.
+//   scores   outlier_moments.hpp's weighted projection (a workgroup per (subspace, 64 rows), 64 components a group, K in staged
+//            slabs of 32 through LDS, a full K range) with z_k = (x_k - mu_k) inv_scale_k: a 16-row tile of V whose weights
+//            are all 0 issues no MFMA, a group of 64 without weight is not staged.  A lane adds w_j y_j^2 over its components
+//            in ascending order (j = (lane >> 4) + 4 i of each tile, tiles ascending), then the four lane groups are added as
+//            (g + g^1) + (g^2 + g^3).  Which tiles are skipped depends on wt alone.
 #include <math.h>
 
 #include "outlier_moments.hpp"
@@ -218,65 +218,13 @@ __global__ __launch_bounds__(kBlock) void pca_scores_kernel(const float* __restr
                                                             int first, const double* __restrict__ mean, const double* __restrict__ inv_scale,
                                                             const double* __restrict__ Vall, const double* __restrict__ wt,
                                                             float* __restrict__ score, long ld_score) {
-    // a row stride of 34 doubles: the 32 lanes of a half-wave (16 rows x 2 k) read 32 different bank pairs
-    __shared__ double zs[kMomBR][kMomKC + 2];  // standardised rows [row][k]
-    __shared__ double vs[kMomBI][kMomKC + 2];  // V [j][k]
-    __shared__ double wl[kMomBI];              // the weights of the group
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = first + blockIdx.y;
     const int f0 = feat_off[s], d = feat_off[s + 1] - f0;
-    const double* V = Vall + sq_off[s];
     const long r0 = (long)blockIdx.x * kMomBR;
-    double total = 0.0;
-    for (int i0 = 0; i0 < d; i0 += kMomBI) {
-        __syncthreads();  // the previous group's weights have been read
-        if (tid < kMomBI) wl[tid] = i0 + tid < d ? wt[f0 + i0 + tid] : 0.0;
-        __syncthreads();
-        bool act[kMomBI / kMomT], any = false;
-#pragma unroll
-        for (int t = 0; t < kMomBI / kMomT; ++t) {
-            act[t] = false;
-            for (int q = 0; q < kMomT; ++q) act[t] |= wl[t * kMomT + q] != 0.0;
-            any |= act[t];
-        }
-        if (!any) continue;  // the same in every thread: it depends on wt alone
-        f64x4 acc[kMomBI / kMomT];
-#pragma unroll
-        for (int t = 0; t < kMomBI / kMomT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-        for (int k0 = 0; k0 < d; k0 += kMomKC) {
-            __syncthreads();  // the previous slab has been read
-            for (int e = tid; e < kMomBR * kMomKC; e += kBlock) {
-                const int rr = e / kMomKC, kk = e % kMomKC;
-                const bool ok = r0 + rr < rows && k0 + kk < d;
-                zs[rr][kk] = ok ? ((double)Xq[(r0 + rr) * ldq + feat[f0 + k0 + kk]] - mean[f0 + k0 + kk]) * inv_scale[f0 + k0 + kk] : 0.0;
-            }
-            for (int e = tid; e < kMomBI * kMomKC; e += kBlock) {
-                const int ii = e / kMomKC, kk = e % kMomKC;
-                const bool ok = i0 + ii < d && k0 + kk < d;
-                vs[ii][kk] = ok ? V[(long)(i0 + ii) * d + k0 + kk] : 0.0;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < kMomBI / kMomT; ++t) {
-                if (!act[t]) continue;
-#pragma unroll
-                for (int ks = 0; ks < kMomKC; ks += 4) {
-                    const int kk = ks + (lane >> 4);
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(vs[t * kMomT + (lane & 15)][kk], zs[wave * kMomT + (lane & 15)][kk], acc[t],
-                                                                  0, 0, 0);
-                }
-            }
-        }
-        // result layout: column = lane & 15 (the data row), row = (lane >> 4) + 4 j (the component)
-#pragma unroll
-        for (int t = 0; t < kMomBI / kMomT; ++t) {
-            if (!act[t]) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) total += wl[t * kMomT + (lane >> 4) + 4 * j] * (acc[t][j] * acc[t][j]);
-        }
-    }
-    total += __shfl_xor(total, 16, 64);
-    total += __shfl_xor(total, 32, 64);
+    const double total = weighted_projection_sqnorm(rows, r0, d, Vall + sq_off[s], wt + f0, [&](long row, int k) {
+        return ((double)Xq[row * ldq + feat[f0 + k]] - mean[f0 + k]) * inv_scale[f0 + k];
+    });
     const long row = r0 + wave * kMomT + (lane & 15);
     if (lane < 16 && row < rows) score[(long)s * ld_score + row] = (float)total;
 }

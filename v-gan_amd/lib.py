@@ -200,9 +200,13 @@ SIGNATURES = {
     "vgan_sod_reverse_lists": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     "vgan_sod_reference_sets": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "vgan_sod_score": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, ctypes.c_double, _i, _p, _p, _i, _p, _p, _i, _p]),
+    "vgan_kpca_center": (_i, [_p, _i, _i, _p, _p, _p, _p]),
+    "vgan_kpca_kernel_rows": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p]),
+    "vgan_kpca_row_means": (_i, [_p, _i64, _i, _p, _p]),
+    "vgan_kpca_scores": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
-ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_sod_* ones last) leave it
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_kpca_* ones last) leave it
 _lib = None
 
 

@@ -1325,6 +1325,50 @@ class HipOps:
                                               _ptr(acc), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
                    "vgan_ocsvm_scores")
 
+    # ---- kernel PCA over subspaces (vgan_amd.outlier.SubspaceKPCA) --------------------------------------------
+    # K float32 [count, m, m] and R float32 [count, rows, m] are the arrays of one chunk; col_mean / wt float64 [S, m], total
+    # float64 [S] and V float64 [S, m, m] are the fitted state of every subspace, indexed by first + z.
+    def kpca_center(self, K, col_mean, total, Kc):
+        """col_mean [count, m], total [count] and the centred matrices Kc float64 [count, m, m] (vgan_pca_eigen's input with the
+        synthetic tables) from the upper triangles of K."""
+        _vec(K, "K"), _vec(col_mean, "col_mean", torch.float64), _vec(total, "total", torch.float64), _vec(Kc, "Kc", torch.float64)
+        if not (K.dim() == 3 and K.shape[1] == K.shape[2]):
+            raise ValueError(f"K: need [count, m, m], got {tuple(K.shape)}")
+        count, m = K.shape[0], K.shape[1]
+        assert col_mean.numel() >= count * m and total.numel() >= count and Kc.numel() >= count * m * m
+        _lib.check(self.lib.vgan_kpca_center(_ptr(K), m, count, _ptr(col_mean), _ptr(total), _ptr(Kc), self._stream()),
+                   "vgan_kpca_center")
+
+    def kpca_kernel_rows(self, Pq, sq_q, nq, Pr, sq_r, m, table, first, count, gamma, engine, splits, R):
+        """R[z][q][c] = exp(-gamma[first + z] d2) of query row q of Pq and landmark row c of Pr, no diagonal rule."""
+        _vec(Pq, "Pq"), _vec(Pr, "Pr"), _vec(gamma, "gamma", torch.float64), _vec(R, "R")
+        assert R.numel() >= count * nq * m and gamma.numel() >= first + count
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_kpca_kernel_rows(_ptr(Pq), _ptr(sq_q), int(nq), _ptr(Pr), _ptr(sq_r), int(m), _ptr(feat_off),
+                                                  _ptr(col_off), int(first), int(count), _ptr(gamma), int(engine), int(splits), _ptr(R),
+                                                  self._stream()), "vgan_kpca_kernel_rows")
+
+    def kpca_row_means(self, R, mean):
+        """mean float64 [count, rows]: the mean of every row of R [count, rows, m] in the header's fixed order."""
+        _vec(R, "R"), _vec(mean, "mean", torch.float64)
+        count, rows, m = R.shape
+        assert mean.numel() >= count * rows
+        _lib.check(self.lib.vgan_kpca_row_means(_ptr(R), count * rows, m, _ptr(mean), self._stream()), "vgan_kpca_row_means")
+
+    def kpca_scores(self, R, first, row_mean, col_mean, total, V, wt, score, score_row=None):
+        """score rows score_row (or z), columns 0 .. rows - 1 = max(pot - proj, 0) of the rows of R [count, rows, m] (a view into
+        the score matrix may be given)."""
+        _vec(R, "R"), _mat(score, "score")
+        for name, v in (("row_mean", row_mean), ("col_mean", col_mean), ("total", total), ("V", V), ("wt", wt)):
+            _vec(v, name, torch.float64)
+        count, rows, m = R.shape
+        S = first + count
+        assert row_mean.numel() >= count * rows and score.shape[1] >= rows
+        assert col_mean.numel() >= S * m and wt.numel() >= S * m and total.numel() >= S and V.numel() >= S * m * m
+        _lib.check(self.lib.vgan_kpca_scores(_ptr(R), rows, m, int(first), count, _ptr(row_mean), _ptr(col_mean), _ptr(total), _ptr(V),
+                                             _ptr(wt), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
+                   "vgan_kpca_scores")
+
     # ---- stochastic outlier selection over subspaces (vgan_amd.outlier.SubspaceSOS) --------------------------
     # D float32 [count, n, n] and beta / dmin / Z float64, n_iter / flags int32 [count, n]: the arrays of one chunk.
     def sos_distance_matrix(self, P, sq, n, table, first, count, metric, engine, splits, D):

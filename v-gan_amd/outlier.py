@@ -2713,6 +2713,19 @@ def ocsvm_chunks(plan, n, limit_bytes):
     return out
 
 
+def _resolve_rbf_gamma(plan, gamma, X):
+    """float64 [S] in processing order: ocsvm_gamma with, for "scale", the block variances over all rows of X (on the device)."""
+    var = None
+    if gamma == "scale":
+        Xd = X.double()
+        mean = Xd.mean(dim=0)
+        ssd = ((Xd - mean) ** 2).sum(dim=0)
+        mean, ssd = mean.cpu().numpy(), ssd.cpu().numpy()
+        var = [ocsvm_block_variance(mean, ssd, X.shape[0], plan.feat[plan.feat_off[z]:plan.feat_off[z + 1]])
+               for z in range(plan.count)]
+    return ocsvm_gamma(gamma, plan.dims, var)
+
+
 class SubspaceOCSVM(_SubspaceScorer):
     """One-class SVM per subspace (Schoelkopf et al. 2001; sklearn's OneClassSVM(kernel="rbf", shrinking=False), pyod's OCSVM),
     combined like the detectors of SubspaceEnsemble: ``fit`` sets ``decision_scores_``, ``decision_function`` scores new rows,
@@ -2797,15 +2810,7 @@ class SubspaceOCSVM(_SubspaceScorer):
 
     def _resolve_gamma(self, X):
         """float64 [S] in processing order."""
-        plan, var = self.plan, None
-        if self.gamma == "scale":
-            Xd = X.double()
-            mean = Xd.mean(dim=0)
-            ssd = ((Xd - mean) ** 2).sum(dim=0)
-            mean, ssd = mean.cpu().numpy(), ssd.cpu().numpy()
-            var = [ocsvm_block_variance(mean, ssd, X.shape[0], plan.feat[plan.feat_off[z]:plan.feat_off[z + 1]])
-                   for z in range(plan.count)]
-        return ocsvm_gamma(self.gamma, plan.dims, var)
+        return _resolve_rbf_gamma(self.plan, self.gamma, X)
 
     def _kernel_matrix(self, X, first, count, gram):
         n = X.shape[0]
@@ -2887,6 +2892,313 @@ class SubspaceOCSVM(_SubspaceScorer):
         self.n_iter_ = self._iters.cpu().numpy()[g].astype(np.int64)
         self.converged_ = self._done.cpu().numpy()[g] == _OCSVM_CONVERGED
         if self.keep_kernel_matrix:
+            self.kernel_matrix_ = kept
+        return self._publish(scores, per)
+
+
+# ---- kernel PCA: the reconstruction error in the feature space of an RBF kernel over landmark rows ------------------------
+KPCA_MAX_LANDMARKS = 1024  # VGAN_KPCA_MAX_LANDMARKS = VGAN_MAHA_MAX_DIMS: the eigensolver's limit
+KPCA_AUTO_LANDMARKS = 256  # max_samples="auto"
+KPCA_MAX_ROWS = MAHA_MAX_ROWS  # rows of one fit or one decision_function call
+_KPCA_SLAB = 64  # query rows of a scoring workgroup: row slabs are multiples of it
+
+
+def check_kpca_landmarks(landmarks):
+    """None, or an integer array [m] of distinct row indices >= 0, 2 <= m <= KPCA_MAX_LANDMARKS; returned as int64."""
+    if landmarks is None:
+        return None
+    idx = _index_array(landmarks)
+    if idx is None or idx.ndim != 1:
+        raise ValueError("landmarks must be None or a one-dimensional integer array of row indices")
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    if not 2 <= idx.shape[0] <= KPCA_MAX_LANDMARKS:
+        raise ValueError(f"landmarks must hold between 2 and {KPCA_MAX_LANDMARKS} rows, got {idx.shape[0]}")
+    if (idx < 0).any():
+        raise ValueError("landmarks must be >= 0")
+    if (np.diff(np.sort(idx)) == 0).any():
+        raise ValueError("landmarks must be distinct")
+    return idx
+
+
+def check_kpca_params(n_components, gamma, max_samples, landmarks, eig_tol, max_sweeps, seed):
+    """The constructor's checks of SubspaceKPCA, usable without a device: n_components None, an integer >= 1 or a float in
+    (0, 1); gamma as for SubspaceOCSVM; max_samples "auto" (256) or an integer between 2 and KPCA_MAX_LANDMARKS; landmarks as
+    check_kpca_landmarks; eig_tol a float in [0, 1); max_sweeps an integer >= 1; seed an integer in [0, 2^64).  Returns the
+    seven values in their canonical types."""
+    n_components, _ = check_pca_components(n_components, "major")
+    _, gamma, _, _ = check_ocsvm_params(0.5, gamma, 1e-3, None)
+    if not (isinstance(max_samples, str) and max_samples == "auto"):
+        if not (_is_int(max_samples) and 2 <= int(max_samples) <= KPCA_MAX_LANDMARKS):
+            raise ValueError(f"max_samples must be 'auto' or an integer between 2 and {KPCA_MAX_LANDMARKS}, got {max_samples!r}")
+        max_samples = int(max_samples)
+    if not (_is_real(eig_tol) and 0.0 <= float(eig_tol) < 1.0):  # False for nan
+        raise ValueError(f"eig_tol must be a float in [0, 1), got {eig_tol!r}")
+    if not (_is_int(max_sweeps) and int(max_sweeps) >= 1):
+        raise ValueError(f"max_sweeps must be a positive integer, got {max_sweeps!r}")
+    return n_components, gamma, max_samples, check_kpca_landmarks(landmarks), float(eig_tol), int(max_sweeps), check_seed(seed)
+
+
+def resolve_kpca_landmarks(landmarks, max_samples, n, seed):
+    """int64 [m]: the landmark rows for n fitted rows.  landmarks given: themselves (every index below n).  Otherwise m = min(n,
+    256) for "auto", min(max_samples, n) for an integer, and the rows are numpy.sort(numpy.random.default_rng(seed).choice(n, m,
+    replace=False))."""
+    if landmarks is not None:
+        if (landmarks >= n).any():
+            raise ValueError(f"landmark row {int(landmarks.max())} is out of range for {n} rows")
+        return landmarks
+    m = min(n, KPCA_AUTO_LANDMARKS if max_samples == "auto" else max_samples)
+    return np.sort(np.random.default_rng(seed).choice(n, m, replace=False)).astype(np.int64)
+
+
+def kpca_weights(evals, n_components, eig_tol):
+    """(wt float64 [m], q, n_usable) from the eigenvalues of a centred kernel matrix in descending order.  Component j is usable
+    iff lambda_j > eig_tol lambda_0 (none when lambda_0 <= 0); q = n_usable for None, min(n_components, n_usable) for an
+    integer, pca_component_count over the usable eigenvalues for a float; wt_j = 1 / lambda_j for j < q and 0 beyond."""
+    lam = np.asarray(evals, dtype=np.float64)
+    usable = int(np.count_nonzero(lam > eig_tol * lam[0])) if lam[0] > 0.0 else 0
+    q = pca_component_count(lam[:usable], n_components) if usable else 0
+    wt = np.zeros(lam.shape[0])
+    wt[:q] = 1.0 / lam[:q]
+    return wt, q, usable
+
+
+def kpca_fit_chunks(plan, m, limit_bytes):
+    """[(first, count, gram)]: consecutive runs of the processing order, one engine each, whose m x m kernel matrices (float32),
+    centred matrices (float64) and packed landmark blocks fit in limit_bytes; a subspace that alone exceeds it forms a chunk
+    of its own."""
+    out, first = [], 0
+    widths = _round4(plan.dims)
+    while first < plan.count:
+        end, used = first, 0
+        while end < plan.count and plan.gram[end] == plan.gram[first] and end - first < 65535:
+            need = int(m) * int(m) * 12 + int(m) * (int(widths[end]) + 1) * 4
+            if end > first and used + need > limit_bytes:
+                break
+            used += need
+            end += 1
+        out.append((first, end - first, bool(plan.gram[first])))
+        first = end
+    return out
+
+
+def kpca_chunks(plan, m, rows, limit_bytes):
+    """[(first, count, gram, slab)]: consecutive runs of the processing order, one engine each, scored `slab` query rows at a
+    time (a multiple of 64, or all `rows`).  A piece is one subspace times 64 rows (all rows when there are fewer): its float32
+    kernel block (m a row), float64 row means and packed query block (values and norms), plus the subspace's packed landmark
+    block.  A run takes subspaces while their pieces fit in limit_bytes, then as many rows a slab as still fit; a piece that
+    alone exceeds limit_bytes forms a chunk of its own."""
+    out, first = [], 0
+    widths = _round4(plan.dims)
+    least = min(int(rows), _KPCA_SLAB)
+    while first < plan.count:
+        end, fixed, per_row = first, 0, 0
+        while end < plan.count and plan.gram[end] == plan.gram[first] and end - first < 65535:
+            f, r = int(m) * (int(widths[end]) + 1) * 4, int(m) * 4 + 8 + (int(widths[end]) + 1) * 4
+            if end > first and fixed + f + (per_row + r) * least > limit_bytes:
+                break
+            fixed, per_row = fixed + f, per_row + r
+            end += 1
+        slab = max((int(limit_bytes) - fixed) // per_row // _KPCA_SLAB * _KPCA_SLAB, least)
+        out.append((first, end - first, bool(plan.gram[first]), min(slab, int(rows))))
+        first = end
+    return out
+
+
+class SubspaceKPCA(_SubspaceScorer):
+    """Kernel PCA novelty scores per subspace (Hoffmann 2007: the reconstruction error in the feature space of an RBF kernel;
+    sklearn's ``KernelPCA`` for the decomposition, pinned in tests/test_outlier_kpca_cpu.py; pyod's ``KPCA`` score as
+    remembered, not pinned), combined like the other detectors of this module: ``fit`` sets ``decision_scores_``,
+    ``decision_function`` scores new rows; higher is more outlying.  It is the nonlinear ``SubspacePCA(components="minor",
+    weighted=False)``: a row is scored by what of its feature-space image the leading kernel components do not explain, so
+    it also finds rows that sit inside the data (the centre of a ring).  This docstring is the contract.
+
+    Landmarks.  m = min(n, 256) for max_samples="auto", else min(max_samples, n) with max_samples in 2 .. 1024
+    (KPCA_MAX_LANDMARKS, the eigensolver's limit).  The rows are numpy.sort(numpy.random.default_rng(seed).choice(n, m,
+    replace=False)), drawn once on the host and the same for every subspace (SubspaceCBLOF's stance: a subspace fitted alone
+    gives the same bits as one fitted with others); ``landmarks`` may be an integer array [m] of distinct row indices
+    instead, used in the given order.  ``fit`` copies the m landmark rows and keeps them; X itself does not stay resident,
+    so ``fit`` takes 2 to 2^24 rows.  Published: ``landmark_rows_``.
+
+    Kernel.  K_s(x, y) = exp(-gamma_s d_s(x, y)^2) on the raw features of subspace s; gamma follows exactly the rules and
+    helpers of SubspaceOCSVM (a positive float, "scale" = 1 / (d_s var) with var the float64 variance over all n x d_s entries
+    of the fitted block, 1.0 where it is 0, or "auto" = 1 / d_s; ocsvm_gamma, ocsvm_block_variance).  ``gamma_`` is float64 [S].
+
+    Fit, per subspace.  K, float32 [m, m], is SubspaceOCSVM's kernel matrix on the packed landmark block (the float32 exp of
+    float32(-gamma_s d2), d2 from the distance engines; the diagonal exactly 1).  It is not bitwise symmetric, so only the
+    entries K[r][c] with r <= c are read; K' is the symmetric matrix they define.  colmean_c = (the float64 sum of K'[r][c] over
+    r ascending) / m; tot = (the sum of colmean_c over c ascending) / m; Kc[i][j] = ((K'[i][j] - colmean_j) - colmean_i) + tot for
+    i <= j, written to both places.  Every operation is rounded on its own and there is no product, so numpy gives the same
+    bits.  The eigenpairs of Kc are SubspacePCA's solver's (vgan_pca_eigen with standardize = 0): eigenvalues descending,
+    ties by position, each vector a_j a unit vector signed by its entry of largest magnitude; ``n_sweeps_`` and
+    ``converged_`` as for SubspacePCA.  Component j is usable iff lambda_j > eig_tol lambda_0: K has float32 entries, so
+    eigenvalues around m 2^-24 are rounding noise, and a centred matrix always has one zero eigenvalue (``n_usable_``).
+    n_components=None takes every usable component, an integer q the first q usable ones, a float in (0, 1) follows
+    pca_component_count's cumulative rule over the usable eigenvalues (``n_components_``).  The weight of component j is w_j =
+    1 / lambda_j where selected and 0 otherwise (kpca_weights, on the host from the fetched eigenvalues).
+
+    Score of a row x (the same path for ``fit`` and ``decision_function``, nothing excluded).  k_c = float32 exp(float32(-gamma_s
+    d2(x, landmark c))) from the distance engines, without a diagonal rule.  rowmean is the float64 mean of the k_c: 64 partial
+    sums, partial l over the columns l, l + 64, ... ascending, combined by the xor butterfly 32, 16, 8, 4, 2, 1, divided by
+    m.  z_c = ((k_c - rowmean) - colmean_c) + tot.  y_j = sum_c a_j[c] z_c on the float64 matrix unit, c ascending.  proj =
+    sum_j w_j y_j^2 in SubspacePCA's order.  pot = (1.0 - 2.0 rowmean) + tot.  score = float32(max(pot - proj, 0.0)): with
+    y_j / sqrt(lambda_j) sklearn's ``KernelPCA.transform``, this is k(x, x) - 2 mean_c k_c + tot - ||transform(x)||^2.
+
+    Special cases and invariants.  A subspace of constant features has K = 1 everywhere, Kc = 0 exactly, no usable component
+    and pot = 0: every row scores exactly 0.  ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.  Every
+    sum has one order and there is no atomic: scores and every published array are bit-identical from run to run, for every
+    workspace_bytes, for every splits, and for a subspace fitted alone or with others.
+
+    Published, beside the common attributes and in the given subspace order: ``eigenvalues_`` (list of S float64 [m]),
+    ``components_`` (list of S float64 [m, m], row j = a_j; fetched on first use), ``n_components_``, ``n_usable_``,
+    ``n_sweeps_`` (int [S]), ``converged_`` (bool [S]), ``column_mean_`` (float64 [S, m]), ``total_mean_`` (float64 [S]),
+    ``gamma_``, ``landmark_rows_`` (int64 [m]).  ``kernel_rows(X, s)`` returns the float32 [n, m] block the scorer reads for
+    subspace s.  One attribute, set after construction, serves tests and changes no result: ``keep_kernel_matrix`` (True:
+    ``fit`` also publishes ``kernel_matrix_``, a list of S float32 [m, m] arrays, the matrices the centring read).
+
+    engine, splits (the landmark split of the two distance sweeps), normalize, combination and contamination are those of
+    SubspaceEnsemble; workspace_bytes bounds the kernel and centred matrices of a fit chunk and the kernel block, row means
+    and packed blocks of a scoring chunk (kpca_fit_chunks, kpca_chunks).
+
+    Not built: other kernels, pyod's ``sampling`` / ``subset_size`` names, a precomputed kernel, more than 1024 landmarks (a
+    blocked or Lanczos eigensolver), pre-images and sklearn's ``fit_inverse_transform``.  All of it runs in libvgan_hip.so
+    (csrc/outlier_kpca.hip; the kernel matrix in csrc/outlier_ocsvm.hip, the eigensolver in csrc/outlier_pca.hip)."""
+
+    _components = None
+
+    def __init__(self, subspaces, proba, n_components=None, gamma="scale", max_samples="auto", landmarks=None, eig_tol=1e-6,
+                 max_sweeps=30, seed=0, engine="auto", splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None,
+                 combination="sum", contamination=0.1):
+        (self.n_components, self.gamma, self.max_samples, self.landmarks, self.eig_tol, self.max_sweeps,
+         self.seed) = check_kpca_params(n_components, gamma, max_samples, landmarks, eig_tol, max_sweeps, seed)
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
+            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
+        self.splits = splits
+        self.keep_kernel_matrix = False
+
+    # ---- pipeline --------------------------------------------------------------------------------
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= KPCA_MAX_ROWS:
+            raise ValueError(f"SubspaceKPCA fit needs between 2 and {KPCA_MAX_ROWS} rows, got {n}")
+
+    def _splits(self, nq, count):
+        if self.splits is not None:
+            return int(self.splits)
+        blocks = -(-nq // 64) * count
+        return int(max(1, min(-(-self._m // 64), -(-_TARGET_BLOCKS // blocks))))
+
+    def _decompose(self, kept):
+        """The kernel matrix, its centring and its eigenpairs for every subspace, chunk by chunk."""
+        m, dev = self._m, self._L.device
+        chunks = kpca_fit_chunks(self.plan, m, self.workspace_bytes)
+        most = max(count for _, count, _ in chunks)
+        syn = (None, torch.as_tensor(np.arange(most + 1, dtype=np.int32) * m, device=dev),
+               torch.as_tensor(np.arange(most + 1, dtype=np.int64) * m * m, device=dev))
+        scale = torch.empty(most * m, dtype=torch.float64, device=dev)
+        for first, count, gram in chunks:
+            P, sq = self._pack(self._L, first, count, gram)
+            K = torch.empty(count, m, m, dtype=torch.float32, device=dev)
+            self.ops.ocsvm_kernel_matrix(P, sq, m, self._table, first, count, self._gamma, ENGINES["gram" if gram else "exact"],
+                                         self._splits(m, count), K)
+            Kc = torch.empty(count * m * m, dtype=torch.float64, device=dev)
+            self.ops.kpca_center(K, self._col_mean[first:first + count], self._total[first:first + count], Kc)
+            self.ops.pca_eigen(Kc, syn, 0, count, m, False, self.max_sweeps, scale[:count * m], self._evals[first:first + count].view(-1),
+                               self._V[first:first + count].view(-1), self._sweeps[first:first + count],
+                               self._status[first:first + count])
+            if kept is not None:
+                host = K.cpu().numpy()
+                for z in range(count):
+                    kept[int(self.plan.order[first + z])] = host[z]
+            del P, sq, K, Kc
+
+    def _select(self):
+        """Host: the usable components, q_s and the weights from the fetched eigenvalues; uploads the weights."""
+        evals = self._evals.cpu().numpy()
+        picks = [kpca_weights(lam, self.n_components, self.eig_tol) for lam in evals]
+        self._wt = torch.as_tensor(np.stack([p[0] for p in picks]), device=self._evals.device)
+        g = self.plan.given
+        self.eigenvalues_ = [evals[z].copy() for z in g]
+        self.n_components_ = np.array([picks[z][1] for z in g], dtype=np.int64)
+        self.n_usable_ = np.array([picks[z][2] for z in g], dtype=np.int64)
+        self.n_sweeps_ = self._sweeps.cpu().numpy()[g].astype(np.int64)
+        self.converged_ = (self._status.cpu().numpy()[g] & _PCA_NOT_CONVERGED) == 0
+
+    def _kernel_rows(self, Xs, Pr, sqr, first, count, gram):
+        """float32 [count, rows, m] on the device: the kernel block of the rows Xs against the chunk's landmark block."""
+        rows = Xs.shape[0]
+        Pq, sqq = self._pack(Xs, first, count, gram)
+        R = torch.empty(count, rows, self._m, dtype=torch.float32, device=Xs.device)
+        self.ops.kpca_kernel_rows(Pq, sqq, rows, Pr, sqr, self._m, self._table, first, count, self._gamma,
+                                  ENGINES["gram" if gram else "exact"], self._splits(rows, count), R)
+        return R
+
+    def _score(self, Xq, fitting):
+        nq = Xq.shape[0]
+        if nq > KPCA_MAX_ROWS:
+            raise ValueError(f"SubspaceKPCA scores at most {KPCA_MAX_ROWS} rows a call, got {nq}")
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xq.device)
+        for first, count, gram, slab in kpca_chunks(self.plan, self._m, nq, self.workspace_bytes):
+            Pr, sqr = self._pack(self._L, first, count, gram)
+            for r0 in range(0, nq, slab):
+                rows = min(slab, nq - r0)
+                R = self._kernel_rows(Xq[r0:r0 + rows], Pr, sqr, first, count, gram)
+                mean = torch.empty(count, rows, dtype=torch.float64, device=Xq.device)
+                self.ops.kpca_row_means(R, mean)
+                self.ops.kpca_scores(R, first, mean, self._col_mean, self._total, self._V, self._wt, per[:, r0:r0 + rows],
+                                     self._rows[first:first + count])
+                del R, mean
+            del Pr, sqr
+        return self._combine(per, fitting), per
+
+    # ---- public surface --------------------------------------------------------------------------
+    def kernel_rows(self, X, s):
+        """float32 [n, m]: exp(-gamma_s d2) of the rows of X against the landmark rows in subspace s (given order), the block
+        the scorer reads."""
+        self._require_fit()
+        if not (_is_int(s) and 0 <= int(s) < self.plan.count):
+            raise ValueError(f"s must be a subspace index between 0 and {self.plan.count - 1}, got {s!r}")
+        Xq = _device_matrix(X, self.plan.d)
+        z = int(self.plan.given[int(s)])
+        gram = bool(self.plan.gram[z])
+        Pr, sqr = self._pack(self._L, z, 1, gram)
+        return self._kernel_rows(Xq, Pr, sqr, z, 1, gram)[0].cpu().numpy()
+
+    @property
+    def components_(self):
+        """List of S float64 [m, m]: row j the coefficients a_j of the j-th kernel component over the landmarks."""
+        self._require_fit()
+        if self._components is None:
+            V = self._V.cpu().numpy()
+            self._components = [V[z].copy() for z in self.plan.given]
+        return self._components
+
+    def fit(self, X, y=None):
+        """The landmarks, their kernel matrix, its centring and eigenpairs, q_s and the weights of every subspace, then the
+        scores of X itself: decision_scores_ (float64 [n]), per_subspace_scores_, eigenvalues_, components_, n_components_,
+        n_usable_, n_sweeps_, converged_, column_mean_, total_mean_, gamma_, landmark_rows_; with normalize also score_center_
+        / score_scale_.  Only the landmark rows stay resident."""
+        X = self._begin_fit(X)
+        n, S, dev = X.shape[0], self.plan.count, X.device
+        self._fitted, self._components = False, None
+        rows = resolve_kpca_landmarks(self.landmarks, self.max_samples, n, self.seed)
+        self._m = m = int(rows.shape[0])
+        self._L = X[torch.as_tensor(rows, device=dev)].contiguous()
+        gamma = _resolve_rbf_gamma(self.plan, self.gamma, X)
+        self._gamma = torch.as_tensor(gamma, device=dev)
+        self._col_mean, self._evals = (torch.empty(S, m, dtype=torch.float64, device=dev) for _ in range(2))
+        self._total = torch.empty(S, dtype=torch.float64, device=dev)
+        self._V = torch.empty(S, m, m, dtype=torch.float64, device=dev)
+        self._sweeps, self._status = (torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2))
+        kept = [None] * S if self.keep_kernel_matrix else None
+        self._decompose(kept)
+        self._select()
+        scores, per = self._score(X, fitting=True)
+        g = self.plan.given
+        self.gamma_ = gamma[g]
+        self.column_mean_ = self._col_mean.cpu().numpy()[g]
+        self.total_mean_ = self._total.cpu().numpy()[g]
+        self.landmark_rows_ = rows.copy()
+        if kept is not None:
             self.kernel_matrix_ = kept
         return self._publish(scores, per)
 

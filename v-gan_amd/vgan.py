@@ -15,7 +15,7 @@ from torch.utils.data import DataLoader
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
 from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
-                      SubspaceINNE, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOD, SubspaceSOS)
+                      SubspaceINNE, SubspaceKPCA, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOD, SubspaceSOS)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -240,7 +240,12 @@ class _RunFolder:
         the most of its n_neighbors nearest neighbours, and it is judged in the features in which that set varies little;
         pyod's SOD, whose default there is 20): its keywords are ref_set, alpha, form ("pyod" or "paper"), engine, splits,
         workspace_bytes and the same normalize / combination / contamination, e.g.
-        outlier_ensemble(method="sod", n_neighbors=32, ref_set=31, alpha=0.3, X=X)."""
+        outlier_ensemble(method="sod", n_neighbors=32, ref_set=31, alpha=0.3, X=X).
+        method "kpca" builds a SubspaceKPCA (kernel PCA novelty scores: the eigenpairs of the centred RBF kernel matrix of a
+        few landmark rows per subspace, the score the reconstruction error in feature space; sklearn's KernelPCA, pyod's
+        KPCA): its keywords are n_components, gamma, max_samples, landmarks, eig_tol, max_sweeps, seed, engine, splits,
+        workspace_bytes and the same normalize / combination / contamination, e.g.
+        outlier_ensemble(method="kpca", n_components=8, X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -273,6 +278,8 @@ class _RunFolder:
             ens = SubspaceSOS(self.subspaces, self.proba, **kw)
         elif method == "dif":
             ens = SubspaceDIF(self.subspaces, self.proba, **kw)
+        elif method == "kpca":
+            ens = SubspaceKPCA(self.subspaces, self.proba, **kw)
         elif method == "sod":
             ens = SubspaceSOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
         else:
