@@ -187,6 +187,52 @@ def test_planner_chunks_respect_the_byte_limit_and_the_engine_boundary():
     assert len(plan.chunks(rows, 10 ** 9)) == (2 if plan.gram.any() and not plan.gram.all() else 1)
 
 
+def _greedy_chunks(plan, need, limit, cap):
+    """The chunk loop as ocsvm_chunks, kpca_fit_chunks (cap 65535) and SubspacePlan.chunks (no cap) each spelt it out; need(z):
+    the bytes of the subspace at processing position z."""
+    out, first = [], 0
+    while first < plan.count:
+        end, used = first, 0
+        while end < plan.count and plan.gram[end] == plan.gram[first] and (cap is None or end - first < cap):
+            if end > first and used + need(end) > limit:
+                break
+            used += need(end)
+            end += 1
+        out.append((first, end - first, bool(plan.gram[first])))
+        first = end
+    return out
+
+
+def test_planner_chunks_with_extra_bytes_and_a_cap_are_the_old_kernel_method_loops():
+    from vgan_amd.outlier import SubspacePlan, kpca_fit_chunks, ocsvm_chunks, sos_chunks
+    mask = np.zeros((5, 256), bool)
+    for s, width in enumerate((1, 3, 17, 33, 200)):
+        mask[s, :width] = True
+    plan = SubspacePlan(mask)
+    assert plan.gram.tolist() == [False, False, False, True, True]
+    many = SubspacePlan(np.ones((65536 + 1, 1), bool))
+    unlimited = 1 << 62
+    for rows in (3, 65, 257):
+        # bytes an entry of the rows x rows matrices next to a packed block: none (the two-argument form), OCSVM / SOS, KPCA
+        for square, entry in ((0, None), (4, ocsvm_chunks), (12, kpca_fit_chunks)):
+            def need(p):
+                return lambda z: rows * rows * square + rows * (int((p.dims[z] + 3) // 4 * 4) + 1) * 4
+            two = need(plan)(0) + need(plan)(1)  # exactly two subspaces' worth
+            for p, limit in ((plan, 1), (plan, two), (plan, 1 << 30), (many, unlimited)):
+                want = _greedy_chunks(p, need(p), limit, 65535 if square else None)
+                if entry is None:
+                    assert p.chunks(rows, limit) == p.chunks(rows, limit, extra_bytes=0, max_count=None) == want
+                else:
+                    assert entry(p, rows, limit) == p.chunks(rows, limit, extra_bytes=square * rows * rows, max_count=65535) == want
+                if square == 4:
+                    assert sos_chunks(p, rows, limit) == want
+            assert _greedy_chunks(plan, need(plan), two, None)[:2] == [(0, 2, False), (2, 1, False)]
+            assert _greedy_chunks(plan, need(plan), two - 1, None)[0] == (0, 1, False)
+    # the cap: 65535 subspaces a chunk for the kernel methods, none for the two-argument form
+    assert ocsvm_chunks(many, 3, unlimited) == kpca_fit_chunks(many, 3, unlimited) == [(0, 65535, False), (65535, 2, False)]
+    assert many.chunks(3, unlimited) == [(0, 65537, False)]
+
+
 def test_planner_rejects_bad_subspaces():
     from vgan_amd.outlier import SubspacePlan
     m = np.ones((3, 5), bool)

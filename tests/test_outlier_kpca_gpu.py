@@ -173,6 +173,34 @@ def test_kernel_rows_meet_float64_within_the_entry_bar(m, n):
     print(f"m={m} n={n}: worst kernel entry error {worst:.3f} of its bar")
 
 
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("m", [2, 65, 130])
+@pytest.mark.parametrize("width", [3, 40])  # one subspace per engine
+def test_the_square_and_the_rectangular_kernel_are_one_kernel(width, m, splits):
+    """vgan_ocsvm_kernel_matrix (by reference row, unit diagonal) and vgan_kpca_kernel_rows (by query row) of the same packed
+    block on both sides: a pair's d2 does not depend on who asks and both apply rbf_entry, so K[c][q] == R[q][c] bit for bit off
+    the diagonal, and K's diagonal is exactly 1."""
+    import torch
+    import vgan_amd
+    from vgan_amd.outlier import ENGINES
+    mask = np.zeros((1, D), bool)
+    mask[0, :width] = True
+    ens = vgan_amd.SubspaceKPCA(mask, [1.0], max_samples=m).fit(case_data(m, m)[0])
+    gram = width >= GRAM_MIN_DIMS
+    assert bool(ens.plan.gram[0]) == gram and ens._L.shape[0] == m
+    P, sq = ens._pack(ens._L, 0, 1, gram)
+    K = torch.full((1, m, m), float("nan"), dtype=torch.float32, device="cuda")
+    R = torch.full((1, m, m), float("nan"), dtype=torch.float32, device="cuda")
+    engine = ENGINES["gram" if gram else "exact"]
+    ens.ops.ocsvm_kernel_matrix(P, sq, m, ens._table, 0, 1, ens._gamma, engine, splits, K)
+    ens.ops.kpca_kernel_rows(P, sq, m, P, sq, m, ens._table, 0, 1, ens._gamma, engine, splits, R)
+    K, R = K[0].cpu().numpy(), R[0].cpu().numpy()
+    off = ~np.eye(m, dtype=bool)
+    assert not np.isnan(K).any() and not np.isnan(R).any()
+    assert np.array_equal(K[off], R.T[off])
+    assert (np.diag(K) == 1).all()
+
+
 # ---- 3. the decomposition ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("m,n", CASES)
 def test_eigenpairs_decompose_the_hosts_centred_matrix(m, n):

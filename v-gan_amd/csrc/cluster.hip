@@ -318,22 +318,17 @@ extern "C" int vgan_cluster_lloyd(const float* Pq, const float* sq_q, const floa
     VGAN_CHECK_ARG(n > 0 && d > 0 && ldx >= d && first >= 0 && count > 0 && count <= 65535 && iterations >= 1);
     VGAN_CHECK_ARG(n_clusters >= 2 && n_clusters <= kCMax && n >= n_clusters);
     VGAN_CHECK_ARG(max_dims >= 1 && max_dims <= d && total_dims >= count && total_dims >= max_dims);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && img_sq));
-    VGAN_CHECK_ARG(aligned16(Pq) && aligned16(img) && workspace && aligned16(workspace));
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq_q && img_sq, 1, Pq, img) && workspace && aligned16(workspace));
     VGAN_CHECK_ARG(workspace_bytes >= cluster_part_bytes(n, n_clusters, count, total_dims));
     const hipStream_t st = (hipStream_t)stream;
     const int C = n_clusters, nb = cluster_slices(n), nt = cluster_partial_threads(C);
     double* part = static_cast<double*>(workspace);
-    const dim3 agrid((n + kOTile - 1) / kOTile, 1, count);
     const dim3 pgrid(nb, (max_dims + 1 + nt - 1) / nt, count);
     for (int it = 0; it < iterations; ++it) {
-        if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-            hipLaunchKernelGGL(cluster_assign_kernel<true>, agrid, dim3(kBlock), 0, st, Pq, sq_q, n, img, img_sq, C, feat_off, col_off,
-                               first, done, label, changed);
-        else
-            hipLaunchKernelGGL(cluster_assign_kernel<false>, agrid, dim3(kBlock), 0, st, Pq, sq_q, n, img, img_sq, C, feat_off, col_off,
-                               first, done, label, changed);
+        dispatch_engine(engine, [&](auto gram) {
+            hipLaunchKernelGGL(cluster_assign_kernel<decltype(gram)::value>, dist_grid(n, 1, count), dim3(kBlock), 0, st, Pq, sq_q, n, img,
+                               img_sq, C, feat_off, col_off, first, done, label, changed);
+        });
         VGAN_CHECK_LAUNCH();
         hipLaunchKernelGGL(cluster_update_partial_kernel, pgrid, dim3(nt), 0, st, X, ldx, n, feat, feat_off, first, C, label, done,
                            changed, part);

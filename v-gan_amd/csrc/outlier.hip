@@ -156,8 +156,8 @@ __global__ void outlier_kde_init_kernel(unsigned* __restrict__ pivot, unsigned l
 //          the bit order is the value order; -0 is mapped to +0).  Min is exact: the same m_q for every J.
 //   !PIVOT sum_r exp2f(c_s (m_q - d2)): every term <= 1 and the nearest row gives exactly 1.  A lane sums its 16 columns of
 //          a tile in float32 in fixed order and adds the partial, rounded at 2^-40, to a uint64 fixed-point accumulator;
-//          the waves merge exactly through LDS and atomicAdd into acc.  Integer sums are associative: the same acc for
-//          every J.  Terms <= 1 and nr < 2^23 keep acc below 2^63.
+//          the merge and the atomicAdd into acc are outlier_dist.hpp's fixed_point_row_sums.  Integer sums are associative:
+//          the same acc for every J.  Terms <= 1 and nr < 2^23 keep acc below 2^63.
 // One atomic per (slice, row), from wave 0, whose 64 lanes hold 64 consecutive rows.
 template <bool GRAM, bool PIVOT>
 __global__ __launch_bounds__(kBlock, 2) void outlier_kde_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
@@ -165,12 +165,12 @@ __global__ __launch_bounds__(kBlock, 2) void outlier_kde_kernel(const float* __r
                                                                 const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
                                                                 int first, int exclude_self, int splits, const double* __restrict__ bandwidth,
                                                                 unsigned* __restrict__ pivot, unsigned long long* __restrict__ acc) {
-    static_assert(DistLds<GRAM>::kFloats >= 2 * kBlock, "merge scratch");
     __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
     const int z = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x * kOTile + lane;
     const long row = (long)z * nq + q;
     if constexpr (PIVOT) {
+        static_assert(DistLds<GRAM>::kFloats >= kBlock, "merge scratch");
         float m = INFINITY;
         outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
 #pragma unroll
@@ -189,21 +189,15 @@ __global__ __launch_bounds__(kBlock, 2) void outlier_kde_kernel(const float* __r
     } else {
         const float c_s = kde_coef(bandwidth[first + z]);
         const float m = q < nq ? __uint_as_float(pivot[row]) : 0.f;
-        unsigned long long a = 0;
-        outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
+        fixed_point_row_sums<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, acc, [&](const float (&d2)[16], int c0) {
             float t = 0.f;
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const int c = c0 + j;
                 if (c < nr && !(exclude_self && c == q)) t += exp2f(c_s * (m - d2[j]));
             }
-            a += (unsigned long long)rintf(t * 0x1p40f);
+            return (unsigned long long)rintf(t * 0x1p40f);
         });
-        __syncthreads();
-        unsigned long long* la = reinterpret_cast<unsigned long long*>(lds);
-        la[tid] = a;
-        __syncthreads();
-        if (wave == 0 && q < nq) atomicAdd(acc + row, la[lane] + la[kWave + lane] + la[2 * kWave + lane] + la[3 * kWave + lane]);
     }
 }
 
@@ -343,13 +337,10 @@ template <int K>
 static int launch_knn(const float* Pq, const float* sqq, int nq, const float* Pr, const float* sqr, int nr, const int32_t* feat_off,
                       const int64_t* col_off, int first, int count, int k, int exclude_self, int engine, int splits, float* part_d,
                       int32_t* part_i, int32_t* nbr, hipStream_t st) {
-    dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
-    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-        hipLaunchKernelGGL((outlier_knn_kernel<K, true>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off,
-                           first, k, exclude_self, splits, part_d, part_i, nbr);
-    else
-        hipLaunchKernelGGL((outlier_knn_kernel<K, false>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off,
-                           first, k, exclude_self, splits, part_d, part_i, nbr);
+    dispatch_engine(engine, [&](auto gram) {
+        hipLaunchKernelGGL((outlier_knn_kernel<K, decltype(gram)::value>), dist_grid(nq, splits, count), dim3(kBlock), 0, st, Pq, sqq, nq, Pr,
+                           sqr, nr, feat_off, col_off, first, k, exclude_self, splits, part_d, part_i, nbr);
+    });
     VGAN_CHECK_LAUNCH();
     if (splits > 1) {
         const long rows = (long)count * nq;
@@ -358,18 +349,6 @@ static int launch_knn(const float* Pq, const float* sqq, int nq, const float* Pr
         VGAN_CHECK_LAUNCH();
     }
     return VGAN_OK;
-}
-
-// the pivot and sum sweeps of a kde call
-template <bool GRAM>
-static void launch_kde(const float* Pq, const float* sqq, int nq, const float* Pr, const float* sqr, int nr, const int32_t* feat_off,
-                       const int64_t* col_off, int first, int count, int exclude_self, int splits, const double* bandwidth,
-                       unsigned* pivot, unsigned long long* acc, hipStream_t st) {
-    const dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
-    hipLaunchKernelGGL((outlier_kde_kernel<GRAM, true>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first,
-                       exclude_self, splits, bandwidth, pivot, acc);
-    hipLaunchKernelGGL((outlier_kde_kernel<GRAM, false>), grid, dim3(kBlock), 0, st, Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first,
-                       exclude_self, splits, bandwidth, pivot, acc);
 }
 
 }  // namespace vgan
@@ -393,10 +372,7 @@ extern "C" int vgan_outlier_knn(const float* Pq, const float* sq_q, int nq, cons
     VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && nbr && nq > 0 && nr > 0 && first >= 0 && count > 0 && count <= 65535);
     VGAN_CHECK_ARG(k >= 1 && k <= VGAN_OUTLIER_MAX_K);
     VGAN_CHECK_ARG(nr >= k + (exclude_self ? 1 : 0) && (!exclude_self || nq == nr));
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && (splits == 1 || (part_d && part_i)));
-    VGAN_CHECK_ARG(aligned16(Pq) && aligned16(Pr));
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq_q && sq_r, splits, Pq, Pr) && (splits == 1 || (part_d && part_i)));
     const hipStream_t st = (hipStream_t)stream;
     if (k <= 8) return launch_knn<8>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
     if (k <= 16) return launch_knn<16>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
@@ -410,19 +386,19 @@ extern "C" int vgan_outlier_kde(const float* Pq, const float* sq_q, int nq, cons
     VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && bandwidth && pivot && acc && score && nq > 0 && nr > 0 && first >= 0);
     VGAN_CHECK_ARG(count > 0 && count <= 65535 && ld_score >= nq && nr <= VGAN_OUTLIER_KDE_MAX_ROWS);
     VGAN_CHECK_ARG(!exclude_self || (nq == nr && nr >= 2));
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(Pq) && aligned16(Pr));
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq_q && sq_r, splits, Pq, Pr));
     const hipStream_t st = (hipStream_t)stream;
     const long rows = (long)count * nq;
     unsigned* piv = reinterpret_cast<unsigned*>(pivot);
     unsigned long long* sum = reinterpret_cast<unsigned long long*>(acc);
     hipLaunchKernelGGL(outlier_kde_init_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, piv, sum, rows);
     VGAN_CHECK_LAUNCH();
-    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-        launch_kde<true>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, exclude_self, splits, bandwidth, piv, sum, st);
-    else
-        launch_kde<false>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, exclude_self, splits, bandwidth, piv, sum, st);
+    dispatch_engine(engine, [&](auto gram) {  // the pivot sweep, then the sum sweep
+        hipLaunchKernelGGL((outlier_kde_kernel<decltype(gram)::value, true>), dist_grid(nq, splits, count), dim3(kBlock), 0, st, Pq, sq_q, nq,
+                           Pr, sq_r, nr, feat_off, col_off, first, exclude_self, splits, bandwidth, piv, sum);
+        hipLaunchKernelGGL((outlier_kde_kernel<decltype(gram)::value, false>), dist_grid(nq, splits, count), dim3(kBlock), 0, st, Pq, sq_q, nq,
+                           Pr, sq_r, nr, feat_off, col_off, first, exclude_self, splits, bandwidth, piv, sum);
+    });
     VGAN_CHECK_LAUNCH();
     hipLaunchKernelGGL(outlier_kde_score_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, piv, sum, nq, count, feat_off,
                        first, bandwidth, exclude_self ? nr - 1 : nr, score, score_row, ld_score);

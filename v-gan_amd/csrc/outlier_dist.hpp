@@ -1,7 +1,12 @@
 // The distance producer of the outlier kernels (outlier.hip: kNN, KDE; cluster.hip: k-means assignment): a workgroup owns
 // 64 query rows of one subspace and walks the reference rows 64 at a time; the n_q x n_r distance matrix never exists.
+// On top of it, the pairwise core of the kernel methods (KDE, OCSVM, SOS, KPCA): one kernel that stores an entry per pair
+// (pair_matrix_kernel), one fixed-point row-sum sweep (fixed_point_row_sums), and the host side all launchers of the producer
+// share (dist_args_ok, dist_grid, dispatch_engine).
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "gemm_core.hpp"
 
@@ -16,6 +21,20 @@ __device__ __forceinline__ bool cand_less(float d, int i, float e, int j) { retu
 // An RBF kernel entry from an engine's d2 (outlier_ocsvm.hip, outlier_kpca.hip): float32 exp(-gamma d2), the argument formed
 // in float64 and rounded once
 __device__ __forceinline__ float rbf_entry(double gamma, float d2) { return expf((float)(-gamma * (double)d2)); }
+
+// The RBF entry functors of pair_matrix_kernel: of(s) loads gamma_s once, and the result gives the entry of the pair (q, c);
+// UNIT_DIAGONAL stores the pairs c == q as exactly 1 (a matrix of a block against itself)
+template <bool UNIT_DIAGONAL>
+struct RbfEntry {
+    const double* __restrict__ gamma;
+    struct Of {
+        double g;
+        __device__ __forceinline__ float operator()(int q, int c, float d2) const {
+            return UNIT_DIAGONAL && c == q ? 1.f : rbf_entry(g, d2);
+        }
+    };
+    __device__ __forceinline__ Of of(int s) const { return {gamma[s]}; }
+};
 
 // LDS of the distance producer's engine: the Gram tile's operand images and a 64 x 65 d2 tile, or the exact engine's
 // two 64-row x 32-feature operand blocks
@@ -113,6 +132,83 @@ __device__ __forceinline__ void outlier_distances(const float* __restrict__ Pq, 
             consume(d2, r0 + 16 * wave);
         }
     }
+}
+
+// out[z] = entry(q, c, d2(q, c)) for every pair of chunk subspace z, float32 [nq, nr] (BY_QUERY: lane l of a wave holds query
+// row q0 + l and 16 neighbouring columns, a lane writes 64 consecutive bytes) or [nr, nq] (by reference row: the entry of the
+// pair (q, c) goes to row c, so that the 64 lanes of a store write 64 consecutive floats).  entry.of(s) is taken once per
+// workgroup, before the producer runs.
+template <bool GRAM, bool BY_QUERY, class Entry>
+__global__ __launch_bounds__(kBlock, 2) void pair_matrix_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
+                                                                const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
+                                                                const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
+                                                                int first, int splits, Entry entry, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
+    const int z = blockIdx.z, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * kOTile + lane;
+    const auto e = entry.of(first + z);
+    float* o = out + (long)z * nq * nr;
+    outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
+        if (q >= nq) return;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = c0 + j;
+            if (c < nr) o[BY_QUERY ? (long)q * nr + c : (long)c * nq + q] = e(q, c, d2[j]);
+        }
+    });
+}
+
+// acc[z nq + q] += the sum over the reference rows of this slice of tile(d2, c0), the unsigned 64-bit fixed-point contribution
+// of the lane's 16 columns of a tile (0 from a lane whose row q0 + l >= nq has none).  The four waves of a row merge through
+// LDS and wave 0, whose 64 lanes hold 64 consecutive rows, issues one atomicAdd per (slice, row): integer sums have no order,
+// so acc is the same for every split.  lds: DistLds<GRAM>::kFloats floats.
+template <bool GRAM, class Tile>
+__device__ __forceinline__ void fixed_point_row_sums(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
+                                                     const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
+                                                     const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
+                                                     int first, int splits, float* lds, unsigned long long* __restrict__ acc,
+                                                     Tile&& tile) {
+    static_assert(DistLds<GRAM>::kFloats >= 2 * kBlock, "merge scratch");
+    const int z = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x * kOTile + lane;
+    unsigned long long a = 0;
+    outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds,
+                            [&](const float (&d2)[16], int c0) { a += tile(d2, c0); });
+    __syncthreads();
+    unsigned long long* la = reinterpret_cast<unsigned long long*>(lds);
+    la[tid] = a;
+    __syncthreads();
+    if (wave == 0 && q < nq) atomicAdd(acc + (long)z * nq + q, la[lane] + la[kWave + lane] + la[2 * kWave + lane] + la[3 * kWave + lane]);
+}
+
+// ---- host side of every launch of the producer -------------------------------------------------------------------------------
+// the engine is one of the two, the Gram engine has its norms, 1 <= splits <= 65535 (grid.y) and the operand blocks can be
+// read 16 bytes at a time
+inline bool dist_args_ok(int engine, bool norms, int splits, const void* Pq, const void* Pr) {
+    return (engine == VGAN_OUTLIER_ENGINE_EXACT || (engine == VGAN_OUTLIER_ENGINE_GRAM && norms)) && splits >= 1 && splits <= 65535 &&
+           aligned16(Pq) && aligned16(Pr);
+}
+
+inline dim3 dist_grid(int nq, int splits, int count) { return dim3((nq + kOTile - 1) / kOTile, splits, count); }
+
+// launch(std::true_type) for the Gram engine, launch(std::false_type) for the exact one: launch(gram) names its kernel as
+// kernel<decltype(gram)::value, ...>
+template <class Launch>
+inline void dispatch_engine(int engine, Launch&& launch) {
+    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
+        launch(std::true_type{});
+    else
+        launch(std::false_type{});
+}
+
+template <bool BY_QUERY, class Entry>
+inline void launch_pair_matrix(int engine, const float* Pq, const float* sqq, int nq, const float* Pr, const float* sqr, int nr,
+                               const int32_t* feat_off, const int64_t* col_off, int first, int count, int splits, Entry entry,
+                               float* out, hipStream_t st) {
+    dispatch_engine(engine, [&](auto gram) {
+        hipLaunchKernelGGL((pair_matrix_kernel<decltype(gram)::value, BY_QUERY, Entry>), dist_grid(nq, splits, count), dim3(kBlock), 0, st,
+                           Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, entry, out);
+    });
 }
 
 }  // namespace vgan

@@ -47,15 +47,6 @@ __device__ __forceinline__ double hist_value(u64 k) {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
 }
 
-// a * b rounded to float64 before anything is added to it.  The library is built with -ffp-contract=fast, and HIP's
-// __dmul_rn / __dadd_rn are plain operators there, which the compiler fuses into one v_fma_f64: the empty asm makes the
-// product a value the optimiser cannot look through, so the sum that follows is a second rounding, as numpy's is.
-__device__ __forceinline__ double mul_rounded(double a, double b) {
-    double p = a * b;
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
 // the bin of x among the edges e[0 .. B]: #{j in 1 .. B - 1 : e[j] <= x}; eight steps, every probe inside 1 .. B - 1
 __device__ __forceinline__ int hist_bin(const double* e, int B, double x) {
     int pos = 0;

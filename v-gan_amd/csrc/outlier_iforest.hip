@@ -119,13 +119,9 @@ __global__ __launch_bounds__(kBlock) void iforest_build_kernel(const float* __re
             }
             lo = if_wave_min(lo);
             hi = wave_max(hi);
-            // three separately rounded float64 operations.  The library is built with -ffp-contract=fast, under which
-            // __dmul_rn and __dadd_rn are a plain product and sum that the back end fuses (read off the disassembly: one
-            // v_fmac_f64); the empty asm makes the rounded product a value of its own, so the sum cannot absorb it.
+            // three separately rounded float64 operations (mul_rounded: the sum must not absorb the product)
             const double u = ((double)ctr[1] + 0.5) * 0x1p-32;  // exact
-            double prod = __dmul_rn(u, __dsub_rn((double)hi, (double)lo));
-            asm volatile("" : "+v"(prod));
-            float p = (float)__dadd_rn((double)lo, prod);
+            float p = (float)__dadd_rn((double)lo, mul_rounded(u, __dsub_rn((double)hi, (double)lo)));
             if (p >= hi) p = lo;
             int nl = 0, nr = 0;
             for (int base = 0; base < m; base += 64) {

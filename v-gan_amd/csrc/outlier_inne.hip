@@ -4,7 +4,7 @@
 // n x n: the build touches psi^2 pairs per estimator, scoring T psi pairs per (row, subspace).
 //
 //   d2       the squared distance of two rows over the features of the subspace in ascending order, float64: per feature the
-//            difference, its square and the sum are three separately rounded operations (mul_rounded below keeps the product
+//            difference, its square and the sum are three separately rounded operations (mul_rounded_free keeps the product
 //            out of an fma), so that every comparison here is the one a plain numpy loop makes.
 //   build    one workgroup per estimator.  The psi row indices (feistel_perm of the estimator's stream, in that order: the
 //            position breaks ties) live in LDS.  A pass owns kBlock centres, one a thread, and walks the other centres in
@@ -34,16 +34,6 @@ constexpr int kInTile = 16;                           // centres of one register
 constexpr int kInFeat = 32;                           // features of one staged tile
 constexpr int kInPad = kInFeat + 1;                   // words of a staged float32 row: lanes over rows hit 64 banks
 
-// the product as a value of its own: the library is built with -ffp-contract=fast, and the empty asm keeps the sum that
-// follows from absorbing it (outlier_ocsvm.hip, outlier_hist.hip).  Not volatile here: the statement has to stay opaque,
-// not in place.  A volatile one orders the LDS reads around it, and the pair loop then waits out one read per centre
-// (measured on the MI355X: 1.3 times the time of the scoring pass at d = 784).
-__device__ __forceinline__ double inne_mul_rounded(double a, double b) {
-    double p = a * b;
-    asm("" : "+v"(p));
-    return p;
-}
-
 // acc[c] += (x - centre c)^2 over the fw features of the staged tile, ascending; the tile's row of a feature is read whole
 // before the first difference is taken
 __device__ __forceinline__ void inne_accumulate(const float* __restrict__ mine, const double (*__restrict__ tile)[kInTile], int fw,
@@ -56,7 +46,7 @@ __device__ __forceinline__ void inne_accumulate(const float* __restrict__ mine, 
 #pragma unroll
         for (int c = 0; c < kInTile; ++c) {
             const double diff = a - b[c];
-            acc[c] += inne_mul_rounded(diff, diff);
+            acc[c] += mul_rounded_free(diff, diff);
         }
     }
 }

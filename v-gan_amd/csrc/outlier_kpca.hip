@@ -9,9 +9,8 @@
 //                     reads the upper-triangle entry of its pair: both places get the same bits.  No products: every
 //                     operation is rounded on its own.
 //   3. eigen          vgan_pca_eigen (outlier_pca.hip) on Kc with standardize = 0.
-//   4. kernel rows    the distance producer (outlier_dist.hpp, both engines) of the query rows against the packed landmark
-//                     block; the consumer stores rbf_entry row-major by query row, float32 [rows, m], no diagonal rule.
-//                     Lane l of a wave holds query row q0 + l and 16 neighbouring columns: a lane writes 64 consecutive bytes.
+//   4. kernel rows    outlier_dist.hpp's pair_matrix_kernel (both engines) of the query rows against the packed landmark
+//                     block, stored by query row: rbf_entry, float32 [rows, m], no diagonal rule (RbfEntry<false>).
 //   5. row means      a wave per row: lane l adds the columns l, l + 64, ... in ascending order in float64, the 64 partials
 //                     combine by the xor butterfly 32, 16, 8, 4, 2, 1, and the sum is divided by m.
 //   6. scores         outlier_moments.hpp's weighted projection (the staging of pca_scores_kernel) with the operand z_c = ((k_c
@@ -57,28 +56,6 @@ __global__ void kpca_center_kernel(const float* __restrict__ K, int m, const dou
     const int i = min(r, c), j = max(r, c);
     const double* cm = col_mean + (long)z * m;
     Kc[(long)z * mm + e] = (((double)K[(long)z * mm + (long)i * m + j] - cm[j]) - cm[i]) + total[z];
-}
-
-// R[z][q][c] = rbf_entry(gamma_s, d2(q, c)): the rectangular sibling of ocsvm_kernel_matrix_kernel, stored by query row
-template <bool GRAM>
-__global__ __launch_bounds__(kBlock, 2) void kpca_kernel_rows_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
-                                                                     const float* __restrict__ Pr, const float* __restrict__ sqr, int m,
-                                                                     const int32_t* __restrict__ feat_off,
-                                                                     const int64_t* __restrict__ col_off, int first, int splits,
-                                                                     const double* __restrict__ gamma, float* __restrict__ R) {
-    __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
-    const int z = blockIdx.z, lane = threadIdx.x & 63;
-    const int q = blockIdx.x * kOTile + lane;
-    const double g = gamma[first + z];
-    float* Rq = R + ((long)z * nq + q) * m;
-    outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, m, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
-        if (q >= nq) return;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = c0 + j;
-            if (c < m) Rq[c] = rbf_entry(g, d2[j]);
-        }
-    });
 }
 
 // mean[row] of the rows of R [rows, m]: a wave per row
@@ -140,17 +117,9 @@ extern "C" int vgan_kpca_kernel_rows(const float* Pq, const float* sq_q, int nq,
                                      int engine, int splits, float* R, vgan_stream_t stream) {
     VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && gamma && R && first >= 0 && kpca_shape_ok(m, count));
     VGAN_CHECK_ARG(nq > 0 && nq <= VGAN_MAHA_MAX_ROWS);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(Pq) && aligned16(Pr));
-    const dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
-    const hipStream_t st = (hipStream_t)stream;
-    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-        hipLaunchKernelGGL(kpca_kernel_rows_kernel<true>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, m, feat_off, col_off, first,
-                           splits, gamma, R);
-    else
-        hipLaunchKernelGGL(kpca_kernel_rows_kernel<false>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, m, feat_off, col_off, first,
-                           splits, gamma, R);
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq_q && sq_r, splits, Pq, Pr));
+    launch_pair_matrix<true>(engine, Pq, sq_q, nq, Pr, sq_r, m, feat_off, col_off, first, count, splits, RbfEntry<false>{gamma}, R,
+                             (hipStream_t)stream);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }

@@ -2,14 +2,14 @@
 // OCSVM; v-gan_amd/outlier.py: SubspaceOCSVM, whose docstring is the contract).
 //
 // Per subspace s with K_s(x, y) = exp(-gamma_s d_s(x, y)^2):
-//   1. kernel matrix  the distance producer (outlier_dist.hpp, both engines) over the packed block against itself; the
-//                     consumer turns every d2 into float32 exp(-gamma_s d2) and stores it, the diagonal as exactly 1.
+//   1. kernel matrix  outlier_dist.hpp's pair_matrix_kernel (both engines) over the packed block against itself, stored by
+//                     reference row: every d2 becomes float32 exp(-gamma_s d2), the diagonal exactly 1 (RbfEntry<true>).
 //   2. init           libsvm's start of the dual and G = K a, row after row.
 //   3. smo            one workgroup per subspace runs WSS2 steps (Fan, Chen, Lin 2005), all float64, every operation
 //                     rounded on its own; at most `iterations` steps per launch, the host polls the done flags.
 //   4. rho            the mean of G over the free rows, or the midpoint / one bound where there is none.
-//   5. scores         the distance producer of the query rows against the fitted rows; the terms a_r K_s(x_r, q) are
-//                     summed in 64-bit fixed point (2^-44), so the sum has no order: score = rho - sum.
+//   5. scores         outlier_dist.hpp's fixed_point_row_sums of the query rows against the fitted rows; the terms a_r
+//                     K_s(x_r, q) are summed in 64-bit fixed point (2^-44), so the sum has no order: score = rho - sum.
 #include <float.h>
 #include <limits.h>
 
@@ -19,37 +19,6 @@ namespace vgan {
 
 constexpr int kSmoLdsRows = VGAN_OCSVM_LDS_ROWS;  // up to here a and G of a subspace live in LDS during a launch (32 KiB)
 constexpr int kSmoWide = 1024;  // threads of the solver's workgroup beyond that: four times fewer rows per thread and pass
-
-// a * b rounded to float64 before anything is added to it: the library is built with -ffp-contract=fast, under which a
-// product and the sum that takes it become one v_fma_f64; the empty asm makes the product a value of its own
-// (outlier_iforest.hip, outlier_hist.hip)
-__device__ __forceinline__ double mul_rounded(double a, double b) {
-    double p = a * b;
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
-// K[z][c][q] = exp(-gamma_s d2(q, c)), 1 on the diagonal.  Lane l of a wave holds row q0 + l of 16 columns: the entry of
-// the pair (q, c) goes to row c, so that the 64 lanes of a store write 64 consecutive floats.
-template <bool GRAM>
-__global__ __launch_bounds__(kBlock, 2) void ocsvm_kernel_matrix_kernel(const float* __restrict__ P, const float* __restrict__ sq, int n,
-                                                                        const int32_t* __restrict__ feat_off,
-                                                                        const int64_t* __restrict__ col_off, int first, int splits,
-                                                                        const double* __restrict__ gamma, float* __restrict__ K) {
-    __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
-    const int z = blockIdx.z, lane = threadIdx.x & 63;
-    const int q = blockIdx.x * kOTile + lane;
-    const double g = gamma[first + z];
-    float* Kz = K + (long)z * n * n;
-    outlier_distances<GRAM>(P, sq, n, P, sq, n, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
-        if (q >= n) return;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = c0 + j;
-            if (c < n) Kz[(long)c * n + q] = c == q ? 1.f : rbf_entry(g, d2[j]);
-        }
-    });
-}
 
 // libsvm's start: a_t = 1 for t < m, a_m (when m < n), 0 beyond; G_t = sum over the nonzero rows r ascending of K[r, t] a_r.
 // One thread per (subspace, t).
@@ -324,35 +293,29 @@ __global__ __launch_bounds__(kBlock) void ocsvm_rho_kernel(const double* __restr
 }
 
 // acc[z nq + q] += sum over the reference rows r of this slice with a_r != 0 of rint(a_r K_s(x_r, q) 2^44): every term lies
-// in [0, 2^44] and nr <= 2^15, so the integer sum stays below 2^63 and has no order.  The merge is the KDE sweep's.
+// in [0, 2^44] and nr <= 2^15, so the integer sum stays below 2^63 and has no order
 template <bool GRAM>
 __global__ __launch_bounds__(kBlock, 2) void ocsvm_sum_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
                                                               const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
                                                               const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off,
                                                               int first, int splits, const double* __restrict__ gamma,
                                                               const double* __restrict__ alpha, unsigned long long* __restrict__ acc) {
-    static_assert(DistLds<GRAM>::kFloats >= 2 * kBlock, "merge scratch");
     __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
-    const int z = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = blockIdx.x * kOTile + lane;
-    const double g = gamma[first + z];
-    const double* az = alpha + (long)(first + z) * nr;
-    unsigned long long a = 0;
-    outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
-        if (q >= nq) return;
+    const int q = blockIdx.x * kOTile + (threadIdx.x & 63);
+    const double g = gamma[first + blockIdx.z];
+    const double* az = alpha + (long)(first + blockIdx.z) * nr;
+    fixed_point_row_sums<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, acc, [&](const float (&d2)[16], int c0) {
+        unsigned long long t = 0;
+        if (q >= nq) return t;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int c = c0 + j;
             if (c >= nr) continue;
             const double w = az[c];
-            if (w != 0.0) a += (unsigned long long)(long long)rint(mul_rounded(w, (double)rbf_entry(g, d2[j])) * 0x1p44);
+            if (w != 0.0) t += (unsigned long long)(long long)rint(mul_rounded(w, (double)rbf_entry(g, d2[j])) * 0x1p44);
         }
+        return t;
     });
-    __syncthreads();
-    unsigned long long* la = reinterpret_cast<unsigned long long*>(lds);
-    la[tid] = a;
-    __syncthreads();
-    if (wave == 0 && q < nq) atomicAdd(acc + (long)z * nq + q, la[lane] + la[kWave + lane] + la[2 * kWave + lane] + la[3 * kWave + lane]);
 }
 
 // score[score_row[z], q] = float32((rint(rho 2^44) - acc) 2^-44): rho enters on the grid of the sum, so that equal terms cancel
@@ -376,16 +339,9 @@ extern "C" int vgan_ocsvm_kernel_matrix(const float* P, const float* sq, int n, 
                                         vgan_stream_t stream) {
     VGAN_CHECK_ARG(P && feat_off && col_off && gamma && K && first >= 0 && count > 0 && count <= 65535);
     VGAN_CHECK_ARG(n >= 2 && n <= VGAN_OCSVM_MAX_ROWS);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || sq);
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(P));
-    const dim3 grid((n + kOTile - 1) / kOTile, splits, count);
-    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-        hipLaunchKernelGGL(ocsvm_kernel_matrix_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, P, sq, n, feat_off, col_off, first,
-                           splits, gamma, K);
-    else
-        hipLaunchKernelGGL(ocsvm_kernel_matrix_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, P, sq, n, feat_off, col_off,
-                           first, splits, gamma, K);
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq != nullptr, splits, P, P));
+    launch_pair_matrix<false>(engine, P, sq, n, P, sq, n, feat_off, col_off, first, count, splits, RbfEntry<true>{gamma}, K,
+                              (hipStream_t)stream);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }
@@ -436,9 +392,7 @@ extern "C" int vgan_ocsvm_scores(const float* Pq, const float* sq_q, int nq, con
                                  const int32_t* score_row, int64_t ld_score, vgan_stream_t stream) {
     VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && gamma && alpha && rho && acc && score && nq > 0 && first >= 0);
     VGAN_CHECK_ARG(count > 0 && count <= 65535 && ld_score >= nq && nr >= 2 && nr <= VGAN_OCSVM_MAX_ROWS);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(Pq) && aligned16(Pr));
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq_q && sq_r, splits, Pq, Pr));
     const hipStream_t st = (hipStream_t)stream;
     const long rows = (long)count * nq;
     unsigned long long* sum = reinterpret_cast<unsigned long long*>(acc);
@@ -446,13 +400,10 @@ extern "C" int vgan_ocsvm_scores(const float* Pq, const float* sq_q, int nq, con
         set_error("%s:%d: hipMemsetAsync failed", __FILE__, __LINE__);
         return VGAN_ERR_HIP;
     }
-    const dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
-    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-        hipLaunchKernelGGL(ocsvm_sum_kernel<true>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, splits,
-                           gamma, alpha, sum);
-    else
-        hipLaunchKernelGGL(ocsvm_sum_kernel<false>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, splits,
-                           gamma, alpha, sum);
+    dispatch_engine(engine, [&](auto gram) {
+        hipLaunchKernelGGL(ocsvm_sum_kernel<decltype(gram)::value>, dist_grid(nq, splits, count), dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r,
+                           nr, feat_off, col_off, first, splits, gamma, alpha, sum);
+    });
     VGAN_CHECK_LAUNCH();
     hipLaunchKernelGGL(ocsvm_score_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, sum, nq, count, first, rho, score,
                        score_row, (long)ld_score);

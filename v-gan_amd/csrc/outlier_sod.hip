@@ -38,13 +38,6 @@ constexpr int kSodWave = 64;                 // threads of a reference-set workg
 constexpr int kSodLevels = VGAN_OUTLIER_MAX_K + 1;
 constexpr int kSodScoreWaves = kBlock / kWave;
 
-// the product as a value of its own: the library is built with -ffp-contract=fast (outlier_inne.hip)
-__device__ __forceinline__ double sod_mul_rounded(double a, double b) {
-    double p = a * b;
-    asm("" : "+v"(p));
-    return p;
-}
-
 // cnt[z, m] += 1 for every entry m of the lists idx [count, n, k]
 __global__ __launch_bounds__(kBlock) void sod_count_kernel(const int32_t* __restrict__ idx, long total, int n, int k,
                                                           int32_t* __restrict__ cnt) {
@@ -256,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void sod_score_kernel(const float* __restri
         for (int r = 0; r < ref_set; ++r) {
             const int row = ref[r];
             const double dlt = (row >= 0 ? (double)Xr[(long)row * ldr + f] : 0.0) - mu;
-            s2 += sod_mul_rounded(dlt, dlt);
+            s2 += mul_rounded_free(dlt, dlt);
         }
         v = s2 / rs;
     };
@@ -271,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void sod_score_kernel(const float* __restri
         if (i < ds) pv += v;
     }
     const double V = sod_lane_order_sum(pv);
-    const double thr = sod_mul_rounded(alpha, V) / (double)ds;
+    const double thr = mul_rounded_free(alpha, V) / (double)ds;
 
     double pq = 0.0;
     int r = 0;
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void sod_score_kernel(const float* __restri
         double mu, v;
         moments(f, mu, v);
         const double dq = (double)xq[f] - mu;
-        const double sq = sod_mul_rounded(dq, dq);
+        const double sq = mul_rounded_free(dq, dq);
         const bool rel = i < ds && v < thr;
         if (rel) pq += sq;
         const unsigned long long bal = __ballot(rel);

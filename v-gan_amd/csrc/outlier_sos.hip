@@ -2,15 +2,15 @@
 // search of t-SNE; v-gan_amd/outlier.py: SubspaceSOS, whose docstring is the contract).
 //
 // Per subspace s:
-//   1. matrix  the distance producer (outlier_dist.hpp, both engines) over the packed block against itself; the consumer stores
-//              sqrtf(d2) or d2 itself.  Row i of D holds the dissimilarities of fitted row i (as the reference side) to all rows.
+//   1. matrix  outlier_dist.hpp's pair_matrix_kernel (both engines) over the packed block against itself, stored by reference
+//              row: sqrtf(d2) or d2 itself.  Row i of D holds the dissimilarities of fitted row i (as the reference side) to all rows.
 //   2. fit     per fitted row the root search for beta_i: the row's entries are read once and stay in LDS for all steps; a step
 //              is a float64 exp per entry and two sums over the row.  A short row belongs to one wave (four rows per
 //              workgroup, the sums are butterflies, no barrier), a long one to a workgroup of 1024 threads (a wave butterfly, one
 //              LDS slot per wave, one barrier per step).  The sums are the same bits in every lane, so the stop is uniform.
 //   3. scores  a row's terms min(-log1p(-b), 128) or min(log1p(a / Z), 128) are summed as rint(term 2^40) in 64-bit fixed point,
-//              so the sum has no order: at fit from the stored matrix (a wave per scored row), for new rows through the distance
-//              producer with the fitted rows as reference side (the merge of the OCSVM and KDE sweeps), then exp(-sum).
+//              so the sum has no order: at fit from the stored matrix (a wave per scored row), for new rows through
+//              outlier_dist.hpp's fixed_point_row_sums with the fitted rows as reference side, then exp(-sum).
 #include <float.h>
 #include <limits.h>
 
@@ -20,35 +20,14 @@ namespace vgan {
 
 constexpr int kSosWide = 1024;  // threads of the workgroup that owns a long row
 
-// a * b rounded to float64 before anything is added to it (outlier_ocsvm.hip: the library is built with -ffp-contract=fast)
-__device__ __forceinline__ double sos_mul_rounded(double a, double b) {
-    double p = a * b;
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
 __device__ __forceinline__ float sos_entry(int metric, float d2) { return metric == VGAN_SOS_METRIC_EUCLIDEAN ? sqrtf(d2) : d2; }
 
-// D[z][c][q] = the dissimilarity of query row q to reference row c: lane l of a wave holds row q0 + l of 16 columns, and the
-// entry of the pair (q, c) goes to row c, so that the 64 lanes of a store write 64 consecutive floats (the OCSVM matrix's layout)
-template <bool GRAM>
-__global__ __launch_bounds__(kBlock, 2) void sos_distance_matrix_kernel(const float* __restrict__ P, const float* __restrict__ sq, int n,
-                                                                        const int32_t* __restrict__ feat_off,
-                                                                        const int64_t* __restrict__ col_off, int first, int splits,
-                                                                        int metric, float* __restrict__ D) {
-    __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
-    const int z = blockIdx.z, lane = threadIdx.x & 63;
-    const int q = blockIdx.x * kOTile + lane;
-    float* Dz = D + (long)z * n * n;
-    outlier_distances<GRAM>(P, sq, n, P, sq, n, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
-        if (q >= n) return;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = c0 + j;
-            if (c < n) Dz[(long)c * n + q] = sos_entry(metric, d2[j]);
-        }
-    });
-}
+// pair_matrix_kernel's entry: the dissimilarity of query row q to reference row c, the same rule in every subspace
+struct SosEntry {
+    int metric;
+    __device__ __forceinline__ SosEntry of(int) const { return *this; }
+    __device__ __forceinline__ float operator()(int, int, float d2) const { return sos_entry(metric, d2); }
+};
 
 // The sums and the minimum of a row's owner, the same bits in every thread of it.  NT = 64: the owner is a wave, the xor
 // butterfly leaves every lane with the same value (each level adds the same two numbers in either lane).  NT = 1024: lane 0 of
@@ -141,26 +120,26 @@ __global__ __launch_bounds__(NT == kWave ? kBlock : NT) void sos_fit_kernel(cons
     int it = 0, flag = 0;
     for (;;) {
         double zs = 0.0, es = 0.0;
-        // two entries a turn, unrolled by hand (the empty asm of sos_mul_rounded keeps the compiler from doing it), added in
+        // two entries a turn, unrolled by hand (the empty asm of mul_rounded keeps the compiler from doing it), added in
         // ascending j all the same
         for (int j = t; j < m; j += 2 * NT) {
             const double e0 = (double)d[j] - dm;
             if (j + NT < m) {
                 const double e1 = (double)d[j + NT] - dm;
-                const double a0 = exp(-sos_mul_rounded(b, e0)), a1 = exp(-sos_mul_rounded(b, e1));
+                const double a0 = exp(-mul_rounded(b, e0)), a1 = exp(-mul_rounded(b, e1));
                 zs += a0;
-                es += sos_mul_rounded(e0, a0);
+                es += mul_rounded(e0, a0);
                 zs += a1;
-                es += sos_mul_rounded(e1, a1);
+                es += mul_rounded(e1, a1);
             } else {
-                const double a0 = exp(-sos_mul_rounded(b, e0));
+                const double a0 = exp(-mul_rounded(b, e0));
                 zs += a0;
-                es += sos_mul_rounded(e0, a0);
+                es += mul_rounded(e0, a0);
             }
         }
         sos_sum2<NT>(zs, es, slots + (it & 1) * 2 * NW);
         Zs = zs;
-        const double diff = (log(zs) + sos_mul_rounded(b, es / zs)) - log_perplexity;
+        const double diff = (log(zs) + mul_rounded(b, es / zs)) - log_perplexity;
         if (fabs(diff) <= tol) break;
         if (it >= max_iter) {
             flag = VGAN_SOS_FLAG_UNCONVERGED;
@@ -192,7 +171,7 @@ __device__ __forceinline__ unsigned long long sos_term(double d, double beta, do
     if (beta == INFINITY)
         a = d <= dmin ? 1.0 : 0.0;
     else
-        a = exp(-sos_mul_rounded(beta, d - dmin));
+        a = exp(-mul_rounded(beta, d - dmin));
     const double r = a / Z;
     const double t = FIT ? -log1p(-fmin(r, 1.0)) : log1p(r);
     return (unsigned long long)(long long)rint(fmin(t, 128.0) * 0x1p40);
@@ -221,8 +200,8 @@ __global__ __launch_bounds__(kBlock) void sos_fit_scores_kernel(const float* __r
     if (lane == 0) score[(long)(score_row ? score_row[z] : z) * ld_score + j] = sos_score(a);
 }
 
-// acc[z nq + q] += the terms of new row q over the reference rows of this slice; the merge is the OCSVM and KDE sweeps'.  Every
-// term is at most 2^47 and nr <= 2^15, so the integer sum stays below 2^63.
+// acc[z nq + q] += the terms of new row q over the reference rows of this slice.  Every term is at most 2^47 and nr <= 2^15, so
+// the integer sum stays below 2^63.
 template <bool GRAM>
 __global__ __launch_bounds__(kBlock, 2) void sos_sum_kernel(const float* __restrict__ Pq, const float* __restrict__ sqq, int nq,
                                                             const float* __restrict__ Pr, const float* __restrict__ sqr, int nr,
@@ -230,27 +209,21 @@ __global__ __launch_bounds__(kBlock, 2) void sos_sum_kernel(const float* __restr
                                                             int first, int splits, int metric, const double* __restrict__ beta,
                                                             const double* __restrict__ dmin, const double* __restrict__ Z,
                                                             unsigned long long* __restrict__ acc) {
-    static_assert(DistLds<GRAM>::kFloats >= 2 * kBlock, "merge scratch");
     __shared__ __attribute__((aligned(16))) float lds[DistLds<GRAM>::kFloats];
-    const int z = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = blockIdx.x * kOTile + lane;
-    const double* bz = beta + (long)(first + z) * nr;
-    const double* mz = dmin + (long)(first + z) * nr;
-    const double* zz = Z + (long)(first + z) * nr;
-    unsigned long long a = 0;
-    outlier_distances<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, [&](const float (&d2)[16], int c0) {
-        if (q >= nq) return;
+    const int q = blockIdx.x * kOTile + (threadIdx.x & 63);
+    const double* bz = beta + (long)(first + blockIdx.z) * nr;
+    const double* mz = dmin + (long)(first + blockIdx.z) * nr;
+    const double* zz = Z + (long)(first + blockIdx.z) * nr;
+    fixed_point_row_sums<GRAM>(Pq, sqq, nq, Pr, sqr, nr, feat_off, col_off, first, splits, lds, acc, [&](const float (&d2)[16], int c0) {
+        unsigned long long t = 0;
+        if (q >= nq) return t;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int c = c0 + j;
-            if (c < nr) a += sos_term<false>((double)sos_entry(metric, d2[j]), bz[c], mz[c], zz[c]);
+            if (c < nr) t += sos_term<false>((double)sos_entry(metric, d2[j]), bz[c], mz[c], zz[c]);
         }
+        return t;
     });
-    __syncthreads();
-    unsigned long long* la = reinterpret_cast<unsigned long long*>(lds);
-    la[tid] = a;
-    __syncthreads();
-    if (wave == 0 && q < nq) atomicAdd(acc + (long)z * nq + q, la[lane] + la[kWave + lane] + la[2 * kWave + lane] + la[3 * kWave + lane]);
 }
 
 // score[score_row[z], q] = float32(exp(-(acc 2^-40))); one thread per row
@@ -271,16 +244,8 @@ extern "C" int vgan_sos_distance_matrix(const float* P, const float* sq, int n, 
     VGAN_CHECK_ARG(P && feat_off && col_off && D && first >= 0 && count > 0 && count <= 65535);
     VGAN_CHECK_ARG(n >= VGAN_SOS_MIN_ROWS && n <= VGAN_SOS_MAX_ROWS);
     VGAN_CHECK_ARG(metric == VGAN_SOS_METRIC_EUCLIDEAN || metric == VGAN_SOS_METRIC_SQEUCLIDEAN);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || sq);
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(P));
-    const dim3 grid((n + kOTile - 1) / kOTile, splits, count);
-    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-        hipLaunchKernelGGL(sos_distance_matrix_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, P, sq, n, feat_off, col_off, first,
-                           splits, metric, D);
-    else
-        hipLaunchKernelGGL(sos_distance_matrix_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, P, sq, n, feat_off, col_off,
-                           first, splits, metric, D);
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq != nullptr, splits, P, P));
+    launch_pair_matrix<false>(engine, P, sq, n, P, sq, n, feat_off, col_off, first, count, splits, SosEntry{metric}, D, (hipStream_t)stream);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }
@@ -323,9 +288,7 @@ extern "C" int vgan_sos_scores(const float* Pq, const float* sq_q, int nq, const
     VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && beta && dmin && Z && acc && score && nq > 0 && first >= 0);
     VGAN_CHECK_ARG(count > 0 && count <= 65535 && ld_score >= nq && nr >= VGAN_SOS_MIN_ROWS && nr <= VGAN_SOS_MAX_ROWS);
     VGAN_CHECK_ARG(metric == VGAN_SOS_METRIC_EUCLIDEAN || metric == VGAN_SOS_METRIC_SQEUCLIDEAN);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || engine == VGAN_OUTLIER_ENGINE_GRAM);
-    VGAN_CHECK_ARG(engine == VGAN_OUTLIER_ENGINE_EXACT || (sq_q && sq_r));
-    VGAN_CHECK_ARG(splits >= 1 && splits <= 65535 && aligned16(Pq) && aligned16(Pr));
+    VGAN_CHECK_ARG(dist_args_ok(engine, sq_q && sq_r, splits, Pq, Pr));
     const hipStream_t st = (hipStream_t)stream;
     const long rows = (long)count * nq;
     unsigned long long* sum = reinterpret_cast<unsigned long long*>(acc);
@@ -333,13 +296,10 @@ extern "C" int vgan_sos_scores(const float* Pq, const float* sq_q, int nq, const
         set_error("%s:%d: hipMemsetAsync failed", __FILE__, __LINE__);
         return VGAN_ERR_HIP;
     }
-    const dim3 grid((nq + kOTile - 1) / kOTile, splits, count);
-    if (engine == VGAN_OUTLIER_ENGINE_GRAM)
-        hipLaunchKernelGGL(sos_sum_kernel<true>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, splits,
-                           metric, beta, dmin, Z, sum);
-    else
-        hipLaunchKernelGGL(sos_sum_kernel<false>, grid, dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, splits,
-                           metric, beta, dmin, Z, sum);
+    dispatch_engine(engine, [&](auto gram) {
+        hipLaunchKernelGGL(sos_sum_kernel<decltype(gram)::value>, dist_grid(nq, splits, count), dim3(kBlock), 0, st, Pq, sq_q, nq, Pr, sq_r,
+                           nr, feat_off, col_off, first, splits, metric, beta, dmin, Z, sum);
+    });
     VGAN_CHECK_LAUNCH();
     hipLaunchKernelGGL(sos_score_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, sum, nq, count, score, score_row,
                        (long)ld_score);

@@ -76,6 +76,24 @@ __device__ __forceinline__ double block_sum_all(double v, double* red) {
     return r;
 }
 
+// a * b rounded to float64 before anything is added to it.  The library is built with -ffp-contract=fast, under which a product
+// and the sum that takes it become one v_fma_f64, HIP's __dmul_rn / __dadd_rn included (they are plain operators there): the
+// empty asm makes the product a value the optimiser cannot look through, so the sum that follows is a second rounding, as
+// numpy's and libsvm's is.  It also keeps the compiler from unrolling a loop around it: callers that want that unroll by hand.
+__device__ __forceinline__ double mul_rounded(double a, double b) {
+    double p = a * b;
+    asm volatile("" : "+v"(p));
+    return p;
+}
+// The same without volatile, for a product between LDS reads (outlier_inne.hip, outlier_sod.hip): the statement has to stay
+// opaque, not in place.  A volatile one orders the LDS reads around it, and iNNE's pair loop then waits out one read per
+// centre (measured on the MI355X: 1.3 times the time of the scoring pass at d = 784).
+__device__ __forceinline__ double mul_rounded_free(double a, double b) {
+    double p = a * b;
+    asm("" : "+v"(p));
+    return p;
+}
+
 // Column-max key: U > 0 always, so its IEEE bits order like the value; ties go to the LOWEST row.
 __device__ __forceinline__ unsigned long long colkey_pack(float u, unsigned row) {
     return ((unsigned long long)__float_as_uint(u) << 32) | (unsigned long long)(0xFFFFFFFFu - row);

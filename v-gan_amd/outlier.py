@@ -280,15 +280,16 @@ class SubspacePlan:
     def count(self):
         return len(self.order)
 
-    def chunks(self, rows, limit_bytes):
+    def chunks(self, rows, limit_bytes, extra_bytes=0, max_count=None):
         """[(first, count, gram)]: consecutive runs of the processing order, one engine each, whose packed blocks of `rows`
-        rows (values and norms, float32) fit in limit_bytes; a subspace that alone exceeds it forms a chunk of its own."""
+        rows (values and norms, float32) plus extra_bytes a subspace fit in limit_bytes; a subspace that alone exceeds it
+        forms a chunk of its own.  max_count: the most subspaces of a chunk (None: no limit)."""
         out, first = [], 0
         widths = _round4(self.dims)
         while first < self.count:
             end, used = first, 0
-            while end < self.count and self.gram[end] == self.gram[first]:
-                need = int(rows) * (int(widths[end]) + 1) * 4
+            while end < self.count and self.gram[end] == self.gram[first] and (max_count is None or end - first < max_count):
+                need = int(extra_bytes) + int(rows) * (int(widths[end]) + 1) * 4
                 if end > first and used + need > limit_bytes:
                     break
                 used += need
@@ -383,6 +384,40 @@ class _SubspaceScorer:
         self.ops.outlier_pack(X, self._center if centred else None, self._table, first, count, packed, sq)
         return packed, sq
 
+    def _configure_splits(self, splits):
+        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
+            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
+        self.splits = splits
+
+    def _splits(self, nq, nr, count, cap=64):
+        """The reference-row split J of a sweep of nq query rows over nr reference rows in count subspaces: the given
+        splits, or enough slices to fill the chip, at most one a 64-row tile and at most cap (None: no cap)."""
+        if self.splits is not None:
+            return int(self.splits)
+        blocks = -(-nq // 64) * count
+        J = min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks))
+        return int(max(1, J if cap is None else min(J, cap)))
+
+    def _sweep(self, Xq, Xr, scores):
+        """float32 [S, nq], rows in the given subspace order: per chunk of the plan the packed blocks of the query rows Xq and
+        of the reference rows Xr (one pair of blocks for both when Xq is Xr), a 64-bit accumulator a (subspace, query row),
+        and scores((Pq, sqq, nq, Pr, sqr, nr), first, count, (engine, J, acc, per, score rows)), which launches the sweep."""
+        nr, nq = Xr.shape[0], Xq.shape[0]
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xr.device)
+        for first, count, gram in self.plan.chunks(nr if Xq is Xr else nr + nq, self.workspace_bytes):
+            Pr, sqr = self._pack(Xr, first, count, gram)
+            Pq, sqq = (Pr, sqr) if Xq is Xr else self._pack(Xq, first, count, gram)
+            acc = torch.empty(count * nq, dtype=torch.int64, device=Xr.device)
+            scores((Pq, sqq, nq, Pr, sqr, nr), first, count, (ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count),
+                                                               acc, per, self._rows[first:first + count]))
+            del Pq, Pr, sqq, sqr, acc
+        return per
+
+    def _keep(self, kept, M, first):
+        """Files the host copies of the chunk's matrices M [count, ...] in the list kept, under the given subspace order."""
+        for z, host in enumerate(M.cpu().numpy()):
+            kept[int(self.plan.order[first + z])] = host
+
     def _combine(self, per, fitting):
         """float64 [n]: the ensemble score of the raw per-subspace scores per [S, n]; fit takes the statistics first."""
         S, n = per.shape
@@ -449,18 +484,10 @@ class _NeighborScorer(_SubspaceScorer):
 
     def _configure_neighbors(self, n_neighbors, splits, least=1):
         self.n_neighbors = check_neighbors(n_neighbors, least)
-        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
-            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
-        self.splits = splits
+        self._configure_splits(splits)
 
     def _check_fit_rows(self, n):
         check_reference_rows(n, self.n_neighbors, exclude_self=True)
-
-    def _splits(self, nq, nr, count):
-        if self.splits is not None:
-            return int(self.splits)
-        blocks = -(-nq // 64) * count
-        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
 
     def _blocks(self, Xq, first, count, gram):
         Pr, sqr = self._pack(self._X, first, count, gram)
@@ -2696,21 +2723,9 @@ def ocsvm_start(nu, n):
 
 
 def ocsvm_chunks(plan, n, limit_bytes):
-    """[(first, count, gram)]: consecutive runs of the processing order, one engine each, whose n x n float32 kernel matrices
-    plus packed blocks (values and norms) fit in limit_bytes; a subspace that alone exceeds it forms a chunk of its own."""
-    out, first = [], 0
-    widths = _round4(plan.dims)
-    while first < plan.count:
-        end, used = first, 0
-        while end < plan.count and plan.gram[end] == plan.gram[first] and end - first < 65535:
-            need = int(n) * int(n) * 4 + int(n) * (int(widths[end]) + 1) * 4
-            if end > first and used + need > limit_bytes:
-                break
-            used += need
-            end += 1
-        out.append((first, end - first, bool(plan.gram[first])))
-        first = end
-    return out
+    """[(first, count, gram)]: SubspacePlan.chunks with the n x n float32 kernel matrix of every subspace next to its packed
+    block, at most 65535 subspaces (a launch's grid) a chunk."""
+    return plan.chunks(n, limit_bytes, extra_bytes=4 * int(n) * int(n), max_count=65535)
 
 
 def _resolve_rbf_gamma(plan, gamma, X):
@@ -2792,21 +2807,13 @@ class SubspaceOCSVM(_SubspaceScorer):
                  workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
         self.nu, self.gamma, self.tol, self.max_iter = check_ocsvm_params(nu, gamma, tol, max_iter)
         self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
-        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
-            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
-        self.splits = splits
+        self._configure_splits(splits)
         self.smo_stride, self.poll_stride, self.storage = OCSVM_SMO_STRIDE, POLL_STRIDE, "auto"
         self.keep_kernel_matrix = False
 
     # ---- pipeline --------------------------------------------------------------------------------
     def _check_fit_rows(self, n):
         check_ocsvm_rows(n)
-
-    def _splits(self, nq, nr, count):
-        if self.splits is not None:
-            return int(self.splits)
-        blocks = -(-nq // 64) * count
-        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
 
     def _resolve_gamma(self, X):
         """float64 [S] in processing order."""
@@ -2843,17 +2850,8 @@ class SubspaceOCSVM(_SubspaceScorer):
         self.ops.ocsvm_rho(a, g, self._rho[first:first + count])
 
     def _score(self, Xq, fitting):
-        Xr = self._X
-        nr, nq = Xr.shape[0], Xq.shape[0]
-        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xr.device)
-        for first, count, gram in self.plan.chunks(nr if Xq is Xr else nr + nq, self.workspace_bytes):
-            Pr, sqr = self._pack(Xr, first, count, gram)
-            Pq, sqq = (Pr, sqr) if Xq is Xr else self._pack(Xq, first, count, gram)
-            acc = torch.empty(count * nq, dtype=torch.int64, device=Xr.device)
-            self.ops.ocsvm_scores(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, self._gamma, self._alpha, self._rho,
-                                  ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count), acc, per,
-                                  self._rows[first:first + count])
-            del Pq, Pr, sqq, sqr, acc
+        per = self._sweep(Xq, self._X, lambda blocks, first, count, tail: self.ops.ocsvm_scores(
+            *blocks, self._table, first, count, self._gamma, self._alpha, self._rho, *tail))
         return self._combine(per, fitting), per
 
     # ---- public surface --------------------------------------------------------------------------
@@ -2877,9 +2875,7 @@ class SubspaceOCSVM(_SubspaceScorer):
             K = self._kernel_matrix(X, first, count, gram)
             self._smo(K, first, count, max_iter, flags)
             if self.keep_kernel_matrix:
-                host = K.cpu().numpy()
-                for z in range(count):
-                    kept[int(self.plan.order[first + z])] = host[z]
+                self._keep(kept, K, first)
             del K
         del self._G
         scores, per = self._score(X, fitting=True)
@@ -2963,22 +2959,9 @@ def kpca_weights(evals, n_components, eig_tol):
 
 
 def kpca_fit_chunks(plan, m, limit_bytes):
-    """[(first, count, gram)]: consecutive runs of the processing order, one engine each, whose m x m kernel matrices (float32),
-    centred matrices (float64) and packed landmark blocks fit in limit_bytes; a subspace that alone exceeds it forms a chunk
-    of its own."""
-    out, first = [], 0
-    widths = _round4(plan.dims)
-    while first < plan.count:
-        end, used = first, 0
-        while end < plan.count and plan.gram[end] == plan.gram[first] and end - first < 65535:
-            need = int(m) * int(m) * 12 + int(m) * (int(widths[end]) + 1) * 4
-            if end > first and used + need > limit_bytes:
-                break
-            used += need
-            end += 1
-        out.append((first, end - first, bool(plan.gram[first])))
-        first = end
-    return out
+    """[(first, count, gram)]: SubspacePlan.chunks with the m x m kernel matrix (float32) and centred matrix (float64) of every
+    subspace next to its packed landmark block, at most 65535 subspaces (a launch's grid) a chunk."""
+    return plan.chunks(m, limit_bytes, extra_bytes=12 * int(m) * int(m), max_count=65535)
 
 
 def kpca_chunks(plan, m, rows, limit_bytes):
@@ -3071,21 +3054,13 @@ class SubspaceKPCA(_SubspaceScorer):
         (self.n_components, self.gamma, self.max_samples, self.landmarks, self.eig_tol, self.max_sweeps,
          self.seed) = check_kpca_params(n_components, gamma, max_samples, landmarks, eig_tol, max_sweeps, seed)
         self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
-        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
-            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
-        self.splits = splits
+        self._configure_splits(splits)
         self.keep_kernel_matrix = False
 
     # ---- pipeline --------------------------------------------------------------------------------
     def _check_fit_rows(self, n):
         if not 2 <= n <= KPCA_MAX_ROWS:
             raise ValueError(f"SubspaceKPCA fit needs between 2 and {KPCA_MAX_ROWS} rows, got {n}")
-
-    def _splits(self, nq, count):
-        if self.splits is not None:
-            return int(self.splits)
-        blocks = -(-nq // 64) * count
-        return int(max(1, min(-(-self._m // 64), -(-_TARGET_BLOCKS // blocks))))
 
     def _decompose(self, kept):
         """The kernel matrix, its centring and its eigenpairs for every subspace, chunk by chunk."""
@@ -3099,16 +3074,14 @@ class SubspaceKPCA(_SubspaceScorer):
             P, sq = self._pack(self._L, first, count, gram)
             K = torch.empty(count, m, m, dtype=torch.float32, device=dev)
             self.ops.ocsvm_kernel_matrix(P, sq, m, self._table, first, count, self._gamma, ENGINES["gram" if gram else "exact"],
-                                         self._splits(m, count), K)
+                                         self._splits(m, m, count, cap=None), K)
             Kc = torch.empty(count * m * m, dtype=torch.float64, device=dev)
             self.ops.kpca_center(K, self._col_mean[first:first + count], self._total[first:first + count], Kc)
             self.ops.pca_eigen(Kc, syn, 0, count, m, False, self.max_sweeps, scale[:count * m], self._evals[first:first + count].view(-1),
                                self._V[first:first + count].view(-1), self._sweeps[first:first + count],
                                self._status[first:first + count])
             if kept is not None:
-                host = K.cpu().numpy()
-                for z in range(count):
-                    kept[int(self.plan.order[first + z])] = host[z]
+                self._keep(kept, K, first)
             del P, sq, K, Kc
 
     def _select(self):
@@ -3129,7 +3102,7 @@ class SubspaceKPCA(_SubspaceScorer):
         Pq, sqq = self._pack(Xs, first, count, gram)
         R = torch.empty(count, rows, self._m, dtype=torch.float32, device=Xs.device)
         self.ops.kpca_kernel_rows(Pq, sqq, rows, Pr, sqr, self._m, self._table, first, count, self._gamma,
-                                  ENGINES["gram" if gram else "exact"], self._splits(rows, count), R)
+                                  ENGINES["gram" if gram else "exact"], self._splits(rows, self._m, count, cap=None), R)
         return R
 
     def _score(self, Xq, fitting):
@@ -3308,9 +3281,7 @@ class SubspaceSOS(_SubspaceScorer):
                  workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
         self.perplexity, self.metric, self.tol, self.max_iter = check_sos_params(perplexity, metric, tol, max_iter)
         self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
-        if splits is not None and (int(splits) < 1 or int(splits) > 65535):
-            raise ValueError(f"splits must be between 1 and 65535, got {splits}")
-        self.splits = splits
+        self._configure_splits(splits)
         self.storage = "auto"
         self.keep_distance_matrix = False
 
@@ -3318,12 +3289,6 @@ class SubspaceSOS(_SubspaceScorer):
     def _check_fit_rows(self, n):
         check_sos_rows(n)
         check_sos_perplexity(self.perplexity, n)
-
-    def _splits(self, nq, nr, count):
-        if self.splits is not None:
-            return int(self.splits)
-        blocks = -(-nq // 64) * count
-        return int(max(1, min(-(-nr // 64), -(-_TARGET_BLOCKS // blocks), 64)))
 
     def _distance_matrix(self, X, first, count, gram):
         n = X.shape[0]
@@ -3345,18 +3310,10 @@ class SubspaceSOS(_SubspaceScorer):
         self.ops.sos_fit_scores(D, self._beta[rng], self._dmin[rng], self._Z[rng], per, self._rows[rng])
 
     def _score(self, Xq, fitting):
-        """The new-row form; fit scores its own rows from the stored matrices, chunk by chunk (_score_fitted)."""
-        Xr = self._X
-        nr, nq = Xr.shape[0], Xq.shape[0]
-        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xr.device)
-        for first, count, gram in self.plan.chunks(nr + nq, self.workspace_bytes):
-            Pr, sqr = self._pack(Xr, first, count, gram)
-            Pq, sqq = self._pack(Xq, first, count, gram)
-            acc = torch.empty(count * nq, dtype=torch.int64, device=Xr.device)
-            self.ops.sos_scores(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, SOS_METRICS[self.metric], self._beta, self._dmin,
-                                self._Z, ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count), acc, per,
-                                self._rows[first:first + count])
-            del Pq, Pr, sqq, sqr, acc
+        """The new-row form (Xq is never the fitted tensor itself); fit scores its own rows from the stored matrices, chunk by
+        chunk (_score_fitted)."""
+        per = self._sweep(Xq, self._X, lambda blocks, first, count, tail: self.ops.sos_scores(
+            *blocks, self._table, first, count, SOS_METRICS[self.metric], self._beta, self._dmin, self._Z, *tail))
         return self._combine(per, fitting), per
 
     # ---- public surface --------------------------------------------------------------------------
@@ -3378,9 +3335,7 @@ class SubspaceSOS(_SubspaceScorer):
             self._search(D, first, count, iters, flags)
             self._score_fitted(D, first, count, per)
             if self.keep_distance_matrix:
-                host = D.cpu().numpy()
-                for z in range(count):
-                    kept[int(self.plan.order[first + z])] = host[z]
+                self._keep(kept, D, first)
             del D
         g = self.plan.given
         self.beta_ = self._beta.cpu().numpy()[g]
