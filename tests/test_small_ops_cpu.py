@@ -6,7 +6,12 @@ evaluation of the shuffle, and the CpuOps provider the CPU tier runs the step en
 It also MEASURES the noise bar: NOISE_F32_CHAIN_ERR is the largest distance, in units of 2^-24 r, between the
 Box-Muller chain evaluated op for op in numpy float32 and its float64 restatement, over the first 2^20 quads of
 (seed 777, step 3).  tests/test_small_ops_gpu.py reads it from this module; the device bar is four times this value.
+
+For the mask / projection forward (tests/test_mask_forward_gpu.py) it pins mask_forward_ref to CpuOps, shows that
+check_mask_forward accepts a correct float32 implementation and rejects every fault of MASK_FWD_MUTATIONS, and asserts that
+the GPU module's case lists reach every kernel instantiation and keep clear of the 1/d threshold.
 """
+import collections
 import functools
 
 import numpy as np
@@ -292,3 +297,147 @@ def test_cpuops_pack_and_packed_optimiser_agree(cpu):
     untouched = np.ones(N, dtype=bool)
     untouched[pmap[live]] = False
     assert (w[untouched] == 7.0).all()
+
+
+# ---------------------------------------------------------------------------------------------- mask / projection forward
+def _mask_case(n, d, centre, sel_mode="table3-cnb1", e0=None, planted=True):
+    """the inputs of one forward case as tests/test_mask_forward_gpu.py draws them, on the host: logits with the planted rows,
+    a data set, a three-batch row table with the cursor one past row_batches and row_offset 3, the planted data row"""
+    from test_small_ops_gpu import edge_logits
+    rng = np.random.default_rng(7 * n + d)
+    lg = edge_logits(rng, n, d) if e0 is None else ref.chain_inputs(rng, n, d, e0)
+    N, nb, off = n + 5, 3, 3
+    stride = off + n + 2
+    data = (rng.normal(size=(N, d)) * 2.0 + 0.5).astype(np.float32)
+    table = rng.integers(0, N, size=(nb + 2) * stride).astype(np.int32)
+    sel = dict(table=table, cursor=nb + 1, row_batches=nb, row_stride=stride, row_offset=off)
+    want = ref.row_sel_ref(table, nb + 1, nb, stride, off, n)
+    if planted and not centre:
+        data[want[2]] = ref.planted_data_row(rng, d)
+    center = rng.normal(size=d).astype(np.float32) if centre else None
+    return lg, data, sel, want, center
+
+
+def _check(out, lg, data, want, center, norm_split, **kw):
+    S64, X, _ = ref.mask_forward_ref(lg, data, want, center)
+    delta = ref.chain_delta(*lg) if isinstance(lg, tuple) else None
+    return ref.check_mask_forward(out, S64, X, center, norm_split=norm_split, delta=delta, sel=want, const_rows=[2], lin_rows=[1], **kw)
+
+
+MASK_FWD_MUTATION_CASES = [  # mutation, n, d, centre, norm_split
+    ("ragged chunk left out of the sum", 8, 260, True, False), ("ragged chunk left out of the sum", 8, 516, True, False),
+    ("ragged chunk left out of the sum", 8, 772, False, True),
+    # (the true maximum of the 200-wide row lies 100 above the first chunk's: expf overflows and the row is NaN; at d = 260 the
+    # first chunk's maximum is within 3.1 of it and the fault changes roundings only)
+    ("row max over the first chunk", 8, 516, True, False), ("row max over the first chunk", 8, 1024, False, True),
+    ("norms of unsplit values", 8, 64, False, True), ("norms of unsplit values", 8, 1024, False, True),
+    ("centre kept where U == 1", 8, 20, True, False), ("selector without the cursor modulo", 8, 20, True, True),
+    ("selector without row_offset", 8, 20, False, False), ("row group unwritten", 72, 8, True, True), ("hi and lo swapped", 16, 12, True, True),
+    ("transposed image shifted by a row group", 16, 12, False, True), ("<= in the mask", 8, 20, True, False), ("<= in the mask", 8, 784, False, True),
+]
+
+
+def test_every_mask_forward_mutation_is_listed():
+    assert {m for m, *_ in MASK_FWD_MUTATION_CASES} == set(ref.MASK_FWD_MUTATIONS)
+
+
+@pytest.mark.parametrize("mutation,n,d,centre,norm_split", MASK_FWD_MUTATION_CASES)
+def test_check_mask_forward_accepts_the_restatement_and_rejects_each_mutation(mutation, n, d, centre, norm_split):
+    """check_mask_forward on the emulated outputs of a correct float32 implementation passes (whole and with every optional
+    output left out); on the outputs of each fault of MASK_FWD_MUTATIONS it raises"""
+    lg, data, sel, want, center = _mask_case(n, d, centre)
+    good = ref.emulate_mask_forward(lg, data, center=center, norm_split=norm_split, **sel)
+    worst = _check(good, lg, data, want, center, norm_split)
+    assert set(worst) == {"S", "near", "Zy", "sqx", "sqy"} and all(v <= 1.0 for v in worst.values())
+    lean = {k: good[k] for k in ("S", "sqy", "Zh", "Zl")}                   # write_x = 0, write_z = 0
+    _check(lean, lg, data, want, center, norm_split, z_from=dict(Zx=good["Zx"], Zy=good["Zy"]), x_half=False)
+    bad = ref.emulate_mask_forward(lg, data, center=center, norm_split=norm_split, mutation=mutation, **sel)
+    with pytest.raises(AssertionError):
+        _check(bad, lg, data, want, center, norm_split)
+
+
+def test_check_mask_forward_on_in_launch_logits():
+    """the chain bar: float32 products of za . At4^T summed in another order pass; a k column left out does not"""
+    n, d, e0 = 8, 260, 20
+    lg, data, sel, want, center = _mask_case(n, d, True, e0=e0)
+    za, At = lg
+    lg32 = np.zeros((n, d), dtype=np.float32)
+    for k in range(e0):                                              # an fma-free float32 chain: two roundings per term
+        lg32 += za[:, k:k + 1] * At[None, :, k]
+    good = ref.emulate_mask_forward(lg32, data, center=center, **sel)
+    assert _check(good, lg, data, want, center, False)["S"] <= 1.0
+    short = ref.emulate_mask_forward((za[:, 1:], At[:, 1:]), data, center=center, **sel)
+    with pytest.raises(AssertionError):
+        _check(short, lg, data, want, center, False)
+
+
+@pytest.mark.parametrize("n,d", [(8, 20), (5, 260)])
+def test_mask_forward_ref_agrees_with_cpuops(cpu, n, d):
+    """The two test-side statements of the forward do not drift.  CpuOps rounds u * x to float32 before it subtracts c, the
+    restatement (and the kernels' fma) round once: the difference is one rounding of u * x, so the pin gets 2^-24 |u x| on
+    top of the one-rounding bar."""
+    lg, data, sel, want, center = _mask_case(n, d, True)
+    S64, X, Xc = ref.mask_forward_ref(lg, data, want, center)
+    S, U, Zx, Zy, sqx, sqy = torch.zeros(n, d), torch.zeros(n, d), torch.zeros(n, d + 4), torch.zeros(n, d + 4), torch.zeros(n), torch.zeros(n)
+    cpu.mask_project_forward(_t(lg), _t(data), _t(sel["table"]), S, U, Zx, Zy, sqx, sqy, _t(np.array([sel["cursor"]], dtype=np.int64)),
+                             sel["row_batches"], sel["row_stride"], sel["row_offset"], center=_t(center), norm_split=True)
+    np.testing.assert_allclose(S.numpy(), S64, rtol=2e-5, atol=2.0 ** -126)
+    u = U.numpy()
+    assert np.array_equal(u, ref.upper_mask_ref(S.numpy()))
+    assert np.array_equal(Zx[:, :d].numpy(), Xc) and (Zx[:, d:] == 0).all()
+    ux = u.astype(np.float64) * X.astype(np.float64)
+    wantzy = ux - center.astype(np.float64)
+    bar = 2.0 ** -24 * np.abs(wantzy) * (1 + 2.0 ** -20) + 2.0 ** -149 + 2.0 ** -24 * np.abs(ux)
+    assert (np.abs(Zy[:, :d].numpy().astype(np.float64) - wantzy) <= bar).all()
+    for sq, rows in ((sqx, Zx), (sqy, Zy)):
+        np.testing.assert_allclose(sq.numpy(), (ref.split_value_ref(rows[:, :d].numpy()).astype(np.float64) ** 2).sum(1), rtol=1e-6)
+    # the emulated outputs are the restatement's own: they pass its check with room to spare
+    assert ref.emulate_mask_forward(lg, data, center=center, norm_split=True, **sel)["xrow"].tolist() == want.tolist()
+
+
+def test_expected_kernel_known_answers():
+    ek = ref.expected_kernel
+    assert ek("fwd", 784, 1024, [0], [784, 784, 784]) == "vec<4>" and ek("fwd", 784, 5, [0, 4], [784]) == "generic"
+    assert ek("fwd", 166, 512, [0], [168]) == "generic" and ek("fwd", 4096, 3, [0], [4096]) == "vec<16>" and ek("fwd", 4100, 3, [0], [4100]) == "generic"
+    assert ek("fwd", 1028, 8, [0], [1028], chain=True) == "invalid" and ek("fwd", 1024, 8, [0], [1028], chain=True) == "vec_chain<4>"
+    assert ek("fwd", 260, 5, [0], [261]) == "generic" and ek("fwd", 260, 5, [0], [261], chain=True) == "invalid"
+    assert ek("bf3", 784, 1024, [0], [784], zt=True) == "bf3<4,zt>" and ek("bf3", 784, 1024, [0], [784]) == "split<4>"
+    assert ek("bf3", 256, 8, [0], [256]) == "bf3<1,lean>" and ek("bf3", 260, 8, [0], [260]) == "split<2>"
+    assert ek("bf3", 260, 8, [0], [260], chain=True) == "bf3_chain<2>" and ek("bf3", 260, 8, [0], [260], chain=True, zt=True) == "invalid"
+    assert ek("bf3", 260, 12, [0], [260]) == "invalid" and ek("bf3", 1028, 8, [0], [1028]) == "invalid"
+
+
+def test_the_mask_forward_gpu_cases_reach_every_kernel():
+    """The dispatch rule of csrc/rows.hip restated (expected_kernel) over the GPU module's case lists: all 23 instantiations are
+    reached -- each test there re-derives the name from the buffers it really passes -- so that the edges stay visited, or
+    this test says so, if the dispatch changes."""
+    import test_mask_forward_gpu as g
+    reached = collections.Counter([g.fwd_dispatch(c) for c in g.FWD_CASES] + [g.bf3_dispatch(c) for c in g.BF3_CASES])
+    assert len(ref.MASK_FWD_KERNELS) == 23 and set(reached) == set(ref.MASK_FWD_KERNELS), sorted(set(ref.MASK_FWD_KERNELS) ^ set(reached))
+    assert g.fwd_dispatch(g.FWD_CHAIN_INVALID) == "invalid"
+    # every unaligned view falls back to the generic kernel; the opt-in boundaries of the dynamic LDS are visited on both sides
+    assert all(g.fwd_dispatch(c) == "generic" for c in g.FWD_PATHS) and len({c.d for c in g.FWD_PATHS}) == 6
+    for cases in (g.FWD_CHAIN, g.BF3_ZT, g.BF3_CHAIN):
+        assert {1016, 1020, 1024} <= {c.d for c in cases}
+    assert {c.n // 8 for c in g.BF3_ZT} == {1, 2, 9, 17} and {c.n for c in g.FWD_CHAIN} == {5, 8}
+
+
+def test_the_mask_forward_gpu_cases_keep_clear_of_the_threshold():
+    """Every GPU case's logits, on the host: each random row has mask entries on both sides of 1/d (d > 1) and at most 0.5 % of
+    a case's random-row entries lie within 1e-4 of the threshold, where the float64 decision is not asserted."""
+    import test_mask_forward_gpu as g
+    worst = 0.0
+    for c in g.FWD_CASES + g.BF3_CASES:
+        assert np.float32(1.0 / c.d) == np.float32(1.0) / np.float32(c.d), c.d   # (upper_mask_ref's threshold is the kernels')
+        _, lg = g.case_logits(c)
+        S64 = ref.mask_forward_ref(lg, np.zeros((1, c.d), dtype=np.float32), [0])[0]
+        rand = np.ones(c.n, dtype=bool)
+        rand[[1, 2] if c.n >= 3 else []] = False
+        if c.d == 1 or not rand.any():
+            continue
+        below = S64[rand] * c.d < 1.0
+        assert below.any(1).all() and (~below).any(1).all(), c
+        near = float((np.abs(S64[rand] * c.d - 1.0) <= 1e-4).mean())
+        assert near <= 0.005, (c, near)
+        worst = max(worst, near)
+    print(f"largest share of threshold-near entries over the GPU cases: {worst:.4%}")

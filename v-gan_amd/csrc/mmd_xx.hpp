@@ -31,9 +31,11 @@ struct XXJob {
 // the block reaches undefined: it holds on gfx950 / ROCm 7.2 because an ended wave leaves the workgroup's barrier count, and it
 // is exercised only by the 512- and 1024-thread carriers (mask_forward_bf3_kernel<.., XX>: opt-in; linear_bwd_params_ks_xx: the
 // late X-X tiles when the MMD backward launch has no room).  The DEFAULT carrier, mmd_backward_bf3_kernel<64, true>, has exactly
-// 256 threads: no wave returns early there.  Each carrier has a GPU parity test in the default tier
-// (test_backward_bf3_rowmajor_operand_equals_transposed_operand, test_xx_tiles_*, the VGAN_GRAM_SLOTS-forced step tests); should a
-// compiler change break the early return, let the surplus waves idle THROUGH the tile's barriers instead.  One tile per CU is the point: alone on a CU a tile takes ~7 us, two sharing one ~15 (measured with
+// 256 threads: no wave returns early there.  GPU parity tests reach the DEFAULT carrier only
+// (test_backward_bf3_rowmajor_operand_equals_transposed_operand, test_backward_rebuilt_operands_equal_operands_read_from_z and the
+// VGAN_GRAM_SLOTS-forced cases of test_engine_lean_step_equals_step_with_fp32_operand); the 512- and 1024-thread carriers are reached by
+// test_xx_tiles_* of tests/test_host_logic.py alone, which run the step engine on the CPU provider and so never execute the
+// early return: no GPU test holds that assumption.  Should a compiler change break the early return, let the surplus waves idle THROUGH the tile's barriers instead.  One tile per CU is the point: alone on a CU a tile takes ~7 us, two sharing one ~15 (measured with
 // tile PAIRS per workgroup: the carrying launch went from 9.4 to 18.2 us).  lds: GemmBF3<64>::kLdsBytes.
 __device__ __forceinline__ void xx_tile_body(const XXJob& job, int t, char* lds, float* red /* [4] */) {
     using G = GemmBF3<64>;
