@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1012,6 +1012,62 @@ int vgan_iforest_build_blocks(const float* R, int64_t block_stride, int64_t n, i
 int vgan_iforest_path_sums_blocks(const float* Rq, int64_t block_stride, int rows, int q, const int32_t* nodes, int first,
                                   int count, int T, int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums,
                                   vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Autoencoder outlier scores (pyod's AutoEncoder without dropout and batch normalisation; replaces a host framework's loop of
+ * nn.Linear forward / MSELoss backward / torch.optim.Adam(weight_decay=) steps over S small nets): one MLP per subspace of the
+ * table (feat, feat_off), trained to reconstruct the standardised rows, scored by the reconstruction distance
+ * (v-gan_amd/outlier.py: SubspaceAutoEncoder, whose docstring is the definition; kernels in csrc/outlier_ae.hip).  BLOCK b is
+ * the subspace at position b.  Its net has the layer sizes K_0 = d_s, hidden[0 .. n_hidden - 1], hidden[n_hidden - 2 .. 0],
+ * d_s (2 n_hidden layers), a bias in every layer, the activation after every layer but the last.  Limits: 1 <= n_hidden <=
+ * VGAN_AE_MAX_HIDDEN (hidden is a HOST array), 1 <= hidden[l] <= VGAN_AE_MAX_WIDTH, d_s <= max_dims <= VGAN_AE_MAX_DIMS (a
+ * block with more than max_dims features is left alone), count <= 65535 blocks a call.
+ * The STATE of the blocks first .. first + count - 1 is one float32 buffer: block first + z starts at state + s_off[z] (s_off
+ *   int64 [count] on the device) and holds theta, m and v, P = sum_l (K_l + 1) N_l floats each; inside each, layer after
+ *   layer, W_l K-MAJOR [K_l][N_l] (W_l[o, i] at i N_l + o) followed by b_l [N_l].  vgan_ae_scores reads theta alone.
+ * z = float32((double(x) - mean_f) / scale_f), mean and scale float64 [d] (scale 1 for a constant column).  skip int32 [S]:
+ *   1 = the subspace is constant: it is not trained and scores exactly 0.
+ * vgan_ae_init: zeroes state[0 .. total) and writes theta of every block of the range: W_l[o, i] and b_l[o] = float32((2 u - 1)
+ *   c_l), u = (w + 0.5) 2^-32 in float64, w the word e & 3 of Philox4x32-10 at counter (lo32(e >> 2), hi32(e >> 2), 0x41450000 +
+ *   l, 0) and key (lo32(seed) ^ lo32(b), hi32(seed) ^ hi32(b) ^ 0x5bd1e995), e = o K_l + i for a weight and N_l K_l + o for a
+ *   bias; c_l = scale[b (2 n_hidden) + l] (float64 on the device, formed on the host as 1 / sqrt(K_l)).
+ * vgan_ae_train: the global steps step_first .. step_first + step_count - 1 (0-based; step g is step g % (n / batch) of
+ *   epoch g / (n / batch) and has t = g + 1) of every block of the range, ONE WORKGROUP PER BLOCK for the whole call.  Row j of
+ *   the batch of step i of epoch e is feistel_perm(i batch + j, n, seed, e).  corr float64 [step_count, 2] on the device:
+ *   1 - beta1^t and 1 - beta2^t of every step of the call, formed on the host.  Per step: z of the batch, the forward, the
+ *   float32 loss sum (out - z)^2 / (batch d_s) into loss[z_block ld_loss + g] (before the update), the exact backward, g +=
+ *   weight_decay theta, torch's Adam in place.  Every product is one fmaf chain in ascending order of its summation index,
+ *   so the bits depend on neither the cut of the steps into calls nor the blocks that share a call.  The activations of the
+ *   batch stay in LDS when batch (2 (max_dims | 1) + sum (h | 1) + (max h | 1)) <= VGAN_AE_LDS_FLOATS, the sum over the 2
+ *   n_hidden - 1 hidden layers; otherwise scratch (float32, scratch_floats >= that many per block of the call) holds them.
+ * vgan_ae_scores: score[z ld_score + i] = float32(sqrt(sum_f (out_if - z_if)^2)), the sum float64 in ascending f, for the rows
+ *   of X [rows, d]; one workgroup per (block, VGAN_AE_ROW_TILE rows), the same layer routine as the training.  recon != NULL
+ *   (count must be 1): float32 [rows, d_s] receives the raw output instead, score may be NULL.  scratch as above with
+ *   VGAN_AE_ROW_TILE ((max_dims | 1) + sum (h | 1)) floats per (block, row tile).
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_AE_MAX_HIDDEN 3
+#define VGAN_AE_MAX_WIDTH 128
+#define VGAN_AE_MAX_DIMS 1024
+#define VGAN_AE_MAX_BATCH 256
+#define VGAN_AE_MAX_ROWS 16777216 /* 2^24 */
+#define VGAN_AE_MAX_LAUNCH_STEPS 65536
+#define VGAN_AE_ROW_TILE 32
+#define VGAN_AE_LDS_FLOATS 38912 /* 152 KiB of the 160 KiB of a CU */
+#define VGAN_AE_ACT_TANH 0
+#define VGAN_AE_ACT_RELU 1
+int vgan_ae_init(const int32_t* feat_off, int first, int count, int n_hidden, const int32_t* hidden, const double* scale,
+                 uint64_t seed, float* state, const int64_t* s_off, int64_t total, vgan_stream_t stream);
+int vgan_ae_train(const float* X, int ldx, int n, int d, const int32_t* feat, const int32_t* feat_off, const double* mean,
+                  const double* scale, const int32_t* skip, int first, int count, int max_dims, int n_hidden,
+                  const int32_t* hidden, int activation, int batch, uint64_t seed, int64_t step_first, int step_count,
+                  const double* corr, double lr, double beta1, double beta2, double eps, double weight_decay, float* state,
+                  const int64_t* s_off, float* loss, int64_t ld_loss, float* scratch, int64_t scratch_floats,
+                  vgan_stream_t stream);
+int vgan_ae_scores(const float* X, int ldx, int rows, int d, const int32_t* feat, const int32_t* feat_off, const double* mean,
+                   const double* scale, const int32_t* skip, int first, int count, int max_dims, int n_hidden,
+                   const int32_t* hidden, int activation, const float* state, const int64_t* s_off, float* score,
+                   int64_t ld_score, float* recon, float* scratch, int64_t scratch_floats, vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * iNNE, isolation by nearest-neighbour ensembles (Bandaragoda, Ting, Albrecht, Liu, Wells 2018; pyod's INNE): T estimators

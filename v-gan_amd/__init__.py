@@ -9,10 +9,10 @@ from .modules import (Generator_big, upper_softmax, Encoder, Decoder, Detector, 
                       MMDLossConstrained)
 from .vgan import VGAN, VGAN_no_kl  # noqa: F401
 from .outlier import (SubspaceEnsemble, SubspaceCBLOF, SubspaceABOD, SubspaceECOD, SubspaceIForest, SubspaceMahalanobis,  # noqa: F401
-                      SubspaceGMM, SubspaceHBOS, SubspaceLODA, SubspacePCA, SubspaceOCSVM, SubspaceCOF, SubspaceINNE, SubspaceSOS, SubspaceDIF, SubspaceSOD,
+                      SubspaceGMM, SubspaceHBOS, SubspaceLODA, SubspacePCA, SubspaceOCSVM, SubspaceCOF, SubspaceINNE, SubspaceSOS, SubspaceDIF, SubspaceSOD, SubspaceAutoEncoder,
                       SubspaceKPCA)
 
 __all__ = ["VGAN", "VGAN_no_kl", "Generator_big", "upper_softmax", "Encoder", "Decoder", "Detector", "RBF",
            "MMDLossConstrained", "SubspaceEnsemble", "SubspaceCBLOF", "SubspaceABOD", "SubspaceECOD", "SubspaceIForest",
            "SubspaceMahalanobis", "SubspaceGMM", "SubspaceHBOS", "SubspaceLODA", "SubspacePCA", "SubspaceOCSVM",
-           "SubspaceCOF", "SubspaceINNE", "SubspaceSOS", "SubspaceDIF", "SubspaceSOD", "SubspaceKPCA", "lib"]
+           "SubspaceCOF", "SubspaceINNE", "SubspaceSOS", "SubspaceDIF", "SubspaceSOD", "SubspaceKPCA", "SubspaceAutoEncoder", "lib"]

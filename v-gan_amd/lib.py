@@ -10,6 +10,7 @@ _p = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _i64 = ctypes.c_int64
+_d = ctypes.c_double
 _u64 = ctypes.c_uint64
 
 class FinalizeJob(ctypes.Structure):
@@ -175,6 +176,10 @@ SIGNATURES = {
     "vgan_iforest_path_sums_blocks": (_i, [_p, _i64, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, _p]),
     "vgan_dif_weights": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _u64, _p, _p, _i64, _p]),
     "vgan_dif_represent": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p]),
+    "vgan_ae_init": (_i, [_p, _i, _i, _i, _p, _p, _u64, _p, _p, _i64, _p]),
+    "vgan_ae_train": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _u64, _i64, _i, _p, _d, _d, _d, _d, _d, _p, _p,
+                           _p, _i64, _p, _i64, _p]),
+    "vgan_ae_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i64, _p, _p, _i64, _p]),
     "vgan_inne_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p, _p, _p, _p]),
     "vgan_inne_scores": (_i, [_p, _i, _i, _i, _p, _i, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]),
     "vgan_maha_moments": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _i64, _p, _p, _p, _p, _i64, _p]),
@@ -206,7 +211,7 @@ SIGNATURES = {
     "vgan_kpca_scores": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
-ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_kpca_* ones last) leave it
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_ae_* ones last) leave it
 _lib = None
 
 

@@ -107,6 +107,11 @@ rows to small representations in one fused fp32 matrix-unit forward that keeps e
 (the block entries of csrc/outlier_iforest.hip).  Its contract (scaling, the nets and their weights, the representation and
 its precision, the trees and the pooled score, determinism, what is not built) is that class's docstring.
 
+``SubspaceAutoEncoder`` is the detector that learns: one small MLP per subspace trained by Adam on mini-batches to reconstruct the
+standardised rows through a bottleneck, one workgroup owning one net for many optimiser steps per launch, the reconstruction
+distance as the score (csrc/outlier_ae.hip).  Its contract (scaling, the net and its initial draw, the batches, the float32
+operation sequence of a step, the score, determinism, what is not built) is that class's docstring.
+
 ``SubspaceHBOS`` and ``SubspaceLODA`` are the histogram detectors, linear in n: equal-width histograms (numpy.linspace's
 edges, numpy.histogram's counts, exact integer sums) of every feature (HBOS: -log2 densities summed over a subspace's
 features, the dense float64 product of ``SubspaceECOD``) or of sparse random projections of every subspace (LODA: the mean
@@ -3644,6 +3649,344 @@ class SubspaceDIF(_SubspaceScorer):
         self._flat_trees = self._trees.view(self.plan.count * self.n_representations, self.n_estimators, 2 << self.depth_limit_, 2)
         self._fitted = False
         scores, per = self._scores(X, True)
+        return self._publish(scores, per)
+
+
+# ---- autoencoders: one small MLP per subspace, trained on the device, the reconstruction distance as the score ---------
+AE_MAX_HIDDEN = 3  # VGAN_AE_MAX_HIDDEN: encoder widths; the net has twice as many layers
+AE_MAX_WIDTH = 128  # VGAN_AE_MAX_WIDTH
+AE_MAX_DIMS = 1024  # VGAN_AE_MAX_DIMS: features of one subspace (the SubspaceMahalanobis limit)
+AE_MAX_BATCH = 256  # VGAN_AE_MAX_BATCH
+AE_MAX_ROWS = 1 << 24  # VGAN_AE_MAX_ROWS
+AE_ROW_TILE = 32  # VGAN_AE_ROW_TILE: rows of one workgroup of the scoring forward
+AE_LDS_FLOATS = 38912  # VGAN_AE_LDS_FLOATS: the activations of a batch stay in LDS up to here, else in a scratch slice
+AE_ACTIVATIONS = {"tanh": 0, "relu": 1}  # VGAN_AE_ACT_*
+AE_PHILOX_TAG = 0x41450000  # counter word 2 of an initial draw is AE_PHILOX_TAG + layer
+AE_MAX_LAUNCH_STEPS = 65536  # VGAN_AE_MAX_LAUNCH_STEPS
+# Multiply-adds of one training launch of one net (a step costs 3 B P of them: forward, passed-down error, gradient): a launch
+# runs AE_LAUNCH_MACS // (3 B P) steps, at least one.  Measured on an MI355X: the largest net (d_s 1024, hidden (128, 128, 128),
+# B 256: 3.1e8 a step, so one step a launch) takes 12.1 ms a launch with 8 nets in flight and 36.0 ms with 256 (their
+# activations in the scratch buffer); the default net at d_s = 375 (B 32, 51 to 53 steps a launch) 8.0 ms with 50 nets and 9.6
+# ms with 256.  All far below a second on a shared machine.
+AE_LAUNCH_MACS = 1 << 28
+_AE_MAX_RANGE = 65535  # blocks of one launch (a grid dimension)
+
+
+def check_ae_hidden(hidden):
+    """A tuple of 1 to AE_MAX_HIDDEN encoder widths, each 1 .. AE_MAX_WIDTH; the decoder mirrors it."""
+    try:
+        widths = tuple(hidden)
+    except TypeError:
+        raise ValueError(f"hidden must be a tuple of 1 to {AE_MAX_HIDDEN} widths, got {hidden!r}") from None
+    if not 1 <= len(widths) <= AE_MAX_HIDDEN:
+        raise ValueError(f"hidden must hold between 1 and {AE_MAX_HIDDEN} widths, got {len(widths)}")
+    for w in widths:
+        if not (_is_int(w) and 1 <= int(w) <= AE_MAX_WIDTH):
+            raise ValueError(f"a hidden width must be an integer between 1 and {AE_MAX_WIDTH}, got {w!r}")
+    return tuple(int(w) for w in widths)
+
+
+def check_ae_params(epochs, batch_size, lr, beta1, beta2, eps, weight_decay):
+    if not (_is_int(epochs) and int(epochs) >= 0):
+        raise ValueError(f"epochs must be a non-negative integer, got {epochs!r}")
+    if not (_is_int(batch_size) and 1 <= int(batch_size) <= AE_MAX_BATCH):
+        raise ValueError(f"batch_size must be an integer between 1 and {AE_MAX_BATCH}, got {batch_size!r}")
+    if not (_is_real(lr) and 0.0 <= float(lr) < float("inf")):
+        raise ValueError(f"lr must be a non-negative number, got {lr!r}")
+    for name, beta in (("beta1", beta1), ("beta2", beta2)):
+        if not (_is_real(beta) and 0.0 <= float(beta) < 1.0):
+            raise ValueError(f"{name} must be a number in [0, 1), got {beta!r}")
+    if not (_is_real(eps) and 0.0 < float(eps) < float("inf")):
+        raise ValueError(f"eps must be a positive number, got {eps!r}")
+    if not (_is_real(weight_decay) and 0.0 <= float(weight_decay) < float("inf")):
+        raise ValueError(f"weight_decay must be a non-negative number, got {weight_decay!r}")
+    return int(epochs), int(batch_size), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay)
+
+
+def ae_layer_sizes(d_s, hidden):
+    """[(K_l, N_l)] of the net of a subspace of d_s features: d_s, the encoder widths, mirrored, d_s."""
+    widths = [int(d_s)] + [int(w) for w in hidden] + [int(w) for w in tuple(hidden)[-2::-1]] + [int(d_s)]
+    return list(zip(widths[:-1], widths[1:]))
+
+
+def ae_param_count(d_s, hidden):
+    """P: the parameters of one net, sum_l (K_l + 1) N_l."""
+    return sum((K + 1) * N for K, N in ae_layer_sizes(d_s, hidden))
+
+
+def ae_act_floats(d_s, hidden, rows, train):
+    """The float32 cells of the activations of `rows` rows (pitches are widths | 1): z and the hidden layers and, when
+    training, the output error and one passed-down error of the widest hidden layer (csrc/outlier_ae.hip)."""
+    per_row = (int(d_s) | 1) * (2 if train else 1) + ((max(hidden) | 1) if train else 0)
+    per_row += sum(N | 1 for _, N in ae_layer_sizes(d_s, hidden)[:-1])
+    return per_row * int(rows)
+
+
+def ae_net_bytes(d_s, hidden, batch, max_dims=None):
+    """The bytes one net needs while it trains: theta, m and v (12 P) and, when the activations of a batch of the widest
+    subspace (max_dims, default d_s) do not fit AE_LDS_FLOATS, its slice of the scratch buffer."""
+    act = ae_act_floats(d_s if max_dims is None else max_dims, hidden, batch, True)
+    return 12 * ae_param_count(d_s, hidden) + (4 * act if act > AE_LDS_FLOATS else 0)
+
+
+def ae_chunks(net_bytes, workspace_bytes):
+    """[(first, count)]: consecutive runs of nets whose training state fits workspace_bytes, at most 65535 each; every chunk
+    trains to the end before the next begins.  ValueError, naming the bytes, when one net alone does not fit."""
+    out, first, ws = [], 0, int(workspace_bytes)
+    sizes = [int(v) for v in net_bytes]
+    for s, need in enumerate(sizes):
+        if need > ws:
+            raise ValueError(f"SubspaceAutoEncoder needs {need} bytes of workspace for the net of subspace {s} with its moments, "
+                             f"workspace_bytes is {ws}")
+    while first < len(sizes):
+        end, used = first, 0
+        while end < len(sizes) and end - first < _AE_MAX_RANGE and used + sizes[end] <= ws:
+            used += sizes[end]
+            end += 1
+        out.append((first, end - first))
+        first = end
+    return out
+
+
+def ae_launch_steps(params, batch):
+    """The steps of one training launch for nets of at most `params` parameters: AE_LAUNCH_MACS // (3 B P), 1 .. 65536."""
+    return int(max(1, min(AE_LAUNCH_MACS // (3 * int(batch) * int(params)), AE_MAX_LAUNCH_STEPS)))
+
+
+def ae_bias_corrections(beta1, beta2, steps):
+    """float64 [steps, 2]: 1 - beta1^t and 1 - beta2^t for t = 1 .. steps (numpy's float64 power)."""
+    t = np.arange(1, int(steps) + 1, dtype=np.float64)
+    return np.stack([1.0 - np.float64(beta1) ** t, 1.0 - np.float64(beta2) ** t], axis=1)
+
+
+class SubspaceAutoEncoder(_SubspaceScorer):
+    """Autoencoder per subspace (pyod's ``AutoEncoder``), combined like the other detectors of this module: a small MLP is
+    trained to reconstruct the standardised rows of the subspace through a bottleneck, and a row is scored by the Euclidean
+    norm of its reconstruction error.  It is the one detector here that LEARNS a representation: rows that leave a curved
+    low-dimensional structure while staying inside every marginal range and close to the covariance ellipsoid are found by
+    it and by none of the linear detectors.  All S nets train at once, one workgroup per net running many optimiser steps
+    per launch.  The defaults are pyod's as remembered (hidden [64, 32], relu, 100 epochs, batch 32, Adam lr 1e-3, weight
+    decay 1e-5).  Not built: dropout and batch normalisation (pyod's defaults use both), a validation split and early
+    stopping, other optimisers and losses, several nets per subspace, a VAE, DeepSVDD.
+
+    Sizes.  X is cast to float32.  hidden: 1 to 3 encoder widths, each 1 .. 128; activation "relu" or "tanh"; batch_size 1 ..
+    256; epochs >= 0; 0 <= beta1, beta2 < 1; eps > 0; lr, weight_decay >= 0; seed in [0, 2^64); a subspace has at most 1024
+    features; ``fit`` takes 2 .. 2^24 rows.
+
+    Scaling.  At ``fit``, per feature f, mean_f and the population variance are taken in float64, deterministically (the
+    two-pass slab sums of SubspacePCA's ``location_`` and ``scale_``); sd_f = sqrt(variance), 1 where the variance is 0
+    (sklearn's StandardScaler).  ``location_``, ``scale_``: float64 [d].  z = float32((double(x) - mean_f) / sd_f), exactly 0
+    for a constant column.  New rows use the stored values.
+
+    Net.  The subspace at position s has the layer sizes d_s, h_1 .. h_L, h_{L-1} .. h_1, d_s (2 L layers l = 0 .. 2 L - 1, layer
+    l mapping K_l inputs to N_l outputs), a bias in every layer, the activation after every layer but the last, a linear
+    output.  relu is max(a, 0); tanh is float32(tanh(double(a))) of the float32 pre-activation a (SubspaceDIF's).
+
+    Initialisation.  torch's ``nn.Linear`` default, U(-1 / sqrt(K_l), 1 / sqrt(K_l)) for weights and biases, drawn as
+    SubspaceDIF draws: with the Philox4x32-10 words of
+
+        counter (lo32(e >> 2), hi32(e >> 2), 0x41450000 + l, 0),  key k0 = lo32(seed) ^ lo32(s),  k1 = hi32(seed) ^ hi32(s) ^ 0x5bd1e995
+
+    w = word e & 3, u = (w + 0.5) 2^-32 in float64, value = float32((2 u - 1) c_l), c_l = 1 / sqrt(K_l) formed on the host in
+    float64; W_l[o, i] has e = o K_l + i (for layer 0, i is the position in the ascending feature list), b_l[o] has e = N_l K_l +
+    o.  m = v = 0.  The nets are keyed by the subspace's POSITION, like SubspaceDIF's.
+
+    Batches.  B = min(batch_size, n); an epoch has n // B steps (the last partial batch is dropped); row j of step i of epoch e
+    is feistel_perm(i B + j, n, seed, e), the same for every subspace.  The global step g = e (n // B) + i has t = g + 1.
+    ``n_steps_`` = epochs (n // B).  epochs = 0 scores with the untrained net.
+
+    One step, all in float32 unless said; fma(a, b, c) is a b + c rounded once.
+      forward     pre_l[i, o] = (fma-chain over k ascending, from 0, of h_{l-1}[i, k] W_l[o, k]) + b_l[o]; h_l = act(pre_l), h_{-1} =
+                  z, out = pre_{2L-1}.
+      loss        r[i, f] = out[i, f] - z[i, f]; rowsum_i = fma-chain over f ascending of r r; loss = (sum over i ascending of
+                  rowsum_i) / float32(B d_s): the batch loss before the update, the mean squared error.
+      backward    D_{2L-1}[i, f] = r[i, f] float32(2 / (B d_s)) (the factor formed in float64); for l from the last layer down:
+                  down[i, k] = fma-chain over o ascending of D_l[i, o] W_l[o, k] with the weights BEFORE their update;
+                  D_{l-1}[i, k] = down[i, k] act'(h_{l-1}[i, k]), act' = (h > 0 ? 1 : 0) for relu and fma(-h, h, 1) for tanh.
+      gradient    g = fma-chain over the batch rows i ascending of D_l[i, o] h_{l-1}[i, k]; for a bias the factor h is 1.
+      Adam        g = fma(wd, theta, g); m = fma(b1, m, omb1 g); v = fma(b2, v, (omb2 g) g); theta = theta - (lrc m) / (sqrt(v) / sc2
+                  + eps) with b1, b2, eps, wd the float32 roundings of beta1, beta2, eps, weight_decay, omb = float32(1 - beta)
+                  formed in float64, lrc = float32(lr / c1_t), sc2 = float32(sqrt(c2_t)), c1_t = 1 - beta1^t and c2_t = 1 -
+                  beta2^t formed ON THE HOST in float64 (numpy's power) and handed over per step: torch's
+                  ``Adam(weight_decay=)``, with beta1 = 0 m is the gradient itself.  Weight decay acts on the biases too.
+    No value depends on how the steps are cut into launches, on workspace_bytes (which cuts the subspaces into chunks that
+    each train to the end: ae_chunks) or on the other subspaces of a launch: weights, losses and scores are bit-identical
+    from run to run and across all of these.  ``fit`` raises ValueError, naming the bytes, when one net with its moments
+    does not fit workspace_bytes.
+
+    Score.  score[s, i] = float32(sqrt(sum_f (out[i, f] - z[i, f])^2)): the float32 differences squared and summed in float64
+    in ascending f.  It depends on the row and the subspace only, and grows like sqrt(d_s): with subspaces of different sizes
+    ``normalize`` is the argument to reach for.  ``fit`` scores the training rows through the trained net with the kernel of
+    ``decision_function``, so ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.  A subspace whose features
+    are all constant is not trained (its weights stay the initial ones, its losses are 0) and scores exactly 0.  NaN input
+    leaves the results unspecified and neither faults nor hangs.
+
+    Fitted state: the weights, ``location_``, ``scale_`` and the seed; neither X nor the moments are kept.  ``fit`` publishes
+    ``weights_`` (a list of S lists of (W_l float32 [N_l, K_l], b_l float32 [N_l]), fetched on first use), ``loss_history_``
+    (float64 [S, epochs]: the float32 step losses of an epoch summed in float64 in step order and divided by their number),
+    ``n_steps_``, ``location_``, ``scale_``.  ``reconstruct(X, s)`` returns float32 [n, d_s], the output of net s on the
+    standardised rows: for inspection and the tests.  normalize, combination, contamination, ``threshold_``, ``labels_``,
+    ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.  pyod is not pinned here: this definition and
+    its numpy restatement in tests/test_outlier_ae_cpu.py are what binds.  All of it runs in libvgan_hip.so
+    (csrc/outlier_ae.hip; the column moments in csrc/outlier_maha.hip)."""
+
+    _host_weights = None
+
+    def __init__(self, subspaces, proba, hidden=(64, 32), activation="relu", epochs=100, batch_size=32, lr=1e-3, beta1=0.9, beta2=0.999,
+                 eps=1e-8, weight_decay=1e-5, seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum",
+                 contamination=0.1):
+        self.hidden = check_ae_hidden(hidden)
+        self.activation = check_activation(activation)
+        (self.epochs, self.batch_size, self.lr, self.beta1, self.beta2, self.eps,
+         self.weight_decay) = check_ae_params(epochs, batch_size, lr, beta1, beta2, eps, weight_decay)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        self._max_dims = int(self.plan.dims.max())
+        if self._max_dims > AE_MAX_DIMS:
+            raise ValueError(f"a subspace has {self._max_dims} features, SubspaceAutoEncoder takes at most {AE_MAX_DIMS}")
+        self._net = (self.hidden, AE_ACTIVATIONS[self.activation])
+        self._params = np.array([ae_param_count(d_s, self.hidden) for d_s in self.plan.dims], dtype=np.int64)
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= AE_MAX_ROWS:
+            raise ValueError(f"SubspaceAutoEncoder fit needs between 2 and {AE_MAX_ROWS} rows, got {n}")
+
+    def _attach(self):
+        if self.ops is not None:
+            return
+        super()._attach()
+        fan_in = np.array([[K for K, _ in ae_layer_sizes(d_s, self.hidden)] for d_s in self.plan.dims], dtype=np.float64)
+        self._init_scale = torch.as_tensor(1.0 / np.sqrt(fan_in), device="cuda")
+        self._w_off_host = np.concatenate([[0], np.cumsum(self._params)]).astype(np.int64)
+        self._w_off = torch.as_tensor(self._w_off_host[:-1].copy(), device="cuda")
+
+    def _column_moments(self, X):
+        """(mean, variance) float64 [d] on the host: vgan_maha_moments over the d one-feature subspaces, the two-pass slab sums
+        whose bits depend on n alone."""
+        n, d = X.shape
+        dev = X.device
+        ones = np.ones(d, dtype=np.int64)
+        table = (torch.arange(d, dtype=torch.int32, device=dev), torch.arange(d + 1, dtype=torch.int32, device=dev),
+                 torch.arange(d + 1, dtype=torch.int64, device=dev))
+        cells, ranges = maha_ranges(ones, self.workspace_bytes)
+        mean, var = (torch.empty(d, dtype=torch.float64, device=dev) for _ in range(2))
+        hcount = torch.full((d,), n, dtype=torch.int32, device=dev)
+        slabs = -(-n // MAHA_SLAB_ROWS)
+        for first, count in ranges:
+            tiles = torch.as_tensor(maha_tiles(ones, first, count), device=dev)
+            ws = torch.empty(min(cells, slabs * MAHA_TILE * MAHA_TILE * count), dtype=torch.float64, device=dev)
+            self.ops.maha_moments(X, table, first, count, count, 1, tiles, None, hcount, mean, var, ws)
+        return mean.cpu().numpy(), var.cpu().numpy()
+
+    def _train(self, X, batch, chunks):
+        """Trains every chunk of nets to the end; the weights go to _theta, the step losses to the returned [S, steps] matrix."""
+        n, dev = X.shape[0], X.device
+        S, steps = self.plan.count, self.epochs * (n // batch)
+        corr = torch.as_tensor(ae_bias_corrections(self.beta1, self.beta2, steps), device=dev)
+        loss = torch.zeros(S, max(steps, 1), dtype=torch.float32, device=dev)
+        adam = (self.lr, self.beta1, self.beta2, self.eps, self.weight_decay)
+        act = ae_act_floats(self._max_dims, self.hidden, batch, True)
+        for first, count in chunks:
+            sizes = self._params[first:first + count]
+            off = np.concatenate([[0], np.cumsum(3 * sizes)]).astype(np.int64)
+            state = torch.empty(int(off[-1]), dtype=torch.float32, device=dev)
+            s_off = torch.as_tensor(off[:-1].copy(), device=dev)
+            self.ops.ae_init(self._table[1], self._net, first, count, self._init_scale, self.seed, state, s_off, int(off[-1]))
+            scratch = torch.empty(count * act, dtype=torch.float32, device=dev) if act > AE_LDS_FLOATS else None
+            per_launch = ae_launch_steps(int(sizes.max()), batch)
+            for g0 in range(0, steps, per_launch):
+                self.ops.ae_train(X, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, batch, self.seed,
+                                  g0, corr[g0:g0 + per_launch], adam, state, s_off, loss[first:first + count], scratch)
+            for z in range(count):
+                at = int(self._w_off_host[first + z])
+                self._theta[at:at + int(sizes[z])].copy_(state[int(off[z]):int(off[z]) + int(sizes[z])])
+            del state, scratch
+        return loss[:, :steps]
+
+    def _distances(self, X, only=None):
+        """float32 [S, nq] on the device: the reconstruction distances of the rows of X; only = s: (the raw output of net s
+        [nq, d_s]) instead."""
+        nq, dev = X.shape[0], X.device
+        act = ae_act_floats(self._max_dims, self.hidden, AE_ROW_TILE, False)
+        spill = act > AE_LDS_FLOATS
+        ranges = list(_launch_ranges(self.plan.count, _AE_MAX_RANGE)) if only is None else [(only, 1)]
+        widest = max(count for _, count in ranges)
+        tiles = -(-nq // AE_ROW_TILE)
+        if spill:  # the scratch slices of a launch, one per (block, row tile), within workspace_bytes; at least one row tile
+            tiles = int(max(1, min(tiles, self.workspace_bytes // (4 * act * widest))))
+        rows = tiles * AE_ROW_TILE
+        scratch = torch.empty(widest * tiles * act, dtype=torch.float32, device=dev) if spill else None
+        if only is None:
+            out = torch.empty(self.plan.count, nq, dtype=torch.float32, device=dev)
+        else:
+            out = torch.empty(nq, int(self.plan.dims[only]), dtype=torch.float32, device=dev)
+        for first, count in ranges:
+            for r0 in range(0, nq, rows):
+                Xc = X[r0:r0 + rows]
+                if only is None:
+                    self.ops.ae_scores(Xc, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, self._theta,
+                                       self._w_off[first:first + count], score=out[first:first + count, r0:], scratch=scratch)
+                else:
+                    self.ops.ae_scores(Xc, self._table, self._scaling, self._skip, self._net, first, 1, self._max_dims, self._theta,
+                                       self._w_off[first:first + 1], recon=out[r0:r0 + rows], scratch=scratch)
+        return out
+
+    def _score(self, X, fitting):
+        per = self._distances(X)
+        return self._combine(per, fitting), per
+
+    def reconstruct(self, X, s):
+        """float32 [n, d_s]: the output of the net of subspace s on the rows of X, standardised by the fitted location_ and scale_."""
+        self._require_fit()
+        s = int(s)
+        if not 0 <= s < self.plan.count:
+            raise ValueError(f"no subspace {s}: {self.plan.count} subspaces")
+        return self._distances(_device_matrix(X, self.plan.d), only=s).cpu().numpy()
+
+    @property
+    def weights_(self):
+        """List of S lists of (W_l float32 [N_l, K_l], b_l float32 [N_l]), one pair per layer."""
+        self._require_fit()
+        if self._host_weights is None:
+            flat, out = self._theta.cpu().numpy(), []
+            for s, d_s in enumerate(self.plan.dims):
+                at, layers = int(self._w_off_host[s]), []
+                for K, N in ae_layer_sizes(d_s, self.hidden):
+                    layers.append((flat[at:at + K * N].reshape(K, N).T.copy(), flat[at + K * N:at + (K + 1) * N].copy()))
+                    at += (K + 1) * N
+                out.append(layers)
+            self._host_weights = out
+        return self._host_weights
+
+    def fit(self, X, y=None):
+        """Takes the column means and deviations of X, then chunk of subspaces by chunk initialises the nets and runs all epochs
+        (steps-per-launch by ae_launch_steps), and scores X through the trained nets: decision_scores_ (float64 [n]),
+        per_subspace_scores_, location_, scale_, loss_history_, n_steps_ and, on first use, weights_; with normalize also
+        score_center_ / score_scale_."""
+        n = _matrix_shape(X, self.plan.d)[0]
+        self._check_fit_rows(n)
+        batch = min(self.batch_size, n)
+        chunks = ae_chunks([ae_net_bytes(d_s, self.hidden, batch, self._max_dims) for d_s in self.plan.dims],
+                           self.workspace_bytes)  # raises before the device is touched
+        X = self._begin_fit(X)
+        dev = X.device
+        self._fitted, self._host_weights = False, None
+        mean, var = self._column_moments(X)
+        self.location_ = mean
+        with np.errstate(invalid="ignore"):
+            self.scale_ = np.where(var > 0.0, np.sqrt(var), 1.0)
+        self._scaling = (torch.as_tensor(self.location_, device=dev), torch.as_tensor(self.scale_, device=dev))
+        off = self.plan.feat_off
+        constant = np.array([not (var[self.plan.feat[off[s]:off[s + 1]]] != 0.0).any() for s in range(self.plan.count)])
+        self._skip = torch.as_tensor(constant.astype(np.int32), device=dev)
+        self._theta = torch.empty(int(self._w_off_host[-1]), dtype=torch.float32, device=dev)
+        steps = n // batch
+        self.n_steps_ = self.epochs * steps
+        loss = self._train(X, batch, chunks).cpu().numpy().astype(np.float64).reshape(self.plan.count, self.epochs, steps)
+        self.loss_history_ = np.cumsum(loss, axis=2)[:, :, -1] / steps  # cumsum adds in step order
+        scores, per = self._score(X, fitting=True)
         return self._publish(scores, per)
 
 

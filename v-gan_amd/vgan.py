@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import (SubspaceABOD, SubspaceCBLOF, SubspaceCOF, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
+from .outlier import (SubspaceABOD, SubspaceAutoEncoder, SubspaceCBLOF, SubspaceCOF, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
                       SubspaceINNE, SubspaceKPCA, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOD, SubspaceSOS)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
@@ -245,7 +245,12 @@ class _RunFolder:
         few landmark rows per subspace, the score the reconstruction error in feature space; sklearn's KernelPCA, pyod's
         KPCA): its keywords are n_components, gamma, max_samples, landmarks, eig_tol, max_sweeps, seed, engine, splits,
         workspace_bytes and the same normalize / combination / contamination, e.g.
-        outlier_ensemble(method="kpca", n_components=8, X=X); n_neighbors is not used there."""
+        outlier_ensemble(method="kpca", n_components=8, X=X); n_neighbors is not used there.
+        method "autoencoder" builds a SubspaceAutoEncoder (one small MLP per subspace trained on the device to reconstruct
+        the standardised rows through a bottleneck, the score the reconstruction distance; pyod's AutoEncoder without dropout
+        and batch normalisation): its keywords are hidden, activation ("relu" or "tanh"), epochs, batch_size, lr, beta1,
+        beta2, eps, weight_decay, seed, workspace_bytes and the same normalize / combination / contamination, e.g.
+        outlier_ensemble(method="autoencoder", hidden=(16, 2), activation="tanh", X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -280,6 +285,8 @@ class _RunFolder:
             ens = SubspaceDIF(self.subspaces, self.proba, **kw)
         elif method == "kpca":
             ens = SubspaceKPCA(self.subspaces, self.proba, **kw)
+        elif method == "autoencoder":
+            ens = SubspaceAutoEncoder(self.subspaces, self.proba, **kw)
         elif method == "sod":
             ens = SubspaceSOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
         else:
