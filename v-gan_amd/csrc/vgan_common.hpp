@@ -52,6 +52,11 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {

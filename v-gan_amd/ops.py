@@ -768,17 +768,20 @@ class HipOps:
                                               _ptr(feat), _ptr(feat_off), int(first), int(count), _ptr(idx), int(k), _ptr(score),
                                               _ptr(score_row), score.stride(0), self._stream()), "vgan_outlier_abod")
 
-    def outlier_abod_floor(self, score, score_floor, n_degenerate=None):
-        """n_degenerate given (fit): score_floor [S] and n_degenerate [S] are taken from score [S, n]; otherwise score_floor
-        is applied as stored.  Either way the NaN scores of row s become score_floor[s]."""
-        _mat(score, "score"), _vec(score_floor, "score_floor", torch.float64)
+    def _outlier_fill_degenerate(self, name, score, value, n_degenerate):
+        _mat(score, "score"), _vec(value, "value", torch.float64)
         S, n = score.shape
-        assert score_floor.numel() >= S
+        assert value.numel() >= S
         if n_degenerate is not None:
             _vec(n_degenerate, "n_degenerate", torch.int32)
             assert n_degenerate.numel() >= S
-        _lib.check(self.lib.vgan_outlier_abod_floor(_ptr(score), score.stride(0), S, n, int(n_degenerate is not None),
-                                                    _ptr(score_floor), _ptr(n_degenerate), self._stream()), "vgan_outlier_abod_floor")
+        _lib.check(getattr(self.lib, name)(_ptr(score), score.stride(0), S, n, int(n_degenerate is not None), _ptr(value),
+                                           _ptr(n_degenerate), self._stream()), name)
+
+    def outlier_abod_floor(self, score, score_floor, n_degenerate=None):
+        """n_degenerate given (fit): score_floor [S] and n_degenerate [S] are taken from score [S, n]; otherwise score_floor
+        is applied as stored.  Either way the NaN scores of row s become score_floor[s]."""
+        self._outlier_fill_degenerate("vgan_outlier_abod_floor", score, score_floor, n_degenerate)
 
     def outlier_cof_chain(self, Xq, Xr, table, first, count, idx, k, chain, ac_out):
         """Average chaining distances (COF) of the refined lists idx [count, nq, k] into ac_out, float64 [count, nq]; chain is
@@ -803,14 +806,7 @@ class HipOps:
     def outlier_cof_ceiling(self, score, score_ceiling, n_degenerate=None):
         """outlier_abod_floor with a maximum: n_degenerate given (fit) takes score_ceiling [S] and n_degenerate [S] from score
         [S, n]; either way the NaN scores of row s become score_ceiling[s]."""
-        _mat(score, "score"), _vec(score_ceiling, "score_ceiling", torch.float64)
-        S, n = score.shape
-        assert score_ceiling.numel() >= S
-        if n_degenerate is not None:
-            _vec(n_degenerate, "n_degenerate", torch.int32)
-            assert n_degenerate.numel() >= S
-        _lib.check(self.lib.vgan_outlier_cof_ceiling(_ptr(score), score.stride(0), S, n, int(n_degenerate is not None),
-                                                     _ptr(score_ceiling), _ptr(n_degenerate), self._stream()), "vgan_outlier_cof_ceiling")
+        self._outlier_fill_degenerate("vgan_outlier_cof_ceiling", score, score_ceiling, n_degenerate)
 
     def outlier_score_stats(self, score, mode, center, scale):
         """center / scale (float64 [S]) of the rows of score [S, n]; mode is a VGAN_OUTLIER_NORM_* value."""

@@ -546,6 +546,17 @@ class _NeighborScorer(_SubspaceScorer):
             D[rows], I[rows] = dist, idx
         return D.cpu().numpy(), I.cpu().numpy()
 
+    def _fill_degenerate(self, per, fitting, op):
+        """Puts the fill value of each subspace into the NaN (degenerate) scores of per [S, n] with op, the detector's
+        ops.outlier_*_floor / _ceiling.  Fitting, op takes the fill values (_fill, float64 [S]) and the NaN counts
+        (_n_degenerate, int32 [S]) from per; otherwise it applies the stored _fill.  Both are in processing order."""
+        if fitting:
+            self._fill = torch.empty(self.plan.count, dtype=torch.float64, device=per.device)
+            self._n_degenerate = torch.empty(self.plan.count, dtype=torch.int32, device=per.device)
+            op(per, self._fill, self._n_degenerate)
+        else:
+            op(per, self._fill)
+
 
 class SubspaceEnsemble(_NeighborScorer):
     """kNN / LOF / KDE detector per subspace, probability-weighted sum of the scores (pyod-style: ``fit`` sets
@@ -690,12 +701,7 @@ class SubspaceABOD(_NeighborScorer):
         for first, count, idx, _ in self._neighbors(Xq):
             self.ops.outlier_abod(self._X if Xq is None else Xq, self._X, self._table, first, count, idx, k, per,
                                   self._rows[first:first + count])
-        if fitting:
-            self._floor = torch.empty(self.plan.count, dtype=torch.float64, device=dev)
-            self._n_degenerate = torch.empty(self.plan.count, dtype=torch.int32, device=dev)
-            self.ops.outlier_abod_floor(per, self._floor, self._n_degenerate)
-        else:
-            self.ops.outlier_abod_floor(per, self._floor)
+        self._fill_degenerate(per, fitting, self.ops.outlier_abod_floor)
         return self._combine(per, fitting), per
 
     def fit(self, X, y=None):
@@ -703,7 +709,7 @@ class SubspaceABOD(_NeighborScorer):
         per_subspace_scores_, score_floor_, n_degenerate_; with normalize also score_center_ / score_scale_."""
         self._X = self._begin_fit(X)
         scores, per = self._score(None, fitting=True)
-        self.score_floor_ = self._floor.cpu().numpy()
+        self.score_floor_ = self._fill.cpu().numpy()
         self.n_degenerate_ = self._n_degenerate.cpu().numpy().astype(np.int64)
         return self._publish(scores, per)
 
@@ -783,12 +789,7 @@ class SubspaceCOF(_NeighborScorer):
             self.ops.outlier_cof_chain(self._X if Xq is None else Xq, self._X, self._table, first, count, idx, k,
                                        COF_CHAINS[self.chain], ac)
             self.ops.outlier_cof_score(ac, ac_ref, idx, k, per, self._rows[first:first + count])
-        if fitting:
-            self._ceiling = torch.empty(self.plan.count, dtype=torch.float64, device=dev)
-            self._n_degenerate = torch.empty(self.plan.count, dtype=torch.int32, device=dev)
-            self.ops.outlier_cof_ceiling(per, self._ceiling, self._n_degenerate)
-        else:
-            self.ops.outlier_cof_ceiling(per, self._ceiling)
+        self._fill_degenerate(per, fitting, self.ops.outlier_cof_ceiling)
         return self._combine(per, fitting), per
 
     def fit(self, X, y=None):
@@ -798,7 +799,7 @@ class SubspaceCOF(_NeighborScorer):
         self._ac = torch.empty(self.plan.count, X.shape[0], dtype=torch.float64, device=X.device)
         scores, per = self._score(None, fitting=True)
         self.ac_dist_ = self._ac[torch.as_tensor(self.plan.given, device=X.device)].cpu().numpy()
-        self.score_ceiling_ = self._ceiling.cpu().numpy()
+        self.score_ceiling_ = self._fill.cpu().numpy()
         self.n_degenerate_ = self._n_degenerate.cpu().numpy().astype(np.int64)
         return self._publish(scores, per)
 
