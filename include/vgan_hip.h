@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1068,6 +1068,54 @@ int vgan_ae_scores(const float* X, int ldx, int rows, int d, const int32_t* feat
                    const double* scale, const int32_t* skip, int first, int count, int max_dims, int n_hidden,
                    const int32_t* hidden, int activation, const float* state, const int64_t* s_off, float* score,
                    int64_t ld_score, float* recon, float* scratch, int64_t scratch_floats, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Deep SVDD one-class scores (Ruff et al. 2018; pyod's DeepSVDD, the one-class objective): one encoder per subspace of the
+ * table (feat, feat_off), trained to map the standardised rows onto one point c, scored by the squared distance of a row's
+ * image from c (v-gan_amd/outlier.py: SubspaceDeepSVDD, whose docstring is the definition; kernels in csrc/outlier_svdd.hip,
+ * the layer routines of csrc/outlier_mlp.hpp shared with the autoencoder).  BLOCK b is the subspace at position b.  Its net
+ * has the layer sizes K_0 = d_s, hidden[0 .. n_hidden - 1] (n_hidden layers), NO BIAS, the activation after every layer but
+ * the last; q = hidden[n_hidden - 1] <= VGAN_SVDD_MAX_OUT is the output dimension.  The limits, z, skip, the activations, the
+ * batches, corr, Adam and the scratch rule are those of the vgan_ae_* entries (VGAN_AE_*).
+ * The STATE of block first + z starts at state + s_off[z] and holds theta, m and v, P = sum_l K_l N_l floats each; inside
+ *   each, layer after layer, W_l K-MAJOR [K_l][N_l] (W_l[o, i] at i N_l + o).
+ * vgan_svdd_init: zeroes state[0 .. total) and writes theta: W_l[o, i] = float32((2 u - 1) c_l) by the rule of vgan_ae_init with
+ *   the counter word 2 = VGAN_SVDD_PHILOX_TAG + l, e = o K_l + i; c_l = scale[b n_hidden + l].
+ * vgan_svdd_center: the forward of the nets over the rows of X [rows, d], one workgroup per (block, VGAN_AE_ROW_TILE rows),
+ *   which writes the float64 sum over its rows (ascending) of every output coordinate to tile_sums [count, tiles, q]
+ *   (tile_cells >= count tiles q); then run_sums [count, q] (float64, zeroed by the caller before the first call) += the tile
+ *   sums in tile order.  n_total = 0: more rows follow (every call but the last passes a multiple of VGAN_AE_ROW_TILE rows).
+ *   n_total > 0, the last call: mean = run_sums / n_total; where center_eps > 0 and |mean| < center_eps the coordinate becomes
+ *   -center_eps when mean < 0 and +center_eps otherwise; center [count, q] = float32 of it, n_clamped int32 [count] the number
+ *   of coordinates the rule moved.  A block with skip = 1 gets a centre of zeros and n_clamped 0.
+ * vgan_svdd_train: as vgan_ae_train with r = out - center[z_block], the float32 loss sum r^2 / batch into loss[z_block ld_loss +
+ *   g] (before the update) and the output error r float32(2 / batch).  The activations of the batch stay in LDS when batch
+ *   ((max_dims | 1) + sum (h | 1) + (max h | 1)) <= VGAN_AE_LDS_FLOATS; otherwise scratch holds them.
+ * vgan_svdd_scores: score[z ld_score + i] = float32(sum_j double(out_ij - center_zj)^2), j ascending, the difference float32.
+ *   embed != NULL (count must be 1): float32 [rows, q] receives the raw output instead; center and score may be NULL.
+ *   scratch as above with VGAN_AE_ROW_TILE ((max_dims | 1) + sum (h | 1)) floats per (block, row tile).
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_SVDD_MAX_OUT 128 /* VGAN_AE_MAX_WIDTH */
+#define VGAN_SVDD_PHILOX_TAG 1398162432 /* 0x53564400 */
+int vgan_svdd_init(const int32_t* feat_off, int first, int count, int n_hidden, const int32_t* hidden, const double* scale,
+                   uint64_t seed, float* state, const int64_t* s_off, int64_t total, vgan_stream_t stream);
+int vgan_svdd_center(const float* X, int ldx, int rows, int d, const int32_t* feat, const int32_t* feat_off, const double* mean,
+                     const double* scale, const int32_t* skip, int first, int count, int max_dims, int n_hidden,
+                     const int32_t* hidden, int activation, const float* state, const int64_t* s_off, double* tile_sums,
+                     int64_t tile_cells, double* run_sums, int64_t n_total, double center_eps, float* center,
+                     int32_t* n_clamped, float* scratch, int64_t scratch_floats, vgan_stream_t stream);
+int vgan_svdd_train(const float* X, int ldx, int n, int d, const int32_t* feat, const int32_t* feat_off, const double* mean,
+                    const double* scale, const int32_t* skip, int first, int count, int max_dims, int n_hidden,
+                    const int32_t* hidden, int activation, int batch, uint64_t seed, int64_t step_first, int step_count,
+                    const double* corr, double lr, double beta1, double beta2, double eps, double weight_decay,
+                    const float* center, float* state, const int64_t* s_off, float* loss, int64_t ld_loss, float* scratch,
+                    int64_t scratch_floats, vgan_stream_t stream);
+int vgan_svdd_scores(const float* X, int ldx, int rows, int d, const int32_t* feat, const int32_t* feat_off, const double* mean,
+                     const double* scale, const int32_t* skip, int first, int count, int max_dims, int n_hidden,
+                     const int32_t* hidden, int activation, const float* state, const int64_t* s_off, const float* center,
+                     float* score, int64_t ld_score, float* embed, float* scratch, int64_t scratch_floats,
+                     vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * iNNE, isolation by nearest-neighbour ensembles (Bandaragoda, Ting, Albrecht, Liu, Wells 2018; pyod's INNE): T estimators

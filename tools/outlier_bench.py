@@ -109,6 +109,12 @@ difference of the two paths' ensemble scores.
     padded torch.bmm batches (all S nets in one [S, B, d_max] batch, the padded outputs masked, torch.optim.Adam with the
     same weight decay, one torch.randperm per epoch) for a sample of the steps, scaled to all of them; and the LOF fit (k =
     20) on the same rows.
+  --method deepsvdd: Deep SVDD encoders (vgan_amd.SubspaceDeepSVDD at its defaults: d_s -> 64 -> 32 without bias, relu, 100
+    epochs of batches of 32, Adam) on the shapes of --method ae: fit and decision_function; one fit split into scaling,
+    centre (init plus the forward over all rows and the fold), training (microseconds per optimiser step) and scoring,
+    each behind a synchronisation; IN THE SAME RUN SubspaceAutoEncoder with hidden (64, 32) on the same rows (fit, training,
+    microseconds per step) and the LOF fit (k = 20); and the same encoders trained in torch on the GPU as padded torch.bmm
+    batches with torch.optim.Adam for a sample of the steps.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1743,6 +1749,93 @@ def run_ae(d, n, count, reps, baselines=True, torch_steps=300):
     return row
 
 
+def svdd_torch_bmm(Xd, ens, steps):
+    """Seconds per optimiser step of the encoders of ens trained in torch on the GPU: every layer one torch.bmm over all S
+    nets (no bias), the first layer padded to the widest subspace (the padded inputs are zero), relu, the sum over the nets
+    of the batch mean of |out - c|^2, torch.optim.Adam(weight_decay=); `steps` steps are timed after 20 warm ones."""
+    dev, S, dims = Xd.device, ens.plan.count, ens.plan.dims
+    n, dmax, B = Xd.shape[0], int(dims.max()), min(ens.batch_size, Xd.shape[0])
+    mean, sd = ens._scaling
+    Z = ((Xd.double() - mean) / sd).float()
+    z = torch.zeros(S, n, dmax, device=dev)
+    for s in range(S):
+        f = torch.as_tensor(ens.plan.feat[ens.plan.feat_off[s]:ens.plan.feat_off[s + 1]].astype(np.int64), device=dev)
+        z[s, :, :len(f)] = Z[:, f]
+    widths = [dmax] + list(ens.hidden)
+    params = [((torch.rand(S, K, N, device=dev) * 2 - 1) / np.sqrt(K)).requires_grad_() for K, N in zip(widths[:-1], widths[1:])]
+    center = ens._center[:, None, :]
+    opt = torch.optim.Adam(params, lr=ens.lr, betas=(ens.beta1, ens.beta2), eps=ens.eps, weight_decay=ens.weight_decay)
+    per_epoch = n // B
+
+    def run(count):
+        perm = None
+        for g in range(count):
+            if g % per_epoch == 0:
+                perm = torch.randperm(n, device=dev)
+            i = g % per_epoch
+            h = z[:, perm[i * B:(i + 1) * B]]
+            for l, W in enumerate(params):
+                h = torch.bmm(h, W)
+                if l + 1 < len(params):
+                    h = torch.relu(h)
+            loss = ((h - center) ** 2).sum() / B
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+
+    run(20)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    run(steps)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps
+
+
+def run_svdd(d, n, count, reps, baselines=True, torch_steps=300):
+    from vgan_amd.outlier import ae_chunks, ae_launch_steps, ae_net_bytes, svdd_net_bytes
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceDeepSVDD(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    batch = min(ens.batch_size, n)
+    chunks = ae_chunks([svdd_net_bytes(d_s, ens.hidden, batch, ens._max_dims) for d_s in ens.plan.dims], ens.workspace_bytes, "SubspaceDeepSVDD")
+    t_scale, _ = timed(lambda: ens._column_moments(Xd), reps)
+    t_all, tt = timed(lambda: ens._train(Xd, batch, chunks), reps)  # init, centre and every training launch
+    epochs, ens.epochs = ens.epochs, 0
+    t_center, _ = timed(lambda: ens._train(Xd, batch, chunks), reps)  # init and centre alone
+    ens.epochs = epochs
+    t_train = t_all - t_center
+    t_score, _ = timed(lambda: ens._score(Xd, False), reps)
+    params = int(ens._params.sum())
+    row = {"method": "deepsvdd", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "hidden": list(ens.hidden), "activation": ens.activation,
+           "epochs": ens.epochs, "batch_size": batch, "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)),
+           "d_s_max": int(dims.max()), "parameters": params, "n_steps": ens.n_steps_, "chunks": len(chunks),
+           "steps_per_launch": ae_launch_steps(int(ens._params.max()), batch),
+           "fit_s": round(t_fit, 5), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td,
+           "scaling_s": round(t_scale, 6), "center_s": round(t_center, 6), "training_s": round(t_train, 5), "center_plus_training_reps_s": tt,
+           "scoring_s": round(t_score, 6), "training_us_per_step": round(t_train / ens.n_steps_ * 1e6, 2),
+           "n_clamped_mean": float(ens.n_clamped_.mean()),
+           "loss_first_epoch_mean": float(ens.loss_history_[:, 0].mean()), "loss_last_epoch_mean": float(ens.loss_history_[:, -1].mean())}
+    ae = vgan_amd.SubspaceAutoEncoder(m, p, hidden=ens.hidden)
+    t_ae_fit, taf = timed(lambda: ae.fit(Xd), reps)
+    ae_chunk = ae_chunks([ae_net_bytes(d_s, ae.hidden, batch, ae._max_dims) for d_s in ae.plan.dims], ae.workspace_bytes)
+    t_ae_train, tat = timed(lambda: ae._train(Xd, batch, ae_chunk), reps)
+    row.update({"ae_fit_s": round(t_ae_fit, 5), "ae_fit_reps_s": taf, "ae_training_s": round(t_ae_train, 5), "ae_training_reps_s": tat,
+                "ae_training_us_per_step": round(t_ae_train / ae.n_steps_ * 1e6, 2),
+                "step_time_over_ae": round(t_train / ens.n_steps_ / (t_ae_train / ae.n_steps_), 3)})
+    lof = vgan_amd.SubspaceEnsemble(m, p, method="lof", n_neighbors=20)
+    t_lof, tl = timed(lambda: lof.fit(Xd), reps)
+    row.update({"lof_k20_fit_s": round(t_lof, 5), "lof_k20_fit_reps_s": tl, "deepsvdd_over_lof_fit": round(t_fit / t_lof, 1)})
+    if baselines:
+        t_step = svdd_torch_bmm(Xd, ens, torch_steps)
+        row.update({"torch_bmm_steps_timed": torch_steps, "torch_bmm_us_per_step": round(t_step * 1e6, 2),
+                    "torch_bmm_training_s": round(t_step * ens.n_steps_, 3),
+                    "training_speedup_vs_torch_bmm": round(t_step * ens.n_steps_ / t_train, 2)})
+    return row
+
+
 def run_sod(d, n, count, k, ref_set, alpha, reps):
     """SubspaceSOD fit and decision_function (the training rows as new rows), the fit split into its stages on the resident
     lists, beside the LOF fit with the same n_neighbors on the same rows in the same run."""
@@ -1797,13 +1890,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / kpca / ae: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / kpca / ae / deepsvdd: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / sod / kpca / ae: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / sod / kpca / ae / deepsvdd: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -1964,6 +2057,14 @@ def main():
             shapes = [tuple(int(v) for v in args.shape.split(","))]
         for d, n, count in shapes:
             out["configs"].append(run_ae(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "deepsvdd":
+        shapes = [(20, 500, 8)] if args.quick else [(784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_svdd(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "gmm":

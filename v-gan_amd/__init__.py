@@ -9,10 +9,11 @@ from .modules import (Generator_big, upper_softmax, Encoder, Decoder, Detector, 
                       MMDLossConstrained)
 from .vgan import VGAN, VGAN_no_kl  # noqa: F401
 from .outlier import (SubspaceEnsemble, SubspaceCBLOF, SubspaceABOD, SubspaceECOD, SubspaceIForest, SubspaceMahalanobis,  # noqa: F401
-                      SubspaceGMM, SubspaceHBOS, SubspaceLODA, SubspacePCA, SubspaceOCSVM, SubspaceCOF, SubspaceINNE, SubspaceSOS, SubspaceDIF, SubspaceSOD, SubspaceAutoEncoder,
+                      SubspaceGMM, SubspaceHBOS, SubspaceLODA, SubspacePCA, SubspaceOCSVM, SubspaceCOF, SubspaceINNE, SubspaceSOS, SubspaceDIF, SubspaceSOD, SubspaceAutoEncoder, SubspaceDeepSVDD,
                       SubspaceKPCA)
 
 __all__ = ["VGAN", "VGAN_no_kl", "Generator_big", "upper_softmax", "Encoder", "Decoder", "Detector", "RBF",
            "MMDLossConstrained", "SubspaceEnsemble", "SubspaceCBLOF", "SubspaceABOD", "SubspaceECOD", "SubspaceIForest",
            "SubspaceMahalanobis", "SubspaceGMM", "SubspaceHBOS", "SubspaceLODA", "SubspacePCA", "SubspaceOCSVM",
-           "SubspaceCOF", "SubspaceINNE", "SubspaceSOS", "SubspaceDIF", "SubspaceSOD", "SubspaceKPCA", "SubspaceAutoEncoder", "lib"]
+           "SubspaceCOF", "SubspaceINNE", "SubspaceSOS", "SubspaceDIF", "SubspaceSOD", "SubspaceKPCA", "SubspaceAutoEncoder", "SubspaceDeepSVDD",
+           "lib"]

@@ -180,6 +180,12 @@ SIGNATURES = {
     "vgan_ae_train": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _u64, _i64, _i, _p, _d, _d, _d, _d, _d, _p, _p,
                            _p, _i64, _p, _i64, _p]),
     "vgan_ae_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i64, _p, _p, _i64, _p]),
+    "vgan_svdd_init": (_i, [_p, _i, _i, _i, _p, _p, _u64, _p, _p, _i64, _p]),
+    "vgan_svdd_center": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i64, _p, _i64, _d, _p, _p, _p, _i64,
+                              _p]),
+    "vgan_svdd_train": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _u64, _i64, _i, _p, _d, _d, _d, _d, _d, _p, _p,
+                             _p, _p, _i64, _p, _i64, _p]),
+    "vgan_svdd_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i64, _p, _p, _i64, _p]),
     "vgan_inne_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p, _p, _p, _p]),
     "vgan_inne_scores": (_i, [_p, _i, _i, _i, _p, _i, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]),
     "vgan_maha_moments": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _i64, _p, _p, _p, _p, _i64, _p]),
@@ -211,7 +217,7 @@ SIGNATURES = {
     "vgan_kpca_scores": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
-ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_ae_* ones last) leave it
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_svdd_* ones last) leave it
 _lib = None
 
 

@@ -1150,6 +1150,98 @@ class HipOps:
                                            _ptr(score), int(ld_score), _ptr(recon), _ptr(scratch),
                                            scratch.numel() if scratch is not None else 0, self._stream()), "vgan_ae_scores")
 
+    # ---- Deep SVDD encoders over subspaces (vgan_amd.outlier.SubspaceDeepSVDD) -----------------------------------
+    # net: (hidden tuple, activation code), q = hidden[-1]; state as the autoencoder's without the bias rows (P = sum K_l N_l);
+    # center float32 [count, q] on the device
+    def svdd_init(self, feat_off, net, first, count, scale, seed, state, s_off, total):
+        """state float32 [>= total]: zeroed (the moments), then the Philox weights of the blocks first .. first + count - 1;
+        scale float64 [S, L]: c_l = 1 / sqrt(K_l) per subspace."""
+        _vec(feat_off, "feat_off", torch.int32), _vec(scale, "scale", torch.float64), _vec(state, "state"), _vec(s_off, "s_off", torch.int64)
+        hidden, _ = net
+        assert state.numel() >= total and s_off.numel() >= count and first + count <= feat_off.numel() - 1
+        assert scale.numel() >= (feat_off.numel() - 1) * len(hidden)
+        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
+        _lib.check(self.lib.vgan_svdd_init(_ptr(feat_off), int(first), int(count), len(hidden), harr, _ptr(scale), int(seed), _ptr(state),
+                                           _ptr(s_off), int(total), self._stream()), "vgan_svdd_init")
+
+    def svdd_center(self, X, table, scaling, skip, net, first, count, max_dims, state, s_off, tile_sums, run_sums, n_total, center_eps,
+                    center, n_clamped, scratch=None):
+        """Adds the output sums of the rows of X (a multiple of 32 rows in every call but the last), tile by tile, to run_sums
+        float64 [count, q] (zeroed by the caller before the first call); n_total > 0 marks the last call, which writes center
+        float32 [count, q] (mean, center_eps rule) and n_clamped int32 [count].  tile_sums: float64 workspace [>= count tiles q]."""
+        _mat(X, "X"), _vec(skip, "skip", torch.int32), _vec(state, "state"), _vec(s_off, "s_off", torch.int64)
+        _vec(tile_sums, "tile_sums", torch.float64), _vec(run_sums, "run_sums", torch.float64)
+        _vec(center, "center"), _vec(n_clamped, "n_clamped", torch.int32)
+        feat, feat_off, _ = table
+        mean, scale = scaling
+        _vec(mean, "mean", torch.float64), _vec(scale, "scale", torch.float64)
+        rows, d = X.shape
+        hidden, act = net
+        q = hidden[-1]
+        assert mean.numel() == d and scale.numel() == d and first + count <= feat_off.numel() - 1 <= skip.numel() and s_off.numel() >= count
+        assert run_sums.numel() >= count * q and center.numel() >= count * q and n_clamped.numel() >= count
+        if scratch is not None:
+            _vec(scratch, "scratch")
+        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
+        _lib.check(self.lib.vgan_svdd_center(_ptr(X), X.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
+                                             int(first), int(count), int(max_dims), len(hidden), harr, int(act), _ptr(state), _ptr(s_off),
+                                             _ptr(tile_sums), tile_sums.numel(), _ptr(run_sums), int(n_total), float(center_eps),
+                                             _ptr(center), _ptr(n_clamped), _ptr(scratch),
+                                             scratch.numel() if scratch is not None else 0, self._stream()), "vgan_svdd_center")
+
+    def svdd_train(self, X, table, scaling, skip, net, first, count, max_dims, batch, seed, step_first, corr, adam, center, state, s_off,
+                   loss, scratch=None):
+        """ae_train's arguments and center float32 [count, q]: the global steps step_first .. step_first + len(corr) - 1 of the
+        one-class objective, in place; loss float32 [count, >= step_first + steps]."""
+        _mat(X, "X"), _vec(skip, "skip", torch.int32), _vec(corr, "corr", torch.float64), _vec(state, "state")
+        _vec(s_off, "s_off", torch.int64), _mat(loss, "loss"), _vec(center, "center")
+        feat, feat_off, _ = table
+        mean, scale = scaling
+        _vec(mean, "mean", torch.float64), _vec(scale, "scale", torch.float64)
+        n, d = X.shape
+        hidden, act = net
+        steps = corr.shape[0]
+        assert corr.dim() == 2 and corr.shape[1] == 2 and mean.numel() == d and scale.numel() == d
+        assert first + count <= feat_off.numel() - 1 <= skip.numel() and s_off.numel() >= count and loss.shape[0] >= count
+        assert center.numel() >= count * hidden[-1]
+        if scratch is not None:
+            _vec(scratch, "scratch")
+        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
+        lr, beta1, beta2, eps, weight_decay = adam
+        _lib.check(self.lib.vgan_svdd_train(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
+                                            int(first), int(count), int(max_dims), len(hidden), harr, int(act), int(batch), int(seed),
+                                            int(step_first), int(steps), _ptr(corr), float(lr), float(beta1), float(beta2), float(eps),
+                                            float(weight_decay), _ptr(center), _ptr(state), _ptr(s_off), _ptr(loss),
+                                            loss.stride(0) if count > 1 else loss.shape[1], _ptr(scratch),
+                                            scratch.numel() if scratch is not None else 0, self._stream()), "vgan_svdd_train")
+
+    def svdd_scores(self, X, table, scaling, skip, net, first, count, max_dims, state, s_off, center=None, score=None, embed=None,
+                    scratch=None):
+        """score float32 [count, >= rows] (a view into the score matrix may be given): the squared distances of the images of
+        the rows of X from center [count, q]; with embed (float32 [rows, q], count 1) the raw output of the net instead."""
+        _mat(X, "X"), _vec(skip, "skip", torch.int32), _vec(state, "state"), _vec(s_off, "s_off", torch.int64)
+        feat, feat_off, _ = table
+        mean, scale = scaling
+        _vec(mean, "mean", torch.float64), _vec(scale, "scale", torch.float64)
+        rows, d = X.shape
+        hidden, act = net
+        assert mean.numel() == d and scale.numel() == d and first + count <= feat_off.numel() - 1 <= skip.numel() and s_off.numel() >= count
+        ld_score = 0
+        if embed is not None:
+            _vec(embed, "embed")
+            assert count == 1 and embed.numel() >= rows * hidden[-1]
+        else:
+            _mat(score, "score"), _vec(center, "center")
+            assert score.shape[0] >= count and score.shape[1] >= rows and center.numel() >= count * hidden[-1]
+            ld_score = score.stride(0) if score.shape[0] > 1 else score.shape[1]
+        if scratch is not None:
+            _vec(scratch, "scratch")
+        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
+        _lib.check(self.lib.vgan_svdd_scores(_ptr(X), X.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
+                                             int(first), int(count), int(max_dims), len(hidden), harr, int(act), _ptr(state), _ptr(s_off),
+                                             _ptr(center), _ptr(score), int(ld_score), _ptr(embed), _ptr(scratch),
+                                             scratch.numel() if scratch is not None else 0, self._stream()), "vgan_svdd_scores")
+
     # ---- iNNE over subspaces (vgan_amd.outlier.SubspaceINNE) -----------------------------------------------
     # state: (rows int32, r2 float64, nn int32, rho float64), each [S, T, psi]
     def inne_build(self, X, table, first, count, max_dims, ratio, seed, state):

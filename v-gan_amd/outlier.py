@@ -112,6 +112,12 @@ standardised rows through a bottleneck, one workgroup owning one net for many op
 distance as the score (csrc/outlier_ae.hip).  Its contract (scaling, the net and its initial draw, the batches, the float32
 operation sequence of a step, the score, determinism, what is not built) is that class's docstring.
 
+``SubspaceDeepSVDD`` is the deep one-class detector: one small encoder without bias per subspace trained by the same loop to map
+the standardised rows onto one centre, the squared distance of a row's image from the centre as the score
+(csrc/outlier_svdd.hip, on the layer routines of csrc/outlier_mlp.hpp that the autoencoder uses with a bias).  Its contract
+(the net, the centre and its center_eps rule, the step, the score, the collapse of bounded activations, what is not built)
+is that class's docstring.
+
 ``SubspaceHBOS`` and ``SubspaceLODA`` are the histogram detectors, linear in n: equal-width histograms (numpy.linspace's
 edges, numpy.histogram's counts, exact integer sums) of every feature (HBOS: -log2 densities summed over a subspace's
 features, the dense float64 product of ``SubspaceECOD``) or of sparse random projections of every subspace (LODA: the mean
@@ -3730,14 +3736,15 @@ def ae_net_bytes(d_s, hidden, batch, max_dims=None):
     return 12 * ae_param_count(d_s, hidden) + (4 * act if act > AE_LDS_FLOATS else 0)
 
 
-def ae_chunks(net_bytes, workspace_bytes):
+def ae_chunks(net_bytes, workspace_bytes, owner="SubspaceAutoEncoder"):
     """[(first, count)]: consecutive runs of nets whose training state fits workspace_bytes, at most 65535 each; every chunk
-    trains to the end before the next begins.  ValueError, naming the bytes, when one net alone does not fit."""
+    trains to the end before the next begins.  ValueError, naming the bytes (and the owner class), when one net alone does
+    not fit."""
     out, first, ws = [], 0, int(workspace_bytes)
     sizes = [int(v) for v in net_bytes]
     for s, need in enumerate(sizes):
         if need > ws:
-            raise ValueError(f"SubspaceAutoEncoder needs {need} bytes of workspace for the net of subspace {s} with its moments, "
+            raise ValueError(f"{owner} needs {need} bytes of workspace for the net of subspace {s} with its moments, "
                              f"workspace_bytes is {ws}")
     while first < len(sizes):
         end, used = first, 0
@@ -3768,7 +3775,7 @@ class SubspaceAutoEncoder(_SubspaceScorer):
     it and by none of the linear detectors.  All S nets train at once, one workgroup per net running many optimiser steps
     per launch.  The defaults are pyod's as remembered (hidden [64, 32], relu, 100 epochs, batch 32, Adam lr 1e-3, weight
     decay 1e-5).  Not built: dropout and batch normalisation (pyod's defaults use both), a validation split and early
-    stopping, other optimisers and losses, several nets per subspace, a VAE, DeepSVDD.
+    stopping, other optimisers and losses, several nets per subspace, a VAE.  The deep one-class objective is SubspaceDeepSVDD.
 
     Sizes.  X is cast to float32.  hidden: 1 to 3 encoder widths, each 1 .. 128; activation "relu" or "tanh"; batch_size 1 ..
     256; epochs >= 0; 0 <= beta1, beta2 < 1; eps > 0; lr, weight_decay >= 0; seed in [0, 2^64); a subspace has at most 1024
@@ -3881,6 +3888,18 @@ class SubspaceAutoEncoder(_SubspaceScorer):
             self.ops.maha_moments(X, table, first, count, count, 1, tiles, None, hcount, mean, var, ws)
         return mean.cpu().numpy(), var.cpu().numpy()
 
+    def _fit_scaling(self, X):
+        """location_, scale_ (sd 1 for a constant column), their device copies and the flags of the constant subspaces."""
+        dev = X.device
+        mean, var = self._column_moments(X)
+        self.location_ = mean
+        with np.errstate(invalid="ignore"):
+            self.scale_ = np.where(var > 0.0, np.sqrt(var), 1.0)
+        self._scaling = (torch.as_tensor(self.location_, device=dev), torch.as_tensor(self.scale_, device=dev))
+        off = self.plan.feat_off
+        self._constant = np.array([not (var[self.plan.feat[off[s]:off[s + 1]]] != 0.0).any() for s in range(self.plan.count)])
+        self._skip = torch.as_tensor(self._constant.astype(np.int32), device=dev)
+
     def _train(self, X, batch, chunks):
         """Trains every chunk of nets to the end; the weights go to _theta, the step losses to the returned [S, steps] matrix."""
         n, dev = X.shape[0], X.device
@@ -3974,19 +3993,307 @@ class SubspaceAutoEncoder(_SubspaceScorer):
         X = self._begin_fit(X)
         dev = X.device
         self._fitted, self._host_weights = False, None
-        mean, var = self._column_moments(X)
-        self.location_ = mean
-        with np.errstate(invalid="ignore"):
-            self.scale_ = np.where(var > 0.0, np.sqrt(var), 1.0)
-        self._scaling = (torch.as_tensor(self.location_, device=dev), torch.as_tensor(self.scale_, device=dev))
-        off = self.plan.feat_off
-        constant = np.array([not (var[self.plan.feat[off[s]:off[s + 1]]] != 0.0).any() for s in range(self.plan.count)])
-        self._skip = torch.as_tensor(constant.astype(np.int32), device=dev)
+        self._fit_scaling(X)
         self._theta = torch.empty(int(self._w_off_host[-1]), dtype=torch.float32, device=dev)
         steps = n // batch
         self.n_steps_ = self.epochs * steps
         loss = self._train(X, batch, chunks).cpu().numpy().astype(np.float64).reshape(self.plan.count, self.epochs, steps)
         self.loss_history_ = np.cumsum(loss, axis=2)[:, :, -1] / steps  # cumsum adds in step order
+        scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)
+
+
+# ---- Deep SVDD: one small encoder per subspace, trained on the device onto one point, the squared distance as the score ----------
+SVDD_MAX_OUT = 128  # VGAN_SVDD_MAX_OUT: the output dimension q = hidden[-1] (AE_MAX_WIDTH)
+SVDD_PHILOX_TAG = 0x53564400  # VGAN_SVDD_PHILOX_TAG: counter word 2 of an initial draw is SVDD_PHILOX_TAG + layer
+
+
+def check_svdd_hidden(hidden):
+    """A tuple of 1 to AE_MAX_HIDDEN layer widths, each 1 .. AE_MAX_WIDTH; the last is the output dimension q."""
+    return check_ae_hidden(hidden)
+
+
+def check_svdd_center(center, center_eps, count, q):
+    """(center, center_eps): center None or a float32 [count, q] array built from a real array [q] (every subspace) or
+    [count, q]; center_eps a finite number >= 0."""
+    if not (_is_real(center_eps) and 0.0 <= float(center_eps) < float("inf")):
+        raise ValueError(f"center_eps must be a non-negative number, got {center_eps!r}")
+    if center is None:
+        return None, float(center_eps)
+    try:
+        c = np.asarray(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"center must be None or a real array of shape ({q},) or ({count}, {q})") from None
+    if c.shape == (q,):
+        c = np.broadcast_to(c, (count, q))
+    if c.shape != (count, q):
+        raise ValueError(f"center must be None or a real array of shape ({q},) or ({count}, {q}), got shape {np.shape(center)}")
+    return np.ascontiguousarray(c, dtype=np.float32), float(center_eps)
+
+
+def svdd_layer_sizes(d_s, hidden):
+    """[(K_l, N_l)] of the encoder of a subspace of d_s features: d_s, h_1 .. h_L."""
+    widths = [int(d_s)] + [int(w) for w in hidden]
+    return list(zip(widths[:-1], widths[1:]))
+
+
+def svdd_param_count(d_s, hidden):
+    """P: the parameters of one net, sum_l K_l N_l (no bias)."""
+    return sum(K * N for K, N in svdd_layer_sizes(d_s, hidden))
+
+
+def svdd_act_floats(d_s, hidden, rows, train):
+    """The float32 cells of the activations of `rows` rows (pitches are widths | 1): z and every layer's output and, when
+    training, one passed-down error of the widest layer (csrc/outlier_svdd.hip)."""
+    per_row = (int(d_s) | 1) + sum(int(w) | 1 for w in hidden) + ((max(hidden) | 1) if train else 0)
+    return per_row * int(rows)
+
+
+def svdd_net_bytes(d_s, hidden, batch, max_dims=None):
+    """The bytes one net needs while it trains: theta, m and v (12 P) and, when the activations of a batch of the widest
+    subspace (max_dims, default d_s) do not fit AE_LDS_FLOATS, its slice of the scratch buffer."""
+    act = svdd_act_floats(d_s if max_dims is None else max_dims, hidden, batch, True)
+    return 12 * svdd_param_count(d_s, hidden) + (4 * act if act > AE_LDS_FLOATS else 0)
+
+
+class SubspaceDeepSVDD(_SubspaceScorer):
+    """Deep SVDD per subspace (Ruff et al., ICML 2018, the one-class objective; pyod's ``DeepSVDD``), combined like the other
+    detectors of this module: a small encoder WITHOUT BIAS is trained to map the standardised rows of the subspace onto one
+    point c, and a row is scored by the squared distance of its image from c.  Where SubspaceAutoEncoder reconstructs a row
+    through a bottleneck, this pulls the normal rows together and lets the others stay away.  All S nets train at once, one
+    workgroup per net running many optimiser steps per launch.  Defaults: hidden (64, 32), relu, 100 epochs, batch 32, Adam
+    lr 1e-3, weight decay 1e-5 (the autoencoder's).  Not built: the soft-boundary objective (``nu``, a radius), autoencoder
+    pre-training (pyod's ``use_ae``), dropout, a validation split, pyod's ``l2_regularizer`` scale (its default 0.1 is not
+    reproduced; the weight decay 1e-5 is the autoencoder's).
+
+    Sizes.  X is cast to float32.  hidden: 1 to 3 widths, each 1 .. 128, the last is the output dimension q; activation
+    "relu" or "tanh"; batch_size 1 .. 256; epochs >= 0; 0 <= beta1, beta2 < 1; eps > 0; lr, weight_decay, center_eps >= 0;
+    seed in [0, 2^64); a subspace has at most 1024 features; ``fit`` takes 2 .. 2^24 rows.
+
+    Scaling.  SubspaceAutoEncoder's exactly: float64 column mean and population deviation (``location_``, ``scale_``: float64
+    [d]), sd 1 for a constant column, z = float32((double(x) - mean_f) / sd_f).  New rows use the stored values.
+
+    Net.  The subspace at position s has the layer sizes d_s, h_1 .. h_L (L layers l = 0 .. L - 1, layer l mapping K_l inputs to
+    N_l outputs), NO BIAS anywhere (with one the objective is minimised by a constant output), the activation after every
+    layer but the last, a linear output of q = h_L coordinates.  relu is max(a, 0); tanh is float32(tanh(double(a))).
+
+    Initialisation.  W_l[o, i] = float32((2 u - 1) c_l), c_l = 1 / sqrt(K_l) formed on the host in float64, e = o K_l + i, u = (w +
+    0.5) 2^-32 in float64 with w the word e & 3 of Philox4x32-10 at
+
+        counter (lo32(e >> 2), hi32(e >> 2), 0x53564400 + l, 0),  key k0 = lo32(seed) ^ lo32(s),  k1 = hi32(seed) ^ hi32(s) ^ 0x5bd1e995
+
+    (SubspaceAutoEncoder's rule under another tag, so the nets are not the autoencoder's).  m = v = 0.  The nets are keyed by
+    the subspace's POSITION.
+
+    Centre.  center = None: the untrained net runs over all n fitted rows; mean_j is the float64 sum of double(out[i, j]) over
+    the rows of a tile of 32 consecutive rows (rows ascending), then over the tiles ascending, divided by n.  Where |mean_j| <
+    center_eps the coordinate becomes -center_eps when mean_j < 0 and +center_eps otherwise (exact and negative zero go to
+    +center_eps; Ruff's code leaves a 0 in place); center_eps = 0 disables the rule.  c_j = float32 of the result.  The value
+    depends neither on how the rows are cut into launches nor on workspace_bytes.  center = a real array [q] (every
+    subspace) or [S, q] is used as given, rounded to float32.  ``center_`` (float32 [S, q]) and ``n_clamped_`` (int [S]: the
+    coordinates the rule moved; 0 with a given centre) are published.  The centre stays fixed during the training.
+
+    Batches.  SubspaceAutoEncoder's: B = min(batch_size, n), n // B steps per epoch, row j of step i of epoch e is
+    feistel_perm(i B + j, n, seed, e); ``n_steps_`` = epochs (n // B); epochs = 0 scores with the untrained net.
+
+    One step, all in float32 unless said; fma(a, b, c) is a b + c rounded once.
+      forward     pre_l[i, o] = fma-chain over k ascending, from 0, of h_{l-1}[i, k] W_l[o, k]; h_l = act(pre_l), h_{-1} = z, out =
+                  pre_{L-1}.  No bias is added.
+      loss        r[i, j] = out[i, j] - c_j; rowsum_i = fma-chain over j ascending of r r; loss = (sum over i ascending of
+                  rowsum_i) / float32(B): the batch loss before the update.
+      backward    D_{L-1}[i, j] = r[i, j] float32(2 / B) (the factor formed in float64); for l from the last layer down:
+                  down[i, k] = fma-chain over o ascending of D_l[i, o] W_l[o, k] with the weights BEFORE their update;
+                  D_{l-1}[i, k] = down[i, k] act'(h_{l-1}[i, k]), act' = (h > 0 ? 1 : 0) for relu and fma(-h, h, 1) for tanh.
+      gradient    g = fma-chain over the batch rows i ascending of D_l[i, o] h_{l-1}[i, k].
+      Adam        SubspaceAutoEncoder's sequence: g = fma(wd, theta, g); m = fma(b1, m, omb1 g); v = fma(b2, v, (omb2 g) g);
+                  theta = theta - (lrc m) / (sqrt(v) / sc2 + eps), the bias corrections formed on the host in float64.
+    Weights, centre, losses and scores are bit-identical from run to run, for every workspace_bytes (which cuts the
+    subspaces into chunks that each train to the end), for every cut of the steps into launches and for every split of
+    the query rows.  ``fit`` raises ValueError, naming the bytes, when one net with its moments does not fit workspace_bytes.
+
+    Score.  score[s, i] = float32(sum_j double(r_j)^2), r_j = out[i, j] - c_j the float32 difference, j ascending: the SQUARED
+    distance to the centre, as in pyod and the paper.  ``fit`` scores the training rows with the kernel of
+    ``decision_function``, so ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit.  A subspace whose features
+    are all constant is not trained: it scores exactly 0, has losses 0 and a centre of zeros (also under a given centre).
+    NaN input leaves the results unspecified and neither faults nor hangs: every loop is bounded by its counts.
+
+    Collapse.  With tanh, or any bounded activation, and no bias the net can drive every output to 0: the loss then sticks
+    at |c|^2 and every row scores the same.  relu is the default for that reason.  On the ring recipe of
+    tests/test_outlier_kpca_cpu.py (outliers inside the data) the float64 restatement with hidden (16, 4) and 50 epochs
+    reaches an AUC of 0.9999 to 1.000 with relu (seeds 0 to 4) and 0.38 to 0.55 with tanh (the loss stuck at 0.0400 = |c|^2),
+    against 0.16 to 0.34 for the covariance.
+
+    Fitted state: the weights, the centres, ``location_``, ``scale_`` and the seed; neither X nor the moments are kept.
+    ``fit`` publishes ``weights_`` (a list of S lists of W_l float32 [N_l, K_l], fetched on first use), ``center_``,
+    ``n_clamped_``, ``loss_history_`` (float64 [S, epochs]: the float32 step losses of an epoch summed in float64 in step
+    order and divided by their number), ``n_steps_``, ``location_``, ``scale_``.  ``embed(X, s)`` returns float32 [n, q], the
+    output of net s on the standardised rows: for inspection and the tests.  normalize, combination, contamination,
+    ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.  pyod is not pinned
+    here: this definition and its numpy restatement in tests/test_outlier_svdd_cpu.py are what binds.  All of it runs in
+    libvgan_hip.so (csrc/outlier_svdd.hip on the layer routines of csrc/outlier_mlp.hpp, which the autoencoder shares; the
+    column moments in csrc/outlier_maha.hip)."""
+
+    _host_weights = None
+    _column_moments = SubspaceAutoEncoder._column_moments
+    _fit_scaling = SubspaceAutoEncoder._fit_scaling
+
+    def __init__(self, subspaces, proba, hidden=(64, 32), activation="relu", epochs=100, batch_size=32, lr=1e-3, beta1=0.9, beta2=0.999,
+                 eps=1e-8, weight_decay=1e-5, center=None, center_eps=0.1, seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None,
+                 combination="sum", contamination=0.1):
+        self.hidden = check_svdd_hidden(hidden)
+        self.activation = check_activation(activation)
+        (self.epochs, self.batch_size, self.lr, self.beta1, self.beta2, self.eps,
+         self.weight_decay) = check_ae_params(epochs, batch_size, lr, beta1, beta2, eps, weight_decay)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        self.center, self.center_eps = check_svdd_center(center, center_eps, self.plan.count, self.hidden[-1])
+        self._max_dims = int(self.plan.dims.max())
+        if self._max_dims > AE_MAX_DIMS:
+            raise ValueError(f"a subspace has {self._max_dims} features, SubspaceDeepSVDD takes at most {AE_MAX_DIMS}")
+        self._net = (self.hidden, AE_ACTIVATIONS[self.activation])
+        self._params = np.array([svdd_param_count(d_s, self.hidden) for d_s in self.plan.dims], dtype=np.int64)
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= AE_MAX_ROWS:
+            raise ValueError(f"SubspaceDeepSVDD fit needs between 2 and {AE_MAX_ROWS} rows, got {n}")
+
+    def _attach(self):
+        if self.ops is not None:
+            return
+        super()._attach()
+        fan_in = np.array([[K for K, _ in svdd_layer_sizes(d_s, self.hidden)] for d_s in self.plan.dims], dtype=np.float64)
+        self._init_scale = torch.as_tensor(1.0 / np.sqrt(fan_in), device="cuda")
+        self._w_off_host = np.concatenate([[0], np.cumsum(self._params)]).astype(np.int64)
+        self._w_off = torch.as_tensor(self._w_off_host[:-1].copy(), device="cuda")
+
+    def _forward_tiles(self, nq, widest, extra_bytes=0):
+        """(row tiles of one forward launch over `widest` blocks, its scratch buffer or None): all tiles of nq rows, or as many
+        as keep the scratch slices (and extra_bytes per (block, tile)) within workspace_bytes, at least one."""
+        act = svdd_act_floats(self._max_dims, self.hidden, AE_ROW_TILE, False)
+        spill = act > AE_LDS_FLOATS
+        tiles = -(-nq // AE_ROW_TILE)
+        per_tile = (4 * act if spill else 0) + extra_bytes
+        if per_tile:
+            tiles = int(max(1, min(tiles, self.workspace_bytes // (per_tile * widest))))
+        scratch = torch.empty(widest * tiles * act, dtype=torch.float32, device="cuda") if spill else None
+        return tiles, scratch
+
+    def _centers(self, X, first, count, state, s_off):
+        """The centres of the untrained nets of a chunk into _center[first : first + count] and _n_clamped: the tile sums of
+        every row chunk are folded into one running float64 sum in tile order."""
+        n, dev, q = X.shape[0], X.device, self.hidden[-1]
+        tiles, scratch = self._forward_tiles(n, count, extra_bytes=8 * q)
+        rows = tiles * AE_ROW_TILE
+        tile_sums = torch.empty(count * tiles * q, dtype=torch.float64, device=dev)
+        run = torch.zeros(count * q, dtype=torch.float64, device=dev)
+        for r0 in range(0, n, rows):
+            self.ops.svdd_center(X[r0:r0 + rows], self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, state, s_off,
+                                 tile_sums, run, n if r0 + rows >= n else 0, self.center_eps, self._center[first:first + count],
+                                 self._n_clamped[first:first + count], scratch)
+
+    def _train(self, X, batch, chunks):
+        """Initialises every chunk of nets, takes its centres and trains it to the end; the weights go to _theta, the step
+        losses to the returned [S, steps] matrix."""
+        n, dev = X.shape[0], X.device
+        S, steps = self.plan.count, self.epochs * (n // batch)
+        corr = torch.as_tensor(ae_bias_corrections(self.beta1, self.beta2, steps), device=dev)
+        loss = torch.zeros(S, max(steps, 1), dtype=torch.float32, device=dev)
+        adam = (self.lr, self.beta1, self.beta2, self.eps, self.weight_decay)
+        act = svdd_act_floats(self._max_dims, self.hidden, batch, True)
+        for first, count in chunks:
+            sizes = self._params[first:first + count]
+            off = np.concatenate([[0], np.cumsum(3 * sizes)]).astype(np.int64)
+            state = torch.empty(int(off[-1]), dtype=torch.float32, device=dev)
+            s_off = torch.as_tensor(off[:-1].copy(), device=dev)
+            self.ops.svdd_init(self._table[1], self._net, first, count, self._init_scale, self.seed, state, s_off, int(off[-1]))
+            if self.center is None:
+                self._centers(X, first, count, state, s_off)
+            scratch = torch.empty(count * act, dtype=torch.float32, device=dev) if act > AE_LDS_FLOATS else None
+            per_launch = ae_launch_steps(int(sizes.max()), batch)
+            for g0 in range(0, steps, per_launch):
+                self.ops.svdd_train(X, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, batch, self.seed,
+                                    g0, corr[g0:g0 + per_launch], adam, self._center[first:first + count], state, s_off,
+                                    loss[first:first + count], scratch)
+            for z in range(count):
+                at = int(self._w_off_host[first + z])
+                self._theta[at:at + int(sizes[z])].copy_(state[int(off[z]):int(off[z]) + int(sizes[z])])
+            del state, scratch
+        return loss[:, :steps]
+
+    def _distances(self, X, only=None):
+        """float32 [S, nq] on the device: the squared distances of the images of the rows of X from the centres; only = s:
+        (the raw output of net s [nq, q]) instead."""
+        nq, dev, q = X.shape[0], X.device, self.hidden[-1]
+        ranges = list(_launch_ranges(self.plan.count, _AE_MAX_RANGE)) if only is None else [(only, 1)]
+        tiles, scratch = self._forward_tiles(nq, max(count for _, count in ranges))
+        rows = tiles * AE_ROW_TILE
+        out = torch.empty((self.plan.count, nq) if only is None else (nq, q), dtype=torch.float32, device=dev)
+        for first, count in ranges:
+            for r0 in range(0, nq, rows):
+                Xc = X[r0:r0 + rows]
+                if only is None:
+                    self.ops.svdd_scores(Xc, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, self._theta,
+                                         self._w_off[first:first + count], center=self._center[first:first + count],
+                                         score=out[first:first + count, r0:], scratch=scratch)
+                else:
+                    self.ops.svdd_scores(Xc, self._table, self._scaling, self._skip, self._net, first, 1, self._max_dims, self._theta,
+                                         self._w_off[first:first + 1], embed=out[r0:r0 + rows], scratch=scratch)
+        return out
+
+    def _score(self, X, fitting):
+        per = self._distances(X)
+        return self._combine(per, fitting), per
+
+    def embed(self, X, s):
+        """float32 [n, q]: the output of the net of subspace s on the rows of X, standardised by the fitted location_ and scale_."""
+        self._require_fit()
+        s = int(s)
+        if not 0 <= s < self.plan.count:
+            raise ValueError(f"no subspace {s}: {self.plan.count} subspaces")
+        return self._distances(_device_matrix(X, self.plan.d), only=s).cpu().numpy()
+
+    @property
+    def weights_(self):
+        """List of S lists of W_l float32 [N_l, K_l], one per layer."""
+        self._require_fit()
+        if self._host_weights is None:
+            flat, out = self._theta.cpu().numpy(), []
+            for s, d_s in enumerate(self.plan.dims):
+                at, layers = int(self._w_off_host[s]), []
+                for K, N in svdd_layer_sizes(d_s, self.hidden):
+                    layers.append(flat[at:at + K * N].reshape(K, N).T.copy())
+                    at += K * N
+                out.append(layers)
+            self._host_weights = out
+        return self._host_weights
+
+    def fit(self, X, y=None):
+        """Takes the column means and deviations of X, then chunk of subspaces by chunk initialises the nets, takes their
+        centres, runs all epochs (steps-per-launch by ae_launch_steps), and scores X through the trained nets:
+        decision_scores_ (float64 [n]), per_subspace_scores_, location_, scale_, center_, n_clamped_, loss_history_, n_steps_
+        and, on first use, weights_; with normalize also score_center_ / score_scale_."""
+        n = _matrix_shape(X, self.plan.d)[0]
+        self._check_fit_rows(n)
+        batch = min(self.batch_size, n)
+        chunks = ae_chunks([svdd_net_bytes(d_s, self.hidden, batch, self._max_dims) for d_s in self.plan.dims], self.workspace_bytes,
+                           "SubspaceDeepSVDD")  # raises before the device is touched
+        X = self._begin_fit(X)
+        dev = X.device
+        self._fitted, self._host_weights = False, None
+        self._fit_scaling(X)
+        S, q = self.plan.count, self.hidden[-1]
+        self._theta = torch.empty(int(self._w_off_host[-1]), dtype=torch.float32, device=dev)
+        given = np.zeros((S, q), np.float32) if self.center is None else np.where(self._constant[:, None], np.float32(0), self.center)
+        self._center = torch.as_tensor(np.ascontiguousarray(given, dtype=np.float32), device=dev)
+        self._n_clamped = torch.zeros(S, dtype=torch.int32, device=dev)
+        steps = n // batch
+        self.n_steps_ = self.epochs * steps
+        loss = self._train(X, batch, chunks).cpu().numpy().astype(np.float64).reshape(S, self.epochs, steps)
+        self.loss_history_ = np.cumsum(loss, axis=2)[:, :, -1] / steps  # cumsum adds in step order
+        self.center_ = self._center.cpu().numpy()
+        self.n_clamped_ = self._n_clamped.cpu().numpy().astype(np.int64)
         scores, per = self._score(X, fitting=True)
         return self._publish(scores, per)
 

@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import (SubspaceABOD, SubspaceAutoEncoder, SubspaceCBLOF, SubspaceCOF, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
+from .outlier import (SubspaceABOD, SubspaceAutoEncoder, SubspaceCBLOF, SubspaceCOF, SubspaceDeepSVDD, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
                       SubspaceINNE, SubspaceKPCA, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOD, SubspaceSOS)
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
@@ -250,7 +250,12 @@ class _RunFolder:
         the standardised rows through a bottleneck, the score the reconstruction distance; pyod's AutoEncoder without dropout
         and batch normalisation): its keywords are hidden, activation ("relu" or "tanh"), epochs, batch_size, lr, beta1,
         beta2, eps, weight_decay, seed, workspace_bytes and the same normalize / combination / contamination, e.g.
-        outlier_ensemble(method="autoencoder", hidden=(16, 2), activation="tanh", X=X); n_neighbors is not used there."""
+        outlier_ensemble(method="autoencoder", hidden=(16, 2), activation="tanh", X=X); n_neighbors is not used there.
+        method "deepsvdd" builds a SubspaceDeepSVDD (one small encoder without bias per subspace trained on the device to
+        map the standardised rows onto one centre, the score the squared distance to it; Ruff et al.'s one-class Deep SVDD,
+        pyod's DeepSVDD without pre-training): its keywords are hidden, activation ("relu" or "tanh"), epochs, batch_size, lr,
+        beta1, beta2, eps, weight_decay, center, center_eps, seed, workspace_bytes and the same normalize / combination /
+        contamination, e.g. outlier_ensemble(method="deepsvdd", hidden=(32, 8), X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         if method == "cblof":
@@ -287,6 +292,8 @@ class _RunFolder:
             ens = SubspaceKPCA(self.subspaces, self.proba, **kw)
         elif method == "autoencoder":
             ens = SubspaceAutoEncoder(self.subspaces, self.proba, **kw)
+        elif method == "deepsvdd":
+            ens = SubspaceDeepSVDD(self.subspaces, self.proba, **kw)
         elif method == "sod":
             ens = SubspaceSOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
         else:
