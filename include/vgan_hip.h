@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1478,6 +1478,42 @@ int vgan_kpca_row_means(const float* R, int64_t rows, int m, double* mean, vgan_
 int vgan_kpca_scores(const float* R, int rows, int m, int first, int count, const double* row_mean, const double* col_mean,
                      const double* total, const double* V, const double* wt, float* score, const int32_t* score_row,
                      int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * HiCS subspace contrast (Keller, Mueller, Boehm, ICDE 2012): the Monte-Carlo contrast of a feature set, the mean over M
+ * draws of the Kolmogorov-Smirnov distance between one feature's sample conditioned on index slices of the others and its
+ * full sample, taken on sort positions in integers (v-gan_amd/hics.py: subspace_contrast and HiCS, whose docstrings are the
+ * definition; kernels in csrc/outlier_hics.hip).  2 <= n <= VGAN_HICS_MAX_ROWS: the two n-bit maps of a draw are 64 KB of LDS.
+ * vgan_hics_argsort_columns: order, rank uint32 [d, n].  order[f, r] = the row at position r of the stable ascending sort
+ *   of column f of X [n, d] (ldx), -0.0 taken as +0.0, ties to the lower row; rank[f, order[f, r]] = r.  A bitonic network
+ *   on the 64-bit keys (orderable float bits << 32) | row, which are distinct, so the result is the unique stable order
+ *   and NaN input cannot change a trip count.  keys: workspace uint64 [d, n_pad], n_pad the power of two with n <= n_pad
+ *   < 2 n; runs of VGAN_HICS_SORT_RUN keys are sorted in LDS.
+ * vgan_hics_contrast: subspace z (0 <= z < S) has the features feat[feat_off[z] .. feat_off[z + 1]) (ascending, k of them),
+ *   the slice width width[z] (1 <= w <= n, computed by the host) and the stream id stream_id[z].  Draw t (0 <= t < M) uses
+ *   the Philox4x32-10 words with key k0 = lo32(seed) ^ lo32(id), k1 = hi32(seed) ^ hi32(id) ^ 0x5bd1e995 and counter (t, q,
+ *   VGAN_HICS_PHILOX_TAG, 0): c = (word 0 of q = 0 * k) >> 32 is the comparison position, start_p = (word p & 3 of q = 1 +
+ *   (p >> 2) * (n - w + 1)) >> 32 the slice start of position p != c.  C = the rows that lie in order[f_p, start_p ..
+ *   start_p + w) for every p != c, m = |C|, cnt(r) = #{rows of C with rank[f_c, .] < r},
+ *       D = max over r = 1 .. n of |cnt(r) n - r m|                                            (64-bit integers).
+ *   D int64, m and c int32 [S, M] receive every draw.  contrast[z] (float64) = (sum over t ascending of float64(D) /
+ *   float64(n m), 0 where m = 0) / M; n_empty[z] (int32) counts the draws with m = 0.  k < 2: no draw is made, D = m = 0,
+ *   c = -1, contrast 0, n_empty 0.  The membership of a draw is a bitmap in LDS indexed by rank[f_c, .]; with 2 w > n the
+ *   complement of each slice is cleared from a full map instead, which gives the same set.  group: draws of one subspace
+ *   that share a workgroup of 256 threads, 1 (a workgroup per draw) or VGAN_HICS_WAVE_GROUP (a wave per draw, n <=
+ *   VGAN_HICS_WAVE_GROUP_MAX_ROWS), 0 = the library's choice; the results do not depend on it.  S * ceil(M / group) < 2^31.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_HICS_MAX_ROWS 262144 /* 2^18 */
+#define VGAN_HICS_SORT_RUN 2048
+#define VGAN_HICS_PHILOX_TAG 0x48494353u
+#define VGAN_HICS_WAVE_GROUP 4
+#define VGAN_HICS_WAVE_GROUP_MAX_ROWS 65536
+int vgan_hics_argsort_columns(const float* X, int ldx, int n, int d, uint64_t* keys, int64_t n_pad, uint32_t* order,
+                              uint32_t* rank, vgan_stream_t stream);
+int vgan_hics_contrast(const uint32_t* order, const uint32_t* rank, int n, int d, const int32_t* feat, const int32_t* feat_off,
+                       const int32_t* width, const uint64_t* stream_id, int S, int M, uint64_t seed, int group, int64_t* D,
+                       int32_t* m, int32_t* c, double* contrast, int32_t* n_empty, vgan_stream_t stream);
 
 #ifdef __cplusplus
 }

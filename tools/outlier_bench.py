@@ -115,6 +115,11 @@ difference of the two paths' ensemble scores.
     each behind a synchronisation; IN THE SAME RUN SubspaceAutoEncoder with hidden (64, 32) on the same rows (fit, training,
     microseconds per step) and the LOF fit (k = 20); and the same encoders trained in torch on the GPU as padded torch.bmm
     batches with torch.optim.Adam for a sample of the steps.
+  --method hics: the HiCS search (vgan_amd.HiCS at its defaults) at d = 784, n = 2000 and 10^4: fit, and its split into the
+    column argsort, level 2 (all 306 936 pairs x 50 draws, under the library's workgroup shape and under both forced ones)
+    and the higher levels (their candidates replayed on the resident index), with draws per second; subspace_contrast of the
+    50 sampled subspaces of a two-epoch model (350 to 390 features each, the complement path); and the numpy restatement
+    in 16 spawned processes on 256 of the pairs and 16 of the model's subspaces, scaled to all and compared bit for bit.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1885,12 +1890,140 @@ def run_sod(d, n, count, k, ref_set, alpha, reps):
             "score_gather_bytes": gather_bytes, "score_gather_GBps": round(gather_bytes / t_score / 1e9, 1)}
 
 
+def _hics_numpy_contrasts(job):
+    """Worker of run_hics: the plain numpy restatement of the contrast (tests/hics_ref.py's, with the library's vectorised
+    draws) for a list of feature sets; runs in a spawned process that never touches the GPU."""
+    from vgan_amd.hics import hics_draws, hics_slice_width
+    order, sets, ids, alpha, M, seed = job
+    n = order.shape[1]
+    r = np.arange(1, n + 1, dtype=np.int64)
+    out = []
+    for feats, sid in zip(sets, ids):
+        k = len(feats)
+        w = hics_slice_width(n, k, alpha)
+        c, start = hics_draws(n, k, w, M, seed, sid)
+        total = 0.0
+        for t in range(M):
+            member = np.ones(n, dtype=bool)
+            for p, f in enumerate(feats):
+                if p != c[t]:
+                    inside = np.zeros(n, dtype=bool)
+                    inside[order[f, start[t, p]:start[t, p] + w]] = True
+                    member &= inside
+            cnt = np.cumsum(member[order[feats[c[t]]]].astype(np.int64))
+            m = int(cnt[-1])
+            if m:
+                total += float(np.abs(cnt * n - r * m).max()) / float(n * m)
+        out.append(total / M)
+    return out
+
+
+def _hics_numpy(pool, workers, order, sets, ids, alpha, M, seed):
+    """(seconds, contrasts) of the restatement over `sets`, dealt to the pool's workers in equal parts."""
+    parts = [(order, sets[i::workers], ids[i::workers], alpha, M, seed) for i in range(workers)]
+    t0 = time.perf_counter()
+    res = pool.map(_hics_numpy_contrasts, parts)
+    dt = time.perf_counter() - t0
+    out = np.empty(len(sets))
+    for i, r in enumerate(res):
+        out[i::workers] = r
+    return dt, out
+
+
+def run_hics(d, n, count, reps, pool, workers=16, numpy_pairs=256, numpy_wide=16):
+    """HiCS at its defaults on X [n, d]: the fit split into the argsort, level 2 (under both workgroup shapes) and the higher
+    levels (their candidates replayed on the resident index), the contrast of the model's `count` sampled subspaces, and the
+    numpy restatement in `workers` processes on a sample of the level-2 pairs and of the model's subspaces, scaled up."""
+    from vgan_amd.hics import HICS_WAVE_GROUP, ContrastIndex, HiCS
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    search = HiCS()
+    alpha, M, seed = search.alpha, search.n_iterations, search.seed
+    t_fit, tf = timed(lambda: search.fit(Xd), reps)
+    t_sort, ts = timed(lambda: ContrastIndex(Xd), reps)
+    index = ContrastIndex(Xd)
+
+    def level(lv, group=0):
+        cands = lv["candidates"]
+        ids = (np.uint64(lv["k"]) << np.uint64(32)) | np.arange(len(cands), dtype=np.uint64)
+        return index.contrast(cands.reshape(-1), np.arange(len(cands) + 1, dtype=np.int64) * lv["k"], alpha, M, seed, ids, group=group)
+
+    lv2, higher = search.levels_[0], search.levels_[1:]
+    t_l2, tl2 = timed(lambda: level(lv2), reps)
+    t_l2_block, _ = timed(lambda: level(lv2, 1), reps)
+    t_l2_wave, _ = timed(lambda: level(lv2, HICS_WAVE_GROUP), reps) if n <= 65536 else (None, None)
+    t_high, th = timed(lambda: [level(lv) for lv in higher], reps)
+    draws2 = len(lv2["candidates"]) * M
+    draws_high = sum(len(lv["candidates"]) for lv in higher) * M
+    dims = m.sum(axis=1)
+    t_model, tm = timed(lambda: vgan_amd.subspace_contrast(Xd, m), reps)
+    _, feat, feat_off = vgan_amd.hics._lists_of(m)
+    t_model_sweep, _ = timed(lambda: index.contrast(feat, feat_off, alpha, M, seed, np.arange(len(m), dtype=np.uint64)), reps)
+    t_model_block, _ = timed(lambda: index.contrast(feat, feat_off, alpha, M, seed, np.arange(len(m), dtype=np.uint64), group=1), reps)
+    t_model_wave, _ = timed(lambda: index.contrast(feat, feat_off, alpha, M, seed, np.arange(len(m), dtype=np.uint64),
+                                                   group=HICS_WAVE_GROUP), reps) if n <= 65536 else (None, None)
+    widths = np.asarray([vgan_amd.hics.hics_slice_width(n, int(k), alpha) for k in dims])
+    marks = float(((dims - 1) * np.minimum(n - widths, widths)).sum()) * M  # bits set or cleared by all draws
+    row = {"method": "hics", "d": d, "n": n, "alpha": alpha, "n_iterations": M, "candidate_cutoff": search.candidate_cutoff,
+           "fit_s": round(t_fit, 4), "fit_reps_s": tf, "argsort_s": round(t_sort, 5), "argsort_reps_s": ts,
+           "level2_candidates": len(lv2["candidates"]), "level2_s": round(t_l2, 4), "level2_reps_s": tl2,
+           "level2_draws_per_s": round(draws2 / t_l2), "level2_workgroup_per_draw_s": round(t_l2_block, 4),
+           "level2_wave_per_draw_s": None if t_l2_wave is None else round(t_l2_wave, 4),
+           "levels": [{"k": lv["k"], "candidates": len(lv["candidates"])} for lv in search.levels_],
+           "higher_levels_s": round(t_high, 4), "higher_levels_reps_s": th,
+           "higher_levels_draws_per_s": round(draws_high / t_high) if draws_high else None,
+           "fit_host_remainder_s": round(t_fit - t_sort - t_l2 - t_high, 4),
+           "found": int(len(search.subspaces)), "best_contrast": float(search.contrast_[0]),
+           "model_subspaces": int(len(m)), "model_d_s_min": int(dims.min()), "model_d_s_median": float(np.median(dims)),
+           "model_d_s_max": int(dims.max()), "model_subspace_contrast_s": round(t_model, 6), "model_subspace_contrast_reps_s": tm,
+           "model_sweep_s": round(t_model_sweep, 6), "model_sweep_workgroup_per_draw_s": round(t_model_block, 6),
+           "model_sweep_wave_per_draw_s": None if t_model_wave is None else round(t_model_wave, 6),
+           "model_marks": marks, "model_marks_per_s": round(marks / t_model_sweep)}
+    if pool is not None:
+        order = index.order.cpu().numpy().astype(np.int64)
+        pick = np.random.default_rng(0).choice(len(lv2["candidates"]), size=min(numpy_pairs, len(lv2["candidates"])), replace=False)
+        pick.sort()
+        sets = [tuple(int(f) for f in lv2["candidates"][i]) for i in pick]
+        ids = [(2 << 32) | int(i) for i in pick]
+        t_np, got = _hics_numpy(pool, workers, order, sets, ids, alpha, M, seed)
+        same = bool(np.array_equal(got.view(np.int64), lv2["contrast"][pick].view(np.int64)))
+        wide = list(range(min(numpy_wide, len(m))))
+        t_np_wide, got_wide = _hics_numpy(pool, workers, order, [tuple(np.flatnonzero(m[z]).tolist()) for z in wide], wide, alpha, M, seed)
+        want_wide = vgan_amd.subspace_contrast(Xd, m[wide])
+        row.update({"numpy_workers": workers, "numpy_pairs_timed": len(sets), "numpy_pairs_s": round(t_np, 3),
+                    "numpy_level2_scaled_s": round(t_np * len(lv2["candidates"]) / len(sets), 1),
+                    "level2_speedup_vs_numpy": round(t_np * len(lv2["candidates"]) / len(sets) / t_l2, 1),
+                    "numpy_pairs_bit_equal": same, "numpy_model_subspaces_timed": len(wide), "numpy_model_subspaces_s": round(t_np_wide, 3),
+                    "numpy_model_scaled_s": round(t_np_wide * len(m) / len(wide), 2),
+                    "model_sweep_speedup_vs_numpy": round(t_np_wide * len(m) / len(wide) / t_model_sweep, 1),
+                    "numpy_model_bit_equal": bool(np.array_equal(got_wide.view(np.int64), want_wide.view(np.int64)))})
+    return row
+
+
+def run_hics_shapes(d, rows, reps, M=50, alpha=0.1):
+    """All pairs of d independent Gaussian features, M draws each, under a workgroup per draw and a wave per draw, per n."""
+    from vgan_amd.hics import HICS_WAVE_GROUP, ContrastIndex
+    a, b = np.triu_indices(d, 1)
+    feat = np.stack([a, b], axis=1).astype(np.int32).reshape(-1)
+    off = np.arange(len(a) + 1, dtype=np.int64) * 2
+    ids = np.arange(len(a), dtype=np.uint64)
+    out = []
+    for n in rows:
+        X = torch.as_tensor(np.random.default_rng(n).standard_normal((n, d)).astype(np.float32), device="cuda")
+        index = ContrastIndex(X)
+        t_block, _ = timed(lambda: index.contrast(feat, off, alpha, M, 0, ids, group=1), reps)
+        t_wave, _ = timed(lambda: index.contrast(feat, off, alpha, M, 0, ids, group=HICS_WAVE_GROUP), reps)
+        out.append({"d": d, "n": n, "pairs": len(a), "n_iterations": M, "workgroup_per_draw_s": round(t_block, 6),
+                    "wave_per_draw_s": round(t_wave, 6), "wave_over_workgroup": round(t_wave / t_block, 3)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
     ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / kpca / ae / deepsvdd: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
@@ -1900,6 +2033,12 @@ def main():
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
+    pool = None
+    if args.method == "hics" and not args.no_baselines:
+        # the numpy workers are spawned before this process touches the GPU and never open it themselves
+        import multiprocessing
+        pool = multiprocessing.get_context("spawn").Pool(16)
+        pool.map(abs, range(16))
     assert torch.cuda.is_available(), "outlier_bench needs an MI355X"
     configs = [(10, 10_000, 50, 5, True), (10, 10_000, 50, 20, True), (10, 50_000, 500, 5, True), (10, 50_000, 500, 20, False),
                (784, 10_000, 50, 5, True), (784, 10_000, 50, 20, False), (784, 50_000, 50, 5, False)]
@@ -2066,6 +2205,19 @@ def main():
         for d, n, count in shapes:
             out["configs"].append(run_svdd(d, n, count, args.reps, baselines=not args.no_baselines))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "hics":
+        shapes = [(20, 500, 8)] if args.quick else [(784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_hics(d, n, count, args.reps, pool))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        if pool is not None:
+            pool.close()
+            pool.join()
+        if not args.shape:  # where the two workgroup shapes of the draw kernel meet
+            out["workgroup_shapes"] = run_hics_shapes(64, [1024, 4096] if args.quick else [4096, 16384, 32768, 65536], args.reps)
         configs = []
     if args.method == "gmm":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),

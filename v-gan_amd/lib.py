@@ -215,9 +215,11 @@ SIGNATURES = {
     "vgan_kpca_kernel_rows": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p]),
     "vgan_kpca_row_means": (_i, [_p, _i64, _i, _p, _p]),
     "vgan_kpca_scores": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "vgan_hics_argsort_columns": (_i, [_p, _i, _i, _i, _p, _i64, _p, _p, _p]),
+    "vgan_hics_contrast": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _u64, _i, _p, _p, _p, _p, _p, _p]),
 }
 
-ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_svdd_* ones last) leave it
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_hics_* ones last) leave it
 _lib = None
 
 

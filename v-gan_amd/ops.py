@@ -919,6 +919,30 @@ class HipOps:
                                              _ptr(mask), S, S, _ptr(terms), _ptr(score), score.stride(0), self._stream()),
                    "vgan_ecod_scores")
 
+    # ---- HiCS subspace contrast (vgan_amd.hics) ---------------------------------------------------------------
+    def hics_argsort_columns(self, X, keys, order, rank):
+        """order / rank int32 [d, n] (read as uint32): the stable ascending order of every column of X [n, d] and its inverse;
+        keys: int64 workspace [d, n_pad], n_pad the power of two with n <= n_pad < 2 n."""
+        _mat(X, "X"), _vec(keys, "keys", torch.int64), _vec(order, "order", torch.int32), _vec(rank, "rank", torch.int32)
+        n, d = X.shape
+        assert keys.dim() == 2 and keys.shape[0] == d and order.numel() >= n * d and rank.numel() >= n * d
+        _lib.check(self.lib.vgan_hics_argsort_columns(_ptr(X), X.stride(0), n, d, _ptr(keys), keys.shape[1], _ptr(order), _ptr(rank),
+                                                      self._stream()), "vgan_hics_argsort_columns")
+
+    def hics_contrast(self, order, rank, feat, feat_off, width, stream_id, S, M, seed, D, m, c, contrast, n_empty, group=0):
+        """The draws (D int64, m / c int32 [S, M]), contrasts (float64 [S]) and empty-draw counts (int32 [S]) of the S
+        subspaces whose offsets start at feat_off[0]; width int32 [S], stream_id int64 [S] (read as uint64)."""
+        _vec(order, "order", torch.int32), _vec(rank, "rank", torch.int32), _vec(feat, "feat", torch.int32)
+        _vec(feat_off, "feat_off", torch.int32), _vec(width, "width", torch.int32), _vec(stream_id, "stream_id", torch.int64)
+        _vec(D, "D", torch.int64), _vec(m, "m", torch.int32), _vec(c, "c", torch.int32)
+        _vec(contrast, "contrast", torch.float64), _vec(n_empty, "n_empty", torch.int32)
+        d, n = order.shape
+        assert rank.shape == order.shape and feat_off.numel() >= S + 1 and width.numel() >= S and stream_id.numel() >= S
+        assert min(D.numel(), m.numel(), c.numel()) >= S * M and contrast.numel() >= S and n_empty.numel() >= S
+        _lib.check(self.lib.vgan_hics_contrast(_ptr(order), _ptr(rank), n, d, _ptr(feat), _ptr(feat_off), _ptr(width), _ptr(stream_id),
+                                               int(S), int(M), int(seed) & (2 ** 64 - 1), int(group), _ptr(D), _ptr(m), _ptr(c),
+                                               _ptr(contrast), _ptr(n_empty), self._stream()), "vgan_hics_contrast")
+
     # ---- histogram scores over subspaces (vgan_amd.outlier.SubspaceHBOS / SubspaceLODA) ----------------------
     # keys: int64 [P, 2] holding the library's uint64 order-preserving keys of a column's minimum and maximum
     def hist_column_range(self, X, keys):

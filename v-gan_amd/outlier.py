@@ -129,6 +129,9 @@ never in a constructor), the head and the tail of ``fit``, ``decision_function``
 combination, contamination, predict) are ``_SubspaceScorer``; the neighbour search and its chunk loop are
 ``_NeighborScorer``.  A new detector brings its own arguments, a row-count check (``_check_fit_rows``), ``_score`` and the
 extra attributes its ``fit`` publishes: the ``_SubspaceScorer`` docstring has the list.
+
+``build_ensemble`` maps a method string to the unfitted detector; the models' ``outlier_ensemble`` and the subspace search of
+``vgan_amd.hics`` (HiCS, a source of subspaces beside the trained generator) both go through it.
 """
 import math
 import os
@@ -4465,3 +4468,25 @@ class SubspaceSOD(_NeighborScorer):
         out = np.zeros((nq, self.plan.d), dtype=bool)
         out[:, self.plan.feat[self.plan.feat_off[pos]:self.plan.feat_off[pos + 1]]] = bits
         return out
+
+
+# ---- one detector per method string ----------------------------------------------------------------------------------
+_METHOD_CLASSES = {"cblof": SubspaceCBLOF, "ecod": SubspaceECOD, "iforest": SubspaceIForest, "inne": SubspaceINNE,
+                   "mahalanobis": SubspaceMahalanobis, "gmm": SubspaceGMM, "hbos": SubspaceHBOS, "loda": SubspaceLODA,
+                   "pca": SubspacePCA, "ocsvm": SubspaceOCSVM, "sos": SubspaceSOS, "dif": SubspaceDIF, "kpca": SubspaceKPCA,
+                   "autoencoder": SubspaceAutoEncoder, "deepsvdd": SubspaceDeepSVDD}
+_NEIGHBOR_CLASSES = {"abod": SubspaceABOD, "cof": SubspaceCOF, "sod": SubspaceSOD}
+
+
+def build_ensemble(subspaces, proba, method="knn", n_neighbors=5, **kw):
+    """The unfitted detector that the `method` string of ``outlier_ensemble`` names, over any boolean subspace matrix and its
+    weights: the models' ``outlier_ensemble`` and ``HiCS.outlier_ensemble`` both end here.  "abod", "cof" and "sod" take
+    n_neighbors; "mcd" is SubspaceMahalanobis(robust=True); the classes of _METHOD_CLASSES do not use n_neighbors; every
+    other string ("knn", "lof", "kde", or an unknown one, which it rejects) goes to SubspaceEnsemble."""
+    if method == "mcd":
+        return SubspaceMahalanobis(subspaces, proba, robust=True, **kw)
+    if method in _METHOD_CLASSES:
+        return _METHOD_CLASSES[method](subspaces, proba, **kw)
+    if method in _NEIGHBOR_CLASSES:
+        return _NEIGHBOR_CLASSES[method](subspaces, proba, n_neighbors=n_neighbors, **kw)
+    return SubspaceEnsemble(subspaces, proba, method=method, n_neighbors=n_neighbors, **kw)

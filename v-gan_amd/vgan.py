@@ -14,8 +14,7 @@ from torch.utils.data import DataLoader
 
 from .modules import Decoder, Detector, Encoder, Generator_big, MMDLossConstrained
 from .ops import default_ops
-from .outlier import (SubspaceABOD, SubspaceAutoEncoder, SubspaceCBLOF, SubspaceCOF, SubspaceDeepSVDD, SubspaceDIF, SubspaceECOD, SubspaceEnsemble, SubspaceGMM, SubspaceHBOS, SubspaceIForest, SubspaceLODA,
-                      SubspaceINNE, SubspaceKPCA, SubspaceMahalanobis, SubspaceOCSVM, SubspacePCA, SubspaceSOD, SubspaceSOS)
+from .outlier import build_ensemble
 from .kl_trainer import KLStepEngine
 from .trainer import NoKLStepEngine
 
@@ -258,47 +257,18 @@ class _RunFolder:
         contamination, e.g. outlier_ensemble(method="deepsvdd", hidden=(32, 8), X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
-        if method == "cblof":
-            ens = SubspaceCBLOF(self.subspaces, self.proba, **kw)
-        elif method == "abod":
-            ens = SubspaceABOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
-        elif method == "cof":
-            ens = SubspaceCOF(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
-        elif method == "ecod":
-            ens = SubspaceECOD(self.subspaces, self.proba, **kw)
-        elif method == "iforest":
-            ens = SubspaceIForest(self.subspaces, self.proba, **kw)
-        elif method == "inne":
-            ens = SubspaceINNE(self.subspaces, self.proba, **kw)
-        elif method == "mahalanobis":
-            ens = SubspaceMahalanobis(self.subspaces, self.proba, **kw)
-        elif method == "mcd":
-            ens = SubspaceMahalanobis(self.subspaces, self.proba, robust=True, **kw)
-        elif method == "gmm":
-            ens = SubspaceGMM(self.subspaces, self.proba, **kw)
-        elif method == "hbos":
-            ens = SubspaceHBOS(self.subspaces, self.proba, **kw)
-        elif method == "loda":
-            ens = SubspaceLODA(self.subspaces, self.proba, **kw)
-        elif method == "pca":
-            ens = SubspacePCA(self.subspaces, self.proba, **kw)
-        elif method == "ocsvm":
-            ens = SubspaceOCSVM(self.subspaces, self.proba, **kw)
-        elif method == "sos":
-            ens = SubspaceSOS(self.subspaces, self.proba, **kw)
-        elif method == "dif":
-            ens = SubspaceDIF(self.subspaces, self.proba, **kw)
-        elif method == "kpca":
-            ens = SubspaceKPCA(self.subspaces, self.proba, **kw)
-        elif method == "autoencoder":
-            ens = SubspaceAutoEncoder(self.subspaces, self.proba, **kw)
-        elif method == "deepsvdd":
-            ens = SubspaceDeepSVDD(self.subspaces, self.proba, **kw)
-        elif method == "sod":
-            ens = SubspaceSOD(self.subspaces, self.proba, n_neighbors=n_neighbors, **kw)
-        else:
-            ens = SubspaceEnsemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
+        ens = build_ensemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
         return ens if X is None else ens.fit(X)
+
+    def subspace_contrast(self, X, subspace_count=500, **kw):
+        """The HiCS contrast (vgan_amd.hics.subspace_contrast, whose keywords are alpha, n_iterations, seed, stream_ids,
+        workspace_bytes and return_draws) of every row of self.subspaces on the rows of X, float64 [S]: which of the
+        model's subspaces carry dependence among their features and which are noise.  approx_subspace_dist(subspace_count)
+        runs first if the subspaces are not set, as in outlier_ensemble."""
+        from .hics import subspace_contrast
+        if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
+            self.approx_subspace_dist(subspace_count)
+        return subspace_contrast(X, self.subspaces, **kw)
 
     def check_if_myopic(self, x_data, bandwidth=0.01, count=500, n_permutations=1000):
         """src/vgan.py:384-431: two-sample (MMD, permutation) test of P(x) against P(u * x + mean(x) * ~u), once per given
