@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_* and vgan_iforest_*_blocks entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_*, vgan_iforest_*_blocks, vgan_outlier_*_metric and vgan_outlier_pack_unit entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -733,8 +733,39 @@ int vgan_rows_dot(const float* A, int lda, const float* B, int ldb, double* out,
  *   score of row s that is not NaN, 1 if every score is NaN; n_degenerate[s] (int32 [S]) = the number of NaN scores.
  *   fit == 0: score_ceiling is read, n_degenerate is not touched (may be NULL).  Then every NaN of row s becomes
  *   (float)score_ceiling[s].
+ * Other metrics of the neighbour search (kNN, LOF, kneighbors).  Over F_s, on the raw float32 features taken as float64:
+ *     VGAN_OUTLIER_METRIC_EUCLIDEAN  sqrt(sum_f (x_f - y_f)^2): the entries above
+ *     VGAN_OUTLIER_METRIC_MANHATTAN  sum_f |x_f - y_f|
+ *     VGAN_OUTLIER_METRIC_CHEBYSHEV  max_f |x_f - y_f|
+ *     VGAN_OUTLIER_METRIC_MINKOWSKI  (sum_f |x_f - y_f|^p)^(1/p), p finite in (0, VGAN_OUTLIER_MAX_P]; p < 1 is allowed
+ *                                    and is not a metric (no triangle inequality)
+ *     VGAN_OUTLIER_METRIC_COSINE     1 - <x, y> / (|x| |y|), not centred; exactly 1 when |x| or |y| is 0 (scipy: NaN)
+ *   Everything after the sorted lists (vgan_outlier_score) is metric free.
+ * vgan_outlier_knn_metric: vgan_outlier_knn for metric MANHATTAN, CHEBYSHEV or MINKOWSKI (any other is rejected: Euclidean
+ *   and cosine lists come from vgan_outlier_knn) on the Minkowski-family producer (csrc/outlier_metric.hpp), a vector-ALU
+ *   sweep with a 4 x 4 register tile per lane.  Pq / Pr are NOT centred packed blocks (vgan_outlier_pack with center NULL:
+ *   a raw difference has one rounding).  The candidates are ranked by (g, index), g in float32 with the features ascending:
+ *   the sum of |q_f - r_f|, their maximum, or the sum of exp2f(p log2f(|q_f - r_f|)) (no root: it is monotone).  Equal
+ *   rows give g = 0 exactly.  For p > 2 a sum beyond FLT_MAX is +inf and such pairs compare equal (ranked by index); this is
+ *   not guarded.  MINKOWSKI with p == 1 runs the MANHATTAN instance.  k, exclude_self, splits, part_d / part_i, nbr, the
+ *   row-count and alignment rules and the independence of J and of the chunking are those of vgan_outlier_knn; all
+ *   arguments are validated before the device is touched.
+ * vgan_outlier_pack_unit: vgan_outlier_pack without a centre, every row divided by its float64 norm over F_s (the quotient
+ *   rounded once to float32; a zero row stays zero); sq (may be NULL) [count, n] is exactly 1.0f for every row.  On these
+ *   blocks vgan_outlier_knn with VGAN_OUTLIER_ENGINE_GRAM ranks by d2 = 2 - 2 cos, for every d_s, and a zero row lies at
+ *   d2 = 2 (cosine distance 1) from every row without a special case in the sweep.
+ * vgan_outlier_refine_metric: vgan_outlier_refine under `metric`: the k pairs re-measured in float64 from the raw rows
+ *   (cosine: the dot product and both squared norms in float64, the distance clipped to [0, 2], exactly 1 when a norm is
+ *   0), rounded to float32, re-sorted by (distance, index); kdist as there.  EUCLIDEAN, and MINKOWSKI with p == 2, run
+ *   vgan_outlier_refine's kernel (the same bits); MINKOWSKI with p == 1 runs MANHATTAN.
  * ------------------------------------------------------------------------------------------- */
 #define VGAN_OUTLIER_MAX_K 32
+#define VGAN_OUTLIER_METRIC_EUCLIDEAN 0
+#define VGAN_OUTLIER_METRIC_MANHATTAN 1
+#define VGAN_OUTLIER_METRIC_CHEBYSHEV 2
+#define VGAN_OUTLIER_METRIC_MINKOWSKI 3
+#define VGAN_OUTLIER_METRIC_COSINE 4
+#define VGAN_OUTLIER_MAX_P 8.0
 #define VGAN_OUTLIER_ENGINE_EXACT 0
 #define VGAN_OUTLIER_ENGINE_GRAM 1
 #define VGAN_OUTLIER_KNN_LARGEST 0
@@ -752,6 +783,14 @@ int vgan_outlier_knn(const float* Pq, const float* sq_q, int nq, const float* Pr
 int vgan_outlier_refine(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
                         const int32_t* feat_off, int first, int count, const int32_t* nbr, int k, int32_t* out_idx,
                         float* out_dist, float* kdist, vgan_stream_t stream);
+int vgan_outlier_pack_unit(const float* X, int ldx, int n, int d, const int32_t* feat, const int32_t* feat_off,
+                           const int64_t* col_off, int first, int count, float* packed, float* sq, vgan_stream_t stream);
+int vgan_outlier_knn_metric(const float* Pq, int nq, const float* Pr, int nr, const int32_t* feat_off, const int64_t* col_off,
+                            int first, int count, int k, int exclude_self, int metric, double p, int splits, float* part_d,
+                            int32_t* part_i, int32_t* nbr, vgan_stream_t stream);
+int vgan_outlier_refine_metric(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
+                               const int32_t* feat_off, int first, int count, const int32_t* nbr, int k, int metric, double p,
+                               int32_t* out_idx, float* out_dist, float* kdist, vgan_stream_t stream);
 int vgan_outlier_score(const int32_t* idx, const float* dist, int nq, int k, int count, int method, const float* kdist_ref,
                        const double* lrd_ref, int nr, float* score, const int32_t* score_row, int ld_score, double* lrd_out,
                        vgan_stream_t stream);

@@ -120,6 +120,11 @@ difference of the two paths' ensemble scores.
     and the higher levels (their candidates replayed on the resident index), with draws per second; subspace_contrast of the
     50 sampled subspaces of a two-epoch model (350 to 390 features each, the complement path); and the numpy restatement
     in 16 spawned processes on 256 of the pairs and 16 of the model's subspaces, scaled to all and compared bit for bit.
+--method metric measures the metrics of the neighbour search (d = 784, 50 sampled subspaces of a two-epoch model, n = 2000 and
+    10^4, k = 20): the LOF fit under euclidean, manhattan, chebyshev, minkowski (p = 0.5) and cosine in one session; the
+    Minkowski-family sweep alone (vgan_outlier_knn_metric on resident blocks) as pair-features per second and, for Manhattan
+    and Chebyshev at two vector operations a pair-feature, as a share of the vector peak; torch.cdist(p=1) + topk per subspace
+    on the GPU; and sklearn's brute-force Manhattan LOF on 16 threads on two subspaces, scaled to all.
 --normalize {zscore,robust,minmax} measures score normalisation instead (kNN, k = 5, the three configurations of the KDE
 table): the median warm fit time with normalize=None, with the given mode, and of the host alternative (the raw fit, then
 the numpy statistics and combination on the score matrix fit copied to the host), plus the device statistics and combine
@@ -1890,6 +1895,77 @@ def run_sod(d, n, count, k, ref_set, alpha, reps):
             "score_gather_bytes": gather_bytes, "score_gather_GBps": round(gather_bytes / t_score / 1e9, 1)}
 
 
+VALU_PEAK_OPS = FP32_PEAK / 2  # vector-ALU operations per second: the fp32 peak counts a fused multiply-add as two
+METRIC_ARMS = [("euclidean", None), ("manhattan", None), ("chebyshev", None), ("minkowski", 0.5), ("cosine", None)]
+
+
+def run_metric(d, n, count, k, reps, baselines=True, sklearn_sample=2):
+    """The LOF fit under each of the five metrics in one session (the Euclidean fit is the yardstick); the Minkowski-family
+    sweep (vgan_outlier_knn_metric on resident blocks) alone, as pair-features per second and, for Manhattan and Chebyshev,
+    whose pair-feature costs two vector operations, as a share of the vector peak; torch.cdist(p=1) + topk per subspace on
+    the GPU; sklearn's brute-force Manhattan LOF on 16 threads on sklearn_sample subspaces, scaled to all."""
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    row = {"method": "metric", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_neighbors": k, "d_s_min": int(dims.min()),
+           "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()), "lof_fit_s": {}, "lof_fit_reps_s": {}, "sweep": {}}
+    fitted = {}
+    for metric, pw in METRIC_ARMS:
+        name = metric if pw is None else f"{metric}_p{pw:g}"
+        ens = vgan_amd.SubspaceEnsemble(m, p, method="lof", n_neighbors=k, metric=metric, p=pw)
+        t, ts = timed(lambda: ens.fit(Xd), reps)
+        row["lof_fit_s"][name], row["lof_fit_reps_s"][name] = round(t, 5), ts
+        fitted[name] = ens
+    row["lof_fit_over_euclidean"] = {name: round(t / row["lof_fit_s"]["euclidean"], 3) for name, t in row["lof_fit_s"].items()}
+    padded = -(-n // 64) * 64
+    pair_features = float(padded) * padded * float(((dims + 3) // 4 * 4).sum())
+    for name, code, pw in (("manhattan", 1, 0.0), ("chebyshev", 2, 0.0), ("minkowski_p0.5", 3, 0.5)):
+        ens = fitted[name]
+        chunks = [(first, cnt, Pq) for first, cnt, _, _, Pq, _, _, _ in ens._chunks(None)]
+        nbr = torch.empty(S, n, k, dtype=torch.int32, device="cuda")
+        J = {first: ens._splits(n, n, cnt) for first, cnt, _ in chunks}
+        parts = {first: (torch.empty(cnt * J[first] * n * k, dtype=torch.float32, device="cuda"),
+                         torch.empty(cnt * J[first] * n * k, dtype=torch.int32, device="cuda")) for first, cnt, _ in chunks}
+
+        def sweep_launches():
+            for first, cnt, P in chunks:
+                ens.ops.outlier_knn_metric(P, n, P, n, ens._table, first, cnt, k, True, code, pw, J[first], nbr[first:first + cnt],
+                                           *(parts[first] if J[first] > 1 else (None, None)))
+
+        t, ts = timed(sweep_launches, max(reps, 5))
+        entry = {"s": round(t, 6), "reps_s": ts, "splits": sorted(set(J.values())), "pair_features_per_s": round(pair_features / t, 1)}
+        if code != 3:
+            entry["valu_ops_per_s"] = round(2.0 * pair_features / t, 1)
+            entry["frac_vector_peak"] = round(2.0 * pair_features / t / VALU_PEAK_OPS, 4)
+        row["sweep"][name] = entry
+        del chunks, parts, nbr
+    if baselines:
+        feats = [torch.as_tensor(np.flatnonzero(m[s]), device="cuda") for s in range(S)]
+
+        def torch_l1():
+            out = []
+            for f in feats:
+                Xs = Xd[:, f].contiguous()
+                for q0 in range(0, n, 4096):
+                    D = torch.cdist(Xs[q0:q0 + 4096], Xs, p=1.0)
+                    D[torch.arange(D.shape[0], device="cuda"), torch.arange(q0, q0 + D.shape[0], device="cuda")] = float("inf")
+                    out.append(torch.topk(D, k, dim=1, largest=False))
+            return out
+
+        t, ts = timed(torch_l1, reps)
+        row.update({"torch_cdist_p1_topk_s": round(t, 5), "torch_cdist_p1_topk_reps_s": ts,
+                    "torch_over_manhattan_sweep": round(t / row["sweep"]["manhattan"]["s"], 3)})
+        from sklearn.neighbors import LocalOutlierFactor
+        pick = list(range(min(sklearn_sample, S)))
+        t0 = time.perf_counter()
+        for s in pick:
+            LocalOutlierFactor(n_neighbors=k, algorithm="brute", metric="manhattan", n_jobs=16).fit(X[:, np.flatnonzero(m[s])])
+        t_sk = (time.perf_counter() - t0) * S / len(pick)
+        row.update({"sklearn_brute_manhattan_16_threads_scaled_s": round(t_sk, 3), "sklearn_subspaces_timed": len(pick),
+                    "sklearn_over_manhattan_fit": round(t_sk / row["lof_fit_s"]["manhattan"], 1)})
+    return row
+
+
 def _hics_numpy_contrasts(job):
     """Worker of run_hics: the plain numpy restatement of the contrast (tests/hics_ref.py's, with the library's vectorised
     draws) for a list of feature sets; runs in a spawned process that never touches the GPU."""
@@ -2023,7 +2099,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics", "metric"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
     ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / kpca / ae / deepsvdd: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
@@ -2218,6 +2294,14 @@ def main():
             pool.join()
         if not args.shape:  # where the two workgroup shapes of the draw kernel meet
             out["workgroup_shapes"] = run_hics_shapes(64, [1024, 4096] if args.quick else [4096, 16384, 32768, 65536], args.reps)
+        configs = []
+    if args.method == "metric":
+        shapes = [(784, 2000, 10)] if args.quick else [(784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_metric(d, n, count, 20, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "gmm":
         shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(10, 10_000, 50), (10, 50_000, 500), (784, 10_000, 50),

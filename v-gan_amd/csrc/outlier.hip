@@ -15,10 +15,14 @@
 //                 kde    pivot sweep (min d2), sum sweep (exp2 terms against the pivot, uint64 fixed point: the same sum
 //                        for every J), score (Gaussian -log density in float64)
 //   3. combine  out[i] = sum_s p_s score_s[i] in float64, subspaces in order
+// Other metrics of knn (vgan_outlier_knn_metric, _pack_unit, _refine_metric): Manhattan, Chebyshev and Minkowski lists come from
+// the vector-ALU producer of outlier_metric.hpp on uncentred blocks (ranked by the float32 sum, maximum or sum of p-th powers);
+// cosine lists from the Gram engine on rows packed to unit length (d2 = 2 - 2 cos); refine re-measures under the metric.
 #include <float.h>
 #include <limits.h>
 
 #include "outlier_dist.hpp"
+#include "outlier_metric.hpp"
 
 namespace vgan {
 
@@ -118,6 +122,76 @@ __global__ __launch_bounds__(kBlock, 2) void outlier_knn_kernel(const float* __r
                 }
         }
     }
+}
+
+// The tail of outlier_knn_kernel as a routine, for the metric kernel below: merges the four waves' lists of each row through lds
+// (KnnLds::kMerge floats, the producer done with it) and stores the k-list of row q, or the slice's list when the reference rows
+// are split.  outlier_knn_kernel keeps its tail spelt out: routed through this routine the compiler allocates its registers
+// differently (K = 8, exact engine: 126 VGPRs against 84), and its device code is to stay the one that was measured.
+template <int K>
+__device__ __forceinline__ void knn_merge_store(TopK<K>& top, float* lds, int q, int nq, int k, int splits, float* __restrict__ part_d,
+                                                int32_t* __restrict__ part_i, int32_t* __restrict__ nbr) {
+    const int z = blockIdx.z, slice = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    float* md = lds;
+    int* mi = reinterpret_cast<int*>(lds + 2 * K * kOTile);
+    for (int round = 0; round < 2; ++round) {
+        const int hi = round == 0 ? 2 : 1;  // waves [hi, 2 hi) give, waves [0, hi) take
+        if (wave >= hi && wave < 2 * hi) {
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+                md[((wave - hi) * K + t) * kOTile + lane] = top.d[t];
+                mi[((wave - hi) * K + t) * kOTile + lane] = top.i[t];
+            }
+        }
+        __syncthreads();
+        if (wave < hi) {
+#pragma unroll
+            for (int t = 0; t < K; ++t) top.push(md[(wave * K + t) * kOTile + lane], mi[(wave * K + t) * kOTile + lane]);
+        }
+        __syncthreads();
+    }
+    if (wave == 0 && q < nq) {
+        if (splits == 1) {
+            int32_t* o = nbr + ((long)z * nq + q) * k;
+#pragma unroll
+            for (int t = 0; t < K; ++t)
+                if (t < k) o[t] = top.i[t];
+        } else {
+            const long off = (((long)z * splits + slice) * nq + q) * k;
+#pragma unroll
+            for (int t = 0; t < K; ++t)
+                if (t < k) {
+                    part_d[off + t] = top.d[t];
+                    part_i[off + t] = top.i[t];
+                }
+        }
+    }
+}
+
+// The same selection over the Minkowski-family producer (outlier_metric.hpp); the candidates are ranked by (g, index)
+template <int K, class Term>
+__global__ __launch_bounds__(kBlock, 2) void outlier_knn_metric_kernel(const float* __restrict__ Pq, int nq, const float* __restrict__ Pr,
+                                                                       int nr, const int32_t* __restrict__ feat_off,
+                                                                       const int64_t* __restrict__ col_off, int first, int k,
+                                                                       int exclude_self, int splits, Term term, float* __restrict__ part_d,
+                                                                       int32_t* __restrict__ part_i, int32_t* __restrict__ nbr) {
+    constexpr int kMerge = 2 * 2 * K * kOTile;
+    __shared__ __attribute__((aligned(16))) float lds[kMetricLdsFloats > kMerge ? kMetricLdsFloats : kMerge];
+    const int q = blockIdx.x * kOTile + (threadIdx.x & 63);
+
+    TopK<K> top;
+    top.init();
+    outlier_metric_distances(Pq, nq, Pr, nr, feat_off, col_off, first, splits, term, lds, [&](const float (&g)[16], int c0) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = c0 + j;
+            if (c < nr && !(exclude_self && c == q)) top.push(g[j], c);
+        }
+    });
+
+    knn_merge_store<K>(top, lds, q, nq, k, splits, part_d, part_i, nbr);
 }
 
 // the J partial lists of a (subspace, query row) -> its k-list; one thread per row
@@ -281,6 +355,78 @@ __global__ void outlier_refine_kernel(const float* __restrict__ Xq, int ldq, int
     }
 }
 
+// outlier_pack_kernel without a centre, every row scaled to unit length: packed[...] = (float)(X[i, f] / |X[i, F_s]|), the norm
+// and the quotient in float64 (a zero row stays zero); sq = 1 for every row, so that the Gram engine's d2 is 2 - 2 cos and a
+// zero row lies at d2 = 2 (cosine distance 1) from every row.
+__global__ void outlier_pack_unit_kernel(const float* __restrict__ X, int ldx, int n, const int32_t* __restrict__ feat,
+                                         const int32_t* __restrict__ feat_off, const int64_t* __restrict__ col_off, int first,
+                                         float* __restrict__ packed, float* __restrict__ sq) {
+    const int z = blockIdx.y, s = first + z;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f0 = feat_off[s], ds = feat_off[s + 1] - f0, w = (ds + 3) & ~3;
+    float* P = packed + (col_off[s] - col_off[first]) * n;
+    for (int i = blockIdx.x * kOTile + wave; i < min(n, (blockIdx.x + 1) * kOTile); i += kBlock / kWave) {
+        double acc = 0.0;
+        for (int c = lane; c < ds; c += kWave) {
+            const double v = X[(long)i * ldx + feat[f0 + c]];
+            acc = fma(v, v, acc);
+        }
+        acc = wave_sum(acc);
+        const double scale = acc > 0.0 ? 1.0 / sqrt(acc) : 0.0;
+        for (int c = lane; c < w; c += kWave) P[(long)i * w + c] = c < ds ? (float)((double)X[(long)i * ldx + feat[f0 + c]] * scale) : 0.f;
+        if (sq != nullptr && lane == 0) sq[(long)z * n + i] = 1.f;
+    }
+}
+
+// outlier_refine_kernel under another metric (METRIC: VGAN_OUTLIER_METRIC_*), float64 from the raw rows, features ascending:
+// sum |e|, max |e|, (sum |e|^p)^(1 / p), or 1 - <x, y> / (|x| |y|) clipped to [0, 2] (exactly 1 when a norm is 0)
+template <int METRIC>
+__global__ void outlier_refine_metric_kernel(const float* __restrict__ Xq, int ldq, int nq, const float* __restrict__ Xr, int ldr, int nr,
+                                             const int32_t* __restrict__ feat, const int32_t* __restrict__ feat_off, int first,
+                                             int count, const int32_t* __restrict__ nbr, int k, double p, int32_t* __restrict__ out_idx,
+                                             float* __restrict__ out_dist, float* __restrict__ kdist) {
+    const long row = (long)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (row >= (long)count * nq) return;
+    const int lane = threadIdx.x & 63;
+    const int z = (int)(row / nq), q = (int)(row % nq), s = first + z;
+    const int f0 = feat_off[s], ds = feat_off[s + 1] - f0;
+    int idx = INT_MAX;
+    float dist = INFINITY;
+    if (lane < k) idx = nbr[row * k + lane];
+    if (idx >= 0 && idx < nr) {
+        const float* xq = Xq + (long)q * ldq;
+        const float* xr = Xr + (long)idx * ldr;
+        double acc = 0.0, nx = 0.0, ny = 0.0;
+        for (int c = 0; c < ds; ++c) {
+            const int f = feat[f0 + c];
+            const double x = xq[f], y = xr[f], e = fabs(x - y);
+            if constexpr (METRIC == VGAN_OUTLIER_METRIC_MANHATTAN) acc += e;
+            if constexpr (METRIC == VGAN_OUTLIER_METRIC_CHEBYSHEV) acc = fmax(acc, e);
+            if constexpr (METRIC == VGAN_OUTLIER_METRIC_MINKOWSKI) acc += pow(e, p);
+            if constexpr (METRIC == VGAN_OUTLIER_METRIC_COSINE) {
+                acc = fma(x, y, acc);
+                nx = fma(x, x, nx);
+                ny = fma(y, y, ny);
+            }
+        }
+        if constexpr (METRIC == VGAN_OUTLIER_METRIC_MINKOWSKI) acc = pow(acc, 1.0 / p);
+        if constexpr (METRIC == VGAN_OUTLIER_METRIC_COSINE)
+            acc = (nx > 0.0 && ny > 0.0) ? fmin(fmax(1.0 - acc / (sqrt(nx) * sqrt(ny)), 0.0), 2.0) : 1.0;
+        dist = (float)acc;
+    }
+    int rank = 0;
+    for (int u = 0; u < k; ++u) {
+        const float du = __shfl(dist, u, 64);
+        const int iu = __shfl(idx, u, 64);
+        rank += cand_less(du, iu, dist, idx) ? 1 : 0;
+    }
+    if (lane < k) {
+        out_idx[row * k + rank] = idx;
+        out_dist[row * k + rank] = dist;
+        if (kdist != nullptr && rank == k - 1) kdist[row] = dist;
+    }
+}
+
 // One thread per (subspace, query row) over its sorted list (dist, idx).
 //   method 0/1/2: kNN largest / mean / median -> score
 //   method 3:     lrd(p) = 1 / (mean_o max(kdist_ref(o), d(p, o)) + 1e-10) -> lrd_out
@@ -351,6 +497,34 @@ static int launch_knn(const float* Pq, const float* sqq, int nq, const float* Pr
     return VGAN_OK;
 }
 
+template <int K, class Term>
+static int launch_knn_metric(const float* Pq, int nq, const float* Pr, int nr, const int32_t* feat_off, const int64_t* col_off, int first,
+                             int count, int k, int exclude_self, Term term, int splits, float* part_d, int32_t* part_i, int32_t* nbr,
+                             hipStream_t st) {
+    hipLaunchKernelGGL((outlier_knn_metric_kernel<K, Term>), dist_grid(nq, splits, count), dim3(kBlock), 0, st, Pq, nq, Pr, nr, feat_off,
+                       col_off, first, k, exclude_self, splits, term, part_d, part_i, nbr);
+    VGAN_CHECK_LAUNCH();
+    if (splits > 1) {
+        const long rows = (long)count * nq;
+        hipLaunchKernelGGL(outlier_knn_merge_kernel<K>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, part_d, part_i, nq,
+                           count, k, splits, nbr);
+        VGAN_CHECK_LAUNCH();
+    }
+    return VGAN_OK;
+}
+
+template <class Term>
+static int launch_knn_metric_k(const float* Pq, int nq, const float* Pr, int nr, const int32_t* feat_off, const int64_t* col_off,
+                               int first, int count, int k, int exclude_self, Term term, int splits, float* part_d, int32_t* part_i,
+                               int32_t* nbr, hipStream_t st) {
+    if (k <= 8) return launch_knn_metric<8>(Pq, nq, Pr, nr, feat_off, col_off, first, count, k, exclude_self, term, splits, part_d, part_i, nbr, st);
+    if (k <= 16) return launch_knn_metric<16>(Pq, nq, Pr, nr, feat_off, col_off, first, count, k, exclude_self, term, splits, part_d, part_i, nbr, st);
+    return launch_knn_metric<32>(Pq, nq, Pr, nr, feat_off, col_off, first, count, k, exclude_self, term, splits, part_d, part_i, nbr, st);
+}
+
+// p of VGAN_OUTLIER_METRIC_MINKOWSKI: finite, in (0, 8]
+static bool minkowski_p_ok(double p) { return p > 0.0 && p <= VGAN_OUTLIER_MAX_P; }  // false for NaN
+
 }  // namespace vgan
 
 using namespace vgan;
@@ -377,6 +551,34 @@ extern "C" int vgan_outlier_knn(const float* Pq, const float* sq_q, int nq, cons
     if (k <= 8) return launch_knn<8>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
     if (k <= 16) return launch_knn<16>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
     return launch_knn<32>(Pq, sq_q, nq, Pr, sq_r, nr, feat_off, col_off, first, count, k, exclude_self, engine, splits, part_d, part_i, nbr, st);
+}
+
+extern "C" int vgan_outlier_pack_unit(const float* X, int ldx, int n, int d, const int32_t* feat, const int32_t* feat_off,
+                                      const int64_t* col_off, int first, int count, float* packed, float* sq, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(X && feat && feat_off && col_off && packed && n > 0 && d > 0 && ldx >= d && first >= 0 && count > 0);
+    VGAN_CHECK_ARG(count <= 65535 && aligned16(packed));
+    hipLaunchKernelGGL(outlier_pack_unit_kernel, dim3((n + kOTile - 1) / kOTile, count), dim3(kBlock), 0, (hipStream_t)stream, X, ldx, n,
+                       feat, feat_off, col_off, first, packed, sq);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_outlier_knn_metric(const float* Pq, int nq, const float* Pr, int nr, const int32_t* feat_off, const int64_t* col_off,
+                                       int first, int count, int k, int exclude_self, int metric, double p, int splits, float* part_d,
+                                       int32_t* part_i, int32_t* nbr, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Pq && Pr && feat_off && col_off && nbr && nq > 0 && nr > 0 && first >= 0 && count > 0 && count <= 65535);
+    VGAN_CHECK_ARG(k >= 1 && k <= VGAN_OUTLIER_MAX_K);
+    VGAN_CHECK_ARG(nr >= k + (exclude_self ? 1 : 0) && (!exclude_self || nq == nr));
+    VGAN_CHECK_ARG(metric == VGAN_OUTLIER_METRIC_MANHATTAN || metric == VGAN_OUTLIER_METRIC_CHEBYSHEV ||
+                   metric == VGAN_OUTLIER_METRIC_MINKOWSKI);
+    VGAN_CHECK_ARG(metric != VGAN_OUTLIER_METRIC_MINKOWSKI || minkowski_p_ok(p));
+    VGAN_CHECK_ARG(dist_args_ok(VGAN_OUTLIER_ENGINE_EXACT, false, splits, Pq, Pr) && (splits == 1 || (part_d && part_i)));
+    const hipStream_t st = (hipStream_t)stream;
+    if (metric == VGAN_OUTLIER_METRIC_CHEBYSHEV)
+        return launch_knn_metric_k(Pq, nq, Pr, nr, feat_off, col_off, first, count, k, exclude_self, MetricLinf{}, splits, part_d, part_i, nbr, st);
+    if (metric == VGAN_OUTLIER_METRIC_MANHATTAN || p == 1.0)  // p == 1 is the Manhattan path
+        return launch_knn_metric_k(Pq, nq, Pr, nr, feat_off, col_off, first, count, k, exclude_self, MetricL1{}, splits, part_d, part_i, nbr, st);
+    return launch_knn_metric_k(Pq, nq, Pr, nr, feat_off, col_off, first, count, k, exclude_self, MetricLp{(float)p}, splits, part_d, part_i, nbr, st);
 }
 
 extern "C" int vgan_outlier_kde(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
@@ -414,6 +616,37 @@ extern "C" int vgan_outlier_refine(const float* Xq, int ldq, int nq, const float
     const long rows = (long)count * nq;
     hipLaunchKernelGGL(outlier_refine_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(kBlock), 0, (hipStream_t)stream, Xq, ldq, nq, Xr, ldr,
                        nr, feat, feat_off, first, count, nbr, k, out_idx, out_dist, kdist);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_outlier_refine_metric(const float* Xq, int ldq, int nq, const float* Xr, int ldr, int nr, int d, const int32_t* feat,
+                                          const int32_t* feat_off, int first, int count, const int32_t* nbr, int k, int metric, double p,
+                                          int32_t* out_idx, float* out_dist, float* kdist, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Xq && Xr && feat && feat_off && nbr && out_idx && out_dist && nq > 0 && nr > 0 && d > 0);
+    VGAN_CHECK_ARG(ldq >= d && ldr >= d && first >= 0 && count > 0 && k >= 1 && k <= VGAN_OUTLIER_MAX_K && nr >= k);
+    VGAN_CHECK_ARG(metric >= VGAN_OUTLIER_METRIC_EUCLIDEAN && metric <= VGAN_OUTLIER_METRIC_COSINE);
+    VGAN_CHECK_ARG(metric != VGAN_OUTLIER_METRIC_MINKOWSKI || minkowski_p_ok(p));
+    if (metric == VGAN_OUTLIER_METRIC_MINKOWSKI && p == 2.0) metric = VGAN_OUTLIER_METRIC_EUCLIDEAN;  // the Euclidean path
+    if (metric == VGAN_OUTLIER_METRIC_MINKOWSKI && p == 1.0) metric = VGAN_OUTLIER_METRIC_MANHATTAN;  // the Manhattan path
+    const long rows = (long)count * nq;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    const hipStream_t st = (hipStream_t)stream;
+    if (metric == VGAN_OUTLIER_METRIC_EUCLIDEAN)
+        hipLaunchKernelGGL(outlier_refine_kernel, grid, dim3(kBlock), 0, st, Xq, ldq, nq, Xr, ldr, nr, feat, feat_off, first, count, nbr, k,
+                           out_idx, out_dist, kdist);
+    else if (metric == VGAN_OUTLIER_METRIC_MANHATTAN)
+        hipLaunchKernelGGL(outlier_refine_metric_kernel<VGAN_OUTLIER_METRIC_MANHATTAN>, grid, dim3(kBlock), 0, st, Xq, ldq, nq, Xr, ldr, nr,
+                           feat, feat_off, first, count, nbr, k, p, out_idx, out_dist, kdist);
+    else if (metric == VGAN_OUTLIER_METRIC_CHEBYSHEV)
+        hipLaunchKernelGGL(outlier_refine_metric_kernel<VGAN_OUTLIER_METRIC_CHEBYSHEV>, grid, dim3(kBlock), 0, st, Xq, ldq, nq, Xr, ldr, nr,
+                           feat, feat_off, first, count, nbr, k, p, out_idx, out_dist, kdist);
+    else if (metric == VGAN_OUTLIER_METRIC_MINKOWSKI)
+        hipLaunchKernelGGL(outlier_refine_metric_kernel<VGAN_OUTLIER_METRIC_MINKOWSKI>, grid, dim3(kBlock), 0, st, Xq, ldq, nq, Xr, ldr, nr,
+                           feat, feat_off, first, count, nbr, k, p, out_idx, out_dist, kdist);
+    else
+        hipLaunchKernelGGL(outlier_refine_metric_kernel<VGAN_OUTLIER_METRIC_COSINE>, grid, dim3(kBlock), 0, st, Xq, ldq, nq, Xr, ldr, nr,
+                           feat, feat_off, first, count, nbr, k, p, out_idx, out_dist, kdist);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }

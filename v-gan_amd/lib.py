@@ -141,6 +141,9 @@ SIGNATURES = {
     "vgan_outlier_pack": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "vgan_outlier_knn": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "vgan_outlier_refine": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "vgan_outlier_pack_unit": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "vgan_outlier_knn_metric": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _d, _i, _p, _p, _p, _p]),
+    "vgan_outlier_refine_metric": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _i, _d, _p, _p, _p, _p]),
     "vgan_outlier_score": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p]),
     "vgan_outlier_kde": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "vgan_outlier_combine": (_i, [_p, _i, _i, _i, _p, _p, _p]),
@@ -219,7 +222,7 @@ SIGNATURES = {
     "vgan_hics_contrast": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _u64, _i, _p, _p, _p, _p, _p, _p]),
 }
 
-ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the vgan_hics_* ones last) leave it
+ABI_VERSION = 11  # counts layout / signature changes; entries that only add symbols (the metric entries of the neighbour search last) leave it
 _lib = None
 
 

@@ -735,6 +735,31 @@ class HipOps:
                                                 _ptr(feat), _ptr(feat_off), int(first), int(count), _ptr(nbr), int(k), _ptr(out_idx),
                                                 _ptr(out_dist), _ptr(kdist), self._stream()), "vgan_outlier_refine")
 
+    # The other metrics of the neighbour search (metric: VGAN_OUTLIER_METRIC_*, p: the Minkowski exponent, else unused)
+    def outlier_pack_unit(self, X, table, first, count, packed, sq=None):
+        _mat(X, "X"), _vec(packed, "packed")
+        feat, feat_off, col_off = table
+        n, d = X.shape
+        _lib.check(self.lib.vgan_outlier_pack_unit(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(col_off), int(first),
+                                                   int(count), _ptr(packed), _ptr(sq), self._stream()), "vgan_outlier_pack_unit")
+
+    def outlier_knn_metric(self, Pq, nq, Pr, nr, table, first, count, k, exclude_self, metric, p, splits, nbr, part_d=None,
+                           part_i=None):
+        _vec(nbr, "nbr", torch.int32)
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_outlier_knn_metric(_ptr(Pq), int(nq), _ptr(Pr), int(nr), _ptr(feat_off), _ptr(col_off), int(first),
+                                                    int(count), int(k), int(bool(exclude_self)), int(metric), float(p), int(splits),
+                                                    _ptr(part_d), _ptr(part_i), _ptr(nbr), self._stream()), "vgan_outlier_knn_metric")
+
+    def outlier_refine_metric(self, Xq, Xr, table, first, count, nbr, k, metric, p, out_idx, out_dist, kdist=None):
+        _mat(Xq, "Xq"), _mat(Xr, "Xr"), _vec(out_idx, "out_idx", torch.int32), _vec(out_dist, "out_dist")
+        feat, feat_off, _ = table
+        assert Xq.shape[1] == Xr.shape[1]
+        _lib.check(self.lib.vgan_outlier_refine_metric(_ptr(Xq), Xq.stride(0), Xq.shape[0], _ptr(Xr), Xr.stride(0), Xr.shape[0],
+                                                       Xq.shape[1], _ptr(feat), _ptr(feat_off), int(first), int(count), _ptr(nbr), int(k),
+                                                       int(metric), float(p), _ptr(out_idx), _ptr(out_dist), _ptr(kdist), self._stream()),
+                   "vgan_outlier_refine_metric")
+
     def outlier_score(self, idx, dist, nq, k, count, method, score=None, score_row=None, kdist_ref=None, lrd_ref=None, nr=0,
                       lrd_out=None):
         ld = score.stride(0) if score is not None else nq

@@ -9,7 +9,10 @@ excludes nothing.  kNN scores are the k-th ("largest"), mean or median distance;
 
     log p_s(q) = logsumexp_r(-dist_s(q, r)^2 / (2 h_s^2)) - log N - d_s log h_s - (d_s / 2) log(2 pi),  score_s = -log p_s
 
-over the N reference rows r, which is sklearn's ``KernelDensity(bandwidth=h_s).score_samples`` negated (pyod's KDE);
+kNN, LOF and ``kneighbors`` also take the Manhattan, Chebyshev, Minkowski (p in (0, 8]) and cosine distances (``metric`` /
+``p`` of ``SubspaceEnsemble``, whose docstring has the definitions): the Minkowski family on a vector-ALU producer of its own
+(csrc/outlier_metric.hpp), the cosine distance as the Gram engine on unit rows; the scores after the lists are metric free.
+The density below is over the N reference rows r, which is sklearn's ``KernelDensity(bandwidth=h_s).score_samples`` negated (pyod's KDE);
 ``fit`` leaves row q's own index out (N = n - 1), ``decision_function`` nothing (N = n).  The ensemble score is
 sum_s p_s score_s in float64, subspaces in order.
 
@@ -133,6 +136,7 @@ extra attributes its ``fit`` publishes: the ``_SubspaceScorer`` docstring has th
 ``build_ensemble`` maps a method string to the unfitted detector; the models' ``outlier_ensemble`` and the subspace search of
 ``vgan_amd.hics`` (HiCS, a source of subspaces beside the trained generator) both go through it.
 """
+import inspect
 import math
 import os
 
@@ -158,6 +162,12 @@ COMBINATIONS = {"sum": 0, "max": 1}  # VGAN_OUTLIER_COMBINE_*
 PROBA_METHODS = ("linear", "unify")
 
 
+METRICS = {"euclidean": 0, "manhattan": 1, "chebyshev": 2, "minkowski": 3, "cosine": 4}  # VGAN_OUTLIER_METRIC_*
+METRIC_ALIASES = {"l2": "euclidean", "l1": "manhattan", "cityblock": "manhattan"}
+MINKOWSKI_FAMILY = ("manhattan", "chebyshev", "minkowski")  # the metrics of the vector-ALU producer (csrc/outlier_metric.hpp)
+MAX_P = 8.0  # VGAN_OUTLIER_MAX_P
+
+
 def _is_int(v):
     return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
@@ -177,6 +187,28 @@ def check_reference_rows(n_ref, k, exclude_self):
     if n_ref < need:
         what = "fit needs at least n_neighbors + 1" if exclude_self else "scoring needs at least n_neighbors"
         raise ValueError(f"{what} reference rows ({need}), got {n_ref}")
+
+
+def check_metric(metric, p=None):
+    """(name, p): the canonical metric name and the Minkowski exponent (None for every other metric).  Aliases: "l2" is
+    "euclidean", "l1" and "cityblock" are "manhattan".  p is a finite float in (0, 8] and is given with "minkowski" only (the
+    default there is 2, as in sklearn); "minkowski" with p == 1 IS "manhattan" and with p == 2 "euclidean"."""
+    if not isinstance(metric, str) or METRIC_ALIASES.get(metric, metric) not in METRICS:
+        raise ValueError(f"metric must be one of {sorted(METRICS) + sorted(METRIC_ALIASES)}, got {metric!r}")
+    metric = METRIC_ALIASES.get(metric, metric)
+    if metric != "minkowski":
+        if p is not None:
+            raise ValueError(f"p is the exponent of metric='minkowski'; got p={p!r} with metric={metric!r}")
+        return metric, None
+    p = 2.0 if p is None else p
+    if not _is_real(p) or not (np.isfinite(p) and 0.0 < float(p) <= MAX_P):
+        raise ValueError(f"p must be a finite float in (0, {MAX_P:g}], got {p!r}")
+    p = float(p)
+    if p == 1.0:
+        return "manhattan", None
+    if p == 2.0:
+        return "euclidean", None
+    return metric, p
 
 
 def check_bandwidth(bandwidth):
@@ -346,14 +378,16 @@ class _SubspaceScorer:
     _decisions = None  # (threshold_, labels_), taken from decision_scores_ on first use
     score_center_ = score_scale_ = None
 
-    def _configure(self, subspaces, proba, engine, workspace_bytes, normalize, combination, contamination):
+    def _configure(self, subspaces, proba, engine, workspace_bytes, normalize, combination, contamination, plan_engine=None):
+        """plan_engine: the one engine group of a metric that has a single producer ("exact": uncentred blocks without
+        norms; "gram"); the engine argument and the environment then do not reach the plan."""
         self.normalize = check_normalize(normalize)
         self.combination = check_combination(combination)
         self.contamination = check_contamination(contamination)
-        if engine == "auto":
+        if engine == "auto" and plan_engine is None:
             engine = os.environ.get(ENGINE_ENV, "auto") or "auto"
         self.engine = engine
-        self.plan = SubspacePlan(subspaces, engine=engine)
+        self.plan = SubspacePlan(subspaces, engine=engine if plan_engine is None else plan_engine)
         self.proba = np.asarray(proba, dtype=np.float64).reshape(-1)
         if self.proba.shape[0] != self.plan.count:
             raise ValueError(f"proba has {self.proba.shape[0]} entries for {self.plan.count} subspaces")
@@ -495,17 +529,45 @@ class _NeighborScorer(_SubspaceScorer):
     _begin_fit returns in _X; _chunks is the chunk loop of whatever else sweeps the query rows over the reference rows."""
 
     _X = None
+    metric, p = "euclidean", None  # set at construction for the detectors that take a metric (_MetricKeywords)
 
     def _configure_neighbors(self, n_neighbors, splits, least=1):
         self.n_neighbors = check_neighbors(n_neighbors, least)
         self._configure_splits(splits)
 
+    def _metric_engine(self, engine):
+        """The plan_engine of _configure under self.metric: None for the Euclidean distance (the engines by subspace size, as
+        ever); "exact" for the Minkowski family, whose one producer reads uncentred blocks without norms; "gram" for the
+        cosine distance, which is the Gram engine on unit rows at every d_s.  Either way all subspaces form one engine
+        group, so no chunk breaks at d_s = 32."""
+        if self.metric == "euclidean":
+            return None
+        if engine not in ("auto", "exact", "gram"):
+            raise ValueError(f"engine must be 'auto', 'exact' or 'gram', got {engine!r}")
+        if self.metric in MINKOWSKI_FAMILY:
+            if engine != "auto":
+                raise ValueError(f"metric {self.metric!r} has one distance producer: engine must be 'auto', got {engine!r}")
+            return "exact"
+        if engine == "exact":
+            raise ValueError("metric 'cosine' runs on the Gram engine: engine must be 'auto' or 'gram', got 'exact'")
+        return "gram"
+
     def _check_fit_rows(self, n):
         check_reference_rows(n, self.n_neighbors, exclude_self=True)
 
+    def _pack_metric(self, X, first, count, gram):
+        if self.metric != "cosine":
+            return self._pack(X, first, count, gram)
+        n = X.shape[0]
+        cols = int(self.plan.col_off[first + count] - self.plan.col_off[first])
+        packed = torch.empty(n * cols, dtype=torch.float32, device=X.device)
+        sq = torch.empty(count, n, dtype=torch.float32, device=X.device)
+        self.ops.outlier_pack_unit(X, self._table, first, count, packed, sq)
+        return packed, sq
+
     def _blocks(self, Xq, first, count, gram):
-        Pr, sqr = self._pack(self._X, first, count, gram)
-        Pq, sqq = (Pr, sqr) if Xq is None else self._pack(Xq, first, count, gram)
+        Pr, sqr = self._pack_metric(self._X, first, count, gram)
+        Pq, sqq = (Pr, sqr) if Xq is None else self._pack_metric(Xq, first, count, gram)
         return Pq, sqq, Pr, sqr
 
     def _chunks(self, Xq, only=None):
@@ -533,12 +595,19 @@ class _NeighborScorer(_SubspaceScorer):
             if J > 1:
                 part_d = torch.empty(count * J * nq * k, dtype=torch.float32, device=Xr.device)
                 part_i = torch.empty(count * J * nq * k, dtype=torch.int32, device=Xr.device)
-            self.ops.outlier_knn(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, k, Xq is None, engine, J, nbr, part_d, part_i)
+            metric, p = METRICS[self.metric], 0.0 if self.p is None else self.p
+            if self.metric in MINKOWSKI_FAMILY:
+                self.ops.outlier_knn_metric(Pq, nq, Pr, nr, self._table, first, count, k, Xq is None, metric, p, J, nbr, part_d, part_i)
+            else:  # Euclidean, or cosine as the Gram engine on unit rows
+                self.ops.outlier_knn(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, k, Xq is None, engine, J, nbr, part_d, part_i)
             del Pq, Pr, sqq, sqr, part_d, part_i
             idx = torch.empty_like(nbr)
             dist = torch.empty(count, nq, k, dtype=torch.float32, device=Xr.device)
-            self.ops.outlier_refine(Xr if Xq is None else Xq, Xr, self._table, first, count, nbr, k, idx, dist,
-                                    None if kdist is None else kdist[first:first + count])
+            kd = None if kdist is None else kdist[first:first + count]
+            if self.metric == "euclidean":
+                self.ops.outlier_refine(Xr if Xq is None else Xq, Xr, self._table, first, count, nbr, k, idx, dist, kd)
+            else:
+                self.ops.outlier_refine_metric(Xr if Xq is None else Xq, Xr, self._table, first, count, nbr, k, metric, p, idx, dist, kd)
             yield first, count, idx, dist
 
     def kneighbors(self, X=None):
@@ -567,7 +636,22 @@ class _NeighborScorer(_SubspaceScorer):
             op(per, self._fill)
 
 
-class SubspaceEnsemble(_NeighborScorer):
+class _MetricKeywords(type):
+    """Construction of a detector that takes ``metric=`` and ``p=``.  The two are keyword-only arguments of the call of the
+    class, not of ``__init__``: the keyword list of ``SubspaceEnsemble.__init__`` is a fixed surface (callers and the
+    constructor test read it through ``inspect``), and the distance is not one of the detector's own settings but what its
+    neighbour search measures.  The call checks them (check_metric: ValueError), keeps the canonical (metric, p) on the new
+    instance and then runs ``__init__`` with the remaining arguments, which finds them there.  ``inspect.signature`` of the
+    class shows the full list (the class's ``__signature__``)."""
+
+    def __call__(cls, *args, metric="euclidean", p=None, **kw):
+        self = cls.__new__(cls)
+        self.metric, self.p = check_metric(metric, p)
+        self.__init__(*args, **kw)
+        return self
+
+
+class SubspaceEnsemble(_NeighborScorer, metaclass=_MetricKeywords):
     """kNN / LOF / KDE detector per subspace, probability-weighted sum of the scores (pyod-style: ``fit`` sets
     ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying).
 
@@ -586,7 +670,30 @@ class SubspaceEnsemble(_NeighborScorer):
     maximization; proba is not used).  contamination in (0, 0.5]: after ``fit``, ``threshold_`` is that upper percentile
     of ``decision_scores_`` and ``labels_`` marks the rows above it (both taken on first use); ``predict`` /
     ``predict_proba`` follow pyod.  ``per_subspace_scores_`` and
-    ``return_per_subspace`` stay the raw detector scores.  Non-finite scores leave the statistics unspecified."""
+    ``return_per_subspace`` stay the raw detector scores.  Non-finite scores leave the statistics unspecified.
+
+    metric, p (pyod's / sklearn's arguments of KNN and LOF; keyword-only, ``SubspaceEnsemble(..., metric="euclidean",
+    p=None)``: see _MetricKeywords): the distance of "knn", "lof" and ``kneighbors``.  F_s is the
+    feature set of subspace s; values are the raw float32 features taken as float64.
+
+    - "euclidean" (alias "l2") is sqrt(sum_f (x_f - y_f)^2), the default.
+    - "manhattan" (aliases "l1", "cityblock") is sum_f |x_f - y_f|.
+    - "chebyshev" is max_f |x_f - y_f|.
+    - "minkowski" with p is (sum_f |x_f - y_f|^p)^(1/p).  p is a finite float in (0, 8] (default 2).  p == 1 is the
+      Manhattan path and p == 2 the Euclidean path, bit for bit.  p < 1 is allowed and is not a metric (no triangle
+      inequality; sklearn's brute force allows it too).  For p > 2, sums of p-th powers whose float32 image exceeds
+      FLT_MAX compare equal in the selection (such pairs are then ranked by index); this is not guarded.
+    - "cosine" is 1 - <x, y> / (|x| |y|) over F_s, not centred.  A row whose norm over F_s is exactly 0 is at distance
+      exactly 1 from every row, zero rows included; scipy gives NaN there.
+
+    For every metric the neighbour order stays the strict total order (distance, reference index) and exclude_self keeps
+    its meaning; exact duplicates give distance exactly 0 under the three Minkowski-family metrics (under "cosine" up to
+    the float64 rounding of 1 - cos).  The selection ranks the pairs in float32 (Minkowski family: a vector-ALU sweep over
+    the uncentred blocks; cosine: the Gram engine on unit rows, d2 = 2 - 2 cos, at every d_s), the selected k pairs are
+    then re-measured in float64 and re-sorted, and everything after the sorted lists (kNN scores, lrd, LOF) is metric free.
+    engine with another metric: the Minkowski family has one producer, so "exact" or "gram" raise and VGAN_OUTLIER_ENGINE
+    is ignored; "cosine" is always Gram, "exact" raises.  method "kde" takes the Euclidean distance only (the Gaussian
+    kernel is Euclidean); p without "minkowski" raises."""
 
     def __init__(self, subspaces, proba, method="knn", n_neighbors=5, knn_method="largest", bandwidth=1.0, engine="auto",
                  splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
@@ -594,7 +701,10 @@ class SubspaceEnsemble(_NeighborScorer):
             raise ValueError(f"method must be 'knn', 'lof' or 'kde', got {method!r}")
         if knn_method not in KNN_METHODS:
             raise ValueError(f"knn_method must be one of {sorted(KNN_METHODS)}, got {knn_method!r}")
-        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        plan_engine = self._metric_engine(engine)
+        if method == "kde" and self.metric != "euclidean":
+            raise ValueError(f"method 'kde' takes the Euclidean distance only (the Gaussian kernel is Euclidean), got metric={self.metric!r}")
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination, plan_engine)
         self._configure_neighbors(n_neighbors, splits)
         self.bandwidth = check_bandwidth(bandwidth) if method == "kde" else bandwidth
         self.method, self.knn_method = method, knn_method
@@ -651,6 +761,12 @@ class SubspaceEnsemble(_NeighborScorer):
             self._kdist = torch.empty(self.plan.count, n, dtype=torch.float32, device=X.device)
             self._lrd = torch.empty(self.plan.count, n, dtype=torch.float64, device=X.device)
         return self._publish(*self._score(None, fitting=True))
+
+
+SubspaceEnsemble.__signature__ = inspect.Signature(
+    list(inspect.signature(SubspaceEnsemble.__init__).parameters.values())[1:]
+    + [inspect.Parameter("metric", inspect.Parameter.KEYWORD_ONLY, default="euclidean"),
+       inspect.Parameter("p", inspect.Parameter.KEYWORD_ONLY, default=None)])
 
 
 # ---- angle-based scores (FastABOD) over the subspaces ----------------------------------------------------------------------

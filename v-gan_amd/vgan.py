@@ -174,7 +174,8 @@ class _RunFolder:
         """A SubspaceEnsemble (vgan_amd.outlier) over this model's subspaces and probabilities: self.subspaces / self.proba
         if they are set, otherwise approx_subspace_dist(subspace_count) first.  Fitted on X when X is given.  method is
         "knn", "lof" or "kde"; further keywords (knn_method, bandwidth, engine, splits, workspace_bytes, normalize,
-        combination, contamination) go to SubspaceEnsemble, e.g. outlier_ensemble(method="kde", bandwidth="scott", X=X) or
+        combination, contamination, and for "knn" / "lof" metric and p: "manhattan", "chebyshev", "minkowski", "cosine") go
+        to SubspaceEnsemble, e.g. outlier_ensemble(method="lof", metric="manhattan", X=X), outlier_ensemble(method="kde", bandwidth="scott", X=X) or
         outlier_ensemble(method="knn", normalize="robust", combination="max", contamination=0.05, X=X).
         method "cblof" builds a SubspaceCBLOF instead (k-means per subspace and the cluster-based local outlier factor):
         its keywords are n_clusters, alpha, beta, use_weights, init, max_iter, tol, seed, engine, workspace_bytes and the
