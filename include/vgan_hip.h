@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_*, vgan_iforest_*_blocks, vgan_outlier_*_metric and vgan_outlier_pack_unit entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_*, vgan_iforest_*_blocks, vgan_outlier_*_metric, vgan_outlier_pack_unit and vgan_loci_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1437,6 +1437,49 @@ int vgan_sos_scores(const float* Pq, const float* sq_q, int nq, const float* Pr,
                     const int32_t* feat_off, const int64_t* col_off, int first, int count, int metric, const double* beta,
                     const double* dmin, const double* Z, int engine, int splits, uint64_t* acc, float* score,
                     const int32_t* score_row, int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Local correlation integral over a fixed grid of radii (LOCI: Papadimitriou, Kitagawa, Gibbons, Faloutsos 2003; pyod's LOCI):
+ * a row's neighbour count within alpha r is compared with the counts of the rows within r of it, at every radius r of the grid,
+ * and the score is the largest deviation in units of the local standard deviation (v-gan_amd/outlier.py: SubspaceLOCI, whose
+ * docstring is the definition; kernels in csrc/outlier_loci.hip).  D float32 [count, n, n] is the Euclidean matrix,
+ * D[z][c][q] with the subject row q contiguous; every entry below takes its diagonal as 0 whatever is
+ * stored.  VGAN_LOCI_MIN_ROWS <= n <= VGAN_LOCI_MAX_ROWS, 1 <= R <= VGAN_LOCI_MAX_RADII, count <= 65535.  r (sampling radii)
+ * and a (counting radii, alpha r) are float32 [count, R], ascending, formed by the caller; all comparisons are float32.
+ * vgan_loci_distance_matrix: D as vgan_sos_distance_matrix writes it with VGAN_SOS_METRIC_EUCLIDEAN (the same arguments, layout
+ *   and bits: sqrtf of the engine's float32 d2 with row q as the query), from VGAN_LOCI_MIN_ROWS = 2 rows on.
+ * vgan_loci_rmax: rmax float32 [count], the largest off-diagonal entry of every matrix (0 where all are 0): an exact maximum
+ *   without an order, from which the caller forms r and a.
+ * vgan_loci_counts: cnt int32 [count, n, R], cnt[z][q][j] = #{c : D[z][c][q] <= a[z][j]} (the row itself included).
+ * vgan_loci_sums: over the rows c with D[z][c][p] <= r[z][j]: m int32 their number, S1 int64 the sum of cnt[z][c][j], S2 int64
+ *   the sum of cnt[z][c][j]^2; all [count, n, R].
+ * vgan_loci_finish: num = S1 - cnt m and den = m S2 - S1^2 in int64 (exact: both products stay below 2^60); radius j is valid
+ *   iff m >= n_min and den > 0; score[score_row[z] (or z), p] = float32(max(0, max over the valid j of float64(num) /
+ *   sqrt(float64(den)))); best (int32, the layout of score, may be null) the lowest j that attains a positive maximum, else -1.
+ * vgan_loci_scores: the nq new rows of Pq against the nr fitted rows of Pr (the packed blocks, squared norms, SUBSPACE TABLE,
+ *   first, count, engine and splits of vgan_sos_scores), each scored alone as appended to the fitted set: with d = sqrtf of the
+ *   engine's d2 (the new row as query), A = #{d <= a_j}, M = #{d <= r_j}, T1 / T2 = the sums of cnt[c][j] / cnt[c][j]^2 over the
+ *   rows counted in M, added as 64-bit integers into acc uint64 [count, nq, 4, R] (scratch, zeroed by the entry); then cnt = A +
+ *   1, m = M + 1, S1 = T1 + cnt, S2 = T2 + cnt^2 and the rule of vgan_loci_finish.  r, a float32 [S, R] and cnt int32 [S, nr, R]
+ *   are indexed by first + z.  dist_out (may be null; count must be 1): float32 [nq, nr], the distances that were counted.
+ * The integer sums have no order: no result depends on splits or on the chunk.  Every entry returns VGAN_ERR_ARG before
+ * touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_LOCI_MIN_ROWS 2
+#define VGAN_LOCI_MAX_ROWS 32768
+#define VGAN_LOCI_MAX_RADII 64
+int vgan_loci_distance_matrix(const float* P, const float* sq, int n, const int32_t* feat_off, const int64_t* col_off, int first,
+                              int count, int engine, int splits, float* D, vgan_stream_t stream);
+int vgan_loci_rmax(const float* D, int n, int count, float* rmax, vgan_stream_t stream);
+int vgan_loci_counts(const float* D, int n, int count, const float* a, int R, int32_t* cnt, vgan_stream_t stream);
+int vgan_loci_sums(const float* D, int n, int count, const float* r, int R, const int32_t* cnt, int32_t* m, int64_t* S1, int64_t* S2,
+                   vgan_stream_t stream);
+int vgan_loci_finish(const int32_t* cnt, const int32_t* m, const int64_t* S1, const int64_t* S2, int n, int count, int R, int n_min,
+                     float* score, const int32_t* score_row, int64_t ld_score, int32_t* best, vgan_stream_t stream);
+int vgan_loci_scores(const float* Pq, const float* sq_q, int nq, const float* Pr, const float* sq_r, int nr,
+                     const int32_t* feat_off, const int64_t* col_off, int first, int count, const float* r, const float* a,
+                     const int32_t* cnt, int R, int n_min, int engine, int splits, uint64_t* acc, float* dist_out, float* score,
+                     const int32_t* score_row, int64_t ld_score, int32_t* best, vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Subspace outlier degree (SOD: Kriegel, Kroeger, Schubert, Zimek 2009; pyod's SOD): a row is judged against the rows that

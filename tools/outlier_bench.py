@@ -81,6 +81,12 @@ difference of the two paths' ensemble scores.
     row (mean, maximum) and the float64 exponentials per second of the search; the search with a row per wave (where it fits)
     and per workgroup of 1024 threads; the same rules in numpy on the host with 16 threads (matrix, search and scores
     separately) for a sample of the subspaces, scaled to all of them; and the LOF fit (k = 20) on the same rows.
+  --method loci: the local correlation integral (vgan_amd.SubspaceLOCI at its defaults: 32 radii at 4 an octave, alpha 0.5, n_min 20,
+    a 16 GiB workspace) on d = 784, S = 50 sampled, n = 2000 and 10^4: fit and decision_function (the training rows as queries);
+    the fit split into its stages (distance matrices, r_max and the radii, counts, sums, finish), each behind a synchronisation;
+    the (pair, radius) rate of the counts and the sums sweeps, the latter also as a share of the chip's vector-ALU rate at the
+    vector instructions the sweep spends on one; the SubspaceSOS (perplexity 30) and LOF (k = 20) fits on the same rows; and the
+    same rules in numpy on the host with 16 threads for a sample of the subspaces, scaled to all of them.
   --method dif: deep isolation forest (vgan_amd.SubspaceDIF at its defaults: 50 random nets d_s -> 500 -> 100 -> 20 per subspace,
     6 trees of 256 rows on each) on d = 10 at n = 10^4 and d = 784 at n = 10^4 and 5 10^4, S = 50 sampled: fit and
     decision_function (the training rows as queries); one pass over all blocks split into its calls, each behind a
@@ -1414,6 +1420,117 @@ def run_sos(d, n, count, reps, baselines=True, perplexity=30.0, sample=2):
     return row
 
 
+VALU_LANE_OPS_PER_S = 256 * 4 * 32 * 2.4e9  # CUs x SIMDs x lanes a clock x clock: the fp32 vector rate of 157.3 TFLOPS in FMAs
+LOCI_SUMS_OPS_PER_PAIR_RADIUS = 6.6  # vector instructions of the sums sweep's inner loop per (pair, radius), counted in its ISA
+
+
+def numpy_loci_one(Xs, n_radii=32, radii_per_octave=4.0, alpha=0.5, n_min=20, threads=16, block=256):
+    """(scores float32 [n], seconds of matrix / counts / sums / finish): SubspaceLOCI's rules for one subspace in numpy, the
+    matrix float32 from float64 squared distances, blocks of subject rows spread over a pool of `threads` threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    from vgan_amd.outlier import loci_radii
+    n = Xs.shape[0]
+    t0 = time.perf_counter()
+    sq = (Xs * Xs).sum(axis=1)
+    Dm = np.sqrt(np.maximum(sq[:, None] + sq[None, :] - 2.0 * (Xs @ Xs.T), 0.0)).astype(np.float32)
+    np.fill_diagonal(Dm, 0.0)
+    r, a = loci_radii(Dm.max(), n_radii, radii_per_octave, alpha)
+    t1 = time.perf_counter()
+    cnt = np.empty((n, n_radii), np.int64)
+    m, S1, S2 = (np.empty((n, n_radii), np.int64) for _ in range(3))
+
+    def counts(lo):
+        blk = Dm[:, lo:lo + block]
+        for j in range(n_radii):
+            cnt[lo:lo + block, j] = (blk <= a[j]).sum(axis=0)
+
+    def sums(lo):
+        blk = Dm[:, lo:lo + block]
+        for j in range(n_radii):
+            inside = (blk <= r[j]).astype(np.float64)  # sums below 2^53: exact in float64
+            m[lo:lo + block, j] = inside.sum(axis=0)
+            S1[lo:lo + block, j] = cf[:, j] @ inside
+            S2[lo:lo + block, j] = cf2[:, j] @ inside
+
+    with ThreadPoolExecutor(threads) as pool:
+        list(pool.map(counts, range(0, n, block)))
+        t2 = time.perf_counter()
+        cf = cnt.astype(np.float64)
+        cf2 = cf * cf
+        list(pool.map(sums, range(0, n, block)))
+    t3 = time.perf_counter()
+    num, den = S1 - cnt * m, m * S2 - S1 * S1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where((m >= n_min) & (den > 0), num / np.sqrt(den.astype(np.float64)), -np.inf)
+    scores = np.maximum(ratio.max(axis=1), 0.0).astype(np.float32)
+    return scores, (t1 - t0, t2 - t1, t3 - t2, time.perf_counter() - t3)
+
+
+def run_loci(d, n, count, reps, baselines=True, sample=2):
+    from vgan_amd.outlier import loci_chunks
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    ens = vgan_amd.SubspaceLOCI(m, p, workspace_bytes=OCSVM_WORKSPACE)
+    t_fit, fit_reps = timed(lambda: ens.fit(Xd), reps)
+    t_dec, dec_reps = timed(lambda: ens.decision_function(Xd), reps)
+    dims, R = m.sum(axis=1), ens.n_radii
+    stages = {}
+
+    def staged(name, fn):
+        def wrapped(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **kw)
+            torch.cuda.synchronize()
+            stages[name] = stages.get(name, 0.0) + time.perf_counter() - t0
+            return out
+        return wrapped
+
+    other = vgan_amd.SubspaceLOCI(m, p, workspace_bytes=OCSVM_WORKSPACE)
+    for name, attr in (("matrix", "_distance_matrix"), ("radii", "_set_radii"), ("counts", "_counts"), ("sums", "_sums"),
+                       ("finish", "_finish")):
+        setattr(other, attr, staged(name, getattr(other, attr)))
+    split = None
+    for _ in range(max(reps, 2)):  # the first pass warms up
+        stages.clear()
+        other.fit(Xd)
+        split = dict(stages) if split is None or stages["sums"] < split["sums"] else split
+    assert np.array_equal(other.decision_scores_, ens.decision_scores_) and np.array_equal(other.best_radius_, ens.best_radius_)
+    split = {k: round(v, 5) for k, v in split.items()}
+    pair_radii = float(len(m)) * n * n * R
+    rate = pair_radii / split["sums"]
+    row = {"method": "loci", "d": d, "n": n, "n_radii": R, "radii_per_octave": ens.radii_per_octave, "alpha": ens.alpha,
+           "n_min": ens.n_min, "S_sampled": count, "S_distinct": int(len(m)), "d_s_min": int(dims.min()),
+           "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()), "gram_subspaces": int(ens.plan.gram.sum()),
+           "chunks": len(loci_chunks(ens.plan, n, R, OCSVM_WORKSPACE)), "distance_matrix_bytes": 4 * n * n * int(len(m)),
+           "fit_s": round(t_fit, 5), "fit_reps_s": fit_reps, "decision_function_s": round(t_dec, 5),
+           "decision_function_reps_s": dec_reps, "fit_stages_s": split,
+           "matrix_TFLOPs": round(2.0 * n * n * float(dims.sum()) / split["matrix"] / 1e12, 2),
+           "counts_pair_radii_per_s": round(pair_radii / split["counts"], 0), "sums_pair_radii_per_s": round(rate, 0),
+           "sums_vector_ops_per_pair_radius": LOCI_SUMS_OPS_PER_PAIR_RADIUS,
+           "sums_share_of_vector_alu_rate": round(rate * LOCI_SUMS_OPS_PER_PAIR_RADIUS / VALU_LANE_OPS_PER_S, 3),
+           "n_flagged_mean": float(ens.n_flagged_.mean())}
+    sos = vgan_amd.SubspaceSOS(m, p, perplexity=30.0, workspace_bytes=OCSVM_WORKSPACE)
+    row["sos_fit_s"], row["sos_fit_reps_s"] = timed(lambda: sos.fit(Xd), reps)
+    row["sos_fit_s"] = round(row["sos_fit_s"], 5)
+    lof = vgan_amd.SubspaceEnsemble(m, p, method="lof", n_neighbors=20)
+    row["lof_k20_fit_s"], row["lof_k20_fit_reps_s"] = timed(lambda: lof.fit(Xd), reps)
+    row["lof_k20_fit_s"] = round(row["lof_k20_fit_s"], 5)
+    if baselines:
+        pick = np.unique(np.linspace(0, len(m) - 1, min(sample, len(m))).astype(int))
+        host, worst = np.zeros(4), 0.0
+        for s in pick:
+            scores, times = numpy_loci_one(X[:, np.flatnonzero(m[s])].astype(np.float64), R, ens.radii_per_octave, ens.alpha, ens.n_min)
+            host += times
+            worst = max(worst, float(np.abs(ens.per_subspace_scores_[s] - scores).max()))
+        scale = len(m) / len(pick)
+        row.update({"numpy16_subspaces_timed": [int(s) for s in pick],
+                    "numpy16_stages_s_scaled": {k: round(float(v) * scale, 3) for k, v in zip(("matrix", "counts", "sums", "finish"), host)},
+                    "numpy16_fit_s_scaled": round(float(host.sum()) * scale, 3),
+                    "max_abs_score_diff_vs_numpy": worst, "speedup_vs_numpy16": round(float(host.sum()) * scale / t_fit, 1)})
+    return row
+
+
 def sweep(n, reps):
     rng = np.random.default_rng(0)
     rows = []
@@ -2099,13 +2216,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics", "metric"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics", "metric", "loci"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / kpca / ae / deepsvdd: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / loci / dif / kpca / ae / deepsvdd: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / dif / sod / kpca / ae / deepsvdd: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / loci / dif / sod / kpca / ae / deepsvdd: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -2247,6 +2364,14 @@ def main():
             shapes = [tuple(int(v) for v in args.shape.split(","))]
         for d, n, count in shapes:
             out["configs"].append(run_sos(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
+        configs = []
+    if args.method == "loci":
+        shapes = [(10, 2000, 20), (784, 2000, 10)] if args.quick else [(784, 2000, 50), (784, 10_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_loci(d, n, count, args.reps, baselines=not args.no_baselines, sample=2 if n <= 2000 else 1))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "sod":

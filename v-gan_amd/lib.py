@@ -211,6 +211,12 @@ SIGNATURES = {
     "vgan_sos_fit": (_i, [_p, _i, _i, ctypes.c_double, ctypes.c_double, _i, _i, _p, _p, _p, _p, _p, _p]),
     "vgan_sos_fit_scores": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     "vgan_sos_scores": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i64, _p]),
+    "vgan_loci_distance_matrix": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "vgan_loci_rmax": (_i, [_p, _i, _i, _p, _p]),
+    "vgan_loci_counts": (_i, [_p, _i, _i, _p, _i, _p, _p]),
+    "vgan_loci_sums": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "vgan_loci_finish": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _i64, _p, _p]),
+    "vgan_loci_scores": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p, _p]),
     "vgan_sod_reverse_lists": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     "vgan_sod_reference_sets": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "vgan_sod_score": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, ctypes.c_double, _i, _p, _p, _i, _p, _p, _i, _p]),

@@ -1621,6 +1621,82 @@ class HipOps:
                                             int(splits), _ptr(acc), _ptr(score), _ptr(score_row), score.stride(0), self._stream()),
                    "vgan_sos_scores")
 
+    # ---- local correlation integral over subspaces (vgan_amd.outlier.SubspaceLOCI) ---------------------------
+    # D float32 [count, n, n] (loci_distance_matrix), radii float32 [count, R], cnt / m int32 and S1 / S2 int64
+    # [count, n, R]: the arrays of one chunk.
+    def _loci_state(self, D, radii, *arrays):
+        _vec(D, "D"), _vec(radii, "radii")
+        if not (D.dim() == 3 and D.shape[1] == D.shape[2]):
+            raise ValueError(f"D: need [count, n, n], got {tuple(D.shape)}")
+        count, n, R = D.shape[0], D.shape[1], radii.shape[-1]
+        assert radii.shape == (count, R)
+        for t, name, dtype in arrays:
+            _vec(t, name, dtype)
+            assert t.shape == (count, n, R), (name, tuple(t.shape))
+        return count, n, R
+
+    def loci_distance_matrix(self, P, sq, n, table, first, count, engine, splits, D):
+        """D[z][c][q] = sqrtf(d2) of rows q and c of the packed block P: sos_distance_matrix's Euclidean matrix, from 2 rows on."""
+        _vec(P, "P"), _vec(D, "D")
+        assert D.numel() >= count * n * n
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_loci_distance_matrix(_ptr(P), _ptr(sq), int(n), _ptr(feat_off), _ptr(col_off), int(first), int(count),
+                                                      int(engine), int(splits), _ptr(D), self._stream()), "vgan_loci_distance_matrix")
+
+    def loci_rmax(self, D, rmax):
+        """rmax[z] = the largest off-diagonal entry of D[z]."""
+        _vec(D, "D"), _vec(rmax, "rmax")
+        if not (D.dim() == 3 and D.shape[1] == D.shape[2] and rmax.shape == (D.shape[0],)):
+            raise ValueError(f"need D [count, n, n] and rmax [count], got {tuple(D.shape)} and {tuple(rmax.shape)}")
+        _lib.check(self.lib.vgan_loci_rmax(_ptr(D), D.shape[1], D.shape[0], _ptr(rmax), self._stream()), "vgan_loci_rmax")
+
+    def loci_counts(self, D, a, cnt):
+        """cnt[z][q][j] = the number of rows c with D[z][c][q] <= a[z][j], the diagonal taken as 0."""
+        count, n, R = self._loci_state(D, a, (cnt, "cnt", torch.int32))
+        _lib.check(self.lib.vgan_loci_counts(_ptr(D), n, count, _ptr(a), R, _ptr(cnt), self._stream()), "vgan_loci_counts")
+
+    def loci_sums(self, D, r, cnt, m, S1, S2):
+        """Over the rows c with D[z][c][p] <= r[z][j]: m their number, S1 the sum of cnt[z][c][j], S2 that of its square."""
+        count, n, R = self._loci_state(D, r, (cnt, "cnt", torch.int32), (m, "m", torch.int32), (S1, "S1", torch.int64),
+                                       (S2, "S2", torch.int64))
+        _lib.check(self.lib.vgan_loci_sums(_ptr(D), n, count, _ptr(r), R, _ptr(cnt), _ptr(m), _ptr(S1), _ptr(S2), self._stream()),
+                   "vgan_loci_sums")
+
+    def loci_finish(self, cnt, m, S1, S2, n_min, score, score_row=None, best=None):
+        """score rows score_row = the largest valid num / sqrt(den) (or 0) of every row of the chunk; best int32, laid out as
+        score: the lowest radius index that attains it, -1 where the score is 0."""
+        _vec(cnt, "cnt", torch.int32), _vec(m, "m", torch.int32), _vec(S1, "S1", torch.int64), _vec(S2, "S2", torch.int64)
+        count, n, R = cnt.shape
+        assert m.shape == cnt.shape and S1.shape == cnt.shape and S2.shape == cnt.shape
+        _mat(score, "score")
+        assert score.shape[1] >= n
+        if best is not None:
+            _vec(best, "best", torch.int32)
+            assert best.shape == score.shape and best.stride(0) == score.stride(0)
+        _lib.check(self.lib.vgan_loci_finish(_ptr(cnt), _ptr(m), _ptr(S1), _ptr(S2), n, count, R, int(n_min), _ptr(score),
+                                             _ptr(score_row), score.stride(0), _ptr(best), self._stream()), "vgan_loci_finish")
+
+    def loci_scores(self, Pq, sq_q, nq, Pr, sq_r, nr, table, first, count, r, a, cnt, n_min, engine, splits, acc, score,
+                    score_row=None, best=None, dist_out=None):
+        """score rows score_row = the scores of the nq new rows for the chunk, each appended alone to the fitted set; r / a
+        [S, R] and cnt [S, nr, R] are indexed by first + z; acc int64 [count, nq, 4, R] leaves with A, M, T1, T2; dist_out
+        float32 [nq, nr] (count 1) the distances that were counted."""
+        _vec(r, "r"), _vec(a, "a"), _vec(cnt, "cnt", torch.int32), _vec(acc, "acc", torch.int64), _mat(score, "score")
+        R = r.shape[1]
+        assert a.shape == r.shape and r.shape[0] >= first + count and cnt.shape == (r.shape[0], nr, R)
+        assert acc.numel() >= count * nq * 4 * R and score.shape[1] >= nq
+        if best is not None:
+            _vec(best, "best", torch.int32)
+            assert best.shape == score.shape and best.stride(0) == score.stride(0)
+        if dist_out is not None:
+            _vec(dist_out, "dist_out")
+            assert count == 1 and dist_out.numel() >= nq * nr
+        _, feat_off, col_off = table
+        _lib.check(self.lib.vgan_loci_scores(_ptr(Pq), _ptr(sq_q), int(nq), _ptr(Pr), _ptr(sq_r), int(nr), _ptr(feat_off), _ptr(col_off),
+                                             int(first), int(count), _ptr(r), _ptr(a), _ptr(cnt), int(R), int(n_min), int(engine),
+                                             int(splits), _ptr(acc), _ptr(dist_out), _ptr(score), _ptr(score_row), score.stride(0),
+                                             _ptr(best), self._stream()), "vgan_loci_scores")
+
     # ---- subspace outlier degree over subspaces (vgan_amd.outlier.SubspaceSOD) -------------------------------
     # Lists are int32 [count, rows, k]; the reverse lists of a chunk are rn_off int32 [count, n + 1], rn_rows int32 [count, n k].
     def sod_reverse_lists(self, idx, rn_off, rn_rows, cursor):

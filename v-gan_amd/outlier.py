@@ -103,6 +103,14 @@ fitted rows formed as a sum of logarithms in fixed point (csrc/outlier_sos.hip);
 exponentials for the search.  Its contract (the matrix, the shift, degenerate rows, the search, the two score forms,
 determinism) is that class's docstring.
 
+``SubspaceLOCI`` is the proximity detector without a k (the local correlation integral): on the matrix of ``SubspaceSOS`` and a
+grid of radii under its largest entry, a row's neighbour count within alpha r against the counts of the rows within r of it, as
+two integer sweeps of the matrix, and the largest deviation in local standard deviations as the score (csrc/outlier_loci.hip);
+n^2 d_s for the matrix, n^2 R predicated integer additions for the sums.  It sees groups of more than MAX_NEIGHBORS close
+anomalous rows, which every neighbour-list detector scores as inliers of their own group.  Its contract (the matrix, the
+radii, counts and sums, the score and the best radius, the new-row rule, determinism, what is not built) is that class's
+docstring.
+
 ``SubspaceDIF`` is the learned-representation detector without the learning (deep isolation forest): per subspace an ensemble
 of randomly initialised, never trained MLPs, regenerated from the seed by a counter-based generator, maps the min-max scaled
 rows to small representations in one fused fp32 matrix-unit forward that keeps every activation in LDS
@@ -3479,6 +3487,239 @@ class SubspaceSOS(_SubspaceScorer):
         return self._publish(self._combine(per, fitting=True), per)
 
 
+# ---- local correlation integral: neighbour counts against those of the neighbourhood, over a grid of radii ---------------
+LOCI_MIN_ROWS = 2  # VGAN_LOCI_MIN_ROWS: r_max is the largest off-diagonal entry
+LOCI_MAX_ROWS = 1 << 15  # VGAN_LOCI_MAX_ROWS: m S2 and S1^2 stay below 2^60
+LOCI_MAX_RADII = 64  # VGAN_LOCI_MAX_RADII
+
+
+def check_loci_params(alpha, n_min, n_radii, radii_per_octave, k_sigma):
+    """alpha in (0, 1]; n_min an integer >= 1 (fit checks it against n); n_radii an integer from 1 to LOCI_MAX_RADII;
+    radii_per_octave positive and finite; k_sigma positive."""
+    if not (_is_real(alpha) and 0.0 < float(alpha) <= 1.0):
+        raise ValueError(f"alpha must lie in (0, 1], got {alpha!r}")
+    if not (_is_int(n_min) and 1 <= int(n_min) < 2 ** 31):
+        raise ValueError(f"n_min must be an integer of 1 or more, got {n_min!r}")
+    if not (_is_int(n_radii) and 1 <= int(n_radii) <= LOCI_MAX_RADII):
+        raise ValueError(f"n_radii must be an integer between 1 and {LOCI_MAX_RADII}, got {n_radii!r}")
+    if not (_is_real(radii_per_octave) and np.isfinite(radii_per_octave) and float(radii_per_octave) > 0.0):
+        raise ValueError(f"radii_per_octave must be positive and finite, got {radii_per_octave!r}")
+    if not (_is_real(k_sigma) and float(k_sigma) > 0.0):  # false for nan
+        raise ValueError(f"k_sigma must be positive, got {k_sigma!r}")
+    return float(alpha), int(n_min), int(n_radii), float(radii_per_octave), float(k_sigma)
+
+
+def check_loci_rows(n, n_min):
+    if not LOCI_MIN_ROWS <= n <= LOCI_MAX_ROWS:
+        raise ValueError(f"the local correlation integral takes between {LOCI_MIN_ROWS} and {LOCI_MAX_ROWS} fitted rows, got {n}")
+    if n_min > n:
+        raise ValueError(f"n_min must not exceed the number of fitted rows {n}, got {n_min}")
+
+
+def loci_radii(r_max, n_radii, radii_per_octave, alpha):
+    """(r, a) float32 [..., R]: the sampling radii r_j = float32(float64(r_max) exp2(-(R - 1 - j) / radii_per_octave)), ascending
+    with r_{R-1} = r_max, and the counting radii a_j = float32(alpha float64(r_j)); r_max float32 [...]."""
+    r_max = np.asarray(r_max, dtype=np.float32)
+    steps = np.exp2(-(n_radii - 1 - np.arange(n_radii, dtype=np.float64)) / float(radii_per_octave))
+    r = (r_max.astype(np.float64)[..., None] * steps).astype(np.float32)
+    return r, (float(alpha) * r.astype(np.float64)).astype(np.float32)
+
+
+def loci_chunks(plan, n, n_radii, limit_bytes):
+    """[(first, count, gram)]: the chunks of sos_chunks with, next to a subspace's n x n float32 matrix, its n x R counts and sums
+    (int32 cnt and m, int64 S1 and S2)."""
+    return plan.chunks(n, limit_bytes, extra_bytes=4 * int(n) * int(n) + 24 * int(n) * int(n_radii), max_count=65535)
+
+
+class SubspaceLOCI(_SubspaceScorer):
+    """The local correlation integral per subspace over a fixed grid of radii (LOCI: Papadimitriou, Kitagawa, Gibbons,
+    Faloutsos, ICDE 2003; pyod's ``LOCI``), combined like the detectors of SubspaceEnsemble: ``fit`` sets ``decision_scores_``,
+    ``decision_function`` scores new rows, higher is more outlying.  It is the proximity detector without a k: a row's
+    neighbour count within alpha r is compared with the counts of the rows within r of it, at every radius r of the grid, and the
+    score is the largest deviation in units of the local standard deviation (MDEF / sigma_MDEF); the paper flags a score above
+    k_sigma = 3, which needs no contamination guess.  A group of more than 32 anomalous rows that lie close together, which
+    every detector with a neighbour list of at most MAX_NEIGHBORS rows scores as inliers of its own group, stands out at the
+    radii that reach beyond the group.  Not built: the exact LOCI over the critical radii of every row (the grid below takes
+    their place), aLOCI's quad-tree approximation, metrics other than the Euclidean one, and more than 2^15 fitted rows.  This
+    docstring is the contract.
+
+    Distance matrix.  Per subspace s, D is the float32 Euclidean matrix of SubspaceSOS (``vgan_sos_distance_matrix``'s bits, written
+    by ``vgan_loci_distance_matrix``, which also takes 2 rows: sqrtf of
+    the engines' float32 d2, exact below GRAM_MIN_DIMS, Gram above with operands centred on the column mean), D[c][q] with the
+    subject row q as the query.  Every kernel takes the diagonal as 0 whatever is stored.  Subspaces are chunked so that the
+    matrices, the counts and sums and the packed blocks fit workspace_bytes (loci_chunks); X stays resident.
+
+    Radii.  r_max[s] is the largest off-diagonal entry of D, an exact float32 maximum that has no order.  On the host
+    (loci_radii), with R = n_radii: r_j = float32(float64(r_max) * exp2(-(R - 1 - j) / radii_per_octave)), j = 0 .. R-1, ascending,
+    r_{R-1} = r_max; the counting radii are a_j = float32(alpha * float64(r_j)).  ``radii_`` float32 [S, R] publishes r.
+
+    Counts and sums, with c over the fitted rows (the row itself included, through the zero diagonal) and every comparison
+    made in float32: cnt[q, j] = #{c : D[c][q] <= a_j} (int32); m[p, j] = #{c : D[c][p] <= r_j}; S1[p, j] = the sum over those c of
+    cnt[c, j]; S2[p, j] = the sum over those c of cnt[c, j]^2 (int64).
+
+    Score.  num = S1 - cnt[p, j] m and den = m S2 - S1^2, both int64, exact because n <= 2^15 keeps both products below 2^60;
+    den >= 0.  Radius j is valid for p iff m >= n_min and den > 0.  The per-subspace score is float32(max(0, max over valid j
+    of float64(num) / sqrt(float64(den)))).  ``best_radius_[s, p]`` is the lowest j attaining a positive maximum and -1 where
+    the score is 0.  A subspace of constant features has r_max = 0 and scores exactly 0 everywhere.  ``fit`` takes 2 to 2^15
+    rows and raises when n_min > n.
+
+    New rows.  ``decision_function`` scores a new row alone, as appended to the fitted set, with the fitted counts unchanged
+    (the stance of SubspaceECOD and SubspaceSOS).  Over the fitted rows c, with d the engine's float32 distance (the new row
+    as query): A_j = #{d <= a_j}, M_j = #{d <= r_j}, T1_j = the sum of cnt[c, j] and T2_j the sum of cnt[c, j]^2 over the rows of
+    M_j, added as 64-bit integers; then cnt_x = A + 1, m = M + 1, S1 = T1 + cnt_x, S2 = T2 + cnt_x^2 and the same rule with the
+    stored ``radii_``.  So ``decision_function(X_train)`` is not ``decision_scores_``.
+
+    Everything up to one division and one square root per (row, radius) is an integer and has no order: counts, sums, scores
+    and ``best_radius_`` are bit-identical from run to run, for every splits and workspace_bytes, and for a subspace fitted
+    alone or with others.
+
+    Published: the common attributes; ``radii_`` float32 [S, R]; ``best_radius_`` int32 [S, n]; ``neighbor_counts_`` int32
+    [S, n, R] (cnt); ``flagged_`` bool [S, n], the per-subspace score above k_sigma, and ``n_flagged_`` int64 [S]; all in the
+    given subspace order.  ``distance_rows(X, s)`` gives the float32 [n, n_fitted] distances of the rows of X that
+    ``decision_function`` counts in subspace s, ``row_sums(X, s)`` the integers (A, M, T1, T2) it forms from them.
+
+    engine, splits (the reference-row split of the matrix and new-row sweeps), normalize, combination and contamination are
+    those of SubspaceEnsemble.  Two attributes, set after construction, serve tests and measurements and change no result:
+    ``keep_sums`` (True: ``fit`` also publishes ``sampling_counts_`` int32 (m), ``sum_counts_`` and ``sum_sq_counts_`` int64 (S1,
+    S2), all [S, n, R]) and ``keep_distance_matrix`` (True: ``distance_matrix_``, a list of S float32 [n, n] arrays, the matrices
+    the sweeps read)."""
+
+    _X = None
+
+    def __init__(self, subspaces, proba, alpha=0.5, n_min=20, n_radii=32, radii_per_octave=4.0, k_sigma=3.0, engine="auto",
+                 splits=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum", contamination=0.1):
+        self.alpha, self.n_min, self.n_radii, self.radii_per_octave, self.k_sigma = check_loci_params(
+            alpha, n_min, n_radii, radii_per_octave, k_sigma)
+        self._configure(subspaces, proba, engine, workspace_bytes, normalize, combination, contamination)
+        self._configure_splits(splits)
+        self.keep_sums = False
+        self.keep_distance_matrix = False
+
+    # ---- pipeline --------------------------------------------------------------------------------
+    def _check_fit_rows(self, n):
+        check_loci_rows(n, self.n_min)
+
+    def _distance_matrix(self, X, first, count, gram):
+        n = X.shape[0]
+        P, sq = self._pack(X, first, count, gram)
+        D = torch.empty(count, n, n, dtype=torch.float32, device=X.device)
+        self.ops.loci_distance_matrix(P, sq, n, self._table, first, count, ENGINES["gram" if gram else "exact"],
+                                      self._splits(n, n, count), D)
+        return D
+
+    def _set_radii(self, D, first, count):
+        """The chunk's radii from its matrices: r_max on the device (an exact maximum off the diagonal), the grid on the host."""
+        r_max = torch.empty(count, dtype=torch.float32, device=D.device)
+        self.ops.loci_rmax(D, r_max)
+        r, a = loci_radii(r_max.cpu().numpy(), self.n_radii, self.radii_per_octave, self.alpha)
+        self._r[first:first + count] = torch.as_tensor(r, device=D.device)
+        self._a[first:first + count] = torch.as_tensor(a, device=D.device)
+
+    def _counts(self, D, first, count):
+        self.ops.loci_counts(D, self._a[first:first + count], self._cnt[first:first + count])
+
+    def _sums(self, D, first, count):
+        shape, dev = (count, D.shape[1], self.n_radii), D.device
+        m = torch.empty(shape, dtype=torch.int32, device=dev)
+        S1, S2 = (torch.empty(shape, dtype=torch.int64, device=dev) for _ in range(2))
+        self.ops.loci_sums(D, self._r[first:first + count], self._cnt[first:first + count], m, S1, S2)
+        return m, S1, S2
+
+    def _finish(self, sums, first, count, per, best):
+        self.ops.loci_finish(self._cnt[first:first + count], *sums, self.n_min, per, self._rows[first:first + count], best)
+
+    def _score(self, Xq, fitting, best=None):
+        """The new-row form (Xq is never the fitted tensor itself); fit scores its own rows from the stored matrices."""
+        nq, nr, R = Xq.shape[0], self._X.shape[0], self.n_radii
+        per = torch.empty(self.plan.count, nq, dtype=torch.float32, device=Xq.device)
+        for first, count, gram in self.plan.chunks(nr + nq, self.workspace_bytes, extra_bytes=32 * nq * R, max_count=65535):
+            Pr, sqr = self._pack(self._X, first, count, gram)
+            Pq, sqq = self._pack(Xq, first, count, gram)
+            acc = torch.empty(count, nq, 4, R, dtype=torch.int64, device=Xq.device)
+            self.ops.loci_scores(Pq, sqq, nq, Pr, sqr, nr, self._table, first, count, self._r, self._a, self._cnt, self.n_min,
+                                 ENGINES["gram" if gram else "exact"], self._splits(nq, nr, count), acc, per,
+                                 self._rows[first:first + count], best)
+            del Pr, sqr, Pq, sqq, acc
+        return self._combine(per, fitting), per
+
+    def _rows_of(self, X, s):
+        """(distances float32 [nq, n], integers int64 [nq, 4, R]) of the rows of X in subspace s, from the entry that scores them."""
+        self._require_fit()
+        if not (_is_int(s) and 0 <= int(s) < self.plan.count):
+            raise ValueError(f"s must be a subspace index between 0 and {self.plan.count - 1}, got {s!r}")
+        Xq = _device_matrix(X, self.plan.d)
+        z = int(self.plan.given[int(s)])
+        gram = bool(self.plan.gram[z])
+        nq, nr = Xq.shape[0], self._X.shape[0]
+        Pr, sqr = self._pack(self._X, z, 1, gram)
+        Pq, sqq = self._pack(Xq, z, 1, gram)
+        acc = torch.empty(1, nq, 4, self.n_radii, dtype=torch.int64, device=Xq.device)
+        dist = torch.empty(nq, nr, dtype=torch.float32, device=Xq.device)
+        score = torch.empty(1, nq, dtype=torch.float32, device=Xq.device)
+        self.ops.loci_scores(Pq, sqq, nq, Pr, sqr, nr, self._table, z, 1, self._r, self._a, self._cnt, self.n_min,
+                             ENGINES["gram" if gram else "exact"], self._splits(nq, nr, 1), acc, score, dist_out=dist)
+        return dist.cpu().numpy(), acc[0].cpu().numpy()
+
+    # ---- public surface --------------------------------------------------------------------------
+    def distance_rows(self, X, s):
+        """float32 [n, n_fitted]: the distances of the rows of X to the fitted rows in subspace s (given order) that
+        ``decision_function`` counts."""
+        return self._rows_of(X, s)[0]
+
+    def row_sums(self, X, s):
+        """(A, M, T1, T2), int64 [n, R] each: the integers ``decision_function`` forms for the rows of X in subspace s."""
+        return tuple(self._rows_of(X, s)[1].transpose(1, 0, 2))
+
+    def decision_function(self, X, return_per_subspace=False, return_best_radius=False):
+        """As _SubspaceScorer.decision_function; with return_best_radius=True also the int32 [S, n] best radius indices of the
+        new rows (last)."""
+        if not return_best_radius:
+            return super().decision_function(X, return_per_subspace)
+        self._require_fit()
+        Xq = _device_matrix(X, self.plan.d)
+        best = torch.empty(self.plan.count, Xq.shape[0], dtype=torch.int32, device=Xq.device)
+        scores, per = self._score(Xq, fitting=False, best=best)
+        out = (scores.cpu().numpy(),) + ((per.cpu().numpy(),) if return_per_subspace else ())
+        return out + (best.cpu().numpy(),)
+
+    def fit(self, X, y=None):
+        """The distance matrices, the radii, the counts and sums and the scores of X itself: decision_scores_ (float64 [n]),
+        per_subspace_scores_, radii_, best_radius_, neighbor_counts_, flagged_, n_flagged_; with normalize also score_center_ /
+        score_scale_.  X stays resident as the fitted rows."""
+        self._X = X = self._begin_fit(X)
+        n, S, R, dev = X.shape[0], self.plan.count, self.n_radii, X.device
+        self._r = torch.empty(S, R, dtype=torch.float32, device=dev)
+        self._a = torch.empty(S, R, dtype=torch.float32, device=dev)
+        self._cnt = torch.empty(S, n, R, dtype=torch.int32, device=dev)
+        per = torch.empty(S, n, dtype=torch.float32, device=dev)
+        best = torch.empty(S, n, dtype=torch.int32, device=dev)
+        kept, kept_sums = [None] * S, [[None] * S for _ in range(3)]
+        for first, count, gram in loci_chunks(self.plan, n, R, self.workspace_bytes):
+            D = self._distance_matrix(X, first, count, gram)
+            self._set_radii(D, first, count)
+            self._counts(D, first, count)
+            sums = self._sums(D, first, count)
+            self._finish(sums, first, count, per, best)
+            if self.keep_distance_matrix:
+                self._keep(kept, D, first)
+            if self.keep_sums:
+                for held, v in zip(kept_sums, sums):
+                    self._keep(held, v, first)
+            del D, sums
+        g = self.plan.given
+        self.radii_ = self._r.cpu().numpy()[g]
+        self.neighbor_counts_ = self._cnt.cpu().numpy()[g]
+        self.best_radius_ = best.cpu().numpy()
+        if self.keep_distance_matrix:
+            self.distance_matrix_ = kept
+        if self.keep_sums:
+            self.sampling_counts_, self.sum_counts_, self.sum_sq_counts_ = (np.stack(v) for v in kept_sums)
+        self._publish(self._combine(per, fitting=True), per)
+        self.flagged_ = self.per_subspace_scores_.astype(np.float64) > self.k_sigma
+        self.n_flagged_ = self.flagged_.sum(axis=1).astype(np.int64)
+        return self
+
+
 # ---- deep isolation forest: isolation trees on random-MLP representations of the subspaces ------------------------------
 DIF_MAX_REPRESENTATIONS = 256  # VGAN_DIF_MAX_NETS
 DIF_MAX_HIDDEN = 3  # VGAN_DIF_MAX_HIDDEN
@@ -4589,7 +4830,7 @@ class SubspaceSOD(_NeighborScorer):
 # ---- one detector per method string ----------------------------------------------------------------------------------
 _METHOD_CLASSES = {"cblof": SubspaceCBLOF, "ecod": SubspaceECOD, "iforest": SubspaceIForest, "inne": SubspaceINNE,
                    "mahalanobis": SubspaceMahalanobis, "gmm": SubspaceGMM, "hbos": SubspaceHBOS, "loda": SubspaceLODA,
-                   "pca": SubspacePCA, "ocsvm": SubspaceOCSVM, "sos": SubspaceSOS, "dif": SubspaceDIF, "kpca": SubspaceKPCA,
+                   "pca": SubspacePCA, "ocsvm": SubspaceOCSVM, "sos": SubspaceSOS, "loci": SubspaceLOCI, "dif": SubspaceDIF, "kpca": SubspaceKPCA,
                    "autoencoder": SubspaceAutoEncoder, "deepsvdd": SubspaceDeepSVDD}
 _NEIGHBOR_CLASSES = {"abod": SubspaceABOD, "cof": SubspaceCOF, "sod": SubspaceSOD}
 

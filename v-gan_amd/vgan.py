@@ -255,7 +255,13 @@ class _RunFolder:
         map the standardised rows onto one centre, the score the squared distance to it; Ruff et al.'s one-class Deep SVDD,
         pyod's DeepSVDD without pre-training): its keywords are hidden, activation ("relu" or "tanh"), epochs, batch_size, lr,
         beta1, beta2, eps, weight_decay, center, center_eps, seed, workspace_bytes and the same normalize / combination /
-        contamination, e.g. outlier_ensemble(method="deepsvdd", hidden=(32, 8), X=X); n_neighbors is not used there."""
+        contamination, e.g. outlier_ensemble(method="deepsvdd", hidden=(32, 8), X=X); n_neighbors is not used there.
+        method "loci" builds a SubspaceLOCI (the local correlation integral over a grid of radii: a row's neighbour count
+        against the counts of the rows around it, the score the largest deviation in local standard deviations, flagged above
+        k_sigma = 3; the proximity detector without a k, which finds groups of more than 32 close anomalous rows; pyod's LOCI):
+        its keywords are alpha, n_min, n_radii, radii_per_octave, k_sigma, engine, splits, workspace_bytes and the same
+        normalize / combination / contamination, e.g. outlier_ensemble(method="loci", n_radii=32, X=X); n_neighbors is not
+        used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         ens = build_ensemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
