@@ -1,6 +1,7 @@
 """GPU parity tests: every C-ABI entry point (through vgan_amd.ops.HipOps -> libvgan_hip.so) against the
 CPU oracle and the golden fixtures generated from the reference.  Run with ``-m gpu`` on an MI355X.
 (The small row / feed / reduction / optimiser kernels have direct edge-shape tests of their own: tests/test_small_ops_gpu.py.)
+(The modules of vgan_amd/modules.py have float64 tests on every autograd path: tests/modules_ref.py, test_modules_cpu.py, test_modules_gpu.py.)
 
 Tolerances (fp32 path, stated per level as SURVEY.md section 7 asks):
   op level     <= 2e-5 relative (exact for mask decisions / integer outputs)

@@ -17,13 +17,23 @@ def _round4(v):
     return (v + 3) // 4 * 4
 
 
+def _dense(t):
+    """Row-major with canonical strides.  ``contiguous()`` alone does not give that: it leaves the stride of a size-1 dimension as
+    it is (the expanded scalar that ``.sum().backward()`` hands a [1, 1] output keeps stride 0), and the kernels take
+    ``stride(0)`` as the leading dimension."""
+    t = t.contiguous()
+    if t.dim() == 2 and t.stride() != (t.shape[1], 1):
+        t = torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
+    return t
+
+
 class _LinearFn(torch.autograd.Function):
     """F.linear on the fp32 MFMA (vgan_linear_forward / _backward_input / _backward_params)."""
 
     @staticmethod
     def forward(ctx, x, W, b):
         ops = default_ops()
-        x = x.contiguous()
+        x = _dense(x)
         y = torch.empty(x.shape[0], W.shape[0], dtype=torch.float32, device=x.device)
         ops.linear_forward(x, W, b, y)
         ctx.save_for_backward(x, W)
@@ -34,7 +44,7 @@ class _LinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         ops = default_ops()
         x, W = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = dW = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -54,7 +64,7 @@ class _UpperSoftmaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         ops = default_ops()
-        x = x.contiguous()
+        x = _dense(x)
         S = torch.empty_like(x)
         U = torch.empty_like(x)
         ops.upper_softmax_forward(x, S, U)
@@ -66,7 +76,7 @@ class _UpperSoftmaxFn(torch.autograd.Function):
         ops = default_ops()
         (S,) = ctx.saved_tensors
         dl = torch.empty_like(S)
-        ops.mask_backward(gU.contiguous(), S, None, 0.0, 0, dl)
+        ops.mask_backward(_dense(gU), S, None, 0.0, 0, dl)
         return dl
 
 
@@ -228,7 +238,7 @@ class RBF(nn.Module):
     def forward(self, X):
         if X.dim() != 2:
             raise ValueError(f"RBF.forward expects a 2-D tensor [N, p], got {tuple(X.shape)}")
-        return _RBFMatrixFn.apply(X.contiguous().float(), self)
+        return _RBFMatrixFn.apply(_dense(X.float()), self)
 
 
 _TILE_TABLES = {}
@@ -287,7 +297,7 @@ class _MMDLossFn(torch.autograd.Function):
         else:
             ops.mmd_gram_general(Z, sq, n, pp, bw, tiles, kernel.bandwidth_multipliers.tolist(), Wg, wrow0 or 0, partial)
         ops.mmd_reduce(partial, tiles, stats, True)
-        Uc = U.detach().contiguous()
+        Uc = _dense(U.detach())
         colpart = torch.empty(ops.colmax_chunks(n) * d, dtype=torch.int64, device=dev)
         colkey = torch.empty(d, dtype=torch.int64, device=dev)
         ops.colmax(Uc, 0, colpart, colkey, False)
@@ -358,7 +368,7 @@ class _MMDLossUnequalFn(torch.autograd.Function):
             ops.rows_dot(K[r0:r1, c0:c1], ones[:, :c1 - c0], rows, broadcast_b=True)
             ops.sum_f64(rows, r1 - r0, 1.0 / (float(r1 - r0) * float(c1 - c0)), sums[slot:slot + 1])
         stats[:3].copy_(sums)  # the three block MEANS; vgan_mmd_loss then forms xx - 2 xy + yy (its n = 1) + the penalty
-        Uc = U.detach().contiguous().float()
+        Uc = _dense(U.detach().float())
         colpart = torch.empty(ops.colmax_chunks(Uc.shape[0]) * d, dtype=torch.int64, device=dev)
         colkey = torch.empty(d, dtype=torch.int64, device=dev)
         ops.colmax(Uc, 0, colpart, colkey, False)
@@ -376,11 +386,14 @@ class _MMDLossUnequalFn(torch.autograd.Function):
         N = nx + ny
         dX = dY = dU = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            W = ctx.saved_tensors[2]  # dK/dL, scaled in place by (gK + gK^T): 2 / n_x^2 | -2 / (n_x n_y) | 2 / n_y^2 per block
-            W[:nx, :nx].mul_(2.0 / (float(nx) * nx))
-            W[:nx, nx:N].mul_(-2.0 / (float(nx) * ny))
-            W[nx:, :nx].mul_(-2.0 / (float(nx) * ny))
-            W[nx:, nx:N].mul_(2.0 / (float(ny) * ny))
+            # W = dK/dL scaled by (gK + gK^T): 2 / n_x^2 | -2 / (n_x n_y) | 2 / n_y^2 per block, formed in a buffer of its own:
+            # dK is a saved tensor, and a retained graph may be differentiated again
+            dK = ctx.saved_tensors[2]
+            W = torch.zeros_like(dK)
+            torch.mul(dK[:nx, :nx], 2.0 / (float(nx) * nx), out=W[:nx, :nx])
+            torch.mul(dK[:nx, nx:N], -2.0 / (float(nx) * ny), out=W[:nx, nx:N])
+            torch.mul(dK[nx:, :nx], -2.0 / (float(nx) * ny), out=W[nx:, :nx])
+            torch.mul(dK[nx:, nx:N], 2.0 / (float(ny) * ny), out=W[nx:, nx:N])
             out = torch.empty(N, pp, dtype=torch.float32, device=Z.device)
             ops.mmd_backward(W, Z, 0, N, N, pp, None, out)
             out = out[:, :p] * gl
@@ -413,7 +426,7 @@ class MMDLossConstrained(nn.Module):
         # the reference passes Y = f(U * X), i.e. equal shapes: that is the fused tile path.  Anything else (n_x != n_y, or a U
         # with another row count) takes the general path on the materialised kernel matrix.
         fn = _MMDLossFn if (Y.shape == X.shape and U.shape[0] == X.shape[0]) else _MMDLossUnequalFn
-        out = fn.apply(X.contiguous().float(), Y.contiguous().float(), U, self.weight, self.kernel)
+        out = fn.apply(_dense(X.float()), _dense(Y.float()), U, self.weight, self.kernel)
         self.bandwidth = self.kernel.bandwidth
         self.bandwidth_multipliers = self.kernel.bandwidth_multipliers
         return out
