@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_*, vgan_iforest_*_blocks, vgan_outlier_*_metric, vgan_outlier_pack_unit and vgan_loci_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_*, vgan_iforest_*_blocks, vgan_outlier_*_metric, vgan_outlier_pack_unit, vgan_loci_* and vgan_rshash_* entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1001,6 +1001,52 @@ int vgan_iforest_path_sums(const float* Xq, int ldq, int rows, int d, const int3
                            int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums, vgan_stream_t stream);
 int vgan_iforest_scores(const int64_t* sums, int64_t ld_sums, int count, int rows, int64_t denom, float* score,
                         int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * RS-Hash (Sathe and Aggarwal, ICDM 2016): T components per subspace, each a randomly shifted grid of width f over r of the
+ * subspace's non-constant features, holding how many of s sampled rows fall into each occupied cell; a row's score falls
+ * with the log of the count of its own cell  (v-gan_amd/outlier.py: SubspaceRSHash, whose docstring is the definition;
+ * kernels in csrc/outlier_rshash.hip).  2 <= s <= VGAN_RSHASH_MAX_SAMPLES, 1 <= T <= VGAN_RSHASH_MAX_COMPONENTS; the three
+ * entries take the same (T, s).  COMPONENT c = z T + t is component t of subspace z; the host draws its parameters
+ * (rshash_components): comp_dims int32 [S, T] (r, 0 .. VGAN_RSHASH_MAX_DIMS; 0: the subspace has no candidate feature),
+ * comp_feat int32 [S, T, VGAN_RSHASH_MAX_DIMS] (columns of X, ascending; held to [0, d)), comp_shift float64 [S, T,
+ * VGAN_RSHASH_MAX_DIMS] (alpha) and comp_width float64 [S, T] (f, in [1 / 64, 63 / 64]).
+ * The digit of a value x of chosen feature j: x' = (x - mn_j) / w_j, 0 where w_j = mx_j - mn_j is 0; y = floor((x' + alpha_j)
+ *   / f) clamped to [-1, floor(1 / f) + 2] (NaN to -1); digit = y + 1.  Float64 on the float32 values, every operation
+ *   rounded on its own.  R = floor(1 / f) + 4 and key = sum_j digit_j R^j in uint64, j over the chosen features in order.
+ * vgan_rshash_build: the components of the subspaces first .. first + count - 1 from X [n, d] (ldx), s <= n <=
+ *   VGAN_RSHASH_MAX_ROWS.  The sample of component c is rows feistel_perm(i, n, seed, c), i < s (the permutation of
+ *   vgan_shuffle_index).  sample_min / sample_max float32 [S, T, VGAN_RSHASH_MAX_DIMS]: the exact float32 min and max of
+ *   every chosen feature over the sample, -0.0 as +0.0, 0 past r.  cell_key uint64 [S, T, s]: the distinct keys of the
+ *   sampled rows, ascending, then 2^64 - 1; cell_count int32 [S, T, s]: their counts, then 0; n_cells int32 [S, T].  r = 0:
+ *   no cell.  sample_rows int32 [S, T, s] (may be NULL) receives the sample's row indices, ascending.  One workgroup per
+ *   component, sample and keys in LDS; no workspace.  Everything depends on the row sets alone: the same bits from run to
+ *   run and for every split of the subspaces over calls.
+ * vgan_rshash_cell_sums: sums int64 [count, ld_sums] (ld_sums >= rows): for every query row and every subspace of the range
+ *   the total over its T components of table[c_t]: c_t the count of the cell of the row's key (0 where absent), plus 1 --
+ *   except, when sample_rows is given (the fit), for a row that is in the component's sample: row i of the call is row
+ *   row_base + i of the fitted X.  A component with r = 0 adds table[s + 1].  table int64 [s + 2] is formed on the host
+ *   (rshash_log_table: rint(log2(c) 2^32); the device computes no logarithm).  Element (i, f) of the query rows is
+ *   Xq[i row_stride + f col_stride]: row-major (col_stride 1, row_stride >= d) or column-major (row_stride 1, col_stride
+ *   >= rows).  Integer sums: the same for every split of the rows or the subspaces over calls.  count <= 65535.
+ * vgan_rshash_scores: score float32 [count, ld_score] = float32(1 - double(sum) / double(denom)), denom = T table[s + 1] > 0.
+ * Every entry returns VGAN_ERR_ARG before touching the device when an argument is out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_RSHASH_MAX_SAMPLES 4096 /* the sample's row indices and keys live in LDS */
+#define VGAN_RSHASH_MAX_COMPONENTS 1024
+#define VGAN_RSHASH_MAX_DIMS 12 /* r at s = 4096 */
+#define VGAN_RSHASH_MAX_ROWS 16777216 /* 2^24: the range pass of the candidate features */
+int vgan_rshash_build(const float* X, int ldx, int64_t n, int d, int first, int count, int T, int s, uint64_t seed,
+                      const int32_t* comp_dims, const int32_t* comp_feat, const double* comp_shift, const double* comp_width,
+                      uint64_t* cell_key, int32_t* cell_count, int32_t* n_cells, float* sample_min, float* sample_max,
+                      int32_t* sample_rows, vgan_stream_t stream);
+int vgan_rshash_cell_sums(const float* Xq, int64_t row_stride, int64_t col_stride, int rows, int d, int64_t row_base, int first,
+                          int count, int T, int s, const int32_t* comp_dims, const int32_t* comp_feat, const double* comp_shift,
+                          const double* comp_width, const uint64_t* cell_key, const int32_t* cell_count, const int32_t* n_cells,
+                          const float* sample_min, const float* sample_max, const int32_t* sample_rows, const int64_t* table,
+                          int64_t* sums, int64_t ld_sums, vgan_stream_t stream);
+int vgan_rshash_scores(const int64_t* sums, int64_t ld_sums, int count, int rows, int64_t denom, float* score,
+                       int64_t ld_score, vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Deep isolation forest (Xu, Pang, Wang, Wang, TKDE 2023; pyod's DIF): r randomly initialised, never trained MLPs per

@@ -96,6 +96,14 @@ difference of the two paths' ensemble scores.
     layer one vgan_gemm_grouped product on the weights of vgan_dif_weights and torch.tanh), scaled to all of them; and numpy
     (float32 products and tanh) plus sklearn's IsolationForest(6 trees, n_jobs=16) per block on 16 CPU threads for 2
     subspaces and 2 000 rows, scaled to all rows and subspaces.
+  --method rshash: RS-Hash (vgan_amd.SubspaceRSHash at its defaults: 100 components on 1 000 sampled rows each) on d = 784, S = 50
+    sampled, n = 2000, 10^4 and 5 10^4: fit (a new detector each time, so with the host draws), refit and decision_function (the
+    training rows as new rows); the three stages of the fit
+    launched alone on the fitted state (build, cell sums with the in-sample test, scores) and the host's share (the range pass
+    and its copy, the draws); the cell sums as (row, component) pairs a second; the cell sums reading X row-major through L2
+    against reading a column-major copy (the copy timed with it); IN THE SAME RUN SubspaceIForest (100 trees), SubspaceHBOS
+    and SubspaceDIF at their defaults on the same rows; and the same rules in numpy on 16 host threads (the components of a
+    subspace dealt to a thread pool, the device's samples given) for two subspaces, scaled to all of them and compared.
   --method sod: the subspace outlier degree (vgan_amd.SubspaceSOD) at d = 784, S = 50 sampled, n = 2000 and 10^4, with pyod's
     defaults (n_neighbors 20, ref_set 10, alpha 0.8) and with (32, 31, 0.3): fit and decision_function (the training rows as
     new rows) beside the LOF fit with the same n_neighbors on the same rows; the fit split into the neighbour lists (pack,
@@ -1793,6 +1801,100 @@ def run_dif(d, n, count, reps, baselines=True, sample=2, host_rows=2000):
     return row
 
 
+def numpy_rshash_component(X, rows, cols, alpha, f, table, fitting):
+    """int64 [n]: table[c] of every row of X for one component, by the rules of SubspaceRSHash in plain numpy."""
+    sub = X[:, cols].astype(np.float64)
+    mn, mx = sub[rows].min(axis=0), sub[rows].max(axis=0)
+    w = mx - mn
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(w > 0, (sub - mn) / w, 0.0)
+    y = np.clip(np.floor((t + alpha) / f), -1.0, np.floor(1.0 / f) + 2.0).astype(np.int64) + 1
+    R = int(np.floor(1.0 / f)) + 4
+    key = (y * R ** np.arange(len(cols), dtype=np.int64)).sum(axis=1)
+    keys, counts = np.unique(key[rows], return_counts=True)
+    at = np.minimum(np.searchsorted(keys, key), len(keys) - 1)
+    c = np.where(keys[at] == key, counts[at], 0) + 1
+    if fitting:
+        c[rows] -= 1
+    return table[c]
+
+
+def rshash_host(X, ens, samples, pick):
+    """(seconds of the numpy fit sums of the subspaces `pick` on 16 threads, whether they equal the device's)."""
+    from multiprocessing.pool import ThreadPool
+    table = ens._log_table.cpu().numpy()
+    equal = True
+    with ThreadPool(16) as pool:
+        t0 = time.perf_counter()
+        for z in pick:
+            jobs = [(X, samples[z, t], ens.component_features_[z, t, :r], ens.component_shift_[z, t, :r], ens.grid_width_[z, t], table, True)
+                    for t, r in enumerate(ens.component_dims_[z]) if r > 0]
+            total = sum(pool.starmap(numpy_rshash_component, jobs)) if jobs else np.full(X.shape[0], ens._denom)
+            equal = equal and bool(np.array_equal(total, ens.cell_sums_[z]))
+        return time.perf_counter() - t0, equal
+
+
+def run_rshash(d, n, count, reps, baselines=True, sample=2):
+    from vgan_amd.outlier import rshash_components
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceRSHash(m, p)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)  # warm: a refit keeps the host draws
+    t_first, tff = timed(lambda: vgan_amd.SubspaceRSHash(m, p).fit(Xd), reps)  # a new detector draws its components first
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    ops, inner = ens.ops, max(reps, 5)
+    T, s = ens.n_estimators, ens.max_samples_
+    state = tuple(torch.empty_like(a) for a in ens._state)
+    samples = torch.empty(S, T, s, dtype=torch.int32, device="cuda")
+    sums = torch.empty(S * n, dtype=torch.int64, device="cuda")
+    per = torch.empty(S, n, dtype=torch.float32, device="cuda")
+    keys = torch.empty(d, 2, dtype=torch.int64, device="cuda")
+    t_range, _ = timed(lambda: (ops.hist_column_range(Xd, keys), keys.cpu()), inner)
+    t0 = time.perf_counter()
+    rshash_components([len(c) for c in ens.candidate_features_], T, s, ens.seed)
+    t_draw = time.perf_counter() - t0
+    t_build, _ = timed(lambda: ops.rshash_build(Xd, 0, S, ens.seed, ens._comp, state, samples), inner)
+    for a, b in zip(state, ens._state):
+        assert torch.equal(a, b)
+    t_sums, _ = timed(lambda: ops.rshash_cell_sums(Xd, False, 0, 0, S, ens._comp, ens._state, samples, ens._log_table, sums), inner)
+    assert np.array_equal(sums.view(S, n).cpu().numpy(), ens.cell_sums_)
+    t_new, _ = timed(lambda: ops.rshash_cell_sums(Xd, False, 0, 0, S, ens._comp, ens._state, None, ens._log_table, sums), inner)
+    row_major = sums.clone()
+    t_copy, _ = timed(lambda: Xd.t().contiguous(), inner)
+    Xt = Xd.t().contiguous()
+    t_col, _ = timed(lambda: ops.rshash_cell_sums(Xt, True, 0, 0, S, ens._comp, ens._state, None, ens._log_table, sums), inner)
+    assert torch.equal(sums, row_major)
+    t_scores, _ = timed(lambda: ops.rshash_scores(sums, S, n, ens._denom, per), inner)
+    live = int((ens.component_dims_ > 0).sum())
+    row = {"method": "rshash", "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_estimators": T, "max_samples": s,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "candidates_median": float(np.median([len(c) for c in ens.candidate_features_])),
+           "r_mean": round(float(ens.component_dims_[ens.component_dims_ > 0].mean()), 2),
+           "cells_mean": round(float(ens.n_cells_[ens.component_dims_ > 0].mean()), 1),
+           "fit_s": round(t_first, 6), "fit_reps_s": tff, "refit_s": round(t_fit, 6), "refit_reps_s": tf,
+           "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td,
+           "range_pass_and_copy_s": round(t_range, 6), "draws_host_s": round(t_draw, 6), "build_s": round(t_build, 6),
+           "cell_sums_fit_s": round(t_sums, 6), "cell_sums_new_rows_s": round(t_new, 6), "scores_s": round(t_scores, 6),
+           "pairs_per_s_fit": round(live * float(n) / t_sums / 1e9, 2), "pairs_per_s_new_rows": round(live * float(n) / t_new / 1e9, 2),
+           "pairs_unit": "1e9 (row, component) pairs / s",
+           "x_row_major_through_l2_s": round(t_new, 6), "x_column_major_copy_s": round(t_col, 6), "x_transpose_s": round(t_copy, 6),
+           "x_layout_kept": "column-major copy" if ens._column_major else "row-major through L2",
+           "state_bytes": int(12 * S * T * s + 2 * 4 * 12 * S * T + 4 * S * T)}
+    for name, other in (("iforest", vgan_amd.SubspaceIForest(m, p)), ("hbos", vgan_amd.SubspaceHBOS(m, p)), ("dif", vgan_amd.SubspaceDIF(m, p))):
+        t_o, to = timed(lambda: other.fit(Xd), reps)
+        t_od, tod = timed(lambda: other.decision_function(Xd), reps)
+        row.update({f"{name}_fit_s": round(t_o, 6), f"{name}_fit_reps_s": to, f"{name}_decision_function_s": round(t_od, 6),
+                    f"{name}_over_rshash_fit": round(t_o / t_first, 2)})
+        del other
+    if baselines:
+        pick = np.unique(np.linspace(0, S - 1, min(S, sample)).astype(int))
+        t_np, equal = rshash_host(X, ens, samples.cpu().numpy(), pick)
+        row.update({"numpy_subspaces_timed": int(len(pick)), "numpy_16_threads_fit_sums_s": round(t_np * S / len(pick), 3),
+                    "numpy_sums_equal_the_device": equal, "fit_speedup_vs_numpy": round(t_np * S / len(pick) / t_first, 1)})
+    return row
+
+
 def ae_torch_bmm(Xd, ens, steps):
     """Seconds per optimiser step of the nets of ens trained in torch on the GPU: every layer one torch.baddbmm over all S
     nets, the first and last layer padded to the widest subspace (the padded inputs are zero, the padded outputs masked out of
@@ -2216,13 +2318,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
-    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics", "metric", "loci"], default="knn")
+    ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics", "metric", "loci", "rshash"], default="knn")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
-    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / loci / dif / kpca / ae / deepsvdd: the fused path only (for a run under a profiler)")
+    ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / loci / dif / kpca / ae / deepsvdd / rshash: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
     ap.add_argument("--normalize", choices=["zscore", "robust", "minmax"], action="append",
                     help="measure score normalisation (repeat for several modes)")
-    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / loci / dif / sod / kpca / ae / deepsvdd: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
+    ap.add_argument("--shape", help="abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / loci / dif / sod / kpca / ae / deepsvdd / rshash: one shape d,n,S_sampled instead of the table's (for a run under a profiler)")
     ap.add_argument("--out", help="also write the JSON result to this file")
     args = ap.parse_args()
     bandwidth = args.bandwidth if args.bandwidth in ("scott", "silverman") else float(args.bandwidth)
@@ -2419,6 +2521,14 @@ def main():
             pool.join()
         if not args.shape:  # where the two workgroup shapes of the draw kernel meet
             out["workgroup_shapes"] = run_hics_shapes(64, [1024, 4096] if args.quick else [4096, 16384, 32768, 65536], args.reps)
+        configs = []
+    if args.method == "rshash":
+        shapes = [(20, 500, 8)] if args.quick else [(784, 2000, 50), (784, 10_000, 50), (784, 50_000, 50)]
+        if args.shape:
+            shapes = [tuple(int(v) for v in args.shape.split(","))]
+        for d, n, count in shapes:
+            out["configs"].append(run_rshash(d, n, count, args.reps, baselines=not args.no_baselines))
+            print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "metric":
         shapes = [(784, 2000, 10)] if args.quick else [(784, 2000, 50), (784, 10_000, 50)]

@@ -10,11 +10,11 @@ from .modules import (Generator_big, upper_softmax, Encoder, Decoder, Detector, 
 from .vgan import VGAN, VGAN_no_kl  # noqa: F401
 from .outlier import (SubspaceEnsemble, SubspaceCBLOF, SubspaceABOD, SubspaceECOD, SubspaceIForest, SubspaceMahalanobis,  # noqa: F401
                       SubspaceGMM, SubspaceHBOS, SubspaceLODA, SubspacePCA, SubspaceOCSVM, SubspaceCOF, SubspaceINNE, SubspaceSOS, SubspaceDIF, SubspaceSOD, SubspaceAutoEncoder, SubspaceDeepSVDD,
-                      SubspaceKPCA, SubspaceLOCI, build_ensemble)
+                      SubspaceKPCA, SubspaceLOCI, SubspaceRSHash, build_ensemble)
 from .hics import HiCS, subspace_contrast, random_subspaces  # noqa: F401
 
 __all__ = ["VGAN", "VGAN_no_kl", "Generator_big", "upper_softmax", "Encoder", "Decoder", "Detector", "RBF",
            "MMDLossConstrained", "SubspaceEnsemble", "SubspaceCBLOF", "SubspaceABOD", "SubspaceECOD", "SubspaceIForest",
            "SubspaceMahalanobis", "SubspaceGMM", "SubspaceHBOS", "SubspaceLODA", "SubspacePCA", "SubspaceOCSVM",
            "SubspaceCOF", "SubspaceINNE", "SubspaceSOS", "SubspaceDIF", "SubspaceSOD", "SubspaceKPCA", "SubspaceAutoEncoder", "SubspaceDeepSVDD",
-           "SubspaceLOCI", "build_ensemble", "HiCS", "subspace_contrast", "random_subspaces", "lib"]
+           "SubspaceLOCI", "SubspaceRSHash", "build_ensemble", "HiCS", "subspace_contrast", "random_subspaces", "lib"]

@@ -1106,6 +1106,60 @@ class HipOps:
                                                           int(depth), _ptr(cq), _ptr(sums), rows, self._stream()),
                    "vgan_iforest_path_sums_blocks")
 
+    # ---- RS-Hash grid counts over subspaces (vgan_amd.outlier.SubspaceRSHash) -------------------------------
+    # comp: (dims int32 [S, T], feat int32 [S, T, 12], shift float64 [S, T, 12], width float64 [S, T]): the host's draws;
+    # state: (cell_key int64 [S, T, s] holding the library's uint64 keys, cell_count int32 [S, T, s], n_cells int32 [S, T],
+    # sample_min float32 [S, T, 12], sample_max float32 [S, T, 12])
+    @staticmethod
+    def _rshash_tables(comp, state):
+        dims, feat, shift, width = comp
+        key, cnt, cells, lo, hi = state
+        S, T, s = key.shape
+        _vec(dims, "comp dims", torch.int32), _vec(feat, "comp feat", torch.int32)
+        _vec(shift, "comp shift", torch.float64), _vec(width, "comp width", torch.float64)
+        _vec(key, "cell_key", torch.int64), _vec(cnt, "cell_count", torch.int32), _vec(cells, "n_cells", torch.int32)
+        _vec(lo, "sample_min"), _vec(hi, "sample_max")
+        assert dims.numel() == S * T and width.numel() == S * T and cells.numel() == S * T and cnt.numel() == S * T * s
+        assert min(feat.numel(), shift.numel(), lo.numel(), hi.numel()) >= S * T * 12
+        return S, T, s
+
+    def rshash_build(self, X, first, count, seed, comp, state, sample_rows=None):
+        """Fills the state of the components of the subspaces first .. first + count - 1 from X [n, d]; sample_rows int32
+        [S, T, s] (optional) receives every component's sorted sample."""
+        _mat(X, "X")
+        S, T, s = self._rshash_tables(comp, state)
+        n, d = X.shape
+        assert first + count <= S
+        if sample_rows is not None:
+            _vec(sample_rows, "sample_rows", torch.int32)
+            assert sample_rows.numel() == S * T * s
+        _lib.check(self.lib.vgan_rshash_build(_ptr(X), X.stride(0), n, d, int(first), int(count), T, s, int(seed), *map(_ptr, comp),
+                                              *map(_ptr, state), _ptr(sample_rows), self._stream()), "vgan_rshash_build")
+
+    def rshash_cell_sums(self, Xq, column_major, row_base, first, count, comp, state, sample_rows, table, sums):
+        """sums int64 [count, rows]: per query row and subspace of the range, table[c] summed over the subspace's components.
+        Xq: float32 [rows, d], or with column_major its transposed copy [d, rows] (a column slice of one may be given);
+        sample_rows: the fit's sorted samples (its rows are rows row_base .. of the fitted X), None for new rows."""
+        _mat(Xq if Xq.shape[1] > 1 else Xq[:, 0:1].as_strided(Xq.shape, (Xq.stride(0), 1)), "Xq")  # a single column has no inner stride
+        _vec(table, "table", torch.int64), _vec(sums, "sums", torch.int64)
+        S, T, s = self._rshash_tables(comp, state)
+        d, rows = Xq.shape if column_major else Xq.shape[::-1]
+        strides = (1, Xq.stride(0)) if column_major else (Xq.stride(0), 1)
+        assert first + count <= S and table.numel() >= s + 2 and sums.numel() >= count * rows
+        if sample_rows is not None:
+            _vec(sample_rows, "sample_rows", torch.int32)
+            assert sample_rows.numel() == S * T * s
+        _lib.check(self.lib.vgan_rshash_cell_sums(_ptr(Xq), *strides, rows, d, int(row_base), int(first), int(count), T, s,
+                                                  *map(_ptr, comp), *map(_ptr, state), _ptr(sample_rows), _ptr(table), _ptr(sums), rows,
+                                                  self._stream()), "vgan_rshash_cell_sums")
+
+    def rshash_scores(self, sums, count, rows, denom, score):
+        """score float32 [count, rows] (a view into the score matrix may be given) = 1 - sums / denom."""
+        _vec(sums, "sums", torch.int64), _mat(score, "score")
+        assert sums.numel() >= count * rows and score.shape[0] == count and score.shape[1] >= rows
+        _lib.check(self.lib.vgan_rshash_scores(_ptr(sums), int(rows), int(count), int(rows), int(denom), _ptr(score), score.stride(0),
+                                               self._stream()), "vgan_rshash_scores")
+
     # ---- deep isolation forest over subspaces (vgan_amd.outlier.SubspaceDIF) --------------------------------
     # net: (r, hidden tuple, q, activation code); w_off: int64 [count] on the device, the blocks' offsets into W
     def dif_weights(self, feat_off, net, first, count, scale, seed, W, w_off, total):

@@ -68,6 +68,11 @@ on the device (csrc/outlier_iforest.hip), with path lengths summed in fixed poin
 order; it never sweeps pairs of rows either.  Its contract (samples, node numbering, the leaf rule, the draws, the
 threshold, the fixed-point path length, the score) is that class's docstring.
 
+``SubspaceRSHash`` is RS-Hash: per subspace a hundred randomly shifted grids over a few of its non-constant features, each
+holding the counts of a few hundred sampled rows per cell, counted and looked up on the device (csrc/outlier_rshash.hip);
+linear in the rows, yet a cell is a joint statement about several features.  Its contract (candidates, the host draws,
+samples, digits and keys, the plus-one rule, the fixed-point log counts, the score) is that class's docstring.
+
 ``SubspaceINNE`` is the nearest-neighbour isolation ensemble (iNNE): per subspace a few hundred estimators of a handful of
 sampled rows each, a hypersphere around every sampled row that reaches its nearest other one, and per query row the
 isolation ratio of the smallest sphere that covers it (csrc/outlier_inne.hip); local and rotation free where the isolation
@@ -1820,6 +1825,276 @@ class SubspaceIForest(_SubspaceScorer):
             self.ops.iforest_build(X, self._table, first, count, int(self.plan.dims[first:first + count].max()), psi, self.depth_limit_,
                                    self.seed, self._trees)
         scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)
+
+
+# ---- RS-Hash: counts of randomly shifted grid cells over the subspaces --------------------------------------------------
+RSHASH_MAX_COMPONENTS = 1024  # VGAN_RSHASH_MAX_COMPONENTS
+RSHASH_MAX_SAMPLES = 4096  # VGAN_RSHASH_MAX_SAMPLES: the sampled rows and their keys live in LDS
+RSHASH_MAX_DIMS = 12  # VGAN_RSHASH_MAX_DIMS: r at s = 4096
+RSHASH_MAX_ROWS = 1 << 24  # VGAN_RSHASH_MAX_ROWS
+RSHASH_AUTO_SAMPLES = 1000  # max_samples="auto", the paper's s
+
+
+def check_rshash_estimators(n_estimators):
+    if not (_is_int(n_estimators) and 1 <= int(n_estimators) <= RSHASH_MAX_COMPONENTS):
+        raise ValueError(f"n_estimators must be an integer between 1 and {RSHASH_MAX_COMPONENTS}, got {n_estimators!r}")
+    return int(n_estimators)
+
+
+def check_rshash_samples(max_samples):
+    """ "auto" (1000) or an integer between 2 and RSHASH_MAX_SAMPLES; fit takes min(max_samples, n)."""
+    if isinstance(max_samples, str) and max_samples == "auto":
+        return RSHASH_AUTO_SAMPLES
+    if not (_is_int(max_samples) and 2 <= int(max_samples) <= RSHASH_MAX_SAMPLES):
+        raise ValueError(f"max_samples must be 'auto' or an integer between 2 and {RSHASH_MAX_SAMPLES}, got {max_samples!r}")
+    return int(max_samples)
+
+
+def rshash_log_table(s):
+    """int64 [s + 2]: table[c] = rint(log2(c) 2^32) in float64, table[0] = 0 (no count is 0)."""
+    c = np.arange(s + 2, dtype=np.float64)
+    c[0] = 1.0
+    return np.rint(np.log2(c) * 4294967296.0).astype(np.int64)
+
+
+def rshash_components(candidate_counts, n_estimators, s, seed):
+    """(grid_width float64 [S, T], dims int32 [S, T], positions int32 [S, T, 12], shifts float64 [S, T, 12]): the draws of
+    every component, from ONE rng = numpy.random.default_rng(seed), subspace by subspace (c_z = candidate_counts[z] candidate
+    features), then component by component, and within a component in this order:
+
+        f = lo + (hi - lo) * rng.random(), lo = 1 / sqrt(s), hi = 1 - lo (as written, also where s < 4 inverts the interval)
+        L = log(s) / log(max(2, 1 / f)), r_lo = floor(1 + L / 2), r_hi = max(r_lo, floor(L))
+        r = min(rng.integers(r_lo, r_hi + 1), c_z)
+        positions = sort(rng.choice(c_z, r, replace=False))   (positions among the candidates in ascending feature order)
+        alpha = f * rng.random(r)
+
+    positions is padded with -1 and shifts with 0 past r.  A subspace with c_z = 0 draws nothing: its rows are f = 0, r = 0.
+    r never exceeds RSHASH_MAX_DIMS (12) for s <= 4096, and (floor(1 / f) + 4)^r stays below 2^63 (asserted)."""
+    rng = np.random.default_rng(seed)
+    T, s = int(n_estimators), int(s)
+    counts = np.asarray(candidate_counts, dtype=np.int64).reshape(-1)
+    S = len(counts)
+    width, dims = np.zeros((S, T), np.float64), np.zeros((S, T), np.int32)
+    positions, shifts = np.full((S, T, RSHASH_MAX_DIMS), -1, np.int32), np.zeros((S, T, RSHASH_MAX_DIMS), np.float64)
+    lo = 1.0 / math.sqrt(s)
+    hi = 1.0 - lo
+    for z, c in enumerate(counts):
+        if c == 0:
+            continue
+        for t in range(T):
+            f = lo + (hi - lo) * rng.random()
+            L = math.log(s) / math.log(max(2.0, 1.0 / f))
+            r_lo = math.floor(1.0 + L / 2.0)
+            r_hi = max(r_lo, math.floor(L))
+            r = min(int(rng.integers(r_lo, r_hi + 1)), int(c))
+            assert 1 <= r <= RSHASH_MAX_DIMS and (math.floor(1.0 / f) + 4) ** r < 1 << 63
+            width[z, t], dims[z, t] = f, r
+            positions[z, t, :r] = np.sort(rng.choice(int(c), r, replace=False))
+            shifts[z, t, :r] = f * rng.random(r)
+    return width, dims, positions, shifts
+
+
+class SubspaceRSHash(_SubspaceScorer):
+    """RS-Hash per subspace (Sathe and Aggarwal, "Subspace Outlier Detection in Linear Time with Randomized Hashing", ICDM
+    2016; pyod's ``RSHash`` is not built on it), combined like the other detectors of this module: ``fit`` sets
+    ``decision_scores_``, ``decision_function`` scores new rows; higher is more outlying.  Each of T components per subspace
+    is a randomly shifted grid of width f over r of the subspace's features and holds how many of s sampled rows fall into
+    each occupied cell; a row's score falls with the log of the count of its own cell.  An r-dimensional cell is a joint
+    statement about r features, so the score sees a broken correlation that no single feature shows; yet there is no sweep
+    over pairs of rows, no tree, no moment and no training: linear in n.  It is itself a subspace method and sits one level
+    below the model's subspaces, the way LODA's sparse projections do.  Neither pyod nor the authors' code was at hand:
+    the rules are the paper's as remembered, made definite here, so this definition and its numpy restatement in
+    tests/test_outlier_rshash_cpu.py are what binds.
+
+    X is cast to float32.  n rows are given to ``fit``, 2 <= n <= 2^24; T = n_estimators (1 .. 1024); s = ``max_samples_`` =
+    min(max_samples, n), max_samples "auto" (1000: the paper's) or 2 .. 4096; seed in [0, 2^64).
+
+    Candidate features.  The candidates of subspace z are the features of F_z whose maximum exceeds their minimum over all n
+    fitted rows (a range pass on the device), c_z their number: a constant pixel uses up no grid dimension.  A subspace with
+    c_z = 0 has no component and scores exactly 0 for every row.
+
+    Draws.  rshash_components(candidate_counts, T, s, seed) draws on the host, from one numpy.random.default_rng(seed),
+    subspace by subspace in the given order and component by component, in this order: f = lo + (hi - lo) rng.random() with
+    lo = 1 / sqrt(s), hi = 1 - lo; with L = log(s) / log(max(2, 1 / f)), r_lo = floor(1 + L / 2), r_hi = max(r_lo, floor(L)):
+    r = min(rng.integers(r_lo, r_hi + 1), c_z); positions = sort(rng.choice(c_z, r, replace=False)) among the candidates in
+    ascending feature order; alpha = f rng.random(r).  r <= 12.  The draws are keyed by the subspace's position in the
+    given set, as SubspaceDIF's nets are: a subspace fitted alone differs from the same subspace at position 3, and so
+    does the same subspace behind others whose candidate counts changed.
+
+    Sample.  Component (z, t) has the stream id = z T + t; its sample is the set of rows feistel_perm(i, n, seed, id), i < s
+    (the permutation of vgan_shuffle_index: the sampler of SubspaceIForest and SubspaceINNE).
+
+    Cells.  For each chosen feature j: mn_j and mx_j are the exact float32 minimum and maximum over the sample (-0.0 as
+    +0.0), w_j = mx_j - mn_j, x' = (x - mn_j) / w_j if w_j > 0, else 0; y = floor((x' + alpha_j) / f), clamped in float64 to
+    [-1, floor(1 / f) + 2] before the conversion (new rows may lie anywhere; NaN goes to -1); digit_j = y + 1.  The
+    arithmetic is float64 on the float32 values, every operation rounded on its own (no fused multiply-add): a plain numpy
+    loop gives the same integers.  R = floor(1 / f) + 4, and the cell key is the uint64 sum_j digit_j R^j, j over the chosen
+    features in ascending order (below 2^32 within the limits above).  Sampled rows produce neither digit 0 nor digit
+    R - 1, so cells with those digits always count 0.
+
+    Score.  c_t is the count of the row's cell in component t, 0 if no sampled row fell into it.  At ``fit`` c_t gets plus 1
+    unless the row is in the sample of component t; in ``decision_function`` it always gets plus 1 (the paper's rule), so
+    c_t >= 1.  table = rshash_log_table(s) is int64 [s + 2], table[c] = rint(log2(c) 2^32), formed on the host in float64 and
+    uploaded (the device computes no logarithm); sum[z, i] = sum_t table[c_t] in int64 (a subspace with c_z = 0 holds
+    T table[s + 1]) and
+
+        score[z, i] = float32(1 - double(sum[z, i]) / (double(T) double(table[s + 1])))
+
+    in [0, 1], 1 for a row alone in its cell in every component.  It is scale free, so like LOF, COF, iNNE and SOS it sums
+    across subspaces of mixed width without ``normalize``.  Because sampled rows count themselves at ``fit``,
+    ``decision_function(X_train)`` is NOT ``decision_scores_`` (as with SubspaceECOD and SubspaceSOS): it exceeds every
+    count of a sampled row by one.
+
+    Keys, counts, sums and scores are integers up to the final division: bit-identical from run to run, for every
+    workspace_bytes (which bounds the transient sums and scores of scoring, iforest_chunks' rule of 12 bytes per subspace
+    and row; not the state, not the sorted samples ``fit`` holds while it scores, 4 T s bytes a subspace, and not the
+    column-major copy of the scored rows, 4 d bytes a row) and for every split of the query rows.  The fitted state takes 12 T s bytes a subspace; X is not kept.  NaN input leaves the results
+    unspecified and neither faults nor hangs.
+
+    ``fit`` publishes, copied to the host on first use: ``cell_key_`` uint64 [S, T, s] (the distinct keys of a component's
+    sampled rows, ascending, padded with 2^64 - 1), ``cell_count_`` int32 [S, T, s] (padded with 0), ``n_cells_`` int32
+    [S, T], ``sample_min_`` / ``sample_max_`` float32 [S, T, 12] (0 past r) and ``cell_sums_`` int64 [S, n] (the sums of the
+    fitted rows; ``cell_sums(X)`` gives those of new rows); and the host tables ``candidate_features_`` (a list of S int
+    arrays), ``component_features_`` int32 [S, T, 12] (columns of X, -1 past r), ``component_shift_`` float64 [S, T, 12],
+    ``grid_width_`` float64 [S, T], ``component_dims_`` int32 [S, T]; and ``max_samples_``.  normalize, combination,
+    contamination, ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.
+    All of it runs in libvgan_hip.so (csrc/outlier_rshash.hip; the range pass is csrc/outlier_hist.hip's)."""
+
+    _host_state = None
+    _draws = None  # (key, the host draws): a refit with the same candidate counts and sample size keeps them
+    # cell sums gather X[row, f] at a fixed f per instruction: from a column-major copy of the query rows the 64 loads of a
+    # wave are neighbouring addresses; False reads X as given through L2 (measured: 7.8 times slower at n = 50 000, DESIGN.md)
+    _column_major = True
+
+    def __init__(self, subspaces, proba, n_estimators=100, max_samples="auto", seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
+                 normalize=None, combination="sum", contamination=0.1):
+        self.n_estimators = check_rshash_estimators(n_estimators)
+        self.max_samples = max_samples
+        self._max_samples = check_rshash_samples(max_samples)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= RSHASH_MAX_ROWS:
+            raise ValueError(f"SubspaceRSHash fit needs between 2 and {RSHASH_MAX_ROWS} rows, got {n}")
+
+    def _ranges(self):
+        count, rows = iforest_chunks(self.plan.count, self.workspace_bytes)
+        return [(first, min(count, self.plan.count - first)) for first in range(0, self.plan.count, count)], rows
+
+    def cell_sums(self, X):
+        """int64 [S, n]: the fixed-point log-count sums of the rows of X, scored as new rows, over every subspace."""
+        self._require_fit()
+        X = _device_matrix(X, self.plan.d)
+        return self._sums(X, None, None).cpu().numpy()
+
+    def _sums(self, X, per, samples):
+        """Looks the rows of X up range by range and row chunk by row chunk; samples: the fit's sorted samples (X is then the
+        fitted matrix), None for new rows.  per None: returns the int64 sums [S, nq]; otherwise fills the float32 scores per
+        [S, nq] and returns the sums only at fit."""
+        nq = X.shape[0]
+        ranges, rows = self._ranges()
+        rows = min(rows, nq)
+        keep = per is None or samples is not None
+        out = torch.empty(self.plan.count, nq, dtype=torch.int64, device=X.device) if keep else None
+        sums = torch.empty(ranges[0][1] * rows, dtype=torch.int64, device=X.device)
+        Xt = X.t().contiguous() if self._column_major else None
+        for first, count in ranges:
+            for r0 in range(0, nq, rows):
+                r1 = min(r0 + rows, nq)
+                Xq = X[r0:r1] if Xt is None else Xt[:, r0:r1]
+                self.ops.rshash_cell_sums(Xq, Xt is not None, r0, first, count, self._comp, self._state, samples, self._log_table, sums)
+                if keep:
+                    out[first:first + count, r0:r1] = sums[:count * (r1 - r0)].view(count, r1 - r0)
+                if per is not None:
+                    self.ops.rshash_scores(sums, count, r1 - r0, self._denom, per[first:first + count, r0:r1])
+        return out
+
+    def _score(self, X, fitting, samples=None):
+        per = torch.empty(self.plan.count, X.shape[0], dtype=torch.float32, device=X.device)
+        sums = self._sums(X, per, samples)
+        if fitting:
+            self._fit_sums = sums
+        return self._combine(per, fitting), per
+
+    def _on_host(self):
+        self._require_fit()
+        if self._host_state is None:
+            key, cnt, cells, lo, hi = (t.cpu().numpy() for t in self._state)
+            self._host_state = (key.view(np.uint64), cnt, cells, lo, hi, self._fit_sums.cpu().numpy())
+        return self._host_state
+
+    @property
+    def cell_key_(self):
+        """uint64 [S, T, s]: the distinct cell keys of every component's sampled rows, ascending, padded with 2^64 - 1."""
+        return self._on_host()[0]
+
+    @property
+    def cell_count_(self):
+        """int32 [S, T, s]: how many sampled rows fell into the cell of cell_key_ at the same place, padded with 0."""
+        return self._on_host()[1]
+
+    @property
+    def n_cells_(self):
+        """int32 [S, T]: the occupied cells of every component."""
+        return self._on_host()[2]
+
+    @property
+    def sample_min_(self):
+        """float32 [S, T, 12]: the minimum of every chosen feature over the component's sample, 0 past r."""
+        return self._on_host()[3]
+
+    @property
+    def sample_max_(self):
+        """float32 [S, T, 12]: the maximum of every chosen feature over the component's sample, 0 past r."""
+        return self._on_host()[4]
+
+    @property
+    def cell_sums_(self):
+        """int64 [S, n]: sum_t table[c_t] of the fitted rows, sampled rows not counting themselves twice."""
+        return self._on_host()[5]
+
+    def fit(self, X, y=None):
+        """Takes the column ranges of X, draws the components on the host, counts the cells of every component's sample on
+        the device and scores X itself: decision_scores_ (float64 [n]), per_subspace_scores_, max_samples_, the host tables
+        of the draws and, on first use, cell_key_ / cell_count_ / n_cells_ / sample_min_ / sample_max_ / cell_sums_; with
+        normalize also score_center_ / score_scale_.  The cells are the fitted state: X itself is not kept."""
+        X = self._begin_fit(X)
+        n, d = X.shape
+        dev = X.device
+        S, T = self.plan.count, self.n_estimators
+        s = min(self._max_samples, n)
+        self.max_samples_, self._host_state, self._fitted = s, None, False
+        keys = torch.empty(d, 2, dtype=torch.int64, device=dev)
+        self.ops.hist_column_range(X, keys)  # keys of the float64 images of the float32 min and max, -0.0 as +0.0
+        k = keys.cpu().numpy().view(np.uint64)
+        lo_hi = np.ascontiguousarray(np.where(k >> np.uint64(63), k & np.uint64(0x7FFFFFFFFFFFFFFF), ~k)).view(np.float64)
+        varying = lo_hi[:, 1] > lo_hi[:, 0]
+        feats = [self.plan.feat[self.plan.feat_off[z]:self.plan.feat_off[z + 1]] for z in range(S)]
+        self.candidate_features_ = [f[varying[f]].astype(np.int32) for f in feats]
+        key = (tuple(len(c) for c in self.candidate_features_), T, s, self.seed)
+        if self._draws is None or self._draws[0] != key:
+            self._draws = (key, rshash_components(key[0], T, s, self.seed))
+        width, dims, positions, shifts = self._draws[1]
+        columns = np.full((S, T, RSHASH_MAX_DIMS), -1, np.int32)
+        for z, cand in enumerate(self.candidate_features_):
+            if len(cand):
+                columns[z] = np.where(positions[z] >= 0, cand[np.maximum(positions[z], 0)], -1)
+        self.grid_width_, self.component_dims_, self.component_features_, self.component_shift_ = width, dims, columns, shifts
+        self._comp = tuple(torch.as_tensor(a, device=dev) for a in (dims, columns, shifts, width))
+        table = rshash_log_table(s)
+        self._log_table = torch.as_tensor(table, device=dev)
+        self._denom = T * int(table[s + 1])
+        self._state = (torch.empty(S, T, s, dtype=torch.int64, device=dev), torch.empty(S, T, s, dtype=torch.int32, device=dev),
+                       torch.empty(S, T, dtype=torch.int32, device=dev), torch.empty(S, T, RSHASH_MAX_DIMS, dtype=torch.float32, device=dev),
+                       torch.empty(S, T, RSHASH_MAX_DIMS, dtype=torch.float32, device=dev))
+        samples = torch.empty(S, T, s, dtype=torch.int32, device=dev)
+        for first, count in self._ranges()[0]:
+            self.ops.rshash_build(X, first, count, self.seed, self._comp, self._state, samples)
+        scores, per = self._score(X, True, samples)
         return self._publish(scores, per)
 
 
@@ -4831,7 +5106,7 @@ class SubspaceSOD(_NeighborScorer):
 _METHOD_CLASSES = {"cblof": SubspaceCBLOF, "ecod": SubspaceECOD, "iforest": SubspaceIForest, "inne": SubspaceINNE,
                    "mahalanobis": SubspaceMahalanobis, "gmm": SubspaceGMM, "hbos": SubspaceHBOS, "loda": SubspaceLODA,
                    "pca": SubspacePCA, "ocsvm": SubspaceOCSVM, "sos": SubspaceSOS, "loci": SubspaceLOCI, "dif": SubspaceDIF, "kpca": SubspaceKPCA,
-                   "autoencoder": SubspaceAutoEncoder, "deepsvdd": SubspaceDeepSVDD}
+                   "autoencoder": SubspaceAutoEncoder, "deepsvdd": SubspaceDeepSVDD, "rshash": SubspaceRSHash}
 _NEIGHBOR_CLASSES = {"abod": SubspaceABOD, "cof": SubspaceCOF, "sod": SubspaceSOD}
 
 

@@ -261,7 +261,12 @@ class _RunFolder:
         k_sigma = 3; the proximity detector without a k, which finds groups of more than 32 close anomalous rows; pyod's LOCI):
         its keywords are alpha, n_min, n_radii, radii_per_octave, k_sigma, engine, splits, workspace_bytes and the same
         normalize / combination / contamination, e.g. outlier_ensemble(method="loci", n_radii=32, X=X); n_neighbors is not
-        used there."""
+        used there.
+        method "rshash" builds a SubspaceRSHash (RS-Hash: per component a randomly shifted grid over a few of the subspace's
+        non-constant features and the counts of a few hundred sampled rows per cell, the score falling with the log of the
+        count of a row's own cell; linear in the rows, yet it sees joint structure; Sathe and Aggarwal 2016): its keywords
+        are n_estimators, max_samples, seed, workspace_bytes and the same normalize / combination / contamination, e.g.
+        outlier_ensemble(method="rshash", n_estimators=100, X=X); n_neighbors is not used there."""
         if getattr(self, "subspaces", None) is None or getattr(self, "proba", None) is None:
             self.approx_subspace_dist(subspace_count)
         ens = build_ensemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)
