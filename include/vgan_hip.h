@@ -27,7 +27,7 @@ extern "C" {
 #define VGAN_ERR_ARG 1  /* bad shape / null pointer / unsupported configuration */
 #define VGAN_ERR_HIP 2  /* a HIP runtime call or launch failed */
 
-#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_*, vgan_iforest_*_blocks, vgan_outlier_*_metric, vgan_outlier_pack_unit, vgan_loci_* and vgan_rshash_* entry points only ADD symbols, so it stands */
+#define VGAN_ABI_VERSION 11 /* counts layout / signature changes; the *_ksplit, *_path, vgan_ecod_*, vgan_iforest_*, vgan_hist_*, vgan_hbos_*, vgan_loda_*, vgan_inne_*, vgan_sos_*, vgan_dif_*, vgan_sod_*, vgan_kpca_*, vgan_ae_*, vgan_svdd_*, vgan_hics_*, vgan_iforest_*_blocks, vgan_outlier_*_metric, vgan_outlier_pack_unit, vgan_loci_*, vgan_rshash_* and vgan_iforest_*_oblique entry points only ADD symbols, so it stands */
 
 typedef void* vgan_stream_t; /* hipStream_t */
 
@@ -1001,6 +1001,36 @@ int vgan_iforest_path_sums(const float* Xq, int ldq, int rows, int d, const int3
                            int psi, int L, const int64_t* cq, int64_t* sums, int64_t ld_sums, vgan_stream_t stream);
 int vgan_iforest_scores(const int64_t* sums, int64_t ld_sums, int count, int rows, int64_t denom, float* score,
                         int64_t ld_score, vgan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Oblique cuts for the isolation forest (the extended isolation forest of Hariri, Carrasco Kind and Brunner, TKDE 2019;
+ * SCiForest, Liu, Ting, Zhou 2010): every internal node cuts with a random sparse hyperplane over at most q of the
+ * subspace's features, 2 <= q <= VGAN_IFOREST_MAX_PLANE  (SubspaceIForest(n_dims = q), whose docstring is the definition:
+ * candidates, attempts, positions, weights, projection, threshold; kernels in csrc/outlier_iforest.hip).  Trees, samples,
+ * stream ids, heap numbering, L, N, cq and vgan_iforest_scores are those of the section above.  Both entries take DENSE
+ * row-major matrices: row i starts i d floats after the base, there is no leading dimension.
+ * nodes is int32 [S, T, N, 2]: word 0 the successful attempt (0 .. 3) of an internal node, -1 a leaf, -2 an absent slot;
+ * word 1 the float32 threshold of an internal node (a row goes left iff float32(projection) <= threshold), the sample rows
+ * of a leaf, 0 where absent.  plane_col int32 [S, T, N, q]: the columns of X of the slot's hyperplane, ascending, -1 in the
+ * unused places and everywhere outside internal nodes; plane_w float32 [S, T, N, q]: their weights, 0 where unused.
+ * vgan_iforest_build_oblique: the T trees of the subspaces first .. first + count - 1 from X [n, d], 2 <= psi <= n <= 2^31 -
+ *   1; cand: the candidate features (columns of X, ascending per subspace) of all subspaces, concatenated, cand_off int32
+ *   [S + 1] their offsets; a subspace without candidates gets root leaves.  The attempts a = 0 .. 3 of a node use the
+ *   Philox4x32-10 blocks at counter (node, 32 a + b, 0x45494600, 0) under the tree's key: b = 0 the threshold word, 1 .. 4
+ *   the positions, 5 + i weight i.  One workgroup per tree; a node reads only its own at most q features.  count <= 65535.
+ * vgan_iforest_path_sums_oblique: vgan_iforest_path_sums on such trees, Xq [rows, d] dense; sums int64 [count, ld_sums],
+ *   ld_sums >= rows.  A plane is read up to its first entry outside [0, d): no column outside Xq is ever read, whatever the
+ *   planes hold.
+ * Both return VGAN_ERR_ARG before touching the device when an argument is out of range (null pointers, n < psi, psi, T, L,
+ * q, count, ld_sums).
+ * ------------------------------------------------------------------------------------------- */
+#define VGAN_IFOREST_MAX_PLANE 16
+int vgan_iforest_build_oblique(const float* X, int64_t n, int d, const int32_t* cand, const int32_t* cand_off, int first,
+                               int count, int T, int psi, int L, int q, uint64_t seed, int32_t* nodes, int32_t* plane_col,
+                               float* plane_w, vgan_stream_t stream);
+int vgan_iforest_path_sums_oblique(const float* Xq, int rows, int d, const int32_t* nodes, const int32_t* plane_col,
+                                   const float* plane_w, int first, int count, int T, int psi, int L, int q, const int64_t* cq,
+                                   int64_t* sums, int64_t ld_sums, vgan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * RS-Hash (Sathe and Aggarwal, ICDM 2016): T components per subspace, each a randomly shifted grid of width f over r of the

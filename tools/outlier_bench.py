@@ -38,7 +38,9 @@ difference of the two paths' ensemble scores.
     training rows as queries); the fit split into its calls (build, path sums, scores); sklearn's IsolationForest(
     n_estimators=100, n_jobs=16) fitted and scored per subspace on the CPUs for a sample of the subspaces, scaled to all of
     them; and the kNN fit (k = 5) of SubspaceEnsemble on the same subspaces.  walk_steps_per_s counts S T n walks of the
-    measured mean depth.
+    measured mean depth.  With --n-dims q >= 2 the forest cuts with hyperplanes over q features: the row holds fit, its build
+    and walk launches, decision_function and the bytes of the fitted state, and from the same process the axis-parallel
+    forest (axis_*) and SubspaceDIF's fit on the same rows; no sklearn or kNN leg.
   --method inne: nearest-neighbour isolation scores (vgan_amd.SubspaceINNE, 200 estimators of 8 centres each) on the shapes of
     the isolation-forest leg: fit and decision_function (the training rows as queries); the fit split into its calls
     (build, scores), with the float64 rate of the scoring pass counted as three operations per (row, centre, feature); the
@@ -827,7 +829,52 @@ def run_loda(d, n, count, reps, baselines=True, numpy_sample=8):
     return row
 
 
-def run_iforest(d, n, count, reps, baselines=True, sklearn_sample=8):
+def run_iforest_oblique(d, n, count, reps, q):
+    """--n-dims q >= 2: fit, its build and walk launches alone, decision_function and the fitted state of the oblique forest;
+    beside it, in the same process, the axis-parallel forest and SubspaceDIF on the same rows."""
+    X, m, p = subspaces_for(d, n, count, seed=d + n + count)
+    Xd = torch.as_tensor(X, device="cuda")
+    S, dims = len(m), m.sum(axis=1)
+    ens = vgan_amd.SubspaceIForest(m, p, n_dims=q)
+    t_fit, tf = timed(lambda: ens.fit(Xd), reps)
+    t_dec, td = timed(lambda: ens.decision_function(Xd), reps)
+    ops, inner = ens.ops, max(reps, 5)
+    T, psi, L = ens.n_estimators, ens.max_samples_, ens.depth_limit_
+    trees, planes = torch.empty_like(ens._trees), tuple(torch.empty_like(t) for t in ens._planes)
+    sums = torch.empty(S * n, dtype=torch.int64, device="cuda")
+    cand = [c for c in ens.candidate_features_]
+    off = np.zeros(S + 1, np.int32)
+    np.cumsum([len(c) for c in cand], out=off[1:])
+    cand_d, off_d = torch.as_tensor(np.concatenate(cand + [np.zeros(1, np.int32)]), device="cuda"), torch.as_tensor(off, device="cuda")
+    t_build, _ = timed(lambda: ops.iforest_build_oblique(Xd, cand_d, off_d, 0, S, psi, L, ens.seed, trees, *planes), inner)
+    t_sums, _ = timed(lambda: ops.iforest_path_sums_oblique(Xd, ens._trees, *ens._planes, 0, S, psi, L, ens._cq, sums), inner)
+    depth = float((sums.view(S, n) >> 32).double().mean()) / T  # the mean number of steps of a walk
+    row = {"method": "iforest", "n_dims": q, "d": d, "n": n, "S_sampled": count, "S_distinct": S, "n_estimators": T, "max_samples": psi,
+           "d_s_min": int(dims.min()), "d_s_median": float(np.median(dims)), "d_s_max": int(dims.max()),
+           "fit_s": round(t_fit, 6), "fit_reps_s": tf, "decision_function_s": round(t_dec, 6), "decision_function_reps_s": td,
+           "build_s": round(t_build, 6), "path_sums_s": round(t_sums, 6),
+           "state_bytes": int(ens._trees.numel() * 4 + sum(t.numel() * 4 for t in ens._planes)), "mean_depth": round(depth, 3),
+           "walk_steps_per_s": round(S * T * n * depth / t_sums / 1e9, 2), "walk_steps_unit": "1e9 steps / s",
+           "build_loads_nominal": float(psi) * float(np.minimum(dims, q).sum()) * T * L,
+           "walk_gathers_nominal": float(S) * T * n * depth * q}
+    flat = vgan_amd.SubspaceIForest(m, p)
+    t_flat, tl = timed(lambda: flat.fit(Xd), reps)
+    flat_trees = torch.empty_like(flat._trees)
+    t_fb, _ = timed(lambda: ops.iforest_build(Xd, flat._table, 0, S, int(dims.max()), psi, L, flat.seed, flat_trees), inner)
+    t_fs, _ = timed(lambda: ops.iforest_path_sums(Xd, flat._trees, 0, S, psi, L, flat._cq, sums), inner)
+    t_fd, _ = timed(lambda: flat.decision_function(Xd), reps)
+    row.update({"axis_fit_s": round(t_flat, 6), "axis_fit_reps_s": tl, "axis_build_s": round(t_fb, 6), "axis_path_sums_s": round(t_fs, 6),
+                "axis_decision_function_s": round(t_fd, 6), "axis_state_bytes": int(flat._trees.numel() * 4),
+                "axis_build_loads_nominal": float(psi) * float(dims.sum()) * T * L})
+    dif = vgan_amd.SubspaceDIF(m, p)
+    t_dif, tdf = timed(lambda: dif.fit(Xd), reps)
+    row.update({"dif_fit_s": round(t_dif, 6), "dif_fit_reps_s": tdf})
+    return row
+
+
+def run_iforest(d, n, count, reps, baselines=True, sklearn_sample=8, n_dims=1):
+    if n_dims > 1:
+        return run_iforest_oblique(d, n, count, reps, n_dims)
     X, m, p = subspaces_for(d, n, count, seed=d + n + count)
     Xd = torch.as_tensor(X, device="cuda")
     S, dims = len(m), m.sum(axis=1)
@@ -2319,6 +2366,8 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--quick", action="store_true", help="small shapes only (a rehearsal)")
     ap.add_argument("--method", choices=["knn", "kde", "cblof", "abod", "cof", "ecod", "iforest", "inne", "mahalanobis", "gmm", "hbos", "loda", "pca", "ocsvm", "sos", "dif", "sod", "kpca", "ae", "deepsvdd", "hics", "metric", "loci", "rshash"], default="knn")
+    ap.add_argument("--n-dims", type=int, default=1, help="iforest: features of an oblique cut (SubspaceIForest's n_dims); from 2 on the "
+                    "row also times the axis-parallel forest and SubspaceDIF on the same rows")
     ap.add_argument("--iters", type=int, default=20, help="cblof: Lloyd iterations of every path")
     ap.add_argument("--no-baselines", action="store_true", help="cblof / abod / cof / ecod / iforest / inne / mahalanobis / gmm / hbos / loda / pca / ocsvm / sos / loci / dif / kpca / ae / deepsvdd / rshash: the fused path only (for a run under a profiler)")
     ap.add_argument("--bandwidth", default="1.0", help="KDE bandwidth: a float, 'scott' or 'silverman'")
@@ -2406,7 +2455,7 @@ def main():
         if args.shape:
             shapes = [tuple(int(v) for v in args.shape.split(","))]
         for d, n, count in shapes:
-            out["configs"].append(run_iforest(d, n, count, args.reps, baselines=not args.no_baselines))
+            out["configs"].append(run_iforest(d, n, count, args.reps, baselines=not args.no_baselines, n_dims=args.n_dims))
             print(json.dumps(out["configs"][-1]), file=sys.stderr, flush=True)
         configs = []
     if args.method == "inne":

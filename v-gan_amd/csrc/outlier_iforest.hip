@@ -211,6 +211,234 @@ __global__ __launch_bounds__(kBlock) void iforest_scores_kernel(const int64_t* _
     if (i < rows) score[z * ld_score + i] = (float)exp2(-((double)sums[z * ld_sums + i] / denom));
 }
 
+// ---- oblique cuts (SubspaceIForest(n_dims = q >= 2); the class docstring is the definition) ------------------------------
+//   nodes    word 0 = the successful attempt (0 .. 3) of an internal node, -1 a leaf, -2 absent; word 1 as above.  The plane
+//            of slot i is plane_col[i q .. i q + q) (columns of X, ascending, -1 in the unused places) and plane_w (0 there).
+//   build    the skeleton above without its all-features scan: a node's wave draws an attempt's 21 Philox blocks one a lane,
+//            chooses the m_s positions (lane k keeps the k-th smallest and its weight), projects the node's rows with lanes
+//            over rows (m_s gathers a row, the same columns for all lanes) into LDS, reduces min and max and partitions from
+//            the kept projections.  Loads: about psi m_s L per tree.
+//   sums     the staging above for the 8-byte nodes; the planes (8 q bytes a slot, at most L of the N slots touched a row)
+//            are read from global memory through L2.
+constexpr int kIfMaxPlane = VGAN_IFOREST_MAX_PLANE;        // q
+constexpr int kIfAttempts = 4;
+constexpr unsigned kIfObliqueTag = 0x45494600u;            // "EIF\0": counter word 2 of every oblique draw
+
+__device__ __forceinline__ float if_readlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+__global__ __launch_bounds__(kBlock) void iforest_build_oblique_kernel(const float* __restrict__ X, unsigned long long n, int d,
+                                                                       const int32_t* __restrict__ cand, const int32_t* __restrict__ cand_off,
+                                                                       int first, int T, int psi, int L, int q, int w, unsigned long long seed,
+                                                                       int2* __restrict__ nodes, int32_t* __restrict__ plane_col,
+                                                                       float* __restrict__ plane_w) {
+    __shared__ int rows[2][kIfMaxSamples];
+    __shared__ int2 tree[kIfMaxSlots];
+    __shared__ unsigned short seg_start[kIfMaxSlots], seg_count[kIfMaxSlots];
+    __shared__ float proj[kIfMaxSamples];  // the projections of a level's rows, by their place in rows[]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = first + (int)(blockIdx.x / (unsigned)T), t = (int)(blockIdx.x % (unsigned)T);
+    const unsigned long long id = (unsigned long long)s * (unsigned long long)T + (unsigned long long)t;
+    const int N = 2 << L;
+    const int off = cand_off[s], c = max(cand_off[s + 1] - off, 0), ms = min(q, c);
+    const unsigned k0 = (unsigned)seed ^ (unsigned)id, k1 = (unsigned)(seed >> 32) ^ (unsigned)(id >> 32) ^ 0x5bd1e995u;
+    const long slot0 = (long)id * N;
+
+    for (int i = tid; i < psi; i += kBlock) rows[0][i] = (int)feistel_perm((unsigned long long)i, n, w, seed, id);
+    for (int i = tid; i < N; i += kBlock) {
+        tree[i] = make_int2(-2, 0);
+        seg_start[i] = 0;
+        seg_count[i] = (unsigned short)(i == 1 ? psi : kIfAbsent);
+    }
+    __syncthreads();
+
+    for (int e = 0; e <= L; ++e) {
+        const int* src = rows[e & 1];
+        int* dst = rows[(e & 1) ^ 1];
+        for (int node = (1 << e) + wave; node < (2 << e); node += kIfWaves) {
+            const int m = seg_count[node];
+            if (m == kIfAbsent) continue;  // the same for the whole wave
+            const int s0 = seg_start[node];
+            int a = kIfAttempts, pk = 0, colk = -1;  // lane k: the k-th smallest chosen position, its column and weight
+            float wk = 0.f, lo = 0.f, hi = 0.f;
+            unsigned w1 = 0u;
+            if (m > 1 && e < L && ms > 0) {
+                for (a = 0; a < kIfAttempts; ++a) {
+                    // block `lane` of the attempt: 0 the threshold word, 1 .. 4 the positions, 5 + i weight i
+                    unsigned ctr[4] = {(unsigned)node, (unsigned)(32 * a + lane), kIfObliqueTag, 0u};
+                    philox4x32_10(ctr, k0, k1);
+                    const unsigned long long sum4 = (unsigned long long)ctr[0] + ctr[1] + ctr[2] + ctr[3];
+                    const float wl = (float)(((double)sum4 - 8589934590.0) * 0x1p-32);  // exact up to the one rounding
+                    w1 = (unsigned)__builtin_amdgcn_readlane((int)ctr[1], 0);
+                    pk = 0x7FFFFFFF;
+                    wk = 0.f;
+                    for (int i = 0; i < ms; ++i) {
+                        const int i3 = i & 3;
+                        const unsigned sel = i3 == 0 ? ctr[0] : i3 == 1 ? ctr[1] : i3 == 2 ? ctr[2] : ctr[3];
+                        const unsigned word = (unsigned)__builtin_amdgcn_readlane((int)sel, 1 + (i >> 2));
+                        int j = (int)(((unsigned long long)word * (unsigned long long)(c - i)) >> 32);
+                        int r = 0;  // ascending walk: the places before r are <= j
+                        for (; r < i; ++r) {
+                            if (__builtin_amdgcn_readlane(pk, r) > j) break;
+                            ++j;
+                        }
+                        const float wi = if_readlane(wl, 5 + i);
+                        const int up = __shfl_up(pk, 1, 64);
+                        const float upw = __shfl_up(wk, 1, 64);
+                        if (lane > r && lane <= i) {
+                            pk = up;
+                            wk = upw;
+                        }
+                        if (lane == r) {
+                            pk = j;
+                            wk = wi;
+                        }
+                    }
+                    // pk < c by construction; the clamp keeps a column of a malformed table inside the row
+                    colk = lane < ms ? min(max(cand[off + pk], 0), d - 1) : -1;
+                    lo = INFINITY;
+                    hi = -INFINITY;
+                    for (int base = 0; base < m; base += 64) {
+                        const int r = base + lane;
+                        const float* xr = X + (long)(r < m ? src[s0 + r] : src[s0]) * d;
+                        double acc = 0.0;
+                        for (int k = 0; k < ms; ++k) {  // ascending positions; every term rounded once, no fused multiply-add
+                            const float x = if_value(xr[__builtin_amdgcn_readlane(colk, k)]);
+                            acc = __dadd_rn(acc, mul_rounded_free((double)if_readlane(wk, k), (double)x));
+                        }
+                        const float zf = (float)acc;
+                        if (r < m) {
+                            proj[s0 + r] = zf;
+                            lo = fminf(lo, zf);
+                            hi = fmaxf(hi, zf);
+                        }
+                    }
+                    lo = if_wave_min(lo);
+                    hi = wave_max(hi);
+                    if (!(lo == hi)) break;  // the same for the whole wave
+                }
+            }
+            if (a == kIfAttempts) {
+                if (lane == 0) tree[node] = make_int2(-1, m);
+                continue;
+            }
+            // three separately rounded float64 operations (mul_rounded: the sum must not absorb the product)
+            const double u = ((double)w1 + 0.5) * 0x1p-32;  // exact
+            float p = (float)__dadd_rn((double)lo, mul_rounded(u, __dsub_rn((double)hi, (double)lo)));
+            if (p >= hi) p = lo;
+            int nl = 0, nr = 0;
+            for (int base = 0; base < m; base += 64) {
+                const int r = base + lane;
+                const int row = r < m ? src[s0 + r] : 0;
+                const float zf = r < m ? proj[s0 + r] : 0.f;  // written by this lane above
+                const bool left = r < m && zf <= p, right = r < m && !left;
+                const unsigned long long bl = __ballot(left), br = __ballot(right);
+                const unsigned long long below = (1ull << lane) - 1ull;
+                if (left) dst[s0 + nl + __popcll(bl & below)] = row;
+                if (right) dst[s0 + m - 1 - nr - __popcll(br & below)] = row;
+                nl += __popcll(bl);
+                nr += __popcll(br);
+            }
+            if (lane < q) {
+                plane_col[(slot0 + node) * q + lane] = colk;
+                plane_w[(slot0 + node) * q + lane] = lane < ms ? wk : 0.f;
+            }
+            if (lane == 0) {
+                tree[node] = make_int2(a, __float_as_int(p));
+                seg_start[2 * node] = (unsigned short)s0;
+                seg_count[2 * node] = (unsigned short)nl;
+                seg_start[2 * node + 1] = (unsigned short)(s0 + nl);
+                seg_count[2 * node + 1] = (unsigned short)nr;
+            }
+        }
+        __syncthreads();
+    }
+    int2* out = nodes + slot0;
+    for (int i = tid; i < N; i += kBlock) out[i] = tree[i];
+    for (int i = tid; i < N * q; i += kBlock)  // the planes of the slots that are not internal: the others were stored above
+        if (tree[i / q].x < 0) {
+            plane_col[slot0 * q + i] = -1;
+            plane_w[slot0 * q + i] = 0.f;
+        }
+}
+
+template <int R>
+__global__ __launch_bounds__(kBlock) void iforest_sums_oblique_kernel(const float* __restrict__ Xq, int rows, int d,
+                                                                      const int2* __restrict__ nodes, const int32_t* __restrict__ plane_col,
+                                                                      const float* __restrict__ plane_w, int first, int T, int psi, int L,
+                                                                      int q, const int64_t* __restrict__ cq, int64_t* __restrict__ sums,
+                                                                      long ld_sums) {
+    __shared__ __attribute__((aligned(16))) int2 group[kIfGroupSlots];
+    const int tid = threadIdx.x;
+    const int N = 2 << L, per_group = kIfGroupSlots / N;
+    const int z = blockIdx.y;
+    const long tree0 = (long)(first + z) * T;
+    const int2* trees = nodes + tree0 * N;
+    const long r0 = (long)blockIdx.x * (R * kBlock) + tid;
+    const float* xr[R];
+    bool live[R];
+    int64_t total[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        live[r] = r0 + (long)r * kBlock < rows;
+        xr[r] = Xq + (live[r] ? r0 + (long)r * kBlock : 0L) * d;
+        total[r] = 0;
+    }
+    for (int t0 = 0; t0 < T; t0 += per_group) {
+        const int g = min(per_group, T - t0);
+        __syncthreads();  // the previous group has been walked
+        const int4* src = reinterpret_cast<const int4*>(trees + (long)t0 * N);  // N >= 4: a tree is a multiple of 16 bytes
+        int4* dst = reinterpret_cast<int4*>(group);
+        for (int i = tid; i < g * N / 2; i += kBlock) dst[i] = src[i];
+        __syncthreads();
+        for (int k = 0; k < g; ++k) {
+            const int2* tree = group + k * N;
+            const long slot0 = (tree0 + t0 + k) * N;
+            int node[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) node[r] = 1;
+            for (int e = 0; e < L; ++e) {
+                bool inner[R], more[R];
+                float thr[R];
+                double acc[R];
+                long at[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int2 rec = tree[node[r]];
+                    inner[r] = more[r] = live[r] && (unsigned)rec.x < (unsigned)kIfAttempts;  // an internal node
+                    thr[r] = __int_as_float(rec.y);
+                    acc[r] = 0.0;
+                    at[r] = (slot0 + node[r]) * q;
+                }
+                for (int f = 0; f < q; ++f) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                        if (more[r]) {
+                            const int col = plane_col[at[r] + f];
+                            if ((unsigned)col >= (unsigned)d) {  // the plane ends at the first place that is no column of Xq
+                                more[r] = false;
+                            } else {
+                                const float x = if_value(xr[r][col]);
+                                acc[r] = __dadd_rn(acc[r], mul_rounded_free((double)plane_w[at[r] + f], (double)x));
+                            }
+                        }
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (inner[r]) node[r] = 2 * node[r] + ((float)acc[r] <= thr[r] ? 0 : 1);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int size = min(max(tree[node[r]].y, 0), psi);
+                const int depth = 31 - __clz(node[r]);
+                total[r] += ((int64_t)depth << 32) + cq[size];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (live[r]) sums[(long)z * ld_sums + r0 + (long)r * kBlock] = total[r];
+}
+
 }  // namespace vgan
 
 using namespace vgan;
@@ -285,6 +513,38 @@ extern "C" int vgan_iforest_scores(const int64_t* sums, int64_t ld_sums, int cou
     VGAN_CHECK_ARG(sums && score && count > 0 && count <= 65535 && rows > 0 && ld_sums >= rows && ld_score >= rows && denom > 0);
     hipLaunchKernelGGL(iforest_scores_kernel, dim3((unsigned)((rows + kBlock - 1) / kBlock), count), dim3(kBlock), 0, (hipStream_t)stream,
                        sums, (long)ld_sums, rows, (double)denom, score, (long)ld_score);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_iforest_build_oblique(const float* X, int64_t n, int d, const int32_t* cand, const int32_t* cand_off, int first,
+                                          int count, int T, int psi, int L, int q, uint64_t seed, int32_t* nodes, int32_t* plane_col,
+                                          float* plane_w, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(X && cand && cand_off && nodes && plane_col && plane_w && d > 0 && n >= 2 && n <= 0x7FFFFFFFLL);
+    VGAN_CHECK_ARG(first >= 0 && count >= 1 && count <= 65535 && q >= 2 && q <= kIfMaxPlane);
+    VGAN_CHECK_ARG(iforest_shape_ok(T, psi, L) && psi <= n && ((int64_t)first + count) * T <= 0x7FFFFFFFLL);
+    hipLaunchKernelGGL(iforest_build_oblique_kernel, dim3((unsigned)(count * T)), dim3(kBlock), 0, (hipStream_t)stream, X,
+                       (unsigned long long)n, d, cand, cand_off, first, T, psi, L, q, feistel_half_bits((unsigned long long)n),
+                       (unsigned long long)seed, reinterpret_cast<int2*>(nodes), plane_col, plane_w);
+    VGAN_CHECK_LAUNCH();
+    return VGAN_OK;
+}
+
+extern "C" int vgan_iforest_path_sums_oblique(const float* Xq, int rows, int d, const int32_t* nodes, const int32_t* plane_col,
+                                              const float* plane_w, int first, int count, int T, int psi, int L, int q,
+                                              const int64_t* cq, int64_t* sums, int64_t ld_sums, vgan_stream_t stream) {
+    VGAN_CHECK_ARG(Xq && nodes && plane_col && plane_w && cq && sums && rows > 0 && d > 0 && first >= 0 && count >= 1 && count <= 65535);
+    VGAN_CHECK_ARG(iforest_shape_ok(T, psi, L) && q >= 2 && q <= kIfMaxPlane && ld_sums >= rows);
+    // the rule of vgan_iforest_path_sums: four rows a thread once that still leaves two workgroups for every CU
+    const long blocks4 = ((long)rows + 4 * kBlock - 1) / (4 * kBlock), blocks1 = ((long)rows + kBlock - 1) / kBlock;
+    const hipStream_t st = (hipStream_t)stream;
+    const int2* tn = reinterpret_cast<const int2*>(nodes);
+    if (blocks4 * count >= 512)
+        hipLaunchKernelGGL(iforest_sums_oblique_kernel<4>, dim3((unsigned)blocks4, count), dim3(kBlock), 0, st, Xq, rows, d, tn, plane_col,
+                           plane_w, first, T, psi, L, q, cq, sums, (long)ld_sums);
+    else
+        hipLaunchKernelGGL(iforest_sums_oblique_kernel<1>, dim3((unsigned)blocks1, count), dim3(kBlock), 0, st, Xq, rows, d, tn, plane_col,
+                           plane_w, first, T, psi, L, q, cq, sums, (long)ld_sums);
     VGAN_CHECK_LAUNCH();
     return VGAN_OK;
 }

@@ -330,7 +330,8 @@ class HiCS:
 
     def outlier_ensemble(self, method="knn", n_neighbors=5, X=None, **kw):
         """A detector of ``vgan_amd.outlier`` on the found subspaces, weighted by ``proba``: the `method` strings and keywords
-        are those of the models' ``outlier_ensemble``; fitted on X when X is given."""
+        are those of the models' ``outlier_ensemble`` (e.g. method="iforest", n_dims=3 for oblique isolation-forest cuts);
+        fitted on X when X is given."""
         if self.subspaces is None:
             raise RuntimeError("HiCS is not fitted: call fit(X) first")
         ens = build_ensemble(self.subspaces, self.proba, method=method, n_neighbors=n_neighbors, **kw)

@@ -175,6 +175,8 @@ SIGNATURES = {
     "vgan_iforest_build": (_i, [_p, _i, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p]),
     "vgan_iforest_path_sums": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, _p]),
     "vgan_iforest_scores": (_i, [_p, _i64, _i, _i, _i64, _p, _i64, _p]),
+    "vgan_iforest_build_oblique": (_i, [_p, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _p, _p, _p, _p]),
+    "vgan_iforest_path_sums_oblique": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i64, _p]),
     "vgan_rshash_build": (_i, [_p, _i, _i64, _i, _i, _i, _i, _i, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "vgan_rshash_cell_sums": (_i, [_p, _i64, _i64, _i, _i, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "vgan_rshash_scores": (_i, [_p, _i64, _i, _i, _i64, _p, _i64, _p]),

@@ -1084,6 +1084,32 @@ class HipOps:
         _lib.check(self.lib.vgan_iforest_scores(_ptr(sums), int(rows), int(count), int(rows), int(denom), _ptr(score), score.stride(0),
                                                 self._stream()), "vgan_iforest_scores")
 
+    def iforest_build_oblique(self, X, cand, cand_off, first, count, psi, depth, seed, nodes, plane_col, plane_w):
+        """nodes int32 [S, T, N, 2], plane_col int32 and plane_w float32 [S, T, N, q] receive the T oblique trees of the
+        subspaces first .. first + count - 1, built from the dense X [n, d]; cand int32: the candidate columns of every
+        subspace, concatenated, cand_off int32 [S + 1] their offsets."""
+        _vec(X, "X"), _vec(nodes, "nodes", torch.int32), _vec(plane_col, "plane_col", torch.int32), _vec(plane_w, "plane_w")
+        _vec(cand, "cand", torch.int32), _vec(cand_off, "cand_off", torch.int32)
+        n, d = X.shape
+        S, T, N, q = plane_col.shape
+        assert tuple(nodes.shape) == (S, T, N, 2) and plane_w.shape == plane_col.shape and N == 2 << depth and first + count <= S
+        assert cand_off.numel() == S + 1
+        _lib.check(self.lib.vgan_iforest_build_oblique(_ptr(X), n, d, _ptr(cand), _ptr(cand_off), int(first), int(count), T, int(psi),
+                                                       int(depth), q, int(seed), _ptr(nodes), _ptr(plane_col), _ptr(plane_w),
+                                                       self._stream()), "vgan_iforest_build_oblique")
+
+    def iforest_path_sums_oblique(self, Xq, nodes, plane_col, plane_w, first, count, psi, depth, cq, sums):
+        """sums int64 [count, rows]: iforest_path_sums through oblique trees; Xq [rows, d] dense."""
+        _vec(Xq, "Xq"), _vec(nodes, "nodes", torch.int32), _vec(plane_col, "plane_col", torch.int32), _vec(plane_w, "plane_w")
+        _vec(cq, "cq", torch.int64), _vec(sums, "sums", torch.int64)
+        rows, d = Xq.shape
+        S, T, N, q = plane_col.shape
+        assert tuple(nodes.shape) == (S, T, N, 2) and plane_w.shape == plane_col.shape and N == 2 << depth and first + count <= S
+        assert cq.numel() >= psi + 1 and sums.numel() >= count * rows
+        _lib.check(self.lib.vgan_iforest_path_sums_oblique(_ptr(Xq), rows, d, _ptr(nodes), _ptr(plane_col), _ptr(plane_w), int(first),
+                                                           int(count), T, int(psi), int(depth), q, _ptr(cq), _ptr(sums), rows,
+                                                           self._stream()), "vgan_iforest_path_sums_oblique")
+
     def iforest_build_blocks(self, R, first, psi, depth, seed, nodes):
         """nodes int32 [blocks, T, N, 2] receives the T trees of the blocks first .. first + count - 1, block first + z grown
         on its own matrix R[z] of R float32 [count, n, q] (every column a candidate); stream id = block T + tree."""

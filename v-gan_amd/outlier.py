@@ -1630,6 +1630,7 @@ IFOREST_MAX_TREES = 1024  # VGAN_IFOREST_MAX_TREES
 IFOREST_MAX_SAMPLES = 1024  # VGAN_IFOREST_MAX_SAMPLES: the sampled rows of a tree live in LDS
 IFOREST_MAX_DIMS = 8192  # VGAN_IFOREST_MAX_DIMS: features of one subspace (a bit per feature and wave in LDS)
 IFOREST_MAX_ROWS = (1 << 31) - 1
+IFOREST_MAX_PLANE = 16  # VGAN_IFOREST_MAX_PLANE: the features of one oblique cut (n_dims)
 IFOREST_AUTO_SAMPLES = 256  # max_samples="auto", sklearn's and pyod's default
 _IFOREST_MAX_RANGE = 65535  # subspaces of one launch (a grid dimension)
 EULER_GAMMA = 0.5772156649015329
@@ -1648,6 +1649,12 @@ def check_max_samples(max_samples):
     if not (_is_int(max_samples) and 2 <= int(max_samples) <= IFOREST_MAX_SAMPLES):
         raise ValueError(f"max_samples must be 'auto' or an integer between 2 and {IFOREST_MAX_SAMPLES}, got {max_samples!r}")
     return int(max_samples)
+
+
+def check_n_dims(n_dims):
+    if not (_is_int(n_dims) and 1 <= int(n_dims) <= IFOREST_MAX_PLANE):
+        raise ValueError(f"n_dims must be an integer between 1 and {IFOREST_MAX_PLANE}, got {n_dims!r}")
+    return int(n_dims)
 
 
 def check_seed(seed):
@@ -1726,16 +1733,54 @@ class SubspaceIForest(_SubspaceScorer):
     of its leaves'); and ``max_samples_``, ``depth_limit_``.  normalize, combination, contamination, ``threshold_``,
     ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.  The definition above and its
     numpy restatement in tests/test_outlier_iforest_cpu.py (pinned there to sklearn's path lengths and scores) are what
-    binds.  All of it runs in libvgan_hip.so (csrc/outlier_iforest.hip)."""
+    binds.  All of it runs in libvgan_hip.so (csrc/outlier_iforest.hip).
+
+    **Oblique cuts, n_dims = q >= 2** (the extended isolation forest of Hariri, Carrasco Kind and Brunner, TKDE 2019, with
+    the sparse hyperplanes of SCiForest, Liu, Ting, Zhou 2010).  Axis-parallel cuts leave "ghost" low-score regions where
+    marginal modes cross: a row there stays inside every marginal range and is isolated late.  With ``n_dims`` = q, an
+    integer 2 .. IFOREST_MAX_PLANE (16), every internal node cuts with a random hyperplane over at most q features of the
+    subspace; n_dims = 1 (the default) is everything above, the same launches and the same bits.  For q >= 2:
+
+    *Candidates.*  The candidates of subspace s are the features of F_s whose column maximum exceeds the column minimum over
+    the fitted rows (float32, -0.0 as +0.0), ascending: ``candidate_features_`` (a list of int32 arrays).  c_s is their
+    number, m_s = min(q, c_s).
+    *Trees.*  Tree (s, t), its stream id s T + t, its sample, heap numbering, L, the key, cq and the score are those above.
+    *Leaves.*  A node at depth e with row set R is a leaf if |R| <= 1, or e == L, or c_s == 0, or all four attempts fail.
+    *Attempts.*  Attempt a = 0, 1, 2, 3 of a node uses the Philox4x32-10 blocks at counter (node, 32 a + b, 0x45494600, 0)
+    under the tree's key.
+    *Positions.*  For i = 0 .. m_s - 1 the word is word i & 3 of block b = 1 + (i >> 2); j = (word (c_s - i)) >> 32 in
+    integers; walking the positions already chosen in ascending order, j grows by one for each that is <= j.  The result is
+    position i (an index into the candidates): uniform over the m_s-subsets, distinct by construction.
+    *Weights.*  For i = 0 .. m_s - 1, t the integer sum of the four words of block b = 5 + i, w_i = float32((double(t) -
+    8589934590.0) 2^-32): exact up to the one rounding, Irwin-Hall of four (mean 0, variance 1/3).  Weight i belongs to
+    position i.
+    *Projection.*  acc = 0.0 in float64; for the chosen positions in ascending order acc = acc + double(w) double(x), the
+    product exact, the sum rounded once per term, no fused multiply-add, x with -0.0 as +0.0; zf = float32(acc).
+    *Threshold.*  lo and hi are the min and max of zf over R; lo == hi fails the attempt.  Otherwise u = (w1 of block 0 of
+    the attempt + 0.5) 2^-32, p = float32(lo + u (hi - lo)) in three separately rounded float64 operations, p >= hi replaced
+    by lo; a row goes left iff zf <= p in float32, and both children are non-empty.
+    *Score.*  A leaf contributes (e << 32) + cq[size] as above; a subspace with c_s = 0 has root leaves and scores exactly
+    0.5; ``decision_function(X_train)`` equals ``decision_scores_`` bit for bit; every loop is bounded by L, psi, 4 and 16.
+
+    Published for q >= 2, copied to the host on first use: ``plane_features_`` int32 [S, T, N, q] (columns of X, ascending,
+    -1 in the unused places and everywhere outside internal nodes), ``plane_weights_`` float32 [S, T, N, q] (0 where
+    unused), ``tree_attempt_`` int32 [S, T, N] (the successful attempt, -1 a leaf, -2 absent), ``tree_threshold_``,
+    ``tree_size_``, and ``tree_feature_`` = plane_features_[..., 0] for an internal node (-1 a leaf, -2 absent).  The fitted
+    state is 8 + 8 q bytes a slot.  The restatement is tests/test_outlier_iforest_oblique_cpu.py.
+
+    Not built: ``n_dims="full"`` (a hyperplane over all features of a wide subspace would make the fitted state tens of
+    megabytes a subspace, or need the weights regenerated at every step of the walk); Hariri's intercept drawn in the
+    bounding box (it can leave a child empty); SCiForest's split-selection criterion."""
 
     _host_trees = None
 
-    def __init__(self, subspaces, proba, n_estimators=100, max_samples="auto", seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
+    def __init__(self, subspaces, proba, n_estimators=100, max_samples="auto", seed=0, n_dims=1, workspace_bytes=DEFAULT_WORKSPACE_BYTES,
                  normalize=None, combination="sum", contamination=0.1):
         self.n_estimators = check_estimators(n_estimators)
         self.max_samples = max_samples
         self._max_samples = check_max_samples(max_samples)
         self.seed = check_seed(seed)
+        self.n_dims = check_n_dims(n_dims)
         # no distance engine here: "exact" for every subspace keeps the processing order the given order
         self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
         del self.engine
@@ -1767,7 +1812,11 @@ class SubspaceIForest(_SubspaceScorer):
         for first, count in ranges:
             for r0 in range(0, nq, rows):
                 r1 = min(r0 + rows, nq)
-                self.ops.iforest_path_sums(X[r0:r1], self._trees, first, count, self.max_samples_, self.depth_limit_, self._cq, sums)
+                if self.n_dims == 1:
+                    self.ops.iforest_path_sums(X[r0:r1], self._trees, first, count, self.max_samples_, self.depth_limit_, self._cq, sums)
+                else:
+                    self.ops.iforest_path_sums_oblique(X[r0:r1], self._trees, *self._planes, first, count, self.max_samples_,
+                                                       self.depth_limit_, self._cq, sums)
                 if per is None:
                     out[first:first + count, r0:r1] = sums[:count * (r1 - r0)].view(count, r1 - r0)
                 else:
@@ -1785,14 +1834,47 @@ class SubspaceIForest(_SubspaceScorer):
             nodes = self._trees.cpu().numpy()
             feature = np.ascontiguousarray(nodes[..., 0])
             word = np.ascontiguousarray(nodes[..., 1])
+            planes = ()
+            if getattr(self, "_planes", None) is not None:  # oblique: word 0 is the attempt, the feature the plane's first column
+                planes = (feature, self._planes[0].cpu().numpy(), self._planes[1].cpu().numpy())
+                feature = np.where(feature >= 0, planes[1][..., 0], feature).astype(np.int32)
             threshold = np.where(feature >= 0, word.view(np.float32), np.float32(0.0))
             size = np.where(feature == -1, word, 0).astype(np.int32)
             for e in range(self.depth_limit_ - 1, -1, -1):  # an internal node holds what its children hold
                 at = np.arange(1 << e, 2 << e)
                 inner = feature[..., at] >= 0
                 size[..., at] = np.where(inner, size[..., 2 * at] + size[..., 2 * at + 1], size[..., at])
-            self._host_trees = (feature, threshold, size)
+            self._host_trees = (feature, threshold, size) + planes
         return self._host_trees
+
+    def _planes_on_host(self):
+        self._require_fit()
+        if self.n_dims == 1:
+            raise AttributeError("tree_attempt_, plane_features_ and plane_weights_ belong to oblique cuts (n_dims >= 2)")
+        return self._trees_on_host()[3:]
+
+    @property
+    def tree_attempt_(self):
+        """int32 [S, T, N], n_dims >= 2: the successful attempt (0 .. 3) of an internal node, -1 a leaf, -2 an absent slot."""
+        return self._planes_on_host()[0]
+
+    @property
+    def plane_features_(self):
+        """int32 [S, T, N, n_dims], n_dims >= 2: the columns of X of every internal node's hyperplane, ascending; -1 elsewhere."""
+        return self._planes_on_host()[1]
+
+    @property
+    def plane_weights_(self):
+        """float32 [S, T, N, n_dims], n_dims >= 2: the weights of plane_features_, 0 where unused."""
+        return self._planes_on_host()[2]
+
+    @property
+    def candidate_features_(self):
+        """list of int32 arrays, n_dims >= 2: the features of every subspace that vary over the fitted rows, ascending."""
+        self._require_fit()
+        if self.n_dims == 1:
+            raise AttributeError("candidate_features_ belongs to oblique cuts (n_dims >= 2)")
+        return self._candidates
 
     @property
     def tree_feature_(self):
@@ -1812,7 +1894,9 @@ class SubspaceIForest(_SubspaceScorer):
     def fit(self, X, y=None):
         """Builds the T trees of every subspace on their samples of X, then scores X itself through them: decision_scores_
         (float64 [n]), per_subspace_scores_, max_samples_, depth_limit_ and, on first use, tree_feature_ / tree_threshold_ /
-        tree_size_; with normalize also score_center_ / score_scale_.  The trees are the fitted state: X itself is not kept."""
+        tree_size_; with normalize also score_center_ / score_scale_.  With n_dims >= 2 the candidates come first
+        (candidate_features_), the trees are oblique, and tree_attempt_ / plane_features_ / plane_weights_ are published
+        too.  The trees (and planes) are the fitted state: X itself is not kept."""
         X = self._begin_fit(X)
         n = X.shape[0]
         psi = min(self._max_samples, n)
@@ -1821,11 +1905,37 @@ class SubspaceIForest(_SubspaceScorer):
         self._cq = torch.as_tensor(cq, device=X.device)
         self._denom = self.n_estimators * int(cq[psi])
         self._trees = torch.empty(self.plan.count, self.n_estimators, 2 << self.depth_limit_, 2, dtype=torch.int32, device=X.device)
-        for first, count in self._ranges()[0]:
-            self.ops.iforest_build(X, self._table, first, count, int(self.plan.dims[first:first + count].max()), psi, self.depth_limit_,
-                                   self.seed, self._trees)
+        self._planes = None
+        if self.n_dims > 1:
+            self._fitted = False
+            self._build_oblique(X, psi)
+        else:
+            for first, count in self._ranges()[0]:
+                self.ops.iforest_build(X, self._table, first, count, int(self.plan.dims[first:first + count].max()), psi,
+                                       self.depth_limit_, self.seed, self._trees)
         scores, per = self._score(X, fitting=True)
         return self._publish(scores, per)
+
+
+    def _build_oblique(self, X, psi):
+        """The candidates of every subspace from the column ranges of X (SubspaceRSHash.fit's rule), then the oblique trees
+        and their planes, range by range."""
+        d, dev, S = X.shape[1], X.device, self.plan.count
+        keys = torch.empty(d, 2, dtype=torch.int64, device=dev)
+        self.ops.hist_column_range(X, keys)  # keys of the float64 images of the float32 min and max, -0.0 as +0.0
+        k = keys.cpu().numpy().view(np.uint64)
+        lo_hi = np.ascontiguousarray(np.where(k >> np.uint64(63), k & np.uint64(0x7FFFFFFFFFFFFFFF), ~k)).view(np.float64)
+        varying = lo_hi[:, 1] > lo_hi[:, 0]
+        feats = [self.plan.feat[self.plan.feat_off[z]:self.plan.feat_off[z + 1]] for z in range(S)]
+        self._candidates = [f[varying[f]].astype(np.int32) for f in feats]
+        off = np.zeros(S + 1, np.int32)
+        np.cumsum([len(c) for c in self._candidates], out=off[1:])
+        cand = np.concatenate(self._candidates + [np.zeros(1, np.int32)])  # never empty: the entry rejects a null pointer
+        shape = tuple(self._trees.shape[:3]) + (self.n_dims,)
+        self._planes = (torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev))
+        cand, off = torch.as_tensor(cand, device=dev), torch.as_tensor(off, device=dev)
+        for first, count in self._ranges()[0]:
+            self.ops.iforest_build_oblique(X, cand, off, first, count, psi, self.depth_limit_, self.seed, self._trees, *self._planes)
 
 
 # ---- RS-Hash: counts of randomly shifted grid cells over the subspaces --------------------------------------------------

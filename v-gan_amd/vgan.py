@@ -188,9 +188,10 @@ class _RunFolder:
         ECOD): its keywords are aggregate, workspace_bytes and the same normalize / combination / contamination, e.g.
         outlier_ensemble(method="ecod", X=X); n_neighbors is not used there.
         method "iforest" builds a SubspaceIForest (isolation forest: random trees on sampled rows, no sweep over pairs of
-        rows; sklearn's IsolationForest, pyod's IForest): its keywords are n_estimators, max_samples, seed, workspace_bytes
-        and the same normalize / combination / contamination, e.g. outlier_ensemble(method="iforest", n_estimators=100,
-        X=X); n_neighbors is not used there.
+        rows; sklearn's IsolationForest, pyod's IForest): its keywords are n_estimators, max_samples, seed, n_dims,
+        workspace_bytes and the same normalize / combination / contamination, e.g. outlier_ensemble(method="iforest",
+        n_estimators=100, X=X); n_dims = 2 .. 16 cuts with random sparse hyperplanes over that many features a node (the
+        extended isolation forest), e.g. outlier_ensemble(method="iforest", n_dims=3, X=X); n_neighbors is not used there.
         method "mahalanobis" builds a SubspaceMahalanobis (squared Mahalanobis distance under a shrunk covariance per
         subspace; sklearn's ShrunkCovariance / OAS .mahalanobis) and method "mcd" the same with robust=True (a
         deterministic single-start concentration MCD; pyod's MCD up to the estimator): its keywords are shrinkage,
