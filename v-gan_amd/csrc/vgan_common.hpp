@@ -15,22 +15,27 @@ constexpr int kBlock = 256;  // 4 waves, one per SIMD; two such workgroups per C
 
 void set_error(const char* fmt, ...);
 
-#define VGAN_CHECK_ARG(cond)                                                        \
-    do {                                                                            \
-        if (!(cond)) {                                                              \
-            ::vgan::set_error("%s:%d: bad argument: %s", __FILE__, __LINE__, #cond); \
-            return VGAN_ERR_ARG;                                                    \
-        }                                                                           \
+// The _AT forms report a given file and line: a routine shared by several entries names the entry that called it.  The
+// condition is turned into text where it is written, before its macros expand.
+#define VGAN_CHECK_ARG_TEXT(file, line, cond, text)                                \
+    do {                                                                           \
+        if (!(cond)) {                                                             \
+            ::vgan::set_error("%s:%d: bad argument: %s", (file), (line), text);    \
+            return VGAN_ERR_ARG;                                                   \
+        }                                                                          \
     } while (0)
+#define VGAN_CHECK_ARG(cond) VGAN_CHECK_ARG_TEXT(__FILE__, __LINE__, cond, #cond)
+#define VGAN_CHECK_ARG_AT(file, line, cond) VGAN_CHECK_ARG_TEXT(file, line, cond, #cond)
 
-#define VGAN_CHECK_LAUNCH()                                                                     \
-    do {                                                                                        \
-        hipError_t e_ = hipGetLastError();                                                      \
-        if (e_ != hipSuccess) {                                                                 \
-            ::vgan::set_error("%s:%d: launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_)); \
-            return VGAN_ERR_HIP;                                                                \
-        }                                                                                       \
+#define VGAN_CHECK_LAUNCH_AT(file, line)                                                              \
+    do {                                                                                              \
+        hipError_t e_ = hipGetLastError();                                                            \
+        if (e_ != hipSuccess) {                                                                       \
+            ::vgan::set_error("%s:%d: launch failed: %s", (file), (line), hipGetErrorString(e_));     \
+            return VGAN_ERR_HIP;                                                                      \
+        }                                                                                             \
     } while (0)
+#define VGAN_CHECK_LAUNCH() VGAN_CHECK_LAUNCH_AT(__FILE__, __LINE__)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

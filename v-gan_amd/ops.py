@@ -1213,25 +1213,24 @@ class HipOps:
                                                int(first), int(count), len(hidden), harr, int(q), int(act), _ptr(W), _ptr(w_off),
                                                _ptr(R), self._stream()), "vgan_dif_represent")
 
-    # ---- autoencoders over subspaces (vgan_amd.outlier.SubspaceAutoEncoder) ----------------------------------
+    # ---- trained MLPs over subspaces (vgan_amd.outlier.SubspaceAutoEncoder / SubspaceDeepSVDD) ------------------------
     # net: (hidden tuple, activation code); state float32 with the block first + z at s_off[z] (int64 [count] on the device):
-    # theta, m, v of P floats each, a layer K-major [K_l][N_l] followed by its bias; scaling: (mean, scale) float64 [d]
-    def ae_init(self, feat_off, net, first, count, scale, seed, state, s_off, total):
-        """state float32 [>= total]: zeroed (the moments), then the Philox weights and biases of the blocks first .. first +
-        count - 1; scale float64 [S, 2 L]: c_l = 1 / sqrt(K_l) per subspace."""
+    # theta, m, v of P floats each, a layer K-major [K_l][N_l], with the autoencoder followed by its bias; scaling: (mean, scale)
+    # float64 [d].  The two detectors' entries differ by the centre (float32 [count, q], q = hidden[-1]) that Deep SVDD's take
+    # behind the Adam arguments (train) or the state (scores): center = () for an entry without one, else (tensor or None,).
+    def _mlp_init(self, entry, layers, feat_off, net, first, count, scale, seed, state, s_off, total):
+        """ae_init / svdd_init through the library's `entry`; `layers`: the layers of a net, so scale is float64 [S, layers]."""
         _vec(feat_off, "feat_off", torch.int32), _vec(scale, "scale", torch.float64), _vec(state, "state"), _vec(s_off, "s_off", torch.int64)
         hidden, _ = net
         assert state.numel() >= total and s_off.numel() >= count and first + count <= feat_off.numel() - 1
-        assert scale.numel() >= (feat_off.numel() - 1) * 2 * len(hidden)
+        assert scale.numel() >= (feat_off.numel() - 1) * layers
         harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
-        _lib.check(self.lib.vgan_ae_init(_ptr(feat_off), int(first), int(count), len(hidden), harr, _ptr(scale), int(seed), _ptr(state),
-                                         _ptr(s_off), int(total), self._stream()), "vgan_ae_init")
+        _lib.check(getattr(self.lib, entry)(_ptr(feat_off), int(first), int(count), len(hidden), harr, _ptr(scale), int(seed), _ptr(state),
+                                            _ptr(s_off), int(total), self._stream()), entry)
 
-    def ae_train(self, X, table, scaling, skip, net, first, count, max_dims, batch, seed, step_first, corr, adam, state, s_off, loss,
-                 scratch=None):
-        """Runs the global steps step_first .. step_first + len(corr) - 1 (0-based) of the blocks first .. first + count - 1 in
-        place, one workgroup per block; corr float64 [steps, 2]: 1 - beta1^t and 1 - beta2^t of every step; adam: (lr, beta1,
-        beta2, eps, weight_decay); loss float32 [count, >= step_first + steps]: column g receives the batch loss of step g."""
+    def _mlp_train(self, entry, X, table, scaling, skip, net, first, count, max_dims, batch, seed, step_first, corr, adam, state, s_off, loss,
+                   scratch, center=()):
+        """ae_train / svdd_train through the library's `entry`; the centre goes behind the Adam arguments."""
         _mat(X, "X"), _vec(skip, "skip", torch.int32), _vec(corr, "corr", torch.float64), _vec(state, "state")
         _vec(s_off, "s_off", torch.int64), _mat(loss, "loss")
         feat, feat_off, _ = table
@@ -1242,20 +1241,24 @@ class HipOps:
         steps = corr.shape[0]
         assert corr.dim() == 2 and corr.shape[1] == 2 and mean.numel() == d and scale.numel() == d
         assert first + count <= feat_off.numel() - 1 <= skip.numel() and s_off.numel() >= count and loss.shape[0] >= count
+        for c in center:
+            _vec(c, "center")
+            assert c.numel() >= count * hidden[-1]
         if scratch is not None:
             _vec(scratch, "scratch")
         harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
         lr, beta1, beta2, eps, weight_decay = adam
-        _lib.check(self.lib.vgan_ae_train(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
-                                          int(first), int(count), int(max_dims), len(hidden), harr, int(act), int(batch), int(seed),
-                                          int(step_first), int(steps), _ptr(corr), float(lr), float(beta1), float(beta2), float(eps),
-                                          float(weight_decay), _ptr(state), _ptr(s_off), _ptr(loss), loss.stride(0) if count > 1 else loss.shape[1],
-                                          _ptr(scratch), scratch.numel() if scratch is not None else 0, self._stream()), "vgan_ae_train")
+        _lib.check(getattr(self.lib, entry)(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
+                                            int(first), int(count), int(max_dims), len(hidden), harr, int(act), int(batch), int(seed),
+                                            int(step_first), int(steps), _ptr(corr), float(lr), float(beta1), float(beta2), float(eps),
+                                            float(weight_decay), *map(_ptr, center), _ptr(state), _ptr(s_off), _ptr(loss),
+                                            loss.stride(0) if count > 1 else loss.shape[1], _ptr(scratch),
+                                            scratch.numel() if scratch is not None else 0, self._stream()), entry)
 
-    def ae_scores(self, X, table, scaling, skip, net, first, count, max_dims, state, s_off, score=None, recon=None, scratch=None):
-        """score float32 [count, >= rows] (a view into the score matrix may be given): the reconstruction distances of the rows
-        of X under the nets of the blocks first .. first + count - 1; with recon (float32 [rows, d_s], count 1) the raw output
-        of the net instead."""
+    def _mlp_scores(self, entry, X, table, scaling, skip, net, first, count, max_dims, state, s_off, score, raw, scratch, center=()):
+        """ae_scores / svdd_scores through the library's `entry`; the centre goes behind s_off.  raw: None, or (name, buffer,
+        width) for the raw output of one net instead of scores: float32 [rows, width]; width None where only the device knows
+        it (d_s of the block), so the size is not checked here."""
         _mat(X, "X"), _vec(skip, "skip", torch.int32), _vec(state, "state"), _vec(s_off, "s_off", torch.int64)
         feat, feat_off, _ = table
         mean, scale = scaling
@@ -1264,34 +1267,49 @@ class HipOps:
         hidden, act = net
         assert mean.numel() == d and scale.numel() == d and first + count <= feat_off.numel() - 1 <= skip.numel() and s_off.numel() >= count
         ld_score = 0
-        if recon is not None:
-            _vec(recon, "recon")
-            assert count == 1
+        if raw is not None:
+            raw_name, raw, raw_width = raw
+            _vec(raw, raw_name)
+            assert count == 1 and (raw_width is None or raw.numel() >= rows * raw_width)
         else:
             _mat(score, "score")
             assert score.shape[0] >= count and score.shape[1] >= rows
+            for c in center:
+                _vec(c, "center")
+                assert c.numel() >= count * hidden[-1]
             ld_score = score.stride(0) if score.shape[0] > 1 else score.shape[1]
         if scratch is not None:
             _vec(scratch, "scratch")
         harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
-        _lib.check(self.lib.vgan_ae_scores(_ptr(X), X.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
-                                           int(first), int(count), int(max_dims), len(hidden), harr, int(act), _ptr(state), _ptr(s_off),
-                                           _ptr(score), int(ld_score), _ptr(recon), _ptr(scratch),
-                                           scratch.numel() if scratch is not None else 0, self._stream()), "vgan_ae_scores")
+        _lib.check(getattr(self.lib, entry)(_ptr(X), X.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
+                                            int(first), int(count), int(max_dims), len(hidden), harr, int(act), _ptr(state), _ptr(s_off),
+                                            *map(_ptr, center), _ptr(score), int(ld_score), _ptr(raw), _ptr(scratch),
+                                            scratch.numel() if scratch is not None else 0, self._stream()), entry)
 
-    # ---- Deep SVDD encoders over subspaces (vgan_amd.outlier.SubspaceDeepSVDD) -----------------------------------
-    # net: (hidden tuple, activation code), q = hidden[-1]; state as the autoencoder's without the bias rows (P = sum K_l N_l);
-    # center float32 [count, q] on the device
+    def ae_init(self, feat_off, net, first, count, scale, seed, state, s_off, total):
+        """state float32 [>= total]: zeroed (the moments), then the Philox weights and biases of the blocks first .. first +
+        count - 1; scale float64 [S, 2 L]: c_l = 1 / sqrt(K_l) per subspace."""
+        self._mlp_init("vgan_ae_init", 2 * len(net[0]), feat_off, net, first, count, scale, seed, state, s_off, total)
+
+    def ae_train(self, X, table, scaling, skip, net, first, count, max_dims, batch, seed, step_first, corr, adam, state, s_off, loss,
+                 scratch=None):
+        """Runs the global steps step_first .. step_first + len(corr) - 1 (0-based) of the blocks first .. first + count - 1 in
+        place, one workgroup per block; corr float64 [steps, 2]: 1 - beta1^t and 1 - beta2^t of every step; adam: (lr, beta1,
+        beta2, eps, weight_decay); loss float32 [count, >= step_first + steps]: column g receives the batch loss of step g."""
+        self._mlp_train("vgan_ae_train", X, table, scaling, skip, net, first, count, max_dims, batch, seed, step_first, corr, adam, state, s_off,
+                        loss, scratch)
+
+    def ae_scores(self, X, table, scaling, skip, net, first, count, max_dims, state, s_off, score=None, recon=None, scratch=None):
+        """score float32 [count, >= rows] (a view into the score matrix may be given): the reconstruction distances of the rows
+        of X under the nets of the blocks first .. first + count - 1; with recon (float32 [rows, d_s], count 1) the raw output
+        of the net instead."""
+        self._mlp_scores("vgan_ae_scores", X, table, scaling, skip, net, first, count, max_dims, state, s_off, score,
+                         None if recon is None else ("recon", recon, None), scratch)
+
     def svdd_init(self, feat_off, net, first, count, scale, seed, state, s_off, total):
         """state float32 [>= total]: zeroed (the moments), then the Philox weights of the blocks first .. first + count - 1;
         scale float64 [S, L]: c_l = 1 / sqrt(K_l) per subspace."""
-        _vec(feat_off, "feat_off", torch.int32), _vec(scale, "scale", torch.float64), _vec(state, "state"), _vec(s_off, "s_off", torch.int64)
-        hidden, _ = net
-        assert state.numel() >= total and s_off.numel() >= count and first + count <= feat_off.numel() - 1
-        assert scale.numel() >= (feat_off.numel() - 1) * len(hidden)
-        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
-        _lib.check(self.lib.vgan_svdd_init(_ptr(feat_off), int(first), int(count), len(hidden), harr, _ptr(scale), int(seed), _ptr(state),
-                                           _ptr(s_off), int(total), self._stream()), "vgan_svdd_init")
+        self._mlp_init("vgan_svdd_init", len(net[0]), feat_off, net, first, count, scale, seed, state, s_off, total)
 
     def svdd_center(self, X, table, scaling, skip, net, first, count, max_dims, state, s_off, tile_sums, run_sums, n_total, center_eps,
                     center, n_clamped, scratch=None):
@@ -1322,54 +1340,15 @@ class HipOps:
                    loss, scratch=None):
         """ae_train's arguments and center float32 [count, q]: the global steps step_first .. step_first + len(corr) - 1 of the
         one-class objective, in place; loss float32 [count, >= step_first + steps]."""
-        _mat(X, "X"), _vec(skip, "skip", torch.int32), _vec(corr, "corr", torch.float64), _vec(state, "state")
-        _vec(s_off, "s_off", torch.int64), _mat(loss, "loss"), _vec(center, "center")
-        feat, feat_off, _ = table
-        mean, scale = scaling
-        _vec(mean, "mean", torch.float64), _vec(scale, "scale", torch.float64)
-        n, d = X.shape
-        hidden, act = net
-        steps = corr.shape[0]
-        assert corr.dim() == 2 and corr.shape[1] == 2 and mean.numel() == d and scale.numel() == d
-        assert first + count <= feat_off.numel() - 1 <= skip.numel() and s_off.numel() >= count and loss.shape[0] >= count
-        assert center.numel() >= count * hidden[-1]
-        if scratch is not None:
-            _vec(scratch, "scratch")
-        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
-        lr, beta1, beta2, eps, weight_decay = adam
-        _lib.check(self.lib.vgan_svdd_train(_ptr(X), X.stride(0), n, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
-                                            int(first), int(count), int(max_dims), len(hidden), harr, int(act), int(batch), int(seed),
-                                            int(step_first), int(steps), _ptr(corr), float(lr), float(beta1), float(beta2), float(eps),
-                                            float(weight_decay), _ptr(center), _ptr(state), _ptr(s_off), _ptr(loss),
-                                            loss.stride(0) if count > 1 else loss.shape[1], _ptr(scratch),
-                                            scratch.numel() if scratch is not None else 0, self._stream()), "vgan_svdd_train")
+        self._mlp_train("vgan_svdd_train", X, table, scaling, skip, net, first, count, max_dims, batch, seed, step_first, corr, adam, state,
+                        s_off, loss, scratch, (center,))
 
     def svdd_scores(self, X, table, scaling, skip, net, first, count, max_dims, state, s_off, center=None, score=None, embed=None,
                     scratch=None):
         """score float32 [count, >= rows] (a view into the score matrix may be given): the squared distances of the images of
         the rows of X from center [count, q]; with embed (float32 [rows, q], count 1) the raw output of the net instead."""
-        _mat(X, "X"), _vec(skip, "skip", torch.int32), _vec(state, "state"), _vec(s_off, "s_off", torch.int64)
-        feat, feat_off, _ = table
-        mean, scale = scaling
-        _vec(mean, "mean", torch.float64), _vec(scale, "scale", torch.float64)
-        rows, d = X.shape
-        hidden, act = net
-        assert mean.numel() == d and scale.numel() == d and first + count <= feat_off.numel() - 1 <= skip.numel() and s_off.numel() >= count
-        ld_score = 0
-        if embed is not None:
-            _vec(embed, "embed")
-            assert count == 1 and embed.numel() >= rows * hidden[-1]
-        else:
-            _mat(score, "score"), _vec(center, "center")
-            assert score.shape[0] >= count and score.shape[1] >= rows and center.numel() >= count * hidden[-1]
-            ld_score = score.stride(0) if score.shape[0] > 1 else score.shape[1]
-        if scratch is not None:
-            _vec(scratch, "scratch")
-        harr = (ctypes.c_int32 * max(len(hidden), 1))(*hidden)
-        _lib.check(self.lib.vgan_svdd_scores(_ptr(X), X.stride(0), rows, d, _ptr(feat), _ptr(feat_off), _ptr(mean), _ptr(scale), _ptr(skip),
-                                             int(first), int(count), int(max_dims), len(hidden), harr, int(act), _ptr(state), _ptr(s_off),
-                                             _ptr(center), _ptr(score), int(ld_score), _ptr(embed), _ptr(scratch),
-                                             scratch.numel() if scratch is not None else 0, self._stream()), "vgan_svdd_scores")
+        self._mlp_scores("vgan_svdd_scores", X, table, scaling, skip, net, first, count, max_dims, state, s_off, score,
+                         None if embed is None else ("embed", embed, net[0][-1]), scratch, (center,))
 
     # ---- iNNE over subspaces (vgan_amd.outlier.SubspaceINNE) -----------------------------------------------
     # state: (rows int32, r2 float64, nn int32, rho float64), each [S, T, psi]

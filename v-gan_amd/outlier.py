@@ -4461,24 +4461,39 @@ def ae_layer_sizes(d_s, hidden):
     return list(zip(widths[:-1], widths[1:]))
 
 
+def _mlp_param_count(sizes, bias):
+    """P of a net of the layer sizes [(K_l, N_l)]: sum_l (K_l + bias) N_l, bias 1 or 0."""
+    return sum((K + int(bias)) * N for K, N in sizes)
+
+
+def _mlp_act_floats(sizes, widest, rows, train, output_kept):
+    """The float32 cells of the activations of `rows` rows (pitches are widths | 1) of a net of the layer sizes [(K_l, N_l)]:
+    z, every layer's output (the last one's only when training, as the output error, unless the scoring forward keeps it
+    too: output_kept) and, when training, one passed-down error of the widest given width (csrc/outlier_mlp.hpp)."""
+    per_row = (sizes[0][0] | 1) + sum(N | 1 for _, N in sizes[:-1]) + ((sizes[-1][1] | 1) if train or output_kept else 0)
+    return (per_row + ((int(widest) | 1) if train else 0)) * int(rows)
+
+
+def _mlp_net_bytes(params, act):
+    """12 P and, when the `act` activation cells of a batch do not fit AE_LDS_FLOATS, the net's slice of the scratch buffer."""
+    return 12 * params + (4 * act if act > AE_LDS_FLOATS else 0)
+
+
 def ae_param_count(d_s, hidden):
     """P: the parameters of one net, sum_l (K_l + 1) N_l."""
-    return sum((K + 1) * N for K, N in ae_layer_sizes(d_s, hidden))
+    return _mlp_param_count(ae_layer_sizes(d_s, hidden), True)
 
 
 def ae_act_floats(d_s, hidden, rows, train):
     """The float32 cells of the activations of `rows` rows (pitches are widths | 1): z and the hidden layers and, when
-    training, the output error and one passed-down error of the widest hidden layer (csrc/outlier_ae.hip)."""
-    per_row = (int(d_s) | 1) * (2 if train else 1) + ((max(hidden) | 1) if train else 0)
-    per_row += sum(N | 1 for _, N in ae_layer_sizes(d_s, hidden)[:-1])
-    return per_row * int(rows)
+    training, the output error and one passed-down error of the widest hidden layer (csrc/outlier_mlp.hpp)."""
+    return _mlp_act_floats(ae_layer_sizes(d_s, hidden), max(hidden), rows, train, False)
 
 
 def ae_net_bytes(d_s, hidden, batch, max_dims=None):
     """The bytes one net needs while it trains: theta, m and v (12 P) and, when the activations of a batch of the widest
     subspace (max_dims, default d_s) do not fit AE_LDS_FLOATS, its slice of the scratch buffer."""
-    act = ae_act_floats(d_s if max_dims is None else max_dims, hidden, batch, True)
-    return 12 * ae_param_count(d_s, hidden) + (4 * act if act > AE_LDS_FLOATS else 0)
+    return _mlp_net_bytes(ae_param_count(d_s, hidden), ae_act_floats(d_s if max_dims is None else max_dims, hidden, batch, True))
 
 
 def ae_chunks(net_bytes, workspace_bytes, owner="SubspaceAutoEncoder"):
@@ -4512,7 +4527,209 @@ def ae_bias_corrections(beta1, beta2, steps):
     return np.stack([1.0 - np.float64(beta1) ** t, 1.0 - np.float64(beta2) ** t], axis=1)
 
 
-class SubspaceAutoEncoder(_SubspaceScorer):
+class _MlpScorer(_SubspaceScorer):
+    """One small MLP per subspace, trained on the device by Adam on mini-batches of the standardised rows, the shared part of
+    SubspaceAutoEncoder and SubspaceDeepSVDD (whose docstrings are the definitions): the arguments, the scaling, the chunks of
+    nets that each train to the end, the cut of the steps into launches, the scoring forward over row tiles and the weights.
+    A subclass sets the traits below; what it adds to a chunk, a train launch or a scoring launch goes through _begin_chunk and
+    _target.  All of it runs in libvgan_hip.so (csrc/outlier_mlp.hpp)."""
+
+    _layer_sizes = None  # staticmethod (d_s, hidden) -> [(K_l, N_l)]
+    _bias = None  # a bias in every layer: weights_ holds (W_l, b_l) pairs, else W_l alone
+    _output_kept = None  # the scoring forward keeps the last layer's output among the activations
+    _entries = None  # the names of ops' init, train and scores
+    _raw = None  # ops' scores takes the buffer of the raw output under this keyword
+    _host_weights = None
+
+    def __init__(self, subspaces, proba, hidden, activation, epochs, batch_size, lr, beta1, beta2, eps, weight_decay, seed, workspace_bytes,
+                 normalize, combination, contamination):
+        self.hidden = check_ae_hidden(hidden)
+        self.activation = check_activation(activation)
+        (self.epochs, self.batch_size, self.lr, self.beta1, self.beta2, self.eps,
+         self.weight_decay) = check_ae_params(epochs, batch_size, lr, beta1, beta2, eps, weight_decay)
+        self.seed = check_seed(seed)
+        # no distance engine here: "exact" for every subspace keeps the processing order the given order
+        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
+        del self.engine
+        self._max_dims = int(self.plan.dims.max())
+        if self._max_dims > AE_MAX_DIMS:
+            raise ValueError(f"a subspace has {self._max_dims} features, {type(self).__name__} takes at most {AE_MAX_DIMS}")
+        self._net = (self.hidden, AE_ACTIVATIONS[self.activation])
+        self._params = np.array([_mlp_param_count(self._layer_sizes(d_s, self.hidden), self._bias) for d_s in self.plan.dims], dtype=np.int64)
+
+    def _act_floats(self, rows, train):
+        """The activation cells of `rows` rows of the widest subspace: what a launch reserves per workgroup."""
+        return _mlp_act_floats(self._layer_sizes(self._max_dims, self.hidden), max(self.hidden), rows, train, self._output_kept)
+
+    def _check_fit_rows(self, n):
+        if not 2 <= n <= AE_MAX_ROWS:
+            raise ValueError(f"{type(self).__name__} fit needs between 2 and {AE_MAX_ROWS} rows, got {n}")
+
+    def _attach(self):
+        if self.ops is not None:
+            return
+        super()._attach()
+        fan_in = np.array([[K for K, _ in self._layer_sizes(d_s, self.hidden)] for d_s in self.plan.dims], dtype=np.float64)
+        self._init_scale = torch.as_tensor(1.0 / np.sqrt(fan_in), device="cuda")
+        self._w_off_host = np.concatenate([[0], np.cumsum(self._params)]).astype(np.int64)
+        self._w_off = torch.as_tensor(self._w_off_host[:-1].copy(), device="cuda")
+
+    def _column_moments(self, X):
+        """(mean, variance) float64 [d] on the host: vgan_maha_moments over the d one-feature subspaces, the two-pass slab sums
+        whose bits depend on n alone."""
+        n, d = X.shape
+        dev = X.device
+        ones = np.ones(d, dtype=np.int64)
+        table = (torch.arange(d, dtype=torch.int32, device=dev), torch.arange(d + 1, dtype=torch.int32, device=dev),
+                 torch.arange(d + 1, dtype=torch.int64, device=dev))
+        cells, ranges = maha_ranges(ones, self.workspace_bytes)
+        mean, var = (torch.empty(d, dtype=torch.float64, device=dev) for _ in range(2))
+        hcount = torch.full((d,), n, dtype=torch.int32, device=dev)
+        slabs = -(-n // MAHA_SLAB_ROWS)
+        for first, count in ranges:
+            tiles = torch.as_tensor(maha_tiles(ones, first, count), device=dev)
+            ws = torch.empty(min(cells, slabs * MAHA_TILE * MAHA_TILE * count), dtype=torch.float64, device=dev)
+            self.ops.maha_moments(X, table, first, count, count, 1, tiles, None, hcount, mean, var, ws)
+        return mean.cpu().numpy(), var.cpu().numpy()
+
+    def _fit_scaling(self, X):
+        """location_, scale_ (sd 1 for a constant column), their device copies and the flags of the constant subspaces."""
+        dev = X.device
+        mean, var = self._column_moments(X)
+        self.location_ = mean
+        with np.errstate(invalid="ignore"):
+            self.scale_ = np.where(var > 0.0, np.sqrt(var), 1.0)
+        self._scaling = (torch.as_tensor(self.location_, device=dev), torch.as_tensor(self.scale_, device=dev))
+        off = self.plan.feat_off
+        self._constant = np.array([not (var[self.plan.feat[off[s]:off[s + 1]]] != 0.0).any() for s in range(self.plan.count)])
+        self._skip = torch.as_tensor(self._constant.astype(np.int32), device=dev)
+
+    def _forward_tiles(self, nq, widest, extra_bytes=0):
+        """(row tiles of one forward launch over `widest` blocks, its scratch buffer or None): all tiles of nq rows, or as many
+        as keep the scratch slices (and extra_bytes per (block, tile)) within workspace_bytes, at least one."""
+        act = self._act_floats(AE_ROW_TILE, False)
+        spill = act > AE_LDS_FLOATS
+        tiles = -(-nq // AE_ROW_TILE)
+        per_tile = (4 * act if spill else 0) + extra_bytes
+        if per_tile:
+            tiles = int(max(1, min(tiles, self.workspace_bytes // (per_tile * widest))))
+        scratch = torch.empty(widest * tiles * act, dtype=torch.float32, device="cuda") if spill else None
+        return tiles, scratch
+
+    def _begin_fit_state(self, dev):
+        """What a subclass allocates per fit beside the weights."""
+
+    def _begin_chunk(self, X, first, count, state, s_off):
+        """What a subclass takes from the initialised, untrained nets of a chunk."""
+
+    def _target(self, first, count):
+        """The arguments a subclass's train and scores entries take for the blocks first .. first + count - 1, as a tuple."""
+        return ()
+
+    def _train(self, X, batch, chunks):
+        """Initialises every chunk of nets and trains it to the end; the weights go to _theta, the step losses to the returned
+        [S, steps] matrix."""
+        n, dev = X.shape[0], X.device
+        S, steps = self.plan.count, self.epochs * (n // batch)
+        init, train, _ = (getattr(self.ops, name) for name in self._entries)
+        corr = torch.as_tensor(ae_bias_corrections(self.beta1, self.beta2, steps), device=dev)
+        loss = torch.zeros(S, max(steps, 1), dtype=torch.float32, device=dev)
+        adam = (self.lr, self.beta1, self.beta2, self.eps, self.weight_decay)
+        act = self._act_floats(batch, True)
+        for first, count in chunks:
+            sizes = self._params[first:first + count]
+            off = np.concatenate([[0], np.cumsum(3 * sizes)]).astype(np.int64)
+            state = torch.empty(int(off[-1]), dtype=torch.float32, device=dev)
+            s_off = torch.as_tensor(off[:-1].copy(), device=dev)
+            init(self._table[1], self._net, first, count, self._init_scale, self.seed, state, s_off, int(off[-1]))
+            self._begin_chunk(X, first, count, state, s_off)
+            scratch = torch.empty(count * act, dtype=torch.float32, device=dev) if act > AE_LDS_FLOATS else None
+            per_launch = ae_launch_steps(int(sizes.max()), batch)
+            for g0 in range(0, steps, per_launch):
+                train(X, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, batch, self.seed, g0,
+                      corr[g0:g0 + per_launch], adam, *self._target(first, count), state, s_off, loss[first:first + count], scratch)
+            for z in range(count):
+                at = int(self._w_off_host[first + z])
+                self._theta[at:at + int(sizes[z])].copy_(state[int(off[z]):int(off[z]) + int(sizes[z])])
+            del state, scratch
+        return loss[:, :steps]
+
+    def _distances(self, X, only=None):
+        """float32 [S, nq] on the device: the scores of the rows of X under every net; only = s: the raw output of net s
+        [nq, its output width] instead."""
+        nq, dev = X.shape[0], X.device
+        scores = getattr(self.ops, self._entries[2])
+        ranges = list(_launch_ranges(self.plan.count, _AE_MAX_RANGE)) if only is None else [(only, 1)]
+        tiles, scratch = self._forward_tiles(nq, max(count for _, count in ranges))
+        rows = tiles * AE_ROW_TILE
+        if only is None:
+            out = torch.empty(self.plan.count, nq, dtype=torch.float32, device=dev)
+        else:
+            out = torch.empty(nq, self._layer_sizes(int(self.plan.dims[only]), self.hidden)[-1][1], dtype=torch.float32, device=dev)
+        for first, count in ranges:
+            for r0 in range(0, nq, rows):
+                where = {"score": out[first:first + count, r0:]} if only is None else {self._raw: out[r0:r0 + rows]}
+                scores(X[r0:r0 + rows], self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, self._theta,
+                       self._w_off[first:first + count], *(self._target(first, count) if only is None else ()), scratch=scratch, **where)
+        return out
+
+    def _score(self, X, fitting):
+        per = self._distances(X)
+        return self._combine(per, fitting), per
+
+    def _output(self, X, s):
+        """float32 [n, width] on the host: the raw output of the net of subspace s on the rows of X."""
+        self._require_fit()
+        s = int(s)
+        if not 0 <= s < self.plan.count:
+            raise ValueError(f"no subspace {s}: {self.plan.count} subspaces")
+        return self._distances(_device_matrix(X, self.plan.d), only=s).cpu().numpy()
+
+    @property
+    def weights_(self):
+        """List of S lists with one entry per layer: (W_l float32 [N_l, K_l], b_l float32 [N_l]) with a bias, else W_l."""
+        self._require_fit()
+        if self._host_weights is None:
+            flat, out = self._theta.cpu().numpy(), []
+            for s, d_s in enumerate(self.plan.dims):
+                at, layers = int(self._w_off_host[s]), []
+                for K, N in self._layer_sizes(d_s, self.hidden):
+                    W = flat[at:at + K * N].reshape(K, N).T.copy()
+                    layers.append((W, flat[at + K * N:at + (K + 1) * N].copy()) if self._bias else W)
+                    at += (K + int(self._bias)) * N
+                out.append(layers)
+            self._host_weights = out
+        return self._host_weights
+
+    def _publish_fit_state(self):
+        """What a subclass publishes after the training beside the losses."""
+
+    def fit(self, X, y=None):
+        """Takes the column means and deviations of X, then chunk of subspaces by chunk initialises the nets (Deep SVDD: and
+        takes their centres) and runs all epochs (steps-per-launch by ae_launch_steps), and scores X through the trained
+        nets: decision_scores_ (float64 [n]), per_subspace_scores_, location_, scale_, loss_history_, n_steps_, what the
+        subclass publishes (center_, n_clamped_) and, on first use, weights_; with normalize also score_center_ / score_scale_."""
+        n = _matrix_shape(X, self.plan.d)[0]
+        self._check_fit_rows(n)
+        batch = min(self.batch_size, n)
+        act = self._act_floats(batch, True)
+        chunks = ae_chunks([_mlp_net_bytes(int(P), act) for P in self._params], self.workspace_bytes,
+                           type(self).__name__)  # raises before the device is touched
+        X = self._begin_fit(X)
+        self._fitted, self._host_weights = False, None
+        self._fit_scaling(X)
+        self._theta = torch.empty(int(self._w_off_host[-1]), dtype=torch.float32, device=X.device)
+        self._begin_fit_state(X.device)
+        steps = n // batch
+        self.n_steps_ = self.epochs * steps
+        loss = self._train(X, batch, chunks).cpu().numpy().astype(np.float64).reshape(self.plan.count, self.epochs, steps)
+        self.loss_history_ = np.cumsum(loss, axis=2)[:, :, -1] / steps  # cumsum adds in step order
+        self._publish_fit_state()
+        scores, per = self._score(X, fitting=True)
+        return self._publish(scores, per)
+
+
+class SubspaceAutoEncoder(_MlpScorer):
     """Autoencoder per subspace (pyod's ``AutoEncoder``), combined like the other detectors of this module: a small MLP is
     trained to reconstruct the standardised rows of the subspace through a bottleneck, and a row is scored by the Euclidean
     norm of its reconstruction error.  It is the one detector here that LEARNS a representation: rows that leave a curved
@@ -4581,171 +4798,22 @@ class SubspaceAutoEncoder(_SubspaceScorer):
     standardised rows: for inspection and the tests.  normalize, combination, contamination, ``threshold_``, ``labels_``,
     ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.  pyod is not pinned here: this definition and
     its numpy restatement in tests/test_outlier_ae_cpu.py are what binds.  All of it runs in libvgan_hip.so
-    (csrc/outlier_ae.hip; the column moments in csrc/outlier_maha.hip)."""
+    (csrc/outlier_ae.hip on the MLP core of csrc/outlier_mlp.hpp, which Deep SVDD shares; the column moments in
+    csrc/outlier_maha.hip)."""
 
-    _host_weights = None
+    _layer_sizes = staticmethod(ae_layer_sizes)
+    _bias, _output_kept = True, False
+    _entries, _raw = ("ae_init", "ae_train", "ae_scores"), "recon"
 
     def __init__(self, subspaces, proba, hidden=(64, 32), activation="relu", epochs=100, batch_size=32, lr=1e-3, beta1=0.9, beta2=0.999,
                  eps=1e-8, weight_decay=1e-5, seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None, combination="sum",
                  contamination=0.1):
-        self.hidden = check_ae_hidden(hidden)
-        self.activation = check_activation(activation)
-        (self.epochs, self.batch_size, self.lr, self.beta1, self.beta2, self.eps,
-         self.weight_decay) = check_ae_params(epochs, batch_size, lr, beta1, beta2, eps, weight_decay)
-        self.seed = check_seed(seed)
-        # no distance engine here: "exact" for every subspace keeps the processing order the given order
-        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
-        del self.engine
-        self._max_dims = int(self.plan.dims.max())
-        if self._max_dims > AE_MAX_DIMS:
-            raise ValueError(f"a subspace has {self._max_dims} features, SubspaceAutoEncoder takes at most {AE_MAX_DIMS}")
-        self._net = (self.hidden, AE_ACTIVATIONS[self.activation])
-        self._params = np.array([ae_param_count(d_s, self.hidden) for d_s in self.plan.dims], dtype=np.int64)
-
-    def _check_fit_rows(self, n):
-        if not 2 <= n <= AE_MAX_ROWS:
-            raise ValueError(f"SubspaceAutoEncoder fit needs between 2 and {AE_MAX_ROWS} rows, got {n}")
-
-    def _attach(self):
-        if self.ops is not None:
-            return
-        super()._attach()
-        fan_in = np.array([[K for K, _ in ae_layer_sizes(d_s, self.hidden)] for d_s in self.plan.dims], dtype=np.float64)
-        self._init_scale = torch.as_tensor(1.0 / np.sqrt(fan_in), device="cuda")
-        self._w_off_host = np.concatenate([[0], np.cumsum(self._params)]).astype(np.int64)
-        self._w_off = torch.as_tensor(self._w_off_host[:-1].copy(), device="cuda")
-
-    def _column_moments(self, X):
-        """(mean, variance) float64 [d] on the host: vgan_maha_moments over the d one-feature subspaces, the two-pass slab sums
-        whose bits depend on n alone."""
-        n, d = X.shape
-        dev = X.device
-        ones = np.ones(d, dtype=np.int64)
-        table = (torch.arange(d, dtype=torch.int32, device=dev), torch.arange(d + 1, dtype=torch.int32, device=dev),
-                 torch.arange(d + 1, dtype=torch.int64, device=dev))
-        cells, ranges = maha_ranges(ones, self.workspace_bytes)
-        mean, var = (torch.empty(d, dtype=torch.float64, device=dev) for _ in range(2))
-        hcount = torch.full((d,), n, dtype=torch.int32, device=dev)
-        slabs = -(-n // MAHA_SLAB_ROWS)
-        for first, count in ranges:
-            tiles = torch.as_tensor(maha_tiles(ones, first, count), device=dev)
-            ws = torch.empty(min(cells, slabs * MAHA_TILE * MAHA_TILE * count), dtype=torch.float64, device=dev)
-            self.ops.maha_moments(X, table, first, count, count, 1, tiles, None, hcount, mean, var, ws)
-        return mean.cpu().numpy(), var.cpu().numpy()
-
-    def _fit_scaling(self, X):
-        """location_, scale_ (sd 1 for a constant column), their device copies and the flags of the constant subspaces."""
-        dev = X.device
-        mean, var = self._column_moments(X)
-        self.location_ = mean
-        with np.errstate(invalid="ignore"):
-            self.scale_ = np.where(var > 0.0, np.sqrt(var), 1.0)
-        self._scaling = (torch.as_tensor(self.location_, device=dev), torch.as_tensor(self.scale_, device=dev))
-        off = self.plan.feat_off
-        self._constant = np.array([not (var[self.plan.feat[off[s]:off[s + 1]]] != 0.0).any() for s in range(self.plan.count)])
-        self._skip = torch.as_tensor(self._constant.astype(np.int32), device=dev)
-
-    def _train(self, X, batch, chunks):
-        """Trains every chunk of nets to the end; the weights go to _theta, the step losses to the returned [S, steps] matrix."""
-        n, dev = X.shape[0], X.device
-        S, steps = self.plan.count, self.epochs * (n // batch)
-        corr = torch.as_tensor(ae_bias_corrections(self.beta1, self.beta2, steps), device=dev)
-        loss = torch.zeros(S, max(steps, 1), dtype=torch.float32, device=dev)
-        adam = (self.lr, self.beta1, self.beta2, self.eps, self.weight_decay)
-        act = ae_act_floats(self._max_dims, self.hidden, batch, True)
-        for first, count in chunks:
-            sizes = self._params[first:first + count]
-            off = np.concatenate([[0], np.cumsum(3 * sizes)]).astype(np.int64)
-            state = torch.empty(int(off[-1]), dtype=torch.float32, device=dev)
-            s_off = torch.as_tensor(off[:-1].copy(), device=dev)
-            self.ops.ae_init(self._table[1], self._net, first, count, self._init_scale, self.seed, state, s_off, int(off[-1]))
-            scratch = torch.empty(count * act, dtype=torch.float32, device=dev) if act > AE_LDS_FLOATS else None
-            per_launch = ae_launch_steps(int(sizes.max()), batch)
-            for g0 in range(0, steps, per_launch):
-                self.ops.ae_train(X, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, batch, self.seed,
-                                  g0, corr[g0:g0 + per_launch], adam, state, s_off, loss[first:first + count], scratch)
-            for z in range(count):
-                at = int(self._w_off_host[first + z])
-                self._theta[at:at + int(sizes[z])].copy_(state[int(off[z]):int(off[z]) + int(sizes[z])])
-            del state, scratch
-        return loss[:, :steps]
-
-    def _distances(self, X, only=None):
-        """float32 [S, nq] on the device: the reconstruction distances of the rows of X; only = s: (the raw output of net s
-        [nq, d_s]) instead."""
-        nq, dev = X.shape[0], X.device
-        act = ae_act_floats(self._max_dims, self.hidden, AE_ROW_TILE, False)
-        spill = act > AE_LDS_FLOATS
-        ranges = list(_launch_ranges(self.plan.count, _AE_MAX_RANGE)) if only is None else [(only, 1)]
-        widest = max(count for _, count in ranges)
-        tiles = -(-nq // AE_ROW_TILE)
-        if spill:  # the scratch slices of a launch, one per (block, row tile), within workspace_bytes; at least one row tile
-            tiles = int(max(1, min(tiles, self.workspace_bytes // (4 * act * widest))))
-        rows = tiles * AE_ROW_TILE
-        scratch = torch.empty(widest * tiles * act, dtype=torch.float32, device=dev) if spill else None
-        if only is None:
-            out = torch.empty(self.plan.count, nq, dtype=torch.float32, device=dev)
-        else:
-            out = torch.empty(nq, int(self.plan.dims[only]), dtype=torch.float32, device=dev)
-        for first, count in ranges:
-            for r0 in range(0, nq, rows):
-                Xc = X[r0:r0 + rows]
-                if only is None:
-                    self.ops.ae_scores(Xc, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, self._theta,
-                                       self._w_off[first:first + count], score=out[first:first + count, r0:], scratch=scratch)
-                else:
-                    self.ops.ae_scores(Xc, self._table, self._scaling, self._skip, self._net, first, 1, self._max_dims, self._theta,
-                                       self._w_off[first:first + 1], recon=out[r0:r0 + rows], scratch=scratch)
-        return out
-
-    def _score(self, X, fitting):
-        per = self._distances(X)
-        return self._combine(per, fitting), per
+        super().__init__(subspaces, proba, hidden, activation, epochs, batch_size, lr, beta1, beta2, eps, weight_decay, seed, workspace_bytes,
+                         normalize, combination, contamination)
 
     def reconstruct(self, X, s):
         """float32 [n, d_s]: the output of the net of subspace s on the rows of X, standardised by the fitted location_ and scale_."""
-        self._require_fit()
-        s = int(s)
-        if not 0 <= s < self.plan.count:
-            raise ValueError(f"no subspace {s}: {self.plan.count} subspaces")
-        return self._distances(_device_matrix(X, self.plan.d), only=s).cpu().numpy()
-
-    @property
-    def weights_(self):
-        """List of S lists of (W_l float32 [N_l, K_l], b_l float32 [N_l]), one pair per layer."""
-        self._require_fit()
-        if self._host_weights is None:
-            flat, out = self._theta.cpu().numpy(), []
-            for s, d_s in enumerate(self.plan.dims):
-                at, layers = int(self._w_off_host[s]), []
-                for K, N in ae_layer_sizes(d_s, self.hidden):
-                    layers.append((flat[at:at + K * N].reshape(K, N).T.copy(), flat[at + K * N:at + (K + 1) * N].copy()))
-                    at += (K + 1) * N
-                out.append(layers)
-            self._host_weights = out
-        return self._host_weights
-
-    def fit(self, X, y=None):
-        """Takes the column means and deviations of X, then chunk of subspaces by chunk initialises the nets and runs all epochs
-        (steps-per-launch by ae_launch_steps), and scores X through the trained nets: decision_scores_ (float64 [n]),
-        per_subspace_scores_, location_, scale_, loss_history_, n_steps_ and, on first use, weights_; with normalize also
-        score_center_ / score_scale_."""
-        n = _matrix_shape(X, self.plan.d)[0]
-        self._check_fit_rows(n)
-        batch = min(self.batch_size, n)
-        chunks = ae_chunks([ae_net_bytes(d_s, self.hidden, batch, self._max_dims) for d_s in self.plan.dims],
-                           self.workspace_bytes)  # raises before the device is touched
-        X = self._begin_fit(X)
-        dev = X.device
-        self._fitted, self._host_weights = False, None
-        self._fit_scaling(X)
-        self._theta = torch.empty(int(self._w_off_host[-1]), dtype=torch.float32, device=dev)
-        steps = n // batch
-        self.n_steps_ = self.epochs * steps
-        loss = self._train(X, batch, chunks).cpu().numpy().astype(np.float64).reshape(self.plan.count, self.epochs, steps)
-        self.loss_history_ = np.cumsum(loss, axis=2)[:, :, -1] / steps  # cumsum adds in step order
-        scores, per = self._score(X, fitting=True)
-        return self._publish(scores, per)
+        return self._output(X, s)
 
 
 # ---- Deep SVDD: one small encoder per subspace, trained on the device onto one point, the squared distance as the score ----------
@@ -4784,24 +4852,22 @@ def svdd_layer_sizes(d_s, hidden):
 
 def svdd_param_count(d_s, hidden):
     """P: the parameters of one net, sum_l K_l N_l (no bias)."""
-    return sum(K * N for K, N in svdd_layer_sizes(d_s, hidden))
+    return _mlp_param_count(svdd_layer_sizes(d_s, hidden), False)
 
 
 def svdd_act_floats(d_s, hidden, rows, train):
     """The float32 cells of the activations of `rows` rows (pitches are widths | 1): z and every layer's output and, when
-    training, one passed-down error of the widest layer (csrc/outlier_svdd.hip)."""
-    per_row = (int(d_s) | 1) + sum(int(w) | 1 for w in hidden) + ((max(hidden) | 1) if train else 0)
-    return per_row * int(rows)
+    training, one passed-down error of the widest layer (csrc/outlier_mlp.hpp)."""
+    return _mlp_act_floats(svdd_layer_sizes(d_s, hidden), max(hidden), rows, train, True)
 
 
 def svdd_net_bytes(d_s, hidden, batch, max_dims=None):
     """The bytes one net needs while it trains: theta, m and v (12 P) and, when the activations of a batch of the widest
     subspace (max_dims, default d_s) do not fit AE_LDS_FLOATS, its slice of the scratch buffer."""
-    act = svdd_act_floats(d_s if max_dims is None else max_dims, hidden, batch, True)
-    return 12 * svdd_param_count(d_s, hidden) + (4 * act if act > AE_LDS_FLOATS else 0)
+    return _mlp_net_bytes(svdd_param_count(d_s, hidden), svdd_act_floats(d_s if max_dims is None else max_dims, hidden, batch, True))
 
 
-class SubspaceDeepSVDD(_SubspaceScorer):
+class SubspaceDeepSVDD(_MlpScorer):
     """Deep SVDD per subspace (Ruff et al., ICML 2018, the one-class objective; pyod's ``DeepSVDD``), combined like the other
     detectors of this module: a small encoder WITHOUT BIAS is trained to map the standardised rows of the subspace onto one
     point c, and a row is scored by the squared distance of its image from c.  Where SubspaceAutoEncoder reconstructs a row
@@ -4875,55 +4941,19 @@ class SubspaceDeepSVDD(_SubspaceScorer):
     output of net s on the standardised rows: for inspection and the tests.  normalize, combination, contamination,
     ``threshold_``, ``labels_``, ``predict``, ``predict_proba`` and return_per_subspace are the shared tail.  pyod is not pinned
     here: this definition and its numpy restatement in tests/test_outlier_svdd_cpu.py are what binds.  All of it runs in
-    libvgan_hip.so (csrc/outlier_svdd.hip on the layer routines of csrc/outlier_mlp.hpp, which the autoencoder shares; the
+    libvgan_hip.so (csrc/outlier_svdd.hip on the MLP core of csrc/outlier_mlp.hpp, which the autoencoder shares; the
     column moments in csrc/outlier_maha.hip)."""
 
-    _host_weights = None
-    _column_moments = SubspaceAutoEncoder._column_moments
-    _fit_scaling = SubspaceAutoEncoder._fit_scaling
+    _layer_sizes = staticmethod(svdd_layer_sizes)
+    _bias, _output_kept = False, True
+    _entries, _raw = ("svdd_init", "svdd_train", "svdd_scores"), "embed"
 
     def __init__(self, subspaces, proba, hidden=(64, 32), activation="relu", epochs=100, batch_size=32, lr=1e-3, beta1=0.9, beta2=0.999,
                  eps=1e-8, weight_decay=1e-5, center=None, center_eps=0.1, seed=0, workspace_bytes=DEFAULT_WORKSPACE_BYTES, normalize=None,
                  combination="sum", contamination=0.1):
-        self.hidden = check_svdd_hidden(hidden)
-        self.activation = check_activation(activation)
-        (self.epochs, self.batch_size, self.lr, self.beta1, self.beta2, self.eps,
-         self.weight_decay) = check_ae_params(epochs, batch_size, lr, beta1, beta2, eps, weight_decay)
-        self.seed = check_seed(seed)
-        # no distance engine here: "exact" for every subspace keeps the processing order the given order
-        self._configure(subspaces, proba, "exact", workspace_bytes, normalize, combination, contamination)
-        del self.engine
+        super().__init__(subspaces, proba, hidden, activation, epochs, batch_size, lr, beta1, beta2, eps, weight_decay, seed, workspace_bytes,
+                         normalize, combination, contamination)
         self.center, self.center_eps = check_svdd_center(center, center_eps, self.plan.count, self.hidden[-1])
-        self._max_dims = int(self.plan.dims.max())
-        if self._max_dims > AE_MAX_DIMS:
-            raise ValueError(f"a subspace has {self._max_dims} features, SubspaceDeepSVDD takes at most {AE_MAX_DIMS}")
-        self._net = (self.hidden, AE_ACTIVATIONS[self.activation])
-        self._params = np.array([svdd_param_count(d_s, self.hidden) for d_s in self.plan.dims], dtype=np.int64)
-
-    def _check_fit_rows(self, n):
-        if not 2 <= n <= AE_MAX_ROWS:
-            raise ValueError(f"SubspaceDeepSVDD fit needs between 2 and {AE_MAX_ROWS} rows, got {n}")
-
-    def _attach(self):
-        if self.ops is not None:
-            return
-        super()._attach()
-        fan_in = np.array([[K for K, _ in svdd_layer_sizes(d_s, self.hidden)] for d_s in self.plan.dims], dtype=np.float64)
-        self._init_scale = torch.as_tensor(1.0 / np.sqrt(fan_in), device="cuda")
-        self._w_off_host = np.concatenate([[0], np.cumsum(self._params)]).astype(np.int64)
-        self._w_off = torch.as_tensor(self._w_off_host[:-1].copy(), device="cuda")
-
-    def _forward_tiles(self, nq, widest, extra_bytes=0):
-        """(row tiles of one forward launch over `widest` blocks, its scratch buffer or None): all tiles of nq rows, or as many
-        as keep the scratch slices (and extra_bytes per (block, tile)) within workspace_bytes, at least one."""
-        act = svdd_act_floats(self._max_dims, self.hidden, AE_ROW_TILE, False)
-        spill = act > AE_LDS_FLOATS
-        tiles = -(-nq // AE_ROW_TILE)
-        per_tile = (4 * act if spill else 0) + extra_bytes
-        if per_tile:
-            tiles = int(max(1, min(tiles, self.workspace_bytes // (per_tile * widest))))
-        scratch = torch.empty(widest * tiles * act, dtype=torch.float32, device="cuda") if spill else None
-        return tiles, scratch
 
     def _centers(self, X, first, count, state, s_off):
         """The centres of the untrained nets of a chunk into _center[first : first + count] and _n_clamped: the tile sums of
@@ -4938,109 +4968,26 @@ class SubspaceDeepSVDD(_SubspaceScorer):
                                  tile_sums, run, n if r0 + rows >= n else 0, self.center_eps, self._center[first:first + count],
                                  self._n_clamped[first:first + count], scratch)
 
-    def _train(self, X, batch, chunks):
-        """Initialises every chunk of nets, takes its centres and trains it to the end; the weights go to _theta, the step
-        losses to the returned [S, steps] matrix."""
-        n, dev = X.shape[0], X.device
-        S, steps = self.plan.count, self.epochs * (n // batch)
-        corr = torch.as_tensor(ae_bias_corrections(self.beta1, self.beta2, steps), device=dev)
-        loss = torch.zeros(S, max(steps, 1), dtype=torch.float32, device=dev)
-        adam = (self.lr, self.beta1, self.beta2, self.eps, self.weight_decay)
-        act = svdd_act_floats(self._max_dims, self.hidden, batch, True)
-        for first, count in chunks:
-            sizes = self._params[first:first + count]
-            off = np.concatenate([[0], np.cumsum(3 * sizes)]).astype(np.int64)
-            state = torch.empty(int(off[-1]), dtype=torch.float32, device=dev)
-            s_off = torch.as_tensor(off[:-1].copy(), device=dev)
-            self.ops.svdd_init(self._table[1], self._net, first, count, self._init_scale, self.seed, state, s_off, int(off[-1]))
-            if self.center is None:
-                self._centers(X, first, count, state, s_off)
-            scratch = torch.empty(count * act, dtype=torch.float32, device=dev) if act > AE_LDS_FLOATS else None
-            per_launch = ae_launch_steps(int(sizes.max()), batch)
-            for g0 in range(0, steps, per_launch):
-                self.ops.svdd_train(X, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, batch, self.seed,
-                                    g0, corr[g0:g0 + per_launch], adam, self._center[first:first + count], state, s_off,
-                                    loss[first:first + count], scratch)
-            for z in range(count):
-                at = int(self._w_off_host[first + z])
-                self._theta[at:at + int(sizes[z])].copy_(state[int(off[z]):int(off[z]) + int(sizes[z])])
-            del state, scratch
-        return loss[:, :steps]
-
-    def _distances(self, X, only=None):
-        """float32 [S, nq] on the device: the squared distances of the images of the rows of X from the centres; only = s:
-        (the raw output of net s [nq, q]) instead."""
-        nq, dev, q = X.shape[0], X.device, self.hidden[-1]
-        ranges = list(_launch_ranges(self.plan.count, _AE_MAX_RANGE)) if only is None else [(only, 1)]
-        tiles, scratch = self._forward_tiles(nq, max(count for _, count in ranges))
-        rows = tiles * AE_ROW_TILE
-        out = torch.empty((self.plan.count, nq) if only is None else (nq, q), dtype=torch.float32, device=dev)
-        for first, count in ranges:
-            for r0 in range(0, nq, rows):
-                Xc = X[r0:r0 + rows]
-                if only is None:
-                    self.ops.svdd_scores(Xc, self._table, self._scaling, self._skip, self._net, first, count, self._max_dims, self._theta,
-                                         self._w_off[first:first + count], center=self._center[first:first + count],
-                                         score=out[first:first + count, r0:], scratch=scratch)
-                else:
-                    self.ops.svdd_scores(Xc, self._table, self._scaling, self._skip, self._net, first, 1, self._max_dims, self._theta,
-                                         self._w_off[first:first + 1], embed=out[r0:r0 + rows], scratch=scratch)
-        return out
-
-    def _score(self, X, fitting):
-        per = self._distances(X)
-        return self._combine(per, fitting), per
-
-    def embed(self, X, s):
-        """float32 [n, q]: the output of the net of subspace s on the rows of X, standardised by the fitted location_ and scale_."""
-        self._require_fit()
-        s = int(s)
-        if not 0 <= s < self.plan.count:
-            raise ValueError(f"no subspace {s}: {self.plan.count} subspaces")
-        return self._distances(_device_matrix(X, self.plan.d), only=s).cpu().numpy()
-
-    @property
-    def weights_(self):
-        """List of S lists of W_l float32 [N_l, K_l], one per layer."""
-        self._require_fit()
-        if self._host_weights is None:
-            flat, out = self._theta.cpu().numpy(), []
-            for s, d_s in enumerate(self.plan.dims):
-                at, layers = int(self._w_off_host[s]), []
-                for K, N in svdd_layer_sizes(d_s, self.hidden):
-                    layers.append(flat[at:at + K * N].reshape(K, N).T.copy())
-                    at += K * N
-                out.append(layers)
-            self._host_weights = out
-        return self._host_weights
-
-    def fit(self, X, y=None):
-        """Takes the column means and deviations of X, then chunk of subspaces by chunk initialises the nets, takes their
-        centres, runs all epochs (steps-per-launch by ae_launch_steps), and scores X through the trained nets:
-        decision_scores_ (float64 [n]), per_subspace_scores_, location_, scale_, center_, n_clamped_, loss_history_, n_steps_
-        and, on first use, weights_; with normalize also score_center_ / score_scale_."""
-        n = _matrix_shape(X, self.plan.d)[0]
-        self._check_fit_rows(n)
-        batch = min(self.batch_size, n)
-        chunks = ae_chunks([svdd_net_bytes(d_s, self.hidden, batch, self._max_dims) for d_s in self.plan.dims], self.workspace_bytes,
-                           "SubspaceDeepSVDD")  # raises before the device is touched
-        X = self._begin_fit(X)
-        dev = X.device
-        self._fitted, self._host_weights = False, None
-        self._fit_scaling(X)
+    def _begin_fit_state(self, dev):
         S, q = self.plan.count, self.hidden[-1]
-        self._theta = torch.empty(int(self._w_off_host[-1]), dtype=torch.float32, device=dev)
         given = np.zeros((S, q), np.float32) if self.center is None else np.where(self._constant[:, None], np.float32(0), self.center)
         self._center = torch.as_tensor(np.ascontiguousarray(given, dtype=np.float32), device=dev)
         self._n_clamped = torch.zeros(S, dtype=torch.int32, device=dev)
-        steps = n // batch
-        self.n_steps_ = self.epochs * steps
-        loss = self._train(X, batch, chunks).cpu().numpy().astype(np.float64).reshape(S, self.epochs, steps)
-        self.loss_history_ = np.cumsum(loss, axis=2)[:, :, -1] / steps  # cumsum adds in step order
+
+    def _begin_chunk(self, X, first, count, state, s_off):
+        if self.center is None:
+            self._centers(X, first, count, state, s_off)
+
+    def _target(self, first, count):
+        return (self._center[first:first + count],)
+
+    def _publish_fit_state(self):
         self.center_ = self._center.cpu().numpy()
         self.n_clamped_ = self._n_clamped.cpu().numpy().astype(np.int64)
-        scores, per = self._score(X, fitting=True)
-        return self._publish(scores, per)
+
+    def embed(self, X, s):
+        """float32 [n, q]: the output of the net of subspace s on the rows of X, standardised by the fitted location_ and scale_."""
+        return self._output(X, s)
 
 
 # ---- subspace outlier degree (SOD) over the subspaces ---------------------------------------------------------------------------
